@@ -1,6 +1,6 @@
 """Benchmark of the ESTDepth hot path on MI355X (contract: see the task statement / DESIGN.md §5 Measurement).
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload joint|estm|cfg5|cfg1|stream] [--no-cpu-baseline]
+    python bench.py [--gpus N --steps K --warmup W] [--workload joint|estm|cfg5|cfg1|stream] [--no-cpu-baseline] [--dump-outputs DIR]
 
 A "step" is one ``DepthNetHybrid.forward`` over one synthetic sequence resident in HBM:
   * joint (default, BASELINE.json configs[1]): seq_len=5, 480x640, D=64, ResNet-50, Joint-mode steady state
@@ -86,7 +86,60 @@ def parse():
     ap.add_argument("--sustained-bucket", type=int, default=200)
     ap.add_argument("--conv2d-arith", default=os.environ.get("ESTD_CONV2D_ARITH", "f32"), choices=["f32", "bf16x3"],
                     help="same choice for the 3x3 NHWC convolutions of the PSM extractor / 2D decoder (opt-in)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps: write what the last timed step returned (outputs, memory record, poses) as DIR/<name>.npy "
+                         "in float32 / float64, at most 64 MB in all; a larger array is replaced by a fixed, seeded sample of its elements")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def _named_arrays(obj, name):
+    """(name, tensor) of every tensor in a nested step result (tuples / lists / dicts with tuple or string keys), in a fixed order."""
+    import torch
+    if isinstance(obj, torch.Tensor):
+        return [(name, obj)]
+    if isinstance(obj, dict):
+        items = [("_".join(str(p) for p in k) if isinstance(k, tuple) else str(k), v) for k, v in obj.items()]
+    elif isinstance(obj, (list, tuple)):
+        items = [(str(i), v) for i, v in enumerate(obj)]
+    else:
+        return []
+    out = []
+    for k, v in sorted(items, key=lambda kv: kv[0]):
+        out += _named_arrays(v, name + "_" + k if name else k)
+    return out
+
+
+def dump_outputs(result, out_dir, limit=DUMP_LIMIT_BYTES):
+    """Writes the tensors of one step's result (outputs, costs, cam_poses) to ``out_dir/<name>.npy``, float64 kept, everything else as
+    float32.  The byte budget is shared out smallest array first: an array that fits its share is written whole, a larger one as the
+    elements at a fixed, seeded set of flat indices (sorted; the same for every run of the same shape).  Returns {name: description}."""
+    import numpy as np
+    import torch
+    names = ("outputs", "costs", "cam_poses")
+    arrays = _named_arrays(dict(zip(names, result)) if isinstance(result, (list, tuple)) else result, "")
+    os.makedirs(out_dir, exist_ok=True)
+    budget = limit - 256 * len(arrays)                  # (room for the .npy headers)
+    info = {}
+    left = len(arrays)
+    for name, t in sorted(arrays, key=lambda nt: (nt[1].numel(), nt[0])):
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        item = 8 if dt == torch.float64 else 4
+        share = max(0, budget // left // item)
+        flat = t.detach().reshape(-1)
+        if t.numel() <= share:
+            a = flat.to(dt).cpu().numpy().reshape(tuple(t.shape))
+            info[name] = {"shape": list(t.shape), "sampled": None}
+        else:
+            idx = np.sort(np.random.default_rng([0, t.numel()]).choice(t.numel(), size=share, replace=False))
+            a = flat[torch.from_numpy(idx).to(flat.device)].to(dt).cpu().numpy()
+            info[name] = {"shape": list(t.shape), "sampled": int(share)}
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        budget -= a.nbytes
+        left -= 1
+    return info
 
 
 def _free_port():
@@ -110,14 +163,12 @@ def self_launch_if_needed(args):
     if ndev < args.gpus:
         env["ESTD_OVERSUBSCRIBED"] = str(max(ndev, 1))
         env.setdefault("ESTD_DIST_BACKEND", "gloo")
-        # several processes on ONE GPU oversubscribe its hardware queues (4 per process by default + gloo's streams): the queue
-        # scheduler then time-slices them with millisecond quanta (measured: 5 ms per cfg1 step with 2 queues per process, 25-500 ms
-        # with 4-8).  Only this code-path mode; one process per GPU is not affected.
-        env.setdefault("GPU_MAX_HW_QUEUES", "2")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execve(sys.executable, cmd, env)
+    # a fresh child process, not an exec: this process has already initialised the HIP runtime (device_count above)
+    import subprocess
+    sys.exit(subprocess.call(cmd, env=env))
 
 
 def rccl_debug_summary(path):
@@ -448,16 +499,18 @@ def stream_bench(args, device, rank, world):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for f in range(f0, f0 + args.steps):
-        st.push(imgs[0, f], poses[0, f], intr[0])
+        last = st.push(imgs[0, f], poses[0, f], intr[0])
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    dump_dir = getattr(args, "dump_outputs", None)
+    dumped = dump_outputs(last, dump_dir) if dump_dir and rank == 0 else None
     return {"metric": "depth frames/sec (ESTM streaming, 480x640, D=64, cached matching features)",
             "value": round(args.steps * world / dt, 3), "unit": "depth frames/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 3), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": "ESTM stream: 1 new frame per step, window 3, memory 2, %s"
                                    % ("eager launches" if args.no_graph else "hipGraph replay (the new frame's PSM features inside stage A of the window forward)"),
-                       "untimed_priming_calls": f0, "captures": len(getattr(st.model, "_graphs", ()))}}
+                       "untimed_priming_calls": f0, "captures": len(getattr(st.model, "_graphs", ())), "dump_outputs": dumped}}
 
 
 def joint_stream_bench(steps, warmup, device, no_graph=False):
@@ -867,6 +920,7 @@ def main():
     ops.profile_mark(1)
     barrier()
     elapsed = time.perf_counter() - t0
+    dumped = dump_outputs(last, args.dump_outputs) if args.dump_outputs and rank == 0 else None       # before any later call reuses the buffers
     gathered = state["allgather"]
     gpu_outputs = {k: v.clone() for k, v in last[0].items()}        # outputs of the timed configuration (for the parity report)
     gpu_logits = {k: v.clone() for k, v in (getattr(model.CostRegNet, "last_logits", None) or {}).items()}
@@ -1099,6 +1153,7 @@ def main():
                        "graph_memory": None if (args.no_graph or state["fwd"] is model) else args.graph_memory,
                        "conv3d_arith": args.conv3d_arith, "conv2d_arith": args.conv2d_arith,
                        "conv3d_algo_32to32": kalgo,
+                       "dump_outputs": dumped,
                        "notes": state["notes"],
                        # the K-step figure against tens of seconds of the same step (timed / sustained: 1.0 = the headline IS a sustained rate)
                        "sustained_ms_per_step": sustained["ms_per_step"] if sustained else None,

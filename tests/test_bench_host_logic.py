@@ -75,3 +75,31 @@ def test_gpu_sampler_without_a_device_reports_an_error_not_a_number():
     time.sleep(0.2)
     out = s.stop().summary([0.0, 0.1, 0.2])
     assert ("error" in out) or (out["samples"] >= 1 and out["sclk_mhz"] is not None or out["power_w"] is not None)
+
+
+def test_dump_outputs_names_dtypes_budget_and_fixed_sample(tmp_path):
+    """bench.dump_outputs on a step result shaped like the model's (outputs keyed by tuples, a memory record, poses): one float32 /
+    float64 .npy per tensor, small arrays whole, the largest one as a seeded sample, all of it within the byte budget, and the same
+    files from a second call."""
+    import numpy as np
+    import bench
+    g = torch.Generator().manual_seed(0)
+    big = torch.rand(1, 4, 64, 64, generator=g)
+    result = ({("depth", 0, 0): torch.rand(1, 1, 8, 8, generator=g), ("prob", 0, 0): torch.rand(1, 1, 8, 8, generator=g).half()},
+              {"keys": [big], "values": [big.double()]},
+              [torch.eye(4, dtype=torch.float64)[None]])
+    limit = 40000
+    info = bench.dump_outputs(result, str(tmp_path / "a"), limit=limit)
+    assert set(info) == {"outputs_depth_0_0", "outputs_prob_0_0", "costs_keys_0", "costs_values_0", "cam_poses_0"}
+    files = {f[:-4]: np.load(os.path.join(tmp_path, "a", f)) for f in os.listdir(tmp_path / "a")}
+    assert set(files) == set(info)
+    assert sum(os.path.getsize(os.path.join(tmp_path, "a", f + ".npy")) for f in files) <= limit
+    assert files["outputs_prob_0_0"].dtype == np.float32 and files["costs_values_0"].dtype == np.float64
+    assert info["outputs_depth_0_0"]["sampled"] is None
+    np.testing.assert_array_equal(files["outputs_depth_0_0"], result[0][("depth", 0, 0)].numpy())
+    np.testing.assert_array_equal(files["cam_poses_0"], result[2][0].numpy())
+    n = info["costs_keys_0"]["sampled"]
+    assert n and files["costs_keys_0"].shape == (n,) and set(files["costs_keys_0"].tolist()) <= set(big.reshape(-1).tolist())
+    bench.dump_outputs(result, str(tmp_path / "b"), limit=limit)
+    for name, a in files.items():
+        np.testing.assert_array_equal(np.load(os.path.join(tmp_path, "b", name + ".npy")), a)

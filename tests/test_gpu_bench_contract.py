@@ -59,6 +59,28 @@ def test_bench_single_gpu_line():
         assert "alt_arith" not in d
 
 
+@pytest.mark.parametrize("workload", ["cfg1", "stream"])
+def test_bench_dump_outputs_are_repeatable(tmp_path, workload):
+    """--dump-outputs DIR: the last timed step's results as float32 / float64 .npy files within 64 MB, the depth maps among them, the
+    same files from a second run of the same command (identical seeded inputs; within 1e-4, the parity bar, since bench.py lets the
+    library pick its 2D convolution algorithms per process); --steps is the timed step count."""
+    import numpy as np
+    dumps = []
+    for run in ("a", "b"):
+        out = subprocess.run([sys.executable, "bench.py", "--workload", workload, "--steps", "2", "--warmup", "1", "--sustained-s", "0", "--no-alt",
+                              "--no-cpu-baseline", "--no-replay-profile", "--dump-outputs", str(tmp_path / run)],
+                             cwd=ROOT, capture_output=True, text=True, timeout=900)
+        d = _last_json(out.stdout)
+        assert d["steps"] == 2 and d["ms_per_step"] > 0 and set(d["config"]["dump_outputs"]) == {f[:-4] for f in os.listdir(tmp_path / run)}
+        dumps.append({f: np.load(os.path.join(tmp_path, run, f)) for f in sorted(os.listdir(tmp_path / run))})
+    a, b = dumps
+    assert any(f.startswith("outputs_depth_") for f in a) and sorted(a) == sorted(b)
+    assert sum(os.path.getsize(os.path.join(tmp_path, "a", f)) for f in a) <= 64 * 2 ** 20
+    for f in a:
+        assert a[f].dtype in (np.float32, np.float64) and np.isfinite(a[f]).all(), f
+        np.testing.assert_allclose(a[f], b[f], rtol=1e-4, atol=1e-4, err_msg=f)
+
+
 def test_bench_headline_workload_roofline_fields_are_hardware_fractions():
     """BASELINE configs[1] (the workload `value` is quoted on): `frac` is the EXECUTED fraction of the fp32 MFMA peak
     (<= 1 -- the algorithmic rate of a Winograd kernel is above the peak and lives in its own field), the dominant kernel's
