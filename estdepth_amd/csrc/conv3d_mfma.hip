@@ -162,6 +162,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_kernel(const estd_conv3d_des
     const int act0 = cbase < p.act_split ? p.act_a : p.act_b;   // both channels of a lane share the range (split is even)
     float sc2 = 0.f, sh2 = 0.f;
     if (XOUT) { sc2 = p.scale[32]; sh2 = p.shift[32]; }
+    const int act32 = 32 < p.act_split ? p.act_a : p.act_b;    // output channel 32 follows the split like every other channel
     float hw = 0.f, hb = 0.f;
     if (NT == 1 && p.head_w) { hw = p.head_w[i]; hb = p.head_b[0]; }
     // stereo heads (the only NT = 1 callers with a head): nothing but the 1x1x1 head leaves the kernel and the activation is one of
@@ -331,7 +332,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_kernel(const estd_conv3d_des
                 if (XOUT) {
                     // ax[m] = channel 32 of voxel (row m, column i), identical in the four lane groups
                     const int xx = tw0 + pi;
-                    if (g == 0 && y < H && xx < W) p.out_extra[plane + (size_t)y * W + xx] = act_apply(ax[m] * sc2 + sh2, p.act_b);
+                    if (g == 0 && y < H && xx < W) p.out_extra[plane + (size_t)y * W + xx] = act_apply(ax[m] * sc2 + sh2, act32);
                 }
             }
 
@@ -596,7 +597,7 @@ extern "C" int estd_conv3d_k3(const estd_conv3d_desc* dp, estd_stream_t s)
     if (d.in_stride < d.cin_main || (d.in_stride & 3)) return ESTD_ERR_ARG;
     if (!d.out_main && !d.out_head) return ESTD_ERR_ARG;
     if (d.out_main && (d.out_stride < 16 * (d.n_tiles > 2 ? 2 : d.n_tiles) || (d.out_stride & 1))) return ESTD_ERR_ARG;
-    if ((d.act_split & 1)) return ESTD_ERR_ARG;
+    if ((d.act_split & 1) && d.act_split < 32) return ESTD_ERR_ARG;      // a lane's channel pair shares one range (33: all 33 channels act_a)
     if (d.head_w && (d.n_tiles != 1 || !d.head_b || !d.out_head)) return ESTD_ERR_ARG;
     const bool extra = d.in_extra != nullptr;
     if (extra && !d.w_extra) return ESTD_ERR_ARG;

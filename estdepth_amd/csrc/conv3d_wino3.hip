@@ -736,7 +736,7 @@ extern "C" int estd_conv3d_k3_wino3(const estd_conv3d_desc* dp, estd_stream_t s)
     if (d.cin_main != 32 || d.n_tiles != 2 || d.out_head || d.out_extra || d.gate_r) return ESTD_ERR_UNSUPPORTED;
     const bool extra = d.in_extra != nullptr;
     if (extra != (d.w_extra != nullptr)) return ESTD_ERR_ARG;
-    if (d.in_stride < 32 || (d.in_stride & 3) || d.out_stride < 32 || (d.out_stride & 3) || (d.act_split & 1)) return ESTD_ERR_ARG;
+    if (d.in_stride < 32 || (d.in_stride & 3) || d.out_stride < 32 || (d.out_stride & 3) || ((d.act_split & 1) && d.act_split < 32)) return ESTD_ERR_ARG;
     const int tiles_w = (d.W + TW - 1) / TW, tiles_h = (d.H + TH - 1) / TH, dpairs = (d.D + 1) / 2;
     const long long total = (long long)d.N * dpairs * tiles_h * tiles_w;
     if (total > 0x7fffffffLL) return ESTD_ERR_ARG;

@@ -179,6 +179,8 @@ extern "C" int estd_conv3d_k3_xout(const estd_conv3d_desc* dp, estd_stream_t s)
     if (d.N <= 0 || d.D <= 0 || d.H <= 0 || d.W <= 0) return ESTD_ERR_ARG;
     if (!d.in_main || !d.in_extra || !d.w_xout || !d.scale || !d.shift || !d.out_extra) return ESTD_ERR_ARG;
     if (d.cin_main != 32 || d.in_stride < 32 || (d.in_stride & 3)) return ESTD_ERR_UNSUPPORTED;
+    const int act32 = 32 < d.act_split ? d.act_a : d.act_b;      // the epilogue knows a ReLU floor or nothing: no tanh
+    if (act32 != ESTD_ACT_NONE && act32 != ESTD_ACT_RELU) return ESTD_ERR_UNSUPPORTED;
     if ((long long)d.D * d.H * d.W * d.in_stride * 4 >= 0x7fffff00LL) return ESTD_ERR_UNSUPPORTED;      // 32-bit byte offsets inside one volume
     const int tiles_w = (d.W + TW - 1) / TW, tiles_h = (d.H + TH - 1) / TH, dsegs = (d.D + DSEG - 1) / DSEG;
     const long long grid = (long long)d.N * tiles_h * tiles_w * dsegs;

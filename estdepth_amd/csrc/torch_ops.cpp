@@ -229,6 +229,9 @@ void conv3d_k3(const Tensor& x, const OptTensor& x_extra, const OptTensor& w_mai
         check_status(estd_conv3d_k3_wino3(&d, cur_stream()), "estd_conv3d_k3_wino3");
     } else if (variant == 6) {          // output channel 32 of the 33 -> 33 instance alone (w_alt = packing.pack_conv3d_xout_taps)
         d.w_xout = fptr(*w_alt, "tap-major weights of output channel 32");
+        // the kernel reads scale[32] / shift[32] and writes N*D*H*W floats of out_extra
+        TORCH_CHECK(scale.numel() >= 33 && shift.numel() >= 33, "conv3d_k3: output channel 32 needs scale and shift with 33 entries");
+        TORCH_CHECK(d.out_extra && out_extra->numel() >= vox, "conv3d_k3: 33rd output channel smaller than N*D*H*W");
         check_status(estd_conv3d_k3_xout(&d, cur_stream()), "estd_conv3d_k3_xout");
     } else {
         TORCH_CHECK(variant == 0, "conv3d_k3: unknown variant ", variant);

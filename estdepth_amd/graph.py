@@ -122,7 +122,7 @@ class GraphedForward:
         return (tuple(imgs.shape), n_mem, None if matching_features is None else int(matching_features.shape[0]), mode, ops.CONV3D_ARITH, ops.CONV2D_ARITH,
                 ops.CONV3D_ALGO, getattr(ops, "CONV2D_ALGO", None), getattr(ops, "CONV2D_NT", None),      # a graph bakes the kernel choice in:
                 # ... the module-level kernel switches tests and tools flip at run time, and the grid sizes of the two stages
-                (ops.W3, ops.W3_EXTRA, ops.W2X, ops.W2_XOUT, ET.GATE_IN_CONV), self.reserve_cus,
+                (ops.W3, ops.W3_EXTRA, ops.W3_XOUT, ops.W2X, ops.W2_XOUT, ET.GATE_IN_CONV), self.reserve_cus,
                 lane,                                              # pipeline mode: the lane's own buffers and graph memory pool (0 otherwise)
                 self.model.camera_algebra,
                 placement,                                         # zero-copy mode: (addresses of the memory records, output ring slot)

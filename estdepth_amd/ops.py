@@ -403,7 +403,7 @@ class Conv3dPlan:
         wino2x = wino2x and not wino3
         # 33 -> 33 (dres2): 32 outputs on the three-axis kernel's 33 -> 32 instance, then output channel 32 alone
         split33 = wino2 and self.n_tiles == 3 and W3 and W3_EXTRA and W3_XOUT and has("w_wino3") and has("w_wino3_extra") and has("w_xout_taps") \
-            and in_extra is not None and out_extra is not None
+            and in_extra is not None and out_extra is not None and not tanh      # (the channel-32 pass has no tanh: the XOUT instance does)
         if split33:
             return self._run_split33(x, dims, in_stride, in_extra, out, out_stride, out_extra)
         variant, alt = (1, "w_split") if split else (3, "w_wino2_c16") if c16 else (3, "w_wino2_o16") if o16 else (5, "w_wino3") if wino3 \

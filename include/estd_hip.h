@@ -109,7 +109,7 @@ typedef struct estd_conv3d_desc {
                                * pack_xout / pack_conv3d_wino_xout / pack_conv3d_wino2_xout), else NULL */
     const float* scale;       /* [n_out] folded BN scale per output channel (n_out = 16, 32 or 33) */
     const float* shift;       /* [n_out] folded BN shift / conv bias */
-    int act_a, act_b, act_split;  /* channels < act_split use act_a, others act_b */
+    int act_a, act_b, act_split;  /* channels < act_split use act_a, others act_b (output channel 32 too); even, or >= 32 */
     /* main output (channels-last, out_stride floats per voxel, may alias a sub-range of a wider tensor) */
     float* out_main;          /* NULL when only the head output is wanted */
     int out_stride;
@@ -194,7 +194,8 @@ int estd_conv3d_k3_wino3(const estd_conv3d_desc* desc, estd_stream_t stream);
  * -> 1 channel) * scale[32] + shift[32]) -- the pass that lets the 32 main output channels of that layer run on estd_conv3d_k3_wino3's 33 -> 32
  * instance (csrc/conv3d_xout.hip: the 27 taps as the matrix core's rows, a shifted sum of scalars behind it).  Reads desc->w_xout in the packing of
  * packing.py::pack_conv3d_xout_taps (float32 [2][2][64][4] + [2][64]); cin_main = 32, in_extra, scale / shift with 33 entries and out_extra required;
- * out_main and every other output field are ignored.  ESTD_ERR_UNSUPPORTED for any other shape. */
+ * out_main and every other output field are ignored.  ESTD_ERR_UNSUPPORTED for any other shape and when channel 32's activation
+ * (act_a if act_split > 32, else act_b) is neither NONE nor RELU. */
 int estd_conv3d_k3_xout(const estd_conv3d_desc* desc, estd_stream_t stream);
 /* number of thread blocks estd_conv3d_k3 launches for a volume (size of stats_partials / 4 doubles) */
 int estd_conv3d_k3_grid(int N, int D, int H, int W);

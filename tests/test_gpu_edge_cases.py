@@ -119,6 +119,60 @@ def test_abi_rejects_bad_arguments():
     assert _native.lib().estd_conv3d_k3(d, None) == -1                          # null pointers
 
 
+def _xout_plan():
+    from estdepth_amd import ops
+    g = torch.Generator().manual_seed(3)
+    w = torch.randn(33, 33, 3, 3, 3, generator=g) * 0.05
+    return ops.Conv3dPlan(w, list(range(1, 33)), 0, list(range(33)), 3, torch.rand(33, generator=g) + 0.5, torch.randn(33, generator=g) * 0.1,
+                          act_a="relu", device=DEV)
+
+
+def test_abi_xout_pass_rejects_tanh_on_channel_32():
+    """estd_conv3d_k3_xout (output channel 32 of dres2 alone) has a ReLU floor or nothing in its epilogue: an activation of channel 32
+    it cannot apply (tanh, as act_b or as act_a with act_split > 32) is ESTD_ERR_UNSUPPORTED, not a silent identity."""
+    from estdepth_amd import ops, _native
+    plan = _xout_plan()
+    x = torch.zeros(1, 4, 16, 16, 32, device=DEV)
+    e = torch.zeros(1, 4, 16, 16, device=DEV)
+    ox = torch.zeros(1, 4, 16, 16, device=DEV)
+    d = _native.Conv3dDesc()
+    d.N, d.D, d.H, d.W = 1, 4, 16, 16
+    d.cin_main, d.in_stride, d.n_tiles = 32, 32, 3
+    d.in_main, d.in_extra, d.out_extra = x.data_ptr(), e.data_ptr(), ox.data_ptr()
+    d.w_xout, d.scale, d.shift = plan.w_xout_taps.data_ptr(), plan.scale.data_ptr(), plan.shift.data_ptr()
+    d.out_scale = 1.0
+    lib = _native.lib()
+    R, T, NONE = ops.ACT["relu"], ops.ACT["tanh"], ops.ACT["none"]
+    for act_a, act_b, split, want in [(R, R, 0, 0), (NONE, NONE, 0, 0), (T, R, 32, 0), (R, T, 0, -3), (T, T, 0, -3), (T, R, 34, -3),
+                                      (R, T, 33, 0)]:
+        d.act_a, d.act_b, d.act_split = act_a, act_b, split
+        assert lib.estd_conv3d_k3_xout(d, None) == want, (act_a, act_b, split)
+    torch.cuda.synchronize()
+
+
+def test_torch_binding_checks_the_xout_pass_sizes():
+    """torch ops variant 6 (the channel-32 pass): scale / shift with fewer than 33 entries or an out_extra smaller than N*D*H*W raise
+    instead of reading / writing past the end."""
+    from estdepth_amd import ops
+    plan = _xout_plan()
+    dims = (1, 4, 16, 16)
+    x = torch.zeros(*dims, 32, device=DEV)
+    e = torch.zeros(*dims, device=DEV)
+
+    def call(scale, shift, out_extra):
+        ops.T().conv3d_k3(x, e, None, plan.w_wino3_extra, None, plan.w_xout_taps, scale, shift, dims, 32, 32, 3, 1, 1, 0, None, 32, 32,
+                          None, None, 1.0, False, out_extra, None, None, None, None, 6, None, None, None, None)
+        torch.cuda.synchronize()
+
+    call(plan.scale, plan.shift, torch.zeros(*dims, device=DEV))
+    with pytest.raises(RuntimeError, match="33 entries"):
+        call(plan.scale[:32].clone(), plan.shift, torch.zeros(*dims, device=DEV))
+    with pytest.raises(RuntimeError, match="33 entries"):
+        call(plan.scale, plan.shift[:32].clone(), torch.zeros(*dims, device=DEV))
+    with pytest.raises(RuntimeError, match="smaller than"):
+        call(plan.scale, plan.shift, torch.zeros(1, 4, 16, 15, device=DEV))
+
+
 def test_full_size_cfg3_properties():
     """BASELINE configs[2] size (64x120x160): size-independent properties of the fused EST step.
     (a) one source with the target's own pose and K_j = K_t: softmax over one view == 1, so h = warp(V_j);

@@ -201,7 +201,7 @@ def test_new_weights_force_a_recapture(zero_copy):
 
 def test_kernel_switches_flipped_at_run_time_force_a_recapture():
     """A capture bakes the kernel choice in.  The module-level switches tests and tools flip at run time (ops.W3: three-axis vs two-axis 3D
-    convolution; epipolar_transformer.GATE_IN_CONV: reset gate folded into the output convolution vs its own pass) are part of the capture key
+    convolution; ops.W3_XOUT: dres2 in two launches vs the two-axis XOUT instance; epipolar_transformer.GATE_IN_CONV: reset gate folded into the output convolution vs its own pass) are part of the capture key
     (round 6, ADVICE): a live GraphedForward re-captures instead of silently replaying the old kernels -- an A/B through one wrapper compares
     two different graphs -- and each graph keeps replaying its own choice."""
     from estdepth_amd import ops
@@ -210,7 +210,7 @@ def test_kernel_switches_flipped_at_run_time_force_a_recapture():
     m = _model()
     imgs, poses, intr, smp = _inputs(5)
     sl = slice(1, 4)
-    old_w3, old_gate = ops.W3, ET.GATE_IN_CONV
+    old_w3, old_gate, old_xout = ops.W3, ET.GATE_IN_CONV, ops.W3_XOUT
     try:
         with torch.no_grad():
             _, c0, p0 = m(imgs[:, 0:3], poses[:, 0:3], intr, smp(slice(0, 3)), None, None, mode="val")
@@ -226,12 +226,17 @@ def test_kernel_switches_flipped_at_run_time_force_a_recapture():
             c, _, _ = gf(*args, mode="val")
             assert len(gf._graphs) == 3
             ops.W3, ET.GATE_IN_CONV = old_w3, old_gate
+            ops.W3_XOUT = not old_xout                       # dres2: three-axis 33 -> 32 + channel-32 pass vs the two-axis XOUT instance
+            e, _, _ = gf(*args, mode="val")
+            assert len(gf._graphs) == 4
+            ops.W3_XOUT = old_xout
             a2, _, _ = gf(*args, mode="val")
-            assert len(gf._graphs) == 3                      # back on the first capture
+            assert len(gf._graphs) == 4                      # back on the first capture
         for k in a:
             assert torch.equal(a[k], a2[k]), k
             assert (a[k] - b[k]).abs().max().item() < 2e-5 and (a[k] - c[k]).abs().max().item() < 2e-5, k
+            assert (a[k] - e[k]).abs().max().item() < 2e-5, k
         # different kernels round differently: the two-axis and the three-axis convolution do not agree bit for bit on every output
         assert any(not torch.equal(a[k], b[k]) for k in a)
     finally:
-        ops.W3, ET.GATE_IN_CONV = old_w3, old_gate
+        ops.W3, ET.GATE_IN_CONV, ops.W3_XOUT = old_w3, old_gate, old_xout

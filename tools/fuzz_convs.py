@@ -1,5 +1,5 @@
 """Randomised A/B of the Winograd kernels against the direct kernels (same operator, same descriptor): random ragged shapes,
-batch sizes, epilogue flags, instances; the 2D case runs the row-only AND the two-axis kernel (the default) and, one time in four, a map with
+batch sizes, epilogue flags, instances; tanh and split activations; the 33 -> 33 case on every route (the default two launches, the XOUT instance); the 2D case runs the row-only AND the two-axis kernel (the default) and, one time in four, a map with
 more work items than persistent workgroups (the multi-item path of the in-loop transform).  python tools/fuzz_convs.py [seconds] [seed]     (GPU; prints the first mismatch and exits 1)"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,12 +22,24 @@ def rnd(*shape, scale=1.0):
 
 
 def run3d(plan, algo, x, dims, **kw):
-    ops.CONV3D_ALGO, ops.W3 = ("wino2", True) if algo == "wino3" else (algo, False)
+    # "wino3": the default switches (33 -> 33: the three-axis 33 -> 32 launch + the channel-32 pass, or the two-axis XOUT instance for tanh);
+    # "wino2xout": the same with ops.W3_XOUT = False (33 -> 33 on the two-axis kernel's XOUT instance); "wino2": ops.W3 = False
+    ops.CONV3D_ALGO, ops.W3 = ("wino2", True) if algo in ("wino3", "wino2xout") else (algo, False)
     ops.W3_EXTRA = ops.W3
+    ops.W3_XOUT = algo == "wino3"
     out = kw.pop("out")
     plan.run(x, dims, out=out, **kw)
     torch.cuda.synchronize()
     return out
+
+
+def draw_acts(xout=False):
+    """Conv3dPlan activation arguments: one activation everywhere, or a split (tanh | ReLU at 16, unaligned ones, for 33 outputs at 32 / 33)"""
+    splits = [("tanh", "relu", 16), ("relu", "tanh", 8), ("tanh", "none", 20)] + ([("none", "relu", 32), ("tanh", "relu", 32), ("relu", "tanh", 33)] if xout else [])
+    if rng.integers(2):
+        return dict(act_a=str(rng.choice(["relu", "none", "tanh"])))
+    a, b, s = splits[int(rng.integers(len(splits)))]
+    return dict(act_a=a, act_b=b, act_split=s)
 
 
 def case_conv3d():
@@ -38,9 +50,9 @@ def case_conv3d():
     kw_common = {}
     if inst == "plain":
         w = rnd(32, 32, 3, 3, 3, scale=0.06).cpu()
-        act = str(rng.choice(["relu", "none", "tanh"]))
+        act = draw_acts()
         plan = ops.Conv3dPlan(w, list(range(32)), None, list(range(32)), 2, torch.rand(32, generator=g) + 0.5, torch.randn(32, generator=g) * 0.1,
-                              act_a=act, device=DEV)
+                              device=DEV, **act)
         mode = rng.choice(["none", "res", "res2", "acc", "stats"])
         if mode == "res":
             kw_common = dict(residual=rnd(N, D, H, W, 32))
@@ -70,22 +82,24 @@ def case_conv3d():
     e = rnd(N, D, H, W)
     if inst == "extra":
         w = rnd(32, 33, 3, 3, 3, scale=0.06).cpu()
+        act = draw_acts()
         plan = ops.Conv3dPlan(w, list(range(32)), 32, list(range(32)), 2, torch.rand(32, generator=g) + 0.5, torch.randn(32, generator=g) * 0.1,
-                              act_a="tanh", act_b="relu", act_split=16, device=DEV)
+                              device=DEV, **act)
         a = run3d(plan, "direct", x, dims, in_extra=e, out=torch.empty_like(x))
         b2 = run3d(plan, "wino2", x, dims, in_extra=e, out=torch.empty_like(x))
         b = run3d(plan, "wino", x, dims, in_extra=e, out=torch.empty_like(x)) if AB else b2
         d2 = float((a - b2).abs().max())
         if not ((d2 == d2) and d2 < 4e-5 * max(1.0, float(a.abs().max()))):
-            return False, ("conv3d", "extra/wino2", dims, d2)
+            return False, ("conv3d", "extra/wino2", dims, act, d2)
         b3 = run3d(plan, "wino3", x, dims, in_extra=e, out=torch.empty_like(x))
         d3 = float((a - b3).abs().max())
         if not ((d3 == d3) and d3 < 4e-5 * max(1.0, float(a.abs().max()))):
-            return False, ("conv3d", "extra/wino3", dims, d3)
+            return False, ("conv3d", "extra/wino3", dims, act, d3)
     else:
         w = rnd(33, 33, 3, 3, 3, scale=0.06).cpu()
+        act = draw_acts(xout=True)
         plan = ops.Conv3dPlan(w, list(range(1, 33)), 0, list(range(33)), 3, torch.rand(33, generator=g) + 0.5, torch.randn(33, generator=g) * 0.1,
-                              act_a="relu", device=DEV)
+                              device=DEV, **act)
         ea, eb = torch.full((N, D, H, W), float("nan"), device=DEV), torch.full((N, D, H, W), float("nan"), device=DEV)
         a = run3d(plan, "direct", x, dims, in_extra=e, out=torch.empty_like(x), out_extra=ea)
         ec = torch.full((N, D, H, W), float("nan"), device=DEV)
@@ -95,11 +109,16 @@ def case_conv3d():
         else:
             b, eb = b2, ec
         a, b, b2 = torch.cat([a, ea[..., None]], -1), torch.cat([b, eb[..., None]], -1), torch.cat([b2, ec[..., None]], -1)
-        d2 = float((a - b2).abs().max())
-        if not ((d2 == d2) and d2 < 4e-5 * max(1.0, float(a.abs().max()))):
-            return False, ("conv3d", "xout/wino2", dims, d2)
+        for alg in ("wino2", "wino3", "wino2xout"):      # W3 = 0; the default route; the XOUT instance under the default W3 / W3_EXTRA
+            if alg != "wino2":
+                ex = torch.full((N, D, H, W), float("nan"), device=DEV)
+                b2 = run3d(plan, alg, x, dims, in_extra=e, out=torch.empty_like(x), out_extra=ex)
+                b2 = torch.cat([b2, ex[..., None]], -1)
+            d2 = float((a - b2).abs().max())
+            if not ((d2 == d2) and d2 < 4e-5 * max(1.0, float(a.abs().max()))):
+                return False, ("conv3d", "xout/" + alg, dims, act, d2)
     d = float((a - b).abs().max())
-    return (d == d) and d < 4e-5 * max(1.0, float(a.abs().max())), ("conv3d", inst, dims, d)
+    return (d == d) and d < 4e-5 * max(1.0, float(a.abs().max())), ("conv3d", inst, dims, act, d)
 
 
 def case_conv2d():
