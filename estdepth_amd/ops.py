@@ -704,6 +704,15 @@ def _need_f32_cuda(name, *ts):
             raise RuntimeError("%s: contiguous float32 ROCm tensors expected (no CPU path)" % name)
 
 
+def _need_vec(name, n, **vs):
+    """optional per-output-channel vectors (scale / shift): float32 ROCm tensors of n entries"""
+    for k, v in vs.items():
+        if v is not None:
+            _need_f32_cuda(name, v)
+            if v.numel() != n:
+                raise RuntimeError("%s: %s [%d] expected, got %d entries" % (name, k, n, v.numel()))
+
+
 def conv2d_k3_to16_nhwc(x, w_packed, scale, shift, upsample=False):
     """3x3 conv (cin 16|32 -> 16) + folded BN + ReLU on an NHWC map, optionally on its nearest-x2 upsampling (never materialised)."""
     if _use_torch():
@@ -725,8 +734,11 @@ def conv1x1_nhwc(x, w2, scale, shift, stride=1, relu=False, residual=None):
     if _use_torch():
         return T().conv1x1_nhwc(x, w2, scale, shift, int(stride), bool(relu), residual)
     _need_f32_cuda("conv1x1_nhwc", x, w2)
+    if x.dim() != 4 or w2.dim() != 2 or w2.shape[1] != x.shape[3]:
+        raise RuntimeError("conv1x1_nhwc: NHWC x [N,H,W,cin] and w [cout,cin] expected")
     n, h, w, c = x.shape
     cout = w2.shape[0]
+    _need_vec("conv1x1_nhwc", cout, scale=scale, shift=shift)
     ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
     out = torch.empty((n, ho, wo, cout), device=x.device, dtype=torch.float32)
     d = N.Conv1x1Desc()
@@ -754,6 +766,7 @@ def conv2d_taps_nhwc(x, w_taps, scale, shift, ksize, stride=1, pad=None, relu=Fa
     if w_taps.dim() != 3 or w_taps.shape[0] != ksize * ksize or w_taps.shape[2] != c:
         raise RuntimeError("conv2d_taps_nhwc: NHWC x [N,H,W,cin] and w [k*k,cout,cin] expected")
     cout = w_taps.shape[1]
+    _need_vec("conv2d_taps_nhwc", cout, scale=scale, shift=shift)
     ho, wo = (h + 2 * pad - ksize) // stride + 1, (w + 2 * pad - ksize) // stride + 1
     out = torch.empty((n, ho, wo, cout), device=x.device, dtype=torch.float32)
     d = N.Conv2dTapsDesc()
@@ -815,7 +828,13 @@ def conv2d_small_nhwc(x, w_packed, scale, shift, cout, ksize, stride, relu):
     if _use_torch():
         return T().conv2d_small_nhwc(x, w_packed, scale, shift, int(cout), int(ksize), int(stride), bool(relu))
     _need_f32_cuda("conv2d_small_nhwc", x, w_packed, scale, shift)
+    if x.dim() != 4:
+        raise RuntimeError("conv2d_small_nhwc: NHWC x expected")
     n, h, w, c = x.shape
+    if ksize not in (1, 3) or stride not in (1, 2) or cout <= 0 or cout % 16 or c % 16:
+        raise RuntimeError("conv2d_small_nhwc: ksize 1|3, stride 1|2, channel counts multiples of 16")
+    if w_packed.numel() != cout // 16 * ksize * ksize * (c // 16) * 256 or scale.numel() != cout or shift.numel() != cout:
+        raise RuntimeError("conv2d_small_nhwc: packed weights [cout/16][taps][cin/16][64][4] and scale/shift [cout] expected")
     pad = ksize // 2
     ho, wo = (h + 2 * pad - ksize) // stride + 1, (w + 2 * pad - ksize) // stride + 1
     out = torch.empty((n, ho, wo, cout), device=x.device, dtype=torch.float32)
