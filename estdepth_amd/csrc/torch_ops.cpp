@@ -397,6 +397,7 @@ void gru_blend(const Tensor& xh, const Tensor& ru, const Tensor& o_raw, const Te
     TORCH_CHECK(xh.numel() == ru.numel() && o_raw.numel() == n_vox * 16, "gru_blend: xh, ru [D,H,W,32]; o_raw [D,H,W,16]");
     TORCH_CHECK(stats_ru.numel() == 4 && stats_o.numel() == 4 && gamma_u.numel() == 16 && beta_u.numel() == 16 &&
                 gamma_o.numel() == 16 && beta_o.numel() == 16, "gru_blend: stats [4], affine [16]");
+    TORCH_CHECK(out_value.numel() >= (n_vox - 1) * out_stride + 16, "gru_blend: out_value must hold (n_vox - 1) * out_stride + 16 floats");
     check_status(estd_gru_blend(fptr(xh, "xh"), fptr(ru, "ru"), fptr(o_raw, "o_raw"), fptr(stats_ru, "stats_ru"), fptr(stats_o, "stats_o"),
                                 fptr(gamma_u, "gamma_u"), fptr(beta_u, "beta_u"), fptr(gamma_o, "gamma_o"), fptr(beta_o, "beta_o"),
                                 fptr_mut(out_value, "out_value", false), (int)out_stride, n_vox, cur_stream()), "estd_gru_blend");

@@ -117,6 +117,12 @@ def _p(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _need(ok, msg):
+    """the ctypes front end's argument checks (the torch binding's TORCH_CHECKs): raise before anything is launched"""
+    if not ok:
+        raise RuntimeError(msg)
+
+
 def set_reserved_cus(n):
     """Compute units the persistent convolution grids leave free for a concurrent collective (include/estd_hip.h)."""
     if _use_torch():
@@ -169,6 +175,8 @@ def cam_volume_mats(pose_j, pose_i, intr, out=None):
 def homo_warping_chw(src_chw, proj12, depth_values, D):
     if _use_torch():
         return T().homo_warping(src_chw, proj12, depth_values, D)
+    _need(src_chw.dim() == 3, "homo_warping: src_fea must be [C,H,W]")
+    _need(depth_values.numel() >= D and _chk(proj12, "proj12").numel() == 12, "homo_warping: depth_values / proj12 size")
     C, H, W = src_chw.shape
     out = torch.empty((C, D, H, W), device=src_chw.device, dtype=torch.float32)
     N.check(N.lib().estd_homo_warping(_p(_chk(src_chw, "src_fea")), _p(proj12), _p(_chk(depth_values, "depth_values")),
@@ -180,8 +188,10 @@ def homo_warping_px_chw(src_chw, proj12, depth_dhw):
     """per-pixel depth hypotheses [D,H,W] (homo_utils.py:462)."""
     if _use_torch():
         return T().homo_warping_px(src_chw, proj12, depth_dhw)
+    _need(src_chw.dim() == 3 and depth_dhw.dim() == 3, "homo_warping_px: src_fea [C,H,W], depth [D,H,W]")
     C, H, W = src_chw.shape
     D = depth_dhw.shape[0]
+    _need(tuple(depth_dhw.shape[1:]) == (H, W) and _chk(proj12, "proj12").numel() == 12, "homo_warping_px: depth / proj12 size")
     out = torch.empty((C, D, H, W), device=src_chw.device, dtype=torch.float32)
     N.check(N.lib().estd_homo_warping_px(_p(_chk(src_chw, "src_fea")), _p(proj12), _p(_chk(depth_dhw, "depth_values")),
                                          _p(out), C, D, H, W, _stream()), "estd_homo_warping_px")
@@ -192,8 +202,10 @@ def mix1x1(in_chw, w, bias):
     """[Cin,H,W] -> [H,W,Cout] channel mix."""
     if _use_torch():
         return T().mix1x1(in_chw, w, bias)
+    _need(in_chw.dim() == 3 and w.dim() == 2 and w.shape[1] == in_chw.shape[0], "mix1x1: in [Cin,H,W], w [Cout,Cin]")
     Cin, H, W = in_chw.shape
     Cout = w.shape[0]
+    _need(bias is None or _chk(bias, "mix bias").numel() == Cout, "mix1x1: bias [Cout]")
     out = torch.empty((H, W, Cout), device=in_chw.device, dtype=torch.float32)
     N.check(N.lib().estd_mix1x1_chw_to_hwc(_p(_chk(in_chw, "feature")), _p(_chk(w, "mix weight")),
                                            _p(bias) if bias is not None else None, _p(out), Cin, Cout, H * W, _stream()),
@@ -209,6 +221,10 @@ def homo_warp_costvol(src_mix, ref_mix, proj12, depth_values, D, out=None):
         if _use_torch():
             T().homo_warp_costvol(src_mix, ref_mix, proj12, depth_values, D, out)
             return out
+        _need(src_mix.dim() == 3 and src_mix.shape[2] == 32 and ref_mix.shape == src_mix.shape,
+              "homo_warp_costvol: src_mix / ref_mix must be [H,W,32] of one shape")
+        _need(depth_values.numel() >= D and D >= 1 and _chk(proj12, "proj12").numel() == 12, "homo_warp_costvol: depth_values / proj12 size")
+        _need(_chk(out, "out").numel() == D * H * W * 32, "homo_warp_costvol: out must be [D,H,W,32]")
         N.check(N.lib().estd_homo_warp_costvol(_p(_chk(src_mix, "src_mix")), _p(_chk(ref_mix, "ref_mix")), _p(proj12),
                                                _p(_chk(depth_values, "depth_values")), _p(out), D, H, W, _stream()),
                 "estd_homo_warp_costvol")
@@ -585,6 +601,8 @@ def conv3d_grid(Nn, D, H, W):
 def groupnorm_finalize(partials, n_blocks, count, eps=1e-5):
     if _use_torch():
         return T().groupnorm_finalize(partials, n_blocks, float(count), float(eps))
+    _need(_chk(partials, "partials", torch.float64).numel() >= n_blocks * 4,
+          "groupnorm_finalize: partials must be a contiguous float64 ROCm tensor with 4 doubles per block")
     out = torch.empty(4, device=partials.device, dtype=torch.float32)
     N.check(N.lib().estd_groupnorm_finalize(_p(partials), n_blocks, float(count), float(eps), _p(out), _stream()),
             "estd_groupnorm_finalize")
@@ -598,6 +616,7 @@ def softargmin_up(logits, depth_values, scale=4):
     with _Prof("softargmin", 4.0 * Nn * H * W * (D + 2 * scale * scale)):       # logits in, depth + prob maps out
         if _use_torch():
             return T().softargmin_up(logits, depth_values, scale)
+        _need(depth_values.numel() >= D, "softargmin_up: one depth value per plane expected")
         depth = torch.empty((Nn, 1, H * scale, W * scale), device=logits.device, dtype=torch.float32)
         prob = torch.empty_like(depth)
         N.check(N.lib().estd_softargmin_up(_p(_chk(logits, "logits")), _p(_chk(depth_values, "depth_values")), _p(depth), _p(prob),
@@ -609,7 +628,9 @@ def softargmin_up(logits, depth_values, scale=4):
 def warp_volume_cdhw(vol, mats30, depth_values, depth_min, depth_interval):
     if _use_torch():
         return T().warp_volume(vol, mats30, depth_values, float(depth_min), float(depth_interval))
+    _need(vol.dim() == 4 and _chk(mats30, "mats30").numel() == 30, "warp_volume: vol [C,D,H,W], mats30 [30]")
     C, D, H, W = vol.shape
+    _need(depth_values.numel() >= D, "warp_volume: one depth value per plane expected")
     out = torch.empty_like(vol)
     N.check(N.lib().estd_warp_volume(_p(_chk(vol, "feat_volume")), _p(mats30), _p(_chk(depth_values, "depth")),
                                      float(depth_min), float(depth_interval), _p(out), C, D, H, W, _stream()),
@@ -628,7 +649,10 @@ def warp_volume_ex_cdhw(vol, mats30, depth, depth_per_voxel, depth_min, depth_in
     if _use_torch():
         return T().warp_volume_ex(vol, mats30, depth, bool(depth_per_voxel), float(depth_min), float(depth_interval), use_disp,
                                   dmin_, dint_, bool(border), float(padding_value))
+    _need(vol.dim() == 4 and _chk(mats30, "mats30").numel() == 30, "warp_volume: vol [C,D,H,W], mats30 [30]")
     C, D, H, W = vol.shape
+    _need(depth.numel() >= (D * H * W if depth_per_voxel else D), "warp_volume: depth must hold one value per %s" %
+          ("voxel" if depth_per_voxel else "plane"))
     out = torch.empty_like(vol)
     o = N.WarpVolumeOpts(int(bool(depth_per_voxel)), int(use_disp), int(bool(border)), float(depth_min), float(depth_interval),
                          dmin_, dint_, float(padding_value))
@@ -644,6 +668,10 @@ def warp_attention(kv_target, kv_sources, mats, depth_values, depth_min, depth_i
     with _Prof("warp_attention", 4.0 * 16 * D * H * W * (2 + 2 * n)):          # K_t, h out, K_j and V_j of every source
         if _use_torch():
             return T().warp_attention(kv_target, list(kv_sources), mats, depth_values, float(depth_min), float(depth_interval))
+        _need(kv_target.dim() == 4 and kv_target.shape[3] == 32, "warp_attention: kv volumes must be [D,H,W,32]")
+        _need(all(k.shape == kv_target.shape for k in kv_sources), "warp_attention: a source has another shape than the target")
+        _need(_chk(mats, "mats").numel() == n * 30, "warp_attention: mats must be [n_src,30]")
+        _need(depth_values.numel() >= D, "warp_attention: one depth value per plane expected")
         arr = (ctypes.c_void_p * n)(*[_chk(k, "kv source").data_ptr() for k in kv_sources])
         xh = torch.empty((D, H, W, 32), device=kv_target.device, dtype=torch.float32)
         N.check(N.lib().estd_warp_attention(_p(_chk(kv_target, "kv target")), arr, _p(_chk(mats, "mats")), n,
@@ -668,6 +696,9 @@ def gru_reset_apply(xh, ru, stats4, gamma_r, beta_r):
     with _Prof("gru_elementwise", 4.0 * 16 * n_vox * 2):       # SURVEY §8d K11+K13 = 5 x 16 channels per voxel: r, h here
         if _use_torch():
             return T().gru_reset_apply(xh, ru, stats4, gamma_r, beta_r)
+        _need(_chk(xh, "xh").numel() == _chk(ru, "ru").numel() and xh.numel() % 32 == 0, "gru_reset_apply: xh and ru are [D,H,W,32] volumes")
+        _need(_chk(stats4, "stats").numel() == 4 and _chk(gamma_r, "gamma").numel() == 16 and _chk(beta_r, "beta").numel() == 16,
+              "gru_reset_apply: stats [4], affine [16]")
         xrh = torch.empty_like(xh)
         N.check(N.lib().estd_gru_reset_apply(_p(xh), _p(ru), _p(stats4), _p(gamma_r), _p(beta_r), _p(xrh), n_vox, _stream()),
                 "estd_gru_reset_apply")
@@ -679,6 +710,12 @@ def gru_blend(xh, ru, o_raw, stats_ru, stats_o, gamma_u, beta_u, gamma_o, beta_o
     with _Prof("gru_elementwise", 4.0 * 16 * n_vox * 3):       # ... u, o_raw, out here (h counted once, in the reset pass)
         if _use_torch():
             return T().gru_blend(xh, ru, o_raw, stats_ru, stats_o, gamma_u, beta_u, gamma_o, beta_o, out_value, out_stride)
+        _need(_chk(xh, "xh").numel() == _chk(ru, "ru").numel() and _chk(o_raw, "o_raw").numel() == n_vox * 16,
+              "gru_blend: xh, ru [D,H,W,32]; o_raw [D,H,W,16]")
+        _need(all(_chk(t, "gru stats").numel() == 4 for t in (stats_ru, stats_o)) and
+              all(_chk(t, "gru affine").numel() == 16 for t in (gamma_u, beta_u, gamma_o, beta_o)), "gru_blend: stats [4], affine [16]")
+        _need(out_value.is_cuda and out_value.dtype == torch.float32 and out_value.numel() >= (n_vox - 1) * out_stride + 16,
+              "gru_blend: out_value must hold (n_vox - 1) * out_stride + 16 floats")
         N.check(N.lib().estd_gru_blend(_p(xh), _p(ru), _p(o_raw), _p(stats_ru), _p(stats_o), _p(gamma_u), _p(beta_u),
                                        _p(gamma_o), _p(beta_o), _p(out_value), out_stride, n_vox, _stream()), "estd_gru_blend")
 
@@ -947,8 +984,10 @@ def cdhw_to_vol(src, dst, dst_stride, dst_off):
     """src [C,D,H,W] contiguous -> channels dst_off.. of the channels-last records of dst."""
     if _use_torch():
         return T().cdhw_to_vol(src, dst, dst_stride, dst_off)
+    _need(src.dim() >= 2, "cdhw_to_vol: src must be [C, ...]")
     C = src.shape[0]
     S = src.numel() // C
+    _need(dst.is_cuda and dst.dtype == torch.float32 and dst.numel() >= S * dst_stride, "cdhw_to_vol: destination too small")
     N.check(N.lib().estd_cdhw_to_vol(_p(_chk(src, "volume")), _p(dst), C, S, dst_stride, dst_off, _stream()), "estd_cdhw_to_vol")
 
 
@@ -956,6 +995,7 @@ def vol_to_cdhw(src, C, dims, src_stride, src_off):
     if _use_torch():
         return T().vol_to_cdhw(src, C, list(dims), src_stride, src_off)
     D, H, W = dims
+    _need(src.is_cuda and src.dtype == torch.float32 and src.numel() >= D * H * W * src_stride, "vol_to_cdhw: source too small")
     out = torch.empty((C, D, H, W), device=src.device, dtype=torch.float32)
     N.check(N.lib().estd_vol_to_cdhw(_p(src), _p(out), C, D * H * W, src_stride, src_off, _stream()), "estd_vol_to_cdhw")
     return out
