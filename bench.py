@@ -1,6 +1,13 @@
 """Benchmark of the ESTDepth hot path on MI355X (contract: see the task statement / DESIGN.md §5 Measurement).
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload joint|estm|cfg5|cfg1|stream] [--no-cpu-baseline] [--dump-outputs DIR]
+    python bench.py [--gpus N --steps K --warmup W] [--workload joint|estm|cfg5|cfg1|stream] [--dump-outputs DIR] [--full]
+
+A plain run does what its headline figure needs: set-up, the W warm-up steps, the K timed steps, the --dump-outputs files, one JSON
+line.  ``--full`` adds everything else the benchmark measures or checks, after the timed steps: the sustained loop, the per-kernel
+rooflines (an eager pass with HIP-event brackets + a rocprofv3-traced child run), the stand-alone HBM kernels, the bf16x3 second
+opinion (A/B builds), the other single-GPU workloads, the CPU baselines with the parity report, and at N > 1 the step times without
+the exchange and without the CU reserve.  --no-cpu-baseline, --no-alt, --no-replay-profile, --no-other-workloads and --sustained-s
+trim what --full adds.
 
 A "step" is one ``DepthNetHybrid.forward`` over one synthetic sequence resident in HBM:
   * joint (default, BASELINE.json configs[1]): seq_len=5, 480x640, D=64, ResNet-50, Joint-mode steady state
@@ -48,7 +55,10 @@ def parse():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="joint", choices=["joint", "estm", "cfg5", "cfg1", "stream"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything beyond the headline figure: sustained loop, rooflines, stand-alone HBM kernels, "
+                         "bf16x3 second opinion, other workloads, CPU baselines + parity, N > 1 step times without exchange / reserve")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baselines and the parity report")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="host threads of the cpu_baseline leg (0 = torch's default = the physical cores of the box; SMT siblings slow both "
                          "the OpenMP oracle and the oneDNN convolutions of the 2D networks down)")
@@ -67,20 +77,20 @@ def parse():
                     help="3D convolutions under f32 arithmetic: wino2 = depth and row axis of the plain 32->32 instance in Winograd F(2,3) "
                          "form (0.444 of the fp32 MFMA products, csrc/conv3d_wino2.hip: every 32/33-channel instance, 32->16 and the 16->16 heads; default), "
                          "wino = depth axis only (2/3 of the products, csrc/conv3d_wino.hip; ESTD_BUILD_AB=1 builds only), direct = 27-tap implicit GEMM (csrc/conv3d_mfma.hip)")
-    ap.add_argument("--no-alt", action="store_true", help="skip the second timed loop with the other convolution arithmetic")
+    ap.add_argument("--no-alt", action="store_true", help="(--full) skip the second timed loop with the other convolution arithmetic")
     ap.add_argument("--no-replay-profile", action="store_true",
-                    help="skip the rocprofv3 kernel trace of a short child run (per-kernel durations INSIDE the hipGraph replay)")
+                    help="(--full) skip the rocprofv3 kernel trace of a short child run (per-kernel durations INSIDE the hipGraph replay)")
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="skip the short timed loops of the other single-GPU workloads (ESTM window, cfg5, stream) reported beside the headline")
+                    help="(--full) skip the short timed loops of the other single-GPU workloads (ESTM window, cfg5, stream) reported beside the headline")
     ap.add_argument("--pipeline", default=os.environ.get("ESTD_PIPELINE", "off"), choices=["on", "off"],
                     help="hipGraph replay: on = stage A (2D networks) of step k + 1 beside the SECOND half of stage B of step k (GraphedForward(pipeline=True): "
                          "two lanes of captures, stage B cut into two graphs behind the key||value convolution; the only dependence between consecutive calls is "
                          "the memory record stage B hands on).  Bit-identical results (tests/test_gpu_pipeline.py) but NOT a robust gain: +0.2 .. +1.2 %% on the "
                          "Joint step in 40-step A/B pairs on four boxes, -2 .. -7 %% in the default 10-step command on a fifth, 200-step buckets between 15.7 and "
                          "16.3 ms where the serial replay holds 15.5 +- 0.05 (profiles/r6_pipeline_ab.txt): what the next stage A meets is left to the hardware "
-                         "queues.  Default off; a line with it on carries the serial replay of the same process (config.serial_replay)")
+                         "queues.  Default off; a --full line with it on carries the serial replay of the same process (config.serial_replay)")
     ap.add_argument("--sustained-s", type=float, default=float(os.environ.get("ESTD_SUSTAINED_S", "20")),
-                    help="after the K timed steps: the same step for about this many seconds in buckets of --sustained-bucket steps, shader clock and "
+                    help="(--full) after the K timed steps: the same step for about this many seconds in buckets of --sustained-bucket steps, shader clock and "
                          "board power sampled beside it by a host thread (config.sustained, config.sustained_ms_per_step, "
                          "config.sustained_over_timed); 0 = skip.  `value` stays the K-step figure of the contract")
     ap.add_argument("--sustained-bucket", type=int, default=200)
@@ -630,10 +640,11 @@ def replay_profile(args):
     env = dict(os.environ, ESTD_BENCH_CHILD="1", TMPDIR=tempfile.gettempdir())
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "ESTD_FORCE_DIST"):
         env.pop(k, None)
+    # a plain run (no --full) that prints its short child line right after the timed loop
     cmd = [rp, "--kernel-trace", "--output-format", "csv", "-d", out, "-o", "p", "--", sys.executable, os.path.abspath(__file__),
-           "--workload", args.workload, "--steps", str(steps), "--warmup", "2", "--no-cpu-baseline", "--no-alt",
+           "--workload", args.workload, "--steps", str(steps), "--warmup", "2",
            "--conv3d-arith", args.conv3d_arith, "--conv2d-arith", args.conv2d_arith, "--conv3d-algo", args.conv3d_algo,
-           "--graph-memory", args.graph_memory, "--pipeline", "off", "--sustained-s", "0"] + (["--no-graph"] if args.no_graph else [])
+           "--graph-memory", args.graph_memory, "--pipeline", "off"] + (["--no-graph"] if args.no_graph else [])
     t0 = time.time()
     try:
         r = subprocess.run(cmd, cwd=tempfile.gettempdir(), env=env, capture_output=True, text=True, timeout=600)
@@ -730,6 +741,85 @@ def summarize(prof, peak_tf, algo="direct", arith="f32", replay=None):
                 hbm[name].update({"avg_launch_us": round(1e3 * ms / n, 1), "source": "eager brackets (no replay trace)"})
                 hbm[name].update(hbm[name]["eager"])
     return mfma, hbm
+
+
+def roofline(args, prof, replay, replay_info, device):
+    """--full: the dominant 3D convolution and every kernel family against its roof (eager HIP-event brackets of ``prof``, the
+    rocprofv3 replay trace beside them) and the HBM-bound kernels alone on the device: the line's ``roofline`` entry."""
+    import torch
+    peak = PEAK_FP32_MATRIX_TFLOPS if args.conv3d_arith == "f32" else PEAK_BF16_MATRIX_TFLOPS / 6.0
+    mfma, hbm = summarize(prof, peak, args.conv3d_algo, args.conv3d_arith, replay)
+    kalgo = conv3d_algo_of("conv3d:32->32", args.conv3d_algo, args.conv3d_arith)
+    zero = {"achieved_tflops": 0.0, "frac": 0.0, "algorithmic_tflops": 0.0, "algorithmic_frac": 0.0}
+    dom = mfma.get("conv3d:32->32", dict(zero, launches=0, eager_bracket_ms=0.0, gflop_per_launch=0.0, eager=zero))
+    # per-family agreement of the two measurements (>15 % apart = a kernel whose neighbours differ between the eager bracket pass
+    # and the replay: the replay figure is the one that describes `value`)
+    perturbed = sorted(k for k, v in list(mfma.items()) + list(hbm.items()) if abs(v.get("eager_over_replay", 1.0) - 1.0) > 0.15)
+    # HBM bytes per launch of the dominant kernel from the committed rocprofv3 PMC passes (FETCH_SIZE x2 correction +
+    # WRITE_SIZE, tools/pmc_collect.sh; counters cannot be read from inside the timed process), scaled to this run's average
+    # volumes per launch; null if the file is absent
+    traffic, traffic_src = None, None
+    vox = WORKLOADS[args.workload][3] * (WORKLOADS[args.workload][1] // 4) * (WORKLOADS[args.workload][2] // 4)
+    for name in ("r6_conv3d_pmc.json", "r5_conv3d_pmc.json", "r4_conv3d_pmc.json", "r3_conv3d_pmc.json", "r2_conv3d_pmc.json", "r1_conv3d_pmc.json"):
+        pmc_file = os.path.join(ROOT, "profiles", name)
+        if os.path.exists(pmc_file) and dom["launches"] and args.workload in ("joint", "estm") and args.conv3d_arith == "f32":
+            rec = json.load(open(pmc_file))
+            per_vol = rec.get("hbm_bytes_per_volume_by_algo", {}).get(kalgo, rec.get("hbm_bytes_per_volume"))
+            if per_vol is None:
+                continue
+            vols = dom["gflop_per_launch"] * 1e9 / (2.0 * 27 * 32 * 32 * vox)
+            traffic, traffic_src = round(per_vol * vols), "profiles/" + name
+            break
+    # the HBM-bound kernels once more, each ALONE on the device (the in-step brackets sit on overlapped streams: they measure
+    # contention with the convolutions, not the kernel)
+    hbm_alone = None
+    if args.workload in ("joint", "estm", "cfg5"):
+        try:
+            from estdepth_amd.microbench import hbm_kernels_standalone
+            hbm_alone = hbm_kernels_standalone(WORKLOADS[args.workload][3], WORKLOADS[args.workload][1] // 4, WORKLOADS[args.workload][2] // 4,
+                                               n=10, device=device, peak_gbs=HBM_PEAK_GBS)
+        except Exception as e:
+            hbm_alone = {"error": "%s: %s" % (type(e).__name__, str(e)[:100])}
+        if args.workload == "joint" and isinstance(hbm_alone, dict) and "error" not in hbm_alone:
+            # ... and the fused warp + attention at the HBM stress size (cfg5: 128 x 240 x 320 voxels, 2 memory volumes): the HBM kernel
+            # furthest below its roof, at the size where it weighs most
+            try:
+                big = hbm_kernels_standalone(128, 240, 320, n=5, device=device, peak_gbs=HBM_PEAK_GBS, only_attention=(2,))
+                hbm_alone["warp_attention N=2 @cfg5 (128x240x320)"] = big["warp_attention N=2"]
+                torch.cuda.empty_cache()
+            except Exception as e:
+                hbm_alone["warp_attention N=2 @cfg5 (128x240x320)"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:100])}
+    kname = {"wino3": "conv3d_wino3_kernel (3x3x3 conv 32->32, fp32 MFMA 16x16x4, all three axes in Winograd F(2,3) form: 8/27 of the products)",
+             "wino2": "conv3d_wino2_kernel (3x3x3 conv 32->32, fp32 MFMA 16x16x4, depth and row axis in Winograd F(2,3) form: 12/27 of the products)",
+             "wino": "conv3d_wino_kernel (3x3x3 conv 32->32, fp32 MFMA 16x16x4, depth axis in Winograd F(2,3) form: 18/27 of the products)",
+             "direct": "conv3d_k3_kernel<32,2> (3x3x3 conv 32->32, fp32 MFMA 16x16x4)"}[kalgo]
+    # `achieved` / `frac` = MFMA FLOPs the dominant kernel actually EXECUTES per second against the fp32 matrix peak (<= 1 by
+    # construction: the hardware fraction).  `algorithmic_*` = the direct convolution's 2*27*Cin*Cout FLOPs per voxel (SURVEY
+    # §8d) over the same time -- above the peak when exact Winograd identities remove products.
+    return {"bound": "mfma",
+            "kernel": kname if args.conv3d_arith == "f32" else
+                      "conv3d_k3_split_kernel (3x3x3 conv 32->32, 6 x bf16 MFMA 16x16x32 per fp32 product block; peak = bf16 dense / 6)",
+            # dominant kernel, live HIP events on its launch stream (the contract's measurement) ...
+            "achieved": dom["eager"]["achieved_tflops"], "peak": round(peak, 1), "unit": "TFLOP/s",
+            "frac": dom["eager"]["frac"],
+            "executed_factor": round(EXECUTED_FACTOR[kalgo], 4),
+            "algorithmic_tflops": dom["eager"]["algorithmic_tflops"], "algorithmic_frac": dom["eager"]["algorithmic_frac"],
+            "traffic": traffic,
+            "traffic_unit": "HBM bytes per launch (rocprofv3 FETCH_SIZE x2 + WRITE_SIZE, %s)" % traffic_src,
+            "launches": dom["launches"], "avg_launch_ms": dom["eager_bracket_ms"],
+            "launches_per_step": round(dom["launches"] / max(args.steps, 1), 2),
+            "how": "HIP events around every launch of the dominant kernel in %d eager steps after the timed loop, on its launch stream" % args.steps,
+            # ... and the same kernel inside the hipGraph replay (rocprofv3 trace of a child run): the two must agree
+            "replay": ({"avg_launch_ms": dom.get("avg_launch_ms"), "frac": dom.get("frac"), "achieved": dom.get("achieved_tflops"),
+                        "algorithmic_tflops": dom.get("algorithmic_tflops"), "eager_over_replay": dom.get("eager_over_replay")}
+                       if dom.get("source") == "replay" else None),
+            "replay_trace": replay_info,
+            # every family: `avg_launch_*` / `frac` / `achieved_*` describe the REPLAY when source == "replay" (the run that
+            # produced `value`); `eager_bracket_*` / `eager` = the HIP-event brackets of the eager pass, kept for comparison
+            "families_perturbed_by_eager_brackets": perturbed,
+            "mfma_kernels": mfma,                     # every 3x3x3 convolution instance: executed and algorithmic TFLOP/s
+            "hbm_kernels": hbm,                       # in-step (overlapped streams): GB/s of ALGORITHMIC bytes, fraction of 8 TB/s
+            "hbm_kernels_standalone": hbm_alone}     # the same kernels alone on the device
 
 
 def main():
@@ -922,10 +1012,12 @@ def main():
     elapsed = time.perf_counter() - t0
     dumped = dump_outputs(last, args.dump_outputs) if args.dump_outputs and rank == 0 else None       # before any later call reuses the buffers
     gathered = state["allgather"]
-    gpu_outputs = {k: v.clone() for k, v in last[0].items()}        # outputs of the timed configuration (for the parity report)
-    gpu_logits = {k: v.clone() for k, v in (getattr(model.CostRegNet, "last_logits", None) or {}).items()}
-    f2d = getattr(state["fwd"], "last_features2d", None) or getattr(model, "last_features2d", None)       # stage A's outputs of the last timed step
-    gpu_feats = {"matching": f2d["matching"].clone(), "semantic_features": [t.clone() for t in f2d["semantic_features"]]} if f2d else None
+    gpu_outputs = gpu_logits = gpu_feats = None
+    if args.full:                   # outputs of the timed configuration (for the parity report and the bf16x3 second opinion)
+        gpu_outputs = {k: v.clone() for k, v in last[0].items()}
+        gpu_logits = {k: v.clone() for k, v in (getattr(model.CostRegNet, "last_logits", None) or {}).items()}
+        f2d = getattr(state["fwd"], "last_features2d", None) or getattr(model, "last_features2d", None)       # stage A's outputs of the last timed step
+        gpu_feats = {"matching": f2d["matching"].clone(), "semantic_features": [t.clone() for t in f2d["semantic_features"]]} if f2d else None
     # "gathered bank equals each owner's tensors bit for bit" -- every rank checks the shard it owns
     bank_ok = None
     if gathered and state["bank"] is not None:
@@ -938,13 +1030,13 @@ def main():
 
     # ---- is the K-step figure a sustained one?  The same step (same launch path, same overlapped exchange) for tens of seconds ----
     sustained = None
-    if args.sustained_s > 0 and os.environ.get("ESTD_BENCH_CHILD") != "1":
+    if args.full and args.sustained_s > 0:
         sustained = sustained_loop(step, drain, barrier, args, elapsed, device, dist if world > 1 else None, local_rank)
 
     # ---- pipelined replay: the SAME K steps once more on the serial replay (stage A and stage B of a step back to back on one stream, no
     #      overlap between steps): the A/B of the pipeline inside every line, and the configuration the per-kernel trace below describes ----
     serial = None
-    if pipelined and state["fwd"] is not model and os.environ.get("ESTD_BENCH_CHILD") != "1":
+    if args.full and pipelined and state["fwd"] is not model:
         try:
             f_ser = GraphedForward(model, zero_copy_memory=zero_copy, reserve_cus=reserve, pipeline=False)
             for _ in range(GRAPH_PRIME + args.warmup):
@@ -1013,7 +1105,7 @@ def main():
             tl = float(tt_[0])
         return tl
 
-    if dist_on and gathered:
+    if args.full and dist_on and gathered:
         # every N: the same K steps WITHOUT the collective (CU reserve still in place) -- what the overlapped exchange costs a step, and the
         # figure that is comparable with the driver's N = 1 line
         t_nc = timed_plain()
@@ -1044,7 +1136,7 @@ def main():
     # Rooflines: the same steps once more, launched eagerly, with a HIP-event pair around every hot-path launch on its
     # launch stream (events cannot bracket nodes inside a graph replay).  Rank 0 only.
     prof = []
-    if rank == 0:
+    if args.full and rank == 0:
         ops.PROFILE = []
         for _ in range(args.steps):
             step(model)
@@ -1052,13 +1144,13 @@ def main():
         prof, ops.PROFILE = ops.PROFILE, None
     # ... and what those kernels take INSIDE the hipGraph replay that produced `value`: kernel trace of a short child run
     replay, replay_info = None, None
-    if rank == 0 and world == 1 and not force_dist and not args.no_replay_profile:
+    if args.full and rank == 0 and world == 1 and not force_dist and not args.no_replay_profile:
         replay, replay_info = replay_profile(args)
     # Second opinion, reported beside (never instead of) the headline: the same K steps with the 3x3x3 / 3x3 convolutions
     # on the exact 3-way bf16 operand split (fp32-level error, tests/test_gpu_split_conv.py), N = 1 only.
     alt = None
     from estdepth_amd import _native
-    if world == 1 and not args.no_alt and (args.conv3d_arith, args.conv2d_arith) == ("f32", "f32") and _native.has_ab():     # (A/B build only: ESTD_BUILD_AB=1)
+    if args.full and world == 1 and not args.no_alt and (args.conv3d_arith, args.conv2d_arith) == ("f32", "f32") and _native.has_ab():     # (A/B build only: ESTD_BUILD_AB=1)
         try:
             ops.CONV3D_ARITH = ops.CONV2D_ARITH = "bf16x3"
             state["fwd"] = model if args.no_graph else GraphedForward(model, zero_copy_memory=zero_copy)
@@ -1090,52 +1182,7 @@ def main():
 
     if rank == 0:
         value = frames * world * args.steps / elapsed
-        peak = PEAK_FP32_MATRIX_TFLOPS if args.conv3d_arith == "f32" else PEAK_BF16_MATRIX_TFLOPS / 6.0
-        mfma, hbm = summarize(prof, peak, args.conv3d_algo, args.conv3d_arith, replay)
         kalgo = conv3d_algo_of("conv3d:32->32", args.conv3d_algo, args.conv3d_arith)
-        zero = {"achieved_tflops": 0.0, "frac": 0.0, "algorithmic_tflops": 0.0, "algorithmic_frac": 0.0}
-        dom = mfma.get("conv3d:32->32", dict(zero, launches=0, eager_bracket_ms=0.0, gflop_per_launch=0.0, eager=zero))
-        # per-family agreement of the two measurements (>15 % apart = a kernel whose neighbours differ between the eager bracket pass
-        # and the replay: the replay figure is the one that describes `value`)
-        perturbed = sorted(k for k, v in list(mfma.items()) + list(hbm.items()) if abs(v.get("eager_over_replay", 1.0) - 1.0) > 0.15)
-        # HBM bytes per launch of the dominant kernel from the committed rocprofv3 PMC passes (FETCH_SIZE x2 correction +
-        # WRITE_SIZE, tools/pmc_collect.sh; counters cannot be read from inside the timed process), scaled to this run's average
-        # volumes per launch; null if the file is absent
-        traffic, traffic_src = None, None
-        vox = WORKLOADS[args.workload][3] * (WORKLOADS[args.workload][1] // 4) * (WORKLOADS[args.workload][2] // 4)
-        for name in ("r6_conv3d_pmc.json", "r5_conv3d_pmc.json", "r4_conv3d_pmc.json", "r3_conv3d_pmc.json", "r2_conv3d_pmc.json", "r1_conv3d_pmc.json"):
-            pmc_file = os.path.join(ROOT, "profiles", name)
-            if os.path.exists(pmc_file) and dom["launches"] and args.workload in ("joint", "estm") and args.conv3d_arith == "f32":
-                rec = json.load(open(pmc_file))
-                per_vol = rec.get("hbm_bytes_per_volume_by_algo", {}).get(kalgo, rec.get("hbm_bytes_per_volume"))
-                if per_vol is None:
-                    continue
-                vols = dom["gflop_per_launch"] * 1e9 / (2.0 * 27 * 32 * 32 * vox)
-                traffic, traffic_src = round(per_vol * vols), "profiles/" + name
-                break
-        # the HBM-bound kernels once more, each ALONE on the device (the in-step brackets sit on overlapped streams: they measure
-        # contention with the convolutions, not the kernel)
-        hbm_alone = None
-        if args.workload in ("joint", "estm", "cfg5"):
-            try:
-                from estdepth_amd.microbench import hbm_kernels_standalone
-                hbm_alone = hbm_kernels_standalone(WORKLOADS[args.workload][3], WORKLOADS[args.workload][1] // 4, WORKLOADS[args.workload][2] // 4,
-                                                   n=10, device=device, peak_gbs=HBM_PEAK_GBS)
-            except Exception as e:
-                hbm_alone = {"error": "%s: %s" % (type(e).__name__, str(e)[:100])}
-            if args.workload == "joint" and isinstance(hbm_alone, dict) and "error" not in hbm_alone:
-                # ... and the fused warp + attention at the HBM stress size (cfg5: 128 x 240 x 320 voxels, 2 memory volumes): the HBM kernel
-                # furthest below its roof, at the size where it weighs most
-                try:
-                    big = hbm_kernels_standalone(128, 240, 320, n=5, device=device, peak_gbs=HBM_PEAK_GBS, only_attention=(2,))
-                    hbm_alone["warp_attention N=2 @cfg5 (128x240x320)"] = big["warp_attention N=2"]
-                    torch.cuda.empty_cache()
-                except Exception as e:
-                    hbm_alone["warp_attention N=2 @cfg5 (128x240x320)"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:100])}
-        kname = {"wino3": "conv3d_wino3_kernel (3x3x3 conv 32->32, fp32 MFMA 16x16x4, all three axes in Winograd F(2,3) form: 8/27 of the products)",
-                 "wino2": "conv3d_wino2_kernel (3x3x3 conv 32->32, fp32 MFMA 16x16x4, depth and row axis in Winograd F(2,3) form: 12/27 of the products)",
-                 "wino": "conv3d_wino_kernel (3x3x3 conv 32->32, fp32 MFMA 16x16x4, depth axis in Winograd F(2,3) form: 18/27 of the products)",
-                 "direct": "conv3d_k3_kernel<32,2> (3x3x3 conv 32->32, fp32 MFMA 16x16x4)"}[kalgo]
         line = {
             "metric": "depth frames/sec (seq_len=5, 480x640, D=64)" if args.workload == "joint" else "depth frames/sec",
             "value": round(value, 3), "unit": "depth frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1154,6 +1201,7 @@ def main():
                        "conv3d_arith": args.conv3d_arith, "conv2d_arith": args.conv2d_arith,
                        "conv3d_algo_32to32": kalgo,
                        "dump_outputs": dumped,
+                       "full": args.full,
                        "notes": state["notes"],
                        # the K-step figure against tens of seconds of the same step (timed / sustained: 1.0 = the headline IS a sustained rate)
                        "sustained_ms_per_step": sustained["ms_per_step"] if sustained else None,
@@ -1163,33 +1211,7 @@ def main():
                        "parallelism": "1 sequence per GPU" + ("; RCCL all-gather of {K,V,pose} per step, overlapped with the next step" if gathered else "")
                                       + (("; %d CUs left free for the collective in stage %s" % (state["reserved_cus"], "A (2D networks)" if state.get("reserve_scope") == "A" else "A and B"))
                                          if state.get("reserved_cus") else "")},
-            # `achieved` / `frac` = MFMA FLOPs the dominant kernel actually EXECUTES per second against the fp32 matrix peak (<= 1 by
-            # construction: the hardware fraction).  `algorithmic_*` = the direct convolution's 2*27*Cin*Cout FLOPs per voxel (SURVEY
-            # §8d) over the same time -- above the peak when exact Winograd identities remove products.
-            "roofline": {"bound": "mfma",
-                         "kernel": kname if args.conv3d_arith == "f32" else
-                                   "conv3d_k3_split_kernel (3x3x3 conv 32->32, 6 x bf16 MFMA 16x16x32 per fp32 product block; peak = bf16 dense / 6)",
-                         # dominant kernel, live HIP events on its launch stream (the contract's measurement) ...
-                         "achieved": dom["eager"]["achieved_tflops"], "peak": round(peak, 1), "unit": "TFLOP/s",
-                         "frac": dom["eager"]["frac"],
-                         "executed_factor": round(EXECUTED_FACTOR[kalgo], 4),
-                         "algorithmic_tflops": dom["eager"]["algorithmic_tflops"], "algorithmic_frac": dom["eager"]["algorithmic_frac"],
-                         "traffic": traffic,
-                         "traffic_unit": "HBM bytes per launch (rocprofv3 FETCH_SIZE x2 + WRITE_SIZE, %s)" % traffic_src,
-                         "launches": dom["launches"], "avg_launch_ms": dom["eager_bracket_ms"],
-                         "launches_per_step": round(dom["launches"] / max(args.steps, 1), 2),
-                         "how": "HIP events around every launch of the dominant kernel in %d eager steps after the timed loop, on its launch stream" % args.steps,
-                         # ... and the same kernel inside the hipGraph replay (rocprofv3 trace of a child run): the two must agree
-                         "replay": ({"avg_launch_ms": dom.get("avg_launch_ms"), "frac": dom.get("frac"), "achieved": dom.get("achieved_tflops"),
-                                     "algorithmic_tflops": dom.get("algorithmic_tflops"), "eager_over_replay": dom.get("eager_over_replay")}
-                                    if dom.get("source") == "replay" else None),
-                         "replay_trace": replay_info,
-                         # every family: `avg_launch_*` / `frac` / `achieved_*` describe the REPLAY when source == "replay" (the run that
-                         # produced `value`); `eager_bracket_*` / `eager` = the HIP-event brackets of the eager pass, kept for comparison
-                         "families_perturbed_by_eager_brackets": perturbed,
-                         "mfma_kernels": mfma,                     # every 3x3x3 convolution instance: executed and algorithmic TFLOP/s
-                         "hbm_kernels": hbm,                       # in-step (overlapped streams): GB/s of ALGORITHMIC bytes, fraction of 8 TB/s
-                         "hbm_kernels_standalone": hbm_alone},     # the same kernels alone on the device
+            "roofline": roofline(args, prof, replay, replay_info, device) if args.full else None,      # (null in a plain run)
         }
         if ag is not None:
             line["config"]["allgather"] = ag
@@ -1199,7 +1221,7 @@ def main():
             del model, fwd
             state["fwd"] = None
             torch.cuda.empty_cache()
-        if world == 1 and not force_dist and not args.no_other_workloads and args.workload == "joint":
+        if args.full and world == 1 and not force_dist and not args.no_other_workloads and args.workload == "joint":
             # the other single-GPU configurations of BASELINE.json (configs[2], configs[4]) and the streaming harness, timed the same way
             # in this very run (short loops): driver-visible numbers beside the headline, not instead of it
             others = {}
@@ -1221,7 +1243,7 @@ def main():
             except Exception as e:
                 others["joint_stream"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:120])}
             line["other_workloads"] = others
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # two CPU restatements on the box's host cores -- the C/OpenMP port (the parity checker, 8 threads: it
             # does not scale further) and the torch-operator leg (oneDNN / ATen, what the reference itself would run: 8 threads for
             # comparability with BASELINE.md section 2 AND torch's default = all physical cores); headline entry = the fastest

@@ -1,5 +1,6 @@
-"""GPU: bench.py contract -- one JSON line with the required keys at N=1, and the N=2 code path (two ranks sharing the
-single test GPU, gloo instead of RCCL) including the memory-bank all-gather and the max-over-ranks timing."""
+"""GPU: bench.py contract -- one JSON line with the required keys at N=1 (a plain run: the headline alone; --full: everything
+else beside it), and the N=2 code path (two ranks sharing the single test GPU, gloo instead of RCCL) including the memory-bank
+all-gather and the max-over-ranks timing."""
 import json
 import os
 import socket
@@ -28,11 +29,24 @@ def _last_json(out):
     return json.loads(lines[0])
 
 
+def test_bench_plain_line_is_the_headline_alone():
+    """a plain run (no --full): set-up, warm-up, the timed steps, one line -- the headline fields, nothing measured beside them"""
+    out = subprocess.run([sys.executable, "bench.py", "--workload", "cfg1", "--steps", "3", "--warmup", "1"], cwd=ROOT,
+                         capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = _last_json(out.stdout)
+    assert REQUIRED <= set(d) and d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["unit"] == "depth frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32" and d["config"]["workload"].startswith("cfg1")
+    assert abs(d["config"]["depth_frames_per_step"] * 1e3 / d["value"] - d["ms_per_step"]) <= 1e-3          # value = frames per step / step time
+    assert d["config"]["full"] is False and d["roofline"] is None and d["config"]["sustained"] is None and d["config"]["dump_outputs"] is None
+    assert not {"cpu_baseline", "parity", "other_workloads", "alt_arith"} & set(d)
+
+
 def test_bench_single_gpu_line():
-    out = subprocess.run([sys.executable, "bench.py", "--workload", "cfg1", "--steps", "3", "--warmup", "1", "--sustained-s", "1", "--sustained-bucket", "50", "--no-replay-profile"], cwd=ROOT,
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--workload", "cfg1", "--steps", "3", "--warmup", "1", "--sustained-s", "1", "--sustained-bucket", "50", "--no-replay-profile"], cwd=ROOT,
                          capture_output=True, text=True, timeout=900)
     d = _last_json(out.stdout)
-    assert REQUIRED <= set(d) and "cpu_baseline" in d
+    assert REQUIRED <= set(d) and "cpu_baseline" in d and d["config"]["full"] is True
     assert d["parity"]["logits_within_tolerance"] and set(d["parity"]["logit_volumes_vs_oracle"]) == {"init", "fused"}
     assert d["n_gpus"] == 1 and d["value"] > 0 and d["config"]["workload"].startswith("cfg1")
     assert d["roofline"]["bound"] == "mfma" and 0 < d["roofline"]["frac"] <= 1
@@ -67,8 +81,7 @@ def test_bench_dump_outputs_are_repeatable(tmp_path, workload):
     import numpy as np
     dumps = []
     for run in ("a", "b"):
-        out = subprocess.run([sys.executable, "bench.py", "--workload", workload, "--steps", "2", "--warmup", "1", "--sustained-s", "0", "--no-alt",
-                              "--no-cpu-baseline", "--no-replay-profile", "--dump-outputs", str(tmp_path / run)],
+        out = subprocess.run([sys.executable, "bench.py", "--workload", workload, "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / run)],
                              cwd=ROOT, capture_output=True, text=True, timeout=900)
         d = _last_json(out.stdout)
         assert d["steps"] == 2 and d["ms_per_step"] > 0 and set(d["config"]["dump_outputs"]) == {f[:-4] for f in os.listdir(tmp_path / run)}
@@ -88,7 +101,7 @@ def test_bench_headline_workload_roofline_fields_are_hardware_fractions():
     hipGraph REPLAY that produced `value` (rocprofv3 kernel trace of a child run), the dominant kernel's live HIP-event brackets
     agree with it within 15 %, and every family whose eager bracket is further off is named.  The other single-GPU workloads
     (ESTM window, cfg5, stream) are timed in the same run."""
-    out = subprocess.run([sys.executable, "bench.py", "--workload", "joint", "--steps", "5", "--warmup", "2", "--no-alt", "--no-cpu-baseline", "--sustained-s", "6"],
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--workload", "joint", "--steps", "5", "--warmup", "2", "--no-alt", "--no-cpu-baseline", "--sustained-s", "6"],
                          cwd=ROOT, capture_output=True, text=True, timeout=1500)
     d = _last_json(out.stdout)
     r = d["roofline"]
@@ -134,7 +147,7 @@ def test_bench_world_size_one_rccl_communicator():
     channel cap, CU reserve, the asynchronous all-gather overlapped with the next step, the own-shard bit-equality check."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["ESTD_FORCE_DIST"] = "1"
-    out = subprocess.run([sys.executable, "bench.py", "--workload", "cfg1", "--steps", "3", "--warmup", "1", "--sustained-s", "1", "--sustained-bucket", "50", "--no-alt", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--workload", "cfg1", "--steps", "3", "--warmup", "1", "--sustained-s", "1", "--sustained-bucket", "50", "--no-alt", "--no-cpu-baseline"],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     d = _last_json(out.stdout)
     ag = d["config"]["allgather"]
@@ -173,7 +186,7 @@ def test_bench_gpus_flag_launches_the_ranks_itself():
     """the driver's command line: `python bench.py --gpus N` with NO launcher and no WORLD_SIZE -> bench.py re-executes
     itself under torch.distributed.run with N ranks (here: 2 ranks sharing the single test GPU, gloo instead of RCCL)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    out = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--workload", "cfg1", "--steps", "3", "--warmup", "1", "--sustained-s", "1", "--sustained-bucket", "50"],
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "2", "--workload", "cfg1", "--steps", "3", "--warmup", "1", "--sustained-s", "1", "--sustained-bucket", "50"],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     d = _last_json(out.stdout)
     _check_two_ranks(d)
@@ -183,7 +196,7 @@ def test_bench_gpus_flag_launches_the_ranks_itself():
 def test_bench_two_ranks_under_an_external_launcher():
     env = dict(os.environ, ESTD_FORCE_DEVICE="0", ESTD_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--workload", "cfg1", "--steps", "3", "--warmup", "1", "--sustained-s", "1", "--sustained-bucket", "50"]
+           "--master-port", str(_free_port()), "bench.py", "--full", "--gpus", "2", "--workload", "cfg1", "--steps", "3", "--warmup", "1", "--sustained-s", "1", "--sustained-bucket", "50"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     _check_two_ranks(_last_json(out.stdout))
 

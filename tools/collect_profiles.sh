@@ -70,22 +70,22 @@ tools/bin/mfma_valu_overlap > $OUT/${P}_mfma_valu_overlap.txt 2>&1
 [ "${ESTD_COLLECT_LINES:-1}" = 1 ] || { ls -la $OUT; exit 0; }
 # default bench lines (with cpu_baseline + parity) of every workload; algorithm A/B; the world-size-1 RCCL run
 last() { grep "^{" | tail -1; }
-python bench.py --steps 20 --warmup 5 2>/dev/null | last > $OUT/${P}_bench_joint.json
-python bench.py --steps 20 --warmup 5 --sustained-s 60 --no-cpu-baseline --no-other-workloads --no-replay-profile 2>/dev/null | last > $OUT/${P}_bench_joint_sustained60.json
-python bench.py --workload estm 2>/dev/null | last > $OUT/${P}_bench_estm.json
-python bench.py --workload cfg1 2>/dev/null | last > $OUT/${P}_bench_cfg1.json
-python bench.py --workload cfg5 --steps 5 --warmup 2 2>/dev/null | last > $OUT/${P}_bench_cfg5.json
+python bench.py --full --steps 20 --warmup 5 2>/dev/null | last > $OUT/${P}_bench_joint.json
+python bench.py --full --steps 20 --warmup 5 --sustained-s 60 --no-cpu-baseline --no-other-workloads --no-replay-profile 2>/dev/null | last > $OUT/${P}_bench_joint_sustained60.json
+python bench.py --full --workload estm 2>/dev/null | last > $OUT/${P}_bench_estm.json
+python bench.py --full --workload cfg1 2>/dev/null | last > $OUT/${P}_bench_cfg1.json
+python bench.py --full --workload cfg5 --steps 5 --warmup 2 2>/dev/null | last > $OUT/${P}_bench_cfg5.json
 python bench.py --workload stream --steps 20 2>/dev/null | last > $OUT/${P}_bench_stream.json
-ESTD_W3=0 python bench.py --no-cpu-baseline --no-alt --no-replay-profile --no-other-workloads 2>/dev/null | last > $OUT/${P}_bench_joint_two_axis.json
-ESTD_GATE_IN_CONV=0 python bench.py --no-cpu-baseline --no-alt --no-replay-profile --no-other-workloads 2>/dev/null | last > $OUT/${P}_bench_joint_gate_pass.json
-python bench.py --conv3d-algo direct --no-cpu-baseline --no-alt --no-replay-profile --no-other-workloads 2>/dev/null | last > $OUT/${P}_bench_joint_direct_conv.json
-python bench.py --no-graph --no-cpu-baseline --no-alt --no-replay-profile --no-other-workloads 2>/dev/null | last > $OUT/${P}_bench_joint_eager.json
-ESTD_FORCE_DIST=1 python bench.py --no-cpu-baseline --no-alt --no-other-workloads 2>/dev/null | last > $OUT/${P}_bench_joint_rccl_world1.json
-ESTD_FORCE_DIST=1 python bench.py --workload estm --no-cpu-baseline --no-alt --no-other-workloads 2>/dev/null | last > $OUT/${P}_bench_estm_rccl_world1.json
-python bench.py --gpus 2 --workload cfg1 --steps 5 --warmup 2 2>/dev/null | last > $OUT/${P}_bench_gpus2_codepath.json
-ESTD_HIP_1X1=0 python bench.py --no-cpu-baseline --no-alt --no-replay-profile --no-other-workloads 2>/dev/null | last > $OUT/${P}_bench_joint_lib1x1.json
-ESTD_HIP_TAPS=0 ESTD_HIP_POOL=0 ESTD_HIP_STEM7=0 python bench.py --no-cpu-baseline --no-alt --no-replay-profile --no-other-workloads 2>/dev/null | last > $OUT/${P}_bench_joint_lib2d.json
-python bench.py --graph-memory copy --no-cpu-baseline --no-alt --no-replay-profile --no-other-workloads 2>/dev/null | last > $OUT/${P}_bench_joint_graph_copy.json
-python bench.py --workload estm --graph-memory copy --no-cpu-baseline --no-alt --no-replay-profile --no-other-workloads 2>/dev/null | last > $OUT/${P}_bench_estm_graph_copy.json
+ESTD_W3=0 python bench.py --full --no-cpu-baseline --no-alt --no-replay-profile --no-other-workloads 2>/dev/null | last > $OUT/${P}_bench_joint_two_axis.json
+ESTD_GATE_IN_CONV=0 python bench.py --full --no-cpu-baseline --no-alt --no-replay-profile --no-other-workloads 2>/dev/null | last > $OUT/${P}_bench_joint_gate_pass.json
+python bench.py --full --conv3d-algo direct --no-cpu-baseline --no-alt --no-replay-profile --no-other-workloads 2>/dev/null | last > $OUT/${P}_bench_joint_direct_conv.json
+python bench.py --full --no-graph --no-cpu-baseline --no-alt --no-replay-profile --no-other-workloads 2>/dev/null | last > $OUT/${P}_bench_joint_eager.json
+ESTD_FORCE_DIST=1 python bench.py --full --no-cpu-baseline --no-alt --no-other-workloads 2>/dev/null | last > $OUT/${P}_bench_joint_rccl_world1.json
+ESTD_FORCE_DIST=1 python bench.py --full --workload estm --no-cpu-baseline --no-alt --no-other-workloads 2>/dev/null | last > $OUT/${P}_bench_estm_rccl_world1.json
+python bench.py --full --gpus 2 --workload cfg1 --steps 5 --warmup 2 2>/dev/null | last > $OUT/${P}_bench_gpus2_codepath.json
+ESTD_HIP_1X1=0 python bench.py --full --no-cpu-baseline --no-alt --no-replay-profile --no-other-workloads 2>/dev/null | last > $OUT/${P}_bench_joint_lib1x1.json
+ESTD_HIP_TAPS=0 ESTD_HIP_POOL=0 ESTD_HIP_STEM7=0 python bench.py --full --no-cpu-baseline --no-alt --no-replay-profile --no-other-workloads 2>/dev/null | last > $OUT/${P}_bench_joint_lib2d.json
+python bench.py --full --graph-memory copy --no-cpu-baseline --no-alt --no-replay-profile --no-other-workloads 2>/dev/null | last > $OUT/${P}_bench_joint_graph_copy.json
+python bench.py --full --workload estm --graph-memory copy --no-cpu-baseline --no-alt --no-replay-profile --no-other-workloads 2>/dev/null | last > $OUT/${P}_bench_estm_graph_copy.json
 timeout 2400 python -m pytest tests/ -q -m gpu > $OUT/${P}_gputests.log 2>&1
 ls -la $OUT
