@@ -73,6 +73,17 @@ class Conv2dTapsDesc(ctypes.Structure):
     ]
 
 
+class TsdfIntegrateDesc(ctypes.Structure):
+    """Mirror of struct estd_tsdf_integrate_desc (include/estd_hip.h)."""
+    _fields_ = [
+        ("Z", ctypes.c_int), ("Y", ctypes.c_int), ("X", ctypes.c_int), ("T", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
+        ("weighted", ctypes.c_int), ("no_skip", ctypes.c_int),
+        ("trunc", ctypes.c_float), ("z_near", ctypes.c_float), ("conf_min", ctypes.c_float), ("w_max", ctypes.c_float),
+        ("tsdf", ctypes.c_void_p), ("weight", ctypes.c_void_p),
+        ("depth", ctypes.c_void_p * 8), ("conf", ctypes.c_void_p * 8), ("mats", (ctypes.c_float * 12) * 8),
+    ]
+
+
 _SIGNATURES = {
     "estd_version": (ctypes.c_int, []),
     "estd_status_string": (ctypes.c_char_p, [ctypes.c_int]),
@@ -139,6 +150,10 @@ _SIGNATURES = {
                                              c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_stream]),
     "estd_cdhw_to_vol": (ctypes.c_int, [c_float_p, c_float_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, c_stream]),
     "estd_vol_to_cdhw": (ctypes.c_int, [c_float_p, c_float_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, c_stream]),
+    "estd_tsdf_integrate": (ctypes.c_int, [ctypes.POINTER(TsdfIntegrateDesc), c_stream]),
+    "estd_tsdf_extract_points": (ctypes.c_int, [c_float_p, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
+                                                ctypes.POINTER(ctypes.c_float), ctypes.c_float, ctypes.c_void_p, ctypes.c_longlong,
+                                                c_float_p, c_float_p, c_float_p, ctypes.c_void_p, c_stream]),
 }
 
 # the superseded A/B kernels: exported only by a library built with ESTD_BUILD_AB=1 (estdepth_amd/build.py)

@@ -187,3 +187,22 @@ def volume_matrices_device(poses, n_targets, cam_intr_q):
         for r, j in enumerate([j for j in range(len(P)) if j != i]):
             ops.cam_volume_mats(P[j], P[i], K, out=out[i, r])
     return out
+
+
+# ------------------------------------------------------------------------------------------------ TSDF fusion
+def tsdf_matrices(cam_poses, cam_intr, origin, voxel_size):
+    """Voxel index -> pixel matrices of estd_tsdf_integrate: A = K [R|t]_world->camera V per frame, formed in float64 on the host and
+    rounded to fp32 -> CPU float32 [T,12] (3x4 row-major).  cam_poses [T,4,4] camera-to-world and cam_intr [3,3] or [T,3,3] in pixels (of
+    the depth maps' resolution), as DepthNetHybrid.forward documents them; V maps a voxel index to its centre
+    origin + (idx + 0.5) voxel_size."""
+    P = cam_poses.detach().to(device="cpu", dtype=torch.float64).reshape(-1, 4, 4)
+    K = cam_intr.detach().to(device="cpu", dtype=torch.float64).reshape(-1, 3, 3)
+    if K.shape[0] not in (1, P.shape[0]):
+        raise RuntimeError("tsdf_matrices: cam_intr must be [3,3] or one [3,3] per pose, got %s for %d poses" % (tuple(cam_intr.shape), P.shape[0]))
+    V = torch.eye(4, dtype=torch.float64)
+    V[:3, :3] *= float(voxel_size)
+    V[:3, 3] = torch.as_tensor(origin, dtype=torch.float64) + 0.5 * float(voxel_size)
+    out = torch.empty(P.shape[0], 12, dtype=torch.float32)
+    for t in range(P.shape[0]):
+        out[t] = ((K[t if K.shape[0] > 1 else 0] @ torch.inverse(P[t])[:3, :4]) @ V).reshape(-1).float()
+    return out

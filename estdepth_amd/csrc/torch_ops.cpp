@@ -338,6 +338,69 @@ Tensor warp_volume_ex(const Tensor& vol, const Tensor& mats30, const Tensor& dep
     return out;
 }
 
+// ------------------------------------------------------------------------------------------------ TSDF fusion (csrc/tsdf.hip)
+// volume [2,Z,Y,X]: plane 0 = D, plane 1 = Wt; in place.  mats: CPU float32 [T,12] (host values of the launch arguments).
+Tensor tsdf_integrate_(Tensor volume, at::TensorList depths, at::TensorList confs, const Tensor& mats, double trunc, double z_near,
+                       double conf_min, bool weighted, double w_max, bool no_skip)
+{
+    const OpScope scope(volume);
+    TORCH_CHECK(volume.dim() == 4 && volume.size(0) == 2, "tsdf_integrate_: volume must be [2,Z,Y,X] (D plane, weight plane)");
+    float* vol = fptr_mut(volume, "volume");
+    const int64_t Z = volume.size(1), Y = volume.size(2), X = volume.size(3);
+    TORCH_CHECK(X % 4 == 0, "tsdf_integrate_: X must be a multiple of 4, got ", X);
+    const int64_t T = (int64_t)depths.size();
+    TORCH_CHECK(T >= 1 && T <= ESTD_TSDF_MAX_FRAMES, "tsdf_integrate_: 1..", ESTD_TSDF_MAX_FRAMES, " frames per call, got ", T);
+    TORCH_CHECK(confs.empty() || (int64_t)confs.size() == T, "tsdf_integrate_: one confidence map per depth map (or none)");
+    TORCH_CHECK(!weighted || !confs.empty(), "tsdf_integrate_: weighted fusion needs confidence maps");
+    TORCH_CHECK(mats.defined() && mats.device().is_cpu() && mats.scalar_type() == at::kFloat && mats.is_contiguous() && mats.numel() == T * 12,
+                "tsdf_integrate_: mats must be a contiguous CPU float32 tensor [T,12]");
+    TORCH_CHECK(depths[0].dim() >= 2, "tsdf_integrate_: depth maps must be [H,W] (leading 1s allowed)");
+    const int64_t H = depths[0].size(-2), W = depths[0].size(-1);
+    estd_tsdf_integrate_desc d{};
+    d.Z = (int)Z; d.Y = (int)Y; d.X = (int)X; d.T = (int)T; d.H = (int)H; d.W = (int)W;
+    d.weighted = weighted; d.no_skip = no_skip;
+    d.trunc = (float)trunc; d.z_near = (float)z_near; d.conf_min = (float)conf_min; d.w_max = (float)w_max;
+    d.tsdf = vol; d.weight = vol + Z * Y * X;
+    for (int64_t t = 0; t < T; ++t) {
+        TORCH_CHECK(depths[t].dim() >= 2 && depths[t].size(-2) == H && depths[t].size(-1) == W && depths[t].numel() == H * W,
+                    "tsdf_integrate_: depth map ", t, " must be [", H, ",", W, "]");
+        d.depth[t] = fptr(depths[t], "depth map");
+        if (!confs.empty()) {
+            TORCH_CHECK(confs[t].dim() >= 2 && confs[t].size(-2) == H && confs[t].size(-1) == W && confs[t].numel() == H * W,
+                        "tsdf_integrate_: confidence map ", t, " must have the depth map's shape [", H, ",", W, "]");
+            d.conf[t] = fptr(confs[t], "confidence map");
+        }
+        for (int i = 0; i < 12; ++i) d.mats[t][i] = mats.data_ptr<float>()[t * 12 + i];
+    }
+    check_status(estd_tsdf_integrate(&d, cur_stream()), "estd_tsdf_integrate");
+    return volume;
+}
+
+// -> (count [1] int64 on the device = TOTAL crossings, xyz [capacity,3], normal [capacity,3], weight [capacity], edge [capacity] int64);
+// capacity 0 counts only.  origin: CPU float32 [3].
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> tsdf_extract_points(const Tensor& volume, double voxel_size, const Tensor& origin,
+                                                                       double w_min, int64_t capacity)
+{
+    const OpScope scope(volume);
+    TORCH_CHECK(volume.dim() == 4 && volume.size(0) == 2, "tsdf_extract_points: volume must be [2,Z,Y,X] (D plane, weight plane)");
+    const float* vol = fptr(volume, "volume");
+    const int64_t Z = volume.size(1), Y = volume.size(2), X = volume.size(3);
+    TORCH_CHECK(X % 4 == 0, "tsdf_extract_points: X must be a multiple of 4, got ", X);
+    TORCH_CHECK(capacity >= 0, "tsdf_extract_points: capacity must not be negative");
+    TORCH_CHECK(origin.defined() && origin.device().is_cpu() && origin.scalar_type() == at::kFloat && origin.is_contiguous() && origin.numel() == 3,
+                "tsdf_extract_points: origin must be a contiguous CPU float32 tensor [3]");
+    Tensor count = at::zeros({1}, volume.options().dtype(at::kLong));
+    Tensor xyz = new_f32({capacity, 3}, volume), normal = new_f32({capacity, 3}, volume), weight = new_f32({capacity}, volume);
+    Tensor edge = at::empty({capacity}, volume.options().dtype(at::kLong));
+    check_status(estd_tsdf_extract_points(vol, vol + Z * Y * X, (int)Z, (int)Y, (int)X, (float)voxel_size, origin.data_ptr<float>(), (float)w_min,
+                                          reinterpret_cast<unsigned long long*>(count.data_ptr<int64_t>()), (long long)capacity,
+                                          capacity ? xyz.data_ptr<float>() : nullptr, capacity ? normal.data_ptr<float>() : nullptr,
+                                          capacity ? weight.data_ptr<float>() : nullptr,
+                                          capacity ? reinterpret_cast<long long*>(edge.data_ptr<int64_t>()) : nullptr, cur_stream()),
+                 "estd_tsdf_extract_points");
+    return {count, xyz, normal, weight, edge};
+}
+
 Tensor warp_attention(const Tensor& kv_target, at::TensorList kv_sources, const Tensor& mats, const Tensor& depth_values,
                       double depth_min, double depth_interval)
 {
@@ -763,6 +826,9 @@ TORCH_LIBRARY(estdepth_hip, m)
     m.def("cdhw_to_vol(Tensor src, Tensor(a!) dst, int dst_stride, int dst_off) -> ()");
     m.def("vol_to_cdhw(Tensor src, int C, int[] dims, int src_stride, int src_off) -> Tensor");
     m.def("camera_matrices_host(Tensor cam_poses, Tensor cam_intr, Tensor[] pre_poses, bool with_volume) -> (Tensor, Tensor)");
+    m.def("tsdf_integrate_(Tensor(a!) volume, Tensor[] depths, Tensor[] confs, Tensor mats, float trunc, float z_near, float conf_min, "
+          "bool weighted, float w_max, bool no_skip) -> Tensor(a!)");
+    m.def("tsdf_extract_points(Tensor volume, float voxel_size, Tensor origin, float w_min, int capacity) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("profile_mark(int id) -> ()");
     m.def("set_reserved_cus(int n) -> int");
     m.def("conv3d_grid(int N, int D, int H, int W) -> int");
@@ -807,6 +873,8 @@ TORCH_LIBRARY_IMPL(estdepth_hip, CUDA, m)
     m.impl("disp_head_nhwc", disp_head_nhwc);
     m.impl("cdhw_to_vol", cdhw_to_vol);
     m.impl("vol_to_cdhw", vol_to_cdhw);
+    m.impl("tsdf_integrate_", tsdf_integrate_);
+    m.impl("tsdf_extract_points", tsdf_extract_points);
 }
 
 TORCH_LIBRARY_IMPL(estdepth_hip, CPU, m)

@@ -999,3 +999,78 @@ def vol_to_cdhw(src, C, dims, src_stride, src_off):
     out = torch.empty((C, D, H, W), device=src.device, dtype=torch.float32)
     N.check(N.lib().estd_vol_to_cdhw(_p(src), _p(out), C, D * H * W, src_stride, src_off, _stream()), "estd_vol_to_cdhw")
     return out
+
+
+# ---------------------------------------------------------------------------------- TSDF fusion (csrc/tsdf.hip)
+TSDF_MAX_FRAMES = 8             # ESTD_TSDF_MAX_FRAMES (include/estd_hip.h)
+
+
+def _maps(ts, name, H, W):
+    for i, t in enumerate(ts):
+        _chk(t, "%s %d" % (name, i))
+        _need(t.dim() >= 2 and tuple(t.shape[-2:]) == (H, W) and t.numel() == H * W, "tsdf_integrate_: %s %d must be [%d,%d], got %s"
+              % (name, i, H, W, tuple(t.shape)))
+
+
+def tsdf_integrate_(volume, depths, confs, mats, trunc, z_near, conf_min, weighted, w_max, no_skip=False):
+    """In place on ``volume`` [2,Z,Y,X] (D plane, weight plane): fuse the depth maps ``depths`` (list of [H,W] device tensors, 1..8) with the
+    host matrices ``mats`` (CPU float32 [T,12], camera.tsdf_matrices) in one pass over the voxels; ``confs``: a list of the same length or
+    empty.  The contract is spelled out in include/estd_hip.h."""
+    depths, confs = list(depths), list(confs) if confs is not None else []
+    if _use_torch():
+        return T().tsdf_integrate_(volume, depths, confs, mats, float(trunc), float(z_near), float(conf_min), bool(weighted), float(w_max), bool(no_skip))
+    _need(isinstance(volume, torch.Tensor) and volume.dim() == 4 and volume.shape[0] == 2, "tsdf_integrate_: volume must be [2,Z,Y,X] (D plane, weight plane)")
+    _chk(volume, "volume")
+    Z, Y, X = volume.shape[1:]
+    _need(X % 4 == 0, "tsdf_integrate_: X must be a multiple of 4, got %d" % X)
+    n = len(depths)
+    _need(1 <= n <= TSDF_MAX_FRAMES, "tsdf_integrate_: 1..%d frames per call, got %d" % (TSDF_MAX_FRAMES, n))
+    _need(len(confs) in (0, n), "tsdf_integrate_: one confidence map per depth map (or none)")
+    _need(not weighted or confs, "tsdf_integrate_: weighted fusion needs confidence maps")
+    _need(isinstance(mats, torch.Tensor) and not mats.is_cuda and mats.dtype == torch.float32 and mats.is_contiguous() and mats.numel() == n * 12,
+          "tsdf_integrate_: mats must be a contiguous CPU float32 tensor [T,12]")
+    _need(isinstance(depths[0], torch.Tensor) and depths[0].dim() >= 2, "tsdf_integrate_: depth maps must be [H,W] (leading 1s allowed)")
+    H, W = depths[0].shape[-2:]
+    _maps(depths, "depth map", H, W)
+    _maps(confs, "confidence map", H, W)
+    for t in depths + confs:
+        _need(t.device == volume.device, "tsdf_integrate_: a map is on %s but the volume on %s" % (t.device, volume.device))
+    d = N.TsdfIntegrateDesc()
+    d.Z, d.Y, d.X, d.T, d.H, d.W = Z, Y, X, n, H, W
+    d.weighted, d.no_skip = int(bool(weighted)), int(bool(no_skip))
+    d.trunc, d.z_near, d.conf_min, d.w_max = float(trunc), float(z_near), float(conf_min), float(w_max)
+    d.tsdf, d.weight = volume.data_ptr(), volume.data_ptr() + 4 * Z * Y * X
+    flat = mats.reshape(-1).tolist()
+    for t in range(n):
+        d.depth[t] = depths[t].data_ptr()
+        d.conf[t] = confs[t].data_ptr() if confs else None
+        for i in range(12):
+            d.mats[t][i] = flat[t * 12 + i]
+    with torch.cuda.device(volume.device):
+        N.check(N.lib().estd_tsdf_integrate(ctypes.byref(d), _stream()), "estd_tsdf_integrate")
+    return volume
+
+
+def tsdf_extract_points(volume, voxel_size, origin, w_min, capacity):
+    """Zero crossings of ``volume`` [2,Z,Y,X] -> (count [1] int64 on the device: the TOTAL number of crossings, xyz [capacity,3],
+    normal [capacity,3], weight [capacity], edge [capacity] int64); ``capacity`` 0 counts only.  ``origin``: CPU float32 [3]."""
+    if _use_torch():
+        return T().tsdf_extract_points(volume, float(voxel_size), origin, float(w_min), int(capacity))
+    _need(isinstance(volume, torch.Tensor) and volume.dim() == 4 and volume.shape[0] == 2, "tsdf_extract_points: volume must be [2,Z,Y,X] (D plane, weight plane)")
+    _chk(volume, "volume")
+    Z, Y, X = volume.shape[1:]
+    _need(X % 4 == 0, "tsdf_extract_points: X must be a multiple of 4, got %d" % X)
+    _need(capacity >= 0, "tsdf_extract_points: capacity must not be negative")
+    _need(isinstance(origin, torch.Tensor) and not origin.is_cuda and origin.dtype == torch.float32 and origin.is_contiguous() and origin.numel() == 3,
+          "tsdf_extract_points: origin must be a contiguous CPU float32 tensor [3]")
+    dev = volume.device
+    with torch.cuda.device(dev):
+        count = torch.zeros(1, device=dev, dtype=torch.int64)
+        xyz, normal = torch.empty((capacity, 3), device=dev), torch.empty((capacity, 3), device=dev)
+        weight, edge = torch.empty(capacity, device=dev), torch.empty(capacity, device=dev, dtype=torch.int64)
+        org = (ctypes.c_float * 3)(*origin.tolist())
+        pp = (lambda t: _p(t)) if capacity else (lambda t: None)
+        N.check(N.lib().estd_tsdf_extract_points(_p(volume), ctypes.c_void_p(volume.data_ptr() + 4 * Z * Y * X), Z, Y, X, float(voxel_size), org,
+                                                 float(w_min), _p(count), int(capacity), pp(xyz), pp(normal), pp(weight), pp(edge), _stream()),
+                "estd_tsdf_extract_points")
+    return count, xyz, normal, weight, edge

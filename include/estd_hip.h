@@ -416,6 +416,55 @@ int estd_upsample2_cat_nhwc(const float* x, int Cx, const float* skip, int Cs, f
 int estd_disp_head_nhwc(const float* in, const float* w, const float* bias, float depth_max, float* out, int N, int H, int W,
                         int C, int upscale, estd_stream_t stream);
 
+/* ---- TSDF fusion of posed depth maps (csrc/tsdf.hip) --------------------------------------------
+ * The reference stops at per-frame .npy depth maps (eval_hybrid_seq.py:215-230); these two entry points accumulate the depth /
+ * confidence maps the model returns into a scene on the device (KinectFusion's truncated signed distance update) and read the
+ * surface back as an oriented point cloud.
+ *
+ * Volume: two fp32 planes of [Z][Y][X] voxels, x fastest: `tsdf` (D in [-1, 1]) and `weight` (Wt >= 0); all zeros = empty.  X must be
+ * a multiple of 4 (a lane moves four voxels = 16 bytes per access), else ESTD_ERR_ARG.  Offsets are 64-bit; Z <= 65535,
+ * Y <= 262140, X <= 2^20 (launch grids), beyond that ESTD_ERR_UNSUPPORTED.
+ *
+ * The integrate call fuses T frames (1..ESTD_TSDF_MAX_FRAMES) in ONE pass over the voxels.  mats[t] is the HOST 3x4 row-major matrix
+ * A = K [R|t]_world->camera V in fp32 (V: voxel index -> voxel centre origin + (idx + 0.5) voxel_size; estdepth_amd/camera.py
+ * tsdf_matrices forms it in float64).  Per voxel (ix, iy, iz), for each frame in order:
+ *   1. a = fma(A0, ix, fma(A1, iy, fma(A2, iz, A3))), b and c likewise from rows 1 and 2; skip if c <= z_near;
+ *   2. ui = floor(a / c + 0.5), vi = floor(b / c + 0.5) (pixel centres on integers); skip if outside [0, W) x [0, H);
+ *   3. d = depth[t][vi * W + ui]; skip unless finite and > 0;
+ *   4. with confidence maps: skip if conf < conf_min; w = conf (weighted; skip unless finite and > 0) else w = 1;
+ *   5. sdf = d - c; skip if sdf < -trunc; tsdf = min(1, sdf / trunc);
+ *   6. D = fma(D, Wt, tsdf * w) / (Wt + w); Wt = min(Wt + w, w_max).
+ * IEEE divisions throughout.  A 16-byte group of four voxels that no frame updates is neither read nor written. */
+#define ESTD_TSDF_MAX_FRAMES 8
+typedef struct estd_tsdf_integrate_desc {
+    int Z, Y, X;                                  /* volume dimensions */
+    int T;                                        /* frames in this call */
+    int H, W;                                     /* size of every depth / confidence map */
+    int weighted;                                 /* 1: w = conf (needs conf), 0: w = 1 */
+    int no_skip;                                  /* 1: measurement only -- every voxel is loaded and stored (tools/tsdf_bench.py) */
+    float trunc, z_near, conf_min, w_max;
+    float* tsdf;                                  /* [Z][Y][X] */
+    float* weight;                                /* [Z][Y][X] */
+    const float* depth[ESTD_TSDF_MAX_FRAMES];     /* [H][W] each */
+    const float* conf[ESTD_TSDF_MAX_FRAMES];      /* [H][W] each: all T set, or all NULL */
+    float mats[ESTD_TSDF_MAX_FRAMES][12];         /* host values, copied into the launch arguments */
+} estd_tsdf_integrate_desc;
+int estd_tsdf_integrate(const estd_tsdf_integrate_desc* desc, estd_stream_t stream);
+
+/* Zero crossings of the volume as points.  For every voxel with Wt >= w_min and each of its +x, +y, +z neighbours with Wt >= w_min:
+ * a point when D0 < 0 <= D1 or D1 < 0 <= D0, at s = D0 / (D0 - D1) along the edge:
+ *   xyz    = origin + (idx + 0.5 + s e_axis) voxel_size                      (fma(cell, voxel_size, origin) per coordinate)
+ *   normal = g / |g|, g = fma(s, g1 - g0, g0): g0, g1 the gradients of D at the two end voxels (per axis the central difference
+ *            0.5 (D+ - D-) where both neighbours exist with Wt >= w_min, the one-sided difference where one does, 0 where
+ *            neither); the zero vector when g = 0.  Points towards increasing D = the free space the cameras saw.
+ *   weight = fma(s, Wt1 - Wt0, Wt0);      edge = 3 * linear voxel index + axis (0 = x, 1 = y, 2 = z), exact.
+ * origin3 is a HOST pointer to three floats.  `counter` (device, zeroed by the caller) ends at the TOTAL number of crossings -- one
+ * increment per wave (lane ballots + population counts); records whose slot is >= capacity are dropped.  capacity == 0 counts only
+ * (the output pointers may then be NULL).  xyz, normal [capacity][3]; point_weight, edge [capacity].  Order unspecified. */
+int estd_tsdf_extract_points(const float* tsdf, const float* weight, int Z, int Y, int X, float voxel_size, const float* origin3,
+                             float w_min, unsigned long long* counter, long long capacity, float* xyz, float* normal,
+                             float* point_weight, long long* edge, estd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,7 @@ ground-truth depth.  Needs an MI355X (the model has no CPU path).
 
     python tools/run_stream.py --scene-dir /data/scannet/scene0707_00 --out /tmp/eval --loadckpt model.ckpt
     python tools/run_stream.py --synthetic 8 --out /tmp/eval          # self-contained demo on a generated scene
+    python tools/run_stream.py --synthetic 8 --out /tmp/eval --fuse /tmp/eval/scene.ply      # + TSDF fusion of every target, point cloud
 """
 import argparse
 import json
@@ -36,6 +37,10 @@ def main():
     ap.add_argument("--memory_size", type=int, default=2)
     ap.add_argument("--layout", choices=("scannet", "7scenes"), default="scannet")
     ap.add_argument("--no-feature-cache", action="store_true")
+    ap.add_argument("--fuse", metavar="PATH.ply", help="fuse every target's depth / fused_prob into a TSDF volume on the device "
+                                                       "(estdepth_amd.fusion3d) and write its surface points here")
+    ap.add_argument("--voxel-size", type=float, default=0.04)
+    ap.add_argument("--volume-dims", type=int, nargs=3, default=(256, 256, 256), metavar=("Z", "Y", "X"))
     args = ap.parse_args()
 
     from estdepth_amd import DepthNetHybrid, synth
@@ -74,6 +79,7 @@ def main():
     stream = ESTMStream(model, lwindow=args.lwindow, memory_size=args.memory_size,
                         cache_features=not args.no_feature_cache)
     errs, times, window, resized = RunningErrors(), [], [], 0
+    volume, fuse_ms = None, []
     for idx in range(len(reader)):
         s = reader[idx]
         window.append(s)
@@ -88,6 +94,20 @@ def main():
         times.append(time.time() - t0)
         outputs = res[0]
         target = window[args.lwindow // 2]                                   # eval_hybrid_seq.py:197
+        if args.fuse:
+            from estdepth_amd.fusion3d import TSDFVolume, frustum_volume
+            if volume is None:      # centred on the first camera's frustum between depth_min and depth_max
+                h, w = s["img"].shape[-2:]
+                origin = frustum_volume(window[0]["cam_pose"], s["cam_intr"], (h, w), args.depth_min, args.depth_max,
+                                        args.volume_dims, args.voxel_size)
+                volume = TSDFVolume(args.volume_dims, args.voxel_size, origin, device=dev)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            volume.integrate_outputs(outputs, torch.stack([f["cam_pose"].reshape(4, 4) for f in window])[None], s["cam_intr"].reshape(1, 3, 3),
+                                     image_hw=tuple(s["img"].shape[-2:]))
+            e1.record()
+            torch.cuda.synchronize()
+            fuse_ms.append(e0.elapsed_time(e1))
         save_window_outputs(outputs, args.out, target["img_path"])
         pred = outputs[("depth", 0, 0)][0, 0].cpu().numpy().astype(np.float64)
         gt = target["dmap"][0, 0].numpy().astype(np.float64)
@@ -103,6 +123,10 @@ def main():
     report = {"scene": scene_dir, "frames": len(reader), "windows": stream.windows,
               "mean_window_ms": 1e3 * float(np.mean(times[1:] or times or [0.0])), "errors": errs.mean(),
               "predictions_resized_to_gt_grid": resized}
+    if volume is not None:
+        os.makedirs(os.path.dirname(os.path.abspath(args.fuse)), exist_ok=True)
+        report.update(fused_voxels=volume.fused_voxels(), points=volume.save_ply(args.fuse),
+                      mean_fuse_ms=float(np.mean(fuse_ms[1:] or fuse_ms)))
     os.makedirs(args.out, exist_ok=True)
     with open(os.path.join(args.out, "metrics.json"), "w") as f:
         json.dump(report, f, indent=1)

@@ -1,0 +1,107 @@
+"""Stand-alone timing of csrc/tsdf.hip on an MI355X (device events, warm-up, many repetitions; not part of bench.py).
+
+    python tools/tsdf_bench.py [--reps 200] [--out profiles/tsdf_bench.txt]
+
+Three 640 x 480 depth maps of the analytic plane-plus-sphere scene of tests/tsdf_ref.py, fused into a 256^3 and a 512 x 512 x 256 volume at
+3 cm, each centred on the first camera's frustum between depth_min and depth_max the way tools/run_stream.py --fuse places it:
+  (a) one T = 3 integrate call               (b) three T = 1 calls on the same data (the plain design (a) exists to beat)
+  (c) (a) with the frustum skip compiled out (every voxel loaded and stored)          (d) the point extraction (count + records)
+For (a): bytes moved per voxel touched and the share of the 6.3 TB/s streaming rate an MI355X reaches (a roofline, not a pass bar), and the
+fuse time beside the 15 ms Joint step it follows.  A 1 GiB buffer is rewritten (untimed) in front of every timed call, so the volume is
+read from HBM as it is behind a model step, not from the Infinity Cache."""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+STREAM_BPS = 6.3e12          # achievable HBM streaming rate of an MI355X
+JOINT_STEP_MS = 15.5         # the Joint step a T = 3 fuse follows (README: 15.43-15.58 ms)
+
+
+def timed(fn, reps, flush=None, warmup=10):
+    """mean ms per call over ``reps`` calls, each between its own pair of device events; ``flush``: a buffer larger than the 256 MB
+    Infinity Cache that is rewritten (untimed) in front of every call, so the call finds the volume in HBM as it does behind a model step"""
+    for _ in range(warmup):
+        fn()
+    pairs = []
+    for i in range(reps):
+        if flush is not None:
+            flush.fill_(float(i))
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        pairs.append((e0, e1))
+    torch.cuda.synchronize()
+    return float(np.mean([a.elapsed_time(b) for a, b in pairs]))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--out")
+    args = ap.parse_args()
+    import tsdf_ref as R
+    from estdepth_amd import camera, ops
+    from estdepth_amd.fusion3d import TSDFVolume, frustum_volume
+    assert torch.cuda.is_available(), "tools/tsdf_bench.py needs a ROCm device"
+    dev = torch.device("cuda:0")
+    H, W, T, vox, dmin, dmax = 480, 640, 3, 0.03, 0.1, 10.0
+    K = R.intrinsics(H, W)
+    poses = R.scene_poses(T, seed=1)
+    depths = torch.from_numpy(np.stack([R.raycast_scene(P, K, H, W) for P in poses]).astype(np.float32)).to(dev)
+    dl = [depths[t] for t in range(T)]
+    flush = torch.empty(256 << 20, device=dev)          # 1 GiB
+    lines = ["tsdf_bench: %d x %d maps, T = %d, voxel %.3f m, %d repetitions per figure, %s" % (W, H, T, vox, args.reps, torch.cuda.get_device_name(0))]
+    for dims in ((256, 256, 256), (256, 512, 512)):
+        origin = frustum_volume(torch.from_numpy(poses[0]), torch.from_numpy(K), (H, W), dmin, dmax, dims, vox)
+        vol = TSDFVolume(dims, vox, origin, device=dev)
+        mats = camera.tsdf_matrices(torch.from_numpy(poses), torch.from_numpy(K), vol.origin, vox)
+        n_vox = dims[0] * dims[1] * dims[2]
+
+        def fuse(group, no_skip=False):
+            ops.tsdf_integrate_(vol.volume, dl[group], [], mats[group].contiguous(), vol.trunc, vol.z_near, 0.0, False, vol.w_max, no_skip)
+
+        # steady state of a stream: the volume already holds earlier frames of the same neighbourhood.  Which voxels a call reads and
+        # writes depends on the maps and matrices alone, not on the volume's state, so every repetition does the same work.
+        fuse(slice(0, T))
+        torch.cuda.synchronize()
+        touched = int((vol.volume[1] > 0).sum().item())
+        groups16 = int((vol.volume[1].reshape(-1, 4) > 0).any(1).sum().item())          # 16-byte groups the kernel reads and writes
+        t_a = timed(lambda: fuse(slice(0, T)), args.reps, flush)
+        t_b = timed(lambda: [fuse(slice(t, t + 1)) for t in range(T)], args.reps, flush)
+        t_c = timed(lambda: fuse(slice(0, T), no_skip=True), args.reps, flush)
+        t_a_warm = timed(lambda: fuse(slice(0, T)), args.reps)
+        pts = vol.extract_points()
+        t_d_count = timed(lambda: ops.tsdf_extract_points(vol.volume, vox, vol.origin, 1.0, 0), args.reps, flush)
+        t_d = timed(lambda: ops.tsdf_extract_points(vol.volume, vox, vol.origin, 1.0, pts["count"]), args.reps, flush)
+        vol_bytes = groups16 * 4 * 16.0                    # D and Wt groups, read and written once
+        map_bytes = T * H * W * 4.0
+        floor_ms = (vol_bytes + map_bytes) / STREAM_BPS * 1e3
+        lines += [
+            "volume %d x %d x %d (Z Y X), origin (%.2f, %.2f, %.2f): %d voxels, %d updated (%.1f %%), %d of %d 16-byte groups (%.1f %%)"
+            % (dims + origin + (n_vox, touched, 100.0 * touched / n_vox, groups16, n_vox // 4, 400.0 * groups16 / n_vox)),
+            "  (a) one T=3 call           %8.3f ms" % t_a,
+            "  (b) three T=1 calls        %8.3f ms   (a)/(b) = %.2f" % (t_b, t_a / t_b),
+            "  (c) (a) without the skip   %8.3f ms   (a)/(c) = %.2f" % (t_c, t_a / t_c),
+            "  (d) extraction             %8.3f ms count only, %.3f ms with %d records" % (t_d_count, t_d, pts["count"]),
+            "  (a) volume traffic %.1f MB = %.1f bytes per voxel touched (+ %.1f MB of depth maps); at %.1f TB/s that is %.3f ms: (a) runs at %.1f %% "
+            "of the streaming rate" % (vol_bytes / 1e6, vol_bytes / max(touched, 1), map_bytes / 1e6, STREAM_BPS / 1e12, floor_ms, 100.0 * floor_ms / t_a),
+            "  (a) beside the %.1f ms Joint step it follows: %.1f %% of the step" % (JOINT_STEP_MS, 100.0 * t_a / JOINT_STEP_MS),
+            "  (a) back to back, no cache flush between calls: %.3f ms" % t_a_warm,
+        ]
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        open(args.out, "w").write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
