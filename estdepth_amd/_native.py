@@ -84,6 +84,17 @@ class TsdfIntegrateDesc(ctypes.Structure):
     ]
 
 
+class TsdfRaycastDesc(ctypes.Structure):
+    """Mirror of struct estd_tsdf_raycast_desc (include/estd_hip.h)."""
+    _fields_ = [
+        ("Z", ctypes.c_int), ("Y", ctypes.c_int), ("X", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("n_steps", ctypes.c_int),
+        ("t_min", ctypes.c_float), ("dt", ctypes.c_float), ("w_min", ctypes.c_float),
+        ("tsdf", ctypes.c_void_p), ("weight", ctypes.c_void_p),
+        ("depth", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("out_weight", ctypes.c_void_p), ("stats", ctypes.c_void_p),
+        ("mat", ctypes.c_float * 12),
+    ]
+
+
 _SIGNATURES = {
     "estd_version": (ctypes.c_int, []),
     "estd_status_string": (ctypes.c_char_p, [ctypes.c_int]),
@@ -154,6 +165,7 @@ _SIGNATURES = {
     "estd_tsdf_extract_points": (ctypes.c_int, [c_float_p, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
                                                 ctypes.POINTER(ctypes.c_float), ctypes.c_float, ctypes.c_void_p, ctypes.c_longlong,
                                                 c_float_p, c_float_p, c_float_p, ctypes.c_void_p, c_stream]),
+    "estd_tsdf_raycast": (ctypes.c_int, [ctypes.POINTER(TsdfRaycastDesc), c_stream]),
 }
 
 # the superseded A/B kernels: exported only by a library built with ESTD_BUILD_AB=1 (estdepth_amd/build.py)

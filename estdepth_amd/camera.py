@@ -206,3 +206,21 @@ def tsdf_matrices(cam_poses, cam_intr, origin, voxel_size):
     for t in range(P.shape[0]):
         out[t] = ((K[t if K.shape[0] > 1 else 0] @ torch.inverse(P[t])[:3, :4]) @ V).reshape(-1).float()
     return out
+
+
+def tsdf_ray_matrix(cam_pose, cam_intr, origin, voxel_size):
+    """Pixel -> ray matrices of estd_tsdf_raycast, the inverse of ``tsdf_matrices``: M = [R K^-1 / voxel_size | (c - origin) / voxel_size - 0.5]
+    per view with R, c from the camera-to-world pose, so that M[:, :3] (u, v, 1) t + M[:, 3] is the voxel-index position (voxel i's centre
+    at i) of pixel (u, v) at z-depth t.  Formed in float64 on the host and rounded to fp32 -> CPU float32 [V,12] (3x4 row-major).
+    cam_pose [4,4] or [V,4,4], cam_intr [3,3] or [V,3,3] in pixels of the rendered image."""
+    P = cam_pose.detach().to(device="cpu", dtype=torch.float64).reshape(-1, 4, 4)
+    K = cam_intr.detach().to(device="cpu", dtype=torch.float64).reshape(-1, 3, 3)
+    if K.shape[0] not in (1, P.shape[0]):
+        raise RuntimeError("tsdf_ray_matrix: cam_intr must be [3,3] or one [3,3] per pose, got %s for %d poses" % (tuple(cam_intr.shape), P.shape[0]))
+    org = torch.as_tensor(origin, dtype=torch.float64).reshape(3)
+    out = torch.empty(P.shape[0], 12, dtype=torch.float32)
+    for t in range(P.shape[0]):
+        A = (P[t, :3, :3] @ torch.inverse(K[t if K.shape[0] > 1 else 0])) / float(voxel_size)
+        o = (P[t, :3, 3] - org) / float(voxel_size) - 0.5
+        out[t] = torch.cat([A, o[:, None]], 1).reshape(-1).float()
+    return out

@@ -17,6 +17,7 @@
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
 
+#include <cmath>
 #include <vector>
 
 #include "estd_hip.h"
@@ -399,6 +400,36 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> tsdf_extract_points(const Ten
                                           capacity ? reinterpret_cast<long long*>(edge.data_ptr<int64_t>()) : nullptr, cur_stream()),
                  "estd_tsdf_extract_points");
     return {count, xyz, normal, weight, edge};
+}
+
+// csrc/tsdf_raycast.hip: volume [2,Z,Y,X], mat: CPU float32 [12] (host values of the launch arguments) -> (depth [H,W], normal [H,W,3],
+// weight [H,W], stats: int32 [H,W,2] when asked for (measurement only), else [0])
+std::tuple<Tensor, Tensor, Tensor, Tensor> tsdf_raycast(const Tensor& volume, const Tensor& mat, int64_t H, int64_t W, double t_min, double dt,
+                                                        int64_t n_steps, double w_min, bool stats)
+{
+    const OpScope scope(volume);
+    TORCH_CHECK(volume.dim() == 4 && volume.size(0) == 2, "tsdf_raycast: volume must be [2,Z,Y,X] (D plane, weight plane)");
+    const float* vol = fptr(volume, "volume");
+    const int64_t Z = volume.size(1), Y = volume.size(2), X = volume.size(3);
+    TORCH_CHECK(X % 4 == 0, "tsdf_raycast: X must be a multiple of 4, got ", X);
+    TORCH_CHECK(mat.defined() && mat.device().is_cpu() && mat.scalar_type() == at::kFloat && mat.is_contiguous() && mat.numel() == 12,
+                "tsdf_raycast: mat must be a contiguous CPU float32 tensor [12] (3x4 row-major)");
+    TORCH_CHECK(H > 0 && W > 0 && H * W <= 0x7fffffffLL, "tsdf_raycast: the image size must be positive (and H * W < 2^31), got ", H, " x ", W);
+    TORCH_CHECK(n_steps > 0 && n_steps <= (1 << 24), "tsdf_raycast: n_steps must be in 1..2^24, got ", n_steps);
+    TORCH_CHECK(std::isfinite(dt) && (float)dt > 0.f, "tsdf_raycast: dt must be positive and finite, got ", dt);
+    TORCH_CHECK(std::isfinite(t_min) && t_min >= 0, "tsdf_raycast: t_min must be finite and not negative, got ", t_min);
+    TORCH_CHECK(w_min == w_min, "tsdf_raycast: w_min must not be NaN");
+    Tensor depth = new_f32({H, W}, volume), normal = new_f32({H, W, 3}, volume), weight = new_f32({H, W}, volume);
+    Tensor st = at::empty({stats ? H : 0, stats ? W : 0, stats ? 2 : 0}, volume.options().dtype(at::kInt));
+    estd_tsdf_raycast_desc d{};
+    d.Z = (int)Z; d.Y = (int)Y; d.X = (int)X; d.H = (int)H; d.W = (int)W; d.n_steps = (int)n_steps;
+    d.t_min = (float)t_min; d.dt = (float)dt; d.w_min = (float)w_min;
+    d.tsdf = vol; d.weight = vol + Z * Y * X;
+    d.depth = depth.data_ptr<float>(); d.normal = normal.data_ptr<float>(); d.out_weight = weight.data_ptr<float>();
+    d.stats = stats ? reinterpret_cast<unsigned int*>(st.data_ptr<int32_t>()) : nullptr;
+    for (int i = 0; i < 12; ++i) d.mat[i] = mat.data_ptr<float>()[i];
+    check_status(estd_tsdf_raycast(&d, cur_stream()), "estd_tsdf_raycast");
+    return {depth, normal, weight, st};
 }
 
 Tensor warp_attention(const Tensor& kv_target, at::TensorList kv_sources, const Tensor& mats, const Tensor& depth_values,
@@ -829,6 +860,8 @@ TORCH_LIBRARY(estdepth_hip, m)
     m.def("tsdf_integrate_(Tensor(a!) volume, Tensor[] depths, Tensor[] confs, Tensor mats, float trunc, float z_near, float conf_min, "
           "bool weighted, float w_max, bool no_skip) -> Tensor(a!)");
     m.def("tsdf_extract_points(Tensor volume, float voxel_size, Tensor origin, float w_min, int capacity) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("tsdf_raycast(Tensor volume, Tensor mat, int H, int W, float t_min, float dt, int n_steps, float w_min, bool stats) -> "
+          "(Tensor, Tensor, Tensor, Tensor)");
     m.def("profile_mark(int id) -> ()");
     m.def("set_reserved_cus(int n) -> int");
     m.def("conv3d_grid(int N, int D, int H, int W) -> int");
@@ -875,6 +908,7 @@ TORCH_LIBRARY_IMPL(estdepth_hip, CUDA, m)
     m.impl("vol_to_cdhw", vol_to_cdhw);
     m.impl("tsdf_integrate_", tsdf_integrate_);
     m.impl("tsdf_extract_points", tsdf_extract_points);
+    m.impl("tsdf_raycast", tsdf_raycast);
 }
 
 TORCH_LIBRARY_IMPL(estdepth_hip, CPU, m)

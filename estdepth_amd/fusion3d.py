@@ -1,5 +1,5 @@
 """Volumetric fusion of the model's depth maps on the device: a truncated signed distance (TSDF) volume as in KinectFusion, fed with the
-``("depth", t, s)`` / ``("fused_prob", t)`` maps ``DepthNetHybrid.forward`` returns, and read back as an oriented point cloud.
+``("depth", t, s)`` / ``("fused_prob", t)`` maps ``DepthNetHybrid.forward`` returns, and read back as an oriented point cloud or as depth / normal / weight maps ray-cast from any camera.
 
     vol = TSDFVolume(dims=(256, 256, 256), voxel_size=0.03, origin=(-3.8, -3.8, 0.0), device="cuda:0")
     stream = JointStream(model, seq_len=5, graph=True)
@@ -7,6 +7,7 @@
         outputs, _, _ = stream.push_clip(clip.imgs, clip.poses, K)
         vol.integrate_outputs(outputs, clip.poses[None], K[None], conf_min=0.3)
     vol.save_ply("scene.ply")
+    maps = vol.render(pose, K, (H, W))                              # depth / normal / weight of the fused surface in any camera
 
 Which frames are fused: target ``t`` of a call is frame ``t + 1`` of its ``cam_poses``.  ``JointStream`` clips advance by ``seq_len - 2`` frames
 and their targets are the INNER frames 1 .. seq_len - 2, so consecutive clips hand over disjoint targets and no frame is fused twice;
@@ -14,10 +15,12 @@ and their targets are the INNER frames 1 .. seq_len - 2, so consecutive clips ha
 what they return to ``integrate_outputs`` together with the poses of the same window / clip.
 
 The volume is one float32 tensor ``[2, Z, Y, X]`` (plane 0 = D in [-1, 1], plane 1 = weight; x fastest; zeros = empty); voxel ``(ix, iy, iz)`` has
-its centre at ``origin + (idx + 0.5) * voxel_size``.  All arithmetic is csrc/tsdf.hip's (the contract: include/estd_hip.h); there is no CPU
+its centre at ``origin + (idx + 0.5) * voxel_size``.  All arithmetic is csrc/tsdf.hip's and csrc/tsdf_raycast.hip's (the contract: include/estd_hip.h); there is no CPU
 path.  ``integrate`` only READS the maps, on the current stream -- the static output buffers of ``GraphedForward(clone_outputs=False)`` can
 be passed as they are, before the next forward overwrites them.
 """
+import math
+
 import torch
 
 from . import camera, ops
@@ -146,6 +149,21 @@ class TSDFVolume:
         n = min(total, int(capacity))
         return {"xyz": xyz[:n], "normal": normal[:n], "weight": weight[:n], "edge": edge[:n], "count": total}
 
+    def render(self, cam_pose, cam_intr, image_hw, depth_min=None, depth_max=None, step=None, w_min=1.0):
+        """The fused surface as the camera ``cam_pose`` [4,4] (camera-to-world) with ``cam_intr`` [3,3] (pixels of an ``image_hw`` = (H, W)
+        image) sees it -> dict(depth [H,W], normal [H,W,3], weight [H,W]) on the device: z-depth along the optical axis with pixel centres
+        on integers (the convention of the model's depth maps, so a render can be scored or fused again as it is), the unit normal in
+        world axes towards the cameras that saw the surface, and the interpolated fusion weight; all zeros where a ray finds no surface
+        between voxels of weight >= ``w_min``.  A pose stack [V,4,4] (``cam_intr`` [3,3] or [V,3,3]) renders V views: leading dimension V.
+        Rays are sampled every ``step`` metres of z-depth (default: one voxel) from ``depth_min`` (default: the volume's ``z_near``) to
+        ``depth_max`` (default: past the farthest corner of the volume, per view).  The contract: include/estd_hip.h, estd_tsdf_raycast."""
+        mats, (H, W), t_min, dt, n_steps, stacked = render_plan(self.dims, self.voxel_size, self.origin, self.z_near, cam_pose, cam_intr, image_hw,
+                                                                depth_min, depth_max, step, w_min)
+        views = [ops.tsdf_raycast(self.volume, mats[i].contiguous(), H, W, t_min, dt, n_steps[i], w_min) for i in range(mats.shape[0])]
+        if not stacked:
+            return dict(zip(("depth", "normal", "weight"), views[0]))
+        return {name: torch.stack([v[j] for v in views]) for j, name in enumerate(("depth", "normal", "weight"))}
+
     def fused_voxels(self):
         """voxels some frame has updated"""
         return int((self.volume[1] > 0).sum().item())
@@ -162,6 +180,48 @@ class TSDFVolume:
         self.volume.zero_()
         self.frames = 0
         return self
+
+
+def render_plan(dims, voxel_size, origin, z_near, cam_pose, cam_intr, image_hw, depth_min=None, depth_max=None, step=None, w_min=1.0):
+    """The argument checks and the host arithmetic of ``TSDFVolume.render`` (no device needed) -> (mats CPU float32 [V,12], (H, W), t_min,
+    dt, [n_steps per view], stacked): ``depth_max=None`` marches each view to the z-depth of the volume's farthest corner in that camera,
+    beyond which no ray is inside the volume."""
+    if not isinstance(cam_pose, torch.Tensor) or cam_pose.dim() not in (2, 3) or tuple(cam_pose.shape[-2:]) != (4, 4):
+        raise RuntimeError("render: cam_pose must be [4,4] or [V,4,4], got %s" % (tuple(getattr(cam_pose, "shape", ())),))
+    stacked = cam_pose.dim() == 3
+    n = cam_pose.shape[0] if stacked else 1
+    if n < 1:
+        raise RuntimeError("render: at least one pose")
+    if not isinstance(cam_intr, torch.Tensor) or cam_intr.numel() not in (9, 9 * n) or tuple(cam_intr.shape[-2:]) != (3, 3):
+        raise RuntimeError("render: cam_intr must be [3,3] or [V,3,3], got %s" % (tuple(getattr(cam_intr, "shape", ())),))
+    if len(tuple(image_hw)) != 2 or int(image_hw[0]) <= 0 or int(image_hw[1]) <= 0:
+        raise RuntimeError("render: image_hw must be two positive sizes (H, W), got %r" % (image_hw,))
+    H, W = int(image_hw[0]), int(image_hw[1])
+    t_min = float(z_near if depth_min is None else depth_min)
+    dt = float(voxel_size if step is None else step)
+    if not (t_min >= 0 and t_min < float("inf")):
+        raise RuntimeError("render: depth_min must be finite and not negative, got %r" % (depth_min,))
+    if not (dt > 0 and dt < float("inf")):
+        raise RuntimeError("render: step must be positive and finite, got %r" % (step,))
+    if depth_max is not None and not (float(depth_max) > t_min and float(depth_max) < float("inf")):
+        raise RuntimeError("render: depth_max must be finite and beyond depth_min = %g, got %r" % (t_min, depth_max))
+    if not float(w_min) == float(w_min):
+        raise RuntimeError("render: w_min must not be NaN")
+    mats = camera.tsdf_ray_matrix(cam_pose, cam_intr, origin, voxel_size)
+    if not bool(torch.isfinite(mats).all()):
+        raise RuntimeError("render: the poses / intrinsics give a matrix that is not finite")
+    P = cam_pose.detach().to("cpu", torch.float64).reshape(-1, 4, 4)
+    org = torch.as_tensor(origin, dtype=torch.float64).reshape(3)
+    ext = float(voxel_size) * torch.tensor([dims[2], dims[1], dims[0]], dtype=torch.float64)
+    corners = torch.stack([org + ext * torch.tensor([i, j, k], dtype=torch.float64) for i in (0, 1) for j in (0, 1) for k in (0, 1)])
+    n_steps = []
+    for t in range(n):
+        far = float(depth_max) if depth_max is not None else float(((corners - P[t, :3, 3]) @ P[t, :3, 2]).max())
+        k = int(math.ceil(max(far - t_min, 0.0) / dt)) + 1
+        if k > 1 << 24:
+            raise RuntimeError("render: %d samples per ray (at most 2^24): step %g is too small for the range %g .. %g" % (k, dt, t_min, far))
+        n_steps.append(k)
+    return mats, (H, W), t_min, dt, n_steps, stacked
 
 
 def write_ply(path, xyz_normal):

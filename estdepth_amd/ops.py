@@ -3,6 +3,7 @@ the arithmetic is libestd_hip.so's).  Every function enqueues on the current HIP
 returns tensors owned by the caching allocator.  CUDA(ROCm)-only: CPU tensors raise RuntimeError.
 """
 import ctypes
+import math
 import os
 
 import torch
@@ -1074,3 +1075,39 @@ def tsdf_extract_points(volume, voxel_size, origin, w_min, capacity):
                                                  float(w_min), _p(count), int(capacity), pp(xyz), pp(normal), pp(weight), pp(edge), _stream()),
                 "estd_tsdf_extract_points")
     return count, xyz, normal, weight, edge
+
+
+def tsdf_raycast(volume, mat, H, W, t_min, dt, n_steps, w_min, stats=False):
+    """Ray-cast ``volume`` [2,Z,Y,X] with the host matrix ``mat`` (CPU float32 [12], camera.tsdf_ray_matrix): ``n_steps`` samples per pixel at
+    z-depths t_min + k dt -> (depth [H,W], normal [H,W,3], weight [H,W]) on the volume's device; zeros where a ray finds no surface.
+    ``stats=True`` (measurement only) appends an int32 [H,W,2] tensor: samples whose weights / whose D values were read.  The contract
+    is spelled out in include/estd_hip.h (csrc/tsdf_raycast.hip)."""
+    H, W, n_steps, t_min, dt, w_min = int(H), int(W), int(n_steps), float(t_min), float(dt), float(w_min)
+    if _use_torch():
+        depth, normal, weight, st = T().tsdf_raycast(volume, mat, H, W, t_min, dt, n_steps, w_min, bool(stats))
+        return (depth, normal, weight, st) if stats else (depth, normal, weight)
+    _need(isinstance(volume, torch.Tensor) and volume.dim() == 4 and volume.shape[0] == 2, "tsdf_raycast: volume must be [2,Z,Y,X] (D plane, weight plane)")
+    _chk(volume, "volume")
+    Z, Y, X = volume.shape[1:]
+    _need(X % 4 == 0, "tsdf_raycast: X must be a multiple of 4, got %d" % X)
+    _need(isinstance(mat, torch.Tensor) and not mat.is_cuda and mat.dtype == torch.float32 and mat.is_contiguous() and mat.numel() == 12,
+          "tsdf_raycast: mat must be a contiguous CPU float32 tensor [12] (3x4 row-major)")
+    _need(H > 0 and W > 0 and H * W <= 0x7fffffff, "tsdf_raycast: the image size must be positive (and H * W < 2^31), got %d x %d" % (H, W))
+    _need(0 < n_steps <= 1 << 24, "tsdf_raycast: n_steps must be in 1..2^24, got %d" % n_steps)
+    _need(math.isfinite(dt) and ctypes.c_float(dt).value > 0, "tsdf_raycast: dt must be positive and finite, got %r" % dt)
+    _need(math.isfinite(t_min) and t_min >= 0, "tsdf_raycast: t_min must be finite and not negative, got %r" % t_min)
+    _need(w_min == w_min, "tsdf_raycast: w_min must not be NaN")
+    dev = volume.device
+    with torch.cuda.device(dev):
+        depth, normal, weight = torch.empty((H, W), device=dev), torch.empty((H, W, 3), device=dev), torch.empty((H, W), device=dev)
+        st = torch.empty((H, W, 2), device=dev, dtype=torch.int32) if stats else None
+        d = N.TsdfRaycastDesc()
+        d.Z, d.Y, d.X, d.H, d.W, d.n_steps = Z, Y, X, H, W, n_steps
+        d.t_min, d.dt, d.w_min = t_min, dt, w_min
+        d.tsdf, d.weight = volume.data_ptr(), volume.data_ptr() + 4 * Z * Y * X
+        d.depth, d.normal, d.out_weight = depth.data_ptr(), normal.data_ptr(), weight.data_ptr()
+        d.stats = st.data_ptr() if stats else None
+        for i, v in enumerate(mat.reshape(-1).tolist()):
+            d.mat[i] = v
+        N.check(N.lib().estd_tsdf_raycast(ctypes.byref(d), _stream()), "estd_tsdf_raycast")
+    return (depth, normal, weight, st) if stats else (depth, normal, weight)

@@ -465,6 +465,49 @@ int estd_tsdf_extract_points(const float* tsdf, const float* weight, int Z, int 
                              float w_min, unsigned long long* counter, long long capacity, float* xyz, float* normal,
                              float* point_weight, long long* edge, estd_stream_t stream);
 
+/* Depth, normal and weight maps of the volume as a pinhole camera sees it (csrc/tsdf_raycast.hip; KinectFusion's surface prediction).
+ * Depth is the z-depth along the optical axis with pixel centres on integers: the convention of the model's depth maps and of
+ * estd_tsdf_integrate's c, so a rendered map can be scored against ground truth or fused again as it is.
+ *
+ * mat is the HOST 3x4 row-major matrix M = [ R K^-1 / voxel_size | (c - origin) / voxel_size - 0.5 ] in fp32 (R, c from the
+ * camera-to-world pose; rows = x, y, z in voxel-index coordinates, where voxel i's centre is at i; estdepth_amd/camera.py
+ * tsdf_ray_matrix forms it in float64).  Per pixel (u, v):
+ *   1. r_j = fma(M[j][0], u, fma(M[j][1], v, M[j][2])); sample k = 0 .. n_steps - 1 at t_k = fma(k, dt, t_min) (never an accumulated
+ *      sum), position p_j = fma(t_k, r_j, M[j][3]);
+ *   2. cell i_j = floor(p_j), f_j = p_j - i_j; the sample is OBSERVED iff 0 <= i_j <= dim_j - 2 on all three axes and all eight corner
+ *      weights are >= w_min.  With lerp(a, b, f) = fma(f, b - a, a) and D_xyz the corner values (x, y, z offsets 0 / 1):
+ *        c_yz = lerp(D_0yz, D_1yz, f_x);  c_z = lerp(c_0z, c_1z, f_y);  F = lerp(c_0, c_1, f_z);  Wb = the same blend of the weights;
+ *        G_x = lerp(lerp(D_100 - D_000, D_110 - D_010, f_y), lerp(D_101 - D_001, D_111 - D_011, f_y), f_z),
+ *        G_y = lerp(c_10 - c_00, c_11 - c_01, f_z),  G_z = c_1 - c_0           (the gradient of the trilinear interpolant, per voxel);
+ *   3. hit = the first k >= 1 with samples k - 1 and k both observed and F_{k-1} > 0 >= F_k (front faces only: a ray that starts behind
+ *      a surface does not hit until it finds such a pair).  s = F_{k-1} / (F_{k-1} - F_k);
+ *        depth  = fma(dt, s, t_{k-1});
+ *        normal = g / |g|, g_j = fma(s, G_k,j - G_{k-1},j, G_{k-1},j), |g| = sqrt(fma(g_z, g_z, fma(g_y, g_y, g_x g_x))): world axes,
+ *                 towards increasing D = the free space the cameras saw (as estd_tsdf_extract_points); the zero vector when |g| = 0;
+ *        weight = fma(s, Wb_k - Wb_{k-1}, Wb_{k-1});
+ *   4. no hit: depth = weight = 0, normal = (0, 0, 0).  Every output pixel is written by every call.
+ * IEEE divisions and square root, no atomics: two calls give the same bits.  The kernel may skip samples it can prove unobserved (a
+ * ray / box slab test with a conservative margin, a weight probe in front of the D gathers); the result does not depend on it.
+ * ESTD_ERR_ARG: null pointers (stats excepted), H, W or n_steps <= 0, dt not finite or <= 0, t_min negative or not finite, w_min or an
+ * element of mat not finite / NaN, X % 4, a dimension <= 0.  ESTD_ERR_UNSUPPORTED: the volume limits above, H * W >= 2^31,
+ * n_steps > 2^24 (k is exact in fp32 up to there). */
+typedef struct estd_tsdf_raycast_desc {
+    int Z, Y, X;                                  /* volume dimensions */
+    int H, W;                                     /* size of the output maps */
+    int n_steps;                                  /* samples per ray */
+    float t_min, dt;                              /* z-depth of sample 0 and the step, in the units of voxel_size */
+    float w_min;                                  /* a corner counts as observed from this weight */
+    const float* tsdf;                            /* [Z][Y][X] */
+    const float* weight;                          /* [Z][Y][X] */
+    float* depth;                                 /* [H][W] */
+    float* normal;                                /* [H][W][3] */
+    float* out_weight;                            /* [H][W] */
+    unsigned int* stats;                          /* NULL, or measurement only (tools/tsdf_bench.py) [H][W][2]: samples whose weights
+                                                     were read, samples whose D values were read */
+    float mat[12];                                /* host values, copied into the launch arguments */
+} estd_tsdf_raycast_desc;
+int estd_tsdf_raycast(const estd_tsdf_raycast_desc* desc, estd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

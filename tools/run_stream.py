@@ -7,6 +7,9 @@ ground-truth depth.  Needs an MI355X (the model has no CPU path).
     python tools/run_stream.py --scene-dir /data/scannet/scene0707_00 --out /tmp/eval --loadckpt model.ckpt
     python tools/run_stream.py --synthetic 8 --out /tmp/eval          # self-contained demo on a generated scene
     python tools/run_stream.py --synthetic 8 --out /tmp/eval --fuse /tmp/eval/scene.ply      # + TSDF fusion of every target, point cloud
+    python tools/run_stream.py --synthetic 8 --out /tmp/eval --fuse /tmp/eval/scene.ply --render-fused
+        # + the fused volume ray-cast at every target's pose (TSDFVolume.render): <out>/fused_depth/*.npy beside refined_depth/ (float16,
+        # same layout) and the fused depth scored against the same ground truth (errors_fused, fused_coverage, errors_on_covered)
 """
 import argparse
 import json
@@ -39,9 +42,13 @@ def main():
     ap.add_argument("--no-feature-cache", action="store_true")
     ap.add_argument("--fuse", metavar="PATH.ply", help="fuse every target's depth / fused_prob into a TSDF volume on the device "
                                                        "(estdepth_amd.fusion3d) and write its surface points here")
+    ap.add_argument("--render-fused", action="store_true", help="with --fuse: after the stream, render the volume at every target's pose, "
+                    "write the fused depth maps to <out>/fused_depth and score them against the ground truth")
     ap.add_argument("--voxel-size", type=float, default=0.04)
     ap.add_argument("--volume-dims", type=int, nargs=3, default=(256, 256, 256), metavar=("Z", "Y", "X"))
     args = ap.parse_args()
+    if args.render_fused and not args.fuse:
+        ap.error("--render-fused needs --fuse PATH.ply")
 
     from estdepth_amd import DepthNetHybrid, synth
     from estdepth_amd.streaming import ESTMStream
@@ -79,7 +86,13 @@ def main():
     stream = ESTMStream(model, lwindow=args.lwindow, memory_size=args.memory_size,
                         cache_features=not args.no_feature_cache)
     errs, times, window, resized = RunningErrors(), [], [], 0
-    volume, fuse_ms = None, []
+    volume, fuse_ms, targets = None, [], []
+
+    def to_gt_grid(a, shape):
+        """nearest neighbour on pixel centres: a map at the network's resolution on the ground truth's pixel grid (no new depth values)"""
+        ys = np.minimum(((np.arange(shape[0]) + 0.5) * a.shape[0] / shape[0]).astype(np.int64), a.shape[0] - 1)
+        xs = np.minimum(((np.arange(shape[1]) + 0.5) * a.shape[1] / shape[1]).astype(np.int64), a.shape[1] - 1)
+        return a[ys][:, xs]
     for idx in range(len(reader)):
         s = reader[idx]
         window.append(s)
@@ -115,11 +128,11 @@ def main():
             # the ground-truth depth stays at native resolution (general_eval_seq.py:191) while the network runs at
             # --image-size: bring the PREDICTION to the ground-truth grid (nearest neighbour on pixel centres, no new
             # depth values are invented) instead of silently skipping the frame
-            ys = np.minimum(((np.arange(gt.shape[0]) + 0.5) * pred.shape[0] / gt.shape[0]).astype(np.int64), pred.shape[0] - 1)
-            xs = np.minimum(((np.arange(gt.shape[1]) + 0.5) * pred.shape[1] / gt.shape[1]).astype(np.int64), pred.shape[1] - 1)
-            pred = pred[ys][:, xs]
+            pred = to_gt_grid(pred, gt.shape)
             resized += 1
         errs.add(pred, gt)
+        if args.render_fused:
+            targets.append((target["img_path"], target["cam_pose"].reshape(4, 4), s["cam_intr"].reshape(3, 3), tuple(s["img"].shape[-2:]), pred, gt))
     report = {"scene": scene_dir, "frames": len(reader), "windows": stream.windows,
               "mean_window_ms": 1e3 * float(np.mean(times[1:] or times or [0.0])), "errors": errs.mean(),
               "predictions_resized_to_gt_grid": resized}
@@ -127,6 +140,30 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(args.fuse)), exist_ok=True)
         report.update(fused_voxels=volume.fused_voxels(), points=volume.save_ply(args.fuse),
                       mean_fuse_ms=float(np.mean(fuse_ms[1:] or fuse_ms)))
+    if volume is not None and args.render_fused:
+        # the fused model in every target's camera, on the pixel grid and in the units of the per-frame predictions
+        from estdepth_amd.metrics import compute_valid_depth_mask
+        errs_fused, errs_covered, n_gt, n_covered, render_ms = RunningErrors(), RunningErrors(), 0, 0, []
+        out_dir = os.path.join(args.out, "fused_depth")
+        os.makedirs(out_dir, exist_ok=True)
+        for img_path, pose, intr, hw, pred, gt in targets:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            maps = volume.render(pose, intr, hw, depth_min=args.depth_min, depth_max=args.depth_max)
+            e1.record()
+            torch.cuda.synchronize()
+            render_ms.append(e0.elapsed_time(e1))
+            fused = maps["depth"].cpu().numpy()
+            np.save(os.path.join(out_dir, os.path.splitext(os.path.basename(img_path))[0] + ".npy"), np.float16(fused[None]))
+            fused = to_gt_grid(fused.astype(np.float64), gt.shape)
+            gt_ok = compute_valid_depth_mask(gt)
+            both = gt_ok & compute_valid_depth_mask(fused) & compute_valid_depth_mask(pred)        # ONE pixel set for both scores
+            n_gt += int(gt_ok.sum())
+            n_covered += int((gt_ok & (fused > 0)).sum())
+            errs_fused.add(np.where(both, fused, 0.0), gt)
+            errs_covered.add(np.where(both, pred, 0.0), gt)
+        report.update(errors_fused=errs_fused.mean(), fused_coverage=n_covered / max(n_gt, 1), errors_on_covered=errs_covered.mean(),
+                      mean_render_ms=float(np.mean(render_ms[1:] or render_ms or [0.0])))
     os.makedirs(args.out, exist_ok=True)
     with open(os.path.join(args.out, "metrics.json"), "w") as f:
         json.dump(report, f, indent=1)

@@ -8,7 +8,13 @@ Three 640 x 480 depth maps of the analytic plane-plus-sphere scene of tests/tsdf
   (c) (a) with the frustum skip compiled out (every voxel loaded and stored)          (d) the point extraction (count + records)
 For (a): bytes moved per voxel touched and the share of the 6.3 TB/s streaming rate an MI355X reaches (a roofline, not a pass bar), and the
 fuse time beside the 15 ms Joint step it follows.  A 1 GiB buffer is rewritten (untimed) in front of every timed call, so the volume is
-read from HBM as it is behind a model step, not from the Infinity Cache."""
+read from HBM as it is behind a model step, not from the Infinity Cache.
+
+    python tools/tsdf_bench.py --raycast [--reps 200] [--out profiles/tsdf_raycast_bench.txt]
+
+times csrc/tsdf_raycast.hip instead: one 640 x 480 render (TSDFVolume.render, default range and step) of the 256^3 volume above after the
+T = 3 fuse, from the first fused camera and from the held-out pose of tests/tsdf_raycast_ref.py, with the kernel's own counters (samples
+whose weights / whose D values were read per ray), beside the fuse + extract pass and the Joint step."""
 import argparse
 import os
 import sys
@@ -46,7 +52,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--out")
+    ap.add_argument("--raycast", action="store_true", help="time the ray caster (csrc/tsdf_raycast.hip) instead of integrate / extract")
     args = ap.parse_args()
+    if args.raycast:
+        return raycast_main(args)
     import tsdf_ref as R
     from estdepth_amd import camera, ops
     from estdepth_amd.fusion3d import TSDFVolume, frustum_volume
@@ -95,6 +104,57 @@ def main():
             "of the streaming rate" % (vol_bytes / 1e6, vol_bytes / max(touched, 1), map_bytes / 1e6, STREAM_BPS / 1e12, floor_ms, 100.0 * floor_ms / t_a),
             "  (a) beside the %.1f ms Joint step it follows: %.1f %% of the step" % (JOINT_STEP_MS, 100.0 * t_a / JOINT_STEP_MS),
             "  (a) back to back, no cache flush between calls: %.3f ms" % t_a_warm,
+        ]
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        open(args.out, "w").write(text + "\n")
+
+
+def raycast_main(args):
+    import tsdf_ref as R
+    import tsdf_raycast_ref as RR
+    from estdepth_amd import ops
+    from estdepth_amd.fusion3d import TSDFVolume, frustum_volume, render_plan
+    assert torch.cuda.is_available(), "tools/tsdf_bench.py needs a ROCm device"
+    dev = torch.device("cuda:0")
+    H, W, T, vox, dmin, dmax, dims = 480, 640, 3, 0.03, 0.1, 10.0, (256, 256, 256)
+    K = R.intrinsics(H, W)
+    poses = R.scene_poses(T, seed=1)
+    depths = torch.from_numpy(np.stack([R.raycast_scene(P, K, H, W) for P in poses]).astype(np.float32)).to(dev)
+    origin = frustum_volume(torch.from_numpy(poses[0]), torch.from_numpy(K), (H, W), dmin, dmax, dims, vox)
+    vol = TSDFVolume(dims, vox, origin, device=dev)
+    vol.integrate(depths, torch.from_numpy(poses), torch.from_numpy(K))
+    flush = torch.empty(256 << 20, device=dev)          # 1 GiB
+    reps = max(args.reps, 100)
+    lines = ["tsdf_bench --raycast: one %d x %d render of the %d x %d x %d volume (voxel %.3f m, origin (%.2f, %.2f, %.2f), T = %d fused), "
+             "%d repetitions per figure after 10 warm-up calls, %s" % ((W, H) + dims + (vox,) + origin + (T, reps, torch.cuda.get_device_name(0)))]
+    fuse_extract_ms = 0.15 + 0.05                       # profiles/tsdf_bench.txt: (a) + (d) of this volume
+    for label, pose in (("first fused camera", poses[0]), ("held-out pose", RR.HELD_OUT_POSE)):
+        mats, _, t_min, dt, n_steps, _ = render_plan(vol.dims, vox, vol.origin, vol.z_near, torch.from_numpy(pose), torch.from_numpy(K), (H, W))
+        mat = mats[0].contiguous()
+
+        def cast(stats=False):
+            return ops.tsdf_raycast(vol.volume, mat, H, W, t_min, dt, n_steps[0], 1.0, stats)
+        depth, _, _, st = cast(stats=True)
+        torch.cuda.synchronize()
+        st = st.cpu().numpy().astype(np.int64)
+        probed, gathered = st[..., 0], st[..., 1]
+        hit = int((depth > 0).sum().item())
+        t_cold = timed(cast, reps, flush)
+        t_warm = timed(cast, reps)
+        bytes_ray = 32.0 * (probed + gathered)
+        lines += [
+            "%s: t = %.3f .. %.2f m in %d steps of %.3f m, %d of %d pixels hit" % (label, t_min, t_min + (n_steps[0] - 1) * dt, n_steps[0], dt, hit, H * W),
+            "  render, volume in HBM (1 GiB rewritten before every call)   %8.3f ms" % t_cold,
+            "  render, back to back                                        %8.3f ms" % t_warm,
+            "  samples per ray whose weights were read: mean %.1f, max %d of %d; whose D values were read: mean %.1f, max %d"
+            % (probed.mean(), probed.max(), n_steps[0], gathered.mean(), gathered.max()),
+            "  gathered bytes per ray: mean %.0f, max %d (8 x 4 bytes per weight probe + 8 x 4 per D gather); %.1f MB per render, %.2f TB/s of "
+            "gathers back to back" % (bytes_ray.mean(), bytes_ray.max(), bytes_ray.sum() / 1e6, bytes_ray.sum() / (t_warm * 1e-3) / 1e12),
+            "  beside the %.1f ms Joint step: %.1f %% of the step; beside the T = 3 integrate + extract pass (%.2f ms): %.1f x"
+            % (JOINT_STEP_MS, 100.0 * t_cold / JOINT_STEP_MS, fuse_extract_ms, t_cold / fuse_extract_ms),
         ]
     text = "\n".join(lines)
     print(text)
