@@ -2,6 +2,7 @@
 the arithmetic is libestd_hip.so's).  Every function enqueues on the current HIP stream and
 returns tensors owned by the caching allocator.  CUDA(ROCm)-only: CPU tensors raise RuntimeError.
 """
+import collections
 import ctypes
 import math
 import os
@@ -233,6 +234,84 @@ def homo_warp_costvol(src_mix, ref_mix, proj12, depth_values, D, out=None):
 
 
 # ---------------------------------------------------------------------------------- conv3d
+# One kernel launch of a route: the C entry point, the torch operator's ``variant``, {descriptor weight field: plan weight form} (a form the
+# plan's shape does not define arrives as NULL), the descriptor fields that differ from the call's, and the number of output channels its
+# ops.PROFILE group counts (None: the plan's).
+_Launch = collections.namedtuple("_Launch", "entry variant weights overrides n_out", defaults=({}, None))
+
+# route name (Conv3dPlan.route) -> its launches, in order
+CONV3D_ROUTES = {
+    "direct": (_Launch("estd_conv3d_k3", 0, dict(w_main="w_main", w_extra="w_extra", w_xout="w_xout")),),
+    # (the operand-split kernel reads the direct form's scalar-channel / 33rd-output weights)
+    "split": (_Launch("estd_conv3d_k3_split", 1, dict(w_main="w_main", w_extra="w_extra", w_xout="w_xout", w_split="w_split")),),
+    "wino": (_Launch("estd_conv3d_k3_wino", 2, dict(w_wino="w_wino", w_extra="w_wino_extra", w_xout="w_wino_xout")),),
+    "wino2": (_Launch("estd_conv3d_k3_wino2", 3, dict(w_wino2="w_wino2", w_extra="w_wino2_extra")),),
+    "wino2_xout": (_Launch("estd_conv3d_k3_wino2", 3, dict(w_wino2="w_wino2", w_extra="w_wino2_extra", w_xout="w_wino2_xout")),),
+    "wino2_o16": (_Launch("estd_conv3d_k3_wino2", 3, dict(w_wino2="w_wino2_o16")),),
+    "wino2_c16": (_Launch("estd_conv3d_k3_wino2", 3, dict(w_wino2="w_wino2_c16")),),
+    "wino2x": (_Launch("estd_conv3d_k3_wino2x", 4, dict(w_wino2="w_wino2x")),),
+    "wino3": (_Launch("estd_conv3d_k3_wino3", 5, dict(w_wino2="w_wino3", w_extra="w_wino3_extra")),),
+    # the 33 -> 33 instance as two launches: 33 -> 32 (the main output channels) + 33 -> 1 (csrc/conv3d_xout.hip); two profile groups,
+    # the launches belong to two kernel families of the replay trace.  (The second kernel reads w_xout only; w_extra is there because the
+    # torch operator refuses a scalar input channel without extra-channel weights.)
+    "wino3+xout": (_Launch("estd_conv3d_k3_wino3", 5, dict(w_wino2="w_wino3", w_extra="w_wino3_extra"),
+                           dict(n_tiles=2, out_channels=32, out_extra=None), n_out=32),
+                   _Launch("estd_conv3d_k3_xout", 6, dict(w_extra="w_wino3_extra", w_xout="w_xout_taps"),
+                           dict(n_tiles=3, out_main=None), n_out=1)),
+}
+# route name (Conv2dPlan.route) -> its launch; {nt}: the work-item width the route function returns next to the name
+CONV2D_ROUTES = {
+    "k3": (_Launch("estd_conv2d_k3", 0, dict(w="w_nt{nt}")),),
+    "k3_split": (_Launch("estd_conv2d_k3_split", 1, dict(w="w_nt{nt}", w_split="w_split")),),       # (validates d.w as well)
+    "wino": (_Launch("estd_conv2d_k3_wino", 2, dict(w_wino="w_wino_nt{nt}")),),
+    "wino2": (_Launch("estd_conv2d_k3_wino2", 3, dict(w_wino="w_wino2")),),
+}
+# the descriptor field the torch operators fill from their ``w_alt`` argument, by variant (csrc/torch_ops.cpp)
+_CONV3D_ALT = (None, "w_split", "w_wino", "w_wino2", "w_wino2", "w_wino2", "w_xout")
+_CONV2D_ALT = (None, "w_split", "w_wino", "w_wino")
+
+
+def _conv3d_torch_args(f, variant):
+    alt = _CONV3D_ALT[variant]
+    return (f["in_main"], f["in_extra"], f["w_main"], f["w_extra"], None if alt == "w_xout" else f["w_xout"], f[alt] if alt else None,
+            f["scale"], f["shift"], (f["N"], f["D"], f["H"], f["W"]), f["cin_main"], f["in_stride"], f["n_tiles"], f["act_a"], f["act_b"],
+            f["act_split"], f["out_main"], f["out_stride"], f["out_channels"], f["residual"], f["residual2"], f["out_scale"],
+            bool(f["accumulate"]), f["out_extra"], f["head_w"], f["head_b"], f["out_head"], f["stats_partials"], variant,
+            f["gate_r"], f["gate_stats"], f["gate_gamma"], f["gate_beta"])
+
+
+def _conv2d_torch_args(f, variant):
+    alt = _CONV2D_ALT[variant]
+    return (f["in_"], f["w"], f[alt] if alt else None, f["scale"], f["shift"], f["cout"], f["dilation"], f["group_tiles"],
+            bool(f["relu_before_residual"]), bool(f["relu_after_residual"]), f["residual"], variant)
+
+
+_CONV_BINDINGS = {"conv3d_k3": (_conv3d_torch_args, N.Conv3dDesc), "conv2d_k3": (_conv2d_torch_args, N.Conv2dDesc)}
+
+
+def _launch_conv(op, launch, fields, weights):
+    """One launch of a route under the current binding: ``fields`` are the descriptor's fields (tensors where it holds a pointer),
+    ``weights`` the launch's {descriptor field: packed tensor or None}.  The torch operator ``op`` takes them as positional arguments
+    (its result is returned), the C entry point as the descriptor."""
+    torch_args, desc = _CONV_BINDINGS[op]
+    f = dict(fields, **launch.overrides)
+    f.update(weights)
+    if _use_torch():
+        return getattr(T(), op)(*torch_args(f, launch.variant))
+    d = desc()
+    for k, v in f.items():
+        if v is not None:                             # (a fresh descriptor is all zeros / NULL)
+            setattr(d, k, v.data_ptr() if isinstance(v, torch.Tensor) else v)
+    N.check(getattr(N.lib(), launch.entry)(ctypes.byref(d), _stream()), launch.entry)
+
+
+def _need_ab(has_ab, switches):
+    """``switches``: (set?, what) of the switches that select a superseded A/B kernel (raises as _native.require_ab does, from the plan's own fact)"""
+    for on, what in switches:
+        if on and not has_ab:
+            raise RuntimeError("%s needs the A/B kernels: rebuild the library with ESTD_BUILD_AB=1 (python -m estdepth_amd.build)" % what)
+
+
 class _Packs:
     """Weight forms of a plan, packed and uploaded on first use (``define`` registers how, ``has`` says whether the plan's shape admits the
     form, ``get`` packs once).  Shared by the copies ``with_shift_scaled`` makes."""
@@ -284,7 +363,7 @@ class Conv3dPlan:
         splittable = len(main_idx) == 32 and head_w is None and \
             (n_tiles == 2 or (n_tiles == 3 and extra_idx is not None) or (n_tiles == 1 and extra_idx is None))
         # the superseded A/B kernels (bf16 operand split, depth-only Winograd, operand-reuse wino2x): only in a library built with ESTD_BUILD_AB=1
-        ab = N.has_ab()
+        ab = self.has_ab = N.has_ab()
         if splittable and ab:
             P.define("w_split", lambda: packing.pack_conv3d_split(weight, main_idx, out_idx, extra_idx, n_tiles))
         wino_ok = len(main_idx) == 32 and head_w is None and \
@@ -324,38 +403,6 @@ class Conv3dPlan:
         self.head_w = head_w.float().contiguous().to(device) if head_w is not None else None
         self.head_b = head_b.float().contiguous().to(device) if head_b is not None else None
 
-    def _run_split33(self, x, dims, in_stride, in_extra, out, out_stride, out_extra):
-        """the 33 -> 33 instance as two launches: estd_conv3d_k3_wino3 (33 -> 32, the main output channels) + estd_conv3d_k3_xout (33 -> 1)"""
-        Nn, D, H, W = dims
-        cin = self.cin_main + 1
-        vox = float(Nn) * D * H * W
-        if _use_torch():
-            # (two profile groups: the launches belong to two kernel families of the replay trace)
-            with _Prof("conv3d:%d->32" % cin, 2.0 * 27 * cin * 32 * vox):
-                T().conv3d_k3(x, in_extra, None, self.w_wino3_extra, None, self.w_wino3, self.scale, self.shift, (Nn, D, H, W), self.cin_main, in_stride, 2,
-                              self.act_a, self.act_b, self.act_split, out, out_stride, 32, None, None, 1.0, False, None, None, None, None, None, 5,
-                              None, None, None, None)
-            with _Prof("conv3d:%d->1" % cin, 2.0 * 27 * cin * vox):
-                T().conv3d_k3(x, in_extra, None, self.w_wino3_extra, None, self.w_xout_taps, self.scale, self.shift, (Nn, D, H, W), self.cin_main, in_stride, 3,
-                              self.act_a, self.act_b, self.act_split, None, out_stride, 32, None, None, 1.0, False, out_extra, None, None, None, None, 6,
-                              None, None, None, None)
-            return
-        d = N.Conv3dDesc()
-        d.N, d.D, d.H, d.W = Nn, D, H, W
-        d.cin_main, d.in_stride, d.n_tiles = self.cin_main, in_stride, 2
-        d.in_main, d.in_extra = x.data_ptr(), in_extra.data_ptr()
-        d.scale, d.shift = self.scale.data_ptr(), self.shift.data_ptr()
-        d.act_a, d.act_b, d.act_split = self.act_a, self.act_b, self.act_split
-        d.out_main, d.out_stride, d.out_channels = out.data_ptr(), out_stride, 32
-        d.out_scale = 1.0
-        d.w_wino2, d.w_extra = self.w_wino3.data_ptr(), self.w_wino3_extra.data_ptr()
-        with _Prof("conv3d:%d->32" % cin, 2.0 * 27 * cin * 32 * vox):
-            N.check(N.lib().estd_conv3d_k3_wino3(ctypes.byref(d), _stream()), "estd_conv3d_k3_wino3")
-        d.n_tiles, d.out_main, d.w_wino2, d.w_extra = 3, None, None, None
-        d.w_xout, d.out_extra = self.w_xout_taps.data_ptr(), out_extra.data_ptr()
-        with _Prof("conv3d:%d->1" % cin, 2.0 * 27 * cin * vox):
-            N.check(N.lib().estd_conv3d_k3_xout(ctypes.byref(d), _stream()), "estd_conv3d_k3_xout")
-
     def with_shift_scaled(self, k):
         """same packed weights, BN shift multiplied by k: sum of k conv+BN results of a LINEAR layer computed as ONE
         convolution of the summed inputs (conv is linear, the shift is counted k times)."""
@@ -364,137 +411,80 @@ class Conv3dPlan:
         other.shift = (self.shift * float(k)).contiguous()
         return other
 
+    def route(self, out=True, in_extra=False, out_extra=False, out_head=False, residual=False, residual2=False, stats_partials=False,
+              gate=False, out_channels=None, accumulate=False, out_scale=1.0):
+        """The route (a key of CONV3D_ROUTES) ``run`` takes for a call under the current module switches.  The first eight arguments say
+        whether the call passes that tensor; ``out_channels`` / ``accumulate`` / ``out_scale`` are ``run``'s.  Pure (nothing is packed or
+        loaded, a plan on any device answers); RuntimeError for a call or a switch setting ``run`` refuses."""
+        _need(in_extra == self.has_extra, "conv3d plan/extra-channel mismatch")
+        if CONV3D_ARITH not in ("f32", "bf16x3"):
+            raise RuntimeError("ESTD_CONV3D_ARITH must be f32 or bf16x3, got %r" % (CONV3D_ARITH,))
+        if CONV3D_ALGO not in ("wino2", "wino", "direct"):
+            raise RuntimeError("ESTD_CONV3D_ALGO must be wino2, wino or direct, got %r" % (CONV3D_ALGO,))
+        _need_ab(self.has_ab, ((CONV3D_ARITH == "bf16x3", "ESTD_CONV3D_ARITH=bf16x3 (csrc/conv3d_split_bf16.hip)"),
+                               (CONV3D_ALGO == "wino", "ESTD_CONV3D_ALGO=wino (csrc/conv3d_wino.hip)"), (W2X, "ESTD_W2X=1 (csrc/conv3d_wino2x.hip)")))
+        has, nt, stats = self._packs.has, self.n_tiles, stats_partials
+        if out_channels is None:
+            out_channels = 16 * min(nt, 2)
+        tanh = ACT["tanh"] in ((self.act_a if self.act_split > 0 else self.act_b), self.act_b)
+        plain_epi = not (residual or residual2 or accumulate) and float(out_scale) == 1.0      # no read-back stream
+        # instances of the split kernel (csrc/conv3d_split_bf16.hip dispatch): plain [+stats], extra input [tanh|relu], 33 -> 33
+        split_inst = (not tanh and not stats) if nt == 3 else (not tanh and not in_extra) if nt == 1 else (not stats) if in_extra else not tanh
+        wino2_algo = CONV3D_ALGO == "wino2"
+        # the 32 -> 32 / 33 -> 32 / 33 -> 33 shapes of the Winograd kernels ...
+        wino_shape = CONV3D_ALGO in ("wino", "wino2") and self.wino_ok and out and out_extra == (nt == 3) and not out_head \
+            and out_channels == 32 and not (stats and in_extra)
+        # ... on the two-axis kernel (its 33 -> 33 instance has no read-back streams / statistics: dres2 needs none) or one that builds on it
+        two_axis = wino_shape and wino2_algo and has("w_wino2") and (nt == 2 or (W2_XOUT and plain_epi and not stats))
+        routes = (                                        # the first route whose condition holds
+            ("split", CONV3D_ARITH == "bf16x3" and has("w_split") and out and split_inst),
+            # the stereo heads: only the head's logit volume leaves the kernel, no tanh
+            ("wino2_c16", wino2_algo and has("w_wino2_c16") and not out and out_head and not in_extra and not out_extra and plain_epi
+             and not stats and not tanh),
+            ("wino2_o16", wino2_algo and has("w_wino2_o16") and out and not out_head and not in_extra and not out_extra and out_channels == 16),
+            # 33 -> 33 (dres2): 32 outputs on the three-axis kernel's 33 -> 32 instance, then output channel 32 alone (that pass has no
+            # tanh: the two-axis kernel's 33 -> 33 instance does)
+            ("wino3+xout", two_axis and nt == 3 and W3 and W3_EXTRA and W3_XOUT and has("w_wino3") and has("w_wino3_extra")
+             and has("w_xout_taps") and not tanh),
+            # GroupNorm partials only without read-back streams; the scalar-channel instance has neither
+            ("wino3", two_axis and nt == 2 and W3 and has("w_wino3") and (plain_epi or not stats)
+             and (not in_extra or (W3_EXTRA and has("w_wino3_extra") and plain_epi and not stats))),
+            # 32 -> 32 without a scalar channel and without tanh: the operand-reuse kernel (GroupNorm partials only without read-back streams)
+            ("wino2x", two_axis and nt == 2 and W2X and has("w_wino2x") and not in_extra and not tanh and (plain_epi or not stats)),
+            ("wino2_xout", two_axis and nt == 3),
+            ("wino2", two_axis),
+            # the depth-only kernel: ESTD_CONV3D_ALGO=wino, or dres2 with ESTD_W2_XOUT=0 -- where the library carries it
+            ("wino", wino_shape and has("w_wino")),
+            ("direct", True))
+        name = next(r for r, ok in routes if ok)
+        _need(not gate or name == "wino2_o16", "the reset gate is folded into the 32 -> 16 instance of the two-axis Winograd kernel only")
+        return name
+
     def run(self, x, dims, in_stride=None, in_extra=None, out=None, out_stride=None, out_channels=None,
             residual=None, residual2=None, out_scale=1.0, accumulate=False, out_extra=None, out_head=None, stats_partials=None, gate=None):
         """x: channels-last volume(s) [N,D,H,W,in_stride] (or a base view of it); dims = (N,D,H,W).
         ``gate`` = (ru [N,D,H,W,32], statistics [4], gamma [16], beta [16]): the ConvGRU's reset gate applied to input channels 16..31 in the
         convolution's own loads (32 -> 16 instance of the two-axis Winograd kernel only; include/estd_hip.h ``gate_r``)."""
         Nn, D, H, W = dims
-        if (in_extra is None) == self.has_extra:
-            raise RuntimeError("conv3d plan/extra-channel mismatch")
-        has = self._packs.has
-        if CONV3D_ARITH not in ("f32", "bf16x3"):
-            raise RuntimeError("ESTD_CONV3D_ARITH must be f32 or bf16x3, got %r" % (CONV3D_ARITH,))
-        in_stride = in_stride if in_stride is not None else self.cin_main
-        out_stride = out_stride if out_stride is not None else (16 * min(self.n_tiles, 2))
         out_channels = out_channels if out_channels is not None else 16 * min(self.n_tiles, 2)
-        head_w = self.head_w if out_head is not None else None
-        head_b = self.head_b if out_head is not None else None
-        # instances of the split kernel (csrc/conv3d_split_bf16.hip dispatch): plain [+stats], extra input [tanh|relu], 33 -> 33
-        tanh = ACT["tanh"] in ((self.act_a if self.act_split > 0 else self.act_b), self.act_b)
-        if self.n_tiles == 3:
-            inst = not tanh and stats_partials is None
-        elif self.n_tiles == 1:
-            inst = not tanh and not self.has_extra
-        elif self.has_extra:
-            inst = stats_partials is None
-        else:
-            inst = not tanh
-        if CONV3D_ARITH == "bf16x3":
-            N.require_ab("ESTD_CONV3D_ARITH=bf16x3 (csrc/conv3d_split_bf16.hip)")
-        split = CONV3D_ARITH == "bf16x3" and has("w_split") and out is not None and inst
-        if CONV3D_ALGO not in ("wino2", "wino", "direct"):
-            raise RuntimeError("ESTD_CONV3D_ALGO must be wino2, wino or direct, got %r" % (CONV3D_ALGO,))
-        if CONV3D_ALGO == "wino":
-            N.require_ab("ESTD_CONV3D_ALGO=wino (csrc/conv3d_wino.hip)")
-        wino_shape = (not split) and CONV3D_ALGO in ("wino", "wino2") and self.wino_ok and out is not None \
-            and (out_extra is not None) == (self.n_tiles == 3) and out_head is None and out_channels == 32 \
-            and (stats_partials is None or not self.has_extra)
-        wino2 = wino_shape and CONV3D_ALGO == "wino2" and has("w_wino2") and (in_extra is None or stats_partials is None)
-        if self.n_tiles == 3:                             # the XOUT instance has no read-back streams / statistics (dres2 needs none)
-            wino2 = wino2 and W2_XOUT and residual is None and residual2 is None and not accumulate and float(out_scale) == 1.0 and stats_partials is None
-        # the depth-only kernel: ESTD_CONV3D_ALGO=wino, or dres2 with ESTD_W2_XOUT=0 -- where the library carries it (else the direct kernel)
-        wino = wino_shape and not wino2 and has("w_wino")
-        o16 = (not split) and CONV3D_ALGO == "wino2" and has("w_wino2_o16") and out is not None and out_head is None \
-            and in_extra is None and out_channels == 16 and out_extra is None
-        # the stereo heads: only the head's logit volume leaves the kernel, no tanh
-        c16 = (not split) and CONV3D_ALGO == "wino2" and has("w_wino2_c16") and out is None and out_head is not None \
-            and in_extra is None and out_extra is None and residual is None and residual2 is None and not accumulate \
-            and stats_partials is None and float(out_scale) == 1.0 and not tanh
-        # 32 -> 32 without a scalar channel and without tanh: the operand-reuse kernel (GroupNorm partials only without read-back streams)
-        wino2x = wino2 and W2X and has("w_wino2x") and in_extra is None and self.n_tiles == 2 and not tanh \
-            and (stats_partials is None or (residual is None and residual2 is None and not accumulate and float(out_scale) == 1.0))
-        plain_epi = residual is None and residual2 is None and not accumulate and float(out_scale) == 1.0
-        wino3 = wino2 and W3 and has("w_wino3") and self.n_tiles == 2 and (stats_partials is None or plain_epi) \
-            and (in_extra is None or (W3_EXTRA and has("w_wino3_extra") and plain_epi and stats_partials is None))
-        wino2x = wino2x and not wino3
-        # 33 -> 33 (dres2): 32 outputs on the three-axis kernel's 33 -> 32 instance, then output channel 32 alone
-        split33 = wino2 and self.n_tiles == 3 and W3 and W3_EXTRA and W3_XOUT and has("w_wino3") and has("w_wino3_extra") and has("w_xout_taps") \
-            and in_extra is not None and out_extra is not None and not tanh      # (the channel-32 pass has no tanh: the XOUT instance does)
-        if split33:
-            return self._run_split33(x, dims, in_stride, in_extra, out, out_stride, out_extra)
-        variant, alt = (1, "w_split") if split else (3, "w_wino2_c16") if c16 else (3, "w_wino2_o16") if o16 else (5, "w_wino3") if wino3 \
-            else (4, "w_wino2x") if wino2x \
-            else (3, "w_wino2") if wino2 else (2, "w_wino") if wino else (0, None)
-        if W2X:
-            N.require_ab("ESTD_W2X=1 (csrc/conv3d_wino2x.hip)")
-        w_alt = self._packs.get(alt) if alt is not None else None
-        if gate is not None and not o16:
-            raise RuntimeError("the reset gate is folded into the 32 -> 16 instance of the two-axis Winograd kernel only")
+        name = self.route(out is not None, in_extra is not None, out_extra is not None, out_head is not None, residual is not None,
+                          residual2 is not None, stats_partials is not None, gate is not None, out_channels, accumulate, out_scale)
         g_r, g_st, g_ga, g_be = gate if gate is not None else (None, None, None, None)
+        fields = dict(
+            N=Nn, D=D, H=H, W=W, cin_main=self.cin_main, in_stride=in_stride if in_stride is not None else self.cin_main, n_tiles=self.n_tiles,
+            in_main=x, in_extra=in_extra, w_main=None, w_extra=None, w_xout=None, scale=self.scale, shift=self.shift,
+            act_a=self.act_a, act_b=self.act_b, act_split=self.act_split,
+            out_main=out, out_stride=out_stride if out_stride is not None else 16 * min(self.n_tiles, 2), out_channels=out_channels,
+            residual=residual, residual2=residual2, out_scale=float(out_scale), accumulate=int(bool(accumulate)), out_extra=out_extra,
+            head_w=self.head_w if out_head is not None else None, head_b=self.head_b if out_head is not None else None, out_head=out_head,
+            stats_partials=stats_partials, w_split=None, w_wino=None, w_wino2=None, gate_r=g_r, gate_stats=g_st, gate_gamma=g_ga, gate_beta=g_be)
+        # (the route's weight forms, packed on first use, before the first launch)
+        launches = [(la, {fld: self._packs.get(form) for fld, form in la.weights.items()}) for la in CONV3D_ROUTES[name]]
         cin = self.cin_main + (1 if self.has_extra else 0)
-        with _Prof("conv3d:%d->%d" % (cin, self.n_out), 2.0 * 27 * cin * self.n_out * Nn * D * H * W):
-            if _use_torch():
-                direct = variant in (0, 1)          # (the operand-split kernel reads the direct form's scalar-channel / 33rd-output weights)
-                T().conv3d_k3(x, in_extra, self.w_main if direct else None,
-                              self.w_wino3_extra if wino3 else self.w_wino2_extra if wino2 else self.w_wino_extra if wino else self.w_extra,
-                              self.w_wino2_xout if wino2 else self.w_wino_xout if wino else self.w_xout, w_alt, self.scale, self.shift,
-                              (Nn, D, H, W), self.cin_main, in_stride, self.n_tiles, self.act_a, self.act_b, self.act_split, out,
-                              out_stride, out_channels, residual, residual2, float(out_scale), bool(accumulate), out_extra, head_w, head_b,
-                              out_head, stats_partials, variant, g_r, g_st, g_ga, g_be)
-                return
-            d = N.Conv3dDesc()
-            d.N, d.D, d.H, d.W = Nn, D, H, W
-            d.cin_main, d.in_stride, d.n_tiles = self.cin_main, in_stride, self.n_tiles
-            d.in_main = x.data_ptr()
-            d.in_extra = in_extra.data_ptr() if in_extra is not None else None
-            if variant in (0, 1):
-                d.w_main = self.w_main.data_ptr()
-                d.w_extra = self.w_extra.data_ptr() if self.has_extra else None
-                d.w_xout = self.w_xout.data_ptr() if self.n_tiles == 3 else None
-            d.scale, d.shift = self.scale.data_ptr(), self.shift.data_ptr()
-            d.act_a, d.act_b, d.act_split = self.act_a, self.act_b, self.act_split
-            d.out_main = out.data_ptr() if out is not None else None
-            d.out_stride, d.out_channels = out_stride, out_channels
-            d.residual = residual.data_ptr() if residual is not None else None
-            d.residual2 = residual2.data_ptr() if residual2 is not None else None
-            d.out_scale = float(out_scale)
-            d.accumulate = 1 if accumulate else 0
-            d.out_extra = out_extra.data_ptr() if out_extra is not None else None
-            d.head_w = head_w.data_ptr() if head_w is not None else None
-            d.head_b = head_b.data_ptr() if head_b is not None else None
-            d.out_head = out_head.data_ptr() if out_head is not None else None
-            d.stats_partials = stats_partials.data_ptr() if stats_partials is not None else None
-            if gate is not None:
-                d.gate_r, d.gate_stats, d.gate_gamma, d.gate_beta = g_r.data_ptr(), g_st.data_ptr(), g_ga.data_ptr(), g_be.data_ptr()
-            if split:
-                d.w_split = self.w_split.data_ptr()
-                N.check(N.lib().estd_conv3d_k3_split(ctypes.byref(d), _stream()), "estd_conv3d_k3_split")
-            elif c16:
-                d.w_wino2 = self.w_wino2_c16.data_ptr()
-                N.check(N.lib().estd_conv3d_k3_wino2(ctypes.byref(d), _stream()), "estd_conv3d_k3_wino2")
-            elif o16:
-                d.w_wino2 = self.w_wino2_o16.data_ptr()
-                N.check(N.lib().estd_conv3d_k3_wino2(ctypes.byref(d), _stream()), "estd_conv3d_k3_wino2")
-            elif wino3:
-                d.w_wino2 = self.w_wino3.data_ptr()
-                d.w_extra = self.w_wino3_extra.data_ptr() if (in_extra is not None) else None
-                N.check(N.lib().estd_conv3d_k3_wino3(ctypes.byref(d), _stream()), "estd_conv3d_k3_wino3")
-            elif wino2x:
-                d.w_wino2 = self.w_wino2x.data_ptr()
-                N.check(N.lib().estd_conv3d_k3_wino2x(ctypes.byref(d), _stream()), "estd_conv3d_k3_wino2x")
-            elif wino2:
-                d.w_wino2 = self.w_wino2.data_ptr()
-                d.w_extra = self.w_wino2_extra.data_ptr() if self.has_extra else None
-                d.w_xout = self.w_wino2_xout.data_ptr() if self.n_tiles == 3 else None
-                N.check(N.lib().estd_conv3d_k3_wino2(ctypes.byref(d), _stream()), "estd_conv3d_k3_wino2")
-            elif wino:
-                d.w_wino = self.w_wino.data_ptr()
-                d.w_extra = self.w_wino_extra.data_ptr() if self.has_extra else None
-                d.w_xout = self.w_wino_xout.data_ptr() if self.n_tiles == 3 else None
-                N.check(N.lib().estd_conv3d_k3_wino(ctypes.byref(d), _stream()), "estd_conv3d_k3_wino")
-            else:
-                N.check(N.lib().estd_conv3d_k3(ctypes.byref(d), _stream()), "estd_conv3d_k3")
+        for la, weights in launches:
+            n_out = la.n_out if la.n_out is not None else self.n_out
+            with _Prof("conv3d:%d->%d" % (cin, n_out), 2.0 * 27 * cin * n_out * Nn * D * H * W):
+                _launch_conv("conv3d_k3", la, fields, weights)
 
 
 class Conv2dPlan:
@@ -518,7 +508,8 @@ class Conv2dPlan:
         self.nts = (2, 4) if self.cout % 64 == 0 else (2,)
         for nt in self.nts:
             P.define("w_nt%d" % nt, lambda nt=nt: packing.pack_conv2d(w, nt))
-        if N.has_ab():       # row-only Winograd / bf16 operand split: only in a library built with ESTD_BUILD_AB=1
+        self.has_ab = N.has_ab()
+        if self.has_ab:      # row-only Winograd / bf16 operand split: only in a library built with ESTD_BUILD_AB=1
             P.define("w_split", lambda: packing.pack_conv2d_split(w))
             for nt in self.nts:
                 P.define("w_wino_nt%d" % nt, lambda nt=nt: packing.pack_conv2d_wino(w, nt))
@@ -542,54 +533,46 @@ class Conv2dPlan:
             return items / (512.0 * ((items + 511) // 512))
         return 2 if 0.93 * balance(tiles * (self.cout // 32)) > balance(tiles * (self.cout // 64)) else 4
 
+    def route(self, n, h, w):
+        """-> (a key of CONV2D_ROUTES, the work-item width nt) for an [n, h, w, cin] input under the current module switches.  Pure, like
+        Conv3dPlan.route; RuntimeError for a switch setting ``run`` refuses."""
+        if CONV2D_ARITH not in ("f32", "bf16x3"):
+            raise RuntimeError("ESTD_CONV2D_ARITH must be f32 or bf16x3, got %r" % (CONV2D_ARITH,))
+        if CONV2D_ALGO not in ("wino2", "wino", "direct"):
+            raise RuntimeError("ESTD_CONV2D_ALGO must be wino2, wino or direct, got %r" % (CONV2D_ALGO,))
+        _need_ab(self.has_ab, ((CONV2D_ARITH == "bf16x3", "ESTD_CONV2D_ARITH=bf16x3 (csrc/conv2d_split_bf16.hip)"),
+                               (CONV2D_ALGO == "wino", "ESTD_CONV2D_ALGO=wino (csrc/conv2d_wino.hip)")))
+        has = self._packs.has
+        split = CONV2D_ARITH == "bf16x3" and has("w_split")
+        nt = self._pick_nt(n, h, w)
+        if self.dil == 2 and not split and CONV2D_ALGO in ("wino", "wino2"):
+            nt = 2        # the 64-channel work item of the dilated Winograd kernel spills registers into its MFMA loop (5x slower)
+        routes = (                                        # the first route whose condition holds
+            ("k3_split", split),
+            ("wino2", CONV2D_ALGO == "wino2" and (self.dil == 1 or C2W2_DIL2)),
+            ("wino", CONV2D_ALGO in ("wino", "wino2") and has("w_wino_nt%d" % nt)),      # (where the library carries it)
+            ("k3", True))
+        return next(r for r, ok in routes if ok), nt
+
     def run(self, x_nhwc, residual=None):
         """x_nhwc [N,H,W,Cin] contiguous -> [N,H,W,Cout]."""
         Nn, H, W, C = x_nhwc.shape
         if C != self.cin or not x_nhwc.is_contiguous():
             raise RuntimeError("Conv2dPlan.run: expected contiguous NHWC input with %d channels" % self.cin)
-        if CONV2D_ARITH not in ("f32", "bf16x3"):
-            raise RuntimeError("ESTD_CONV2D_ARITH must be f32 or bf16x3, got %r" % (CONV2D_ARITH,))
         if residual is not None and (tuple(residual.shape) != (Nn, H, W, self.cout) or not residual.is_contiguous()):
             raise RuntimeError("Conv2dPlan.run: residual must be contiguous NHWC of the output shape")
-        nt = self._pick_nt(Nn, H, W)
-        if CONV2D_ARITH == "bf16x3":
-            N.require_ab("ESTD_CONV2D_ARITH=bf16x3 (csrc/conv2d_split_bf16.hip)")
-        if CONV2D_ALGO == "wino":
-            N.require_ab("ESTD_CONV2D_ALGO=wino (csrc/conv2d_wino.hip)")
-        has = self._packs.has
-        split = CONV2D_ARITH == "bf16x3" and has("w_split")
-        if self.dil == 2 and not split and CONV2D_ALGO in ("wino", "wino2"):
-            nt = 2        # the 64-channel work item of the dilated Winograd kernel spills registers into its MFMA loop (5x slower)
-        if CONV2D_ALGO not in ("wino2", "wino", "direct"):
-            raise RuntimeError("ESTD_CONV2D_ALGO must be wino2, wino or direct, got %r" % (CONV2D_ALGO,))
-        wino2 = (not split) and CONV2D_ALGO == "wino2" and (self.dil == 1 or C2W2_DIL2)
-        wino = (not split) and not wino2 and CONV2D_ALGO in ("wino", "wino2") and has("w_wino_nt%d" % nt)
-        variant, alt = (1, "w_split") if split else (3, "w_wino2") if wino2 else (2, "w_wino_nt%d" % nt) if wino else (0, None)
-        w_alt = self._packs.get(alt) if alt is not None else None
-        w_direct = self._packs.get("w_nt%d" % nt) if variant in (0, 1) else None      # (the operand-split kernel validates d.w as well)
-        if _use_torch():
-            return T().conv2d_k3(x_nhwc, w_direct, w_alt, self.scale, self.shift, self.cout, self.dil, nt,
-                                 bool(self.relu_before), bool(self.relu_after), residual, variant)
-        out = torch.empty((Nn, H, W, self.cout), device=x_nhwc.device, dtype=torch.float32)
-        d = N.Conv2dDesc()
-        d.N, d.H, d.W, d.cin, d.cout, d.dilation, d.group_tiles = Nn, H, W, self.cin, self.cout, self.dil, nt
-        d.in_ = _chk(x_nhwc, "conv2d input").data_ptr()
-        d.w, d.scale, d.shift = (w_direct.data_ptr() if w_direct is not None else None), self.scale.data_ptr(), self.shift.data_ptr()
-        d.relu_before_residual, d.relu_after_residual = self.relu_before, self.relu_after
-        d.residual = residual.data_ptr() if residual is not None else None
-        d.out = out.data_ptr()
-        if split:
-            d.w_split = w_alt.data_ptr()
-            N.check(N.lib().estd_conv2d_k3_split(ctypes.byref(d), _stream()), "estd_conv2d_k3_split")
-        elif wino2:
-            d.w_wino = w_alt.data_ptr()
-            N.check(N.lib().estd_conv2d_k3_wino2(ctypes.byref(d), _stream()), "estd_conv2d_k3_wino2")
-        elif wino:
-            d.w_wino = w_alt.data_ptr()
-            N.check(N.lib().estd_conv2d_k3_wino(ctypes.byref(d), _stream()), "estd_conv2d_k3_wino")
-        else:
-            N.check(N.lib().estd_conv2d_k3(ctypes.byref(d), _stream()), "estd_conv2d_k3")
-        return out
+        name, nt = self.route(Nn, H, W)
+        la, = CONV2D_ROUTES[name]
+        weights = {fld: self._packs.get(form.format(nt=nt)) for fld, form in la.weights.items()}
+        out = None         # (the torch operator allocates its own)
+        if not _use_torch():
+            _chk(x_nhwc, "conv2d input")
+            out = torch.empty((Nn, H, W, self.cout), device=x_nhwc.device, dtype=torch.float32)
+        fields = dict(N=Nn, H=H, W=W, cin=self.cin, cout=self.cout, dilation=self.dil, group_tiles=nt, in_=x_nhwc, w=None,
+                      scale=self.scale, shift=self.shift, relu_before_residual=self.relu_before, relu_after_residual=self.relu_after,
+                      residual=residual, out=out, w_split=None, w_wino=None)
+        res = _launch_conv("conv2d_k3", la, fields, weights)
+        return res if _use_torch() else out
 
 
 def conv3d_grid(Nn, D, H, W):

@@ -376,7 +376,7 @@ def _op(case, m, x, res):
 def _raw(case, m, x, res, out):
     """the same launch through the C ABI directly, on caller-provided (guarded) buffers -> estd_status"""
     import ctypes
-    from estdepth_amd import _native as NV, ops
+    from estdepth_amd import _native as NV
     lib, st = NV.lib(), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
     fam = case["fam"]
@@ -385,9 +385,7 @@ def _raw(case, m, x, res, out):
         plan, kern = m["plan"], case["kern"]
         d = NV.Conv2dDesc()
         d.N, d.H, d.W, d.cin, d.cout, d.dilation = N, H, W, plan.cin, plan.cout, plan.dil
-        nt = plan._pick_nt(N, H, W)
-        if plan.dil == 2 and ops.CONV2D_ARITH != "bf16x3" and ops.CONV2D_ALGO in ("wino", "wino2"):
-            nt = 2
+        nt = plan.route(N, H, W)[1]
         d.group_tiles = nt
         d.in_, d.scale, d.shift, d.out = x.data_ptr(), plan.scale.data_ptr(), plan.shift.data_ptr(), out.data_ptr()
         d.relu_before_residual, d.relu_after_residual = plan.relu_before, plan.relu_after

@@ -11,8 +11,8 @@ One case per (route, plan, activation, epilogue, strides, switches).  Each case
   * runs small shapes at the tile edges of the kernels (8 x 16 tiles of the direct / Winograd kernels, 16 x 16 of the channel-32 pass and
     the stereo-head kernel, its 32-plane depth segments, the Winograd depth pairs), a full-size volume per route family and one batch whose
     total size crosses 2^31 bytes (64-bit batch offsets; the reference then at sampled voxels only).
-The two routes with ctypes code of their own (dres2 in two launches, the 32 -> 16 instance with the reset gate) run under both bindings
-and must agree bit for bit."""
+Both bindings launch from one wiring (ops.CONV3D_ROUTES): one small-shape case of every route, and the reset-gate cases, run under both and
+must agree bit for bit."""
 import re
 
 import numpy as np
@@ -63,7 +63,7 @@ def C(cid, route, plan, acts=("relu",), epi=(), ins=None, outs=None, sw=None, sh
 
 CASES = [
     # ---- the direct kernel (ESTD_CONV3D_ALGO=direct): every instance, every epilogue
-    C("direct-32-split20-res-res2-scale-acc", "direct", "32>32", ("tanh", "relu", 20), ("res", "res2", "scale", "acc"), 36, 40, DIRECT),
+    C("direct-32-split20-res-res2-scale-acc", "direct", "32>32", ("tanh", "relu", 20), ("res", "res2", "scale", "acc"), 36, 40, DIRECT, both=True),
     C("direct-32-none-stats-res", "direct", "32>32", ("none",), ("stats", "res"), 32, 32, DIRECT),
     C("direct-33to32-split8", "direct", "33>32", ("relu", "tanh", 8), (), 64, 36, DIRECT),
     C("direct-33to33-split33", "direct", "33>33", ("relu", "none", 33), (), 36, 32, DIRECT),
@@ -72,7 +72,7 @@ CASES = [
     C("direct-16to16-relu-res-acc", "direct", "16>16", ("relu",), ("res", "acc", "scale"), 32, 24, DIRECT),
     C("direct-16to16-head-and-main", "direct", "16>16h", ("relu", "none", 8), ("head", "main"), 16, 16, DIRECT),
     # ---- three-axis Winograd (the default 32 -> 32 and 33 -> 32 launches)
-    C("wino3-32-relu", "wino3", "32>32", ("relu",)),
+    C("wino3-32-relu", "wino3", "32>32", ("relu",), both=True),
     C("wino3-32-tanh-res-res2-scale", "wino3", "32>32", ("tanh",), ("res", "res2", "scale"), 32, 36),
     C("wino3-32-split16-acc-scale", "wino3", "32>32", ("tanh", "relu", 16), ("acc", "scale"), 36, 64),
     C("wino3-32-split8-res", "wino3", "32>32", ("relu", "tanh", 8), ("res",), 64, 32),
@@ -81,12 +81,12 @@ CASES = [
     C("wino3-33to32-relu", "wino3", "33>32", ("relu",), (), 36, 40),
     C("wino3-33to32-split16", "wino3", "33>32", ("tanh", "relu", 16), ()),
     # ---- two-axis Winograd (ESTD_W3=0)
-    C("wino2-32-split20-res-res2-scale-acc", "wino2", "32>32", ("tanh", "relu", 20), ("res", "res2", "scale", "acc"), 64, 36, W2),
+    C("wino2-32-split20-res-res2-scale-acc", "wino2", "32>32", ("tanh", "relu", 20), ("res", "res2", "scale", "acc"), 64, 36, W2, both=True),
     C("wino2-32-none-stats", "wino2", "32>32", ("none",), ("stats",), 36, 32, W2),
     C("wino2-33to32-tanh", "wino2", "33>32", ("tanh",), (), 36, 40, W2),
     C("wino2-33to32-relu-res-acc", "wino2", "33>32", ("relu",), ("res", "acc"), 32, 32, W2),
     # ---- the two-axis kernel's 33 -> 33 instance (ESTD_W3_XOUT=0)
-    C("wino2xout-33-relu", "wino2_xout", "33>33", ("relu",), (), 36, 40, W2XOUT),
+    C("wino2xout-33-relu", "wino2_xout", "33>33", ("relu",), (), 36, 40, W2XOUT, both=True),
     C("wino2xout-33-split32", "wino2_xout", "33>33", ("tanh", "relu", 32), (), 32, 32, W2XOUT),
     C("wino2xout-33-split33", "wino2_xout", "33>33", ("tanh", "none", 33), (), 64, 32, W2XOUT),
     # ---- dres2 in two launches (the default 33 -> 33 route): 33 -> 32 three-axis + the channel-32 pass
@@ -100,7 +100,7 @@ CASES = [
     C("o16-gate-stats", "wino2_o16", "32>16", ("none",), ("gate", "stats"), 32, 24, both=True),
     C("o16-gate-relu", "wino2_o16", "32>16", ("relu",), ("gate",), 32, 16, both=True),
     # ---- the stereo heads: 16 -> 16 + 1x1x1 head, only the logit volume
-    C("c16-relu", "wino2_c16", "16>16h", ("relu",), ("head",), 32),
+    C("c16-relu", "wino2_c16", "16>16h", ("relu",), ("head",), 32, both=True),
     C("c16-split8", "wino2_c16", "16>16h", ("relu", "none", 8), ("head",), 16),
     # ---- deliberate fallbacks under the default switches
     C("fallback-33to33-residual-to-direct", "direct", "33>33", ("relu",), ("res",), 32, 32),
