@@ -84,6 +84,11 @@ class TsdfIntegrateDesc(ctypes.Structure):
     ]
 
 
+class TsdfIntegrateColorDesc(ctypes.Structure):
+    """Mirror of struct estd_tsdf_integrate_color_desc (include/estd_hip.h)."""
+    _fields_ = TsdfIntegrateDesc._fields_ + [("color", ctypes.c_void_p), ("image", ctypes.c_void_p * 8)]
+
+
 class TsdfRaycastDesc(ctypes.Structure):
     """Mirror of struct estd_tsdf_raycast_desc (include/estd_hip.h)."""
     _fields_ = [
@@ -93,6 +98,11 @@ class TsdfRaycastDesc(ctypes.Structure):
         ("depth", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("out_weight", ctypes.c_void_p), ("stats", ctypes.c_void_p),
         ("mat", ctypes.c_float * 12),
     ]
+
+
+class TsdfRaycastColorDesc(ctypes.Structure):
+    """Mirror of struct estd_tsdf_raycast_color_desc (include/estd_hip.h)."""
+    _fields_ = TsdfRaycastDesc._fields_ + [("color", ctypes.c_void_p), ("out_color", ctypes.c_void_p)]
 
 
 _SIGNATURES = {
@@ -166,6 +176,10 @@ _SIGNATURES = {
                                                 ctypes.POINTER(ctypes.c_float), ctypes.c_float, ctypes.c_void_p, ctypes.c_longlong,
                                                 c_float_p, c_float_p, c_float_p, ctypes.c_void_p, c_stream]),
     "estd_tsdf_raycast": (ctypes.c_int, [ctypes.POINTER(TsdfRaycastDesc), c_stream]),
+    "estd_tsdf_integrate_color": (ctypes.c_int, [ctypes.POINTER(TsdfIntegrateColorDesc), c_stream]),
+    "estd_tsdf_edge_colors": (ctypes.c_int, [c_float_p, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong,
+                                             c_float_p, c_stream]),
+    "estd_tsdf_raycast_color": (ctypes.c_int, [ctypes.POINTER(TsdfRaycastColorDesc), c_stream]),
 }
 
 # the superseded A/B kernels: exported only by a library built with ESTD_BUILD_AB=1 (estdepth_amd/build.py)

@@ -432,6 +432,110 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> tsdf_raycast(const Tensor& volume, co
     return {depth, normal, weight, st};
 }
 
+// ------------------------------------------------------------------------------------------------ TSDF colour
+static void check_color_planes(const Tensor& color, const Tensor& volume, const char* op)
+{
+    TORCH_CHECK(color.dim() == 4 && color.size(0) == 3 && color.size(1) == volume.size(1) && color.size(2) == volume.size(2) &&
+                color.size(3) == volume.size(3), op, ": color must be [3,Z,Y,X] with the volume's Z, Y, X");
+    TORCH_CHECK(color.device() == volume.device(), op, ": color and the volume are on different devices");
+}
+
+// tsdf_integrate_ with colour: color [3,Z,Y,X] in place beside the volume; images: one [3,H,W] per depth map.
+Tensor tsdf_integrate_color_(Tensor volume, Tensor color, at::TensorList depths, at::TensorList confs, at::TensorList images, const Tensor& mats,
+                             double trunc, double z_near, double conf_min, bool weighted, double w_max, bool no_skip)
+{
+    const OpScope scope(volume);
+    TORCH_CHECK(volume.dim() == 4 && volume.size(0) == 2, "tsdf_integrate_color_: volume must be [2,Z,Y,X] (D plane, weight plane)");
+    float* vol = fptr_mut(volume, "volume");
+    check_color_planes(color, volume, "tsdf_integrate_color_");
+    float* col = fptr_mut(color, "color");
+    const int64_t Z = volume.size(1), Y = volume.size(2), X = volume.size(3);
+    TORCH_CHECK(X % 4 == 0, "tsdf_integrate_color_: X must be a multiple of 4, got ", X);
+    const int64_t T = (int64_t)depths.size();
+    TORCH_CHECK(T >= 1 && T <= ESTD_TSDF_MAX_FRAMES, "tsdf_integrate_color_: 1..", ESTD_TSDF_MAX_FRAMES, " frames per call, got ", T);
+    TORCH_CHECK(confs.empty() || (int64_t)confs.size() == T, "tsdf_integrate_color_: one confidence map per depth map (or none)");
+    TORCH_CHECK((int64_t)images.size() == T, "tsdf_integrate_color_: one image per depth map, got ", images.size(), " for ", T);
+    TORCH_CHECK(!weighted || !confs.empty(), "tsdf_integrate_color_: weighted fusion needs confidence maps");
+    TORCH_CHECK(mats.defined() && mats.device().is_cpu() && mats.scalar_type() == at::kFloat && mats.is_contiguous() && mats.numel() == T * 12,
+                "tsdf_integrate_color_: mats must be a contiguous CPU float32 tensor [T,12]");
+    TORCH_CHECK(depths[0].dim() >= 2, "tsdf_integrate_color_: depth maps must be [H,W] (leading 1s allowed)");
+    const int64_t H = depths[0].size(-2), W = depths[0].size(-1);
+    estd_tsdf_integrate_color_desc d{};
+    d.Z = (int)Z; d.Y = (int)Y; d.X = (int)X; d.T = (int)T; d.H = (int)H; d.W = (int)W;
+    d.weighted = weighted; d.no_skip = no_skip;
+    d.trunc = (float)trunc; d.z_near = (float)z_near; d.conf_min = (float)conf_min; d.w_max = (float)w_max;
+    d.tsdf = vol; d.weight = vol + Z * Y * X; d.color = col;
+    for (int64_t t = 0; t < T; ++t) {
+        TORCH_CHECK(depths[t].dim() >= 2 && depths[t].size(-2) == H && depths[t].size(-1) == W && depths[t].numel() == H * W,
+                    "tsdf_integrate_color_: depth map ", t, " must be [", H, ",", W, "]");
+        TORCH_CHECK(depths[t].device() == volume.device(), "tsdf_integrate_color_: depth map ", t, " is not on the volume's device");
+        d.depth[t] = fptr(depths[t], "depth map");
+        if (!confs.empty()) {
+            TORCH_CHECK(confs[t].dim() >= 2 && confs[t].size(-2) == H && confs[t].size(-1) == W && confs[t].numel() == H * W,
+                        "tsdf_integrate_color_: confidence map ", t, " must have the depth map's shape [", H, ",", W, "]");
+            TORCH_CHECK(confs[t].device() == volume.device(), "tsdf_integrate_color_: confidence map ", t, " is not on the volume's device");
+            d.conf[t] = fptr(confs[t], "confidence map");
+        }
+        TORCH_CHECK(images[t].dim() >= 3 && images[t].size(-3) == 3 && images[t].size(-2) == H && images[t].size(-1) == W &&
+                    images[t].numel() == 3 * H * W, "tsdf_integrate_color_: image ", t, " must be [3,", H, ",", W, "]");
+        TORCH_CHECK(images[t].device() == volume.device(), "tsdf_integrate_color_: image ", t, " is not on the volume's device");
+        d.image[t] = fptr(images[t], "image");
+        for (int i = 0; i < 12; ++i) d.mats[t][i] = mats.data_ptr<float>()[t * 12 + i];
+    }
+    check_status(estd_tsdf_integrate_color(&d, cur_stream()), "estd_tsdf_integrate_color");
+    return volume;
+}
+
+// edge: int64 [N] (the ids of tsdf_extract_points) -> colour at the crossings [N,3]
+Tensor tsdf_edge_colors(const Tensor& volume, const Tensor& color, const Tensor& edge)
+{
+    const OpScope scope(volume);
+    TORCH_CHECK(volume.dim() == 4 && volume.size(0) == 2, "tsdf_edge_colors: volume must be [2,Z,Y,X] (D plane, weight plane)");
+    const float* vol = fptr(volume, "volume");
+    check_color_planes(color, volume, "tsdf_edge_colors");
+    const float* col = fptr(color, "color");
+    const int64_t Z = volume.size(1), Y = volume.size(2), X = volume.size(3);
+    TORCH_CHECK(X % 4 == 0, "tsdf_edge_colors: X must be a multiple of 4, got ", X);
+    TORCH_CHECK(edge.defined() && edge.dim() == 1 && edge.scalar_type() == at::kLong && edge.is_contiguous() && edge.device() == volume.device(),
+                "tsdf_edge_colors: edge must be a contiguous int64 tensor [N] on the volume's device");
+    const int64_t n = edge.size(0);
+    Tensor out = new_f32({n, 3}, volume);
+    if (n)
+        check_status(estd_tsdf_edge_colors(vol, col, (int)Z, (int)Y, (int)X, reinterpret_cast<const long long*>(edge.data_ptr<int64_t>()),
+                                           (long long)n, out.data_ptr<float>(), cur_stream()), "estd_tsdf_edge_colors");
+    return out;
+}
+
+// tsdf_raycast with a colour map -> (depth [H,W], normal [H,W,3], weight [H,W], color [H,W,3])
+std::tuple<Tensor, Tensor, Tensor, Tensor> tsdf_raycast_color(const Tensor& volume, const Tensor& color, const Tensor& mat, int64_t H, int64_t W,
+                                                              double t_min, double dt, int64_t n_steps, double w_min)
+{
+    const OpScope scope(volume);
+    TORCH_CHECK(volume.dim() == 4 && volume.size(0) == 2, "tsdf_raycast_color: volume must be [2,Z,Y,X] (D plane, weight plane)");
+    const float* vol = fptr(volume, "volume");
+    check_color_planes(color, volume, "tsdf_raycast_color");
+    const float* col = fptr(color, "color");
+    const int64_t Z = volume.size(1), Y = volume.size(2), X = volume.size(3);
+    TORCH_CHECK(X % 4 == 0, "tsdf_raycast_color: X must be a multiple of 4, got ", X);
+    TORCH_CHECK(mat.defined() && mat.device().is_cpu() && mat.scalar_type() == at::kFloat && mat.is_contiguous() && mat.numel() == 12,
+                "tsdf_raycast_color: mat must be a contiguous CPU float32 tensor [12] (3x4 row-major)");
+    TORCH_CHECK(H > 0 && W > 0 && H * W <= 0x7fffffffLL, "tsdf_raycast_color: the image size must be positive (and H * W < 2^31), got ", H, " x ", W);
+    TORCH_CHECK(n_steps > 0 && n_steps <= (1 << 24), "tsdf_raycast_color: n_steps must be in 1..2^24, got ", n_steps);
+    TORCH_CHECK(std::isfinite(dt) && (float)dt > 0.f, "tsdf_raycast_color: dt must be positive and finite, got ", dt);
+    TORCH_CHECK(std::isfinite(t_min) && t_min >= 0, "tsdf_raycast_color: t_min must be finite and not negative, got ", t_min);
+    TORCH_CHECK(w_min == w_min, "tsdf_raycast_color: w_min must not be NaN");
+    Tensor depth = new_f32({H, W}, volume), normal = new_f32({H, W, 3}, volume), weight = new_f32({H, W}, volume), rgb = new_f32({H, W, 3}, volume);
+    estd_tsdf_raycast_color_desc d{};
+    d.Z = (int)Z; d.Y = (int)Y; d.X = (int)X; d.H = (int)H; d.W = (int)W; d.n_steps = (int)n_steps;
+    d.t_min = (float)t_min; d.dt = (float)dt; d.w_min = (float)w_min;
+    d.tsdf = vol; d.weight = vol + Z * Y * X; d.color = col;
+    d.depth = depth.data_ptr<float>(); d.normal = normal.data_ptr<float>(); d.out_weight = weight.data_ptr<float>();
+    d.out_color = rgb.data_ptr<float>();
+    for (int i = 0; i < 12; ++i) d.mat[i] = mat.data_ptr<float>()[i];
+    check_status(estd_tsdf_raycast_color(&d, cur_stream()), "estd_tsdf_raycast_color");
+    return {depth, normal, weight, rgb};
+}
+
 Tensor warp_attention(const Tensor& kv_target, at::TensorList kv_sources, const Tensor& mats, const Tensor& depth_values,
                       double depth_min, double depth_interval)
 {
@@ -862,6 +966,11 @@ TORCH_LIBRARY(estdepth_hip, m)
     m.def("tsdf_extract_points(Tensor volume, float voxel_size, Tensor origin, float w_min, int capacity) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("tsdf_raycast(Tensor volume, Tensor mat, int H, int W, float t_min, float dt, int n_steps, float w_min, bool stats) -> "
           "(Tensor, Tensor, Tensor, Tensor)");
+    m.def("tsdf_integrate_color_(Tensor(a!) volume, Tensor(b!) color, Tensor[] depths, Tensor[] confs, Tensor[] images, Tensor mats, float trunc, "
+          "float z_near, float conf_min, bool weighted, float w_max, bool no_skip) -> Tensor(a!)");
+    m.def("tsdf_edge_colors(Tensor volume, Tensor color, Tensor edge) -> Tensor");
+    m.def("tsdf_raycast_color(Tensor volume, Tensor color, Tensor mat, int H, int W, float t_min, float dt, int n_steps, float w_min) -> "
+          "(Tensor, Tensor, Tensor, Tensor)");
     m.def("profile_mark(int id) -> ()");
     m.def("set_reserved_cus(int n) -> int");
     m.def("conv3d_grid(int N, int D, int H, int W) -> int");
@@ -909,6 +1018,9 @@ TORCH_LIBRARY_IMPL(estdepth_hip, CUDA, m)
     m.impl("tsdf_integrate_", tsdf_integrate_);
     m.impl("tsdf_extract_points", tsdf_extract_points);
     m.impl("tsdf_raycast", tsdf_raycast);
+    m.impl("tsdf_integrate_color_", tsdf_integrate_color_);
+    m.impl("tsdf_edge_colors", tsdf_edge_colors);
+    m.impl("tsdf_raycast_color", tsdf_raycast_color);
 }
 
 TORCH_LIBRARY_IMPL(estdepth_hip, CPU, m)

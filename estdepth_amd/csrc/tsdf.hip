@@ -22,6 +22,13 @@
 // volume access at all (exec = 0 skips the block), and a 16-byte group no frame updates is neither read nor written.  The matrices, pointers
 // and constants are kernel arguments (uniform values in SGPRs); the depth / confidence gathers go through the ordinary cached path.
 // Offsets into the volume are 64-bit.
+//
+// estd_tsdf_integrate_color: the same kernel with COLOR set.  The colour volume is three more planes [3][Z][Y][X] that share the weight plane:
+//     C_k = fma(C_k, Wt, image[t][k][vi][ui] * w) / (Wt + w)            (Wt before the update of D, the pixel the depth was read at)
+// Phase 1 keeps the pixel index beside (tsdf, w) -- 32 registers, where 8 x 4 x 3 colours would take 96 -- and phase 2, where only updating
+// lanes run, gathers the three channels.  estd_tsdf_edge_colors blends the colour planes along the edges the extraction emitted.
+#include <type_traits>
+
 #include "estd_common.h"
 
 namespace {
@@ -38,9 +45,18 @@ struct IntegrateParams {
     float A[ESTD_TSDF_MAX_FRAMES][12];
 };
 
-// SKIP = false (the tool's ablation): every lane inside the volume loads and stores its voxels whether a frame updates them or not
-template <bool SKIP>
-__global__ __launch_bounds__(256) void tsdf_integrate_kernel(const IntegrateParams p)
+// the colour instances' arguments: the same fields first, then the three colour planes [3][Z][Y][X] and one [3][H][W] image per frame
+struct IntegrateColorParams : IntegrateParams {
+    float* C;
+    const float* image[ESTD_TSDF_MAX_FRAMES];
+};
+
+// SKIP = false (the tool's ablation): every lane inside the volume loads and stores its voxels whether a frame updates them or not.
+// COLOR (estd_tsdf_integrate_color): phase 1 also keeps the pixel it chose, phase 2 gathers that pixel's three channels -- only in lanes
+// that update, once per (frame, voxel) update -- and blends them with the weight the D update starts from; D and Wt take the same
+// operations in the same order as without colour.
+template <bool SKIP, bool COLOR>
+__global__ __launch_bounds__(256) void tsdf_integrate_kernel(const std::conditional_t<COLOR, IntegrateColorParams, IntegrateParams> p)
 {
     const int x0 = ((int)blockIdx.x * 16 + ((int)threadIdx.x & 15)) * 4;
     const int y = (int)blockIdx.y * 16 + ((int)threadIdx.x >> 4);
@@ -53,14 +69,20 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(const IntegratePara
 
     for (int z = z_begin; z < z_end; ++z) {
         const float fz = (float)z;
+        // COLOR: the per-frame arguments (12 + 3 x 2 SGPRs each, 144 for eight frames) do not fit the scalar registers beside the rest; an
+        // offset of zero the compiler cannot see through makes it fetch them from the argument segment where they are used, plane by
+        // plane (scalar loads that hit the scalar cache), instead of parking them all in VGPR lanes across the z loop
+        int fo = 0;
+        if constexpr (COLOR) asm volatile("s_mov_b32 %0, 0" : "=s"(fo));
         float ts[ESTD_TSDF_MAX_FRAMES][4], ws[ESTD_TSDF_MAX_FRAMES][4];
+        int px[COLOR ? ESTD_TSDF_MAX_FRAMES : 1][4];
         bool any = false;
 #pragma unroll
         for (int t = 0; t < ESTD_TSDF_MAX_FRAMES; ++t) {
 #pragma unroll
             for (int v = 0; v < 4; ++v) { ts[t][v] = 0.f; ws[t][v] = 0.f; }
             if (t < p.T && inside) {
-                const float* A = p.A[t];
+                const float* A = p.A[t + fo];
                 const float ra = fmaf(A[1], fy, fmaf(A[2], fz, A[3]));
                 const float rb = fmaf(A[5], fy, fmaf(A[6], fz, A[7]));
                 const float rc = fmaf(A[9], fy, fmaf(A[10], fz, A[11]));
@@ -77,11 +99,11 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(const IntegratePara
                     const float u = floorf(a / c + 0.5f), w = floorf(b / c + 0.5f);
                     if (!(u >= 0.f && u < fW && w >= 0.f && w < fH)) continue;
                     const int pix = (int)w * p.W + (int)u;
-                    const float d = p.depth[t][pix];
+                    const float d = p.depth[t + fo][pix];
                     if (!(d > 0.f && d < __builtin_inff())) continue;
                     float wgt = 1.f;
                     if (has_conf) {
-                        const float cf = p.conf[t][pix];
+                        const float cf = p.conf[t + fo][pix];
                         if (cf < p.conf_min) continue;
                         if (p.weighted) wgt = cf;
                         if (!(wgt > 0.f && wgt < __builtin_inff())) continue;       // a sample of zero (or undefined) weight carries nothing
@@ -90,6 +112,7 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(const IntegratePara
                     if (sdf < -p.trunc) continue;
                     ts[t][v] = fminf(1.f, sdf / p.trunc);
                     ws[t][v] = wgt;
+                    if constexpr (COLOR) px[t][v] = pix;
                     any = true;
                 }
             }
@@ -99,6 +122,16 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(const IntegratePara
             float4 d4 = *reinterpret_cast<const float4*>(p.D + off);
             float4 w4 = *reinterpret_cast<const float4*>(p.Wt + off);
             float dv[4] = {d4.x, d4.y, d4.z, d4.w}, wv[4] = {w4.x, w4.y, w4.z, w4.w};
+            float cv[COLOR ? 3 : 1][4];
+            const long long plane = (long long)p.Z * p.Y * p.X;
+            const long long hw = (long long)p.H * p.W;
+            if constexpr (COLOR) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const float4 c4 = *reinterpret_cast<const float4*>(p.C + k * plane + off);
+                    cv[k][0] = c4.x; cv[k][1] = c4.y; cv[k][2] = c4.z; cv[k][3] = c4.w;
+                }
+            }
 #pragma unroll
             for (int t = 0; t < ESTD_TSDF_MAX_FRAMES; ++t) {
                 if (t < p.T) {
@@ -106,6 +139,13 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(const IntegratePara
                     for (int v = 0; v < 4; ++v) {
                         if (ws[t][v] > 0.f) {
                             const float den = wv[v] + ws[t][v];
+                            if constexpr (COLOR) {
+#pragma unroll
+                                for (int k = 0; k < 3; ++k) {
+                                    const float col = p.image[t + fo][k * hw + px[t][v]];
+                                    cv[k][v] = fmaf(cv[k][v], wv[v], col * ws[t][v]) / den;
+                                }
+                            }
                             dv[v] = fmaf(dv[v], wv[v], ts[t][v] * ws[t][v]) / den;
                             wv[v] = fminf(den, p.w_max);
                         }
@@ -114,6 +154,11 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(const IntegratePara
             }
             *reinterpret_cast<float4*>(p.D + off) = make_float4(dv[0], dv[1], dv[2], dv[3]);
             *reinterpret_cast<float4*>(p.Wt + off) = make_float4(wv[0], wv[1], wv[2], wv[3]);
+            if constexpr (COLOR) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k)
+                    *reinterpret_cast<float4*>(p.C + k * plane + off) = make_float4(cv[k][0], cv[k][1], cv[k][2], cv[k][3]);
+            }
         }
     }
 }
@@ -215,6 +260,46 @@ __global__ __launch_bounds__(256) void tsdf_extract_kernel(const ExtractParams p
     }
 }
 
+struct EdgeColorParams {
+    int Z, Y, X;
+    long long n;
+    const float* D;
+    const float* C;
+    const long long* edge;
+    float* out;
+};
+
+// one lane per record: the colour at the crossing of edge id 3 * voxel + axis, blended with the s the extraction computed from the same
+// stored D values; an id outside the volume (or whose far end is) gives zeros
+__global__ __launch_bounds__(256) void tsdf_edge_colors_kernel(const EdgeColorParams p)
+{
+    const long long i = (long long)blockIdx.x * 256 + (long long)threadIdx.x;
+    if (i >= p.n) return;
+    const long long plane = (long long)p.Z * p.Y * p.X;
+    const long long e = p.edge[i];
+    float c[3] = {0.f, 0.f, 0.f};
+    if (e >= 0 && e < 3 * plane) {
+        const long long idx = e / 3;
+        const int k = (int)(e - 3 * idx);
+        const long long row = idx / p.X;
+        const int q[3] = {(int)(idx - row * p.X), (int)(row % p.Y), (int)(row / p.Y)};
+        const int dims[3] = {p.X, p.Y, p.Z};
+        const long long strides[3] = {1, p.X, (long long)p.X * p.Y};
+        if (q[k] + 1 < dims[k]) {
+            const long long far = idx + strides[k];
+            const float d0 = p.D[idx], d1 = p.D[far];
+            const float s = d0 / (d0 - d1);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const float c0 = p.C[j * plane + idx], c1 = p.C[j * plane + far];
+                c[j] = fmaf(s, c1 - c0, c0);
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) p.out[i * 3 + j] = c[j];
+}
+
 inline bool finite_pos(float v) { return v > 0.f && v < __builtin_inff(); }
 
 inline int check_dims(int Z, int Y, int X)
@@ -225,11 +310,11 @@ inline int check_dims(int Z, int Y, int X)
     return ESTD_OK;
 }
 
-}  // namespace
-
-extern "C" int estd_tsdf_integrate(const estd_tsdf_integrate_desc* d, estd_stream_t s)
+// the argument checks and the launch arguments the two integrate entry points share
+template <class Desc, class Params>
+inline int integrate_setup(const Desc* d, Params& p)
 {
-    if (!d || !d->tsdf || !d->weight) return ESTD_ERR_ARG;
+    if (!d->tsdf || !d->weight) return ESTD_ERR_ARG;
     if (d->T < 1 || d->T > ESTD_TSDF_MAX_FRAMES || d->H <= 0 || d->W <= 0) return ESTD_ERR_ARG;
     if ((long long)d->H * d->W > 0x7fffffffLL) return ESTD_ERR_ARG;
     if (!finite_pos(d->trunc) || !finite_pos(d->w_max) || !(d->z_near >= 0.f) || !(d->conf_min == d->conf_min)) return ESTD_ERR_ARG;
@@ -239,7 +324,6 @@ extern "C" int estd_tsdf_integrate(const estd_tsdf_integrate_desc* d, estd_strea
     }
     if (d->weighted && !d->conf[0]) return ESTD_ERR_ARG;
     if (const int st = check_dims(d->Z, d->Y, d->X)) return st;
-    IntegrateParams p;
     p.Z = d->Z; p.Y = d->Y; p.X = d->X; p.T = d->T; p.H = d->H; p.W = d->W; p.weighted = d->weighted != 0;
     p.trunc = d->trunc; p.z_near = d->z_near; p.conf_min = d->conf_min; p.w_max = d->w_max;
     p.D = d->tsdf; p.Wt = d->weight;
@@ -248,11 +332,57 @@ extern "C" int estd_tsdf_integrate(const estd_tsdf_integrate_desc* d, estd_strea
         p.conf[t] = t < d->T ? d->conf[t] : nullptr;
         for (int i = 0; i < 12; ++i) p.A[t][i] = t < d->T ? d->mats[t][i] : 0.f;
     }
-    const dim3 grid((unsigned)estd_ceil_div(d->X, 64), (unsigned)estd_ceil_div(d->Y, 16), (unsigned)estd_ceil_div(d->Z, ZCHUNK));
+    return ESTD_OK;
+}
+
+inline dim3 integrate_grid(int Z, int Y, int X)
+{
+    return dim3((unsigned)estd_ceil_div(X, 64), (unsigned)estd_ceil_div(Y, 16), (unsigned)estd_ceil_div(Z, ZCHUNK));
+}
+
+}  // namespace
+
+extern "C" int estd_tsdf_integrate(const estd_tsdf_integrate_desc* d, estd_stream_t s)
+{
+    if (!d) return ESTD_ERR_ARG;
+    IntegrateParams p;
+    if (const int st = integrate_setup(d, p)) return st;
+    const dim3 grid = integrate_grid(d->Z, d->Y, d->X);
     if (d->no_skip)
-        hipLaunchKernelGGL(tsdf_integrate_kernel<false>, grid, dim3(256), 0, estd_stream(s), p);
+        hipLaunchKernelGGL((tsdf_integrate_kernel<false, false>), grid, dim3(256), 0, estd_stream(s), p);
     else
-        hipLaunchKernelGGL(tsdf_integrate_kernel<true>, grid, dim3(256), 0, estd_stream(s), p);
+        hipLaunchKernelGGL((tsdf_integrate_kernel<true, false>), grid, dim3(256), 0, estd_stream(s), p);
+    return ESTD_LAUNCH_CHECK();
+}
+
+extern "C" int estd_tsdf_integrate_color(const estd_tsdf_integrate_color_desc* d, estd_stream_t s)
+{
+    if (!d || !d->color) return ESTD_ERR_ARG;
+    for (int t = 0; t < d->T && t < ESTD_TSDF_MAX_FRAMES; ++t)
+        if (!d->image[t]) return ESTD_ERR_ARG;
+    IntegrateColorParams p;
+    if (const int st = integrate_setup(d, p)) return st;
+    p.C = d->color;
+    for (int t = 0; t < ESTD_TSDF_MAX_FRAMES; ++t) p.image[t] = t < d->T ? d->image[t] : nullptr;
+    const dim3 grid = integrate_grid(d->Z, d->Y, d->X);
+    if (d->no_skip)
+        hipLaunchKernelGGL((tsdf_integrate_kernel<false, true>), grid, dim3(256), 0, estd_stream(s), p);
+    else
+        hipLaunchKernelGGL((tsdf_integrate_kernel<true, true>), grid, dim3(256), 0, estd_stream(s), p);
+    return ESTD_LAUNCH_CHECK();
+}
+
+extern "C" int estd_tsdf_edge_colors(const float* tsdf, const float* color, int Z, int Y, int X, const long long* edge, long long n, float* out,
+                                     estd_stream_t s)
+{
+    if (!tsdf || !color || n < 0) return ESTD_ERR_ARG;
+    if (n > 0 && (!edge || !out)) return ESTD_ERR_ARG;
+    if (const int st = check_dims(Z, Y, X)) return st;
+    if (n > 0x7fffffffLL * 256) return ESTD_ERR_UNSUPPORTED;          // one workgroup of 256 records per blockIdx.x
+    if (n == 0) return ESTD_OK;
+    EdgeColorParams p;
+    p.Z = Z; p.Y = Y; p.X = X; p.n = n; p.D = tsdf; p.C = color; p.edge = edge; p.out = out;
+    hipLaunchKernelGGL(tsdf_edge_colors_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, estd_stream(s), p);
     return ESTD_LAUNCH_CHECK();
 }
 

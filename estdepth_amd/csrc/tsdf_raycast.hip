@@ -23,6 +23,12 @@
 //   * a lane is done at its hit or past its interval, and the wave leaves the loop once all its lanes are done.
 // The matrix, pointers and constants are kernel arguments (uniform values in SGPRs); the gathers go through the ordinary cached path; offsets
 // into the volume are 64-bit.
+//
+// estd_tsdf_raycast_color: the same kernel with COLOR set.  That instance alone keeps the previous sample's cell base and fractions; at the hit
+// -- once per pixel, not per sample -- it gathers the 2 x 8 x 3 corner colours of the two cells, blends each cell the way Wb is blended and
+// writes fma(s, Cb_k - Cb_{k-1}, Cb_{k-1}).  Depth, normal and weight take the same operations as without colour.
+#include <type_traits>
+
 #include "estd_common.h"
 
 namespace {
@@ -39,7 +45,19 @@ struct RaycastParams {
     unsigned int* stats;
 };
 
+struct RaycastColorParams : RaycastParams {
+    const float* C;
+    float* color;
+};
+
 __device__ inline float lerpf(float a, float b, float f) { return fmaf(f, b - a, a); }
+
+// the trilinear blend (x, then y, then z: the nesting of Wb) of one plane at the cell whose first corner is c
+__device__ inline float blend_cell(const float* c, long long sy, long long sz, float fx, float fy, float fz)
+{
+    return lerpf(lerpf(lerpf(c[0], c[1], fx), lerpf(c[sy], c[sy + 1], fx), fy),
+                 lerpf(lerpf(c[sz], c[sz + 1], fx), lerpf(c[sz + sy], c[sz + sy + 1], fx), fy), fz);
+}
 
 __device__ inline int wave_min(int v)
 {
@@ -56,8 +74,8 @@ __device__ inline int wave_max(int v)
 }
 
 // STATS (the bench tool's counters): per pixel the samples whose weights were probed and the samples whose D values were gathered
-template <bool STATS>
-__global__ __launch_bounds__(256) void tsdf_raycast_kernel(const RaycastParams p)
+template <bool STATS, bool COLOR>
+__global__ __launch_bounds__(256) void tsdf_raycast_kernel(const std::conditional_t<COLOR, RaycastColorParams, RaycastParams> p)
 {
     // workgroup id -> 16 x 16 tile, row-major within the band of its XCD: ids b, b + 8, b + 16, ... share an XCD
     const int b = (int)blockIdx.x;
@@ -112,12 +130,16 @@ __global__ __launch_bounds__(256) void tsdf_raycast_kernel(const RaycastParams p
     float F_p = 0.f, Wb_p = 0.f, G_p[3] = {0.f, 0.f, 0.f}, t_p = 0.f;
     float out_depth = 0.f, out_weight = 0.f, out_n[3] = {0.f, 0.f, 0.f};
     unsigned int n_probed = 0, n_gathered = 0;
+    long long base_p = 0;                                   // COLOR only: the previous sample's cell and fractions
+    float f_p[3] = {0.f, 0.f, 0.f}, out_c[3] = {0.f, 0.f, 0.f};
 
     for (int k = k_begin; k <= k_end; ++k) {
         if (__all(done)) break;
         const float t = fmaf((float)k, p.dt, p.t_min);
         bool obs = false;
         float F = 0.f, Wb = 0.f, G[3] = {0.f, 0.f, 0.f};
+        long long base_k = 0;
+        float f_k[3] = {0.f, 0.f, 0.f};
         if (!done && k >= k_lo) {
             const float px = fmaf(t, r[0], o[0]), py = fmaf(t, r[1], o[1]), pz = fmaf(t, r[2], o[2]);
             const float ix = floorf(px), iy = floorf(py), iz = floorf(pz);
@@ -143,6 +165,7 @@ __global__ __launch_bounds__(256) void tsdf_raycast_kernel(const RaycastParams p
                     G[2] = c1 - c0;
                     Wb = lerpf(lerpf(lerpf(w000, w100, fx), lerpf(w010, w110, fx), fy),
                                lerpf(lerpf(w001, w101, fx), lerpf(w011, w111, fx), fy), fz);
+                    if constexpr (COLOR) { base_k = base; f_k[0] = fx; f_k[1] = fy; f_k[2] = fz; }
                     obs = true;
                 }
             }
@@ -157,11 +180,25 @@ __global__ __launch_bounds__(256) void tsdf_raycast_kernel(const RaycastParams p
 #pragma unroll
             for (int j = 0; j < 3; ++j) out_n[j] = len > 0.f ? g[j] / len : 0.f;
             out_weight = fmaf(s, Wb - Wb_p, Wb_p);
+            if constexpr (COLOR) {
+                const long long plane = (long long)p.Z * p.Y * p.X;
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    const float c0 = blend_cell(p.C + j * plane + base_p, sy, sz, f_p[0], f_p[1], f_p[2]);
+                    const float c1 = blend_cell(p.C + j * plane + base_k, sy, sz, f_k[0], f_k[1], f_k[2]);
+                    out_c[j] = fmaf(s, c1 - c0, c0);
+                }
+            }
             done = true;
         }
         obs_p = obs; F_p = F; Wb_p = Wb; t_p = t;
 #pragma unroll
         for (int j = 0; j < 3; ++j) G_p[j] = G[j];
+        if constexpr (COLOR) {
+            base_p = base_k;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) f_p[j] = f_k[j];
+        }
         if (k >= k_hi) done = true;
     }
 
@@ -171,6 +208,10 @@ __global__ __launch_bounds__(256) void tsdf_raycast_kernel(const RaycastParams p
         p.weight[pix] = out_weight;
 #pragma unroll
         for (int j = 0; j < 3; ++j) p.normal[pix * 3 + j] = out_n[j];
+        if constexpr (COLOR) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) p.color[pix * 3 + j] = out_c[j];
+        }
         if (STATS) {
             p.stats[pix * 2] = n_probed;
             p.stats[pix * 2 + 1] = n_gathered;
@@ -180,29 +221,50 @@ __global__ __launch_bounds__(256) void tsdf_raycast_kernel(const RaycastParams p
 
 inline bool finite_f(float v) { return v - v == 0.f; }
 
-}  // namespace
-
-extern "C" int estd_tsdf_raycast(const estd_tsdf_raycast_desc* d, estd_stream_t s)
+template <class Desc, class Params>
+inline int raycast_setup(const Desc* d, Params& p)
 {
-    if (!d || !d->tsdf || !d->weight || !d->depth || !d->normal || !d->out_weight) return ESTD_ERR_ARG;
+    if (!d->tsdf || !d->weight || !d->depth || !d->normal || !d->out_weight) return ESTD_ERR_ARG;
     if (d->H <= 0 || d->W <= 0 || d->n_steps <= 0) return ESTD_ERR_ARG;
     if (!finite_f(d->dt) || !(d->dt > 0.f) || !finite_f(d->t_min) || !(d->t_min >= 0.f) || !(d->w_min == d->w_min)) return ESTD_ERR_ARG;
     for (int i = 0; i < 12; ++i)
         if (!finite_f(d->mat[i])) return ESTD_ERR_ARG;
     if (d->Z <= 0 || d->Y <= 0 || d->X <= 0 || (d->X & 3)) return ESTD_ERR_ARG;
-    // the volume limits of the other two entry points; one workgroup per 16 x 16 pixels on blockIdx.x; k is exact in fp32 up to 2^24
+    // the volume limits of the other entry points; one workgroup per 16 x 16 pixels on blockIdx.x; k is exact in fp32 up to 2^24
     if (d->Z > 65535 || d->Y > 65535 * 4 || d->X > (1 << 20)) return ESTD_ERR_UNSUPPORTED;
     if ((long long)d->H * d->W > 0x7fffffffLL || d->n_steps > (1 << 24)) return ESTD_ERR_UNSUPPORTED;
-    RaycastParams p;
     p.Z = d->Z; p.Y = d->Y; p.X = d->X; p.H = d->H; p.W = d->W; p.n_steps = d->n_steps;
     p.tiles_x = estd_ceil_div(d->W, 16);
     p.n_blocks = p.tiles_x * estd_ceil_div(d->H, 16);
     p.t_min = d->t_min; p.dt = d->dt; p.w_min = d->w_min;
     for (int i = 0; i < 12; ++i) p.M[i] = d->mat[i];
     p.D = d->tsdf; p.Wt = d->weight; p.depth = d->depth; p.normal = d->normal; p.weight = d->out_weight; p.stats = d->stats;
+    return ESTD_OK;
+}
+
+}  // namespace
+
+extern "C" int estd_tsdf_raycast(const estd_tsdf_raycast_desc* d, estd_stream_t s)
+{
+    if (!d) return ESTD_ERR_ARG;
+    RaycastParams p;
+    if (const int st = raycast_setup(d, p)) return st;
     if (d->stats)
-        hipLaunchKernelGGL(tsdf_raycast_kernel<true>, dim3((unsigned)p.n_blocks), dim3(256), 0, estd_stream(s), p);
+        hipLaunchKernelGGL((tsdf_raycast_kernel<true, false>), dim3((unsigned)p.n_blocks), dim3(256), 0, estd_stream(s), p);
     else
-        hipLaunchKernelGGL(tsdf_raycast_kernel<false>, dim3((unsigned)p.n_blocks), dim3(256), 0, estd_stream(s), p);
+        hipLaunchKernelGGL((tsdf_raycast_kernel<false, false>), dim3((unsigned)p.n_blocks), dim3(256), 0, estd_stream(s), p);
+    return ESTD_LAUNCH_CHECK();
+}
+
+extern "C" int estd_tsdf_raycast_color(const estd_tsdf_raycast_color_desc* d, estd_stream_t s)
+{
+    if (!d || !d->color || !d->out_color) return ESTD_ERR_ARG;
+    RaycastColorParams p;
+    if (const int st = raycast_setup(d, p)) return st;
+    p.C = d->color; p.color = d->out_color;
+    if (d->stats)
+        hipLaunchKernelGGL((tsdf_raycast_kernel<true, true>), dim3((unsigned)p.n_blocks), dim3(256), 0, estd_stream(s), p);
+    else
+        hipLaunchKernelGGL((tsdf_raycast_kernel<false, true>), dim3((unsigned)p.n_blocks), dim3(256), 0, estd_stream(s), p);
     return ESTD_LAUNCH_CHECK();
 }

@@ -9,6 +9,9 @@
     vol.save_ply("scene.ply")
     maps = vol.render(pose, K, (H, W))                              # depth / normal / weight of the fused surface in any camera
 
+Colour: ``TSDFVolume(..., color=True)`` keeps the frames' colour beside the distances -- pass ``imgs=clip.imgs`` to ``integrate_outputs`` (or
+``images=`` to ``integrate``); ``extract_points`` and ``render`` then return a ``"color"`` entry and ``save_ply`` writes red / green / blue.
+
 Which frames are fused: target ``t`` of a call is frame ``t + 1`` of its ``cam_poses``.  ``JointStream`` clips advance by ``seq_len - 2`` frames
 and their targets are the INNER frames 1 .. seq_len - 2, so consecutive clips hand over disjoint targets and no frame is fused twice;
 ``ESTMStream.push`` returns one target (the window's middle frame) per push, each frame once.  Both keep their signatures and results: pass
@@ -16,11 +19,14 @@ what they return to ``integrate_outputs`` together with the poses of the same wi
 
 The volume is one float32 tensor ``[2, Z, Y, X]`` (plane 0 = D in [-1, 1], plane 1 = weight; x fastest; zeros = empty); voxel ``(ix, iy, iz)`` has
 its centre at ``origin + (idx + 0.5) * voxel_size``.  All arithmetic is csrc/tsdf.hip's and csrc/tsdf_raycast.hip's (the contract: include/estd_hip.h); there is no CPU
-path.  ``integrate`` only READS the maps, on the current stream -- the static output buffers of ``GraphedForward(clone_outputs=False)`` can
+path.  A colour volume adds ``self.color``, float32 ``[3, Z, Y, X]`` (12 more bytes per voxel: 201 MB at 256^3 beside the volume's 134 MB), the
+weighted average of the image values at the pixels the depths were read at, with the SAME weight plane; values are kept as they are given
+(0..255, 0..1 or normalised), so ``save_ply(color_scale=, color_offset=)`` maps them to 0..255 at export.  ``integrate`` only READS the maps, on the current stream -- the static output buffers of ``GraphedForward(clone_outputs=False)`` can
 be passed as they are, before the next forward overwrites them.
 """
 import math
 
+import numpy as np
 import torch
 
 from . import camera, ops
@@ -44,10 +50,28 @@ def _as_maps(x, name):
     return list(x)
 
 
+def _as_images(x):
+    """[T,3,H,W] tensor or a list of [3,H,W] / [1,3,H,W] images -> list of T tensors"""
+    if isinstance(x, torch.Tensor):
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise RuntimeError("images must be [T,3,H,W], got %s" % (tuple(x.shape),))
+        return [x[t] for t in range(x.shape[0])]
+    return list(x)
+
+
+def _three(v, name):
+    """a scalar or three values -> float64 array [3]"""
+    a = np.asarray(v, dtype=np.float64).reshape(-1)
+    if a.size not in (1, 3):
+        raise RuntimeError("%s must be a scalar or three values, got %r" % (name, v))
+    return np.broadcast_to(a, (3,)) if a.size == 1 else a
+
+
 class TSDFVolume:
-    def __init__(self, dims, voxel_size, origin, trunc=None, w_max=64.0, z_near=1e-3, device="cuda:0"):
+    def __init__(self, dims, voxel_size, origin, trunc=None, w_max=64.0, z_near=1e-3, device="cuda:0", color=False):
         """dims (Z, Y, X) voxels, X a multiple of 4; ``origin`` (x0, y0, z0) = world position of the corner of voxel (0, 0, 0);
-        ``trunc`` in metres (default: 4 voxels)."""
+        ``trunc`` in metres (default: 4 voxels).  ``color=True`` allocates the colour planes ``self.color`` [3,Z,Y,X] (12 bytes per voxel,
+        201 MB at 256^3); every ``integrate`` call then needs the frames' images."""
         dims = tuple(int(d) for d in dims)
         if len(dims) != 3 or min(dims) <= 0:
             raise RuntimeError("TSDFVolume: dims must be three positive sizes (Z, Y, X), got %r" % (dims,))
@@ -69,11 +93,13 @@ class TSDFVolume:
         if self.device.type != "cuda":
             raise RuntimeError("TSDFVolume lives on a ROCm device (estdepth_amd has no CPU path); got %s" % self.device)
         self.volume = torch.zeros((2,) + dims, device=self.device, dtype=torch.float32)
+        self.color = torch.zeros((3,) + dims, device=self.device, dtype=torch.float32) if color else None
 
     # ------------------------------------------------------------------------------------------------ fusion
     @staticmethod
-    def check_frames(depths, cam_poses, cam_intr, conf=None, weighted=False):
-        """argument checks of integrate() that need no device -> (depth list, conf list, poses [T,4,4], T)"""
+    def check_frames(depths, cam_poses, cam_intr, conf=None, weighted=False, images=None):
+        """argument checks of integrate() that need no device -> (depth list, conf list, poses [T,4,4], T); with ``images`` the list of
+        [3,H,W] images is appended"""
         depths = _as_maps(depths, "depths")
         confs = _as_maps(conf, "conf") if conf is not None else []
         n = len(depths)
@@ -92,25 +118,50 @@ class TSDFVolume:
         for i, m in enumerate(depths + confs):
             if tuple(m.shape[-2:]) != hw or m.numel() != hw[0] * hw[1]:
                 raise RuntimeError("integrate: %s map %d is %s, expected %s" % ("depth" if i < n else "confidence", i % n, tuple(m.shape), hw))
-        return depths, confs, poses, n
+        if images is None:
+            return depths, confs, poses, n
+        images = _as_images(images)
+        if len(images) != n:
+            raise RuntimeError("integrate: %d depth maps but %d images" % (n, len(images)))
+        for i, m in enumerate(images):
+            if not isinstance(m, torch.Tensor) or m.dim() < 3 or tuple(m.shape[-3:]) != (3,) + hw or m.numel() != 3 * hw[0] * hw[1]:
+                raise RuntimeError("integrate: image %d is %s, expected %s (the depth maps' size)" % (i, tuple(getattr(m, "shape", ())), (3,) + hw))
+            if m.device != depths[i].device:
+                raise RuntimeError("integrate: image %d is on %s but its depth map on %s" % (i, m.device, depths[i].device))
+            if m.dtype != torch.float32:
+                raise RuntimeError("integrate: image %d must be float32, got %s" % (i, m.dtype))
+        return depths, confs, poses, n, images
 
-    def integrate(self, depths, cam_poses, cam_intr, conf=None, conf_min=0.0, weighted=False):
+    def integrate(self, depths, cam_poses, cam_intr, conf=None, conf_min=0.0, weighted=False, images=None):
         """depths [T,H,W] / [T,1,H,W] (or a list of maps), cam_poses [T,4,4] camera-to-world, cam_intr [3,3] / [T,3,3] in pixels of the maps;
         ``conf``: confidence maps of the same shape -- samples below ``conf_min`` are skipped, ``weighted`` uses them as weights.
-        More than 8 frames are fused in groups of 8, in order."""
-        depths, confs, poses, n = self.check_frames(depths, cam_poses, cam_intr, conf, weighted)
+        More than 8 frames are fused in groups of 8, in order.  ``images`` [T,3,H,W] (or a list of [3,H,W]): the frames the maps belong
+        to, at the maps' size -- required by a colour volume (weight and colour would drift apart without), an error for any other."""
+        if (images is None) != (self.color is None):
+            raise RuntimeError("integrate: a colour volume needs images= with every call" if images is None else
+                               "integrate: images= given but the volume has no colour (TSDFVolume(..., color=True))")
+        if images is None:
+            depths, confs, poses, n = self.check_frames(depths, cam_poses, cam_intr, conf, weighted)
+        else:
+            depths, confs, poses, n, images = self.check_frames(depths, cam_poses, cam_intr, conf, weighted, images)
         mats = camera.tsdf_matrices(poses, cam_intr, self.origin, self.voxel_size)
         for a, b in frame_groups(n):
-            ops.tsdf_integrate_(self.volume, [d.contiguous() for d in depths[a:b]], [c.contiguous() for c in confs[a:b]], mats[a:b].contiguous(),
-                                self.trunc, self.z_near, conf_min, weighted, self.w_max)
+            dd, cc = [d.contiguous() for d in depths[a:b]], [c.contiguous() for c in confs[a:b]]
+            if images is None:
+                ops.tsdf_integrate_(self.volume, dd, cc, mats[a:b].contiguous(), self.trunc, self.z_near, conf_min, weighted, self.w_max)
+            else:
+                ops.tsdf_integrate_color_(self.volume, self.color, dd, cc, [m.contiguous() for m in images[a:b]], mats[a:b].contiguous(),
+                                          self.trunc, self.z_near, conf_min, weighted, self.w_max)
         self.frames += n
         return self
 
-    def integrate_outputs(self, outputs, cam_poses, cam_intr, scale=0, conf_min=0.0, weighted=False, image_hw=None):
+    def integrate_outputs(self, outputs, cam_poses, cam_intr, scale=0, conf_min=0.0, weighted=False, image_hw=None, imgs=None):
         """The output dict of ``DepthNetHybrid.forward`` (or of the streams) as it is: ("depth", t, scale) and ("fused_prob", t) of every
         target t = frame t + 1 of ``cam_poses`` [1,V,4,4]; ONE integrate call (for up to 8 targets).  ``cam_intr`` [1,3,3] belongs to the
         input images; the decoder returns every scale's depth map at the images' resolution, so it applies as it is -- for maps of another
-        size pass the images' ``image_hw`` and rows 0, 1 are scaled to the maps' the way ``scale_cam_intr`` does."""
+        size pass the images' ``image_hw`` and rows 0, 1 are scaled to the maps' the way ``scale_cam_intr`` does.  ``imgs``: the forward's
+        own [1,V,3,H,W] images for a colour volume -- target t takes ``imgs[0, t + 1]`` as it lies (no copy); they must have the depth
+        maps' size."""
         n = 0
         while ("depth", n, scale) in outputs:
             n += 1
@@ -135,19 +186,30 @@ class TSDFVolume:
                     raise RuntimeError("integrate_outputs: fused_prob %s does not divide the depth map %s" % ((ch, cw), (h, w)))
                 c = c.reshape(ch, cw).repeat_interleave(h // ch, 0).repeat_interleave(w // cw, 1)
             confs.append(c)
-        return self.integrate(depths, poses[1:n + 1], k, conf=confs, conf_min=conf_min, weighted=weighted)
+        images = None
+        if imgs is not None:
+            if not isinstance(imgs, torch.Tensor) or imgs.dim() != 5 or imgs.shape[0] != 1 or imgs.shape[1] != n + 2 or imgs.shape[2] != 3:
+                raise RuntimeError("integrate_outputs: imgs must be [1,%d,3,H,W], got %s" % (n + 2, tuple(getattr(imgs, "shape", ()))))
+            if tuple(imgs.shape[-2:]) != (h, w):
+                raise RuntimeError("integrate_outputs: images %s and depth maps %s differ in size" % (tuple(imgs.shape[-2:]), (h, w)))
+            images = [imgs[0, t + 1] for t in range(n)]
+        return self.integrate(depths, poses[1:n + 1], k, conf=confs, conf_min=conf_min, weighted=weighted, images=images)
 
     # ------------------------------------------------------------------------------------------------ read-back
     def extract_points(self, w_min=1.0, capacity=None):
         """Zero crossings between voxels of weight >= ``w_min`` -> dict(xyz [N,3], normal [N,3], weight [N], edge [N] int64, count) on
         the device; ``edge`` = 3 * linear voxel index + axis makes the unordered records sortable.  ``capacity=None`` counts first and
-        allocates exactly; a smaller ``capacity`` keeps that many records (``count`` is the total either way)."""
+        allocates exactly; a smaller ``capacity`` keeps that many records (``count`` is the total either way).  A colour volume adds
+        ``color`` [N,3]: the colour planes blended along each edge with the crossing's own s."""
         if capacity is None:
             capacity = int(ops.tsdf_extract_points(self.volume, self.voxel_size, self.origin, w_min, 0)[0].item())
         count, xyz, normal, weight, edge = ops.tsdf_extract_points(self.volume, self.voxel_size, self.origin, w_min, int(capacity))
         total = int(count.item())
         n = min(total, int(capacity))
-        return {"xyz": xyz[:n], "normal": normal[:n], "weight": weight[:n], "edge": edge[:n], "count": total}
+        out = {"xyz": xyz[:n], "normal": normal[:n], "weight": weight[:n], "edge": edge[:n], "count": total}
+        if self.color is not None:
+            out["color"] = ops.tsdf_edge_colors(self.volume, self.color, out["edge"].contiguous())
+        return out
 
     def render(self, cam_pose, cam_intr, image_hw, depth_min=None, depth_max=None, step=None, w_min=1.0):
         """The fused surface as the camera ``cam_pose`` [4,4] (camera-to-world) with ``cam_intr`` [3,3] (pixels of an ``image_hw`` = (H, W)
@@ -156,28 +218,43 @@ class TSDFVolume:
         world axes towards the cameras that saw the surface, and the interpolated fusion weight; all zeros where a ray finds no surface
         between voxels of weight >= ``w_min``.  A pose stack [V,4,4] (``cam_intr`` [3,3] or [V,3,3]) renders V views: leading dimension V.
         Rays are sampled every ``step`` metres of z-depth (default: one voxel) from ``depth_min`` (default: the volume's ``z_near``) to
-        ``depth_max`` (default: past the farthest corner of the volume, per view).  The contract: include/estd_hip.h, estd_tsdf_raycast."""
+        ``depth_max`` (default: past the farthest corner of the volume, per view).  A colour volume adds ``color`` [H,W,3] ([V,H,W,3]): the
+        fused colour at the hit, zeros without one.  The contract: include/estd_hip.h, estd_tsdf_raycast / estd_tsdf_raycast_color."""
         mats, (H, W), t_min, dt, n_steps, stacked = render_plan(self.dims, self.voxel_size, self.origin, self.z_near, cam_pose, cam_intr, image_hw,
                                                                 depth_min, depth_max, step, w_min)
-        views = [ops.tsdf_raycast(self.volume, mats[i].contiguous(), H, W, t_min, dt, n_steps[i], w_min) for i in range(mats.shape[0])]
+        if self.color is None:
+            names = ("depth", "normal", "weight")
+            views = [ops.tsdf_raycast(self.volume, mats[i].contiguous(), H, W, t_min, dt, n_steps[i], w_min) for i in range(mats.shape[0])]
+        else:
+            names = ("depth", "normal", "weight", "color")
+            views = [ops.tsdf_raycast_color(self.volume, self.color, mats[i].contiguous(), H, W, t_min, dt, n_steps[i], w_min)
+                     for i in range(mats.shape[0])]
         if not stacked:
-            return dict(zip(("depth", "normal", "weight"), views[0]))
-        return {name: torch.stack([v[j] for v in views]) for j, name in enumerate(("depth", "normal", "weight"))}
+            return dict(zip(names, views[0]))
+        return {name: torch.stack([v[j] for v in views]) for j, name in enumerate(names)}
 
     def fused_voxels(self):
         """voxels some frame has updated"""
         return int((self.volume[1] > 0).sum().item())
 
-    def save_ply(self, path, w_min=1.0):
-        """binary little-endian PLY with normals (host side); returns the number of points"""
+    def save_ply(self, path, w_min=1.0, color_scale=1.0, color_offset=0.0):
+        """binary little-endian PLY with normals (host side); returns the number of points.  A colour volume appends uchar red / green /
+        blue = clamp(round(c * color_scale + color_offset), 0, 255); ``color_scale`` / ``color_offset``: a scalar or three values (one per
+        channel), e.g. 255 for 0..1 images or (255 std, 255 mean) to undo a normalisation."""
         pts = self.extract_points(w_min=w_min)
         order = torch.argsort(pts["edge"])
         rec = torch.cat([pts["xyz"][order], pts["normal"][order]], 1).cpu().contiguous()
-        write_ply(path, rec.numpy())
+        rgb = None
+        if self.color is not None:
+            c = pts["color"][order].cpu().numpy().astype(np.float64) * _three(color_scale, "color_scale") + _three(color_offset, "color_offset")
+            rgb = np.clip(np.rint(np.nan_to_num(c)), 0, 255).astype(np.uint8)
+        write_ply(path, rec.numpy(), rgb)
         return rec.shape[0]
 
     def reset(self):
         self.volume.zero_()
+        if self.color is not None:
+            self.color.zero_()
         self.frames = 0
         return self
 
@@ -224,14 +301,25 @@ def render_plan(dims, voxel_size, origin, z_near, cam_pose, cam_intr, image_hw, 
     return mats, (H, W), t_min, dt, n_steps, stacked
 
 
-def write_ply(path, xyz_normal):
-    """xyz_normal: float32 array [N,6] -> binary little-endian PLY (x y z nx ny nz)"""
+def write_ply(path, xyz_normal, rgb=None):
+    """xyz_normal: float32 array [N,6] -> binary little-endian PLY (x y z nx ny nz); ``rgb``: uint8 array [N,3] appends uchar red green
+    blue to every vertex (27 bytes per record)"""
     n = int(xyz_normal.shape[0])
     head = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
-            "property float nx\nproperty float ny\nproperty float nz\nend_header\n" % n)
+            "property float nx\nproperty float ny\nproperty float nz\n" % n)
+    if rgb is None:
+        body = xyz_normal.astype("<f4").tobytes()
+    else:
+        rgb = np.asarray(rgb)
+        if rgb.shape != (n, 3) or rgb.dtype != np.uint8:
+            raise RuntimeError("write_ply: rgb must be uint8 [%d,3], got %s %s" % (n, rgb.dtype, rgb.shape))
+        head += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+        rec = np.empty(n, dtype=[("v", "<f4", (6,)), ("c", "u1", (3,))])
+        rec["v"], rec["c"] = xyz_normal, rgb
+        body = rec.tobytes()
     with open(path, "wb") as f:
-        f.write(head.encode("ascii"))
-        f.write(xyz_normal.astype("<f4").tobytes())
+        f.write((head + "end_header\n").encode("ascii"))
+        f.write(body)
 
 
 def frustum_volume(cam_pose, cam_intr, image_hw, depth_min, depth_max, dims, voxel_size):

@@ -1094,3 +1094,113 @@ def tsdf_raycast(volume, mat, H, W, t_min, dt, n_steps, w_min, stats=False):
             d.mat[i] = v
         N.check(N.lib().estd_tsdf_raycast(ctypes.byref(d), _stream()), "estd_tsdf_raycast")
     return (depth, normal, weight, st) if stats else (depth, normal, weight)
+
+
+# ---------------------------------------------------------------------------------- TSDF colour (csrc/tsdf.hip, csrc/tsdf_raycast.hip)
+def _color_planes(color, volume, op):
+    _need(isinstance(color, torch.Tensor) and color.dim() == 4 and color.shape[0] == 3 and tuple(color.shape[1:]) == tuple(volume.shape[1:]),
+          "%s: color must be [3,Z,Y,X] with the volume's Z, Y, X" % op)
+    _chk(color, "color")
+    _need(color.device == volume.device, "%s: color is on %s but the volume on %s" % (op, color.device, volume.device))
+
+
+def tsdf_integrate_color_(volume, color, depths, confs, images, mats, trunc, z_near, conf_min, weighted, w_max, no_skip=False):
+    """tsdf_integrate_ with colour, in place on ``volume`` [2,Z,Y,X] and ``color`` [3,Z,Y,X]: ``images`` is one [3,H,W] device tensor per depth
+    map (the frame the map belongs to, at the map's size).  D and the weight come out as from tsdf_integrate_; the colour planes share the
+    weight plane.  The contract is spelled out in include/estd_hip.h (estd_tsdf_integrate_color)."""
+    depths, confs, images = list(depths), list(confs) if confs is not None else [], list(images)
+    if _use_torch():
+        return T().tsdf_integrate_color_(volume, color, depths, confs, images, mats, float(trunc), float(z_near), float(conf_min), bool(weighted),
+                                         float(w_max), bool(no_skip))
+    _need(isinstance(volume, torch.Tensor) and volume.dim() == 4 and volume.shape[0] == 2, "tsdf_integrate_color_: volume must be [2,Z,Y,X] (D plane, weight plane)")
+    _chk(volume, "volume")
+    _color_planes(color, volume, "tsdf_integrate_color_")
+    Z, Y, X = volume.shape[1:]
+    _need(X % 4 == 0, "tsdf_integrate_color_: X must be a multiple of 4, got %d" % X)
+    n = len(depths)
+    _need(1 <= n <= TSDF_MAX_FRAMES, "tsdf_integrate_color_: 1..%d frames per call, got %d" % (TSDF_MAX_FRAMES, n))
+    _need(len(confs) in (0, n), "tsdf_integrate_color_: one confidence map per depth map (or none)")
+    _need(len(images) == n, "tsdf_integrate_color_: one image per depth map, got %d for %d" % (len(images), n))
+    _need(not weighted or confs, "tsdf_integrate_color_: weighted fusion needs confidence maps")
+    _need(isinstance(mats, torch.Tensor) and not mats.is_cuda and mats.dtype == torch.float32 and mats.is_contiguous() and mats.numel() == n * 12,
+          "tsdf_integrate_color_: mats must be a contiguous CPU float32 tensor [T,12]")
+    _need(isinstance(depths[0], torch.Tensor) and depths[0].dim() >= 2, "tsdf_integrate_color_: depth maps must be [H,W] (leading 1s allowed)")
+    H, W = depths[0].shape[-2:]
+    _maps(depths, "depth map", H, W)
+    _maps(confs, "confidence map", H, W)
+    for i, t in enumerate(images):
+        _chk(t, "image %d" % i)
+        _need(t.dim() >= 3 and tuple(t.shape[-3:]) == (3, H, W) and t.numel() == 3 * H * W, "tsdf_integrate_color_: image %d must be [3,%d,%d], got %s"
+              % (i, H, W, tuple(t.shape)))
+    for t in depths + confs + images:
+        _need(t.device == volume.device, "tsdf_integrate_color_: a map is on %s but the volume on %s" % (t.device, volume.device))
+    d = N.TsdfIntegrateColorDesc()
+    d.Z, d.Y, d.X, d.T, d.H, d.W = Z, Y, X, n, H, W
+    d.weighted, d.no_skip = int(bool(weighted)), int(bool(no_skip))
+    d.trunc, d.z_near, d.conf_min, d.w_max = float(trunc), float(z_near), float(conf_min), float(w_max)
+    d.tsdf, d.weight, d.color = volume.data_ptr(), volume.data_ptr() + 4 * Z * Y * X, color.data_ptr()
+    flat = mats.reshape(-1).tolist()
+    for t in range(n):
+        d.depth[t] = depths[t].data_ptr()
+        d.conf[t] = confs[t].data_ptr() if confs else None
+        d.image[t] = images[t].data_ptr()
+        for i in range(12):
+            d.mats[t][i] = flat[t * 12 + i]
+    with torch.cuda.device(volume.device):
+        N.check(N.lib().estd_tsdf_integrate_color(ctypes.byref(d), _stream()), "estd_tsdf_integrate_color")
+    return volume
+
+
+def tsdf_edge_colors(volume, color, edge):
+    """The colour at the crossings ``edge`` [N] int64 (the ids tsdf_extract_points returns) of ``volume`` [2,Z,Y,X] / ``color`` [3,Z,Y,X]
+    -> [N,3] on the device; an id outside the volume gives zeros (include/estd_hip.h, estd_tsdf_edge_colors)."""
+    if _use_torch():
+        return T().tsdf_edge_colors(volume, color, edge)
+    _need(isinstance(volume, torch.Tensor) and volume.dim() == 4 and volume.shape[0] == 2, "tsdf_edge_colors: volume must be [2,Z,Y,X] (D plane, weight plane)")
+    _chk(volume, "volume")
+    _color_planes(color, volume, "tsdf_edge_colors")
+    Z, Y, X = volume.shape[1:]
+    _need(X % 4 == 0, "tsdf_edge_colors: X must be a multiple of 4, got %d" % X)
+    _need(isinstance(edge, torch.Tensor) and edge.dim() == 1 and edge.dtype == torch.int64 and edge.is_contiguous() and edge.device == volume.device,
+          "tsdf_edge_colors: edge must be a contiguous int64 tensor [N] on the volume's device")
+    n = edge.shape[0]
+    with torch.cuda.device(volume.device):
+        out = torch.empty((n, 3), device=volume.device)
+        if n:
+            N.check(N.lib().estd_tsdf_edge_colors(_p(volume), _p(color), Z, Y, X, ctypes.c_void_p(edge.data_ptr()), n, _p(out), _stream()),
+                    "estd_tsdf_edge_colors")
+    return out
+
+
+def tsdf_raycast_color(volume, color, mat, H, W, t_min, dt, n_steps, w_min):
+    """tsdf_raycast with a colour map: -> (depth [H,W], normal [H,W,3], weight [H,W], color [H,W,3]); the first three as from tsdf_raycast,
+    the colour blended from ``color`` [3,Z,Y,X] at the hit, zeros without one (include/estd_hip.h, estd_tsdf_raycast_color)."""
+    H, W, n_steps, t_min, dt, w_min = int(H), int(W), int(n_steps), float(t_min), float(dt), float(w_min)
+    if _use_torch():
+        return tuple(T().tsdf_raycast_color(volume, color, mat, H, W, t_min, dt, n_steps, w_min))
+    _need(isinstance(volume, torch.Tensor) and volume.dim() == 4 and volume.shape[0] == 2, "tsdf_raycast_color: volume must be [2,Z,Y,X] (D plane, weight plane)")
+    _chk(volume, "volume")
+    _color_planes(color, volume, "tsdf_raycast_color")
+    Z, Y, X = volume.shape[1:]
+    _need(X % 4 == 0, "tsdf_raycast_color: X must be a multiple of 4, got %d" % X)
+    _need(isinstance(mat, torch.Tensor) and not mat.is_cuda and mat.dtype == torch.float32 and mat.is_contiguous() and mat.numel() == 12,
+          "tsdf_raycast_color: mat must be a contiguous CPU float32 tensor [12] (3x4 row-major)")
+    _need(H > 0 and W > 0 and H * W <= 0x7fffffff, "tsdf_raycast_color: the image size must be positive (and H * W < 2^31), got %d x %d" % (H, W))
+    _need(0 < n_steps <= 1 << 24, "tsdf_raycast_color: n_steps must be in 1..2^24, got %d" % n_steps)
+    _need(math.isfinite(dt) and ctypes.c_float(dt).value > 0, "tsdf_raycast_color: dt must be positive and finite, got %r" % dt)
+    _need(math.isfinite(t_min) and t_min >= 0, "tsdf_raycast_color: t_min must be finite and not negative, got %r" % t_min)
+    _need(w_min == w_min, "tsdf_raycast_color: w_min must not be NaN")
+    dev = volume.device
+    with torch.cuda.device(dev):
+        depth, normal, weight = torch.empty((H, W), device=dev), torch.empty((H, W, 3), device=dev), torch.empty((H, W), device=dev)
+        rgb = torch.empty((H, W, 3), device=dev)
+        d = N.TsdfRaycastColorDesc()
+        d.Z, d.Y, d.X, d.H, d.W, d.n_steps = Z, Y, X, H, W, n_steps
+        d.t_min, d.dt, d.w_min = t_min, dt, w_min
+        d.tsdf, d.weight, d.color = volume.data_ptr(), volume.data_ptr() + 4 * Z * Y * X, color.data_ptr()
+        d.depth, d.normal, d.out_weight, d.out_color = depth.data_ptr(), normal.data_ptr(), weight.data_ptr(), rgb.data_ptr()
+        d.stats = None
+        for i, v in enumerate(mat.reshape(-1).tolist()):
+            d.mat[i] = v
+        N.check(N.lib().estd_tsdf_raycast_color(ctypes.byref(d), _stream()), "estd_tsdf_raycast_color")
+    return depth, normal, weight, rgb

@@ -417,7 +417,7 @@ int estd_disp_head_nhwc(const float* in, const float* w, const float* bias, floa
                         int C, int upscale, estd_stream_t stream);
 
 /* ---- TSDF fusion of posed depth maps (csrc/tsdf.hip) --------------------------------------------
- * The reference stops at per-frame .npy depth maps (eval_hybrid_seq.py:215-230); these two entry points accumulate the depth /
+ * The reference stops at per-frame .npy depth maps (eval_hybrid_seq.py:215-230); these entry points accumulate the depth /
  * confidence maps the model returns into a scene on the device (KinectFusion's truncated signed distance update) and read the
  * surface back as an oriented point cloud.
  *
@@ -451,6 +451,32 @@ typedef struct estd_tsdf_integrate_desc {
 } estd_tsdf_integrate_desc;
 int estd_tsdf_integrate(const estd_tsdf_integrate_desc* desc, estd_stream_t stream);
 
+/* The same fusion with colour.  The colour volume is one more fp32 tensor [3][Z][Y][X] (planar, x fastest, zeros = empty) that SHARES the
+ * weight plane: colour is updated in exactly the voxels, frames and order in which D is, with the same w.  image[t] is the frame the
+ * depth map t belongs to, [3][H][W] planar at the depth maps' size.  Steps 1-6 above apply verbatim -- D and Wt come out bit-identical to
+ * the call without colour on the same inputs -- and, with Wt the weight BEFORE step 6, for channel k = 0, 1, 2:
+ *   7. col_k = image[t][k * H * W + vi * W + ui] (the pixel the depth was read at);  C_k = fma(C_k, Wt, col_k * w) / (Wt + w).
+ * Colour values are used as they are: finite values are the caller's duty (a NaN or an infinity stays in the voxel); negative values
+ * (normalised images) are fine -- the average is affine, so a caller can undo the normalisation at export.  A 16-byte group that no
+ * frame updates is neither read nor written in any of the five planes.  One T = 3 call equals three T = 1 calls bit for bit.
+ * Argument errors as for the call without colour; in addition ESTD_ERR_ARG for a null `color` or a null image[t], t < T. */
+typedef struct estd_tsdf_integrate_color_desc {
+    int Z, Y, X;
+    int T;
+    int H, W;                                     /* size of every depth / confidence map and of every image plane */
+    int weighted;
+    int no_skip;                                  /* 1: measurement only (tools/tsdf_bench.py) */
+    float trunc, z_near, conf_min, w_max;
+    float* tsdf;                                  /* [Z][Y][X] */
+    float* weight;                                /* [Z][Y][X] */
+    const float* depth[ESTD_TSDF_MAX_FRAMES];     /* [H][W] each */
+    const float* conf[ESTD_TSDF_MAX_FRAMES];      /* [H][W] each: all T set, or all NULL */
+    float mats[ESTD_TSDF_MAX_FRAMES][12];
+    float* color;                                 /* [3][Z][Y][X] */
+    const float* image[ESTD_TSDF_MAX_FRAMES];     /* [3][H][W] each */
+} estd_tsdf_integrate_color_desc;
+int estd_tsdf_integrate_color(const estd_tsdf_integrate_color_desc* desc, estd_stream_t stream);
+
 /* Zero crossings of the volume as points.  For every voxel with Wt >= w_min and each of its +x, +y, +z neighbours with Wt >= w_min:
  * a point when D0 < 0 <= D1 or D1 < 0 <= D0, at s = D0 / (D0 - D1) along the edge:
  *   xyz    = origin + (idx + 0.5 + s e_axis) voxel_size                      (fma(cell, voxel_size, origin) per coordinate)
@@ -464,6 +490,14 @@ int estd_tsdf_integrate(const estd_tsdf_integrate_desc* desc, estd_stream_t stre
 int estd_tsdf_extract_points(const float* tsdf, const float* weight, int Z, int Y, int X, float voxel_size, const float* origin3,
                              float w_min, unsigned long long* counter, long long capacity, float* xyz, float* normal,
                              float* point_weight, long long* edge, estd_stream_t stream);
+
+/* The colour at crossings: for each of the n ids edge[i] = 3 * linear voxel index + axis (as the extraction emits them), with D0, C0 at
+ * that voxel and D1, C1 at its neighbour along the axis:  s = D0 / (D0 - D1) from the stored values (the extraction's expression);
+ *   out[i][k] = fma(s, C1_k - C0_k, C0_k).
+ * An id that is negative or >= 3 Z Y X, or whose neighbour along the axis lies outside the volume, writes (0, 0, 0).  The weights are not
+ * read: ids of unobserved voxels blend whatever the planes hold.  edge, out: device, [n] and [n][3]; n == 0 launches nothing. */
+int estd_tsdf_edge_colors(const float* tsdf, const float* color, int Z, int Y, int X, const long long* edge, long long n, float* out,
+                          estd_stream_t stream);
 
 /* Depth, normal and weight maps of the volume as a pinhole camera sees it (csrc/tsdf_raycast.hip; KinectFusion's surface prediction).
  * Depth is the z-depth along the optical axis with pixel centres on integers: the convention of the model's depth maps and of
@@ -507,6 +541,29 @@ typedef struct estd_tsdf_raycast_desc {
     float mat[12];                                /* host values, copied into the launch arguments */
 } estd_tsdf_raycast_desc;
 int estd_tsdf_raycast(const estd_tsdf_raycast_desc* desc, estd_stream_t stream);
+
+/* The same render with a colour map.  Depth, normal and weight come out bit-identical to the call without colour.  At the hit between
+ * samples k - 1 and k, per channel: Cb = the trilinear blend of the eight corner colours of a sample's cell with the nesting of Wb;
+ *   out_color = fma(s, Cb_k - Cb_{k-1}, Cb_{k-1}).
+ * Both cells are observed, so every corner has been fused at least once.  No hit: (0, 0, 0).  The 2 x 8 x 3 colour values are read once
+ * per pixel, at the hit.  Errors as above; in addition ESTD_ERR_ARG for a null `color` or `out_color`. */
+typedef struct estd_tsdf_raycast_color_desc {
+    int Z, Y, X;
+    int H, W;
+    int n_steps;
+    float t_min, dt;
+    float w_min;
+    const float* tsdf;                            /* [Z][Y][X] */
+    const float* weight;                          /* [Z][Y][X] */
+    float* depth;                                 /* [H][W] */
+    float* normal;                                /* [H][W][3] */
+    float* out_weight;                            /* [H][W] */
+    unsigned int* stats;                          /* NULL, or measurement only [H][W][2] */
+    float mat[12];
+    const float* color;                           /* [3][Z][Y][X] */
+    float* out_color;                             /* [H][W][3] */
+} estd_tsdf_raycast_color_desc;
+int estd_tsdf_raycast_color(const estd_tsdf_raycast_color_desc* desc, estd_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,9 @@ ground-truth depth.  Needs an MI355X (the model has no CPU path).
     python tools/run_stream.py --scene-dir /data/scannet/scene0707_00 --out /tmp/eval --loadckpt model.ckpt
     python tools/run_stream.py --synthetic 8 --out /tmp/eval          # self-contained demo on a generated scene
     python tools/run_stream.py --synthetic 8 --out /tmp/eval --fuse /tmp/eval/scene.ply      # + TSDF fusion of every target, point cloud
+    python tools/run_stream.py --synthetic 8 --out /tmp/eval --fuse /tmp/eval/scene.ply --color --render-fused
+        # + colour: every target's 0..255 RGB frame is fused beside its depth; scene.ply gets red / green / blue and --render-fused also
+        # writes <out>/fused_rgb/<stem>.png
     python tools/run_stream.py --synthetic 8 --out /tmp/eval --fuse /tmp/eval/scene.ply --render-fused
         # + the fused volume ray-cast at every target's pose (TSDFVolume.render): <out>/fused_depth/*.npy beside refined_depth/ (float16,
         # same layout) and the fused depth scored against the same ground truth (errors_fused, fused_coverage, errors_on_covered)
@@ -44,11 +47,15 @@ def main():
                                                        "(estdepth_amd.fusion3d) and write its surface points here")
     ap.add_argument("--render-fused", action="store_true", help="with --fuse: after the stream, render the volume at every target's pose, "
                     "write the fused depth maps to <out>/fused_depth and score them against the ground truth")
+    ap.add_argument("--color", action="store_true", help="with --fuse: fuse every target's frame (the reader's 0..255 RGB, whatever the model is "
+                    "fed) beside its depth; the PLY gets red / green / blue and --render-fused also writes <out>/fused_rgb/<stem>.png")
     ap.add_argument("--voxel-size", type=float, default=0.04)
     ap.add_argument("--volume-dims", type=int, nargs=3, default=(256, 256, 256), metavar=("Z", "Y", "X"))
     args = ap.parse_args()
     if args.render_fused and not args.fuse:
         ap.error("--render-fused needs --fuse PATH.ply")
+    if args.color and not args.fuse:
+        ap.error("--color needs --fuse PATH.ply")
 
     from estdepth_amd import DepthNetHybrid, synth
     from estdepth_amd.streaming import ESTMStream
@@ -113,11 +120,12 @@ def main():
                 h, w = s["img"].shape[-2:]
                 origin = frustum_volume(window[0]["cam_pose"], s["cam_intr"], (h, w), args.depth_min, args.depth_max,
                                         args.volume_dims, args.voxel_size)
-                volume = TSDFVolume(args.volume_dims, args.voxel_size, origin, device=dev)
+                volume = TSDFVolume(args.volume_dims, args.voxel_size, origin, device=dev, color=args.color)
+            frames_rgb = torch.stack([f["img"][0] for f in window])[None].to(dev) if args.color else None
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             volume.integrate_outputs(outputs, torch.stack([f["cam_pose"].reshape(4, 4) for f in window])[None], s["cam_intr"].reshape(1, 3, 3),
-                                     image_hw=tuple(s["img"].shape[-2:]))
+                                     image_hw=tuple(s["img"].shape[-2:]), imgs=frames_rgb)
             e1.record()
             torch.cuda.synchronize()
             fuse_ms.append(e0.elapsed_time(e1))
@@ -144,8 +152,11 @@ def main():
         # the fused model in every target's camera, on the pixel grid and in the units of the per-frame predictions
         from estdepth_amd.metrics import compute_valid_depth_mask
         errs_fused, errs_covered, n_gt, n_covered, render_ms = RunningErrors(), RunningErrors(), 0, 0, []
-        out_dir = os.path.join(args.out, "fused_depth")
+        out_dir, rgb_dir = os.path.join(args.out, "fused_depth"), os.path.join(args.out, "fused_rgb")
         os.makedirs(out_dir, exist_ok=True)
+        if args.color:
+            from PIL import Image
+            os.makedirs(rgb_dir, exist_ok=True)
         for img_path, pose, intr, hw, pred, gt in targets:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -154,6 +165,9 @@ def main():
             torch.cuda.synchronize()
             render_ms.append(e0.elapsed_time(e1))
             fused = maps["depth"].cpu().numpy()
+            if args.color:          # what the fused scene looks like from this pose, to hold beside the photograph; black where no surface is hit
+                rgb = maps["color"].round().clamp(0, 255).byte().cpu().numpy()
+                Image.fromarray(rgb).save(os.path.join(rgb_dir, os.path.splitext(os.path.basename(img_path))[0] + ".png"))
             np.save(os.path.join(out_dir, os.path.splitext(os.path.basename(img_path))[0] + ".npy"), np.float16(fused[None]))
             fused = to_gt_grid(fused.astype(np.float64), gt.shape)
             gt_ok = compute_valid_depth_mask(gt)

@@ -14,7 +14,13 @@ read from HBM as it is behind a model step, not from the Infinity Cache.
 
 times csrc/tsdf_raycast.hip instead: one 640 x 480 render (TSDFVolume.render, default range and step) of the 256^3 volume above after the
 T = 3 fuse, from the first fused camera and from the held-out pose of tests/tsdf_raycast_ref.py, with the kernel's own counters (samples
-whose weights / whose D values were read per ray), beside the fuse + extract pass and the Joint step."""
+whose weights / whose D values were read per ray), beside the fuse + extract pass and the Joint step.
+
+    python tools/tsdf_bench.py --color [--reps 200] [--out profiles/tsdf_color_bench.txt]
+
+times the colour path beside the plain one on the 256^3 volume: the T = 3 fuse with and without colour (estd_tsdf_integrate_color: five
+planes per touched group instead of two), the edge colours of the extracted points, and the 640 x 480 render with and without a colour map
+from the held-out pose.  The two plain figures are the ones to hold against another commit's."""
 import argparse
 import os
 import sys
@@ -53,9 +59,12 @@ def main():
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--out")
     ap.add_argument("--raycast", action="store_true", help="time the ray caster (csrc/tsdf_raycast.hip) instead of integrate / extract")
+    ap.add_argument("--color", action="store_true", help="time the colour fuse, the edge colours and the colour render beside the plain figures")
     args = ap.parse_args()
     if args.raycast:
         return raycast_main(args)
+    if args.color:
+        return color_main(args)
     import tsdf_ref as R
     from estdepth_amd import camera, ops
     from estdepth_amd.fusion3d import TSDFVolume, frustum_volume
@@ -156,6 +165,75 @@ def raycast_main(args):
             "  beside the %.1f ms Joint step: %.1f %% of the step; beside the T = 3 integrate + extract pass (%.2f ms): %.1f x"
             % (JOINT_STEP_MS, 100.0 * t_cold / JOINT_STEP_MS, fuse_extract_ms, t_cold / fuse_extract_ms),
         ]
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        open(args.out, "w").write(text + "\n")
+
+
+def color_main(args):
+    import tsdf_color_ref as CR
+    import tsdf_raycast_ref as RR
+    import tsdf_ref as R
+    from estdepth_amd import camera, ops
+    from estdepth_amd.fusion3d import TSDFVolume, frustum_volume, render_plan
+    assert torch.cuda.is_available(), "tools/tsdf_bench.py needs a ROCm device"
+    dev = torch.device("cuda:0")
+    H, W, T, vox, dmin, dmax, dims = 480, 640, 3, 0.03, 0.1, 10.0, (256, 256, 256)
+    K = R.intrinsics(H, W)
+    poses = R.scene_poses(T, seed=1)
+    depths_np = np.stack([R.raycast_scene(P, K, H, W) for P in poses]).astype(np.float32)
+    images = torch.from_numpy(CR.case_images(dict(depths=depths_np, poses=poses, K=K))).to(dev)
+    depths = torch.from_numpy(depths_np).to(dev)
+    dl, il = [depths[t] for t in range(T)], [images[t] for t in range(T)]
+    origin = frustum_volume(torch.from_numpy(poses[0]), torch.from_numpy(K), (H, W), dmin, dmax, dims, vox)
+    vol = TSDFVolume(dims, vox, origin, device=dev, color=True)
+    mats = camera.tsdf_matrices(torch.from_numpy(poses), torch.from_numpy(K), vol.origin, vox).contiguous()
+    flush = torch.empty(256 << 20, device=dev)          # 1 GiB
+    reps = args.reps
+
+    def fuse():
+        ops.tsdf_integrate_(vol.volume, dl, [], mats, vol.trunc, vol.z_near, 0.0, False, vol.w_max)
+
+    def fuse_color():
+        ops.tsdf_integrate_color_(vol.volume, vol.color, dl, [], il, mats, vol.trunc, vol.z_near, 0.0, False, vol.w_max)
+    fuse_color()
+    torch.cuda.synchronize()
+    groups16 = int((vol.volume[1].reshape(-1, 4) > 0).any(1).sum().item())
+    pts = vol.extract_points()
+    edge = pts["edge"].contiguous()
+    rmats, _, t_min, dt, n_steps, _ = render_plan(vol.dims, vox, vol.origin, vol.z_near, torch.from_numpy(RR.HELD_OUT_POSE), torch.from_numpy(K), (H, W))
+    mat = rmats[0].contiguous()
+
+    def cast():
+        return ops.tsdf_raycast(vol.volume, mat, H, W, t_min, dt, n_steps[0], 1.0)
+
+    def cast_color():
+        return ops.tsdf_raycast_color(vol.volume, vol.color, mat, H, W, t_min, dt, n_steps[0], 1.0)
+    # alternating rounds, so that a drift of the clock or of the box falls on both members of a pair alike
+    rounds, per = 4, max(reps // 4, 1)
+    fig = {k: [] for k in ("fuse", "fuse_color", "cast", "cast_color")}
+    for _ in range(rounds):
+        fig["fuse"].append(timed(fuse, per, flush))
+        fig["fuse_color"].append(timed(fuse_color, per, flush))
+        fig["cast"].append(timed(cast, per, flush))
+        fig["cast_color"].append(timed(cast_color, per, flush))
+    t_edge = timed(lambda: ops.tsdf_edge_colors(vol.volume, vol.color, edge), reps, flush)
+    med = {k: float(np.median(v)) for k, v in fig.items()}
+    lines = [
+        "tsdf_bench --color: %d x %d maps and renders, T = %d, volume %d x %d x %d at %.3f m, %d rounds of %d repetitions per figure (median of the "
+        "rounds; every call behind a 1 GiB cache flush), %s" % ((W, H, T) + dims + (vox, rounds, per, torch.cuda.get_device_name(0))),
+        "  plain T=3 fuse              %8.3f ms   (rounds: %s)" % (med["fuse"], " ".join("%.3f" % v for v in fig["fuse"])),
+        "  colour T=3 fuse             %8.3f ms   (rounds: %s)   colour / plain = %.2f" % (med["fuse_color"], " ".join("%.3f" % v for v in fig["fuse_color"]),
+                                                                                       med["fuse_color"] / med["fuse"]),
+        "    %d 16-byte groups touched: %.1f MB of volume traffic with colour (160 bytes per group), %.1f MB without (64)"
+        % (groups16, groups16 * 160.0 / 1e6, groups16 * 64.0 / 1e6),
+        "  edge colours                %8.3f ms   for %d records" % (t_edge, pts["count"]),
+        "  plain render, held-out pose %8.3f ms   (rounds: %s)" % (med["cast"], " ".join("%.3f" % v for v in fig["cast"])),
+        "  colour render               %8.3f ms   (rounds: %s)   colour / plain = %.2f" % (med["cast_color"], " ".join("%.3f" % v for v in fig["cast_color"]),
+                                                                                       med["cast_color"] / med["cast"]),
+    ]
     text = "\n".join(lines)
     print(text)
     if args.out:
