@@ -105,6 +105,17 @@ class TsdfRaycastColorDesc(ctypes.Structure):
     _fields_ = TsdfRaycastDesc._fields_ + [("color", ctypes.c_void_p), ("out_color", ctypes.c_void_p)]
 
 
+class DepthConsistencyDesc(ctypes.Structure):
+    """Mirror of struct estd_depth_consistency_desc (include/estd_hip.h)."""
+    _fields_ = [
+        ("H", ctypes.c_int), ("W", ctypes.c_int), ("S", ctypes.c_int),
+        ("px_max", ctypes.c_float), ("rel_max", ctypes.c_float), ("z_near", ctypes.c_float),
+        ("target", ctypes.c_void_p), ("source", ctypes.c_void_p * 8),
+        ("views", ctypes.c_void_p), ("visible", ctypes.c_void_p), ("depth", ctypes.c_void_p), ("rel_err", ctypes.c_void_p),
+        ("mats", ((ctypes.c_float * 12) * 2) * 8),
+    ]
+
+
 _SIGNATURES = {
     "estd_version": (ctypes.c_int, []),
     "estd_status_string": (ctypes.c_char_p, [ctypes.c_int]),
@@ -180,6 +191,7 @@ _SIGNATURES = {
     "estd_tsdf_edge_colors": (ctypes.c_int, [c_float_p, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong,
                                              c_float_p, c_stream]),
     "estd_tsdf_raycast_color": (ctypes.c_int, [ctypes.POINTER(TsdfRaycastColorDesc), c_stream]),
+    "estd_depth_consistency": (ctypes.c_int, [ctypes.POINTER(DepthConsistencyDesc), c_stream]),
 }
 
 # the superseded A/B kernels: exported only by a library built with ESTD_BUILD_AB=1 (estdepth_amd/build.py)

@@ -224,3 +224,25 @@ def tsdf_ray_matrix(cam_pose, cam_intr, origin, voxel_size):
         o = (P[t, :3, 3] - org) / float(voxel_size) - 0.5
         out[t] = torch.cat([A, o[:, None]], 1).reshape(-1).float()
     return out
+
+
+# ------------------------------------------------------------------------------------------------ cross-view consistency
+def consistency_matrices(pose_t, K_t, poses_s, K_s):
+    """The matrices of estd_depth_consistency for one target and S sources: per source F_s = [K_s R_st K_t^-1 | K_s t_st], which takes a
+    target pixel (u, v, 1) times its z-depth to the source's (x, y, 1) times the depth there, and B_s, the same from the source back to the
+    target; R_st, t_st from inv(P_s) P_t with camera-to-world poses.  pose_t [4,4], K_t [3,3], poses_s [S,4,4], K_s [3,3] or [S,3,3] (pixels
+    of the depth maps).  Formed in float64 on the host and rounded to fp32 -> CPU float32 [S,2,12] (3x4 row-major, F then B)."""
+    Pt = pose_t.detach().to(device="cpu", dtype=torch.float64).reshape(4, 4)
+    Kt = K_t.detach().to(device="cpu", dtype=torch.float64).reshape(3, 3)
+    Ps = poses_s.detach().to(device="cpu", dtype=torch.float64).reshape(-1, 4, 4)
+    Ks = K_s.detach().to(device="cpu", dtype=torch.float64).reshape(-1, 3, 3)
+    if Ks.shape[0] not in (1, Ps.shape[0]):
+        raise RuntimeError("consistency_matrices: K_s must be [3,3] or one [3,3] per source, got %s for %d sources" % (tuple(K_s.shape), Ps.shape[0]))
+    out = torch.empty(Ps.shape[0], 2, 12, dtype=torch.float32)
+    for s in range(Ps.shape[0]):
+        K = Ks[s if Ks.shape[0] > 1 else 0]
+        for j, (Ka, Pa, Kb, Pb) in enumerate(((Kt, Pt, K, Ps[s]), (K, Ps[s], Kt, Pt))):         # from camera a into camera b
+            rel = torch.inverse(Pb) @ Pa
+            M = torch.cat([Kb @ rel[:3, :3] @ torch.inverse(Ka), (Kb @ rel[:3, 3])[:, None]], 1)
+            out[s, j] = M.reshape(-1).float()
+    return out

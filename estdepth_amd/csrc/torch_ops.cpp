@@ -536,6 +536,45 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> tsdf_raycast_color(const Tensor& volu
     return {depth, normal, weight, rgb};
 }
 
+// ------------------------------------------------------------------------------------------------ cross-view consistency
+// csrc/depth_consistency.hip: target [H,W] and 1..8 sources of the same size, mats: CPU float32 [S,2,12] (F_s, B_s: host values of the
+// launch arguments) -> (views, visible, depth, rel_err), each [H,W]
+std::tuple<Tensor, Tensor, Tensor, Tensor> depth_consistency(const Tensor& target, at::TensorList sources, const Tensor& mats, double px_max,
+                                                             double rel_max, double z_near)
+{
+    const OpScope scope(target);
+    const float* tgt = fptr(target, "target");
+    TORCH_CHECK(target.dim() >= 2, "depth_consistency: the target must be [H,W] (leading 1s allowed)");
+    const int64_t H = target.size(-2), W = target.size(-1);
+    TORCH_CHECK(target.numel() == H * W, "depth_consistency: the target must be [H,W] (leading 1s allowed)");
+    TORCH_CHECK(H >= 2 && W >= 2 && H * W <= 0x7fffffffLL, "depth_consistency: maps must be at least 2 x 2 (and H * W < 2^31), got ", H, " x ", W);
+    const int64_t S = (int64_t)sources.size();
+    TORCH_CHECK(S >= 1 && S <= ESTD_CONSISTENCY_MAX_SOURCES, "depth_consistency: 1..", ESTD_CONSISTENCY_MAX_SOURCES, " sources per call, got ", S);
+    TORCH_CHECK(mats.defined() && mats.device().is_cpu() && mats.scalar_type() == at::kFloat && mats.is_contiguous() && mats.numel() == S * 24,
+                "depth_consistency: mats must be a contiguous CPU float32 tensor [S,2,12]");
+    TORCH_CHECK(std::isfinite(px_max) && (float)px_max > 0.f, "depth_consistency: px_max must be positive and finite, got ", px_max);
+    TORCH_CHECK(std::isfinite(rel_max) && (float)rel_max > 0.f, "depth_consistency: rel_max must be positive and finite, got ", rel_max);
+    TORCH_CHECK(std::isfinite(z_near) && z_near >= 0, "depth_consistency: z_near must be finite and not negative, got ", z_near);
+    estd_depth_consistency_desc d{};
+    d.H = (int)H; d.W = (int)W; d.S = (int)S;
+    d.px_max = (float)px_max; d.rel_max = (float)rel_max; d.z_near = (float)z_near;
+    d.target = tgt;
+    for (int64_t s = 0; s < S; ++s) {
+        TORCH_CHECK(sources[s].dim() >= 2 && sources[s].size(-2) == H && sources[s].size(-1) == W && sources[s].numel() == H * W,
+                    "depth_consistency: source ", s, " must be [", H, ",", W, "]");
+        d.source[s] = fptr(sources[s], "source map");
+        for (int i = 0; i < 24; ++i) {
+            const float m = mats.data_ptr<float>()[s * 24 + i];
+            TORCH_CHECK(std::isfinite(m), "depth_consistency: mats holds a value that is not finite");
+            d.mats[s][i / 12][i % 12] = m;
+        }
+    }
+    Tensor views = new_f32({H, W}, target), visible = new_f32({H, W}, target), depth = new_f32({H, W}, target), rel_err = new_f32({H, W}, target);
+    d.views = views.data_ptr<float>(); d.visible = visible.data_ptr<float>(); d.depth = depth.data_ptr<float>(); d.rel_err = rel_err.data_ptr<float>();
+    check_status(estd_depth_consistency(&d, cur_stream()), "estd_depth_consistency");
+    return {views, visible, depth, rel_err};
+}
+
 Tensor warp_attention(const Tensor& kv_target, at::TensorList kv_sources, const Tensor& mats, const Tensor& depth_values,
                       double depth_min, double depth_interval)
 {
@@ -971,6 +1010,8 @@ TORCH_LIBRARY(estdepth_hip, m)
     m.def("tsdf_edge_colors(Tensor volume, Tensor color, Tensor edge) -> Tensor");
     m.def("tsdf_raycast_color(Tensor volume, Tensor color, Tensor mat, int H, int W, float t_min, float dt, int n_steps, float w_min) -> "
           "(Tensor, Tensor, Tensor, Tensor)");
+    m.def("depth_consistency(Tensor target, Tensor[] sources, Tensor mats, float px_max, float rel_max, float z_near) -> "
+          "(Tensor, Tensor, Tensor, Tensor)");
     m.def("profile_mark(int id) -> ()");
     m.def("set_reserved_cus(int n) -> int");
     m.def("conv3d_grid(int N, int D, int H, int W) -> int");
@@ -1021,6 +1062,7 @@ TORCH_LIBRARY_IMPL(estdepth_hip, CUDA, m)
     m.impl("tsdf_integrate_color_", tsdf_integrate_color_);
     m.impl("tsdf_edge_colors", tsdf_edge_colors);
     m.impl("tsdf_raycast_color", tsdf_raycast_color);
+    m.impl("depth_consistency", depth_consistency);
 }
 
 TORCH_LIBRARY_IMPL(estdepth_hip, CPU, m)

@@ -195,6 +195,35 @@ class TSDFVolume:
             images = [imgs[0, t + 1] for t in range(n)]
         return self.integrate(depths, poses[1:n + 1], k, conf=confs, conf_min=conf_min, weighted=weighted, images=images)
 
+    def integrate_filtered(self, record, min_views=None, conf_min=0.0):
+        """Fuse one frame that went through the cross-view filter: ``record`` as ``consistency.ConsistencyWindow`` returns it (or any dict
+        with depth, views, pose, K and optionally conf, min_views, extra).  Only pixels on which ``views >= min_views`` sources agree enter
+        the volume (default: the record's own ``min_views``, else 2).  Without a network confidence this is
+        ``integrate(depth, pose, K, conf=views, conf_min=min_views)``; with ``record["conf"]`` the depth is set to 0 -- "no sample" for the
+        integrate kernel -- where too few views agree, and the confidence gates (``conf_min``) as in ``integrate``.  A colour volume takes the frame's image from ``record["extra"]`` ([3,H,W])."""
+        if min_views is None:
+            min_views = record.get("min_views", 2)
+        if not float(min_views) >= 1:
+            raise RuntimeError("integrate_filtered: min_views must be at least 1, got %r" % (min_views,))
+        for key in ("depth", "views", "pose", "K"):
+            if record.get(key) is None:
+                raise RuntimeError("integrate_filtered: the record has no %r" % key)
+        depth, views = record["depth"], record["views"]
+        if tuple(views.shape[-2:]) != tuple(depth.shape[-2:]):
+            raise RuntimeError("integrate_filtered: views is %s but the depth %s" % (tuple(views.shape), tuple(depth.shape)))
+        hw = tuple(depth.shape[-2:])
+        images = None if self.color is None else record.get("extra")
+        if images is not None:
+            images = images.reshape((1, 3) + hw)
+        pose, K = record["pose"].reshape(1, 4, 4), record["K"].reshape(3, 3)
+        conf = record.get("conf")
+        if conf is None:
+            return self.integrate(depth.reshape((1,) + hw), pose, K, conf=views.reshape((1,) + hw), conf_min=float(min_views), images=images)
+        if tuple(conf.shape[-2:]) != hw or conf.numel() != hw[0] * hw[1]:
+            raise RuntimeError("integrate_filtered: conf is %s but the depth %s" % (tuple(conf.shape), hw))
+        kept = torch.where(views.reshape(hw) >= float(min_views), depth.reshape(hw), torch.zeros_like(depth.reshape(hw)))
+        return self.integrate(kept[None], pose, K, conf=conf.reshape((1,) + hw), conf_min=conf_min, images=images)
+
     # ------------------------------------------------------------------------------------------------ read-back
     def extract_points(self, w_min=1.0, capacity=None):
         """Zero crossings between voxels of weight >= ``w_min`` -> dict(xyz [N,3], normal [N,3], weight [N], edge [N] int64, count) on

@@ -1204,3 +1204,51 @@ def tsdf_raycast_color(volume, color, mat, H, W, t_min, dt, n_steps, w_min):
             d.mat[i] = v
         N.check(N.lib().estd_tsdf_raycast_color(ctypes.byref(d), _stream()), "estd_tsdf_raycast_color")
     return depth, normal, weight, rgb
+
+
+# ---------------------------------------------------------------------------------- cross-view consistency (csrc/depth_consistency.hip)
+CONSISTENCY_MAX_SOURCES = 8     # ESTD_CONSISTENCY_MAX_SOURCES (include/estd_hip.h)
+
+
+def depth_consistency(target, sources, mats, px_max, rel_max, z_near):
+    """Check the depth map ``target`` [H,W] against the 1..8 ``sources`` (device tensors of the same size) with the host matrices ``mats``
+    (CPU float32 [S,2,12]: F_s and B_s of camera.consistency_matrices) -> (views, visible, depth, rel_err), each [H,W] on the target's device:
+    the number of sources that agree with a pixel within ``px_max`` pixels of reprojection and ``rel_max`` of relative depth, the number that
+    see it, the average of the target's depth and the agreeing sources' and their mean relative difference.  The contract is spelled out in
+    include/estd_hip.h (estd_depth_consistency)."""
+    sources = list(sources)
+    px_max, rel_max, z_near = float(px_max), float(rel_max), float(z_near)
+    if _use_torch():
+        return tuple(T().depth_consistency(target, sources, mats, px_max, rel_max, z_near))
+    _chk(target, "target")
+    _need(target.dim() >= 2 and target.numel() == target.shape[-2] * target.shape[-1], "depth_consistency: the target must be [H,W] (leading 1s allowed)")
+    H, W = target.shape[-2:]
+    _need(H >= 2 and W >= 2 and H * W <= 0x7fffffff, "depth_consistency: maps must be at least 2 x 2 (and H * W < 2^31), got %d x %d" % (H, W))
+    S = len(sources)
+    _need(1 <= S <= CONSISTENCY_MAX_SOURCES, "depth_consistency: 1..%d sources per call, got %d" % (CONSISTENCY_MAX_SOURCES, S))
+    _need(isinstance(mats, torch.Tensor) and not mats.is_cuda and mats.dtype == torch.float32 and mats.is_contiguous() and mats.numel() == S * 24,
+          "depth_consistency: mats must be a contiguous CPU float32 tensor [S,2,12]")
+    _need(math.isfinite(px_max) and ctypes.c_float(px_max).value > 0, "depth_consistency: px_max must be positive and finite, got %r" % px_max)
+    _need(math.isfinite(rel_max) and ctypes.c_float(rel_max).value > 0, "depth_consistency: rel_max must be positive and finite, got %r" % rel_max)
+    _need(math.isfinite(z_near) and z_near >= 0, "depth_consistency: z_near must be finite and not negative, got %r" % z_near)
+    for i, t in enumerate(sources):
+        _chk(t, "source map %d" % i)
+        _need(t.dim() >= 2 and tuple(t.shape[-2:]) == (H, W) and t.numel() == H * W, "depth_consistency: source %d must be [%d,%d], got %s"
+              % (i, H, W, tuple(t.shape)))
+        _need(t.device == target.device, "depth_consistency: source %d is on %s but the target on %s" % (i, t.device, target.device))
+    flat = mats.reshape(-1).tolist()
+    _need(all(math.isfinite(v) for v in flat), "depth_consistency: mats holds a value that is not finite")
+    dev = target.device
+    with torch.cuda.device(dev):
+        views, visible, depth, rel_err = (torch.empty((H, W), device=dev) for _ in range(4))
+        d = N.DepthConsistencyDesc()
+        d.H, d.W, d.S = H, W, S
+        d.px_max, d.rel_max, d.z_near = px_max, rel_max, z_near
+        d.target = target.data_ptr()
+        d.views, d.visible, d.depth, d.rel_err = views.data_ptr(), visible.data_ptr(), depth.data_ptr(), rel_err.data_ptr()
+        for s in range(S):
+            d.source[s] = sources[s].data_ptr()
+            for i in range(24):
+                d.mats[s][i // 12][i % 12] = flat[s * 24 + i]
+        N.check(N.lib().estd_depth_consistency(ctypes.byref(d), _stream()), "estd_depth_consistency")
+    return views, visible, depth, rel_err

@@ -565,6 +565,48 @@ typedef struct estd_tsdf_raycast_color_desc {
 } estd_tsdf_raycast_color_desc;
 int estd_tsdf_raycast_color(const estd_tsdf_raycast_color_desc* desc, estd_stream_t stream);
 
+/* ---- cross-view consistency of depth maps (csrc/depth_consistency.hip) ---------------------------
+ * The step multi-view pipelines put between "depth per frame" and fusion (MVSNet's / COLMAP's geometric filter; the reference has none):
+ * ONE target depth map is checked against S = 1..ESTD_CONSISTENCY_MAX_SOURCES source maps.  All maps are fp32 [H][W] of one size, pixel
+ * centres on integers, z-depth along the optical axis: the conventions of estd_tsdf_integrate and estd_tsdf_raycast.
+ *
+ * mats[s][0] = F_s = [ K_s R_st K_t^-1 | K_s t_st ] takes (target pixel) x depth to source s, mats[s][1] = B_s is the same the other
+ * way; R_st, t_st from inv(P_s) P_t with camera-to-world poses P.  HOST 3x4 row-major matrices in fp32 (estdepth_amd/camera.py
+ * consistency_matrices forms them in float64).  With row(M, j; x, y, z) = fma(z, fma(M[j][0], x, fma(M[j][1], y, M[j][2])), M[j][3])
+ * and lerp(a, b, f) = fma(f, b - a, a), per target pixel (u, v):
+ *   1. d = target[v][u]; the pixel is INVALID unless d is finite and d > z_near: all four outputs are 0.  For each source, in order:
+ *   2. a, b, c = row(F, 0 / 1 / 2; u, v, d); skip the source unless c > z_near; us = a / c, vs = b / c;
+ *   3. skip unless 0 <= us <= W - 1 and 0 <= vs <= H - 1 (false for a NaN); x0 = min(floor(us), W - 2), y0 = min(floor(vs), H - 2);
+ *      the taps t00 = source[y0][x0], t10 = [y0][x0 + 1], t01 = [y0 + 1][x0], t11 = [y0 + 1][x0 + 1]; skip unless all four are finite
+ *      and > z_near;
+ *   4. fx = us - x0, fy = vs - y0; ds = lerp(lerp(t00, t10, fx), lerp(t01, t11, fx), fy);
+ *   5. a', b', c' = row(B, 0 / 1 / 2; us, vs, ds); skip unless c' > z_near; u' = a' / c', v' = b' / c'.  The source is now VISIBLE;
+ *   6. e2 = fma(u' - u, u' - u, (v' - v) (v' - v)), rel = |c' - d| / d; the source is CONSISTENT iff e2 < px_max^2 and rel < rel_max
+ *      (px_max^2 = px_max * px_max, formed once on the host in fp32).
+ * Outputs, fp32 [H][W], every pixel written by every call:
+ *   views   = the number of consistent sources;          visible = the number of visible sources;
+ *   depth   = (d + c'_1 + c'_2 + ...) / (1 + views), the c' of the consistent sources added to d in source order: the target's own depth
+ *             where nothing agrees, so the map can be fused as it is (gate it with `views`);
+ *   rel_err = (rel_1 + rel_2 + ...) / views over the consistent sources in source order; 0 where views = 0.
+ * IEEE divisions, no atomics: two calls give the same bits.
+ * ESTD_ERR_ARG (before any launch, no device needed): a null descriptor, a null map pointer (source[s] for s < S), S outside
+ * 1..ESTD_CONSISTENCY_MAX_SOURCES, H < 2 or W < 2, px_max or rel_max not finite or <= 0 (or px_max^2 not a positive finite fp32),
+ * z_near negative or not finite, a matrix element of a source s < S not finite.  ESTD_ERR_UNSUPPORTED: H * W >= 2^31. */
+#define ESTD_CONSISTENCY_MAX_SOURCES 8
+typedef struct estd_depth_consistency_desc {
+    int H, W;                                                 /* size of every map */
+    int S;                                                    /* sources in this call */
+    float px_max, rel_max, z_near;
+    const float* target;                                      /* [H][W] */
+    const float* source[ESTD_CONSISTENCY_MAX_SOURCES];        /* [H][W] each */
+    float* views;                                             /* [H][W] */
+    float* visible;                                           /* [H][W] */
+    float* depth;                                             /* [H][W] */
+    float* rel_err;                                           /* [H][W] */
+    float mats[ESTD_CONSISTENCY_MAX_SOURCES][2][12];          /* F_s, B_s: host values, copied into the launch arguments */
+} estd_depth_consistency_desc;
+int estd_depth_consistency(const estd_depth_consistency_desc* desc, estd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,10 @@ ground-truth depth.  Needs an MI355X (the model has no CPU path).
     python tools/run_stream.py --synthetic 8 --out /tmp/eval --fuse /tmp/eval/scene.ply --render-fused
         # + the fused volume ray-cast at every target's pose (TSDFVolume.render): <out>/fused_depth/*.npy beside refined_depth/ (float16,
         # same layout) and the fused depth scored against the same ground truth (errors_fused, fused_coverage, errors_on_covered)
+    python tools/run_stream.py --synthetic 8 --out /tmp/eval --fuse /tmp/eval/scene.ply --geo-filter 2
+        # + the cross-view consistency filter (estdepth_amd.consistency): every target's depth is checked against the 2 targets before and
+        # after it; what is fused is the averaged depth on the pixels at least --geo-min-views neighbours agree on (fusion runs 2 targets
+        # behind the stream); metrics.json gains consistency, errors_filtered and filtered_coverage
 """
 import argparse
 import json
@@ -49,6 +53,11 @@ def main():
                     "write the fused depth maps to <out>/fused_depth and score them against the ground truth")
     ap.add_argument("--color", action="store_true", help="with --fuse: fuse every target's frame (the reader's 0..255 RGB, whatever the model is "
                     "fed) beside its depth; the PLY gets red / green / blue and --render-fused also writes <out>/fused_rgb/<stem>.png")
+    ap.add_argument("--geo-filter", type=int, default=0, metavar="R", help="check every target's depth against the R targets before and after it "
+                    "(estdepth_amd.consistency.ConsistencyWindow); with --fuse the filtered depth is what is fused, R targets behind the stream")
+    ap.add_argument("--geo-px", type=float, default=1.0, help="with --geo-filter: largest reprojection error in pixels")
+    ap.add_argument("--geo-rel", type=float, default=0.01, help="with --geo-filter: largest relative depth difference")
+    ap.add_argument("--geo-min-views", type=int, default=2, help="with --geo-filter: a pixel is kept where at least this many neighbours agree")
     ap.add_argument("--voxel-size", type=float, default=0.04)
     ap.add_argument("--volume-dims", type=int, nargs=3, default=(256, 256, 256), metavar=("Z", "Y", "X"))
     args = ap.parse_args()
@@ -94,6 +103,29 @@ def main():
                         cache_features=not args.no_feature_cache)
     errs, times, window, resized = RunningErrors(), [], [], 0
     volume, fuse_ms, targets = None, [], []
+    geo, errs_filtered, geo_count = None, RunningErrors(), {"gt": 0, "kept": 0}
+    if args.geo_filter:
+        from estdepth_amd.consistency import ConsistencyWindow
+        from estdepth_amd.metrics import compute_valid_depth_mask as valid_depth
+        geo = ConsistencyWindow(radius=args.geo_filter, min_views=args.geo_min_views, px_max=args.geo_px, rel_max=args.geo_rel)
+
+    def take_filtered(rec):
+        """a target the consistency window hands back: fuse it (--fuse) and score its averaged depth on the kept pixels"""
+        if volume is not None:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            volume.integrate_filtered(dict(rec, extra=rec["extra"]["rgb"]))
+            e1.record()
+            torch.cuda.synchronize()
+            fuse_ms.append(e0.elapsed_time(e1))
+        kept = torch.where(rec["views"] >= float(args.geo_min_views), rec["depth"], torch.zeros_like(rec["depth"])).cpu().numpy().astype(np.float64)
+        gt = rec["extra"]["gt"]
+        if gt.shape != kept.shape:
+            kept = to_gt_grid(kept, gt.shape)
+        errs_filtered.add(kept, gt)
+        gt_ok = valid_depth(gt)
+        geo_count["gt"] += int(gt_ok.sum())
+        geo_count["kept"] += int((gt_ok & (kept > 0)).sum())
 
     def to_gt_grid(a, shape):
         """nearest neighbour on pixel centres: a map at the network's resolution on the ground truth's pixel grid (no new depth values)"""
@@ -121,6 +153,7 @@ def main():
                 origin = frustum_volume(window[0]["cam_pose"], s["cam_intr"], (h, w), args.depth_min, args.depth_max,
                                         args.volume_dims, args.voxel_size)
                 volume = TSDFVolume(args.volume_dims, args.voxel_size, origin, device=dev, color=args.color)
+        if args.fuse and geo is None:
             frames_rgb = torch.stack([f["img"][0] for f in window])[None].to(dev) if args.color else None
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -139,11 +172,25 @@ def main():
             pred = to_gt_grid(pred, gt.shape)
             resized += 1
         errs.add(pred, gt)
+        if geo is not None:
+            dmap = outputs[("depth", 0, 0)][0, 0]
+            intr, image_hw = s["cam_intr"].reshape(3, 3).clone(), tuple(s["img"].shape[-2:])
+            if tuple(dmap.shape) != image_hw:                                # as TSDFVolume.integrate_outputs: the intrinsics of the maps' size
+                intr[0:2] = intr[0:2] * (dmap.shape[0] / float(image_hw[0]))
+            rgb = target["img"][0].to(dev) if args.color else None           # the colour frame travels with its depth
+            rec = geo.push(dmap, target["cam_pose"].reshape(4, 4), intr, extra={"rgb": rgb, "gt": gt})
+            if rec is not None:
+                take_filtered(rec)
         if args.render_fused:
             targets.append((target["img_path"], target["cam_pose"].reshape(4, 4), s["cam_intr"].reshape(3, 3), tuple(s["img"].shape[-2:]), pred, gt))
+    if geo is not None:
+        for rec in geo.flush():
+            take_filtered(rec)
     report = {"scene": scene_dir, "frames": len(reader), "windows": stream.windows,
               "mean_window_ms": 1e3 * float(np.mean(times[1:] or times or [0.0])), "errors": errs.mean(),
               "predictions_resized_to_gt_grid": resized}
+    if geo is not None:
+        report.update(consistency=geo.summary(), errors_filtered=errs_filtered.mean(), filtered_coverage=geo_count["kept"] / max(geo_count["gt"], 1))
     if volume is not None:
         os.makedirs(os.path.dirname(os.path.abspath(args.fuse)), exist_ok=True)
         report.update(fused_voxels=volume.fused_voxels(), points=volume.save_ply(args.fuse),
