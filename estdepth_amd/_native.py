@@ -116,6 +116,16 @@ class DepthConsistencyDesc(ctypes.Structure):
     ]
 
 
+class CloudNearestDesc(ctypes.Structure):
+    """Mirror of struct estd_cloud_nearest_desc (include/estd_hip.h)."""
+    _fields_ = [
+        ("M", ctypes.c_longlong), ("N", ctypes.c_longlong),
+        ("query", ctypes.c_void_p), ("order", ctypes.c_void_p), ("records", ctypes.c_void_p), ("cell_start", ctypes.c_void_p),
+        ("dist", ctypes.c_void_p), ("index", ctypes.c_void_p), ("stats", ctypes.c_void_p),
+        ("lo", ctypes.c_float * 3), ("cell", ctypes.c_float), ("max_dist", ctypes.c_float), ("dims", ctypes.c_int * 3),
+    ]
+
+
 _SIGNATURES = {
     "estd_version": (ctypes.c_int, []),
     "estd_status_string": (ctypes.c_char_p, [ctypes.c_int]),
@@ -192,6 +202,11 @@ _SIGNATURES = {
                                              c_float_p, c_stream]),
     "estd_tsdf_raycast_color": (ctypes.c_int, [ctypes.POINTER(TsdfRaycastColorDesc), c_stream]),
     "estd_depth_consistency": (ctypes.c_int, [ctypes.POINTER(DepthConsistencyDesc), c_stream]),
+    "estd_cloud_cell_keys": (ctypes.c_int, [c_float_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_float), ctypes.c_float,
+                                            ctypes.POINTER(ctypes.c_int), ctypes.c_void_p, c_stream]),
+    "estd_cloud_nearest": (ctypes.c_int, [ctypes.POINTER(CloudNearestDesc), c_stream]),
+    "estd_cloud_cell_centroids": (ctypes.c_int, [c_float_p, c_float_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_longlong, c_float_p, c_float_p, c_stream]),
 }
 
 # the superseded A/B kernels: exported only by a library built with ESTD_BUILD_AB=1 (estdepth_amd/build.py)

@@ -1,0 +1,243 @@
+"""3D scores of a fused reconstruction on the device: nearest-neighbour distances between two point clouds (csrc/cloud_nn.hip) and the figures
+reconstruction papers on ScanNet / 7-Scenes report from them (Atlas, NeuralRecon, SimpleRecon): accuracy, completeness, chamfer distance,
+precision / recall / F-score at a threshold.  The clouds are what ``TSDFVolume.extract_points`` produces or ``fusion3d.read_ply`` reads.
+
+    pred = vol.extract_points()                                        # dict(xyz, normal, ...)
+    gt = fusion3d.read_ply("scene_gt.ply")
+    scores = compare_clouds(pred["xyz"], torch.from_numpy(gt["xyz"]).to(dev), threshold=0.05, downsample=0.02)
+    scores = vol.compare(other_volume)                                 # the same between two volumes
+
+    grid = PointGrid(target, max_dist=1.0)                             # sort and cell table once ...
+    dist, index = grid.query(points)                                   # ... any number of queries
+
+The nearest-neighbour result is defined to the bit (include/estd_hip.h, estd_cloud_nearest): per query the smallest fp32
+``d2 = fma(dx, dx, fma(dy, dy, dz * dz))`` over ALL targets, the smallest original index attaining it, found iff ``d2 <= max_dist^2``;
+``dist = sqrt(d2)`` or ``max_dist``, ``index`` or -1.  The uniform grid behind it only decides which targets are looked at first; the cell
+edge is a tuning parameter and never changes a bit of the output.  There is no CPU path.
+
+The cell edge (``grid_plan``, ``cell=None``): two points per occupied cell of a SURFACE -- ``sqrt(2 A / n)`` with A the product of the two
+largest extents of the target's bounding box -- but not below ``max_dist / 32`` (a query with no target within ``max_dist`` walks at most 32
+rings).  The dense cell table is capped at 2^24 cells and 1024 cells per axis; a cell edge (the default or a given one) that would exceed
+either is enlarged in steps of 1/8 until it fits.
+"""
+import ctypes
+import math
+
+import numpy as np
+import torch
+
+from . import ops
+
+MAX_CELLS = ops.CLOUD_MAX_CELLS          # the dense table: cells in all
+MAX_DIM = ops.CLOUD_MAX_DIM              # ... and per axis (the kernel's conservative ring bound is derived for this many)
+RINGS_MAX = 32                           # the default cell is at least max_dist / RINGS_MAX
+POINTS_PER_CELL = 2.0                    # the default cell aims at this many points per occupied cell of a surface
+
+
+def _need(ok, msg):
+    if not ok:
+        raise RuntimeError(msg)
+
+
+def _dims(ext, cell):
+    return tuple(int(math.floor(e / cell)) + 1 for e in ext)
+
+
+def grid_plan(lo, hi, n, max_dist, cell=None):
+    """The grid of a target cloud with bounding box ``lo`` .. ``hi`` (three values each) and ``n`` points -> (cell, (nx, ny, nz)): the cell
+    edge as the fp32 value the kernels receive and the number of cells along x, y, z, ``floor((hi - lo) / cell) + 1`` each.  ``cell=None``:
+    the default rule of the module docstring.  Needs no device."""
+    lo = np.asarray(lo, dtype=np.float64).reshape(-1)
+    hi = np.asarray(hi, dtype=np.float64).reshape(-1)
+    _need(lo.size == 3 and hi.size == 3 and np.isfinite(lo).all() and np.isfinite(hi).all() and (hi >= lo).all(),
+          "grid_plan: lo and hi must be three finite values each with lo <= hi, got %r, %r" % (lo.tolist(), hi.tolist()))
+    _need(int(n) >= 1, "grid_plan: n must be at least 1, got %r" % (n,))
+    max_dist = float(max_dist)
+    _need(math.isfinite(max_dist) and max_dist > 0, "grid_plan: max_dist must be positive and finite, got %r" % (max_dist,))
+    ext = (hi - lo).tolist()
+    if cell is None:
+        e = sorted(ext, reverse=True)
+        cell = max(math.sqrt(POINTS_PER_CELL * e[0] * e[1] / int(n)), max_dist / RINGS_MAX)
+    else:
+        cell = float(cell)
+        _need(math.isfinite(cell) and cell > 0, "grid_plan: cell must be positive and finite, got %r" % (cell,))
+    cell = float(np.float32(cell))
+    _need(cell > 0 and math.isfinite(cell), "grid_plan: the cell edge %r leaves fp32" % (cell,))
+    dims = _dims(ext, cell)
+    while max(dims) > MAX_DIM or dims[0] * dims[1] * dims[2] > MAX_CELLS:
+        cell = float(np.float32(cell * 1.125))
+        _need(math.isfinite(cell), "grid_plan: the bounding box %r .. %r is too large for fp32" % (lo.tolist(), hi.tolist()))
+        dims = _dims(ext, cell)
+    return cell, dims
+
+
+def _check_cloud(t, name, op, device=None):
+    _need(isinstance(t, torch.Tensor), "%s: %s must be a tensor" % (op, name))
+    _need(t.is_cuda, "%s: %s must live on a ROCm device (estdepth_amd has no CPU path); got %s" % (op, name, t.device))
+    _need(t.dtype == torch.float32, "%s: %s must be float32, got %s" % (op, name, t.dtype))
+    _need(t.dim() == 2 and t.shape[1] == 3 and t.shape[0] < 2 ** 31, "%s: %s must be [n,3] with n < 2^31, got %s" % (op, name, tuple(t.shape)))
+    _need(device is None or t.device == device, "%s: %s is on %s but the other cloud on %s" % (op, name, t.device, device))
+    t = t.contiguous()
+    _need(bool(torch.isfinite(t).all()), "%s: %s holds a coordinate that is not finite" % (op, name))
+    return t
+
+
+def _check_max_dist(max_dist, op):
+    f32 = lambda v: ctypes.c_float(v).value
+    _need(isinstance(max_dist, (int, float)) and math.isfinite(max_dist) and f32(max_dist) > 0 and math.isfinite(f32(f32(max_dist) ** 2)),
+          "%s: max_dist must be positive and finite (and its square in fp32 too), got %r" % (op, max_dist))
+    return float(max_dist)
+
+
+class PointGrid:
+    """The search structure of one target cloud: the stable sort by cell key, the dense cell table and the 16-byte records, built once.
+    ``target`` [N,3] float32 on a ROCm device with finite coordinates (N = 0: nothing is ever found); ``cell``: the cell edge, None for the
+    default rule of ``grid_plan``."""
+
+    def __init__(self, target, max_dist, cell=None):
+        self.max_dist = _check_max_dist(max_dist, "PointGrid")
+        _need(cell is None or (isinstance(cell, (int, float)) and math.isfinite(cell) and cell > 0), "PointGrid: cell must be positive and finite, got %r" % (cell,))
+        target = _check_cloud(target, "target", "PointGrid")
+        self.device, self.n = target.device, int(target.shape[0])
+        if self.n == 0:
+            self.cell, self.dims, self.lo = float(np.float32(self.max_dist)), (1, 1, 1), torch.zeros(3)
+            self.records = torch.empty((0, 4), device=self.device)
+            self.cell_start = torch.zeros(2, device=self.device, dtype=torch.int32)
+            return
+        lo, hi = target.amin(0).cpu(), target.amax(0).cpu()
+        self.lo = lo.contiguous()
+        self.cell, self.dims = grid_plan(lo.tolist(), hi.tolist(), self.n, self.max_dist, cell)
+        cells = self.dims[0] * self.dims[1] * self.dims[2]
+        keys = ops.cloud_cell_keys(target, self.lo, self.cell, self.dims)
+        sorted_keys, order = torch.sort(keys, stable=True)
+        self.cell_start = torch.searchsorted(sorted_keys, torch.arange(cells + 1, device=self.device, dtype=torch.int64), out_int32=True).contiguous()
+        rec = torch.empty((self.n, 4), device=self.device, dtype=torch.int32)    # filled as integers: the bits of the coordinates and the original index
+        rec[:, :3] = target[order].view(torch.int32)
+        rec[:, 3] = order.to(torch.int32)
+        self.records = rec.view(torch.float32)
+
+    def query(self, points, stats=False):
+        """``points`` [M,3] -> (dist [M] float32, index [M] int64): the distance to and the original index of the nearest target within
+        ``max_dist``; ``max_dist`` and -1 where there is none.  ``stats=True`` (measurement only) appends the candidates examined per
+        query, int32 [M]."""
+        points = _check_cloud(points, "points", "PointGrid.query", self.device)
+        if points.shape[0] == 0:
+            out = (torch.empty(0, device=self.device), torch.empty(0, device=self.device, dtype=torch.int64))
+            return out + (torch.empty(0, device=self.device, dtype=torch.int32),) if stats else out
+        if self.n:
+            order = torch.sort(ops.cloud_cell_keys(points, self.lo, self.cell, self.dims), stable=True)[1]
+        else:
+            order = torch.arange(points.shape[0], device=self.device, dtype=torch.int64)
+        return ops.cloud_nearest(points, order, self.records, self.cell_start, self.lo, self.cell, self.dims, self.max_dist, stats=stats)
+
+
+def nearest(query, target, max_dist, cell=None):
+    """One-shot form of ``PointGrid(target, max_dist, cell).query(query)`` -> (dist [M], index [M])."""
+    _check_max_dist(max_dist, "nearest")
+    _need(isinstance(query, torch.Tensor) and isinstance(target, torch.Tensor), "nearest: query and target must be tensors")
+    _need(query.device == target.device, "nearest: query is on %s but the target on %s" % (query.device, target.device))
+    return PointGrid(target, max_dist, cell).query(query)
+
+
+def voxel_downsample(points, cell, attrs=None):
+    """Voxel-grid down-sampling: one point per occupied cell of edge ``cell`` (the grid starts at the cloud's bounding-box minimum), the mean
+    of the cell's points -> (points [K,3], attrs [K,C] or None, counts [K] int64), cells in ascending key order (z, then y, then x).
+    ``attrs`` [N,C], C <= 6 (normals, colour) are averaged the same way.  Sums run in float64 in the original order of the points and are
+    rounded to fp32 once: the result is the same for every call."""
+    _need(isinstance(cell, (int, float)) and math.isfinite(cell) and float(np.float32(cell)) > 0, "voxel_downsample: cell must be positive and finite, got %r" % (cell,))
+    points = _check_cloud(points, "points", "voxel_downsample")
+    n = points.shape[0]
+    if attrs is not None:
+        _need(isinstance(attrs, torch.Tensor) and attrs.dtype == torch.float32 and attrs.dim() == 2 and attrs.shape[0] == n
+              and 1 <= attrs.shape[1] <= ops.CLOUD_MAX_ATTRS and attrs.device == points.device,
+              "voxel_downsample: attrs must be float32 [%d,C] with 1 <= C <= %d on the points' device" % (n, ops.CLOUD_MAX_ATTRS))
+        attrs = attrs.contiguous()
+    if n == 0:
+        return points, attrs, torch.empty(0, device=points.device, dtype=torch.int64)
+    lo, hi = points.amin(0).cpu(), points.amax(0).cpu()
+    cell = float(np.float32(cell))
+    dims = _dims((hi.double() - lo.double()).tolist(), cell)
+    _need(max(dims) <= ops.CLOUD_KEY_MAX_DIM, "voxel_downsample: %r cells per axis (at most %d): the cell %g is too small for this cloud" % (dims, ops.CLOUD_KEY_MAX_DIM, cell))
+    keys = ops.cloud_cell_keys(points, lo.contiguous(), cell, dims)
+    sorted_keys, order = torch.sort(keys, stable=True)
+    _, counts = torch.unique_consecutive(sorted_keys, return_counts=True)
+    segments = torch.zeros(counts.shape[0] + 1, device=points.device, dtype=torch.int64)
+    segments[1:] = torch.cumsum(counts, 0)
+    out, out_attrs = ops.cloud_cell_centroids(points, attrs, order.contiguous(), segments)
+    return out, out_attrs, counts
+
+
+def _side(dist, index, max_dist, threshold):
+    """the figures of one direction from the clamped distances"""
+    n = int(dist.shape[0])
+    d64 = dist.double()
+    return dict(mean=float(d64.mean().item()) if n else 0.0, median=float(d64.median().item()) if n else 0.0,
+                share=float((dist < threshold).double().mean().item()) if n else 0.0, clamped=int((index < 0).sum().item()))
+
+
+def compare_clouds(pred, gt, threshold=0.05, max_dist=None, downsample=None, pred_normal=None, gt_normal=None, pred_color=None, gt_color=None,
+                   cell=None):
+    """The 3D scores of the cloud ``pred`` [P,3] against ``gt`` [G,3] (float32, one ROCm device, finite) -> dict of floats / ints:
+
+    accuracy / completeness: the mean distance pred -> gt / gt -> pred, each distance clamped to ``max_dist`` (default 20 ``threshold``);
+    chamfer: their mean;  precision / recall: the share of pred / gt with dist < ``threshold``;  fscore = 2 P R / (P + R), 0 when both are 0;
+    accuracy_median, completeness_median (torch.median: the lower of two middle values);  n_pred, n_gt;  clamped_pred, clamped_gt: the points with no neighbour within ``max_dist``, which
+    enter the means as ``max_dist`` -- with any, the means are lower bounds.  With both normals: normal_consistency = the mean
+    |n_pred . n_gt[index]| over found pairs, both directions averaged.  With both colours: color_l1 = the mean absolute colour difference at
+    the nearest neighbour over pairs with dist < ``threshold``, both directions averaged.  ``downsample``: a voxel edge -- both clouds (and
+    their normals / colours) go through ``voxel_downsample`` first, as evaluation protocols do (2 cm in Atlas's).  An empty cloud gives
+    zeros for its own means and shares.  Means are float64 sums by torch; ``cell`` is the search grid's edge (None: the default)."""
+    _need(isinstance(threshold, (int, float)) and math.isfinite(threshold) and threshold > 0, "compare_clouds: threshold must be positive and finite, got %r" % (threshold,))
+    if max_dist is None:
+        max_dist = 20.0 * threshold
+    max_dist = _check_max_dist(max_dist, "compare_clouds")
+    _need(threshold <= max_dist, "compare_clouds: threshold %g must not exceed max_dist %g" % (threshold, max_dist))
+    _need(downsample is None or (isinstance(downsample, (int, float)) and math.isfinite(downsample) and downsample > 0),
+          "compare_clouds: downsample must be a positive voxel edge, got %r" % (downsample,))
+    _need(isinstance(pred, torch.Tensor) and isinstance(gt, torch.Tensor), "compare_clouds: pred and gt must be tensors")
+    _need(pred.device == gt.device, "compare_clouds: pred is on %s but gt on %s" % (pred.device, gt.device))
+    pred, gt = _check_cloud(pred, "pred", "compare_clouds"), _check_cloud(gt, "gt", "compare_clouds", pred.device)
+    attrs = {}
+    for name, cloud, a in (("pred_normal", pred, pred_normal), ("gt_normal", gt, gt_normal), ("pred_color", pred, pred_color), ("gt_color", gt, gt_color)):
+        if a is not None:
+            _need(isinstance(a, torch.Tensor) and a.dtype == torch.float32 and tuple(a.shape) == tuple(cloud.shape) and a.device == cloud.device,
+                  "compare_clouds: %s must be float32 %s on the cloud's device" % (name, tuple(cloud.shape)))
+            attrs[name] = a.contiguous()
+    if downsample is not None:
+        for side, cloud in (("pred", pred), ("gt", gt)):
+            cols = [attrs[k] for k in (side + "_normal", side + "_color") if k in attrs]
+            pts, att, _ = voxel_downsample(cloud, downsample, torch.cat(cols, 1) if cols else None)
+            for j, k in enumerate(k for k in (side + "_normal", side + "_color") if k in attrs):
+                attrs[k] = att[:, 3 * j:3 * j + 3].contiguous()
+            if side == "pred":
+                pred = pts
+            else:
+                gt = pts
+    thr32 = float(np.float32(threshold))
+    d_pg, i_pg = PointGrid(gt, max_dist, cell).query(pred)
+    d_gp, i_gp = PointGrid(pred, max_dist, cell).query(gt)
+    a, c = _side(d_pg, i_pg, max_dist, thr32), _side(d_gp, i_gp, max_dist, thr32)
+    P, R = a["share"], c["share"]
+    out = dict(accuracy=a["mean"], completeness=c["mean"], chamfer=0.5 * (a["mean"] + c["mean"]), precision=P, recall=R,
+               fscore=2.0 * P * R / (P + R) if P + R > 0 else 0.0, accuracy_median=a["median"], completeness_median=c["median"],
+               n_pred=int(pred.shape[0]), n_gt=int(gt.shape[0]), clamped_pred=a["clamped"], clamped_gt=c["clamped"])
+
+    def pairs(src, dst, dist, index, fn, keep):
+        m = keep(dist, index)
+        if not bool(m.any()):
+            return None
+        return float(fn(src[m].double(), dst[index[m]].double()).mean().item())
+
+    if "pred_normal" in attrs and "gt_normal" in attrs:
+        dot = lambda x, y: (x * y).sum(1).abs()
+        found = lambda dist, index: index >= 0
+        v = [x for x in (pairs(attrs["pred_normal"], attrs["gt_normal"], d_pg, i_pg, dot, found),
+                         pairs(attrs["gt_normal"], attrs["pred_normal"], d_gp, i_gp, dot, found)) if x is not None]
+        out["normal_consistency"] = sum(v) / len(v) if v else 0.0
+    if "pred_color" in attrs and "gt_color" in attrs:
+        l1 = lambda x, y: (x - y).abs().mean(1)
+        near = lambda dist, index: (index >= 0) & (dist < thr32)
+        v = [x for x in (pairs(attrs["pred_color"], attrs["gt_color"], d_pg, i_pg, l1, near),
+                         pairs(attrs["gt_color"], attrs["pred_color"], d_gp, i_gp, l1, near)) if x is not None]
+        out["color_l1"] = sum(v) / len(v) if v else 0.0
+    return out

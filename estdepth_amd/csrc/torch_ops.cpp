@@ -575,6 +575,107 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> depth_consistency(const Tensor& targe
     return {views, visible, depth, rel_err};
 }
 
+// ------------------------------------------------------------------------------------------------ point clouds (csrc/cloud_nn.hip)
+static void check_cloud(const Tensor& t, const char* op, const char* name, int64_t cols)
+{
+    TORCH_CHECK(t.dim() == 2 && t.size(1) == cols && t.size(0) <= 0x7fffffffLL, op, ": ", name, " must be [n,", cols, "] with n < 2^31");
+}
+
+static void check_cloud_grid(const Tensor& lo, double cell, at::IntArrayRef dims, const char* op, int64_t max_dim)
+{
+    TORCH_CHECK(lo.defined() && lo.device().is_cpu() && lo.scalar_type() == at::kFloat && lo.is_contiguous() && lo.numel() == 3,
+                op, ": lo must be a contiguous CPU float32 tensor [3]");
+    for (int j = 0; j < 3; ++j) TORCH_CHECK(std::isfinite(lo.data_ptr<float>()[j]), op, ": lo holds a value that is not finite");
+    TORCH_CHECK(std::isfinite(cell) && (float)cell > 0.f && std::isfinite((float)cell) && std::isfinite(1.0f / (float)cell),
+                op, ": cell must be positive and finite in fp32 (and its reciprocal too), got ", cell);
+    TORCH_CHECK(dims.size() == 3, op, ": dims must be three sizes");
+    for (int j = 0; j < 3; ++j) TORCH_CHECK(dims[j] >= 1 && dims[j] <= max_dim, op, ": dims must be three sizes in 1..", max_dim, ", got ", dims[j]);
+}
+
+static const int64_t* lptr(const Tensor& t, const char* op, const char* name, const Tensor& like, int64_t size)
+{
+    TORCH_CHECK(t.defined() && t.dim() == 1 && t.scalar_type() == at::kLong && t.is_contiguous() && t.device() == like.device() &&
+                (size < 0 || t.size(0) == size), op, ": ", name, " must be a contiguous int64 vector of the right length on the cloud's device");
+    return t.data_ptr<int64_t>();
+}
+
+// points [n,3], lo: CPU float32 [3], dims: cells along x, y, z -> keys int64 [n]
+Tensor cloud_cell_keys(const Tensor& points, const Tensor& lo, double cell, at::IntArrayRef dims)
+{
+    const OpScope scope(points);
+    const float* pts = fptr(points, "points");
+    check_cloud(points, "cloud_cell_keys", "points", 3);
+    check_cloud_grid(lo, cell, dims, "cloud_cell_keys", ESTD_CLOUD_KEY_MAX_DIM);
+    const int64_t n = points.size(0);
+    Tensor keys = at::empty({n}, points.options().dtype(at::kLong));
+    const int d3[3] = {(int)dims[0], (int)dims[1], (int)dims[2]};
+    if (n)
+        check_status(estd_cloud_cell_keys(pts, (long long)n, lo.data_ptr<float>(), (float)cell, d3, reinterpret_cast<long long*>(keys.data_ptr<int64_t>()),
+                                          cur_stream()), "estd_cloud_cell_keys");
+    return keys;
+}
+
+// query [M,3], order int64 [M], records [N,4], cell_start int32 [cells + 1] -> (dist [M], index int64 [M], stats int32 [M] when asked
+// for (measurement only), else [0])
+std::tuple<Tensor, Tensor, Tensor> cloud_nearest(const Tensor& query, const Tensor& order, const Tensor& records, const Tensor& cell_start,
+                                                 const Tensor& lo, double cell, at::IntArrayRef dims, double max_dist, bool stats)
+{
+    const OpScope scope(query);
+    const float* q = fptr(query, "query");
+    check_cloud(query, "cloud_nearest", "query", 3);
+    const float* rec = fptr(records, "records");
+    check_cloud(records, "cloud_nearest", "records", 4);
+    const int64_t M = query.size(0), N = records.size(0);
+    const int64_t* ord = lptr(order, "cloud_nearest", "order", query, M);
+    TORCH_CHECK(std::isfinite(max_dist) && (float)max_dist > 0.f && std::isfinite((float)max_dist * (float)max_dist),
+                "cloud_nearest: max_dist must be positive and finite (and its square too), got ", max_dist);
+    check_cloud_grid(lo, cell, dims, "cloud_nearest", ESTD_CLOUD_MAX_DIM);
+    const int64_t cells = dims[0] * dims[1] * dims[2];
+    TORCH_CHECK(cells <= ESTD_CLOUD_MAX_CELLS, "cloud_nearest: ", cells, " cells, at most ", ESTD_CLOUD_MAX_CELLS);
+    TORCH_CHECK(cell_start.defined() && cell_start.dim() == 1 && cell_start.scalar_type() == at::kInt && cell_start.is_contiguous() &&
+                cell_start.size(0) == cells + 1 && cell_start.device() == query.device(),
+                "cloud_nearest: cell_start must be a contiguous int32 tensor [", cells + 1, "] (cells + 1) on the query's device");
+    Tensor dist = new_f32({M}, query), index = at::empty({M}, query.options().dtype(at::kLong));
+    Tensor st = at::empty({stats ? M : 0}, query.options().dtype(at::kInt));
+    if (M) {
+        estd_cloud_nearest_desc d{};
+        d.M = (long long)M; d.N = (long long)N;
+        d.query = q; d.order = reinterpret_cast<const long long*>(ord); d.records = rec; d.cell_start = cell_start.data_ptr<int32_t>();
+        d.dist = dist.data_ptr<float>(); d.index = reinterpret_cast<long long*>(index.data_ptr<int64_t>());
+        d.stats = stats ? reinterpret_cast<unsigned int*>(st.data_ptr<int32_t>()) : nullptr;
+        d.cell = (float)cell; d.max_dist = (float)max_dist;
+        for (int j = 0; j < 3; ++j) { d.lo[j] = lo.data_ptr<float>()[j]; d.dims[j] = (int)dims[j]; }
+        check_status(estd_cloud_nearest(&d, cur_stream()), "estd_cloud_nearest");
+    }
+    return {dist, index, st};
+}
+
+// points [n,3], attrs [n,C] (C = 0: none), order int64 [n], segments int64 [K + 1] -> (points [K,3], attrs [K,C])
+std::tuple<Tensor, Tensor> cloud_cell_centroids(const Tensor& points, const Tensor& attrs, const Tensor& order, const Tensor& segments)
+{
+    const OpScope scope(points);
+    const float* pts = fptr(points, "points");
+    check_cloud(points, "cloud_cell_centroids", "points", 3);
+    const int64_t n = points.size(0);
+    TORCH_CHECK(attrs.defined() && attrs.dim() == 2, "cloud_cell_centroids: attrs must be [n,C]");
+    const int64_t C = attrs.size(1);
+    const float* att = nullptr;
+    if (C) {
+        att = fptr(attrs, "attrs");
+        TORCH_CHECK(attrs.size(0) == n && C <= ESTD_CLOUD_MAX_ATTRS, "cloud_cell_centroids: attrs must be [n,C] with C <= ", ESTD_CLOUD_MAX_ATTRS);
+    }
+    const int64_t* ord = lptr(order, "cloud_cell_centroids", "order", points, n);
+    const int64_t* seg = lptr(segments, "cloud_cell_centroids", "segments", points, -1);
+    TORCH_CHECK(segments.size(0) >= 1 && segments.size(0) <= n + 1, "cloud_cell_centroids: segments must be [K + 1] with K <= n");
+    const int64_t K = segments.size(0) - 1;
+    Tensor out = new_f32({K, 3}, points), out_attrs = new_f32({K, C}, points);
+    if (K)
+        check_status(estd_cloud_cell_centroids(pts, att, (int)C, (long long)n, reinterpret_cast<const long long*>(ord),
+                                               reinterpret_cast<const long long*>(seg), (long long)K, out.data_ptr<float>(),
+                                               C ? out_attrs.data_ptr<float>() : nullptr, cur_stream()), "estd_cloud_cell_centroids");
+    return {out, out_attrs};
+}
+
 Tensor warp_attention(const Tensor& kv_target, at::TensorList kv_sources, const Tensor& mats, const Tensor& depth_values,
                       double depth_min, double depth_interval)
 {
@@ -1012,6 +1113,10 @@ TORCH_LIBRARY(estdepth_hip, m)
           "(Tensor, Tensor, Tensor, Tensor)");
     m.def("depth_consistency(Tensor target, Tensor[] sources, Tensor mats, float px_max, float rel_max, float z_near) -> "
           "(Tensor, Tensor, Tensor, Tensor)");
+    m.def("cloud_cell_keys(Tensor points, Tensor lo, float cell, int[] dims) -> Tensor");
+    m.def("cloud_nearest(Tensor query, Tensor order, Tensor records, Tensor cell_start, Tensor lo, float cell, int[] dims, float max_dist, "
+          "bool stats) -> (Tensor, Tensor, Tensor)");
+    m.def("cloud_cell_centroids(Tensor points, Tensor attrs, Tensor order, Tensor segments) -> (Tensor, Tensor)");
     m.def("profile_mark(int id) -> ()");
     m.def("set_reserved_cus(int n) -> int");
     m.def("conv3d_grid(int N, int D, int H, int W) -> int");
@@ -1063,6 +1168,9 @@ TORCH_LIBRARY_IMPL(estdepth_hip, CUDA, m)
     m.impl("tsdf_edge_colors", tsdf_edge_colors);
     m.impl("tsdf_raycast_color", tsdf_raycast_color);
     m.impl("depth_consistency", depth_consistency);
+    m.impl("cloud_cell_keys", cloud_cell_keys);
+    m.impl("cloud_nearest", cloud_nearest);
+    m.impl("cloud_cell_centroids", cloud_cell_centroids);
 }
 
 TORCH_LIBRARY_IMPL(estdepth_hip, CPU, m)

@@ -280,6 +280,29 @@ class TSDFVolume:
         write_ply(path, rec.numpy(), rgb)
         return rec.shape[0]
 
+    def compare(self, other, threshold=0.05, w_min=1.0, max_dist=None, downsample=None, cell=None):
+        """The 3D scores (``cloud_metrics.compare_clouds``: accuracy, completeness, chamfer, precision / recall / F-score at ``threshold``
+        metres, ...) of this volume's surface as the prediction against ``other`` as the ground truth: another ``TSDFVolume`` -- both sides
+        go through ``extract_points(w_min)`` -- or a dict with ``xyz`` [N,3] and optionally ``normal`` / ``color`` (device tensors or numpy
+        arrays, e.g. what ``read_ply`` returns).  Normals are compared when both sides have them, colours when both have a ``color``."""
+        from . import cloud_metrics
+
+        def side(x):
+            pts = x.extract_points(w_min=w_min) if isinstance(x, TSDFVolume) else x
+            if not isinstance(pts, dict) or pts.get("xyz") is None:
+                raise RuntimeError("compare: the other side must be a TSDFVolume or a dict with 'xyz'")
+            out = {}
+            for k in ("xyz", "normal", "color"):
+                v = pts.get(k)
+                if v is not None:
+                    out[k] = (torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)) if isinstance(v, np.ndarray) else v).to(self.device).contiguous()
+            return out
+        a, b = side(self), side(other)
+        return cloud_metrics.compare_clouds(a["xyz"], b["xyz"], threshold=threshold, max_dist=max_dist, downsample=downsample,
+                                            pred_normal=a.get("normal") if "normal" in b else None, gt_normal=b.get("normal") if "normal" in a else None,
+                                            pred_color=a.get("color") if "color" in b else None, gt_color=b.get("color") if "color" in a else None,
+                                            cell=cell)
+
     def reset(self):
         self.volume.zero_()
         if self.color is not None:
@@ -349,6 +372,86 @@ def write_ply(path, xyz_normal, rgb=None):
     with open(path, "wb") as f:
         f.write((head + "end_header\n").encode("ascii"))
         f.write(body)
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
+              "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def read_ply(path):
+    """The counterpart of ``write_ply`` -> dict(xyz float32 [N,3], normal float32 [N,3] or None, rgb uint8 [N,3] or None) as numpy arrays.
+    Reads what ``write_ply`` writes and any ``binary_little_endian`` or ``ascii`` file whose vertex element has float x y z, optionally
+    float nx ny nz and uchar red green blue; other vertex properties are skipped by their declared size, other elements (faces) are
+    ignored -- the vertex element must come first in a binary file unless the elements before it have no list property.  A big-endian or
+    malformed file raises RuntimeError."""
+    def bad(why):
+        raise RuntimeError("read_ply: %s: %s" % (path, why))
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header")
+    stop = data.find(b"\n", end)                               # the header may end its lines with CR LF
+    if not data.startswith(b"ply") or end < 0 or stop < 0:
+        bad("not a PLY file (no 'ply' magic or no end_header)")
+    try:
+        lines = [l.split() for l in data[:end].decode("ascii").splitlines()]
+    except UnicodeDecodeError:
+        bad("the header is not ASCII")
+    body = data[stop + 1:]
+    fmt, elements = None, []                                   # elements: [name, count, [(property, dtype or None for a list)]]
+    for w in lines[1:]:
+        if not w or w[0] in ("comment", "obj_info"):
+            continue
+        if w[0] == "format" and len(w) == 3:
+            fmt = w[1]
+        elif w[0] == "element" and len(w) == 3 and w[2].isdigit():
+            elements.append([w[1], int(w[2]), []])
+        elif w[0] == "property" and elements and len(w) == 3 and w[1] in _PLY_TYPES:
+            elements[-1][2].append((w[2], _PLY_TYPES[w[1]]))
+        elif w[0] == "property" and elements and len(w) == 5 and w[1] == "list" and w[2] in _PLY_TYPES and w[3] in _PLY_TYPES:
+            elements[-1][2].append((w[4], None))
+        else:
+            bad("header line %r not understood" % " ".join(w))
+    if fmt not in ("binary_little_endian", "ascii"):
+        bad("format %r is not supported (binary_little_endian and ascii are)" % (fmt,))
+    at = [i for i, e in enumerate(elements) if e[0] == "vertex"]
+    if len(at) != 1:
+        bad("expected one vertex element, found %d" % len(at))
+    _, n, props = elements[at[0]]
+    names = [p[0] for p in props]
+    if len(set(names)) != len(names) or any(t is None for _, t in props):
+        bad("the vertex element has a repeated or a list property")
+    types = dict(props)
+    if not all(types.get(k) == "f4" for k in ("x", "y", "z")):
+        bad("the vertex element needs float x, y, z")
+    has_normal = all(types.get(k) == "f4" for k in ("nx", "ny", "nz"))
+    has_rgb = all(types.get(k) == "u1" for k in ("red", "green", "blue"))
+    if fmt == "ascii":
+        rows = body.decode("ascii", errors="replace").split("\n")
+        skip = 0
+        for e in elements[:at[0]]:
+            skip += e[1]
+        if len(rows) < skip + n:
+            bad("%d vertex lines declared, the file ends early" % n)
+        try:
+            table = np.array([[float(v) for v in r.split()] for r in rows[skip:skip + n]], dtype=np.float64).reshape(n, -1)
+        except ValueError:
+            bad("a vertex line is not numeric or the lines differ in length")
+        if n and table.shape[1] != len(props):
+            bad("a vertex line has %d values, the header declares %d properties" % (table.shape[1], len(props)))
+        col = lambda keys, dt: np.ascontiguousarray(np.stack([table[:, names.index(k)] for k in keys], 1).astype(dt)) if n else np.zeros((0, 3), dt)
+    else:
+        offset = 0
+        for e in elements[:at[0]]:
+            if any(t is None for _, t in e[2]):
+                bad("a list property in front of the vertex element")
+            offset += e[1] * sum(np.dtype(t).itemsize for _, t in e[2])
+        dt = np.dtype([(k, "<" + t) for k, t in props])
+        if len(body) < offset + n * dt.itemsize:
+            bad("%d vertices of %d bytes declared, the file holds %d bytes" % (n, dt.itemsize, len(body) - offset))
+        rec = np.frombuffer(body, dtype=dt, count=n, offset=offset)
+        col = lambda keys, dt_: np.ascontiguousarray(np.stack([rec[k] for k in keys], 1).astype(dt_)) if n else np.zeros((0, 3), dt_)
+    return dict(xyz=col(("x", "y", "z"), np.float32), normal=col(("nx", "ny", "nz"), np.float32) if has_normal else None,
+                rgb=col(("red", "green", "blue"), np.uint8) if has_rgb else None)
 
 
 def frustum_volume(cam_pose, cam_intr, image_hw, depth_min, depth_max, dims, voxel_size):

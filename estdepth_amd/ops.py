@@ -1252,3 +1252,116 @@ def depth_consistency(target, sources, mats, px_max, rel_max, z_near):
                 d.mats[s][i // 12][i % 12] = flat[s * 24 + i]
         N.check(N.lib().estd_depth_consistency(ctypes.byref(d), _stream()), "estd_depth_consistency")
     return views, visible, depth, rel_err
+
+
+# ---------------------------------------------------------------------------------- point clouds (csrc/cloud_nn.hip)
+CLOUD_KEY_MAX_DIM = 1 << 20     # ESTD_CLOUD_KEY_MAX_DIM (include/estd_hip.h)
+CLOUD_MAX_DIM = 1024            # ESTD_CLOUD_MAX_DIM
+CLOUD_MAX_CELLS = 1 << 24       # ESTD_CLOUD_MAX_CELLS
+CLOUD_MAX_ATTRS = 6             # ESTD_CLOUD_MAX_ATTRS
+
+
+def _cloud(t, name, op, cols=3):
+    _chk(t, name)
+    _need(t.dim() == 2 and t.shape[1] == cols and t.shape[0] <= 0x7fffffff, "%s: %s must be [n,%d] with n < 2^31, got %s" % (op, name, cols, tuple(t.shape)))
+
+
+def _cloud_grid(lo, cell, dims, op, max_dim):
+    _need(isinstance(lo, torch.Tensor) and not lo.is_cuda and lo.dtype == torch.float32 and lo.is_contiguous() and lo.numel() == 3,
+          "%s: lo must be a contiguous CPU float32 tensor [3]" % op)
+    lo3 = lo.tolist()
+    _need(all(math.isfinite(v) for v in lo3), "%s: lo holds a value that is not finite" % op)
+    c = ctypes.c_float(cell).value if math.isfinite(cell) else float("nan")
+    _need(c > 0 and math.isfinite(c) and math.isfinite(ctypes.c_float(1.0 / c).value), "%s: cell must be positive and finite in fp32 (and its reciprocal too), got %r" % (op, cell))
+    dims = tuple(int(v) for v in dims)
+    _need(len(dims) == 3 and all(1 <= v <= max_dim for v in dims), "%s: dims must be three sizes in 1..%d, got %r" % (op, max_dim, dims))
+    return lo3, dims
+
+
+def cloud_cell_keys(points, lo, cell, dims):
+    """Grid keys of ``points`` [n,3] -> int64 [n] on the points' device: ``lo`` CPU float32 [3], ``cell`` the cell edge, ``dims`` the cells
+    along x, y, z; a point outside the grid gets the clamped cell (include/estd_hip.h, estd_cloud_cell_keys)."""
+    cell, dims = float(cell), [int(v) for v in dims]
+    if _use_torch():
+        return T().cloud_cell_keys(points, lo, cell, dims)
+    _cloud(points, "points", "cloud_cell_keys")
+    lo3, dims = _cloud_grid(lo, cell, dims, "cloud_cell_keys", CLOUD_KEY_MAX_DIM)
+    n = points.shape[0]
+    with torch.cuda.device(points.device):
+        keys = torch.empty(n, device=points.device, dtype=torch.int64)
+        if n:
+            N.check(N.lib().estd_cloud_cell_keys(_p(points), n, (ctypes.c_float * 3)(*lo3), cell, (ctypes.c_int * 3)(*dims),
+                                                 ctypes.c_void_p(keys.data_ptr()), _stream()), "estd_cloud_cell_keys")
+    return keys
+
+
+def cloud_nearest(query, order, records, cell_start, lo, cell, dims, max_dist, stats=False):
+    """Nearest target of every row of ``query`` [M,3] -> (dist [M] float32, index [M] int64[, stats [M] int32]) on the query's device.
+    ``records`` [N,4] / ``cell_start`` int32 [cells + 1]: the key-sorted targets and the cell table (cloud_metrics.PointGrid builds them),
+    ``order`` int64 [M]: the order the queries are taken in (a permutation, sorted by the queries' keys).  Not found within ``max_dist``:
+    dist = max_dist, index = -1.  The contract is spelled out in include/estd_hip.h (estd_cloud_nearest)."""
+    cell, max_dist, dims = float(cell), float(max_dist), [int(v) for v in dims]
+    if _use_torch():
+        dist, index, st = T().cloud_nearest(query, order, records, cell_start, lo, cell, dims, max_dist, bool(stats))
+        return (dist, index, st) if stats else (dist, index)
+    _cloud(query, "query", "cloud_nearest")
+    _cloud(records, "records", "cloud_nearest", cols=4)
+    M, n = query.shape[0], records.shape[0]
+    _need(isinstance(order, torch.Tensor) and order.dim() == 1 and order.dtype == torch.int64 and order.is_contiguous() and order.shape[0] == M
+          and order.device == query.device, "cloud_nearest: order must be a contiguous int64 tensor [M] on the query's device")
+    _need(records.device == query.device, "cloud_nearest: records are on %s but the query on %s" % (records.device, query.device))
+    _need(math.isfinite(max_dist) and ctypes.c_float(max_dist).value > 0 and math.isfinite(ctypes.c_float(ctypes.c_float(max_dist).value ** 2).value),
+          "cloud_nearest: max_dist must be positive and finite (and its square too), got %r" % max_dist)
+    lo3, dims = _cloud_grid(lo, cell, dims, "cloud_nearest", CLOUD_MAX_DIM)
+    cells = dims[0] * dims[1] * dims[2]
+    _need(cells <= CLOUD_MAX_CELLS, "cloud_nearest: %d cells, at most %d" % (cells, CLOUD_MAX_CELLS))
+    _need(isinstance(cell_start, torch.Tensor) and cell_start.dim() == 1 and cell_start.dtype == torch.int32 and cell_start.is_contiguous()
+          and cell_start.shape[0] == cells + 1 and cell_start.device == query.device,
+          "cloud_nearest: cell_start must be a contiguous int32 tensor [%d] (cells + 1) on the query's device" % (cells + 1))
+    dev = query.device
+    with torch.cuda.device(dev):
+        dist, index = torch.empty(M, device=dev), torch.empty(M, device=dev, dtype=torch.int64)
+        st = torch.empty(M, device=dev, dtype=torch.int32) if stats else None
+        if M:
+            d = N.CloudNearestDesc()
+            d.M, d.N = M, n
+            d.query, d.order, d.records, d.cell_start = query.data_ptr(), order.data_ptr(), records.data_ptr(), cell_start.data_ptr()
+            d.dist, d.index = dist.data_ptr(), index.data_ptr()
+            d.stats = st.data_ptr() if stats else None
+            d.cell, d.max_dist = cell, max_dist
+            for j in range(3):
+                d.lo[j], d.dims[j] = lo3[j], dims[j]
+            N.check(N.lib().estd_cloud_nearest(ctypes.byref(d), _stream()), "estd_cloud_nearest")
+    return (dist, index, st) if stats else (dist, index)
+
+
+def cloud_cell_centroids(points, attrs, order, segments):
+    """Means of the cells of a key-sorted cloud: ``points`` [n,3], ``attrs`` [n,C] (C <= 6) or None, ``order`` int64 [n] (sorted position ->
+    original index), ``segments`` int64 [K + 1] -> (points [K,3], attrs [K,C] or None), summed in float64 in the sorted order
+    (include/estd_hip.h, estd_cloud_cell_centroids)."""
+    if _use_torch():
+        _need(isinstance(points, torch.Tensor), "points must be a tensor")
+        pts, att = T().cloud_cell_centroids(points, attrs if attrs is not None else points.new_empty((0, 0)), order, segments)      # C = 0: no attributes
+        return pts, (att if attrs is not None else None)
+    _cloud(points, "points", "cloud_cell_centroids")
+    n = points.shape[0]
+    C = 0
+    if attrs is not None:
+        _chk(attrs, "attrs")
+        _need(attrs.dim() == 2 and attrs.shape[0] == n and attrs.shape[1] <= CLOUD_MAX_ATTRS and attrs.device == points.device,
+              "cloud_cell_centroids: attrs must be [n,C] with C <= %d on the points' device, got %s" % (CLOUD_MAX_ATTRS, tuple(attrs.shape)))
+        C = attrs.shape[1]
+    for t, name, size in ((order, "order", n), (segments, "segments", None)):
+        _need(isinstance(t, torch.Tensor) and t.dim() == 1 and t.dtype == torch.int64 and t.is_contiguous() and t.device == points.device
+              and (size is None or t.shape[0] == size), "cloud_cell_centroids: %s must be a contiguous int64 vector on the points' device" % name)
+    _need(1 <= segments.shape[0] <= n + 1, "cloud_cell_centroids: segments must be [K + 1] with K <= n, got %d for n = %d" % (segments.shape[0], n))
+    K = segments.shape[0] - 1
+    dev = points.device
+    with torch.cuda.device(dev):
+        out = torch.empty((K, 3), device=dev)
+        out_attrs = torch.empty((K, C), device=dev) if attrs is not None else None
+        if K:
+            N.check(N.lib().estd_cloud_cell_centroids(_p(points), _p(attrs) if C else None, C, n, ctypes.c_void_p(order.data_ptr()),
+                                                      ctypes.c_void_p(segments.data_ptr()), K, _p(out), _p(out_attrs) if C else None, _stream()),
+                    "estd_cloud_cell_centroids")
+    return out, out_attrs

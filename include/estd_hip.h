@@ -607,6 +607,70 @@ typedef struct estd_depth_consistency_desc {
 } estd_depth_consistency_desc;
 int estd_depth_consistency(const estd_depth_consistency_desc* desc, estd_stream_t stream);
 
+/* ---- nearest neighbours between point clouds and voxel-grid down-sampling (csrc/cloud_nn.hip) ----
+ * What the 3D scores of a reconstruction are made of (estdepth_amd/cloud_metrics.py: accuracy, completeness, precision / recall /
+ * F-score, chamfer distance).  Clouds are fp32 [n][3], every coordinate finite (the caller's duty; cloud_metrics.py checks it).
+ *
+ * The grid: cell_j(p) = (int)min(max(floor((p_j - lo_j) * inv_cell), 0), dims_j - 1) with inv_cell = 1.0f / cell formed once by the
+ * entry point in fp32, and key(p) = (cell_2 dims[1] + cell_1) dims[0] + cell_0; dims[j] counts the cells along coordinate j.
+ * lo3 and dims3 are HOST pointers to three values.  estd_cloud_cell_keys writes key(points[i]) to keys[i], i < n (a point outside
+ * the grid gets the clamped cell).  ESTD_ERR_ARG: n < 0, a null pointer (points / keys: with n > 0), lo not finite, cell or
+ * 1.0f / cell not positive and finite, a dims_j outside 1..ESTD_CLOUD_KEY_MAX_DIM.  ESTD_ERR_UNSUPPORTED: n >= 2^31.  n == 0 launches
+ * nothing. */
+#define ESTD_CLOUD_KEY_MAX_DIM (1 << 20)
+#define ESTD_CLOUD_MAX_DIM 1024
+#define ESTD_CLOUD_MAX_CELLS (1 << 24)
+#define ESTD_CLOUD_MAX_ATTRS 6
+int estd_cloud_cell_keys(const float* points, long long n, const float* lo3, float cell, const int* dims3, long long* keys,
+                         estd_stream_t stream);
+
+/* Nearest target per query.  THE CONTRACT, defined to the bit and independent of the grid: for query q and EVERY target p, in fp32,
+ *   dx = qx - px, dy = qy - py, dz = qz - pz;   d2 = fma(dx, dx, fma(dy, dy, dz * dz));
+ *   d2min = the smallest d2 over all targets;   index = the SMALLEST original target index attaining d2min;
+ *   found iff d2min <= r2, r2 = max_dist * max_dist (formed once by the entry point in fp32);
+ *   dist[q] = the IEEE correctly rounded square root of d2min, or max_dist when not found;   index[q] = index, or -1 when not found.
+ * Every element of dist [M] and index [M] is written by every call, with plain vector stores and no atomics: two calls give the same
+ * bits.  N == 0: nothing is found (records, cell_start and the grid are not read).  M == 0: no launch.
+ *
+ * The targets arrive sorted by key (stable) as 16-byte records: records[j] = (x, y, z, the bits of the int32 original index), 16-byte
+ * aligned, and cell_start [cells + 1] (int32): cell_start[k] = the number of targets whose key is < k.  The kernel walks the cells in
+ * rings around the query's (clamped) cell and stops in front of ring r >= 2 once (1 - 2^-5) ((r - 1) cell)^2 exceeds the smallest d2
+ * so far (at most r2): with dims_j <= ESTD_CLOUD_MAX_DIM the cell coordinates are off by less than 2^-12 cells, so no target that could
+ * win or tie is skipped, and `cell` never changes a bit of the output.  `order` [M] (or NULL = identity) is the order the queries are
+ * taken in -- a permutation of 0..M-1, sorted by the queries' own keys so that the lanes of a wave share cells; results are written
+ * at the query's own position; an entry outside 0..M-1 is ignored.  `stats` (or NULL; measurement only, tools/cloud_bench.py): [M]
+ * uint32, the candidates whose distance was evaluated.
+ * ESTD_ERR_ARG (before any launch, no device needed): a null descriptor, M or N negative, max_dist not finite or <= 0 or with a square
+ * that leaves fp32; with N > 0: null or misaligned records, null cell_start, a grid estd_cloud_cell_keys would reject, a dims_j above
+ * ESTD_CLOUD_MAX_DIM, more than ESTD_CLOUD_MAX_CELLS cells; with M > 0: null query, dist or index.  ESTD_ERR_UNSUPPORTED: M or
+ * N >= 2^31. */
+typedef struct estd_cloud_nearest_desc {
+    long long M, N;                               /* queries, targets */
+    const float* query;                           /* [M][3] */
+    const long long* order;                       /* [M] or NULL */
+    const float* records;                         /* [N][4], sorted by key */
+    const int* cell_start;                        /* [dims[0] dims[1] dims[2] + 1] */
+    float* dist;                                  /* [M] */
+    long long* index;                             /* [M] */
+    unsigned int* stats;                          /* NULL, or [M] */
+    float lo[3];                                  /* host values, copied into the launch arguments */
+    float cell;
+    float max_dist;
+    int dims[3];
+} estd_cloud_nearest_desc;
+int estd_cloud_nearest(const estd_cloud_nearest_desc* desc, estd_stream_t stream);
+
+/* Voxel-grid down-sampling: one output point per occupied cell, the mean of the cell's points.  The host sorts the points by key
+ * (stable, so a cell's points keep their original order) and passes `order` [n] (sorted position -> original index) and `segments`
+ * [K + 1] (cell k owns the sorted positions segments[k] .. segments[k + 1] - 1).  Per cell and column the values are added in float64
+ * in that order, divided by the count in float64 and rounded to fp32 once: out_points [K][3], and out_attrs [K][C] from the optional
+ * attribute columns attrs [n][C], C <= ESTD_CLOUD_MAX_ATTRS (normals, colour).  Cells come out in the order of `segments` (ascending
+ * key): the result does not depend on the launch shape.  Entries of `order` outside 0..n-1 are left out, segment bounds are clamped
+ * to 0..n.  ESTD_ERR_ARG: n or K negative, K > n, C outside 0..ESTD_CLOUD_MAX_ATTRS, a null pointer with K > 0 (attrs / out_attrs:
+ * with C > 0).  ESTD_ERR_UNSUPPORTED: n >= 2^31.  K == 0 launches nothing. */
+int estd_cloud_cell_centroids(const float* points, const float* attrs, int C, long long n, const long long* order,
+                              const long long* segments, long long K, float* out_points, float* out_attrs, estd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

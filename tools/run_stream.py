@@ -17,6 +17,10 @@ ground-truth depth.  Needs an MI355X (the model has no CPU path).
         # + the cross-view consistency filter (estdepth_amd.consistency): every target's depth is checked against the 2 targets before and
         # after it; what is fused is the averaged depth on the pixels at least --geo-min-views neighbours agree on (fusion runs 2 targets
         # behind the stream); metrics.json gains consistency, errors_filtered and filtered_coverage
+    python tools/run_stream.py --synthetic 8 --out /tmp/eval --fuse /tmp/eval/scene.ply --score-3d
+        # + the 3D scores of the fused scene (estdepth_amd.cloud_metrics): the ground-truth depth maps of the same targets are fused into a
+        # second volume of the same geometry and the two surfaces compared -- accuracy, completeness, chamfer, precision / recall / F-score;
+        # --score-3d GT.ply compares against that cloud instead; metrics.json gains recon_3d
 """
 import argparse
 import json
@@ -58,6 +62,12 @@ def main():
     ap.add_argument("--geo-px", type=float, default=1.0, help="with --geo-filter: largest reprojection error in pixels")
     ap.add_argument("--geo-rel", type=float, default=0.01, help="with --geo-filter: largest relative depth difference")
     ap.add_argument("--geo-min-views", type=int, default=2, help="with --geo-filter: a pixel is kept where at least this many neighbours agree")
+    ap.add_argument("--score-3d", nargs="?", const=True, default=None, metavar="GT.ply", help="with --fuse: score the fused surface in 3D "
+                    "(estdepth_amd.cloud_metrics.compare_clouds) against this ground-truth cloud, or without a path against the reader's "
+                    "ground-truth depth maps of the same targets fused into a second volume of the same geometry (no confidence gating)")
+    ap.add_argument("--score-threshold", type=float, default=0.05, help="with --score-3d: the precision / recall / F-score threshold in metres")
+    ap.add_argument("--score-max-dist", type=float, default=None, help="with --score-3d: distances are clamped here (default: 20 thresholds)")
+    ap.add_argument("--score-downsample", type=float, default=None, help="with --score-3d: voxel-grid down-sampling of both clouds first (metres)")
     ap.add_argument("--voxel-size", type=float, default=0.04)
     ap.add_argument("--volume-dims", type=int, nargs=3, default=(256, 256, 256), metavar=("Z", "Y", "X"))
     args = ap.parse_args()
@@ -65,6 +75,8 @@ def main():
         ap.error("--render-fused needs --fuse PATH.ply")
     if args.color and not args.fuse:
         ap.error("--color needs --fuse PATH.ply")
+    if args.score_3d is not None and not args.fuse:
+        ap.error("--score-3d needs --fuse PATH.ply")
 
     from estdepth_amd import DepthNetHybrid, synth
     from estdepth_amd.streaming import ESTMStream
@@ -103,6 +115,7 @@ def main():
                         cache_features=not args.no_feature_cache)
     errs, times, window, resized = RunningErrors(), [], [], 0
     volume, fuse_ms, targets = None, [], []
+    volume_gt = None                                                         # --score-3d without a path: the ground-truth depth maps, fused
     geo, errs_filtered, geo_count = None, RunningErrors(), {"gt": 0, "kept": 0}
     if args.geo_filter:
         from estdepth_amd.consistency import ConsistencyWindow
@@ -153,6 +166,15 @@ def main():
                 origin = frustum_volume(window[0]["cam_pose"], s["cam_intr"], (h, w), args.depth_min, args.depth_max,
                                         args.volume_dims, args.voxel_size)
                 volume = TSDFVolume(args.volume_dims, args.voxel_size, origin, device=dev, color=args.color)
+                if args.score_3d is True:
+                    volume_gt = TSDFVolume(args.volume_dims, args.voxel_size, origin, device=dev)
+            if volume_gt is not None:                                        # the target's ground truth on its own grid, intrinsics scaled to it
+                gt_map, image_hw = target["dmap"][0, 0].to(dev), tuple(s["img"].shape[-2:])
+                intr_gt = s["cam_intr"].reshape(3, 3).clone()
+                if tuple(gt_map.shape) != image_hw:
+                    intr_gt[0] = intr_gt[0] * (gt_map.shape[1] / float(image_hw[1]))
+                    intr_gt[1] = intr_gt[1] * (gt_map.shape[0] / float(image_hw[0]))
+                volume_gt.integrate(gt_map[None], target["cam_pose"].reshape(1, 4, 4), intr_gt)
         if args.fuse and geo is None:
             frames_rgb = torch.stack([f["img"][0] for f in window])[None].to(dev) if args.color else None
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -195,6 +217,22 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(args.fuse)), exist_ok=True)
         report.update(fused_voxels=volume.fused_voxels(), points=volume.save_ply(args.fuse),
                       mean_fuse_ms=float(np.mean(fuse_ms[1:] or fuse_ms)))
+    if volume is not None and args.score_3d is not None:
+        from estdepth_amd.fusion3d import read_ply
+        if volume_gt is not None:
+            other, gt_name = volume_gt, "ground-truth depth maps fused into a volume of the same geometry"
+        else:
+            ply = read_ply(args.score_3d)
+            other, gt_name = {"xyz": ply["xyz"], "normal": ply["normal"]}, args.score_3d
+            if args.color and ply["rgb"] is not None:                        # the volume keeps the reader's 0..255 RGB
+                other["color"] = ply["rgb"].astype(np.float32)
+        max_dist = args.score_max_dist if args.score_max_dist is not None else 20.0 * args.score_threshold
+        torch.cuda.synchronize()
+        t0 = time.time()
+        scores = volume.compare(other, threshold=args.score_threshold, max_dist=max_dist, downsample=args.score_downsample)
+        torch.cuda.synchronize()
+        report["recon_3d"] = dict(scores, threshold=args.score_threshold, max_dist=max_dist, downsample=args.score_downsample, ground_truth=gt_name,
+                                  compare_ms=1e3 * (time.time() - t0))
     if volume is not None and args.render_fused:
         # the fused model in every target's camera, on the pixel grid and in the units of the per-frame predictions
         from estdepth_amd.metrics import compute_valid_depth_mask
