@@ -317,7 +317,8 @@ int estd_vol_to_cdhw(const float* src, float* dst_cdhw, int C, int64_t S, int sr
 /* ---- fused inference BatchNorm2d (+ residual add) (+ ReLU) on NHWC maps, in place --------------------------------
  * x[p][c] = act(x[p][c] * scale[c] + shift[c] + residual[p][c]); replaces the BatchNorm2d -> (add) -> ReLU launches that
  * follow the library convolutions of the 2D backbones (resnet_encoder.py:43-49, psm_submodule.py:14-37,
- * hybrid_depth_decoder.py:17-30).  C multiple of 4; residual may be NULL. */
+ * hybrid_depth_decoder.py:17-30).  C multiple of 4; residual may be NULL.
+ * The ReLU is fmaxf(v, 0): a NaN becomes 0, where torch's ReLU propagates it (without relu a NaN passes through). */
 int estd_bn_act_nhwc(float* x, const float* scale, const float* shift, const float* residual, int relu,
                      int64_t n_pix, int C, estd_stream_t stream);
 
@@ -332,6 +333,7 @@ int estd_spp_upsample_cat(const float* raw, int c_raw, const float* skip, int c_
 /* ---- 2D refinement tail of the decoder (hybrid_models/hybrid_depth_decoder.py:267-290 / :392-415), glue around its convolutions --
  * estd_planes_cat_nhwc:    torch.cat([a, relu?(b)], 1) of two NCHW stacks a [N][Ca][HW], b [N][Cb][HW] (:268
  *                          cat([semantic_vs, relu(all_fused_logits)])) written as the NHWC map [N][HW][Ca+Cb]; Ca+Cb <= 496.
+ *                          The ReLU is v > 0 ? v : 0: a NaN in b becomes 0, where torch's ReLU propagates it (relu_b = 0 copies it).
  * estd_upsample2_cat_nhwc: torch.cat([upsample(x), skip], 1) (:269-272, :280-281): x [N][H/2][W/2][Cx] nearest x2 beside
  *                          skip [N][H][W][Cs] -> out [N][H][W][Cx+Cs] (NHWC; channel counts multiples of 4, H and W even).
  * estd_disp_head_nhwc:     depth_max * sigmoid(Conv2d(C, 1, 3, stride 1, padding 1, bias)(in)) (:274 dispconv_1, :279 dispconv_0):

@@ -41,6 +41,9 @@ U = 2.0 ** -24
 FIRST = 3.5                  # first-order bound of dist, in u, relative to the distance (derivation above)
 C_CLOUD = 2.0                # route constant
 BOUND = C_CLOUD * FIRST * U
+# test-only knob: plausible kernel mistakes of the nearest-neighbour search, evaluated by ``nearest32`` (tests/test_cloud_metrics_cpu.py
+# asserts that compare / check_ties / the closed form of the lattice pair reject each on some case)
+MISTAKES = ("largest_index_on_ties", "strict_radius", "ring_early")
 
 
 # ------------------------------------------------------------------------------------------------------------ float64 brute force
@@ -73,8 +76,11 @@ def distance64(query, target, index):
 
 
 # ------------------------------------------------------------------------------------------------------------ the contract in fp32
-def nearest32(query, target, max_dist, chunk=256):
-    """the contract of estd_cloud_nearest with numpy in fp32 (fma through float64, see above) -> (dist float32 [M], index int64 [M])"""
+def nearest32(query, target, max_dist, chunk=256, mistake=None, cell=None):
+    """the contract of estd_cloud_nearest with numpy in fp32 (fma through float64, see above) -> (dist float32 [M], index int64 [M]).
+    ``mistake``: one of MISTAKES, a deliberately wrong variant ("ring_early" searches a grid of edge ``cell`` anchored at the targets'
+    minimum and leaves out the last ring of cells a candidate within max_dist can lie in)."""
+    assert mistake is None or mistake in MISTAKES, mistake
     q, p = np.asarray(query, dtype=np.float32), np.asarray(target, dtype=np.float32)
     M, N = q.shape[0], p.shape[0]
     md = np.float32(max_dist)
@@ -89,9 +95,17 @@ def nearest32(query, target, max_dist, chunk=256):
         inner = (dz * dz).astype(np.float32)
         inner = (dy.astype(np.float64) * dy.astype(np.float64) + inner.astype(np.float64)).astype(np.float32)
         d2 = (dx.astype(np.float64) * dx.astype(np.float64) + inner.astype(np.float64)).astype(np.float32)
+        if mistake == "ring_early":                              # candidates in the rings 0 .. ceil(max_dist / cell) - 1 only
+            lo = p.min(0).astype(np.float64)
+            cq = np.floor((q[a:a + chunk].astype(np.float64) - lo) / cell)
+            cp = np.floor((p.astype(np.float64) - lo) / cell)
+            ring = np.abs(cq[:, None] - cp[None]).max(2)
+            d2 = np.where(ring <= np.ceil(float(md) / cell - 1e-6) - 1, d2, np.float32(np.inf))
         i = d2.argmin(1)                                         # the first = smallest index attaining the minimum
+        if mistake == "largest_index_on_ties":
+            i = d2.shape[1] - 1 - d2[:, ::-1].argmin(1)
         v = d2[np.arange(d2.shape[0]), i]
-        found = v <= r2
+        found = (v < r2) if mistake == "strict_radius" else (v <= r2)
         dist[a:a + chunk] = np.where(found, np.sqrt(v), md)
         index[a:a + chunk] = np.where(found, i, -1)
     return dist, index
@@ -126,6 +140,20 @@ def compare(dist, index, query, target, max_dist, dmin, label=""):
         assert (dist[~found] == np.float32(max_dist)).all(), label
         assert (dmin[~found] >= md * (1 - BOUND)).all(), label
     return fig
+
+
+def check_ties(index, target, label=""):
+    """the tie rule where it is exact: among targets with identical coordinates (identical d2 whatever the rounding) the reported index
+    is the smallest"""
+    index, t = np.asarray(index), np.ascontiguousarray(np.asarray(target, dtype=np.float32))
+    if t.shape[0] == 0:
+        return 0
+    _, first, inv = np.unique(t.view(np.uint32).reshape(t.shape[0], 3), axis=0, return_index=True, return_inverse=True)
+    first_of = first[inv.reshape(-1)]                  # per target: the smallest index with its coordinates
+    found = index >= 0
+    bad = found & (first_of[np.where(found, index, 0)] != index)
+    assert not bad.any(), "%s: %d queries report a duplicate target that is not the smallest index, first query %d" % (label, int(bad.sum()), int(np.argmax(bad)))
+    return int((first_of != np.arange(t.shape[0])).sum())
 
 
 def count_bracket(dmin, threshold):
@@ -188,6 +216,14 @@ def lattice_pair(n=24, spacing=0.05, delta=DELTA):
     return a, b
 
 
+def check_lattice(dist, index, delta=DELTA):
+    """the closed form of ``lattice_pair`` queried with max_dist = delta itself: dx = dy = 0 and dz = delta exactly, so d2 = fl(delta^2) = r2
+    and the contract's d2 <= r2 finds every query's own partner at exactly delta"""
+    dist, index = np.asarray(dist), np.asarray(index)
+    assert (index == np.arange(index.shape[0])).all(), "%d of %d partners at exactly max_dist were not found" % (int((index < 0).sum()), index.shape[0])
+    assert (dist == np.float32(delta)).all()
+
+
 def surface_points(pose, K, H, W):
     """points of the analytic plane + sphere of tsdf_ref.raycast_scene, one per pixel the camera sees -> float32 [n,3]"""
     depth = R.raycast_scene(pose, K, H, W)
@@ -200,6 +236,22 @@ def surface_points(pose, K, H, W):
 SIZES = ((1, 63), (63, 1), (64, 65), (65, 64), (257, 4096), (4096, 257), (4096, 4096))      # (targets, queries)
 CASES = ["rand_%dx%d" % s for s in SIZES] + ["outside", "one_cell", "cell_faces", "negative", "translated", "sparse", "clusters"]
 CELL_FACES = 0.25            # the explicit cell edge of "cell_faces" (and the lattice its targets sit on)
+
+
+# the route suite's clouds: every pair of these target / query counts (none, one, one short of / exactly / one past a block of 256)
+ROUTE_SIZES = (0, 1, 255, 256, 257)
+
+
+def route_case(n_target, n_query):
+    """dict(target, query, max_dist): uniform clouds of the route suite; with more than one point each the last target duplicates the
+    first (the smaller index wins) and the first query sits on it (distance exactly 0)"""
+    rng = np.random.RandomState(1000 * n_target + n_query)
+    target = rng.uniform(0.0, 1.0, (n_target, 3)).astype(np.float32)
+    query = rng.uniform(-0.1, 1.1, (n_query, 3)).astype(np.float32)
+    if n_target > 1 and n_query > 1:
+        target[-1] = target[0]
+        query[0] = target[0]
+    return dict(target=target, query=query, max_dist=0.2)
 
 
 def build_case(name):

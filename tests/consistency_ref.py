@@ -66,6 +66,9 @@ CASES = {
     "kdiff": dict(hw=(120, 160), S=2, kdiff=True),
 }
 FULL_CASE = dict(hw=(480, 640), S=4)
+# the route suite's maps: the smallest the contract allows and the edges of the kernel's 16 x 16 tiles, under 1 and 8 sources each
+# (make_case(hw, S, seed=S + hw[0])); tests/test_consistency_ref_cpu.py checks their ambiguous share
+ROUTE_SIZES, ROUTE_SOURCES = [(2, 2), (15, 17), (16, 16), (17, 33)], (1, 8)
 
 
 def matrices64(pose_t, K_t, poses_s, K_s):

@@ -81,6 +81,48 @@ def test_compare_rejects_wrong_results():
 
 
 # ------------------------------------------------------------------------------------------------ grid_plan
+@pytest.mark.parametrize("n_query", C.ROUTE_SIZES)
+@pytest.mark.parametrize("n_target", C.ROUTE_SIZES)
+def test_route_cases_standin_within_bound(n_target, n_query):
+    """the clouds of tests/test_gpu_recon3d_routes.py: the fp32 stand-in passes the comparison and the tie rule the device is held to"""
+    c = C.route_case(n_target, n_query)
+    dist, index = C.nearest32(c["query"], c["target"], c["max_dist"])
+    C.compare(dist, index, c["query"], c["target"], c["max_dist"], C.nearest64(c["query"], c["target"])[0], "route %d x %d" % (n_target, n_query))
+    assert C.check_ties(index, c["target"]) == (1 if n_target > 1 and n_query > 1 else 0)
+    if n_target > 1 and n_query > 1:
+        assert index[0] == 0 and dist[0] == 0
+
+
+@pytest.mark.parametrize("mistake", C.MISTAKES)
+def test_checks_reject_each_plausible_search_mistake(mistake):
+    """each plausible mistake of the search, evaluated by the fp32 stand-in, fails a check the GPU suites apply: the tie rule on exact
+    duplicates, the closed form of the lattice pair at max_dist = the distance itself, the comparison on a target three cells away"""
+    if mistake == "largest_index_on_ties":
+        c = C.build_case("one_cell")
+        dist, index = C.nearest32(c["query"], c["target"], c["max_dist"])
+        assert C.check_ties(index, c["target"]) == 32
+        dist, index = C.nearest32(c["query"], c["target"], c["max_dist"], mistake=mistake)
+        C.compare(dist, index, c["query"], c["target"], c["max_dist"], C.nearest64(c["query"], c["target"])[0])     # the bound alone passes it
+        with pytest.raises(AssertionError):
+            C.check_ties(index, c["target"])
+    elif mistake == "strict_radius":
+        a, b = C.lattice_pair()
+        C.check_lattice(*C.nearest32(a, b, C.DELTA))
+        dist, index = C.nearest32(a, b, C.DELTA, mistake=mistake)
+        assert (dist == np.float32(C.DELTA)).all()                  # "not found" reports max_dist too, and the bound accepts either side
+        C.compare(dist, index, a, b, C.DELTA, C.nearest64(a, b)[0])
+        with pytest.raises(AssertionError):
+            C.check_lattice(dist, index)
+    else:
+        a, b = C.lattice_pair(delta=0.11)
+        b[:, 2] = -b[:, 2]                                          # queries 2.2 cells below the targets' plane: three rings away
+        dmin = C.nearest64(b, a)[0]
+        C.compare(*C.nearest32(b, a, 0.15), b, a, 0.15, dmin)
+        dist, index = C.nearest32(b, a, 0.15, mistake=mistake, cell=0.05)
+        with pytest.raises(AssertionError):
+            C.compare(dist, index, b, a, 0.15, dmin)
+
+
 def test_grid_plan_default_rule():
     from estdepth_amd import cloud_metrics as M
     cell, dims = M.grid_plan([0, 0, 0], [2, 2, 2], 4096, 0.15)

@@ -44,6 +44,18 @@ def test_ambiguous_share_and_fp32_evaluation(name):
 
 
 # ------------------------------------------------------------------------------------------------------------ closed forms
+@pytest.mark.parametrize("S", C.ROUTE_SOURCES)
+@pytest.mark.parametrize("hw", C.ROUTE_SIZES)
+def test_route_cases_ambiguous_share_and_fp32_evaluation(hw, S):
+    """the small maps of tests/test_gpu_recon3d_routes.py (the edges of the 16 x 16 tiles, 1 and 8 sources): the same two properties"""
+    import test_gpu_recon3d_routes as G
+    assert (hw in G.CONS_SIZES) and len(G.CONS_SIZES) == 4
+    c = C.make_case(hw, S, seed=S + hw[0], name="route")
+    ref = C.evaluate(c["target"], c["sources"], c["mats"])
+    fig = C.compare(C.evaluate(c["target"], c["sources"], c["mats"], dtype=np.float32), ref, "route %dx%d S%d" % (hw + (S,)))
+    assert fig["amb_share"] <= C.AMB_CAP and fig["valid"] >= 4
+
+
 def test_identical_pose_and_maps():
     """a source at the target's own pose with the target's own map: the round trip ends where it started"""
     H, W, S = 60, 80, 3

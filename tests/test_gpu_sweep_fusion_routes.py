@@ -68,11 +68,10 @@ INSTANCES = {
     "softargmin": ["softargmin_up_kernel"],
     "layout": ["cdhw_to_vol_kernel", "vol_to_cdhw_kernel"],
 }
-# kernels of the two files that are not routes of this suite
+# kernels of the two files that are no routes of any suite (the 2D glue kernels that share est_fusion.hip -- bn_act_nhwc_kernel,
+# spp_upsample_cat_kernel -- are routes of tests/test_gpu_glue2d_routes.py)
 NOT_ROUTES = {
     "estd_mark_kernel": "profiler marker (estd_profile_mark), computes nothing",
-    "bn_act_nhwc_kernel": "2D glue kernel sharing est_fusion.hip, tested by the 2D suites",
-    "spp_upsample_cat_kernel": "2D glue kernel sharing est_fusion.hip, tested by the 2D suites",
 }
 KERNEL_RE = re.compile(r"\b(cam_\w+_kernel|homo_warp\w*_kernel|mix1x1_kernel|warp_\w+_kernel|attention_prewarped_kernel|groupnorm_finalize_kernel|"
                        r"gru_\w+_kernel|softargmin_up_kernel|cdhw_to_vol_kernel|vol_to_cdhw_kernel)(<[^>()]*>)?")

@@ -46,6 +46,24 @@ def test_reference_restates_tsdf_ref_and_bounds_fp32(name):
         D0, W0, C0 = got["D"], got["Wt"], got["C"]
 
 
+@pytest.mark.parametrize("mistake", CR.MISTAKES)
+def test_compare_rejects_each_colour_mistake(mistake):
+    """the colour blended with the weight the D update leaves behind, evaluated in fp32 as the kernel would: rejected (eight frames, so
+    every voxel but the first update sees the difference)"""
+    c = R.build_case("r8x16x64-t8-120x160")
+    from estdepth_amd import camera
+    mats = camera.tsdf_matrices(torch.from_numpy(c["poses"]), torch.from_numpy(c["K"]), c["origin"], c["voxel"]).numpy().reshape(-1, 3, 4)
+    images = CR.case_images(c)
+    Z0, C0 = np.zeros(c["dims"], np.float32), np.zeros((3,) + tuple(c["dims"]), np.float32)
+    ref = CR.integrate(Z0, Z0, C0, mats, c["depths"], images, None, **c["params"])
+    good = CR.integrate(Z0, Z0, C0, mats, c["depths"], images, None, dtype=np.float32, **c["params"])
+    assert CR.compare(good["C"], ref, C_before=C0)["updated"] > 1000
+    bad = CR.integrate(Z0, Z0, C0, mats, c["depths"], images, None, dtype=np.float32, mistake=mistake, **c["params"])
+    assert np.array_equal(bad["D"], good["D"]) and np.array_equal(bad["Wt"], good["Wt"])       # D and the weight are not affected
+    with pytest.raises(AssertionError):
+        CR.compare(bad["C"], ref, C_before=C0)
+
+
 @pytest.mark.parametrize("name", CR.NORMALISED)
 def test_normalised_images_with_negative_values(name):
     fx = CR.fixture(name, True)

@@ -166,6 +166,58 @@ def test_comparison_rejects_a_wrong_kernel():
     RR.compare(good, ref, "right")
 
 
+def test_brick_form_equals_the_whole_volume():
+    """raycast on a brick with index_offset (positions in the whole volume's voxel coordinates) == raycast on the whole volume whose
+    weights are zero outside the brick"""
+    vox, trunc, plane_z, dims, origin = 0.05, 0.2, 2.02, (40, 24, 32), (-0.83, -0.61, 1.0)
+    z = origin[2] + (np.arange(dims[0]) + 0.5) * vox
+    D = np.broadcast_to(np.clip((plane_z - z) / trunc, -1, 1)[:, None, None], dims).astype(np.float32)
+    Wt = np.zeros(dims, np.float32)
+    Wt[12:, 4:, 8:] = 2.0
+    M = RR.ray_matrix(np.eye(4), R.intrinsics(30, 40, fov_scale=2.3), origin, vox)
+    whole = RR.raycast(D, Wt, M, 30, 40, 0.5, vox, 60, 1.0)
+    brick = RR.raycast(D[12:, 4:, 8:], Wt[12:, 4:, 8:], M, 30, 40, 0.5, vox, 60, 1.0, index_offset=(8, 4, 12))
+    assert whole["hit"].sum() > 100
+    for k in ("depth", "normal", "weight", "hit", "amb", "tol_depth"):
+        assert np.array_equal(whole[k], brick[k]), k
+
+
+def _route_views():
+    import test_gpu_recon3d_routes as G
+    return [("%dx%d" % hw, hw) for hw in G.RAY_SIZES] + [(label, None) for label, _ in G.special_views()]
+
+
+@pytest.mark.parametrize("label,hw", _route_views())
+def test_route_views_ambiguous_share_and_fp32_evaluation(label, hw):
+    """the views of tests/test_gpu_recon3d_routes.py on its slab volume: the reference alone stays within the cap (depth and colour), and
+    the numpy-fp32 evaluation passes the comparison"""
+    import test_gpu_recon3d_routes as G
+    import tsdf_color_ref as CR
+    s = G._fused_slab()
+    view = G.slab_view(*hw) if hw else dict(G.special_views())[label]
+    args = (s["D"], s["W"], view["M"], view["H"], view["W"], view["t_min"], view["dt"], view["n_steps"], 1.0)
+    ref = RR.raycast(*args)
+    fig = RR.compare(RR.raycast(*args, dtype=np.float32), ref, label)
+    cref = CR.render_colors(s["D"], s["W"], s["C"], view, 1.0, ray=ref)
+    assert fig["amb_share"] <= RR.AMB_CAP and int(cref["amb"].sum()) <= RR.AMB_CAP * fig["hit"]
+    assert fig["hit"] >= (max(1, hw[0] * hw[1] // 16) if hw else 0)
+
+
+@pytest.mark.parametrize("mistake", RR.MISTAKES)
+def test_compare_rejects_each_plausible_kernel_mistake(mistake):
+    """each plausible mistake of the ray caster, evaluated in fp32 as the kernel would, fails the comparison: a back face from a ray that
+    starts inside the sphere, a hit whose first sample lies in an unobserved cell and w > w_min where the observed voxels hold exactly
+    w_min (w_min = 3 after three frames)"""
+    c, D, Wt = _fused("t3")
+    v = RR.view(c)
+    t_min, w_min = (1.7, 1.0) if mistake == "back_face" else (v["t_min"], 3.0)
+    args = (D, Wt, v["M"], v["H"], v["W"], t_min, v["dt"], v["n_steps"], w_min)
+    ref = RR.raycast(*args)
+    assert RR.compare(RR.raycast(*args, dtype=np.float32), ref, "right")["hit"] > 1000
+    with pytest.raises(AssertionError):
+        RR.compare(RR.raycast(*args, dtype=np.float32, mistake=mistake), ref, mistake)
+
+
 def test_special_views_of_the_gpu_suite():
     """the inputs the GPU suite asserts fixed outcomes on: looking away and from the side (no hit, no ambiguity), t_min inside the sphere
     (front faces only) and behind the plane (no hit at all)"""

@@ -91,6 +91,67 @@ def test_comparison_rejects_a_wrong_kernel():
         R.compare(got["D"], got["Wt"], ref)
 
 
+@pytest.mark.parametrize("name", sorted(R.ROUTE_CASES))
+def test_route_cases_ambiguous_share_and_fp32_evaluation(name):
+    """the small cases of tests/test_gpu_recon3d_routes.py: the same two properties under the same cap"""
+    c = R.build_case(name)
+    mats = _mats(c)
+    Z0 = np.zeros(c["dims"], np.float32)
+    ref = R.integrate(Z0, Z0, mats, c["depths"], None, **c["params"])
+    got = R.integrate(Z0, Z0, mats, c["depths"], None, dtype=np.float32, **c["params"])
+    fig = R.compare(got["D"], got["Wt"], ref, D_before=Z0, W_before=Z0)
+    assert fig["amb_share"] <= R.AMB_CAP and fig["updated"] >= 4
+    # the brick form: any sub-range of the volume evaluates to the same values at the volume's own indices
+    Z, Y, X = c["dims"]
+    rng = ((Z // 2, Z), (Y // 3, Y), (4 * (X // 8), X))
+    sl = tuple(slice(a, b) for a, b in rng)
+    brick = R.integrate(Z0[sl], Z0[sl], mats, c["depths"], None, voxel_range=rng, **c["params"])
+    for k in ("D", "Wt", "A", "updated", "amb"):
+        assert np.array_equal(brick[k], ref[k][sl]), k
+
+
+def test_big_volume_bricks_ambiguous_share_and_brick_forms():
+    """the bricks of the 520 x 1024 x 1024 case of tests/test_gpu_recon3d_routes.py: each within the cap on its own, the fp32 evaluation
+    passes; and the brick form of the extraction gives the whole volume's records (ids, positions, normals) away from the brick's faces"""
+    import test_gpu_recon3d_routes as G
+    case = G.big_case()
+    mats = _mats(case)
+    Z0 = np.zeros((8, 16, 64), np.float32)
+    for b in G.BIG_BRICKS:
+        rng = G.big_brick_range(b)
+        assert all(lo % s == 0 and hi <= d for (lo, hi), s, d in zip(rng, (8, 16, 64), G.BIG_DIMS))
+        ref = R.integrate(Z0, Z0, mats, case["depths"], None, voxel_range=rng, **case["params"])
+        got = R.integrate(Z0, Z0, mats, case["depths"], None, voxel_range=rng, dtype=np.float32, **case["params"])
+        fig = R.compare(got["D"], got["Wt"], ref, D_before=Z0, W_before=Z0)
+        assert fig["amb_share"] <= R.AMB_CAP and (fig["updated"] > 1000) == (b != (0, 0, 0))
+    assert tuple(b + s for b, s in zip(G.BIG_BRICKS[3], (8, 16, 64))) == G.BIG_DIMS            # the last brick of the volume
+    D, W, vox, origin, _ = _sphere_volume(n=24)
+    whole = R.extract(D, W, 1.0, vox, origin)
+    rng = ((6, 24), (0, 20), (4, 24))
+    part = R.extract(D[6:, :20, 4:], W[6:, :20, 4:], 1.0, vox, origin, voxel_range=rng, dims=D.shape)
+    idx = part["edge"] // 3
+    keep = (idx // (24 * 24) >= 8) & ((idx // 24) % 24 < 17) & (idx % 24 >= 6)
+    sel = np.isin(whole["edge"], part["edge"][keep])
+    assert keep.sum() > 100 and sel.sum() == keep.sum()
+    for k in ("xyz", "normal", "weight", "tol_xyz"):
+        assert np.array_equal(part[k][keep], whole[k][sel]), k
+
+
+@pytest.mark.parametrize("mistake", R.INTEGRATE_MISTAKES)
+def test_compare_rejects_each_integrate_mistake(mistake):
+    """each plausible mistake of the integrate kernel, evaluated in fp32 as the kernel would, fails the comparison the GPU suites apply
+    (eight frames into a volume whose weight is capped at 4, so that the cap is reached)"""
+    c = R.build_case("r8x16x64-t8-120x160")
+    mats, params = _mats(c), dict(c["params"], w_max=4.0)
+    Z0 = np.zeros(c["dims"], np.float32)
+    ref = R.integrate(Z0, Z0, mats, c["depths"], None, **params)
+    good = R.integrate(Z0, Z0, mats, c["depths"], None, dtype=np.float32, **params)
+    assert R.compare(good["D"], good["Wt"], ref)["updated"] > 1000 and good["Wt"].max() == 4.0
+    bad = R.integrate(Z0, Z0, mats, c["depths"], None, dtype=np.float32, mistake=mistake, **params)
+    with pytest.raises(AssertionError):
+        R.compare(bad["D"], bad["Wt"], ref)
+
+
 def _sphere_volume(n=48, vox=0.05, radius=0.8, trunc=0.2):
     origin = (-n * vox / 2,) * 3
     c = (np.arange(n) + 0.5) * vox + origin[0]
@@ -122,6 +183,27 @@ def test_extraction_reference_on_a_sphere():
     assert cos.min() > 1.0 - 2.0 * (vox / radius), cos.min()
     np.testing.assert_allclose(np.linalg.norm(ref["normal"], axis=1), 1.0, atol=1e-12)
     assert (ref["weight"] == 2.0).all()
+
+
+@pytest.mark.parametrize("mistake", R.EXTRACT_MISTAKES)
+def test_compare_points_rejects_each_extraction_mistake(mistake):
+    """each plausible mistake of the extraction, evaluated by the reference itself, fails compare_points: on a sphere (curved, so a
+    one-sided difference tilts the normal), and for the double count on a ramp through a voxel that is exactly zero"""
+    if mistake == "cross_counted_twice":
+        x = np.arange(8, dtype=np.float32)
+        D = np.broadcast_to(0.25 * (x - 3.0), (4, 4, 8)).astype(np.float32).copy()
+        W, vox, origin = np.full((4, 4, 8), 2.0, np.float32), 0.1, (0.0, 0.0, 0.0)
+        assert (D[..., 3] == 0).all()
+    else:
+        D, W, vox, origin, _ = _sphere_volume(n=24)
+    ref = R.extract(D, W, 1.0, vox, origin)
+    bad = R.extract(D, W, 1.0, vox, origin, mistake=mistake)
+    as_got = lambda r: {k: r[k].astype(np.float32) if k != "edge" else r[k] for k in ("edge", "xyz", "normal", "weight")}       # noqa: E731
+    R.compare_points(as_got(ref), ref)
+    if mistake == "cross_counted_twice":
+        assert len(bad["edge"]) == 2 * len(ref["edge"]) == 32
+    with pytest.raises(AssertionError):
+        R.compare_points(as_got(bad), ref)
 
 
 def test_extraction_one_sided_and_unobserved_neighbours():

@@ -47,6 +47,8 @@ def color_constant(n_updates, weighted=True):
     (the rounded weight sums), rounded up to the next multiple of 1 / 2 and never below C_COLOR"""
     c = 1.25 + (max(int(n_updates), 1) - 1) / 8.0 * bool(weighted)
     return max(C_COLOR, float(np.ceil(2 * c) / 2))
+# test-only knob: plausible kernel mistakes (tests/test_tsdf_color_ref_cpu.py asserts that compare rejects each on some case)
+MISTAKES = ("color_weight_after",)
 CASES = ("t1", "t3", "t8", "gated", "weighted", "second", "holes", "odd")
 NORMALISED = ("t3", "weighted")          # cases that are also run with images normalised to negative values
 MEDIAN_FACTOR = 1.25         # the semantic bar: median colour error at the extracted points <= this x the float64 reference's own median
@@ -79,10 +81,12 @@ def case_images(case, normalised=False):
 
 # ------------------------------------------------------------------------------------------------------------ integrate
 def integrate(D0, W0, C0, mats, depths, images, confs=None, *, trunc, z_near=1e-3, conf_min=0.0, weighted=False, w_max=64.0, dtype=np.float64,
-              z_block=16):
+              z_block=16, mistake=None):
     """D0, W0 [Z,Y,X], C0 [3,Z,Y,X] float32 (before the call); mats [T,3,4] float32; depths / confs [T,H,W], images [T,3,H,W] float32.
     ``dtype=np.float32`` evaluates the contract in numpy fp32 arithmetic (the CPU stand-in for the kernel).
+    ``mistake``: one of MISTAKES, a deliberately wrong variant for the discrimination test.
     Returns dict(D, Wt, C (``dtype``), A_c [Z,Y,X] (float64, units of 2^-24), updated, amb (bool))."""
+    assert mistake is None or mistake in MISTAKES, mistake
     f = dtype
     D0, W0, C0 = np.asarray(D0, dtype=np.float32), np.asarray(W0, dtype=np.float32), np.asarray(C0, dtype=np.float32)
     mats = np.asarray(mats, dtype=np.float32).reshape(-1, 3, 4)
@@ -160,6 +164,10 @@ def integrate(D0, W0, C0, mats, depths, images, confs=None, *, trunc, z_near=1e-
             for k in range(3):
                 col = images[t, k][vi, ui].astype(f)
                 m = np.maximum(m, np.maximum(np.abs(C[k].astype(np.float64)), np.abs(col.astype(np.float64))))
+                if mistake == "color_weight_after":          # blended with the weight the D update leaves behind, not the one it starts from
+                    Wn = np.minimum(den, f(wmax32))
+                    C[k] = np.where(ok, (C[k] * Wn + col * w) / (Wn + w), C[k])
+                    continue
                 C[k] = np.where(ok, (C[k] * Wt + col * w) / den, C[k])
             Ac = np.where(ok, Ac * Wt.astype(np.float64) / den.astype(np.float64) + 4.0 * m, Ac)
             D = np.where(ok, Dn, D)

@@ -44,6 +44,8 @@ U = 2.0 ** -24
 C_POS = 2.0                  # decision tolerance = C_POS * rounding bound
 C_RAY = 4.0                  # route constant of the depth / normal / weight bounds, from the derivation above
 AMB_CAP = R.AMB_CAP          # ambiguous pixels: at most this share of the hit pixels in every case
+# test-only knob: plausible kernel mistakes (tests/test_tsdf_raycast_ref_cpu.py asserts that compare rejects each on some case)
+MISTAKES = ("back_face", "prev_unobserved", "corner_gt")
 
 # the inputs of the suite: a pose that was never fused, rays sampled from 0.3 m to 3.6 m in steps of one voxel
 HELD_OUT_POSE = R.look_at((0.12, -0.08, -0.05), (0.1, 0.0, 2.2))
@@ -53,6 +55,11 @@ N_STEPS = int(round((T_MAX - T_MIN) / R.VOXEL)) + 1
 # the ambiguity cap and are not compared; "t1", "gated", "weighted" have no voxel of weight 3
 VALUE_CASES = [("t1", 1.0)] + [(n, w) for n in ("t3", "t8", "second", "inside", "holes", "odd") for w in (1.0, 3.0)] + [("weighted", 0.25)]
 FULL_CASE = ("full", 1.0)
+# image sizes (H, W) of the route suite's renders of the 9 x 17 x 68 slab of tsdf_ref.ROUTE_CASES (tests/test_gpu_recon3d_routes.py builds
+# the views): 1, 2, 1 and 6 tiles of 16 x 16 pixels (the map edges), then 7, 8, 9 and 17 tiles -- fewer workgroups than the eight XCDs
+# the kernel spreads them over, as many, one more, two rounds and one.  tests/test_tsdf_raycast_ref_cpu.py checks the ambiguous share of
+# every one (a 40 x 40 render of nine tiles sits above the cap and was replaced by 33 x 40).
+ROUTE_SIZES = [(1, 1), (15, 17), (16, 16), (17, 33), (15, 100), (20, 60), (33, 40), (10, 270)]
 
 
 def ray_matrix(pose, K, origin, voxel):
@@ -64,9 +71,11 @@ def ray_matrix(pose, K, origin, voxel):
     return np.concatenate([A, o[:, None]], 1).astype(np.float32)
 
 
-def cell_observed(Wt, w_min):
+def cell_observed(Wt, w_min, mistake=None):
     """[Z-1,Y-1,X-1] bool: all eight corner weights of the cell >= w_min (compared as stored fp32 values: exact)"""
     ok = np.asarray(Wt, np.float32) >= np.float32(w_min)
+    if mistake == "corner_gt":                       # w > w_min: a corner of exactly w_min counts as unobserved
+        ok = np.asarray(Wt, np.float32) > np.float32(w_min)
     return (ok[:-1, :-1, :-1] & ok[:-1, :-1, 1:] & ok[:-1, 1:, :-1] & ok[:-1, 1:, 1:]
             & ok[1:, :-1, :-1] & ok[1:, :-1, 1:] & ok[1:, 1:, :-1] & ok[1:, 1:, 1:])
 
@@ -80,14 +89,14 @@ def _lookup(cobs, ix, iy, iz):
     return out
 
 
-def _k_interval(r, o, dims, t_min, dt, n_steps):
+def _k_interval(r, o, dims, t_min, dt, n_steps, first=(0.0, 0.0, 0.0)):
     """per ray the sample indices [klo, khi] that can lie inside the volume (float64 slab test on the box widened by 1e-3 voxel and a
     relative margin, the interval by two samples); klo > khi: none"""
     n = r.shape[0]
     klo, khi = np.zeros(n), np.full(n, float(n_steps - 1))
     for j in range(3):
         eps = 1e-3 + 1e-5 * (abs(o[j]) + dims[j])
-        lo, hi = -eps, dims[j] - 1 + eps
+        lo, hi = first[j] - eps, first[j] + dims[j] - 1 + eps
         rj = r[:, j]
         zero = rj == 0
         with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
@@ -108,11 +117,16 @@ def _lerp(a, b, t):
     return a + t * (b - a)
 
 
-def raycast(D, Wt, M, H, W, t_min, dt, n_steps, w_min, dtype=np.float64, rows=16):
+def raycast(D, Wt, M, H, W, t_min, dt, n_steps, w_min, dtype=np.float64, rows=16, mistake=None, index_offset=None):
     """D, Wt [Z,Y,X] float32; M [3,4] float32; t_min, dt, w_min as the kernel receives them (rounded to fp32 here).  Returns a dict of [H,W]
     arrays: depth, weight, normal [H,W,3] (``dtype``), hit, amb, skip_normal (bool), tol_depth, tol_weight, tol_normal [H,W,3] (float64,
-    absolute, to be scaled by C_RAY) and samples (int: samples evaluated up to the hit)."""
+    absolute, to be scaled by C_RAY) and samples (int: samples evaluated up to the hit).  ``mistake``: one of MISTAKES, a deliberately
+    wrong variant for the discrimination test.  ``index_offset`` = (x0, y0, z0): D, Wt are the brick of a larger volume that starts at
+    that voxel, and M is the larger volume's matrix (positions stay in its voxel coordinates, so the fp32 arithmetic is the kernel's);
+    everything outside the brick counts as unobserved, which is the larger volume's truth when its weights are zero there."""
+    assert mistake is None or mistake in MISTAKES, mistake
     f = dtype
+    off = np.zeros(3, np.int64) if index_offset is None else np.asarray(index_offset, np.int64)
     D, Wt = np.asarray(D, dtype=np.float32), np.asarray(Wt, dtype=np.float32)
     Z, Y, X = D.shape
     dims = np.array([X, Y, Z], dtype=np.float64)
@@ -120,7 +134,7 @@ def raycast(D, Wt, M, H, W, t_min, dt, n_steps, w_min, dtype=np.float64, rows=16
     Mf, M64 = M32.astype(f), M32.astype(np.float64)
     tmin32, dt32 = np.float32(t_min), np.float32(dt)
     tmin64, dt64 = float(tmin32), float(dt32)
-    cobs = cell_observed(Wt, w_min)
+    cobs = cell_observed(Wt, w_min, mistake)
     o, o64 = Mf[:, 3], M64[:, 3]
     out = {"depth": np.zeros((H, W), f), "weight": np.zeros((H, W), f), "normal": np.zeros((H, W, 3), f), "hit": np.zeros((H, W), bool),
            "amb": np.zeros((H, W), bool), "skip_normal": np.zeros((H, W), bool), "tol_depth": np.zeros((H, W)), "tol_weight": np.zeros((H, W)),
@@ -134,7 +148,7 @@ def raycast(D, Wt, M, H, W, t_min, dt, n_steps, w_min, dtype=np.float64, rows=16
         r = np.stack([Mf[j, 0] * uf + (Mf[j, 1] * vf + Mf[j, 2]) for j in range(3)], 1)                       # [n,3] in f
         r64 = r.astype(np.float64)
         S = np.stack([np.abs(M64[j, 0] * uu) + np.abs(M64[j, 1] * vv) + np.abs(M64[j, 2]) for j in range(3)], 1)
-        klo, khi = _k_interval(r64, o64, dims, tmin64, dt64, n_steps)
+        klo, khi = _k_interval(r64, o64, dims, tmin64, dt64, n_steps, off.astype(np.float64))
         done = ~(klo <= khi)
         amb = np.zeros(n, bool)
         hit_b = np.zeros(n, bool)
@@ -161,7 +175,7 @@ def raycast(D, Wt, M, H, W, t_min, dt, n_steps, w_min, dtype=np.float64, rows=16
             p = (o[None] + t * r[idx]).astype(f)
             p64 = p.astype(np.float64)
             fl = np.floor(p)
-            ii = fl.astype(np.int64)
+            ii = fl.astype(np.int64) - off[None]
             obs = _lookup(cobs, ii[:, 0], ii[:, 1], ii[:, 2])
             e_p = U * (4 * t64 * S[idx] + 4 * np.abs(t64 * r64[idx]) + np.abs(o64)[None])
             rnd = np.round(p64)
@@ -172,12 +186,14 @@ def raycast(D, Wt, M, H, W, t_min, dt, n_steps, w_min, dtype=np.float64, rows=16
                 sel = np.nonzero(near[:, j])[0]
                 if sel.size:
                     a, b = ii[sel].copy(), ii[sel].copy()
-                    a[:, j] = rnd[sel, j].astype(np.int64) - 1
-                    b[:, j] = rnd[sel, j].astype(np.int64)
+                    a[:, j] = rnd[sel, j].astype(np.int64) - off[j] - 1
+                    b[:, j] = rnd[sel, j].astype(np.int64) - off[j]
                     amb_face[sel] |= _lookup(cobs, a[:, 0], a[:, 1], a[:, 2]) != _lookup(cobs, b[:, 0], b[:, 1], b[:, 2])
             F, Wb, G = np.zeros(m, f), np.zeros(m, f), np.zeros((m, 3), f)
             eF, eWb, eG = np.zeros(m), np.zeros(m), np.zeros((m, 3))
             sub = np.nonzero(obs)[0]
+            if mistake == "prev_unobserved":         # F is interpolated in every cell of the volume, observed or not
+                sub = np.nonzero(((ii >= 0) & (ii <= np.array([X - 2, Y - 2, Z - 2])[None])).all(1))[0]
             if sub.size:
                 ix, iy, iz = ii[sub, 0], ii[sub, 1], ii[sub, 2]
                 fx, fy, fz = ((p[sub] - fl[sub]).astype(f)).T
@@ -212,6 +228,10 @@ def raycast(D, Wt, M, H, W, t_min, dt, n_steps, w_min, dtype=np.float64, rows=16
             amb[idx] |= amb_face
             Fp, Gp, Wbp = P["F"][idx], P["G"][idx], P["Wb"][idx]
             hit = obs & P["obs"][idx] & (Fp > 0) & (F <= 0)
+            if mistake == "back_face":               # any sign change, the surface seen from behind included
+                hit = obs & P["obs"][idx] & (((Fp > 0) & (F <= 0)) | ((Fp < 0) & (F >= 0)))
+            if mistake == "prev_unobserved":         # ... and only sample k has to be observed
+                hit = obs & (Fp > 0) & (F <= 0)
             if hit.any():
                 h = np.nonzero(hit)[0]
                 gi = idx[h]

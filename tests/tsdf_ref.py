@@ -37,6 +37,9 @@ C_POS = 2.0                  # decision tolerance = C_POS * running rounding bou
 C_INTEGRATE = 5.0            # route constant of the integrate bound, from the derivation above
 C_EXTRACT = 8.0              # route constant of the extraction bounds
 AMB_CAP = 0.03               # ambiguous voxels: at most this share of the updated voxels in every case
+# test-only knob: plausible kernel mistakes (tests/test_tsdf_ref_cpu.py asserts that compare / compare_points reject each on some case)
+MISTAKES = ("pixel_truncation", "wt_uncapped", "cap_before_blend", "cross_counted_twice", "normal_negated", "one_sided_gradient")
+INTEGRATE_MISTAKES, EXTRACT_MISTAKES = MISTAKES[:3], MISTAKES[3:]
 
 
 # ------------------------------------------------------------------------------------------------------------ analytic fixture
@@ -114,10 +117,14 @@ def _dot4(A_row, ix, iy, iz, f):
 
 
 def integrate(D0, W0, mats, depths, confs=None, *, trunc, z_near=1e-3, conf_min=0.0, weighted=False, w_max=64.0, dtype=np.float64,
-              z_block=16):
+              z_block=16, voxel_range=None, mistake=None):
     """D0, W0 [Z,Y,X] float32 (the volume before the call); mats [T,3,4] float32; depths / confs [T,H,W] float32.
     ``dtype=np.float32`` evaluates the same contract in numpy fp32 arithmetic (the CPU stand-in for the kernel).
+    ``voxel_range`` = ((z0, z1), (y0, y1), (x0, x1)): D0, W0 (and every result) are the brick [z0:z1, y0:y1, x0:x1] of a larger volume,
+    evaluated at the voxel indices of that volume with the volume's own matrices (a cropped volume with a shifted origin would hand the
+    kernel other fp32 matrices).  ``mistake``: one of INTEGRATE_MISTAKES, a deliberately wrong variant for the discrimination test.
     Returns dict(D, Wt (``dtype``), A (float64, units of 2^-24), updated, amb (bool), n_updates (int))."""
+    assert mistake is None or mistake in INTEGRATE_MISTAKES, mistake
     f = dtype
     D0, W0 = np.asarray(D0, dtype=np.float32), np.asarray(W0, dtype=np.float32)
     mats = np.asarray(mats, dtype=np.float32).reshape(-1, 3, 4)
@@ -125,6 +132,8 @@ def integrate(D0, W0, mats, depths, confs=None, *, trunc, z_near=1e-3, conf_min=
     T, H, W = depths.shape
     assert mats.shape[0] == T
     Z, Y, X = D0.shape
+    (z0, z1), (y0, y1), (x0, x1) = voxel_range if voxel_range is not None else ((0, Z), (0, Y), (0, X))
+    assert (z1 - z0, y1 - y0, x1 - x0) == (Z, Y, X), "D0 / W0 must have the shape of voxel_range"
     trunc32, znear32, cmin32, wmax32 = (np.float32(v) for v in (trunc, z_near, conf_min, w_max))
     # the farthest valid depth in the 3 x 3 pixels around each pixel (-inf where none is valid)
     dvalid = np.where(np.isfinite(depths) & (depths > 0), depths.astype(np.float64), -np.inf)
@@ -134,8 +143,8 @@ def integrate(D0, W0, mats, depths, confs=None, *, trunc, z_near=1e-3, conf_min=
            "updated": np.zeros((Z, Y, X), dtype=bool), "amb": np.zeros((Z, Y, X), dtype=bool), "n_updates": np.zeros((Z, Y, X), dtype=np.int32)}
     for zb in range(0, Z, z_block):
         sl = slice(zb, min(Z, zb + z_block))
-        iz, iy, ix = np.meshgrid(np.arange(sl.start, sl.stop, dtype=np.float64), np.arange(Y, dtype=np.float64),
-                                 np.arange(X, dtype=np.float64), indexing="ij")
+        iz, iy, ix = np.meshgrid(np.arange(z0 + sl.start, z0 + sl.stop, dtype=np.float64), np.arange(y0, y1, dtype=np.float64),
+                                 np.arange(x0, x1, dtype=np.float64), indexing="ij")
         D, Wt = D0[sl].astype(f), W0[sl].astype(f)
         A = np.zeros(D.shape)
         upd = np.zeros(D.shape, dtype=bool)
@@ -154,6 +163,8 @@ def integrate(D0, W0, mats, depths, confs=None, *, trunc, z_near=1e-3, conf_min=
                 e_qu = (ea + np.abs(qa.astype(np.float64)) * ec) / c64 + U * np.abs(qa.astype(np.float64)) + U * np.abs(qu.astype(np.float64))
                 e_qv = (eb + np.abs(qb.astype(np.float64)) * ec) / c64 + U * np.abs(qb.astype(np.float64)) + U * np.abs(qv.astype(np.float64))
                 fu, fv = np.floor(qu), np.floor(qv)
+                if mistake == "pixel_truncation":                      # (int)(a / c): the pixel by truncation, not floor(x + 0.5)
+                    fu, fv = np.trunc(qa), np.trunc(qb)
             inimg = front & (fu >= 0) & (fu < W) & (fv >= 0) & (fv < H)
             # ---- ambiguity of the discontinuous decisions
             d_c = C_POS * ec
@@ -193,12 +204,12 @@ def integrate(D0, W0, mats, depths, confs=None, *, trunc, z_near=1e-3, conf_min=
             w = np.where(ok, w, f(1.0))
             tsdf = np.where(ok, tsdf, f(0.0))
             den = Wt + w
-            Dn = (D * Wt + tsdf * w) / den
+            Dn = (D * Wt + tsdf * w) / (np.minimum(den, f(wmax32)) if mistake == "cap_before_blend" else den)
             A_f = (Sc + d.astype(np.float64)) / float(trunc32) + 1.0
             An = (A * Wt.astype(np.float64) + A_f * w.astype(np.float64)) / den.astype(np.float64) + 4.0
             D = np.where(ok, Dn, D)
             A = np.where(ok, An, A)
-            Wt = np.where(ok, np.minimum(den, f(wmax32)), Wt)
+            Wt = np.where(ok, den if mistake == "wt_uncapped" else np.minimum(den, f(wmax32)), Wt)
             upd |= ok
             nup += ok
         out["D"][sl], out["Wt"][sl], out["A"][sl], out["updated"][sl], out["amb"][sl], out["n_updates"][sl] = D, Wt, A, upd, amb, nup
@@ -240,7 +251,7 @@ def compare(got_D, got_W, ref, weighted=False, D_before=None, W_before=None):
 
 
 # ------------------------------------------------------------------------------------------------------------ extraction
-def _gradient(D, obs):
+def _gradient(D, obs, mistake=None):
     """per-axis (x, y, z) gradient of D [Z,Y,X] float64 with the contract's central / one-sided / zero choice -> [3][Z,Y,X]"""
     g = []
     for axis in (2, 1, 0):                       # x, y, z
@@ -254,20 +265,33 @@ def _gradient(D, obs):
         dl[1:] = np.where(lo[1:], Dm[:-1], Dm[1:])
         dh[:-1] = np.where(hi[:-1], Dm[1:], Dm[:-1])
         gk = np.where(lo & hi, 0.5 * (dh - dl), dh - dl)
+        if mistake == "one_sided_gradient":          # D[q + 1] - D[q] wherever the upper neighbour is observed, the central difference never
+            gk = np.where(hi, dh - Dm, dh - dl)
         g.append(np.moveaxis(gk, 0, axis))
     return g
 
 
-def extract(D32, W32, w_min, voxel_size, origin):
+def extract(D32, W32, w_min, voxel_size, origin, mistake=None, voxel_range=None, dims=None):
     """D32, W32 [Z,Y,X] float32.  Returns dict sorted by edge id: edge (int64), xyz, normal [N,3], weight [N] (float64) and the bound
-    magnitudes tol_xyz, tol_normal [N,3], tol_weight [N] (absolute), skip_normal [N] (bool)."""
+    magnitudes tol_xyz, tol_normal [N,3], tol_weight [N] (absolute), skip_normal [N] (bool).  ``mistake``: one of EXTRACT_MISTAKES.
+    ``voxel_range`` = ((z0, z1), (y0, y1), (x0, x1)) with ``dims`` = the (Z, Y, X) of the whole volume: D32, W32 are that brick of the
+    volume; edge ids, positions and their bounds are the whole volume's.  The brick's outer voxel layers see no neighbour beyond the
+    brick: records within two voxels of a face of the brick that is no face of the volume are the caller's to discard."""
+    assert mistake is None or mistake in EXTRACT_MISTAKES, mistake
     D32, W32 = np.asarray(D32, dtype=np.float32), np.asarray(W32, dtype=np.float32)
     Z, Y, X = D32.shape
     vs, org = float(np.float32(voxel_size)), np.asarray(origin, dtype=np.float32).astype(np.float64)
     D, Wt = D32.astype(np.float64), W32.astype(np.float64)
     obs = W32 >= np.float32(w_min)
-    g = _gradient(D, obs)
-    lin = np.arange(Z * Y * X, dtype=np.int64).reshape(Z, Y, X)
+    g = _gradient(D, obs, mistake)
+    if voxel_range is None:
+        off, lin = np.zeros(3), np.arange(Z * Y * X, dtype=np.int64).reshape(Z, Y, X)
+    else:
+        (z0, z1), (y0, y1), (x0, x1) = voxel_range
+        assert (z1 - z0, y1 - y0, x1 - x0) == (Z, Y, X), "D32 / W32 must have the shape of voxel_range"
+        off = np.array([x0, y0, z0], dtype=np.float64)
+        gz, gy, gx = np.meshgrid(np.arange(z0, z1, dtype=np.int64), np.arange(y0, y1, dtype=np.int64), np.arange(x0, x1, dtype=np.int64), indexing="ij")
+        lin = (gz * dims[1] + gy) * dims[2] + gx
     recs = {k: [] for k in ("edge", "xyz", "normal", "weight", "tol_xyz", "tol_normal", "tol_weight", "skip_normal")}
     for k, axis in enumerate((2, 1, 0)):
         a = [slice(None)] * 3
@@ -276,10 +300,12 @@ def extract(D32, W32, w_min, voxel_size, origin):
         a, b = tuple(a), tuple(b)
         d0, d1 = D[a], D[b]
         cr = obs[a] & obs[b] & (((d0 < 0) & (0 <= d1)) | ((d1 < 0) & (0 <= d0)))
+        if mistake == "cross_counted_twice":         # d0 <= 0 <= d1: a voxel at exactly 0 closes one edge and opens the next
+            cr = obs[a] & obs[b] & (((d0 <= 0) & (0 <= d1)) | ((d1 <= 0) & (0 <= d0))) & ((d0 != 0) | (d1 != 0))
         sel = np.nonzero(cr)
         d0, d1 = d0[sel], d1[sel]
         s = d0 / (d0 - d1)
-        idx3 = np.stack([sel[2], sel[1], sel[0]], -1).astype(np.float64)          # (x, y, z) of the edge's first voxel
+        idx3 = np.stack([sel[2], sel[1], sel[0]], -1).astype(np.float64) + off    # (x, y, z) of the edge's first voxel
         cell = idx3 + 0.5
         cell[:, k] += s
         g0 = np.stack([gj[a][sel] for gj in g], -1)
@@ -289,6 +315,8 @@ def extract(D32, W32, w_min, voxel_size, origin):
         length = np.sqrt((gg * gg).sum(-1))
         with np.errstate(divide="ignore", invalid="ignore"):
             n = np.where(length[:, None] > 0, gg / length[:, None], 0.0)
+            if mistake == "normal_negated":
+                n = -n
             tol_n = C_EXTRACT * U * ((G + G.sum(-1, keepdims=True)) / length[:, None] + 1.0)
         skip = (length <= 16 * U * G.sum(-1)) & (G.sum(-1) > 0)
         w0, w1 = Wt[a][sel], Wt[b][sel]
@@ -347,9 +375,18 @@ CASES = {
 }
 
 
+# Small cases for a route suite of the integration: volumes at the edges of the integrate kernel's 64 x 16 x ZCHUNK (8) bricks -- one 16-byte
+# group, one voxel short of a brick in every dimension, one voxel past it, exactly one brick -- under 1 and 8 frames and maps of 1 x 1,
+# 3 x 5 and 120 x 160 pixels, placed where the sphere's near side runs through them.  A table of its own: the suites over CASES ask for
+# more than a thousand updated voxels per case.  tests/test_tsdf_ref_cpu.py checks the ambiguous share of every one of them.
+ROUTE_DIMS = {(1, 1, 4): (0.04, 0.035, 1.43), (7, 15, 60): (-0.8, -0.17, 1.36), (9, 17, 68): (-0.92, -0.2, 1.33), (8, 16, 64): (-0.86, -0.19, 1.35)}
+ROUTE_CASES = {"r%dx%dx%d-t%d-%dx%d" % (dims + (T,) + hw): dict(T=T, hw=hw, dims=dims, origin=org)
+               for dims, org in ROUTE_DIMS.items() for T in (1, 8) for hw in ((1, 1), (3, 5), (120, 160))}
+
+
 def build_case(name):
     """dict(dims, origin, voxel, trunc, poses [T,4,4] f64, K [3,3] f64, depths [T,H,W] f32, confs or None, params for integrate())"""
-    c = dict(CASES[name])
+    c = dict(CASES[name] if name in CASES else ROUTE_CASES[name])
     T, (H, W) = c["T"], c["hw"]
     K = intrinsics(H, W)
     poses = scene_poses(T, seed=len(name))
