@@ -126,6 +126,17 @@ class CloudNearestDesc(ctypes.Structure):
     ]
 
 
+class FrameAlignDesc(ctypes.Structure):
+    """Mirror of struct estd_frame_align_desc (include/estd_hip.h)."""
+    _fields_ = [
+        ("H", ctypes.c_int), ("W", ctypes.c_int), ("Hm", ctypes.c_int), ("Wm", ctypes.c_int),
+        ("dist_max", ctypes.c_float), ("z_near", ctypes.c_float), ("conf_min", ctypes.c_float),
+        ("depth", ctypes.c_void_p), ("conf", ctypes.c_void_p), ("m_depth", ctypes.c_void_p), ("m_normal", ctypes.c_void_p),
+        ("residual", ctypes.c_void_p), ("match", ctypes.c_void_p), ("sums", ctypes.c_void_p), ("partials", ctypes.c_void_p),
+        ("L", ctypes.c_float * 12), ("Fm", ctypes.c_float * 12), ("Bm", ctypes.c_float * 12),
+    ]
+
+
 _SIGNATURES = {
     "estd_version": (ctypes.c_int, []),
     "estd_status_string": (ctypes.c_char_p, [ctypes.c_int]),
@@ -207,6 +218,8 @@ _SIGNATURES = {
     "estd_cloud_nearest": (ctypes.c_int, [ctypes.POINTER(CloudNearestDesc), c_stream]),
     "estd_cloud_cell_centroids": (ctypes.c_int, [c_float_p, c_float_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
                                                  ctypes.c_longlong, c_float_p, c_float_p, c_stream]),
+    "estd_frame_align_partials": (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int]),
+    "estd_frame_align": (ctypes.c_int, [ctypes.POINTER(FrameAlignDesc), c_stream]),
 }
 
 # the superseded A/B kernels: exported only by a library built with ESTD_BUILD_AB=1 (estdepth_amd/build.py)

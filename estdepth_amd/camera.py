@@ -246,3 +246,21 @@ def consistency_matrices(pose_t, K_t, poses_s, K_s):
             M = torch.cat([Kb @ rel[:3, :3] @ torch.inverse(Ka), (Kb @ rel[:3, 3])[:, None]], 1)
             out[s, j] = M.reshape(-1).float()
     return out
+
+
+# ------------------------------------------------------------------------------------------------ frame-to-model alignment
+def frame_align_matrices(pose_guess, K, model_pose, K_m):
+    """The three matrices of estd_frame_align for a live frame at the camera-to-world ``pose_guess`` [4,4] with intrinsics ``K`` [3,3] and
+    model maps rendered at ``model_pose`` [4,4] with ``K_m`` [3,3]: L = [R_g K^-1 | c_g] takes a live pixel (u, v, 1) times its z-depth to
+    the world, Fm = K_m [R|t]_world->model takes a world point to the model's (x, y, 1) times the depth there, Bm = [R_m K_m^-1 | c_m]
+    takes a model pixel times its depth to the world.  Formed in float64 on the host and rounded to fp32 -> CPU float32 [3,12] (3x4
+    row-major: L, Fm, Bm)."""
+    Pg = pose_guess.detach().to(device="cpu", dtype=torch.float64).reshape(4, 4)
+    Pm = model_pose.detach().to(device="cpu", dtype=torch.float64).reshape(4, 4)
+    Kg = K.detach().to(device="cpu", dtype=torch.float64).reshape(3, 3)
+    Km = K_m.detach().to(device="cpu", dtype=torch.float64).reshape(3, 3)
+    out = torch.empty(3, 12, dtype=torch.float32)
+    out[0] = torch.cat([Pg[:3, :3] @ torch.inverse(Kg), Pg[:3, 3:4]], 1).reshape(-1).float()
+    out[1] = (Km @ torch.inverse(Pm)[:3, :4]).reshape(-1).float()
+    out[2] = torch.cat([Pm[:3, :3] @ torch.inverse(Km), Pm[:3, 3:4]], 1).reshape(-1).float()
+    return out

@@ -1047,6 +1047,52 @@ std::tuple<Tensor, Tensor> camera_matrices_host(const Tensor& cam_poses, const T
 }
 
 int64_t set_reserved_cus(int64_t n) { return estd_set_reserved_cus((int)n); }
+// ------------------------------------------------------------------------------------------------ frame-to-model alignment
+// csrc/track/frame_align.hip: live depth [H,W] (+ optional conf) against the model maps m_depth [Hm,Wm] / m_normal [Hm,Wm,3]; mats: CPU
+// float32 [3,12] (L, Fm, Bm: host values of the launch arguments) -> (residual [H,W], match int32 [H,W], sums float64 [29])
+std::tuple<Tensor, Tensor, Tensor> frame_align(const Tensor& depth, const OptTensor& conf, const Tensor& m_depth, const Tensor& m_normal,
+                                               const Tensor& mats, double dist_max, double z_near, double conf_min)
+{
+    const OpScope scope(depth);
+    const float* dp = fptr(depth, "depth");
+    TORCH_CHECK(depth.dim() >= 2, "frame_align: depth must be [H,W] (leading 1s allowed)");
+    const int64_t H = depth.size(-2), W = depth.size(-1);
+    TORCH_CHECK(depth.numel() == H * W, "frame_align: depth must be [H,W] (leading 1s allowed)");
+    TORCH_CHECK(H > 0 && W > 0 && H * W <= 0x7fffffffLL, "frame_align: the map size must be positive (and H * W < 2^31), got ", H, " x ", W);
+    const float* cp = opt_fptr(conf, "conf");
+    if (cp) TORCH_CHECK(conf->dim() >= 2 && conf->size(-2) == H && conf->size(-1) == W && conf->numel() == H * W, "frame_align: conf must be [", H, ",", W, "]");
+    const float* mdp = fptr(m_depth, "m_depth");
+    TORCH_CHECK(m_depth.dim() >= 2, "frame_align: m_depth must be [Hm,Wm] (leading 1s allowed)");
+    const int64_t Hm = m_depth.size(-2), Wm = m_depth.size(-1);
+    TORCH_CHECK(m_depth.numel() == Hm * Wm && Hm > 0 && Wm > 0 && Hm * Wm <= 0x7fffffffLL,
+                "frame_align: m_depth must be [Hm,Wm] with a positive size (and Hm * Wm < 2^31)");
+    const float* mnp = fptr(m_normal, "m_normal");
+    TORCH_CHECK(m_normal.dim() >= 3 && m_normal.size(-3) == Hm && m_normal.size(-2) == Wm && m_normal.size(-1) == 3 && m_normal.numel() == 3 * Hm * Wm,
+                "frame_align: m_normal must be [", Hm, ",", Wm, ",3]");
+    TORCH_CHECK(mats.defined() && mats.device().is_cpu() && mats.scalar_type() == at::kFloat && mats.is_contiguous() && mats.numel() == 36,
+                "frame_align: mats must be a contiguous CPU float32 tensor [3,12] (L, Fm, Bm)");
+    TORCH_CHECK(std::isfinite(dist_max) && (float)dist_max > 0.f && std::isfinite((float)dist_max * (float)dist_max) && (float)dist_max * (float)dist_max > 0.f,
+                "frame_align: dist_max (and its square in fp32) must be positive and finite, got ", dist_max);
+    TORCH_CHECK(std::isfinite(z_near) && z_near >= 0, "frame_align: z_near must be finite and not negative, got ", z_near);
+    TORCH_CHECK(conf_min == conf_min, "frame_align: conf_min must not be NaN");
+    estd_frame_align_desc d{};
+    d.H = (int)H; d.W = (int)W; d.Hm = (int)Hm; d.Wm = (int)Wm;
+    d.dist_max = (float)dist_max; d.z_near = (float)z_near; d.conf_min = (float)conf_min;
+    d.depth = dp; d.conf = cp; d.m_depth = mdp; d.m_normal = mnp;
+    for (int i = 0; i < 36; ++i) {
+        const float m = mats.data_ptr<float>()[i];
+        TORCH_CHECK(std::isfinite(m), "frame_align: mats holds a value that is not finite");
+        (i < 12 ? d.L : i < 24 ? d.Fm : d.Bm)[i % 12] = m;
+    }
+    Tensor residual = new_f32({H, W}, depth), match = at::empty({H, W}, depth.options().dtype(at::kInt));
+    Tensor sums = at::empty({ESTD_FRAME_ALIGN_SUMS}, depth.options().dtype(at::kDouble));
+    Tensor partials = at::empty({estd_frame_align_partials((int)H, (int)W) / 8}, depth.options().dtype(at::kDouble));
+    d.residual = residual.data_ptr<float>(); d.match = match.data_ptr<int>();
+    d.sums = sums.data_ptr<double>(); d.partials = partials.data_ptr<double>();
+    check_status(estd_frame_align(&d, cur_stream()), "estd_frame_align");
+    return {residual, match, sums};
+}
+
 void profile_mark(int64_t id) { check_status(estd_profile_mark((int)id, cur_stream()), "estd_profile_mark"); }
 int64_t conv3d_grid(int64_t N, int64_t D, int64_t H, int64_t W)
 {
@@ -1117,6 +1163,8 @@ TORCH_LIBRARY(estdepth_hip, m)
     m.def("cloud_nearest(Tensor query, Tensor order, Tensor records, Tensor cell_start, Tensor lo, float cell, int[] dims, float max_dist, "
           "bool stats) -> (Tensor, Tensor, Tensor)");
     m.def("cloud_cell_centroids(Tensor points, Tensor attrs, Tensor order, Tensor segments) -> (Tensor, Tensor)");
+    m.def("frame_align(Tensor depth, Tensor? conf, Tensor m_depth, Tensor m_normal, Tensor mats, float dist_max, float z_near, float conf_min) -> "
+          "(Tensor, Tensor, Tensor)");
     m.def("profile_mark(int id) -> ()");
     m.def("set_reserved_cus(int n) -> int");
     m.def("conv3d_grid(int N, int D, int H, int W) -> int");
@@ -1171,6 +1219,7 @@ TORCH_LIBRARY_IMPL(estdepth_hip, CUDA, m)
     m.impl("cloud_cell_keys", cloud_cell_keys);
     m.impl("cloud_nearest", cloud_nearest);
     m.impl("cloud_cell_centroids", cloud_cell_centroids);
+    m.impl("frame_align", frame_align);
 }
 
 TORCH_LIBRARY_IMPL(estdepth_hip, CPU, m)

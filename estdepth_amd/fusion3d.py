@@ -8,6 +8,7 @@
         vol.integrate_outputs(outputs, clip.poses[None], K[None], conf_min=0.3)
     vol.save_ply("scene.ply")
     maps = vol.render(pose, K, (H, W))                              # depth / normal / weight of the fused surface in any camera
+    out = vol.track(depth, pose_guess, K)                           # the guess refined against the fused surface before the frame is fused
 
 Colour: ``TSDFVolume(..., color=True)`` keeps the frames' colour beside the distances -- pass ``imgs=clip.imgs`` to ``integrate_outputs`` (or
 ``images=`` to ``integrate``); ``extract_points`` and ``render`` then return a ``"color"`` entry and ``save_ply`` writes red / green / blue.
@@ -261,6 +262,42 @@ class TSDFVolume:
         if not stacked:
             return dict(zip(names, views[0]))
         return {name: torch.stack([v[j] for v in views]) for j, name in enumerate(names)}
+
+    # ------------------------------------------------------------------------------------------------ frame-to-model tracking
+    def _model_at(self, cam_pose, cam_intr, image_hw, w_min):
+        """the model maps of align_step: the surface as the camera ``cam_pose`` sees it (a colour volume's colour is not used)"""
+        if not isinstance(cam_pose, torch.Tensor) or tuple(cam_pose.shape) != (4, 4):
+            raise RuntimeError("track: cam_pose must be a tensor [4,4], got %s" % (tuple(getattr(cam_pose, "shape", ())),))
+        maps = self.render(cam_pose, cam_intr, image_hw, w_min=w_min)
+        return dict(depth=maps["depth"], normal=maps["normal"], pose=cam_pose, K=cam_intr)
+
+    def track(self, depth, cam_pose, cam_intr, conf=None, conf_min=0.0, dist_max=None, max_iter=10, min_count=100, w_min=1.0):
+        """Refine the camera-to-world guess ``cam_pose`` [4,4] of the depth map ``depth`` [H,W] (``cam_intr`` [3,3], optional ``conf`` gated
+        at ``conf_min``) against the fused surface: the model is rendered ONCE at the guess (``render``), then ``tracking.refine_pose``
+        runs up to ``max_iter`` Gauss-Newton steps of projective point-to-plane alignment, keeping matches within ``dist_max`` metres
+        (default: the truncation distance).  -> its dict: pose (float64 CPU [4,4]; the guess itself where the update was refused),
+        converged, reason, iterations, trace, correction (metres, radians), plus ``matched_share`` = first count / valid depth pixels."""
+        from . import tracking
+        if not isinstance(depth, torch.Tensor) or depth.dim() < 2:
+            raise RuntimeError("track: depth must be a tensor [H,W] (leading 1s allowed), got %s" % (tuple(getattr(depth, "shape", ())),))
+        dist_max = self.trunc if dist_max is None else dist_max
+        model = self._model_at(cam_pose, cam_intr, tuple(depth.shape[-2:]), w_min)
+        out = tracking.refine_pose(depth, cam_intr, cam_pose, model, conf, conf_min, dist_max, max_iter, min_count, self.z_near)
+        out["matched_share"] = out["trace"][0]["count"] / max(int((torch.isfinite(depth) & (depth > self.z_near)).sum().item()), 1)
+        return out
+
+    def check_frame(self, depth, cam_pose, cam_intr, conf=None, conf_min=0.0, dist_max=None, w_min=1.0):
+        """Does the frame sit on the model?  The zero-iteration form of ``track``: the model rendered at ``cam_pose`` and one evaluation of
+        the alignment -> dict(residual [H,W] (the point-to-plane distance in metres, 0 without a match), match int32 [H,W], rmse, count,
+        matched_share = count / valid depth pixels)."""
+        from . import tracking
+        if not isinstance(depth, torch.Tensor) or depth.dim() < 2:
+            raise RuntimeError("check_frame: depth must be a tensor [H,W] (leading 1s allowed), got %s" % (tuple(getattr(depth, "shape", ())),))
+        dist_max = self.trunc if dist_max is None else dist_max
+        model = self._model_at(cam_pose, cam_intr, tuple(depth.shape[-2:]), w_min)
+        s = tracking.align_step(depth, cam_intr, cam_pose, model, conf, conf_min, dist_max, self.z_near)
+        valid = int((torch.isfinite(depth) & (depth > self.z_near)).sum().item())
+        return dict(residual=s["residual"], match=s["match"], rmse=s["rmse"], count=s["count"], matched_share=s["count"] / max(valid, 1))
 
     def fused_voxels(self):
         """voxels some frame has updated"""

@@ -1365,3 +1365,59 @@ def cloud_cell_centroids(points, attrs, order, segments):
                                                       ctypes.c_void_p(segments.data_ptr()), K, _p(out), _p(out_attrs) if C else None, _stream()),
                     "estd_cloud_cell_centroids")
     return out, out_attrs
+
+
+# ---------------------------------------------------------------------------------- frame-to-model alignment (csrc/track/frame_align.hip)
+FRAME_ALIGN_SUMS = 29           # ESTD_FRAME_ALIGN_SUMS (include/estd_hip.h)
+
+
+def frame_align(depth, conf, m_depth, m_normal, mats, dist_max, z_near, conf_min=0.0):
+    """The Gauss-Newton system of the live ``depth`` [H,W] (``conf`` [H,W] or None: pixels below ``conf_min`` are skipped) against the model
+    maps ``m_depth`` [Hm,Wm] / ``m_normal`` [Hm,Wm,3] with the host matrices ``mats`` (CPU float32 [3,12]: L, Fm, Bm of
+    camera.frame_align_matrices) -> (residual [H,W], match int32 [H,W], sums float64 [29]) on the depth's device: the point-to-plane
+    residual and the model pixel of every matched pixel (0 / -1 elsewhere), the 21 upper entries of sum J J^T, the 6 of sum J r, sum r^2
+    and the match count.  The contract is spelled out in include/estd_hip.h (estd_frame_align)."""
+    dist_max, z_near, conf_min = float(dist_max), float(z_near), float(conf_min)
+    if _use_torch():
+        return tuple(T().frame_align(depth, conf, m_depth, m_normal, mats, dist_max, z_near, conf_min))
+    _chk(depth, "depth")
+    _need(depth.dim() >= 2 and depth.numel() == depth.shape[-2] * depth.shape[-1], "frame_align: depth must be [H,W] (leading 1s allowed)")
+    H, W = depth.shape[-2:]
+    _need(H > 0 and W > 0 and H * W <= 0x7fffffff, "frame_align: the map size must be positive (and H * W < 2^31), got %d x %d" % (H, W))
+    if conf is not None:
+        _chk(conf, "conf")
+        _need(conf.dim() >= 2 and tuple(conf.shape[-2:]) == (H, W) and conf.numel() == H * W, "frame_align: conf must be [%d,%d], got %s" % (H, W, tuple(conf.shape)))
+    _chk(m_depth, "m_depth")
+    _need(m_depth.dim() >= 2 and m_depth.numel() == m_depth.shape[-2] * m_depth.shape[-1], "frame_align: m_depth must be [Hm,Wm] (leading 1s allowed)")
+    Hm, Wm = m_depth.shape[-2:]
+    _need(Hm > 0 and Wm > 0 and Hm * Wm <= 0x7fffffff, "frame_align: m_depth must have a positive size (and Hm * Wm < 2^31), got %d x %d" % (Hm, Wm))
+    _chk(m_normal, "m_normal")
+    _need(m_normal.dim() >= 3 and tuple(m_normal.shape[-3:]) == (Hm, Wm, 3) and m_normal.numel() == 3 * Hm * Wm,
+          "frame_align: m_normal must be [%d,%d,3], got %s" % (Hm, Wm, tuple(m_normal.shape)))
+    for t, name in ((conf, "conf"), (m_depth, "m_depth"), (m_normal, "m_normal")):
+        _need(t is None or t.device == depth.device, "frame_align: %s is on %s but the depth on %s" % (name, getattr(t, "device", None), depth.device))
+    _need(isinstance(mats, torch.Tensor) and not mats.is_cuda and mats.dtype == torch.float32 and mats.is_contiguous() and mats.numel() == 36,
+          "frame_align: mats must be a contiguous CPU float32 tensor [3,12] (L, Fm, Bm)")
+    d32 = ctypes.c_float(dist_max).value if math.isfinite(dist_max) else dist_max
+    d2 = ctypes.c_float(d32 * d32).value if math.isfinite(d32) else d32
+    _need(math.isfinite(dist_max) and d32 > 0 and math.isfinite(d2) and d2 > 0,
+          "frame_align: dist_max (and its square in fp32) must be positive and finite, got %r" % dist_max)
+    _need(math.isfinite(z_near) and z_near >= 0, "frame_align: z_near must be finite and not negative, got %r" % z_near)
+    _need(conf_min == conf_min, "frame_align: conf_min must not be NaN")
+    flat = mats.reshape(-1).tolist()
+    _need(all(math.isfinite(v) for v in flat), "frame_align: mats holds a value that is not finite")
+    dev = depth.device
+    with torch.cuda.device(dev):
+        residual, match = torch.empty((H, W), device=dev), torch.empty((H, W), device=dev, dtype=torch.int32)
+        sums = torch.empty((FRAME_ALIGN_SUMS,), device=dev, dtype=torch.float64)
+        partials = torch.empty((N.lib().estd_frame_align_partials(H, W) // 8,), device=dev, dtype=torch.float64)
+        d = N.FrameAlignDesc()
+        d.H, d.W, d.Hm, d.Wm = H, W, Hm, Wm
+        d.dist_max, d.z_near, d.conf_min = dist_max, z_near, conf_min
+        d.depth, d.conf = depth.data_ptr(), conf.data_ptr() if conf is not None else None
+        d.m_depth, d.m_normal = m_depth.data_ptr(), m_normal.data_ptr()
+        d.residual, d.match, d.sums, d.partials = residual.data_ptr(), match.data_ptr(), sums.data_ptr(), partials.data_ptr()
+        for i in range(12):
+            d.L[i], d.Fm[i], d.Bm[i] = flat[i], flat[12 + i], flat[24 + i]
+        N.check(N.lib().estd_frame_align(ctypes.byref(d), _stream()), "estd_frame_align")
+    return residual, match, sums

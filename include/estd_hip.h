@@ -673,6 +673,61 @@ int estd_cloud_nearest(const estd_cloud_nearest_desc* desc, estd_stream_t stream
 int estd_cloud_cell_centroids(const float* points, const float* attrs, int C, long long n, const long long* order,
                               const long long* segments, long long K, float* out_points, float* out_attrs, estd_stream_t stream);
 
+/* ---- frame-to-model alignment of a depth map (csrc/track/frame_align.hip) -------------------------
+ * Projective point-to-plane alignment, KinectFusion's tracking step: ONE live depth map against ONE set of model maps, the depth and
+ * normal maps estd_tsdf_raycast writes (normals in world axes towards the cameras, no hit = zeros).  One call forms the Gauss-Newton
+ * system of the frame at the pose guess and the per-pixel picture "does this frame sit on the model".  All maps are fp32, pixel centres
+ * on integers, z-depth along the optical axis: the conventions of estd_tsdf_integrate and estd_tsdf_raycast.
+ *
+ * Three HOST 3x4 row-major fp32 matrices (estdepth_amd/camera.py frame_align_matrices forms them in float64; poses are camera-to-world,
+ * R_g, c_g of the guess, R_m, c_m of the model camera):
+ *   L  = [ R_g K^-1 | c_g ]            (live pixel) x depth -> world;
+ *   Fm = K_m [R|t]_world->model        world -> (model pixel) x depth;
+ *   Bm = [ R_m K_m^-1 | c_m ]          (model pixel) x depth -> world.
+ * With row(M, j; x, y, z) = fma(z, fma(M[j][0], x, fma(M[j][1], y, M[j][2])), M[j][3]), per live pixel (u, v):
+ *   1. d = depth[v][u]; the pixel is SKIPPED unless d is finite, d > z_near and conf is NULL or conf[v][u] >= conf_min;
+ *   2. p_j = row(L, j; u, v, d), j = x, y, z;
+ *   3. a, b, c = fma(Fm[j][0], p_x, fma(Fm[j][1], p_y, fma(Fm[j][2], p_z, Fm[j][3]))), j = 0, 1, 2; skipped unless c > z_near;
+ *   4. um = floor(a / c + 0.5), vm = floor(b / c + 0.5); skipped unless 0 <= um < Wm and 0 <= vm < Hm (false for a NaN);
+ *   5. dm = m_depth[vm][um]; skipped unless dm > 0; n = m_normal[vm][um]; q_j = row(Bm, j; um, vm, dm);
+ *   6. e = q - p; skipped unless fma(e_x, e_x, fma(e_y, e_y, e_z e_z)) <= dist_max^2 (dist_max * dist_max, formed once on the host in
+ *      fp32; false for a NaN, so a model depth that is not finite skips the pixel);
+ *   7. r = fma(n_x, e_x, fma(n_y, e_y, n_z e_z));  J = (n_x, n_y, n_z, w_x, w_y, w_z) with w = p x n:
+ *        w_x = fma(p_y, n_z, -(p_z n_y)),  w_y = fma(p_z, n_x, -(p_x n_z)),  w_z = fma(p_x, n_y, -(p_y n_x)).
+ *      r ~ n . (q - Exp(xi) p) linearised: the system belongs to the LEFT update P <- Exp(xi) P of the guess with xi = (t, omega) in world
+ *      axes, and the Gauss-Newton step solves (sum J J^T) xi = sum J r.
+ * Per-pixel outputs, every pixel written by every call with plain vector stores:
+ *   residual [H][W] = r, or 0 where the pixel was skipped;   match [H][W] (int32) = vm Wm + um, or -1 where it was skipped.
+ * sums: ESTD_FRAME_ALIGN_SUMS = 29 float64 values on the device,
+ *   [0..20]  the upper triangle of sum J J^T, row by row: (0,0) (0,1) .. (0,5) (1,1) .. (1,5) (2,2) .. (5,5);
+ *   [21..26] sum J_i r;   [27] sum r^2;   [28] the number of matched pixels.
+ * Each per-pixel term is ONE fp32 value (J_i * J_j, J_i * r, r * r, 1: a product rounded once), widened and added in float64.  No
+ * atomics; the order is fixed: the lanes of a wave (an exclusive-or butterfly over lane distances 32 .. 1), the four waves of a 16 x 16
+ * pixel workgroup in wave order, then the workgroups: lane l of the reduction adds workgroups l, l + 64, ... in ascending order and the
+ * same butterfly joins the lanes.  The 29 values are bit-identical across calls.
+ * partials: device scratch of estd_frame_align_partials(H, W) BYTES (29 float64 per 16 x 16 tile of the live map), owned by the caller;
+ * the function returns 0 for sizes the entry point refuses.
+ * ESTD_ERR_ARG (before any launch, no device needed): a null descriptor or pointer (conf excepted), a size <= 0, dist_max or its square
+ * not a positive finite fp32, z_near negative or not finite, conf_min NaN with a conf map, a matrix element not finite.
+ * ESTD_ERR_UNSUPPORTED: H * W or Hm * Wm >= 2^31. */
+#define ESTD_FRAME_ALIGN_SUMS 29
+typedef struct estd_frame_align_desc {
+    int H, W;                                     /* size of the live maps */
+    int Hm, Wm;                                   /* size of the model maps */
+    float dist_max, z_near, conf_min;
+    const float* depth;                           /* [H][W] */
+    const float* conf;                            /* [H][W] or NULL */
+    const float* m_depth;                         /* [Hm][Wm] */
+    const float* m_normal;                        /* [Hm][Wm][3] */
+    float* residual;                              /* [H][W] */
+    int* match;                                   /* [H][W] */
+    double* sums;                                 /* [ESTD_FRAME_ALIGN_SUMS] */
+    double* partials;                             /* estd_frame_align_partials(H, W) bytes */
+    float L[12], Fm[12], Bm[12];                  /* host values, copied into the launch arguments */
+} estd_frame_align_desc;
+long long estd_frame_align_partials(int H, int W);
+int estd_frame_align(const estd_frame_align_desc* desc, estd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,11 @@ ground-truth depth.  Needs an MI355X (the model has no CPU path).
         # + the 3D scores of the fused scene (estdepth_amd.cloud_metrics): the ground-truth depth maps of the same targets are fused into a
         # second volume of the same geometry and the two surfaces compared -- accuracy, completeness, chamfer, precision / recall / F-score;
         # --score-3d GT.ply compares against that cloud instead; metrics.json gains recon_3d
+    python tools/run_stream.py --synthetic 8 --out /tmp/eval --fuse /tmp/eval/scene.ply --track
+        # + frame-to-model tracking (estdepth_amd.tracking): from the second fused target on, every target's pose is refined against the
+        # volume (TSDFVolume.track: point-to-plane alignment of its depth map with the ray-cast model) before the target is fused -- the
+        # filtered record too under --geo-filter; metrics.json gains tracking: per frame the correction, the rmse before and after, the
+        # matched share and whether the refinement converged
 """
 import argparse
 import json
@@ -68,6 +73,11 @@ def main():
     ap.add_argument("--score-threshold", type=float, default=0.05, help="with --score-3d: the precision / recall / F-score threshold in metres")
     ap.add_argument("--score-max-dist", type=float, default=None, help="with --score-3d: distances are clamped here (default: 20 thresholds)")
     ap.add_argument("--score-downsample", type=float, default=None, help="with --score-3d: voxel-grid down-sampling of both clouds first (metres)")
+    ap.add_argument("--track", action="store_true", help="with --fuse: refine every target's pose against the fused volume before the target is "
+                    "fused (TSDFVolume.track), from the second fused target on")
+    ap.add_argument("--track-dist", type=float, default=None, metavar="D", help="with --track: matches farther than D metres from the model are "
+                    "left out (default: the volume's truncation distance)")
+    ap.add_argument("--track-iters", type=int, default=10, metavar="N", help="with --track: Gauss-Newton iterations per target at most")
     ap.add_argument("--voxel-size", type=float, default=0.04)
     ap.add_argument("--volume-dims", type=int, nargs=3, default=(256, 256, 256), metavar=("Z", "Y", "X"))
     args = ap.parse_args()
@@ -77,6 +87,8 @@ def main():
         ap.error("--color needs --fuse PATH.ply")
     if args.score_3d is not None and not args.fuse:
         ap.error("--score-3d needs --fuse PATH.ply")
+    if args.track and not args.fuse:
+        ap.error("--track needs --fuse PATH.ply")
 
     from estdepth_amd import DepthNetHybrid, synth
     from estdepth_amd.streaming import ESTMStream
@@ -122,8 +134,29 @@ def main():
         from estdepth_amd.metrics import compute_valid_depth_mask as valid_depth
         geo = ConsistencyWindow(radius=args.geo_filter, min_views=args.geo_min_views, px_max=args.geo_px, rel_max=args.geo_rel)
 
+    tracked, track_ms = [], []
+
+    def refined_pose(name, dmap, pose, intr):
+        """--track: the pose to fuse a target at -- its own until something is fused, then the one TSDFVolume.track finds against the volume"""
+        pose = pose.detach().reshape(4, 4).to("cpu", torch.float64)
+        if volume.frames == 0:
+            return pose
+        torch.cuda.synchronize()
+        t0 = time.time()
+        out = volume.track(dmap, pose, intr, dist_max=args.track_dist, max_iter=args.track_iters)
+        after = volume.check_frame(dmap, out["pose"], intr, dist_max=args.track_dist)
+        torch.cuda.synchronize()
+        track_ms.append(1e3 * (time.time() - t0))
+        tracked.append({"frame": os.path.basename(str(name)), "correction_m": out["correction"][0], "correction_rad": out["correction"][1],
+                        "rmse_before": out["trace"][0]["rmse"], "rmse_after": after["rmse"], "matched_share": out["matched_share"],
+                        "converged": out["converged"], "reason": out["reason"], "iterations": out["iterations"]})
+        return out["pose"]
+
     def take_filtered(rec):
         """a target the consistency window hands back: fuse it (--fuse) and score its averaged depth on the kept pixels"""
+        if volume is not None and args.track:                                # the filtered record is refined on the pixels that will be fused
+            kept_dev = torch.where(rec["views"] >= float(args.geo_min_views), rec["depth"], torch.zeros_like(rec["depth"]))
+            rec = dict(rec, pose=refined_pose(rec["extra"]["name"], kept_dev, rec["pose"], rec["K"]))
         if volume is not None:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -177,9 +210,16 @@ def main():
                 volume_gt.integrate(gt_map[None], target["cam_pose"].reshape(1, 4, 4), intr_gt)
         if args.fuse and geo is None:
             frames_rgb = torch.stack([f["img"][0] for f in window])[None].to(dev) if args.color else None
+            window_poses = torch.stack([f["cam_pose"].reshape(4, 4) for f in window])[None]
+            if args.track:
+                dmap, intr, image_hw = outputs[("depth", 0, 0)][0, 0], s["cam_intr"].reshape(3, 3).clone(), tuple(s["img"].shape[-2:])
+                if tuple(dmap.shape) != image_hw:                            # as TSDFVolume.integrate_outputs: the intrinsics of the maps' size
+                    intr[0:2] = intr[0:2] * (dmap.shape[0] / float(image_hw[0]))
+                window_poses = window_poses.detach().to("cpu", torch.float64).clone()
+                window_poses[0, args.lwindow // 2] = refined_pose(target["img_path"], dmap, target["cam_pose"], intr)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            volume.integrate_outputs(outputs, torch.stack([f["cam_pose"].reshape(4, 4) for f in window])[None], s["cam_intr"].reshape(1, 3, 3),
+            volume.integrate_outputs(outputs, window_poses, s["cam_intr"].reshape(1, 3, 3),
                                      image_hw=tuple(s["img"].shape[-2:]), imgs=frames_rgb)
             e1.record()
             torch.cuda.synchronize()
@@ -200,7 +240,7 @@ def main():
             if tuple(dmap.shape) != image_hw:                                # as TSDFVolume.integrate_outputs: the intrinsics of the maps' size
                 intr[0:2] = intr[0:2] * (dmap.shape[0] / float(image_hw[0]))
             rgb = target["img"][0].to(dev) if args.color else None           # the colour frame travels with its depth
-            rec = geo.push(dmap, target["cam_pose"].reshape(4, 4), intr, extra={"rgb": rgb, "gt": gt})
+            rec = geo.push(dmap, target["cam_pose"].reshape(4, 4), intr, extra={"rgb": rgb, "gt": gt, "name": target["img_path"]})
             if rec is not None:
                 take_filtered(rec)
         if args.render_fused:
@@ -217,6 +257,9 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(args.fuse)), exist_ok=True)
         report.update(fused_voxels=volume.fused_voxels(), points=volume.save_ply(args.fuse),
                       mean_fuse_ms=float(np.mean(fuse_ms[1:] or fuse_ms)))
+    if args.track and volume is not None:
+        report["tracking"] = {"frames": tracked, "dist_max": args.track_dist if args.track_dist is not None else volume.trunc,
+                              "max_iter": args.track_iters, "mean_track_ms": float(np.mean(track_ms[1:] or track_ms or [0.0]))}
     if volume is not None and args.score_3d is not None:
         from estdepth_amd.fusion3d import read_ply
         if volume_gt is not None:

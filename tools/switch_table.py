@@ -94,7 +94,8 @@ def scan():
             for m in re.finditer(r"\"(ESTD_[A-Z0-9_]+)\" in os\.environ|ESTD_[A-Z0-9_]+=", line):
                 if m.group(1):
                     env.setdefault(m.group(1), ["", []])[1].append("%s:%d" % (os.path.relpath(f, ROOT), n))
-    for f in sorted(glob.glob(os.path.join(ROOT, "estdepth_amd", "csrc", "*"))):
+    csrc = os.path.join(ROOT, "estdepth_amd", "csrc")
+    for f in sorted(f for f in glob.glob(os.path.join(csrc, "*")) + glob.glob(os.path.join(csrc, "*", "*")) if os.path.isfile(f)):
         for n, line in enumerate(open(f, errors="replace"), 1):
             m = re.search(r"getenv\(\"(ESTD_[A-Z0-9_]+)\"\)", line)
             if m:
