@@ -326,6 +326,9 @@ class TSDFVolume:
 
         def side(x):
             pts = x.extract_points(w_min=w_min) if isinstance(x, TSDFVolume) else x
+            if isinstance(x, TSDFVolume):                      # records come back in no fixed order: sorted by edge, so that which of two equally
+                order = torch.argsort(pts["edge"])             # near neighbours is the nearest (its normal, its colour) does not change from run to run
+                pts = {k: v[order] for k, v in pts.items() if isinstance(v, torch.Tensor)}
             if not isinstance(pts, dict) or pts.get("xyz") is None:
                 raise RuntimeError("compare: the other side must be a TSDFVolume or a dict with 'xyz'")
             out = {}

@@ -26,6 +26,13 @@ ground-truth depth.  Needs an MI355X (the model has no CPU path).
         # volume (TSDFVolume.track: point-to-plane alignment of its depth map with the ray-cast model) before the target is fused -- the
         # filtered record too under --geo-filter; metrics.json gains tracking: per frame the correction, the rmse before and after, the
         # matched share and whether the refinement converged
+    python tools/run_stream.py --scene-dir SCENE --frame-interval 1 --out /tmp/eval --depth-source gt --fuse /tmp/eval/scene.ply
+        # the chain WITHOUT the network: no model is built; a stand-in with ESTMStream.push's contract (GroundTruthStream) hands every
+        # target's ground-truth depth, brought to --image-size by nearest neighbour on pixel centres, with confidence 1 where it is valid,
+        # to everything behind the stream.  For checking a scene's poses and intrinsics and the reconstruction chain (fusion, filter,
+        # tracking, rendering, 3D scores) on their own: with true depths every error left is the scene's or the chain's, not the model's
+
+parse(argv) and run(args) -> (report, state) drive the tool from a program (tests/test_gpu_run_stream.py); main() is parse + run + metrics.json.
 """
 import argparse
 import json
@@ -40,7 +47,47 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def main():
+def nearest_index(n_out, n_in):
+    """nearest neighbour on pixel centres: the index in a row of ``n_in`` samples under each of ``n_out`` (the identity at n_out == n_in)"""
+    return np.minimum(((np.arange(n_out) + 0.5) * n_in / n_out).astype(np.int64), n_in - 1)
+
+
+def to_gt_grid(a, shape):
+    """nearest neighbour on pixel centres: a map at the network's resolution on the ground truth's pixel grid (no new depth values)"""
+    return a[nearest_index(shape[0], a.shape[0])][:, nearest_index(shape[1], a.shape[1])]
+
+
+class GroundTruthStream:
+    """--depth-source gt: ESTMStream.push's contract without a network.  None until ``lwindow`` frames are in, then per push the output
+    dict of one target -- the window's frame ``lwindow // 2`` -- whose depths are that frame's ground-truth map on the ``image_hw`` grid
+    (nearest neighbour on pixel centres, the identity at the native size) and whose confidences are 1 where that depth is valid, else 0.
+    Works on whatever device the maps are on."""
+
+    def __init__(self, lwindow=3, image_hw=None):
+        if lwindow < 3:
+            raise RuntimeError("a window needs at least 3 frames (model_hybrid.py:123)")
+        self.lwindow, self.image_hw = lwindow, image_hw
+        self._dmaps, self.windows = [], 0
+
+    def push(self, img, cam_pose, cam_intr, dmap=None, dmask=None):
+        if dmap is None:
+            raise RuntimeError("GroundTruthStream.push: every frame needs its ground-truth depth map")
+        self._dmaps = (self._dmaps + [dmap.reshape(dmap.shape[-2:])])[-self.lwindow:]
+        if len(self._dmaps) < self.lwindow:
+            return None
+        gt = self._dmaps[self.lwindow // 2]
+        h, w = self.image_hw if self.image_hw is not None else tuple(img.shape[-2:])
+        ys = torch.from_numpy(nearest_index(h, gt.shape[0])).to(gt.device)
+        xs = torch.from_numpy(nearest_index(w, gt.shape[1])).to(gt.device)
+        depth = gt[ys][:, xs].to(torch.float32)
+        depth = torch.where(torch.isfinite(depth) & (depth > 0), depth, torch.zeros_like(depth))[None, None].contiguous()
+        conf = (depth > 0).to(torch.float32)
+        self.windows += 1
+        outputs = {("depth", 0, 0): depth, ("depth", 0, 2): depth.clone(), ("fused_prob", 0): conf, ("init_prob", 0): conf.clone()}
+        return outputs, None, None
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--scene-dir")
     ap.add_argument("--synthetic", type=int, default=0, help="generate a scene of this many frames instead")
@@ -80,7 +127,10 @@ def main():
     ap.add_argument("--track-iters", type=int, default=10, metavar="N", help="with --track: Gauss-Newton iterations per target at most")
     ap.add_argument("--voxel-size", type=float, default=0.04)
     ap.add_argument("--volume-dims", type=int, nargs=3, default=(256, 256, 256), metavar=("Z", "Y", "X"))
-    args = ap.parse_args()
+    ap.add_argument("--depth-source", choices=("net", "gt"), default="net", help="gt: no network is built; every target's depth is its own "
+                    "ground-truth map at --image-size (nearest neighbour) with confidence 1 where valid -- checks a scene's poses and "
+                    "intrinsics and the reconstruction chain without the model")
+    args = ap.parse_args(argv)
     if args.render_fused and not args.fuse:
         ap.error("--render-fused needs --fuse PATH.ply")
     if args.color and not args.fuse:
@@ -89,7 +139,15 @@ def main():
         ap.error("--score-3d needs --fuse PATH.ply")
     if args.track and not args.fuse:
         ap.error("--track needs --fuse PATH.ply")
+    if not args.scene_dir and not args.synthetic:
+        ap.error("--scene-dir or --synthetic is required")
+    return args
 
+
+def run(args):
+    """the whole evaluation -> (report, state): what main() writes to metrics.json, and the live objects behind it -- state.volume,
+    state.volume_gt, state.geo (None without their flags), state.fused = [(frame name, the float64 pose the target was fused at)] in
+    fusion order, state.targets (--render-fused: name, pose, intrinsics, size, prediction and ground truth of every target)"""
     from estdepth_amd import DepthNetHybrid, synth
     from estdepth_amd.streaming import ESTMStream
     from estdepth_amd.eval_io import SequenceReader, save_window_outputs, write_synthetic_scene
@@ -105,26 +163,28 @@ def main():
         dmaps = [sample["dmaps"][0, i, 0].numpy() for i in range(args.synthetic)]
         write_synthetic_scene(scene_dir, imgs, dmaps, [poses[0, i].numpy() for i in range(args.synthetic)])
         interval = 1
-    if not scene_dir:
-        ap.error("--scene-dir or --synthetic is required")
 
     dev = torch.device("cuda:0")
-    model = DepthNetHybrid(ndepths=args.ndepths, depth_min=args.depth_min, depth_max=args.depth_max,
-                           resnet=args.resnet, IF_EST_transformer=True)
-    if args.loadckpt:
-        sd = torch.load(args.loadckpt, map_location="cpu")
-        model.load_state_dict(sd.get("model", sd))
-    else:
-        synth.fill_state_dict(model, seed=2, head_gain=1.0)
-    model = model.to(dev).eval()
-    model.use_channels_last_2d()
-    model.use_hip_psm()
+    if args.depth_source == "net":
+        model = DepthNetHybrid(ndepths=args.ndepths, depth_min=args.depth_min, depth_max=args.depth_max,
+                               resnet=args.resnet, IF_EST_transformer=True)
+        if args.loadckpt:
+            sd = torch.load(args.loadckpt, map_location="cpu")
+            model.load_state_dict(sd.get("model", sd))
+        else:
+            synth.fill_state_dict(model, seed=2, head_gain=1.0)
+        model = model.to(dev).eval()
+        model.use_channels_last_2d()
+        model.use_hip_psm()
 
     reader = SequenceReader(scene_dir, image_size=tuple(args.image_size), depth_min=args.depth_min,
                             depth_max=args.depth_max, frame_interval=interval,
                             scannet_layout=args.layout == "scannet")
-    stream = ESTMStream(model, lwindow=args.lwindow, memory_size=args.memory_size,
-                        cache_features=not args.no_feature_cache)
+    if args.depth_source == "net":
+        stream = ESTMStream(model, lwindow=args.lwindow, memory_size=args.memory_size,
+                            cache_features=not args.no_feature_cache)
+    else:
+        stream = GroundTruthStream(lwindow=args.lwindow, image_hw=(args.image_size[1], args.image_size[0]))
     errs, times, window, resized = RunningErrors(), [], [], 0
     volume, fuse_ms, targets = None, [], []
     volume_gt = None                                                         # --score-3d without a path: the ground-truth depth maps, fused
@@ -134,7 +194,7 @@ def main():
         from estdepth_amd.metrics import compute_valid_depth_mask as valid_depth
         geo = ConsistencyWindow(radius=args.geo_filter, min_views=args.geo_min_views, px_max=args.geo_px, rel_max=args.geo_rel)
 
-    tracked, track_ms = [], []
+    tracked, track_ms, fused_at = [], [], []
 
     def refined_pose(name, dmap, pose, intr):
         """--track: the pose to fuse a target at -- its own until something is fused, then the one TSDFVolume.track finds against the volume"""
@@ -161,6 +221,7 @@ def main():
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             volume.integrate_filtered(dict(rec, extra=rec["extra"]["rgb"]))
+            fused_at.append((rec["extra"]["name"], rec["pose"].detach().reshape(4, 4).to("cpu", torch.float64).clone()))
             e1.record()
             torch.cuda.synchronize()
             fuse_ms.append(e0.elapsed_time(e1))
@@ -173,11 +234,6 @@ def main():
         geo_count["gt"] += int(gt_ok.sum())
         geo_count["kept"] += int((gt_ok & (kept > 0)).sum())
 
-    def to_gt_grid(a, shape):
-        """nearest neighbour on pixel centres: a map at the network's resolution on the ground truth's pixel grid (no new depth values)"""
-        ys = np.minimum(((np.arange(shape[0]) + 0.5) * a.shape[0] / shape[0]).astype(np.int64), a.shape[0] - 1)
-        xs = np.minimum(((np.arange(shape[1]) + 0.5) * a.shape[1] / shape[1]).astype(np.int64), a.shape[1] - 1)
-        return a[ys][:, xs]
     for idx in range(len(reader)):
         s = reader[idx]
         window.append(s)
@@ -224,6 +280,7 @@ def main():
             e1.record()
             torch.cuda.synchronize()
             fuse_ms.append(e0.elapsed_time(e1))
+            fused_at.append((target["img_path"], window_poses[0, args.lwindow // 2].detach().to("cpu", torch.float64).clone()))
         save_window_outputs(outputs, args.out, target["img_path"])
         pred = outputs[("depth", 0, 0)][0, 0].cpu().numpy().astype(np.float64)
         gt = target["dmap"][0, 0].numpy().astype(np.float64)
@@ -306,6 +363,12 @@ def main():
             errs_covered.add(np.where(both, pred, 0.0), gt)
         report.update(errors_fused=errs_fused.mean(), fused_coverage=n_covered / max(n_gt, 1), errors_on_covered=errs_covered.mean(),
                       mean_render_ms=float(np.mean(render_ms[1:] or render_ms or [0.0])))
+    return report, argparse.Namespace(volume=volume, volume_gt=volume_gt, geo=geo, fused=fused_at, targets=targets)
+
+
+def main():
+    args = parse()
+    report, _ = run(args)
     os.makedirs(args.out, exist_ok=True)
     with open(os.path.join(args.out, "metrics.json"), "w") as f:
         json.dump(report, f, indent=1)
