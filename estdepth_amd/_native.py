@@ -73,6 +73,10 @@ class Conv2dTapsDesc(ctypes.Structure):
     ]
 
 
+TSDF_MAX_FRAMES = 8             # ESTD_TSDF_MAX_FRAMES (include/estd_hip.h): the array fields below and the check in ops.py
+CONSISTENCY_MAX_SOURCES = 8     # ESTD_CONSISTENCY_MAX_SOURCES
+
+
 class TsdfIntegrateDesc(ctypes.Structure):
     """Mirror of struct estd_tsdf_integrate_desc (include/estd_hip.h)."""
     _fields_ = [
@@ -80,13 +84,13 @@ class TsdfIntegrateDesc(ctypes.Structure):
         ("weighted", ctypes.c_int), ("no_skip", ctypes.c_int),
         ("trunc", ctypes.c_float), ("z_near", ctypes.c_float), ("conf_min", ctypes.c_float), ("w_max", ctypes.c_float),
         ("tsdf", ctypes.c_void_p), ("weight", ctypes.c_void_p),
-        ("depth", ctypes.c_void_p * 8), ("conf", ctypes.c_void_p * 8), ("mats", (ctypes.c_float * 12) * 8),
+        ("depth", ctypes.c_void_p * TSDF_MAX_FRAMES), ("conf", ctypes.c_void_p * TSDF_MAX_FRAMES), ("mats", (ctypes.c_float * 12) * TSDF_MAX_FRAMES),
     ]
 
 
 class TsdfIntegrateColorDesc(ctypes.Structure):
     """Mirror of struct estd_tsdf_integrate_color_desc (include/estd_hip.h)."""
-    _fields_ = TsdfIntegrateDesc._fields_ + [("color", ctypes.c_void_p), ("image", ctypes.c_void_p * 8)]
+    _fields_ = TsdfIntegrateDesc._fields_ + [("color", ctypes.c_void_p), ("image", ctypes.c_void_p * TSDF_MAX_FRAMES)]
 
 
 class TsdfRaycastDesc(ctypes.Structure):
@@ -110,9 +114,9 @@ class DepthConsistencyDesc(ctypes.Structure):
     _fields_ = [
         ("H", ctypes.c_int), ("W", ctypes.c_int), ("S", ctypes.c_int),
         ("px_max", ctypes.c_float), ("rel_max", ctypes.c_float), ("z_near", ctypes.c_float),
-        ("target", ctypes.c_void_p), ("source", ctypes.c_void_p * 8),
+        ("target", ctypes.c_void_p), ("source", ctypes.c_void_p * CONSISTENCY_MAX_SOURCES),
         ("views", ctypes.c_void_p), ("visible", ctypes.c_void_p), ("depth", ctypes.c_void_p), ("rel_err", ctypes.c_void_p),
-        ("mats", ((ctypes.c_float * 12) * 2) * 8),
+        ("mats", ((ctypes.c_float * 12) * 2) * CONSISTENCY_MAX_SOURCES),
     ]
 
 

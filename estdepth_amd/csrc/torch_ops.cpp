@@ -18,6 +18,7 @@
 #include <torch/library.h>
 
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 #include "estd_hip.h"
@@ -339,42 +340,146 @@ Tensor warp_volume_ex(const Tensor& vol, const Tensor& mats30, const Tensor& dep
     return out;
 }
 
+// ------------------------------------------------------------------------------------------------ reconstruction operators: argument checks
+// One helper per kind of check for the operators below (estdepth_amd/ops.py has the same set for the ctypes binding); each takes the
+// operator's and the argument's name for its message.
+
+// the volume argument: two float32 planes (0 = D, 1 = Wt), contiguous, on the operator's device, X % 4 == 0
+struct VolumeArg { int64_t Z, Y, X; float* tsdf; float* weight; };
+static VolumeArg check_volume(const Tensor& volume, const char* op)
+{
+    TORCH_CHECK(volume.dim() == 4 && volume.size(0) == 2, op, ": volume must be [2,Z,Y,X] (D plane, weight plane)");
+    float* vol = fptr_mut(volume, "volume");
+    const int64_t Z = volume.size(1), Y = volume.size(2), X = volume.size(3);
+    TORCH_CHECK(X % 4 == 0, op, ": X must be a multiple of 4, got ", X);
+    return {Z, Y, X, vol, vol + Z * Y * X};
+}
+
+static float* check_color_planes(const Tensor& color, const Tensor& volume, const char* op)
+{
+    TORCH_CHECK(color.dim() == 4 && color.size(0) == 3 && color.size(1) == volume.size(1) && color.size(2) == volume.size(2) &&
+                color.size(3) == volume.size(3), op, ": color must be [3,Z,Y,X] with the volume's Z, Y, X");
+    TORCH_CHECK(color.device() == volume.device(), op, ": color and the volume are on different devices");
+    return fptr_mut(color, "color");
+}
+
+// host values of the launch arguments: exactly n of them (finite: none NaN or infinite)
+static const float* host_values(const Tensor& t, int64_t n, const char* op, const char* name, const char* shape, bool finite = false)
+{
+    TORCH_CHECK(t.defined() && t.device().is_cpu() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.numel() == n,
+                op, ": ", name, " must be a contiguous CPU float32 tensor ", shape);
+    const float* v = t.data_ptr<float>();
+    for (int64_t i = 0; finite && i < n; ++i) TORCH_CHECK(std::isfinite(v[i]), op, ": ", name, " holds a value that is not finite");
+    return v;
+}
+
+// a float32 map on the operator's device whose last sizes are `tail` (-1: any size), leading 1s allowed
+static const float* map_ptr(const Tensor& t, at::IntArrayRef tail, const char* op, const char* name)
+{
+    const float* p = fptr(t, name);
+    const int64_t k = (int64_t)tail.size();
+    bool ok = t.dim() >= k;
+    int64_t n = 1;
+    for (int64_t i = 0; ok && i < k; ++i) {
+        const int64_t s = t.size(t.dim() - k + i);
+        ok = tail[i] < 0 || tail[i] == s;
+        n *= s;
+    }
+    TORCH_CHECK(ok && t.numel() == n, op, ": ", name, " must end in the sizes ", tail, " (-1: any; leading 1s allowed), got ", t.sizes());
+    return p;
+}
+
+static void check_map_size(int64_t H, int64_t W, const char* op, const char* name, int64_t least = 1)
+{
+    TORCH_CHECK(H >= least && W >= least && H * W <= 0x7fffffffLL, op, ": ", name, " must be at least ", least, " x ", least,
+                " (and H * W < 2^31), got ", H, " x ", W);
+}
+
+// a contiguous integer vector (int64 unless I says otherwise) on `like`'s device, of `size` elements (< 0: any number)
+template <class I = int64_t>
+static const I* lptr(const Tensor& t, const char* op, const char* name, const Tensor& like, int64_t size)
+{
+    TORCH_CHECK(t.defined() && t.dim() == 1 && t.scalar_type() == c10::CppTypeToScalarType<I>::value && t.is_contiguous() &&
+                t.device() == like.device() && (size < 0 || t.size(0) == size), op, ": ", name, " must be a contiguous ",
+                c10::CppTypeToScalarType<I>::value, " vector of the right length on the operator's device");
+    return t.data_ptr<I>();
+}
+
+// the four rules for a scalar that a kernel takes as fp32 -> the fp32 value
+static float positive_f32(double v, const char* op, const char* name)
+{
+    TORCH_CHECK(std::isfinite(v) && (float)v > 0.f, op, ": ", name, " must be positive and finite, got ", v);
+    return (float)v;
+}
+static float not_negative_f32(double v, const char* op, const char* name)
+{
+    TORCH_CHECK(std::isfinite(v) && v >= 0, op, ": ", name, " must be finite and not negative, got ", v);
+    return (float)v;
+}
+static float not_nan_f32(double v, const char* op, const char* name)
+{
+    TORCH_CHECK(v == v, op, ": ", name, " must not be NaN");
+    return (float)v;
+}
+// positive and finite, and its square finite in fp32 (square_positive: and not rounded to 0)
+static float positive_square_f32(double v, const char* op, const char* name, bool square_positive = false)
+{
+    const float f = (float)v, sq = f * f;
+    TORCH_CHECK(std::isfinite(v) && f > 0.f && std::isfinite(sq) && (sq > 0.f || !square_positive),
+                op, ": ", name, " (and its square in fp32) must be positive and finite, got ", v);
+    return f;
+}
+
 // ------------------------------------------------------------------------------------------------ TSDF fusion (csrc/tsdf.hip)
+// The body of tsdf_integrate_ and tsdf_integrate_color_.  Desc is the plain or the colour descriptor (the colour one begins with the plain
+// one's fields) and `launch` the C entry point that takes it; `color` and `images` are read for the colour descriptor only.
+template <class Desc>
+static Tensor integrate(const char* op, int (*launch)(const Desc*, estd_stream_t), const char* what, Tensor volume, const Tensor& color,
+                        at::TensorList depths, at::TensorList confs, at::TensorList images, const Tensor& mats, double trunc, double z_near,
+                        double conf_min, bool weighted, double w_max, bool no_skip)
+{
+    const OpScope scope(volume);
+    const VolumeArg v = check_volume(volume, op);
+    const int64_t T = (int64_t)depths.size();
+    TORCH_CHECK(T >= 1 && T <= ESTD_TSDF_MAX_FRAMES, op, ": 1..", ESTD_TSDF_MAX_FRAMES, " frames per call, got ", T);
+    TORCH_CHECK(confs.empty() || (int64_t)confs.size() == T, op, ": one confidence map per depth map (or none)");
+    TORCH_CHECK(!weighted || !confs.empty(), op, ": weighted fusion needs confidence maps");
+    const float* m = host_values(mats, T * 12, op, "mats", "[T,12]");
+    map_ptr(depths[0], {-1, -1}, op, "depth map");
+    const int64_t H = depths[0].size(-2), W = depths[0].size(-1);
+    Desc d{};
+    d.Z = (int)v.Z; d.Y = (int)v.Y; d.X = (int)v.X; d.T = (int)T; d.H = (int)H; d.W = (int)W;
+    d.weighted = weighted; d.no_skip = no_skip;
+    d.trunc = (float)trunc; d.z_near = (float)z_near; d.conf_min = (float)conf_min; d.w_max = (float)w_max;
+    d.tsdf = v.tsdf; d.weight = v.weight;
+    for (int64_t t = 0; t < T; ++t) {
+        d.depth[t] = map_ptr(depths[t], {H, W}, op, "depth map");
+        if (!confs.empty()) d.conf[t] = map_ptr(confs[t], {H, W}, op, "confidence map");
+        for (int i = 0; i < 12; ++i) d.mats[t][i] = m[t * 12 + i];
+    }
+    if constexpr (std::is_same_v<Desc, estd_tsdf_integrate_color_desc>) {
+        d.color = check_color_planes(color, volume, op);
+        TORCH_CHECK((int64_t)images.size() == T, op, ": one image per depth map, got ", images.size(), " for ", T);
+        for (int64_t t = 0; t < T; ++t) d.image[t] = map_ptr(images[t], {3, H, W}, op, "image");
+    }
+    check_status(launch(&d, cur_stream()), what);
+    return volume;
+}
+
 // volume [2,Z,Y,X]: plane 0 = D, plane 1 = Wt; in place.  mats: CPU float32 [T,12] (host values of the launch arguments).
 Tensor tsdf_integrate_(Tensor volume, at::TensorList depths, at::TensorList confs, const Tensor& mats, double trunc, double z_near,
                        double conf_min, bool weighted, double w_max, bool no_skip)
 {
-    const OpScope scope(volume);
-    TORCH_CHECK(volume.dim() == 4 && volume.size(0) == 2, "tsdf_integrate_: volume must be [2,Z,Y,X] (D plane, weight plane)");
-    float* vol = fptr_mut(volume, "volume");
-    const int64_t Z = volume.size(1), Y = volume.size(2), X = volume.size(3);
-    TORCH_CHECK(X % 4 == 0, "tsdf_integrate_: X must be a multiple of 4, got ", X);
-    const int64_t T = (int64_t)depths.size();
-    TORCH_CHECK(T >= 1 && T <= ESTD_TSDF_MAX_FRAMES, "tsdf_integrate_: 1..", ESTD_TSDF_MAX_FRAMES, " frames per call, got ", T);
-    TORCH_CHECK(confs.empty() || (int64_t)confs.size() == T, "tsdf_integrate_: one confidence map per depth map (or none)");
-    TORCH_CHECK(!weighted || !confs.empty(), "tsdf_integrate_: weighted fusion needs confidence maps");
-    TORCH_CHECK(mats.defined() && mats.device().is_cpu() && mats.scalar_type() == at::kFloat && mats.is_contiguous() && mats.numel() == T * 12,
-                "tsdf_integrate_: mats must be a contiguous CPU float32 tensor [T,12]");
-    TORCH_CHECK(depths[0].dim() >= 2, "tsdf_integrate_: depth maps must be [H,W] (leading 1s allowed)");
-    const int64_t H = depths[0].size(-2), W = depths[0].size(-1);
-    estd_tsdf_integrate_desc d{};
-    d.Z = (int)Z; d.Y = (int)Y; d.X = (int)X; d.T = (int)T; d.H = (int)H; d.W = (int)W;
-    d.weighted = weighted; d.no_skip = no_skip;
-    d.trunc = (float)trunc; d.z_near = (float)z_near; d.conf_min = (float)conf_min; d.w_max = (float)w_max;
-    d.tsdf = vol; d.weight = vol + Z * Y * X;
-    for (int64_t t = 0; t < T; ++t) {
-        TORCH_CHECK(depths[t].dim() >= 2 && depths[t].size(-2) == H && depths[t].size(-1) == W && depths[t].numel() == H * W,
-                    "tsdf_integrate_: depth map ", t, " must be [", H, ",", W, "]");
-        d.depth[t] = fptr(depths[t], "depth map");
-        if (!confs.empty()) {
-            TORCH_CHECK(confs[t].dim() >= 2 && confs[t].size(-2) == H && confs[t].size(-1) == W && confs[t].numel() == H * W,
-                        "tsdf_integrate_: confidence map ", t, " must have the depth map's shape [", H, ",", W, "]");
-            d.conf[t] = fptr(confs[t], "confidence map");
-        }
-        for (int i = 0; i < 12; ++i) d.mats[t][i] = mats.data_ptr<float>()[t * 12 + i];
-    }
-    check_status(estd_tsdf_integrate(&d, cur_stream()), "estd_tsdf_integrate");
-    return volume;
+    return integrate("tsdf_integrate_", estd_tsdf_integrate, "estd_tsdf_integrate", volume, Tensor(), depths, confs, {}, mats, trunc, z_near,
+                     conf_min, weighted, w_max, no_skip);
+}
+
+// tsdf_integrate_ with colour: color [3,Z,Y,X] in place beside the volume; images: one [3,H,W] per depth map.
+Tensor tsdf_integrate_color_(Tensor volume, Tensor color, at::TensorList depths, at::TensorList confs, at::TensorList images, const Tensor& mats,
+                             double trunc, double z_near, double conf_min, bool weighted, double w_max, bool no_skip)
+{
+    return integrate("tsdf_integrate_color_", estd_tsdf_integrate_color, "estd_tsdf_integrate_color", volume, color, depths, confs, images, mats,
+                     trunc, z_near, conf_min, weighted, w_max, no_skip);
 }
 
 // -> (count [1] int64 on the device = TOTAL crossings, xyz [capacity,3], normal [capacity,3], weight [capacity], edge [capacity] int64);
@@ -383,17 +488,13 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> tsdf_extract_points(const Ten
                                                                        double w_min, int64_t capacity)
 {
     const OpScope scope(volume);
-    TORCH_CHECK(volume.dim() == 4 && volume.size(0) == 2, "tsdf_extract_points: volume must be [2,Z,Y,X] (D plane, weight plane)");
-    const float* vol = fptr(volume, "volume");
-    const int64_t Z = volume.size(1), Y = volume.size(2), X = volume.size(3);
-    TORCH_CHECK(X % 4 == 0, "tsdf_extract_points: X must be a multiple of 4, got ", X);
+    const VolumeArg v = check_volume(volume, "tsdf_extract_points");
     TORCH_CHECK(capacity >= 0, "tsdf_extract_points: capacity must not be negative");
-    TORCH_CHECK(origin.defined() && origin.device().is_cpu() && origin.scalar_type() == at::kFloat && origin.is_contiguous() && origin.numel() == 3,
-                "tsdf_extract_points: origin must be a contiguous CPU float32 tensor [3]");
+    const float* org = host_values(origin, 3, "tsdf_extract_points", "origin", "[3]");
     Tensor count = at::zeros({1}, volume.options().dtype(at::kLong));
     Tensor xyz = new_f32({capacity, 3}, volume), normal = new_f32({capacity, 3}, volume), weight = new_f32({capacity}, volume);
     Tensor edge = at::empty({capacity}, volume.options().dtype(at::kLong));
-    check_status(estd_tsdf_extract_points(vol, vol + Z * Y * X, (int)Z, (int)Y, (int)X, (float)voxel_size, origin.data_ptr<float>(), (float)w_min,
+    check_status(estd_tsdf_extract_points(v.tsdf, v.weight, (int)v.Z, (int)v.Y, (int)v.X, (float)voxel_size, org, (float)w_min,
                                           reinterpret_cast<unsigned long long*>(count.data_ptr<int64_t>()), (long long)capacity,
                                           capacity ? xyz.data_ptr<float>() : nullptr, capacity ? normal.data_ptr<float>() : nullptr,
                                           capacity ? weight.data_ptr<float>() : nullptr,
@@ -402,138 +503,68 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> tsdf_extract_points(const Ten
     return {count, xyz, normal, weight, edge};
 }
 
+// The body of tsdf_raycast and tsdf_raycast_color, over the plain or the colour descriptor as in integrate() -> (depth, normal, weight and
+// a fourth map: the colour of the colour call, the stats of the plain one).  n_steps is in 1..2^24, dt must be positive and finite as
+// fp32, t_min finite and not negative, w_min not NaN.
+template <class Desc>
+static std::tuple<Tensor, Tensor, Tensor, Tensor> raycast(const char* op, int (*launch)(const Desc*, estd_stream_t), const char* what,
+                                                          const Tensor& volume, const Tensor& color, const Tensor& mat, int64_t H, int64_t W,
+                                                          double t_min, double dt, int64_t n_steps, double w_min, bool stats)
+{
+    const OpScope scope(volume);
+    const VolumeArg v = check_volume(volume, op);
+    const float* m = host_values(mat, 12, op, "mat", "[12] (3x4 row-major)");
+    check_map_size(H, W, op, "the image");
+    TORCH_CHECK(n_steps > 0 && n_steps <= (1 << 24), op, ": n_steps must be in 1..2^24, got ", n_steps);
+    Desc d{};
+    d.Z = (int)v.Z; d.Y = (int)v.Y; d.X = (int)v.X; d.H = (int)H; d.W = (int)W; d.n_steps = (int)n_steps;
+    d.dt = positive_f32(dt, op, "dt"); d.t_min = not_negative_f32(t_min, op, "t_min"); d.w_min = not_nan_f32(w_min, op, "w_min");
+    d.tsdf = v.tsdf; d.weight = v.weight;
+    for (int i = 0; i < 12; ++i) d.mat[i] = m[i];
+    Tensor fourth;
+    if constexpr (std::is_same_v<Desc, estd_tsdf_raycast_color_desc>) {
+        d.color = check_color_planes(color, volume, op);
+        fourth = new_f32({H, W, 3}, volume);
+        d.out_color = fourth.data_ptr<float>();
+    } else {
+        fourth = at::empty({stats ? H : 0, stats ? W : 0, stats ? 2 : 0}, volume.options().dtype(at::kInt));
+        d.stats = stats ? reinterpret_cast<unsigned int*>(fourth.data_ptr<int32_t>()) : nullptr;
+    }
+    Tensor depth = new_f32({H, W}, volume), normal = new_f32({H, W, 3}, volume), weight = new_f32({H, W}, volume);
+    d.depth = depth.data_ptr<float>(); d.normal = normal.data_ptr<float>(); d.out_weight = weight.data_ptr<float>();
+    check_status(launch(&d, cur_stream()), what);
+    return {depth, normal, weight, fourth};
+}
+
 // csrc/tsdf_raycast.hip: volume [2,Z,Y,X], mat: CPU float32 [12] (host values of the launch arguments) -> (depth [H,W], normal [H,W,3],
 // weight [H,W], stats: int32 [H,W,2] when asked for (measurement only), else [0])
 std::tuple<Tensor, Tensor, Tensor, Tensor> tsdf_raycast(const Tensor& volume, const Tensor& mat, int64_t H, int64_t W, double t_min, double dt,
                                                         int64_t n_steps, double w_min, bool stats)
 {
-    const OpScope scope(volume);
-    TORCH_CHECK(volume.dim() == 4 && volume.size(0) == 2, "tsdf_raycast: volume must be [2,Z,Y,X] (D plane, weight plane)");
-    const float* vol = fptr(volume, "volume");
-    const int64_t Z = volume.size(1), Y = volume.size(2), X = volume.size(3);
-    TORCH_CHECK(X % 4 == 0, "tsdf_raycast: X must be a multiple of 4, got ", X);
-    TORCH_CHECK(mat.defined() && mat.device().is_cpu() && mat.scalar_type() == at::kFloat && mat.is_contiguous() && mat.numel() == 12,
-                "tsdf_raycast: mat must be a contiguous CPU float32 tensor [12] (3x4 row-major)");
-    TORCH_CHECK(H > 0 && W > 0 && H * W <= 0x7fffffffLL, "tsdf_raycast: the image size must be positive (and H * W < 2^31), got ", H, " x ", W);
-    TORCH_CHECK(n_steps > 0 && n_steps <= (1 << 24), "tsdf_raycast: n_steps must be in 1..2^24, got ", n_steps);
-    TORCH_CHECK(std::isfinite(dt) && (float)dt > 0.f, "tsdf_raycast: dt must be positive and finite, got ", dt);
-    TORCH_CHECK(std::isfinite(t_min) && t_min >= 0, "tsdf_raycast: t_min must be finite and not negative, got ", t_min);
-    TORCH_CHECK(w_min == w_min, "tsdf_raycast: w_min must not be NaN");
-    Tensor depth = new_f32({H, W}, volume), normal = new_f32({H, W, 3}, volume), weight = new_f32({H, W}, volume);
-    Tensor st = at::empty({stats ? H : 0, stats ? W : 0, stats ? 2 : 0}, volume.options().dtype(at::kInt));
-    estd_tsdf_raycast_desc d{};
-    d.Z = (int)Z; d.Y = (int)Y; d.X = (int)X; d.H = (int)H; d.W = (int)W; d.n_steps = (int)n_steps;
-    d.t_min = (float)t_min; d.dt = (float)dt; d.w_min = (float)w_min;
-    d.tsdf = vol; d.weight = vol + Z * Y * X;
-    d.depth = depth.data_ptr<float>(); d.normal = normal.data_ptr<float>(); d.out_weight = weight.data_ptr<float>();
-    d.stats = stats ? reinterpret_cast<unsigned int*>(st.data_ptr<int32_t>()) : nullptr;
-    for (int i = 0; i < 12; ++i) d.mat[i] = mat.data_ptr<float>()[i];
-    check_status(estd_tsdf_raycast(&d, cur_stream()), "estd_tsdf_raycast");
-    return {depth, normal, weight, st};
-}
-
-// ------------------------------------------------------------------------------------------------ TSDF colour
-static void check_color_planes(const Tensor& color, const Tensor& volume, const char* op)
-{
-    TORCH_CHECK(color.dim() == 4 && color.size(0) == 3 && color.size(1) == volume.size(1) && color.size(2) == volume.size(2) &&
-                color.size(3) == volume.size(3), op, ": color must be [3,Z,Y,X] with the volume's Z, Y, X");
-    TORCH_CHECK(color.device() == volume.device(), op, ": color and the volume are on different devices");
-}
-
-// tsdf_integrate_ with colour: color [3,Z,Y,X] in place beside the volume; images: one [3,H,W] per depth map.
-Tensor tsdf_integrate_color_(Tensor volume, Tensor color, at::TensorList depths, at::TensorList confs, at::TensorList images, const Tensor& mats,
-                             double trunc, double z_near, double conf_min, bool weighted, double w_max, bool no_skip)
-{
-    const OpScope scope(volume);
-    TORCH_CHECK(volume.dim() == 4 && volume.size(0) == 2, "tsdf_integrate_color_: volume must be [2,Z,Y,X] (D plane, weight plane)");
-    float* vol = fptr_mut(volume, "volume");
-    check_color_planes(color, volume, "tsdf_integrate_color_");
-    float* col = fptr_mut(color, "color");
-    const int64_t Z = volume.size(1), Y = volume.size(2), X = volume.size(3);
-    TORCH_CHECK(X % 4 == 0, "tsdf_integrate_color_: X must be a multiple of 4, got ", X);
-    const int64_t T = (int64_t)depths.size();
-    TORCH_CHECK(T >= 1 && T <= ESTD_TSDF_MAX_FRAMES, "tsdf_integrate_color_: 1..", ESTD_TSDF_MAX_FRAMES, " frames per call, got ", T);
-    TORCH_CHECK(confs.empty() || (int64_t)confs.size() == T, "tsdf_integrate_color_: one confidence map per depth map (or none)");
-    TORCH_CHECK((int64_t)images.size() == T, "tsdf_integrate_color_: one image per depth map, got ", images.size(), " for ", T);
-    TORCH_CHECK(!weighted || !confs.empty(), "tsdf_integrate_color_: weighted fusion needs confidence maps");
-    TORCH_CHECK(mats.defined() && mats.device().is_cpu() && mats.scalar_type() == at::kFloat && mats.is_contiguous() && mats.numel() == T * 12,
-                "tsdf_integrate_color_: mats must be a contiguous CPU float32 tensor [T,12]");
-    TORCH_CHECK(depths[0].dim() >= 2, "tsdf_integrate_color_: depth maps must be [H,W] (leading 1s allowed)");
-    const int64_t H = depths[0].size(-2), W = depths[0].size(-1);
-    estd_tsdf_integrate_color_desc d{};
-    d.Z = (int)Z; d.Y = (int)Y; d.X = (int)X; d.T = (int)T; d.H = (int)H; d.W = (int)W;
-    d.weighted = weighted; d.no_skip = no_skip;
-    d.trunc = (float)trunc; d.z_near = (float)z_near; d.conf_min = (float)conf_min; d.w_max = (float)w_max;
-    d.tsdf = vol; d.weight = vol + Z * Y * X; d.color = col;
-    for (int64_t t = 0; t < T; ++t) {
-        TORCH_CHECK(depths[t].dim() >= 2 && depths[t].size(-2) == H && depths[t].size(-1) == W && depths[t].numel() == H * W,
-                    "tsdf_integrate_color_: depth map ", t, " must be [", H, ",", W, "]");
-        TORCH_CHECK(depths[t].device() == volume.device(), "tsdf_integrate_color_: depth map ", t, " is not on the volume's device");
-        d.depth[t] = fptr(depths[t], "depth map");
-        if (!confs.empty()) {
-            TORCH_CHECK(confs[t].dim() >= 2 && confs[t].size(-2) == H && confs[t].size(-1) == W && confs[t].numel() == H * W,
-                        "tsdf_integrate_color_: confidence map ", t, " must have the depth map's shape [", H, ",", W, "]");
-            TORCH_CHECK(confs[t].device() == volume.device(), "tsdf_integrate_color_: confidence map ", t, " is not on the volume's device");
-            d.conf[t] = fptr(confs[t], "confidence map");
-        }
-        TORCH_CHECK(images[t].dim() >= 3 && images[t].size(-3) == 3 && images[t].size(-2) == H && images[t].size(-1) == W &&
-                    images[t].numel() == 3 * H * W, "tsdf_integrate_color_: image ", t, " must be [3,", H, ",", W, "]");
-        TORCH_CHECK(images[t].device() == volume.device(), "tsdf_integrate_color_: image ", t, " is not on the volume's device");
-        d.image[t] = fptr(images[t], "image");
-        for (int i = 0; i < 12; ++i) d.mats[t][i] = mats.data_ptr<float>()[t * 12 + i];
-    }
-    check_status(estd_tsdf_integrate_color(&d, cur_stream()), "estd_tsdf_integrate_color");
-    return volume;
-}
-
-// edge: int64 [N] (the ids of tsdf_extract_points) -> colour at the crossings [N,3]
-Tensor tsdf_edge_colors(const Tensor& volume, const Tensor& color, const Tensor& edge)
-{
-    const OpScope scope(volume);
-    TORCH_CHECK(volume.dim() == 4 && volume.size(0) == 2, "tsdf_edge_colors: volume must be [2,Z,Y,X] (D plane, weight plane)");
-    const float* vol = fptr(volume, "volume");
-    check_color_planes(color, volume, "tsdf_edge_colors");
-    const float* col = fptr(color, "color");
-    const int64_t Z = volume.size(1), Y = volume.size(2), X = volume.size(3);
-    TORCH_CHECK(X % 4 == 0, "tsdf_edge_colors: X must be a multiple of 4, got ", X);
-    TORCH_CHECK(edge.defined() && edge.dim() == 1 && edge.scalar_type() == at::kLong && edge.is_contiguous() && edge.device() == volume.device(),
-                "tsdf_edge_colors: edge must be a contiguous int64 tensor [N] on the volume's device");
-    const int64_t n = edge.size(0);
-    Tensor out = new_f32({n, 3}, volume);
-    if (n)
-        check_status(estd_tsdf_edge_colors(vol, col, (int)Z, (int)Y, (int)X, reinterpret_cast<const long long*>(edge.data_ptr<int64_t>()),
-                                           (long long)n, out.data_ptr<float>(), cur_stream()), "estd_tsdf_edge_colors");
-    return out;
+    return raycast("tsdf_raycast", estd_tsdf_raycast, "estd_tsdf_raycast", volume, Tensor(), mat, H, W, t_min, dt, n_steps, w_min, stats);
 }
 
 // tsdf_raycast with a colour map -> (depth [H,W], normal [H,W,3], weight [H,W], color [H,W,3])
 std::tuple<Tensor, Tensor, Tensor, Tensor> tsdf_raycast_color(const Tensor& volume, const Tensor& color, const Tensor& mat, int64_t H, int64_t W,
                                                               double t_min, double dt, int64_t n_steps, double w_min)
 {
+    return raycast("tsdf_raycast_color", estd_tsdf_raycast_color, "estd_tsdf_raycast_color", volume, color, mat, H, W, t_min, dt, n_steps, w_min,
+                   false);
+}
+
+// edge: int64 [N] (the ids of tsdf_extract_points) -> colour at the crossings [N,3]
+Tensor tsdf_edge_colors(const Tensor& volume, const Tensor& color, const Tensor& edge)
+{
     const OpScope scope(volume);
-    TORCH_CHECK(volume.dim() == 4 && volume.size(0) == 2, "tsdf_raycast_color: volume must be [2,Z,Y,X] (D plane, weight plane)");
-    const float* vol = fptr(volume, "volume");
-    check_color_planes(color, volume, "tsdf_raycast_color");
-    const float* col = fptr(color, "color");
-    const int64_t Z = volume.size(1), Y = volume.size(2), X = volume.size(3);
-    TORCH_CHECK(X % 4 == 0, "tsdf_raycast_color: X must be a multiple of 4, got ", X);
-    TORCH_CHECK(mat.defined() && mat.device().is_cpu() && mat.scalar_type() == at::kFloat && mat.is_contiguous() && mat.numel() == 12,
-                "tsdf_raycast_color: mat must be a contiguous CPU float32 tensor [12] (3x4 row-major)");
-    TORCH_CHECK(H > 0 && W > 0 && H * W <= 0x7fffffffLL, "tsdf_raycast_color: the image size must be positive (and H * W < 2^31), got ", H, " x ", W);
-    TORCH_CHECK(n_steps > 0 && n_steps <= (1 << 24), "tsdf_raycast_color: n_steps must be in 1..2^24, got ", n_steps);
-    TORCH_CHECK(std::isfinite(dt) && (float)dt > 0.f, "tsdf_raycast_color: dt must be positive and finite, got ", dt);
-    TORCH_CHECK(std::isfinite(t_min) && t_min >= 0, "tsdf_raycast_color: t_min must be finite and not negative, got ", t_min);
-    TORCH_CHECK(w_min == w_min, "tsdf_raycast_color: w_min must not be NaN");
-    Tensor depth = new_f32({H, W}, volume), normal = new_f32({H, W, 3}, volume), weight = new_f32({H, W}, volume), rgb = new_f32({H, W, 3}, volume);
-    estd_tsdf_raycast_color_desc d{};
-    d.Z = (int)Z; d.Y = (int)Y; d.X = (int)X; d.H = (int)H; d.W = (int)W; d.n_steps = (int)n_steps;
-    d.t_min = (float)t_min; d.dt = (float)dt; d.w_min = (float)w_min;
-    d.tsdf = vol; d.weight = vol + Z * Y * X; d.color = col;
-    d.depth = depth.data_ptr<float>(); d.normal = normal.data_ptr<float>(); d.out_weight = weight.data_ptr<float>();
-    d.out_color = rgb.data_ptr<float>();
-    for (int i = 0; i < 12; ++i) d.mat[i] = mat.data_ptr<float>()[i];
-    check_status(estd_tsdf_raycast_color(&d, cur_stream()), "estd_tsdf_raycast_color");
-    return {depth, normal, weight, rgb};
+    const VolumeArg v = check_volume(volume, "tsdf_edge_colors");
+    const float* col = check_color_planes(color, volume, "tsdf_edge_colors");
+    const int64_t* ids = lptr(edge, "tsdf_edge_colors", "edge", volume, -1);
+    const int64_t n = edge.size(0);
+    Tensor out = new_f32({n, 3}, volume);
+    if (n)
+        check_status(estd_tsdf_edge_colors(v.tsdf, col, (int)v.Z, (int)v.Y, (int)v.X, reinterpret_cast<const long long*>(ids), (long long)n,
+                                           out.data_ptr<float>(), cur_stream()), "estd_tsdf_edge_colors");
+    return out;
 }
 
 // ------------------------------------------------------------------------------------------------ cross-view consistency
@@ -542,32 +573,20 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> tsdf_raycast_color(const Tensor& volu
 std::tuple<Tensor, Tensor, Tensor, Tensor> depth_consistency(const Tensor& target, at::TensorList sources, const Tensor& mats, double px_max,
                                                              double rel_max, double z_near)
 {
+    const char* op = "depth_consistency";
     const OpScope scope(target);
-    const float* tgt = fptr(target, "target");
-    TORCH_CHECK(target.dim() >= 2, "depth_consistency: the target must be [H,W] (leading 1s allowed)");
+    estd_depth_consistency_desc d{};
+    d.target = map_ptr(target, {-1, -1}, op, "target");
     const int64_t H = target.size(-2), W = target.size(-1);
-    TORCH_CHECK(target.numel() == H * W, "depth_consistency: the target must be [H,W] (leading 1s allowed)");
-    TORCH_CHECK(H >= 2 && W >= 2 && H * W <= 0x7fffffffLL, "depth_consistency: maps must be at least 2 x 2 (and H * W < 2^31), got ", H, " x ", W);
+    check_map_size(H, W, op, "maps", 2);
     const int64_t S = (int64_t)sources.size();
     TORCH_CHECK(S >= 1 && S <= ESTD_CONSISTENCY_MAX_SOURCES, "depth_consistency: 1..", ESTD_CONSISTENCY_MAX_SOURCES, " sources per call, got ", S);
-    TORCH_CHECK(mats.defined() && mats.device().is_cpu() && mats.scalar_type() == at::kFloat && mats.is_contiguous() && mats.numel() == S * 24,
-                "depth_consistency: mats must be a contiguous CPU float32 tensor [S,2,12]");
-    TORCH_CHECK(std::isfinite(px_max) && (float)px_max > 0.f, "depth_consistency: px_max must be positive and finite, got ", px_max);
-    TORCH_CHECK(std::isfinite(rel_max) && (float)rel_max > 0.f, "depth_consistency: rel_max must be positive and finite, got ", rel_max);
-    TORCH_CHECK(std::isfinite(z_near) && z_near >= 0, "depth_consistency: z_near must be finite and not negative, got ", z_near);
-    estd_depth_consistency_desc d{};
+    const float* m = host_values(mats, S * 24, op, "mats", "[S,2,12]", true);
     d.H = (int)H; d.W = (int)W; d.S = (int)S;
-    d.px_max = (float)px_max; d.rel_max = (float)rel_max; d.z_near = (float)z_near;
-    d.target = tgt;
+    d.px_max = positive_f32(px_max, op, "px_max"); d.rel_max = positive_f32(rel_max, op, "rel_max"); d.z_near = not_negative_f32(z_near, op, "z_near");
     for (int64_t s = 0; s < S; ++s) {
-        TORCH_CHECK(sources[s].dim() >= 2 && sources[s].size(-2) == H && sources[s].size(-1) == W && sources[s].numel() == H * W,
-                    "depth_consistency: source ", s, " must be [", H, ",", W, "]");
-        d.source[s] = fptr(sources[s], "source map");
-        for (int i = 0; i < 24; ++i) {
-            const float m = mats.data_ptr<float>()[s * 24 + i];
-            TORCH_CHECK(std::isfinite(m), "depth_consistency: mats holds a value that is not finite");
-            d.mats[s][i / 12][i % 12] = m;
-        }
+        d.source[s] = map_ptr(sources[s], {H, W}, op, "source");
+        for (int i = 0; i < 24; ++i) d.mats[s][i / 12][i % 12] = m[s * 24 + i];
     }
     Tensor views = new_f32({H, W}, target), visible = new_f32({H, W}, target), depth = new_f32({H, W}, target), rel_err = new_f32({H, W}, target);
     d.views = views.data_ptr<float>(); d.visible = visible.data_ptr<float>(); d.depth = depth.data_ptr<float>(); d.rel_err = rel_err.data_ptr<float>();
@@ -576,35 +595,27 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> depth_consistency(const Tensor& targe
 }
 
 // ------------------------------------------------------------------------------------------------ point clouds (csrc/cloud_nn.hip)
-static void check_cloud(const Tensor& t, const char* op, const char* name, int64_t cols)
+static const float* check_cloud(const Tensor& t, const char* op, const char* name, int64_t cols)
 {
+    const float* p = fptr(t, name);
     TORCH_CHECK(t.dim() == 2 && t.size(1) == cols && t.size(0) <= 0x7fffffffLL, op, ": ", name, " must be [n,", cols, "] with n < 2^31");
+    return p;
 }
 
 static void check_cloud_grid(const Tensor& lo, double cell, at::IntArrayRef dims, const char* op, int64_t max_dim)
 {
-    TORCH_CHECK(lo.defined() && lo.device().is_cpu() && lo.scalar_type() == at::kFloat && lo.is_contiguous() && lo.numel() == 3,
-                op, ": lo must be a contiguous CPU float32 tensor [3]");
-    for (int j = 0; j < 3; ++j) TORCH_CHECK(std::isfinite(lo.data_ptr<float>()[j]), op, ": lo holds a value that is not finite");
-    TORCH_CHECK(std::isfinite(cell) && (float)cell > 0.f && std::isfinite((float)cell) && std::isfinite(1.0f / (float)cell),
-                op, ": cell must be positive and finite in fp32 (and its reciprocal too), got ", cell);
+    host_values(lo, 3, op, "lo", "[3]", true);
+    const float c = positive_f32(cell, op, "cell");
+    TORCH_CHECK(std::isfinite(c) && std::isfinite(1.0f / c), op, ": cell must be finite in fp32 (and its reciprocal too), got ", cell);
     TORCH_CHECK(dims.size() == 3, op, ": dims must be three sizes");
     for (int j = 0; j < 3; ++j) TORCH_CHECK(dims[j] >= 1 && dims[j] <= max_dim, op, ": dims must be three sizes in 1..", max_dim, ", got ", dims[j]);
-}
-
-static const int64_t* lptr(const Tensor& t, const char* op, const char* name, const Tensor& like, int64_t size)
-{
-    TORCH_CHECK(t.defined() && t.dim() == 1 && t.scalar_type() == at::kLong && t.is_contiguous() && t.device() == like.device() &&
-                (size < 0 || t.size(0) == size), op, ": ", name, " must be a contiguous int64 vector of the right length on the cloud's device");
-    return t.data_ptr<int64_t>();
 }
 
 // points [n,3], lo: CPU float32 [3], dims: cells along x, y, z -> keys int64 [n]
 Tensor cloud_cell_keys(const Tensor& points, const Tensor& lo, double cell, at::IntArrayRef dims)
 {
     const OpScope scope(points);
-    const float* pts = fptr(points, "points");
-    check_cloud(points, "cloud_cell_keys", "points", 3);
+    const float* pts = check_cloud(points, "cloud_cell_keys", "points", 3);
     check_cloud_grid(lo, cell, dims, "cloud_cell_keys", ESTD_CLOUD_KEY_MAX_DIM);
     const int64_t n = points.size(0);
     Tensor keys = at::empty({n}, points.options().dtype(at::kLong));
@@ -620,30 +631,25 @@ Tensor cloud_cell_keys(const Tensor& points, const Tensor& lo, double cell, at::
 std::tuple<Tensor, Tensor, Tensor> cloud_nearest(const Tensor& query, const Tensor& order, const Tensor& records, const Tensor& cell_start,
                                                  const Tensor& lo, double cell, at::IntArrayRef dims, double max_dist, bool stats)
 {
+    const char* op = "cloud_nearest";
     const OpScope scope(query);
-    const float* q = fptr(query, "query");
-    check_cloud(query, "cloud_nearest", "query", 3);
-    const float* rec = fptr(records, "records");
-    check_cloud(records, "cloud_nearest", "records", 4);
+    estd_cloud_nearest_desc d{};
+    d.query = check_cloud(query, op, "query", 3);
+    d.records = check_cloud(records, op, "records", 4);
     const int64_t M = query.size(0), N = records.size(0);
-    const int64_t* ord = lptr(order, "cloud_nearest", "order", query, M);
-    TORCH_CHECK(std::isfinite(max_dist) && (float)max_dist > 0.f && std::isfinite((float)max_dist * (float)max_dist),
-                "cloud_nearest: max_dist must be positive and finite (and its square too), got ", max_dist);
-    check_cloud_grid(lo, cell, dims, "cloud_nearest", ESTD_CLOUD_MAX_DIM);
+    d.order = reinterpret_cast<const long long*>(lptr(order, op, "order", query, M));
+    d.max_dist = positive_square_f32(max_dist, op, "max_dist");
+    check_cloud_grid(lo, cell, dims, op, ESTD_CLOUD_MAX_DIM);
     const int64_t cells = dims[0] * dims[1] * dims[2];
     TORCH_CHECK(cells <= ESTD_CLOUD_MAX_CELLS, "cloud_nearest: ", cells, " cells, at most ", ESTD_CLOUD_MAX_CELLS);
-    TORCH_CHECK(cell_start.defined() && cell_start.dim() == 1 && cell_start.scalar_type() == at::kInt && cell_start.is_contiguous() &&
-                cell_start.size(0) == cells + 1 && cell_start.device() == query.device(),
-                "cloud_nearest: cell_start must be a contiguous int32 tensor [", cells + 1, "] (cells + 1) on the query's device");
+    d.cell_start = lptr<int32_t>(cell_start, op, "cell_start (cells + 1)", query, cells + 1);
     Tensor dist = new_f32({M}, query), index = at::empty({M}, query.options().dtype(at::kLong));
     Tensor st = at::empty({stats ? M : 0}, query.options().dtype(at::kInt));
     if (M) {
-        estd_cloud_nearest_desc d{};
         d.M = (long long)M; d.N = (long long)N;
-        d.query = q; d.order = reinterpret_cast<const long long*>(ord); d.records = rec; d.cell_start = cell_start.data_ptr<int32_t>();
         d.dist = dist.data_ptr<float>(); d.index = reinterpret_cast<long long*>(index.data_ptr<int64_t>());
         d.stats = stats ? reinterpret_cast<unsigned int*>(st.data_ptr<int32_t>()) : nullptr;
-        d.cell = (float)cell; d.max_dist = (float)max_dist;
+        d.cell = (float)cell;
         for (int j = 0; j < 3; ++j) { d.lo[j] = lo.data_ptr<float>()[j]; d.dims[j] = (int)dims[j]; }
         check_status(estd_cloud_nearest(&d, cur_stream()), "estd_cloud_nearest");
     }
@@ -653,9 +659,9 @@ std::tuple<Tensor, Tensor, Tensor> cloud_nearest(const Tensor& query, const Tens
 // points [n,3], attrs [n,C] (C = 0: none), order int64 [n], segments int64 [K + 1] -> (points [K,3], attrs [K,C])
 std::tuple<Tensor, Tensor> cloud_cell_centroids(const Tensor& points, const Tensor& attrs, const Tensor& order, const Tensor& segments)
 {
+    const char* op = "cloud_cell_centroids";
     const OpScope scope(points);
-    const float* pts = fptr(points, "points");
-    check_cloud(points, "cloud_cell_centroids", "points", 3);
+    const float* pts = check_cloud(points, op, "points", 3);
     const int64_t n = points.size(0);
     TORCH_CHECK(attrs.defined() && attrs.dim() == 2, "cloud_cell_centroids: attrs must be [n,C]");
     const int64_t C = attrs.size(1);
@@ -664,8 +670,8 @@ std::tuple<Tensor, Tensor> cloud_cell_centroids(const Tensor& points, const Tens
         att = fptr(attrs, "attrs");
         TORCH_CHECK(attrs.size(0) == n && C <= ESTD_CLOUD_MAX_ATTRS, "cloud_cell_centroids: attrs must be [n,C] with C <= ", ESTD_CLOUD_MAX_ATTRS);
     }
-    const int64_t* ord = lptr(order, "cloud_cell_centroids", "order", points, n);
-    const int64_t* seg = lptr(segments, "cloud_cell_centroids", "segments", points, -1);
+    const int64_t* ord = lptr(order, op, "order", points, n);
+    const int64_t* seg = lptr(segments, op, "segments", points, -1);
     TORCH_CHECK(segments.size(0) >= 1 && segments.size(0) <= n + 1, "cloud_cell_centroids: segments must be [K + 1] with K <= n");
     const int64_t K = segments.size(0) - 1;
     Tensor out = new_f32({K, 3}, points), out_attrs = new_f32({K, C}, points);
@@ -1053,37 +1059,23 @@ int64_t set_reserved_cus(int64_t n) { return estd_set_reserved_cus((int)n); }
 std::tuple<Tensor, Tensor, Tensor> frame_align(const Tensor& depth, const OptTensor& conf, const Tensor& m_depth, const Tensor& m_normal,
                                                const Tensor& mats, double dist_max, double z_near, double conf_min)
 {
+    const char* op = "frame_align";
     const OpScope scope(depth);
-    const float* dp = fptr(depth, "depth");
-    TORCH_CHECK(depth.dim() >= 2, "frame_align: depth must be [H,W] (leading 1s allowed)");
-    const int64_t H = depth.size(-2), W = depth.size(-1);
-    TORCH_CHECK(depth.numel() == H * W, "frame_align: depth must be [H,W] (leading 1s allowed)");
-    TORCH_CHECK(H > 0 && W > 0 && H * W <= 0x7fffffffLL, "frame_align: the map size must be positive (and H * W < 2^31), got ", H, " x ", W);
-    const float* cp = opt_fptr(conf, "conf");
-    if (cp) TORCH_CHECK(conf->dim() >= 2 && conf->size(-2) == H && conf->size(-1) == W && conf->numel() == H * W, "frame_align: conf must be [", H, ",", W, "]");
-    const float* mdp = fptr(m_depth, "m_depth");
-    TORCH_CHECK(m_depth.dim() >= 2, "frame_align: m_depth must be [Hm,Wm] (leading 1s allowed)");
-    const int64_t Hm = m_depth.size(-2), Wm = m_depth.size(-1);
-    TORCH_CHECK(m_depth.numel() == Hm * Wm && Hm > 0 && Wm > 0 && Hm * Wm <= 0x7fffffffLL,
-                "frame_align: m_depth must be [Hm,Wm] with a positive size (and Hm * Wm < 2^31)");
-    const float* mnp = fptr(m_normal, "m_normal");
-    TORCH_CHECK(m_normal.dim() >= 3 && m_normal.size(-3) == Hm && m_normal.size(-2) == Wm && m_normal.size(-1) == 3 && m_normal.numel() == 3 * Hm * Wm,
-                "frame_align: m_normal must be [", Hm, ",", Wm, ",3]");
-    TORCH_CHECK(mats.defined() && mats.device().is_cpu() && mats.scalar_type() == at::kFloat && mats.is_contiguous() && mats.numel() == 36,
-                "frame_align: mats must be a contiguous CPU float32 tensor [3,12] (L, Fm, Bm)");
-    TORCH_CHECK(std::isfinite(dist_max) && (float)dist_max > 0.f && std::isfinite((float)dist_max * (float)dist_max) && (float)dist_max * (float)dist_max > 0.f,
-                "frame_align: dist_max (and its square in fp32) must be positive and finite, got ", dist_max);
-    TORCH_CHECK(std::isfinite(z_near) && z_near >= 0, "frame_align: z_near must be finite and not negative, got ", z_near);
-    TORCH_CHECK(conf_min == conf_min, "frame_align: conf_min must not be NaN");
     estd_frame_align_desc d{};
+    d.depth = map_ptr(depth, {-1, -1}, op, "depth");
+    const int64_t H = depth.size(-2), W = depth.size(-1);
+    check_map_size(H, W, op, "depth");
+    d.conf = opt_fptr(conf, "conf");
+    if (d.conf) map_ptr(*conf, {H, W}, op, "conf");
+    d.m_depth = map_ptr(m_depth, {-1, -1}, op, "m_depth");
+    const int64_t Hm = m_depth.size(-2), Wm = m_depth.size(-1);
+    check_map_size(Hm, Wm, op, "m_depth");
+    d.m_normal = map_ptr(m_normal, {Hm, Wm, 3}, op, "m_normal");
+    const float* m = host_values(mats, 36, op, "mats", "[3,12] (L, Fm, Bm)", true);
     d.H = (int)H; d.W = (int)W; d.Hm = (int)Hm; d.Wm = (int)Wm;
-    d.dist_max = (float)dist_max; d.z_near = (float)z_near; d.conf_min = (float)conf_min;
-    d.depth = dp; d.conf = cp; d.m_depth = mdp; d.m_normal = mnp;
-    for (int i = 0; i < 36; ++i) {
-        const float m = mats.data_ptr<float>()[i];
-        TORCH_CHECK(std::isfinite(m), "frame_align: mats holds a value that is not finite");
-        (i < 12 ? d.L : i < 24 ? d.Fm : d.Bm)[i % 12] = m;
-    }
+    d.dist_max = positive_square_f32(dist_max, op, "dist_max", true); d.z_near = not_negative_f32(z_near, op, "z_near");
+    d.conf_min = not_nan_f32(conf_min, op, "conf_min");
+    for (int i = 0; i < 12; ++i) { d.L[i] = m[i]; d.Fm[i] = m[12 + i]; d.Bm[i] = m[24 + i]; }
     Tensor residual = new_f32({H, W}, depth), match = at::empty({H, W}, depth.options().dtype(at::kInt));
     Tensor sums = at::empty({ESTD_FRAME_ALIGN_SUMS}, depth.options().dtype(at::kDouble));
     Tensor partials = at::empty({estd_frame_align_partials((int)H, (int)W) / 8}, depth.options().dtype(at::kDouble));

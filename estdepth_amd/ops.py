@@ -985,15 +985,113 @@ def vol_to_cdhw(src, C, dims, src_stride, src_off):
     return out
 
 
+# ---------------------------------------------------------------------------------- reconstruction operators: argument checks
+# One helper per kind of check for the ctypes front ends below (csrc/torch_ops.cpp has the same set for the torch binding); each takes
+# the operator's and the argument's name for its message.
+def _volume(volume, op):
+    """the volume argument: two float32 planes (D, weight), contiguous, on a device, X % 4 == 0 -> (Z, Y, X, address of the weight plane)"""
+    _need(isinstance(volume, torch.Tensor) and volume.dim() == 4 and volume.shape[0] == 2, "%s: volume must be [2,Z,Y,X] (D plane, weight plane)" % op)
+    _chk(volume, "volume")
+    Z, Y, X = volume.shape[1:]
+    _need(X % 4 == 0, "%s: X must be a multiple of 4, got %d" % (op, X))
+    return Z, Y, X, volume.data_ptr() + 4 * Z * Y * X
+
+
+def _color_planes(color, volume, op):
+    _need(isinstance(color, torch.Tensor) and color.dim() == 4 and color.shape[0] == 3 and tuple(color.shape[1:]) == tuple(volume.shape[1:]),
+          "%s: color must be [3,Z,Y,X] with the volume's Z, Y, X" % op)
+    _chk(color, "color")
+    _need(color.device == volume.device, "%s: color is on %s but the volume on %s" % (op, color.device, volume.device))
+
+
+def _host_values(t, n, op, name, shape, finite=False):
+    """host values of the launch arguments: exactly ``n`` of them (``finite``: none NaN or infinite) -> the values as a list"""
+    _need(isinstance(t, torch.Tensor) and not t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n,
+          "%s: %s must be a contiguous CPU float32 tensor %s" % (op, name, shape))
+    flat = t.reshape(-1).tolist()
+    _need(not finite or all(math.isfinite(v) for v in flat), "%s: %s holds a value that is not finite" % (op, name))
+    return flat
+
+
+def _map(t, tail, op, name, dev=None):
+    """``t`` is a float32 device map whose last sizes are ``tail`` (-1: any size), leading 1s allowed, on ``dev`` -> its last sizes"""
+    _chk(t, name)
+    got = tuple(t.shape[-len(tail):])
+    _need(t.dim() >= len(tail) and all(w in (-1, g) for w, g in zip(tail, got)) and t.numel() == math.prod(got),
+          "%s: %s must end in the sizes %s (-1: any; leading 1s allowed), got %s" % (op, name, tail, tuple(t.shape)))
+    _need(dev is None or t.device == dev, "%s: %s is on %s but the operator runs on %s" % (op, name, t.device, dev))
+    return got
+
+
+def _map_size(H, W, op, name, least=1):
+    _need(H >= least and W >= least and H * W <= 0x7fffffff, "%s: %s must be at least %d x %d (and H * W < 2^31), got %d x %d" % (op, name, least, least, H, W))
+
+
+def _ivec(t, op, name, dev, size=None, dtype=torch.int64):
+    _need(isinstance(t, torch.Tensor) and t.dim() == 1 and t.dtype == dtype and t.is_contiguous() and t.device == dev
+          and (size is None or t.shape[0] == size),
+          "%s: %s must be a contiguous %s vector%s on the operator's device" % (op, name, dtype, "" if size is None else " [%d]" % size))
+
+
+# the four rules for a scalar that a kernel takes as fp32
+def _positive(v, op, name):
+    _need(math.isfinite(v) and ctypes.c_float(v).value > 0, "%s: %s must be positive and finite, got %r" % (op, name, v))
+
+
+def _not_negative(v, op, name):
+    _need(math.isfinite(v) and v >= 0, "%s: %s must be finite and not negative, got %r" % (op, name, v))
+
+
+def _not_nan(v, op, name):
+    _need(v == v, "%s: %s must not be NaN" % (op, name))
+
+
+def _positive_square(v, op, name, square_positive=False):
+    """positive and finite, and its square finite in fp32 (``square_positive``: and not rounded to 0)"""
+    v32 = ctypes.c_float(v).value if math.isfinite(v) else float("nan")
+    sq = ctypes.c_float(v32 * v32).value
+    _need(v32 > 0 and math.isfinite(sq) and (sq > 0 or not square_positive),
+          "%s: %s (and its square in fp32) must be positive and finite, got %r" % (op, name, v))
+
+
 # ---------------------------------------------------------------------------------- TSDF fusion (csrc/tsdf.hip)
-TSDF_MAX_FRAMES = 8             # ESTD_TSDF_MAX_FRAMES (include/estd_hip.h)
+TSDF_MAX_FRAMES = N.TSDF_MAX_FRAMES
 
 
-def _maps(ts, name, H, W):
-    for i, t in enumerate(ts):
-        _chk(t, "%s %d" % (name, i))
-        _need(t.dim() >= 2 and tuple(t.shape[-2:]) == (H, W) and t.numel() == H * W, "tsdf_integrate_: %s %d must be [%d,%d], got %s"
-              % (name, i, H, W, tuple(t.shape)))
+def _tsdf_integrate(op, volume, color, depths, confs, images, mats, trunc, z_near, conf_min, weighted, w_max, no_skip):
+    """tsdf_integrate_ (``color`` and ``images`` None) and tsdf_integrate_color_ under the ctypes binding"""
+    Z, Y, X, weight = _volume(volume, op)
+    n = len(depths)
+    _need(1 <= n <= TSDF_MAX_FRAMES, "%s: 1..%d frames per call, got %d" % (op, TSDF_MAX_FRAMES, n))
+    _need(len(confs) in (0, n), "%s: one confidence map per depth map (or none)" % op)
+    _need(not weighted or confs, "%s: weighted fusion needs confidence maps" % op)
+    flat = _host_values(mats, n * 12, op, "mats", "[T,12]")
+    dev = volume.device
+    H, W = _map(depths[0], (-1, -1), op, "depth map 0", dev)
+    for name, maps in (("depth map", depths), ("confidence map", confs)):
+        for i, t in enumerate(maps):
+            _map(t, (H, W), op, "%s %d" % (name, i), dev)
+    d = N.TsdfIntegrateDesc() if color is None else N.TsdfIntegrateColorDesc()
+    d.Z, d.Y, d.X, d.T, d.H, d.W = Z, Y, X, n, H, W
+    d.weighted, d.no_skip = int(bool(weighted)), int(bool(no_skip))
+    d.trunc, d.z_near, d.conf_min, d.w_max = float(trunc), float(z_near), float(conf_min), float(w_max)
+    d.tsdf, d.weight = volume.data_ptr(), weight
+    for t in range(n):
+        d.depth[t] = depths[t].data_ptr()
+        d.conf[t] = confs[t].data_ptr() if confs else None
+        d.mats[t][:] = flat[t * 12:t * 12 + 12]
+    launch, what = N.lib().estd_tsdf_integrate, "estd_tsdf_integrate"
+    if color is not None:
+        _color_planes(color, volume, op)
+        _need(len(images) == n, "%s: one image per depth map, got %d for %d" % (op, len(images), n))
+        d.color = color.data_ptr()
+        for t in range(n):
+            _map(images[t], (3, H, W), op, "image %d" % t, dev)
+            d.image[t] = images[t].data_ptr()
+        launch, what = N.lib().estd_tsdf_integrate_color, "estd_tsdf_integrate_color"
+    with torch.cuda.device(dev):
+        N.check(launch(ctypes.byref(d), _stream()), what)
+    return volume
 
 
 def tsdf_integrate_(volume, depths, confs, mats, trunc, z_near, conf_min, weighted, w_max, no_skip=False):
@@ -1003,105 +1101,7 @@ def tsdf_integrate_(volume, depths, confs, mats, trunc, z_near, conf_min, weight
     depths, confs = list(depths), list(confs) if confs is not None else []
     if _use_torch():
         return T().tsdf_integrate_(volume, depths, confs, mats, float(trunc), float(z_near), float(conf_min), bool(weighted), float(w_max), bool(no_skip))
-    _need(isinstance(volume, torch.Tensor) and volume.dim() == 4 and volume.shape[0] == 2, "tsdf_integrate_: volume must be [2,Z,Y,X] (D plane, weight plane)")
-    _chk(volume, "volume")
-    Z, Y, X = volume.shape[1:]
-    _need(X % 4 == 0, "tsdf_integrate_: X must be a multiple of 4, got %d" % X)
-    n = len(depths)
-    _need(1 <= n <= TSDF_MAX_FRAMES, "tsdf_integrate_: 1..%d frames per call, got %d" % (TSDF_MAX_FRAMES, n))
-    _need(len(confs) in (0, n), "tsdf_integrate_: one confidence map per depth map (or none)")
-    _need(not weighted or confs, "tsdf_integrate_: weighted fusion needs confidence maps")
-    _need(isinstance(mats, torch.Tensor) and not mats.is_cuda and mats.dtype == torch.float32 and mats.is_contiguous() and mats.numel() == n * 12,
-          "tsdf_integrate_: mats must be a contiguous CPU float32 tensor [T,12]")
-    _need(isinstance(depths[0], torch.Tensor) and depths[0].dim() >= 2, "tsdf_integrate_: depth maps must be [H,W] (leading 1s allowed)")
-    H, W = depths[0].shape[-2:]
-    _maps(depths, "depth map", H, W)
-    _maps(confs, "confidence map", H, W)
-    for t in depths + confs:
-        _need(t.device == volume.device, "tsdf_integrate_: a map is on %s but the volume on %s" % (t.device, volume.device))
-    d = N.TsdfIntegrateDesc()
-    d.Z, d.Y, d.X, d.T, d.H, d.W = Z, Y, X, n, H, W
-    d.weighted, d.no_skip = int(bool(weighted)), int(bool(no_skip))
-    d.trunc, d.z_near, d.conf_min, d.w_max = float(trunc), float(z_near), float(conf_min), float(w_max)
-    d.tsdf, d.weight = volume.data_ptr(), volume.data_ptr() + 4 * Z * Y * X
-    flat = mats.reshape(-1).tolist()
-    for t in range(n):
-        d.depth[t] = depths[t].data_ptr()
-        d.conf[t] = confs[t].data_ptr() if confs else None
-        for i in range(12):
-            d.mats[t][i] = flat[t * 12 + i]
-    with torch.cuda.device(volume.device):
-        N.check(N.lib().estd_tsdf_integrate(ctypes.byref(d), _stream()), "estd_tsdf_integrate")
-    return volume
-
-
-def tsdf_extract_points(volume, voxel_size, origin, w_min, capacity):
-    """Zero crossings of ``volume`` [2,Z,Y,X] -> (count [1] int64 on the device: the TOTAL number of crossings, xyz [capacity,3],
-    normal [capacity,3], weight [capacity], edge [capacity] int64); ``capacity`` 0 counts only.  ``origin``: CPU float32 [3]."""
-    if _use_torch():
-        return T().tsdf_extract_points(volume, float(voxel_size), origin, float(w_min), int(capacity))
-    _need(isinstance(volume, torch.Tensor) and volume.dim() == 4 and volume.shape[0] == 2, "tsdf_extract_points: volume must be [2,Z,Y,X] (D plane, weight plane)")
-    _chk(volume, "volume")
-    Z, Y, X = volume.shape[1:]
-    _need(X % 4 == 0, "tsdf_extract_points: X must be a multiple of 4, got %d" % X)
-    _need(capacity >= 0, "tsdf_extract_points: capacity must not be negative")
-    _need(isinstance(origin, torch.Tensor) and not origin.is_cuda and origin.dtype == torch.float32 and origin.is_contiguous() and origin.numel() == 3,
-          "tsdf_extract_points: origin must be a contiguous CPU float32 tensor [3]")
-    dev = volume.device
-    with torch.cuda.device(dev):
-        count = torch.zeros(1, device=dev, dtype=torch.int64)
-        xyz, normal = torch.empty((capacity, 3), device=dev), torch.empty((capacity, 3), device=dev)
-        weight, edge = torch.empty(capacity, device=dev), torch.empty(capacity, device=dev, dtype=torch.int64)
-        org = (ctypes.c_float * 3)(*origin.tolist())
-        pp = (lambda t: _p(t)) if capacity else (lambda t: None)
-        N.check(N.lib().estd_tsdf_extract_points(_p(volume), ctypes.c_void_p(volume.data_ptr() + 4 * Z * Y * X), Z, Y, X, float(voxel_size), org,
-                                                 float(w_min), _p(count), int(capacity), pp(xyz), pp(normal), pp(weight), pp(edge), _stream()),
-                "estd_tsdf_extract_points")
-    return count, xyz, normal, weight, edge
-
-
-def tsdf_raycast(volume, mat, H, W, t_min, dt, n_steps, w_min, stats=False):
-    """Ray-cast ``volume`` [2,Z,Y,X] with the host matrix ``mat`` (CPU float32 [12], camera.tsdf_ray_matrix): ``n_steps`` samples per pixel at
-    z-depths t_min + k dt -> (depth [H,W], normal [H,W,3], weight [H,W]) on the volume's device; zeros where a ray finds no surface.
-    ``stats=True`` (measurement only) appends an int32 [H,W,2] tensor: samples whose weights / whose D values were read.  The contract
-    is spelled out in include/estd_hip.h (csrc/tsdf_raycast.hip)."""
-    H, W, n_steps, t_min, dt, w_min = int(H), int(W), int(n_steps), float(t_min), float(dt), float(w_min)
-    if _use_torch():
-        depth, normal, weight, st = T().tsdf_raycast(volume, mat, H, W, t_min, dt, n_steps, w_min, bool(stats))
-        return (depth, normal, weight, st) if stats else (depth, normal, weight)
-    _need(isinstance(volume, torch.Tensor) and volume.dim() == 4 and volume.shape[0] == 2, "tsdf_raycast: volume must be [2,Z,Y,X] (D plane, weight plane)")
-    _chk(volume, "volume")
-    Z, Y, X = volume.shape[1:]
-    _need(X % 4 == 0, "tsdf_raycast: X must be a multiple of 4, got %d" % X)
-    _need(isinstance(mat, torch.Tensor) and not mat.is_cuda and mat.dtype == torch.float32 and mat.is_contiguous() and mat.numel() == 12,
-          "tsdf_raycast: mat must be a contiguous CPU float32 tensor [12] (3x4 row-major)")
-    _need(H > 0 and W > 0 and H * W <= 0x7fffffff, "tsdf_raycast: the image size must be positive (and H * W < 2^31), got %d x %d" % (H, W))
-    _need(0 < n_steps <= 1 << 24, "tsdf_raycast: n_steps must be in 1..2^24, got %d" % n_steps)
-    _need(math.isfinite(dt) and ctypes.c_float(dt).value > 0, "tsdf_raycast: dt must be positive and finite, got %r" % dt)
-    _need(math.isfinite(t_min) and t_min >= 0, "tsdf_raycast: t_min must be finite and not negative, got %r" % t_min)
-    _need(w_min == w_min, "tsdf_raycast: w_min must not be NaN")
-    dev = volume.device
-    with torch.cuda.device(dev):
-        depth, normal, weight = torch.empty((H, W), device=dev), torch.empty((H, W, 3), device=dev), torch.empty((H, W), device=dev)
-        st = torch.empty((H, W, 2), device=dev, dtype=torch.int32) if stats else None
-        d = N.TsdfRaycastDesc()
-        d.Z, d.Y, d.X, d.H, d.W, d.n_steps = Z, Y, X, H, W, n_steps
-        d.t_min, d.dt, d.w_min = t_min, dt, w_min
-        d.tsdf, d.weight = volume.data_ptr(), volume.data_ptr() + 4 * Z * Y * X
-        d.depth, d.normal, d.out_weight = depth.data_ptr(), normal.data_ptr(), weight.data_ptr()
-        d.stats = st.data_ptr() if stats else None
-        for i, v in enumerate(mat.reshape(-1).tolist()):
-            d.mat[i] = v
-        N.check(N.lib().estd_tsdf_raycast(ctypes.byref(d), _stream()), "estd_tsdf_raycast")
-    return (depth, normal, weight, st) if stats else (depth, normal, weight)
-
-
-# ---------------------------------------------------------------------------------- TSDF colour (csrc/tsdf.hip, csrc/tsdf_raycast.hip)
-def _color_planes(color, volume, op):
-    _need(isinstance(color, torch.Tensor) and color.dim() == 4 and color.shape[0] == 3 and tuple(color.shape[1:]) == tuple(volume.shape[1:]),
-          "%s: color must be [3,Z,Y,X] with the volume's Z, Y, X" % op)
-    _chk(color, "color")
-    _need(color.device == volume.device, "%s: color is on %s but the volume on %s" % (op, color.device, volume.device))
+    return _tsdf_integrate("tsdf_integrate_", volume, None, depths, confs, None, mats, trunc, z_near, conf_min, weighted, w_max, no_skip)
 
 
 def tsdf_integrate_color_(volume, color, depths, confs, images, mats, trunc, z_near, conf_min, weighted, w_max, no_skip=False):
@@ -1112,43 +1112,72 @@ def tsdf_integrate_color_(volume, color, depths, confs, images, mats, trunc, z_n
     if _use_torch():
         return T().tsdf_integrate_color_(volume, color, depths, confs, images, mats, float(trunc), float(z_near), float(conf_min), bool(weighted),
                                          float(w_max), bool(no_skip))
-    _need(isinstance(volume, torch.Tensor) and volume.dim() == 4 and volume.shape[0] == 2, "tsdf_integrate_color_: volume must be [2,Z,Y,X] (D plane, weight plane)")
-    _chk(volume, "volume")
-    _color_planes(color, volume, "tsdf_integrate_color_")
-    Z, Y, X = volume.shape[1:]
-    _need(X % 4 == 0, "tsdf_integrate_color_: X must be a multiple of 4, got %d" % X)
-    n = len(depths)
-    _need(1 <= n <= TSDF_MAX_FRAMES, "tsdf_integrate_color_: 1..%d frames per call, got %d" % (TSDF_MAX_FRAMES, n))
-    _need(len(confs) in (0, n), "tsdf_integrate_color_: one confidence map per depth map (or none)")
-    _need(len(images) == n, "tsdf_integrate_color_: one image per depth map, got %d for %d" % (len(images), n))
-    _need(not weighted or confs, "tsdf_integrate_color_: weighted fusion needs confidence maps")
-    _need(isinstance(mats, torch.Tensor) and not mats.is_cuda and mats.dtype == torch.float32 and mats.is_contiguous() and mats.numel() == n * 12,
-          "tsdf_integrate_color_: mats must be a contiguous CPU float32 tensor [T,12]")
-    _need(isinstance(depths[0], torch.Tensor) and depths[0].dim() >= 2, "tsdf_integrate_color_: depth maps must be [H,W] (leading 1s allowed)")
-    H, W = depths[0].shape[-2:]
-    _maps(depths, "depth map", H, W)
-    _maps(confs, "confidence map", H, W)
-    for i, t in enumerate(images):
-        _chk(t, "image %d" % i)
-        _need(t.dim() >= 3 and tuple(t.shape[-3:]) == (3, H, W) and t.numel() == 3 * H * W, "tsdf_integrate_color_: image %d must be [3,%d,%d], got %s"
-              % (i, H, W, tuple(t.shape)))
-    for t in depths + confs + images:
-        _need(t.device == volume.device, "tsdf_integrate_color_: a map is on %s but the volume on %s" % (t.device, volume.device))
-    d = N.TsdfIntegrateColorDesc()
-    d.Z, d.Y, d.X, d.T, d.H, d.W = Z, Y, X, n, H, W
-    d.weighted, d.no_skip = int(bool(weighted)), int(bool(no_skip))
-    d.trunc, d.z_near, d.conf_min, d.w_max = float(trunc), float(z_near), float(conf_min), float(w_max)
-    d.tsdf, d.weight, d.color = volume.data_ptr(), volume.data_ptr() + 4 * Z * Y * X, color.data_ptr()
-    flat = mats.reshape(-1).tolist()
-    for t in range(n):
-        d.depth[t] = depths[t].data_ptr()
-        d.conf[t] = confs[t].data_ptr() if confs else None
-        d.image[t] = images[t].data_ptr()
-        for i in range(12):
-            d.mats[t][i] = flat[t * 12 + i]
-    with torch.cuda.device(volume.device):
-        N.check(N.lib().estd_tsdf_integrate_color(ctypes.byref(d), _stream()), "estd_tsdf_integrate_color")
-    return volume
+    _need(color is not None, "tsdf_integrate_color_: color must be a tensor")
+    return _tsdf_integrate("tsdf_integrate_color_", volume, color, depths, confs, images, mats, trunc, z_near, conf_min, weighted, w_max, no_skip)
+
+
+def tsdf_extract_points(volume, voxel_size, origin, w_min, capacity):
+    """Zero crossings of ``volume`` [2,Z,Y,X] -> (count [1] int64 on the device: the TOTAL number of crossings, xyz [capacity,3],
+    normal [capacity,3], weight [capacity], edge [capacity] int64); ``capacity`` 0 counts only.  ``origin``: CPU float32 [3]."""
+    if _use_torch():
+        return T().tsdf_extract_points(volume, float(voxel_size), origin, float(w_min), int(capacity))
+    Z, Y, X, weight = _volume(volume, "tsdf_extract_points")
+    _need(capacity >= 0, "tsdf_extract_points: capacity must not be negative")
+    org = (ctypes.c_float * 3)(*_host_values(origin, 3, "tsdf_extract_points", "origin", "[3]"))
+    dev = volume.device
+    with torch.cuda.device(dev):
+        count = torch.zeros(1, device=dev, dtype=torch.int64)
+        xyz, normal = torch.empty((capacity, 3), device=dev), torch.empty((capacity, 3), device=dev)
+        weight_out, edge = torch.empty(capacity, device=dev), torch.empty(capacity, device=dev, dtype=torch.int64)
+        pp = (lambda t: _p(t)) if capacity else (lambda t: None)
+        N.check(N.lib().estd_tsdf_extract_points(_p(volume), ctypes.c_void_p(weight), Z, Y, X, float(voxel_size), org, float(w_min), _p(count),
+                                                 int(capacity), pp(xyz), pp(normal), pp(weight_out), pp(edge), _stream()),
+                "estd_tsdf_extract_points")
+    return count, xyz, normal, weight_out, edge
+
+
+def _tsdf_raycast(op, volume, color, mat, H, W, t_min, dt, n_steps, w_min, stats):
+    """tsdf_raycast (``color`` None) and tsdf_raycast_color under the ctypes binding -> (depth, normal, weight, stats or None, colour map or
+    None).  n_steps is in 1..2^24, dt must be positive and finite as fp32, t_min finite and not negative, w_min not NaN."""
+    Z, Y, X, weight = _volume(volume, op)
+    m = _host_values(mat, 12, op, "mat", "[12] (3x4 row-major)")
+    _map_size(H, W, op, "the image")
+    _need(0 < n_steps <= 1 << 24, "%s: n_steps must be in 1..2^24, got %d" % (op, n_steps))
+    _positive(dt, op, "dt")
+    _not_negative(t_min, op, "t_min")
+    _not_nan(w_min, op, "w_min")
+    dev = volume.device
+    with torch.cuda.device(dev):
+        depth, normal, out_weight = torch.empty((H, W), device=dev), torch.empty((H, W, 3), device=dev), torch.empty((H, W), device=dev)
+        st = torch.empty((H, W, 2), device=dev, dtype=torch.int32) if stats else None
+        d = N.TsdfRaycastDesc() if color is None else N.TsdfRaycastColorDesc()
+        d.Z, d.Y, d.X, d.H, d.W, d.n_steps = Z, Y, X, H, W, n_steps
+        d.t_min, d.dt, d.w_min = t_min, dt, w_min
+        d.tsdf, d.weight = volume.data_ptr(), weight
+        d.depth, d.normal, d.out_weight = depth.data_ptr(), normal.data_ptr(), out_weight.data_ptr()
+        d.stats = st.data_ptr() if stats else None
+        d.mat[:] = m
+        launch, what, rgb = N.lib().estd_tsdf_raycast, "estd_tsdf_raycast", None
+        if color is not None:
+            _color_planes(color, volume, op)
+            rgb = torch.empty((H, W, 3), device=dev)
+            d.color, d.out_color = color.data_ptr(), rgb.data_ptr()
+            launch, what = N.lib().estd_tsdf_raycast_color, "estd_tsdf_raycast_color"
+        N.check(launch(ctypes.byref(d), _stream()), what)
+    return depth, normal, out_weight, st, rgb
+
+
+def tsdf_raycast(volume, mat, H, W, t_min, dt, n_steps, w_min, stats=False):
+    """Ray-cast ``volume`` [2,Z,Y,X] with the host matrix ``mat`` (CPU float32 [12], camera.tsdf_ray_matrix): ``n_steps`` samples per pixel at
+    z-depths t_min + k dt -> (depth [H,W], normal [H,W,3], weight [H,W]) on the volume's device; zeros where a ray finds no surface.
+    ``stats=True`` (measurement only) appends an int32 [H,W,2] tensor: samples whose weights / whose D values were read.  The contract
+    is spelled out in include/estd_hip.h (csrc/tsdf_raycast.hip)."""
+    H, W, n_steps, t_min, dt, w_min = int(H), int(W), int(n_steps), float(t_min), float(dt), float(w_min)
+    if _use_torch():
+        out = T().tsdf_raycast(volume, mat, H, W, t_min, dt, n_steps, w_min, bool(stats))
+    else:
+        out = _tsdf_raycast("tsdf_raycast", volume, None, mat, H, W, t_min, dt, n_steps, w_min, stats)
+    return tuple(out[:4 if stats else 3])
 
 
 def tsdf_edge_colors(volume, color, edge):
@@ -1156,13 +1185,9 @@ def tsdf_edge_colors(volume, color, edge):
     -> [N,3] on the device; an id outside the volume gives zeros (include/estd_hip.h, estd_tsdf_edge_colors)."""
     if _use_torch():
         return T().tsdf_edge_colors(volume, color, edge)
-    _need(isinstance(volume, torch.Tensor) and volume.dim() == 4 and volume.shape[0] == 2, "tsdf_edge_colors: volume must be [2,Z,Y,X] (D plane, weight plane)")
-    _chk(volume, "volume")
+    Z, Y, X, _ = _volume(volume, "tsdf_edge_colors")
     _color_planes(color, volume, "tsdf_edge_colors")
-    Z, Y, X = volume.shape[1:]
-    _need(X % 4 == 0, "tsdf_edge_colors: X must be a multiple of 4, got %d" % X)
-    _need(isinstance(edge, torch.Tensor) and edge.dim() == 1 and edge.dtype == torch.int64 and edge.is_contiguous() and edge.device == volume.device,
-          "tsdf_edge_colors: edge must be a contiguous int64 tensor [N] on the volume's device")
+    _ivec(edge, "tsdf_edge_colors", "edge", volume.device)
     n = edge.shape[0]
     with torch.cuda.device(volume.device):
         out = torch.empty((n, 3), device=volume.device)
@@ -1178,36 +1203,13 @@ def tsdf_raycast_color(volume, color, mat, H, W, t_min, dt, n_steps, w_min):
     H, W, n_steps, t_min, dt, w_min = int(H), int(W), int(n_steps), float(t_min), float(dt), float(w_min)
     if _use_torch():
         return tuple(T().tsdf_raycast_color(volume, color, mat, H, W, t_min, dt, n_steps, w_min))
-    _need(isinstance(volume, torch.Tensor) and volume.dim() == 4 and volume.shape[0] == 2, "tsdf_raycast_color: volume must be [2,Z,Y,X] (D plane, weight plane)")
-    _chk(volume, "volume")
-    _color_planes(color, volume, "tsdf_raycast_color")
-    Z, Y, X = volume.shape[1:]
-    _need(X % 4 == 0, "tsdf_raycast_color: X must be a multiple of 4, got %d" % X)
-    _need(isinstance(mat, torch.Tensor) and not mat.is_cuda and mat.dtype == torch.float32 and mat.is_contiguous() and mat.numel() == 12,
-          "tsdf_raycast_color: mat must be a contiguous CPU float32 tensor [12] (3x4 row-major)")
-    _need(H > 0 and W > 0 and H * W <= 0x7fffffff, "tsdf_raycast_color: the image size must be positive (and H * W < 2^31), got %d x %d" % (H, W))
-    _need(0 < n_steps <= 1 << 24, "tsdf_raycast_color: n_steps must be in 1..2^24, got %d" % n_steps)
-    _need(math.isfinite(dt) and ctypes.c_float(dt).value > 0, "tsdf_raycast_color: dt must be positive and finite, got %r" % dt)
-    _need(math.isfinite(t_min) and t_min >= 0, "tsdf_raycast_color: t_min must be finite and not negative, got %r" % t_min)
-    _need(w_min == w_min, "tsdf_raycast_color: w_min must not be NaN")
-    dev = volume.device
-    with torch.cuda.device(dev):
-        depth, normal, weight = torch.empty((H, W), device=dev), torch.empty((H, W, 3), device=dev), torch.empty((H, W), device=dev)
-        rgb = torch.empty((H, W, 3), device=dev)
-        d = N.TsdfRaycastColorDesc()
-        d.Z, d.Y, d.X, d.H, d.W, d.n_steps = Z, Y, X, H, W, n_steps
-        d.t_min, d.dt, d.w_min = t_min, dt, w_min
-        d.tsdf, d.weight, d.color = volume.data_ptr(), volume.data_ptr() + 4 * Z * Y * X, color.data_ptr()
-        d.depth, d.normal, d.out_weight, d.out_color = depth.data_ptr(), normal.data_ptr(), weight.data_ptr(), rgb.data_ptr()
-        d.stats = None
-        for i, v in enumerate(mat.reshape(-1).tolist()):
-            d.mat[i] = v
-        N.check(N.lib().estd_tsdf_raycast_color(ctypes.byref(d), _stream()), "estd_tsdf_raycast_color")
-    return depth, normal, weight, rgb
+    _need(color is not None, "tsdf_raycast_color: color must be a tensor")
+    out = _tsdf_raycast("tsdf_raycast_color", volume, color, mat, H, W, t_min, dt, n_steps, w_min, False)
+    return out[:3] + out[4:]
 
 
 # ---------------------------------------------------------------------------------- cross-view consistency (csrc/depth_consistency.hip)
-CONSISTENCY_MAX_SOURCES = 8     # ESTD_CONSISTENCY_MAX_SOURCES (include/estd_hip.h)
+CONSISTENCY_MAX_SOURCES = N.CONSISTENCY_MAX_SOURCES
 
 
 def depth_consistency(target, sources, mats, px_max, rel_max, z_near):
@@ -1220,25 +1222,18 @@ def depth_consistency(target, sources, mats, px_max, rel_max, z_near):
     px_max, rel_max, z_near = float(px_max), float(rel_max), float(z_near)
     if _use_torch():
         return tuple(T().depth_consistency(target, sources, mats, px_max, rel_max, z_near))
-    _chk(target, "target")
-    _need(target.dim() >= 2 and target.numel() == target.shape[-2] * target.shape[-1], "depth_consistency: the target must be [H,W] (leading 1s allowed)")
-    H, W = target.shape[-2:]
-    _need(H >= 2 and W >= 2 and H * W <= 0x7fffffff, "depth_consistency: maps must be at least 2 x 2 (and H * W < 2^31), got %d x %d" % (H, W))
+    op = "depth_consistency"
+    H, W = _map(target, (-1, -1), op, "target")
+    _map_size(H, W, op, "maps", least=2)
     S = len(sources)
     _need(1 <= S <= CONSISTENCY_MAX_SOURCES, "depth_consistency: 1..%d sources per call, got %d" % (CONSISTENCY_MAX_SOURCES, S))
-    _need(isinstance(mats, torch.Tensor) and not mats.is_cuda and mats.dtype == torch.float32 and mats.is_contiguous() and mats.numel() == S * 24,
-          "depth_consistency: mats must be a contiguous CPU float32 tensor [S,2,12]")
-    _need(math.isfinite(px_max) and ctypes.c_float(px_max).value > 0, "depth_consistency: px_max must be positive and finite, got %r" % px_max)
-    _need(math.isfinite(rel_max) and ctypes.c_float(rel_max).value > 0, "depth_consistency: rel_max must be positive and finite, got %r" % rel_max)
-    _need(math.isfinite(z_near) and z_near >= 0, "depth_consistency: z_near must be finite and not negative, got %r" % z_near)
-    for i, t in enumerate(sources):
-        _chk(t, "source map %d" % i)
-        _need(t.dim() >= 2 and tuple(t.shape[-2:]) == (H, W) and t.numel() == H * W, "depth_consistency: source %d must be [%d,%d], got %s"
-              % (i, H, W, tuple(t.shape)))
-        _need(t.device == target.device, "depth_consistency: source %d is on %s but the target on %s" % (i, t.device, target.device))
-    flat = mats.reshape(-1).tolist()
-    _need(all(math.isfinite(v) for v in flat), "depth_consistency: mats holds a value that is not finite")
+    flat = _host_values(mats, S * 24, op, "mats", "[S,2,12]", finite=True)
+    _positive(px_max, op, "px_max")
+    _positive(rel_max, op, "rel_max")
+    _not_negative(z_near, op, "z_near")
     dev = target.device
+    for i, t in enumerate(sources):
+        _map(t, (H, W), op, "source %d" % i, dev)
     with torch.cuda.device(dev):
         views, visible, depth, rel_err = (torch.empty((H, W), device=dev) for _ in range(4))
         d = N.DepthConsistencyDesc()
@@ -1248,8 +1243,7 @@ def depth_consistency(target, sources, mats, px_max, rel_max, z_near):
         d.views, d.visible, d.depth, d.rel_err = views.data_ptr(), visible.data_ptr(), depth.data_ptr(), rel_err.data_ptr()
         for s in range(S):
             d.source[s] = sources[s].data_ptr()
-            for i in range(24):
-                d.mats[s][i // 12][i % 12] = flat[s * 24 + i]
+            d.mats[s][0][:], d.mats[s][1][:] = flat[s * 24:s * 24 + 12], flat[s * 24 + 12:s * 24 + 24]
         N.check(N.lib().estd_depth_consistency(ctypes.byref(d), _stream()), "estd_depth_consistency")
     return views, visible, depth, rel_err
 
@@ -1261,18 +1255,16 @@ CLOUD_MAX_CELLS = 1 << 24       # ESTD_CLOUD_MAX_CELLS
 CLOUD_MAX_ATTRS = 6             # ESTD_CLOUD_MAX_ATTRS
 
 
-def _cloud(t, name, op, cols=3):
+def _cloud(t, op, name, cols=3):
     _chk(t, name)
     _need(t.dim() == 2 and t.shape[1] == cols and t.shape[0] <= 0x7fffffff, "%s: %s must be [n,%d] with n < 2^31, got %s" % (op, name, cols, tuple(t.shape)))
 
 
 def _cloud_grid(lo, cell, dims, op, max_dim):
-    _need(isinstance(lo, torch.Tensor) and not lo.is_cuda and lo.dtype == torch.float32 and lo.is_contiguous() and lo.numel() == 3,
-          "%s: lo must be a contiguous CPU float32 tensor [3]" % op)
-    lo3 = lo.tolist()
-    _need(all(math.isfinite(v) for v in lo3), "%s: lo holds a value that is not finite" % op)
-    c = ctypes.c_float(cell).value if math.isfinite(cell) else float("nan")
-    _need(c > 0 and math.isfinite(c) and math.isfinite(ctypes.c_float(1.0 / c).value), "%s: cell must be positive and finite in fp32 (and its reciprocal too), got %r" % (op, cell))
+    lo3 = _host_values(lo, 3, op, "lo", "[3]", finite=True)
+    _positive(cell, op, "cell")
+    c = ctypes.c_float(cell).value
+    _need(math.isfinite(c) and math.isfinite(ctypes.c_float(1.0 / c).value), "%s: cell must be finite in fp32 (and its reciprocal too), got %r" % (op, cell))
     dims = tuple(int(v) for v in dims)
     _need(len(dims) == 3 and all(1 <= v <= max_dim for v in dims), "%s: dims must be three sizes in 1..%d, got %r" % (op, max_dim, dims))
     return lo3, dims
@@ -1284,7 +1276,7 @@ def cloud_cell_keys(points, lo, cell, dims):
     cell, dims = float(cell), [int(v) for v in dims]
     if _use_torch():
         return T().cloud_cell_keys(points, lo, cell, dims)
-    _cloud(points, "points", "cloud_cell_keys")
+    _cloud(points, "cloud_cell_keys", "points")
     lo3, dims = _cloud_grid(lo, cell, dims, "cloud_cell_keys", CLOUD_KEY_MAX_DIM)
     n = points.shape[0]
     with torch.cuda.device(points.device):
@@ -1304,21 +1296,17 @@ def cloud_nearest(query, order, records, cell_start, lo, cell, dims, max_dist, s
     if _use_torch():
         dist, index, st = T().cloud_nearest(query, order, records, cell_start, lo, cell, dims, max_dist, bool(stats))
         return (dist, index, st) if stats else (dist, index)
-    _cloud(query, "query", "cloud_nearest")
-    _cloud(records, "records", "cloud_nearest", cols=4)
-    M, n = query.shape[0], records.shape[0]
-    _need(isinstance(order, torch.Tensor) and order.dim() == 1 and order.dtype == torch.int64 and order.is_contiguous() and order.shape[0] == M
-          and order.device == query.device, "cloud_nearest: order must be a contiguous int64 tensor [M] on the query's device")
-    _need(records.device == query.device, "cloud_nearest: records are on %s but the query on %s" % (records.device, query.device))
-    _need(math.isfinite(max_dist) and ctypes.c_float(max_dist).value > 0 and math.isfinite(ctypes.c_float(ctypes.c_float(max_dist).value ** 2).value),
-          "cloud_nearest: max_dist must be positive and finite (and its square too), got %r" % max_dist)
-    lo3, dims = _cloud_grid(lo, cell, dims, "cloud_nearest", CLOUD_MAX_DIM)
+    op = "cloud_nearest"
+    _cloud(query, op, "query")
+    _cloud(records, op, "records", cols=4)
+    M, n, dev = query.shape[0], records.shape[0], query.device
+    _ivec(order, op, "order", dev, M)
+    _need(records.device == dev, "cloud_nearest: records are on %s but the query on %s" % (records.device, dev))
+    _positive_square(max_dist, op, "max_dist")
+    lo3, dims = _cloud_grid(lo, cell, dims, op, CLOUD_MAX_DIM)
     cells = dims[0] * dims[1] * dims[2]
     _need(cells <= CLOUD_MAX_CELLS, "cloud_nearest: %d cells, at most %d" % (cells, CLOUD_MAX_CELLS))
-    _need(isinstance(cell_start, torch.Tensor) and cell_start.dim() == 1 and cell_start.dtype == torch.int32 and cell_start.is_contiguous()
-          and cell_start.shape[0] == cells + 1 and cell_start.device == query.device,
-          "cloud_nearest: cell_start must be a contiguous int32 tensor [%d] (cells + 1) on the query's device" % (cells + 1))
-    dev = query.device
+    _ivec(cell_start, op, "cell_start (cells + 1)", dev, cells + 1, torch.int32)
     with torch.cuda.device(dev):
         dist, index = torch.empty(M, device=dev), torch.empty(M, device=dev, dtype=torch.int64)
         st = torch.empty(M, device=dev, dtype=torch.int32) if stats else None
@@ -1329,8 +1317,7 @@ def cloud_nearest(query, order, records, cell_start, lo, cell, dims, max_dist, s
             d.dist, d.index = dist.data_ptr(), index.data_ptr()
             d.stats = st.data_ptr() if stats else None
             d.cell, d.max_dist = cell, max_dist
-            for j in range(3):
-                d.lo[j], d.dims[j] = lo3[j], dims[j]
+            d.lo[:], d.dims[:] = lo3, dims
             N.check(N.lib().estd_cloud_nearest(ctypes.byref(d), _stream()), "estd_cloud_nearest")
     return (dist, index, st) if stats else (dist, index)
 
@@ -1343,20 +1330,19 @@ def cloud_cell_centroids(points, attrs, order, segments):
         _need(isinstance(points, torch.Tensor), "points must be a tensor")
         pts, att = T().cloud_cell_centroids(points, attrs if attrs is not None else points.new_empty((0, 0)), order, segments)      # C = 0: no attributes
         return pts, (att if attrs is not None else None)
-    _cloud(points, "points", "cloud_cell_centroids")
-    n = points.shape[0]
+    op = "cloud_cell_centroids"
+    _cloud(points, op, "points")
+    n, dev = points.shape[0], points.device
     C = 0
     if attrs is not None:
         _chk(attrs, "attrs")
-        _need(attrs.dim() == 2 and attrs.shape[0] == n and attrs.shape[1] <= CLOUD_MAX_ATTRS and attrs.device == points.device,
+        _need(attrs.dim() == 2 and attrs.shape[0] == n and attrs.shape[1] <= CLOUD_MAX_ATTRS and attrs.device == dev,
               "cloud_cell_centroids: attrs must be [n,C] with C <= %d on the points' device, got %s" % (CLOUD_MAX_ATTRS, tuple(attrs.shape)))
         C = attrs.shape[1]
-    for t, name, size in ((order, "order", n), (segments, "segments", None)):
-        _need(isinstance(t, torch.Tensor) and t.dim() == 1 and t.dtype == torch.int64 and t.is_contiguous() and t.device == points.device
-              and (size is None or t.shape[0] == size), "cloud_cell_centroids: %s must be a contiguous int64 vector on the points' device" % name)
+    _ivec(order, op, "order", dev, n)
+    _ivec(segments, op, "segments", dev)
     _need(1 <= segments.shape[0] <= n + 1, "cloud_cell_centroids: segments must be [K + 1] with K <= n, got %d for n = %d" % (segments.shape[0], n))
     K = segments.shape[0] - 1
-    dev = points.device
     with torch.cuda.device(dev):
         out = torch.empty((K, 3), device=dev)
         out_attrs = torch.empty((K, C), device=dev) if attrs is not None else None
@@ -1380,33 +1366,19 @@ def frame_align(depth, conf, m_depth, m_normal, mats, dist_max, z_near, conf_min
     dist_max, z_near, conf_min = float(dist_max), float(z_near), float(conf_min)
     if _use_torch():
         return tuple(T().frame_align(depth, conf, m_depth, m_normal, mats, dist_max, z_near, conf_min))
-    _chk(depth, "depth")
-    _need(depth.dim() >= 2 and depth.numel() == depth.shape[-2] * depth.shape[-1], "frame_align: depth must be [H,W] (leading 1s allowed)")
-    H, W = depth.shape[-2:]
-    _need(H > 0 and W > 0 and H * W <= 0x7fffffff, "frame_align: the map size must be positive (and H * W < 2^31), got %d x %d" % (H, W))
-    if conf is not None:
-        _chk(conf, "conf")
-        _need(conf.dim() >= 2 and tuple(conf.shape[-2:]) == (H, W) and conf.numel() == H * W, "frame_align: conf must be [%d,%d], got %s" % (H, W, tuple(conf.shape)))
-    _chk(m_depth, "m_depth")
-    _need(m_depth.dim() >= 2 and m_depth.numel() == m_depth.shape[-2] * m_depth.shape[-1], "frame_align: m_depth must be [Hm,Wm] (leading 1s allowed)")
-    Hm, Wm = m_depth.shape[-2:]
-    _need(Hm > 0 and Wm > 0 and Hm * Wm <= 0x7fffffff, "frame_align: m_depth must have a positive size (and Hm * Wm < 2^31), got %d x %d" % (Hm, Wm))
-    _chk(m_normal, "m_normal")
-    _need(m_normal.dim() >= 3 and tuple(m_normal.shape[-3:]) == (Hm, Wm, 3) and m_normal.numel() == 3 * Hm * Wm,
-          "frame_align: m_normal must be [%d,%d,3], got %s" % (Hm, Wm, tuple(m_normal.shape)))
-    for t, name in ((conf, "conf"), (m_depth, "m_depth"), (m_normal, "m_normal")):
-        _need(t is None or t.device == depth.device, "frame_align: %s is on %s but the depth on %s" % (name, getattr(t, "device", None), depth.device))
-    _need(isinstance(mats, torch.Tensor) and not mats.is_cuda and mats.dtype == torch.float32 and mats.is_contiguous() and mats.numel() == 36,
-          "frame_align: mats must be a contiguous CPU float32 tensor [3,12] (L, Fm, Bm)")
-    d32 = ctypes.c_float(dist_max).value if math.isfinite(dist_max) else dist_max
-    d2 = ctypes.c_float(d32 * d32).value if math.isfinite(d32) else d32
-    _need(math.isfinite(dist_max) and d32 > 0 and math.isfinite(d2) and d2 > 0,
-          "frame_align: dist_max (and its square in fp32) must be positive and finite, got %r" % dist_max)
-    _need(math.isfinite(z_near) and z_near >= 0, "frame_align: z_near must be finite and not negative, got %r" % z_near)
-    _need(conf_min == conf_min, "frame_align: conf_min must not be NaN")
-    flat = mats.reshape(-1).tolist()
-    _need(all(math.isfinite(v) for v in flat), "frame_align: mats holds a value that is not finite")
+    op = "frame_align"
+    H, W = _map(depth, (-1, -1), op, "depth")
+    _map_size(H, W, op, "depth")
     dev = depth.device
+    if conf is not None:
+        _map(conf, (H, W), op, "conf", dev)
+    Hm, Wm = _map(m_depth, (-1, -1), op, "m_depth", dev)
+    _map_size(Hm, Wm, op, "m_depth")
+    _map(m_normal, (Hm, Wm, 3), op, "m_normal", dev)
+    flat = _host_values(mats, 36, op, "mats", "[3,12] (L, Fm, Bm)", finite=True)
+    _positive_square(dist_max, op, "dist_max", square_positive=True)
+    _not_negative(z_near, op, "z_near")
+    _not_nan(conf_min, op, "conf_min")
     with torch.cuda.device(dev):
         residual, match = torch.empty((H, W), device=dev), torch.empty((H, W), device=dev, dtype=torch.int32)
         sums = torch.empty((FRAME_ALIGN_SUMS,), device=dev, dtype=torch.float64)
@@ -1417,7 +1389,6 @@ def frame_align(depth, conf, m_depth, m_normal, mats, dist_max, z_near, conf_min
         d.depth, d.conf = depth.data_ptr(), conf.data_ptr() if conf is not None else None
         d.m_depth, d.m_normal = m_depth.data_ptr(), m_normal.data_ptr()
         d.residual, d.match, d.sums, d.partials = residual.data_ptr(), match.data_ptr(), sums.data_ptr(), partials.data_ptr()
-        for i in range(12):
-            d.L[i], d.Fm[i], d.Bm[i] = flat[i], flat[12 + i], flat[24 + i]
+        d.L[:], d.Fm[:], d.Bm[:] = flat[:12], flat[12:24], flat[24:]
         N.check(N.lib().estd_frame_align(ctypes.byref(d), _stream()), "estd_frame_align")
     return residual, match, sums

@@ -7,6 +7,8 @@ import subprocess
 
 import pytest
 
+from helpers import check_desc_layout
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -62,35 +64,14 @@ def test_argument_validation_without_gpu(libpath):
 
 def test_desc_struct_layout(libpath, tmp_path):
     """sizeof/offsetof of estd_conv3d_desc as the C compiler sees it == the ctypes mirror."""
-    from estdepth_amd import _native
-    src = tmp_path / "layout.c"
-    fields = [f[0] for f in _native.Conv3dDesc._fields_]
-    body = "\n".join('printf("%%zu\\n", offsetof(estd_conv3d_desc, %s));' % f for f in fields)
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "estd_hip.h"\nint main(){printf("%zu\\n", sizeof(estd_conv3d_desc));\n'
-                   + body + "\nreturn 0;}\n")
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    out = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert out[0] == ctypes.sizeof(_native.Conv3dDesc)
-    for f, off in zip(fields, out[1:]):
-        assert getattr(_native.Conv3dDesc, f).offset == off, f
+    from estdepth_amd import _native, ops
+    assert check_desc_layout(tmp_path, "estd_conv3d_desc", _native.Conv3dDesc, macros=["ESTD_MAX_ATTENTION_SOURCES"]) == [ops.MAX_ATTENTION_SOURCES]
 
 
 def test_conv1x1_desc_struct_layout(libpath, tmp_path):
     """sizeof/offsetof of estd_conv1x1_desc as the C compiler sees it == the ctypes mirror."""
     from estdepth_amd import _native
-    src = tmp_path / "layout1.c"
-    names = {"in_": "in"}
-    fields = [f[0] for f in _native.Conv1x1Desc._fields_]
-    body = "\n".join('printf("%%zu\\n", offsetof(estd_conv1x1_desc, %s));' % names.get(f, f) for f in fields)
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "estd_hip.h"\nint main(){printf("%zu\\n", sizeof(estd_conv1x1_desc));\n'
-                   + body + "\nreturn 0;}\n")
-    exe = tmp_path / "layout1"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    out = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert out[0] == ctypes.sizeof(_native.Conv1x1Desc)
-    for f, off in zip(fields, out[1:]):
-        assert getattr(_native.Conv1x1Desc, f).offset == off, f
+    check_desc_layout(tmp_path, "estd_conv1x1_desc", _native.Conv1x1Desc, renamed={"in_": "in"})
     assert _native.lib().estd_conv1x1_nhwc(None, None) == -1
     assert _native.lib().estd_conv1x1_nhwc(ctypes.byref(_native.Conv1x1Desc()), None) == -1
 
@@ -98,18 +79,7 @@ def test_conv1x1_desc_struct_layout(libpath, tmp_path):
 def test_conv2d_taps_desc_struct_layout(libpath, tmp_path):
     """sizeof/offsetof of estd_conv2d_taps_desc as the C compiler sees it == the ctypes mirror; NULL / empty descriptors are argument errors."""
     from estdepth_amd import _native
-    src = tmp_path / "layout2.c"
-    names = {"in_": "in"}
-    fields = [f[0] for f in _native.Conv2dTapsDesc._fields_]
-    body = "\n".join('printf("%%zu\\n", offsetof(estd_conv2d_taps_desc, %s));' % names.get(f, f) for f in fields)
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "estd_hip.h"\nint main(){printf("%zu\\n", sizeof(estd_conv2d_taps_desc));\n'
-                   + body + "\nreturn 0;}\n")
-    exe = tmp_path / "layout2"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    out = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert out[0] == ctypes.sizeof(_native.Conv2dTapsDesc)
-    for f, off in zip(fields, out[1:]):
-        assert getattr(_native.Conv2dTapsDesc, f).offset == off, f
+    check_desc_layout(tmp_path, "estd_conv2d_taps_desc", _native.Conv2dTapsDesc, renamed={"in_": "in"})
     assert _native.lib().estd_conv2d_taps_nhwc(None, None) == -1
     assert _native.lib().estd_conv2d_taps_nhwc(ctypes.byref(_native.Conv2dTapsDesc()), None) == -1
     assert _native.lib().estd_stem7x7s2_nhwc(None, None, None, None, None, 1, 8, 8, None) == -1

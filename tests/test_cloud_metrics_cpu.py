@@ -4,13 +4,13 @@ errors that need no device, the ABI and the compiler's resource account of the k
 import ctypes
 import importlib.util
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import cloud_metrics_ref as C
+from helpers import check_desc_layout
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -307,18 +307,10 @@ def test_entry_points_validate_before_launch(lib):
 
 def test_cloud_nearest_desc_struct_layout(lib, tmp_path):
     """sizeof/offsetof of estd_cloud_nearest_desc as the C compiler sees it == the ctypes mirror"""
-    from estdepth_amd import _native
-    fields = [f[0] for f in _native.CloudNearestDesc._fields_]
-    body = "\n".join('printf("%%zu\\n", offsetof(estd_cloud_nearest_desc, %s));' % f for f in fields)
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "estd_hip.h"\nint main(){printf("%zu\\n", sizeof(estd_cloud_nearest_desc));\n'
-                   + body + "\nreturn 0;}\n")
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    out = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert out[0] == ctypes.sizeof(_native.CloudNearestDesc)
-    for f, off in zip(fields, out[1:]):
-        assert getattr(_native.CloudNearestDesc, f).offset == off, f
+    from estdepth_amd import _native, ops
+    limits = check_desc_layout(tmp_path, "estd_cloud_nearest_desc", _native.CloudNearestDesc,
+                               macros=["ESTD_CLOUD_KEY_MAX_DIM", "ESTD_CLOUD_MAX_DIM", "ESTD_CLOUD_MAX_CELLS", "ESTD_CLOUD_MAX_ATTRS"])
+    assert limits == [ops.CLOUD_KEY_MAX_DIM, ops.CLOUD_MAX_DIM, ops.CLOUD_MAX_CELLS, ops.CLOUD_MAX_ATTRS]
 
 
 def test_cloud_kernels_use_no_scratch_and_spill_nothing():

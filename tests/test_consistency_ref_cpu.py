@@ -4,8 +4,6 @@ kernels that the comparison rejects, camera.consistency_matrices, the host layer
 replaced by the reference, the ESTD_ERR_* returns of estd_depth_consistency and the descriptor's layout against gcc."""
 import ctypes
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,8 +11,7 @@ import torch
 
 import consistency_ref as C
 import tsdf_ref as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from helpers import check_desc_layout
 
 
 def _dilate(mask, r):
@@ -340,17 +337,6 @@ def test_entry_point_validates_without_gpu():
 
 def test_desc_struct_layout(tmp_path):
     """sizeof / offsetof of estd_depth_consistency_desc as the C compiler sees it == the ctypes mirror"""
-    from estdepth_amd import _native
-    fields = [f[0] for f in _native.DepthConsistencyDesc._fields_]
-    body = "\n".join('printf("%%zu\\n", offsetof(estd_depth_consistency_desc, %s));' % f for f in fields)
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "estd_hip.h"\nint main(){printf("%zu\\n", sizeof(estd_depth_consistency_desc));\n'
-                   + body + '\nprintf("%d\\n", ESTD_CONSISTENCY_MAX_SOURCES);\nreturn 0;}\n')
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    out = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert out[0] == ctypes.sizeof(_native.DepthConsistencyDesc)
-    for f, off in zip(fields, out[1:]):
-        assert getattr(_native.DepthConsistencyDesc, f).offset == off, f
-    from estdepth_amd import ops
+    from estdepth_amd import _native, ops
+    out = check_desc_layout(tmp_path, "estd_depth_consistency_desc", _native.DepthConsistencyDesc, macros=["ESTD_CONSISTENCY_MAX_SOURCES"])
     assert out[-1] == ops.CONSISTENCY_MAX_SOURCES == 8

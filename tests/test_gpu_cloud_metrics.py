@@ -12,17 +12,12 @@ import torch
 
 import cloud_metrics_ref as C
 import tsdf_ref as R
+from helpers import _binding
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 BINDINGS = ["torch", "ctypes"]
 _REFS = {}
-
-
-def _binding(monkeypatch, name):
-    from estdepth_amd import ops
-    ops.T()
-    monkeypatch.setattr(ops, "BINDING", name)
 
 
 def _dev(a):

@@ -16,17 +16,12 @@ import torch
 
 import consistency_ref as C
 import tsdf_ref as R
+from helpers import _binding
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 NAMES = ("views", "visible", "depth", "rel_err")
 _REFS = {}
-
-
-def _binding(monkeypatch, name):
-    from estdepth_amd import ops
-    ops.T()
-    monkeypatch.setattr(ops, "BINDING", name)
 
 
 def _tensors(c):

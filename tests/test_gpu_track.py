@@ -18,16 +18,11 @@ from estdepth_amd import tracking  # noqa: F401 -- the feature under test: witho
 
 import track_ref as T
 import tsdf_ref as R
+from helpers import _binding
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 MARGIN = 1.25                # the semantic bar of the colour test (tsdf_color_ref.MEDIAN_FACTOR)
-
-
-def _binding(monkeypatch, name):
-    from estdepth_amd import ops
-    ops.T()
-    monkeypatch.setattr(ops, "BINDING", name)
 
 
 def _dev(a):

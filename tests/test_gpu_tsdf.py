@@ -11,15 +11,10 @@ import pytest
 import torch
 
 import tsdf_ref as R
+from helpers import _binding
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
-
-
-def _binding(monkeypatch, name):
-    from estdepth_amd import ops
-    ops.T()
-    monkeypatch.setattr(ops, "BINDING", name)
 
 
 def _volume(case, fill=None):

@@ -12,16 +12,11 @@ import torch
 import tsdf_color_ref as CR
 import tsdf_raycast_ref as RR
 import tsdf_ref as R
+from helpers import _binding
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 _CACHE = {}
-
-
-def _binding(monkeypatch, name):
-    from estdepth_amd import ops
-    ops.T()
-    monkeypatch.setattr(ops, "BINDING", name)
 
 
 def _volume(case, color=True, D0=None, C0=None):

@@ -17,17 +17,12 @@ import torch
 
 import tsdf_ref as R
 import tsdf_raycast_ref as RR
+from helpers import _binding
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 _FUSED = {}
 _REFS = {}
-
-
-def _binding(monkeypatch, name):
-    from estdepth_amd import ops
-    ops.T()
-    monkeypatch.setattr(ops, "BINDING", name)
 
 
 def _fused(name):

@@ -7,8 +7,6 @@ Figures of the numpy-fp32 stand-in against the reference (printed per case, pyte
 is the one-pixel map).  The convergence fixture: eigenvalues of A / count 0.0063 .. 1.03 (ratio 164, bar COND_FIXTURE = 1000); from a guess off
 by 9.8 mm and 0.50 degrees the float64 reference is within 1e-8 m and 1e-8 rad after 10 iterations (bar: a tenth of the perturbation)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,8 +16,8 @@ from estdepth_amd import tracking  # noqa: F401 -- the feature under test: witho
 
 import track_ref as T
 import tsdf_ref as R
+from helpers import check_desc_layout
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ALL_CASES = list(T.CASES) + ["tie", "full"]
 
 
@@ -322,15 +320,5 @@ def test_null_descriptor_and_sizes_beyond_2_31(lib):
 def test_descriptor_layout(lib, tmp_path):
     """sizeof / offsetof of estd_frame_align_desc as the C compiler sees it == the ctypes mirror; ESTD_FRAME_ALIGN_SUMS == the bindings'"""
     from estdepth_amd import _native, ops
-    fields = [f[0] for f in _native.FrameAlignDesc._fields_]
-    body = "\n".join('printf("%%zu\\n", offsetof(estd_frame_align_desc, %s));' % f for f in fields)
-    src = tmp_path / "layout_track.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "estd_hip.h"\nint main(){printf("%zu\\n", sizeof(estd_frame_align_desc));\n'
-                   + body + '\nprintf("%d\\n", ESTD_FRAME_ALIGN_SUMS);\nreturn 0;}\n')
-    exe = tmp_path / "layout_track"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    out = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert out[0] == ctypes.sizeof(_native.FrameAlignDesc)
-    for f, off in zip(fields, out[1:]):
-        assert getattr(_native.FrameAlignDesc, f).offset == off, f
+    out = check_desc_layout(tmp_path, "estd_frame_align_desc", _native.FrameAlignDesc, macros=["ESTD_FRAME_ALIGN_SUMS"])
     assert out[-1] == ops.FRAME_ALIGN_SUMS == T.N_SUMS == 29

@@ -6,8 +6,6 @@ Measured here (numpy fp32 stand-in): largest |C - C_ref| / (2^-24 A_c) 0.25 (unw
 ambiguous share 0.0026; median colour error of the float64 reference at its own points 0.43 ("t3") of 255, 4.3 with the images shifted
 by one pixel along u, 61 with two channels swapped."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,8 +14,7 @@ import torch
 import tsdf_color_ref as CR
 import tsdf_raycast_ref as RR
 import tsdf_ref as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from helpers import check_desc_layout
 
 
 def _stand_in(fx, D0, W0, C0, images=None):
@@ -165,16 +162,7 @@ def test_colour_desc_struct_layout(libpath, tmp_path, mirror, struct):
     prefix of the one with; NULL and empty descriptors are argument errors (no GPU needed)"""
     from estdepth_amd import _native
     cls = getattr(_native, mirror)
-    fields = [f[0] for f in cls._fields_]
-    body = "\n".join('printf("%%zu\\n", offsetof(%s, %s));' % (struct, f) for f in fields)
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "estd_hip.h"\nint main(){printf("%%zu\\n", sizeof(%s));\n' % struct + body + "\nreturn 0;}\n")
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    out = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert out[0] == ctypes.sizeof(cls)
-    for f, off in zip(fields, out[1:]):
-        assert getattr(cls, f).offset == off, f
+    check_desc_layout(tmp_path, struct, cls)
     plain = _native.TsdfIntegrateDesc if "Integrate" in mirror else _native.TsdfRaycastDesc
     for f in plain._fields_:
         assert getattr(plain, f[0]).offset == getattr(cls, f[0]).offset, f[0]

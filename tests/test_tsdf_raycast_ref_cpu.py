@@ -5,8 +5,6 @@ test applies, a plausible wrong kernel that the comparison rejects, render's arg
 the layout of its descriptor."""
 import ctypes
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,8 +12,7 @@ import torch
 
 import tsdf_ref as R
 import tsdf_raycast_ref as RR
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from helpers import check_desc_layout
 
 
 @functools.lru_cache(maxsize=3)
@@ -279,15 +276,5 @@ def test_entry_point_validates_without_gpu():
 def test_raycast_desc_struct_layout(tmp_path):
     """sizeof / offsetof of estd_tsdf_raycast_desc as the C compiler sees it == the ctypes mirror"""
     from estdepth_amd import _native
-    src = tmp_path / "layout.c"
-    fields = [f[0] for f in _native.TsdfRaycastDesc._fields_]
-    body = "\n".join('printf("%%zu\\n", offsetof(estd_tsdf_raycast_desc, %s));' % f for f in fields)
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "estd_hip.h"\nint main(){printf("%zu\\n", sizeof(estd_tsdf_raycast_desc));\n'
-                   + body + "\nreturn 0;}\n")
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    out = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert out[0] == ctypes.sizeof(_native.TsdfRaycastDesc)
-    for f, off in zip(fields, out[1:]):
-        assert getattr(_native.TsdfRaycastDesc, f).offset == off, f
+    check_desc_layout(tmp_path, "estd_tsdf_raycast_desc", _native.TsdfRaycastDesc)
     assert ctypes.sizeof(_native.TsdfRaycastDesc) == 40 + 48 + 48

@@ -2,16 +2,13 @@
 against closed forms, the ambiguous share of every GPU case's fixture, a numpy-fp32 evaluation through the very comparison the GPU test
 applies, the extraction reference on an analytic sphere, TSDFVolume's argument checks and the ESTD_ERR_ARG returns of both entry points."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import tsdf_ref as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from helpers import check_desc_layout
 
 
 def _mats(case):
@@ -294,16 +291,7 @@ def test_entry_points_validate_without_gpu():
 
 def test_tsdf_desc_struct_layout(tmp_path):
     """sizeof/offsetof of estd_tsdf_integrate_desc as the C compiler sees it == the ctypes mirror."""
-    from estdepth_amd import _native
-    src = tmp_path / "layout.c"
-    fields = [f[0] for f in _native.TsdfIntegrateDesc._fields_]
-    body = "\n".join('printf("%%zu\\n", offsetof(estd_tsdf_integrate_desc, %s));' % f for f in fields)
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "estd_hip.h"\nint main(){printf("%zu\\n", sizeof(estd_tsdf_integrate_desc));\n'
-                   + body + "\nreturn 0;}\n")
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    out = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert out[0] == ctypes.sizeof(_native.TsdfIntegrateDesc)
-    for f, off in zip(fields, out[1:]):
-        assert getattr(_native.TsdfIntegrateDesc, f).offset == off, f
+    from estdepth_amd import _native, ops
+    frames, = check_desc_layout(tmp_path, "estd_tsdf_integrate_desc", _native.TsdfIntegrateDesc, macros=["ESTD_TSDF_MAX_FRAMES"])
+    assert frames == ops.TSDF_MAX_FRAMES == _native.TSDF_MAX_FRAMES
     assert ctypes.sizeof(_native.TsdfIntegrateDesc) == 48 + 16 + 128 + 384
