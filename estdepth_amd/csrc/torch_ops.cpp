@@ -1,8 +1,10 @@
 // torch_ops.cpp -- PyTorch-ROCm custom-operator registration of the ESTDepth hot path (namespace `estdepth_hip`).
 //
 // Thin, allocation-and-validation-only wrappers over the torch-free C ABI of libestd_hip.so (include/estd_hip.h):
-//   * TORCH_CHECK on device / dtype / contiguity / shapes  -> Python RuntimeError, the way ATen shape errors surface
-//     from the reference today (SURVEY §8b "Errors");
+//   * device / dtype / contiguity / shapes / buffer sizes are checked by one helper per kind of rule ("argument checks" below; the
+//     ctypes front ends of estdepth_amd/ops.py call the same set in the same order)  -> Python RuntimeError naming the operator and
+//     the argument, the way ATen shape errors surface from the reference today (SURVEY §8b "Errors"); value rules the C ABI
+//     enforces itself (strides, channel multiples, 32-bit limits) come back as its status;
 //   * outputs allocated with at::empty on the input device (caching allocator), never retained;
 //   * every kernel is enqueued on at::hip::getCurrentHIPStream() -- asynchronous, graph-capturable;
 //   * a negative estd_status becomes TORCH_CHECK(false, estd_status_string(status)).
@@ -17,7 +19,9 @@
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
 
+#include <algorithm>
 #include <cmath>
+#include <string>
 #include <type_traits>
 #include <vector>
 
@@ -49,13 +53,16 @@ inline void check_status(int st, const char* what)
     TORCH_CHECK(st == ESTD_OK, what, " failed: ", estd_status_string(st), " (estd_status ", st, ")");
 }
 
-inline const float* fptr(const Tensor& t, const char* name, bool need_contiguous = true)
+// `op`: the operator's name, put in front of the message (the helpers of the argument checks pass it)
+inline const float* fptr(const Tensor& t, const char* name, bool need_contiguous = true, const char* op = nullptr)
 {
-    TORCH_CHECK(t.defined(), name, " must be a tensor");
-    TORCH_CHECK(t.is_cuda(), name, " must live on a ROCm device (estdepth_hip has no CPU path); got ", t.device());
-    if (OpScope::cur) TORCH_CHECK(t.device() == *OpScope::cur, name, " is on ", t.device(), " but the operator runs on ", *OpScope::cur);
-    TORCH_CHECK(t.scalar_type() == at::kFloat, name, " must be float32, got ", t.scalar_type());
-    if (need_contiguous) TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+    const char* sep = op ? ": " : "";
+    if (!op) op = "";
+    TORCH_CHECK(t.defined(), op, sep, name, " must be a tensor");
+    TORCH_CHECK(t.is_cuda(), op, sep, name, " must live on a ROCm device (estdepth_hip has no CPU path); got ", t.device());
+    if (OpScope::cur) TORCH_CHECK(t.device() == *OpScope::cur, op, sep, name, " is on ", t.device(), " but the operator runs on ", *OpScope::cur);
+    TORCH_CHECK(t.scalar_type() == at::kFloat, op, sep, name, " must be float32, got ", t.scalar_type());
+    if (need_contiguous) TORCH_CHECK(t.is_contiguous(), op, sep, name, " must be contiguous");
     return t.data_ptr<float>();
 }
 inline float* fptr_mut(const Tensor& t, const char* name, bool need_contiguous = true) { return const_cast<float*>(fptr(t, name, need_contiguous)); }
@@ -63,86 +70,236 @@ inline const float* opt_fptr(const OptTensor& t, const char* name, bool need_con
 {
     return (t.has_value() && t->defined()) ? fptr(*t, name, need_contiguous) : nullptr;
 }
+inline float* mut(const float* p) { return const_cast<float*>(p); }      // an argument the operator writes
 inline Tensor new_f32(at::IntArrayRef shape, const Tensor& like) { return at::empty(shape, like.options().dtype(at::kFloat)); }
+
+// ------------------------------------------------------------------------------------------------ argument checks
+// One helper per kind of check for every operator of this file but the convolution plans' (estdepth_amd/ops.py has the same set for the
+// ctypes binding, and each operator calls them in the same order there); each takes the operator's and the argument's name for its message.
+
+// the volume argument: two float32 planes (0 = D, 1 = Wt), contiguous, on the operator's device, X % 4 == 0
+struct VolumeArg { int64_t Z, Y, X; float* tsdf; float* weight; };
+static VolumeArg check_volume(const Tensor& volume, const char* op)
+{
+    TORCH_CHECK(volume.dim() == 4 && volume.size(0) == 2, op, ": volume must be [2,Z,Y,X] (D plane, weight plane)");
+    float* vol = mut(fptr(volume, "volume", true, op));
+    const int64_t Z = volume.size(1), Y = volume.size(2), X = volume.size(3);
+    TORCH_CHECK(X % 4 == 0, op, ": X must be a multiple of 4, got ", X);
+    return {Z, Y, X, vol, vol + Z * Y * X};
+}
+
+static float* check_color_planes(const Tensor& color, const Tensor& volume, const char* op)
+{
+    TORCH_CHECK(color.dim() == 4 && color.size(0) == 3 && color.size(1) == volume.size(1) && color.size(2) == volume.size(2) &&
+                color.size(3) == volume.size(3), op, ": color must be [3,Z,Y,X] with the volume's Z, Y, X");
+    TORCH_CHECK(color.device() == volume.device(), op, ": color and the volume are on different devices");
+    return mut(fptr(color, "color", true, op));
+}
+
+// host values of the launch arguments: exactly n of them (finite: none NaN or infinite)
+static const float* host_values(const Tensor& t, int64_t n, const char* op, const char* name, const char* shape, bool finite = false)
+{
+    TORCH_CHECK(t.defined() && t.device().is_cpu() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.numel() == n,
+                op, ": ", name, " must be a contiguous CPU float32 tensor ", shape);
+    const float* v = t.data_ptr<float>();
+    for (int64_t i = 0; finite && i < n; ++i) TORCH_CHECK(std::isfinite(v[i]), op, ": ", name, " holds a value that is not finite");
+    return v;
+}
+
+// a float32 map on the operator's device whose last sizes are `tail` (-1: any size), leading 1s allowed; its sizes: t.size(-k)
+static const float* map_ptr(const Tensor& t, at::IntArrayRef tail, const char* op, const char* name)
+{
+    const float* p = fptr(t, name, true, op);
+    const int64_t k = (int64_t)tail.size();
+    bool ok = t.dim() >= k;
+    int64_t n = 1;
+    for (int64_t i = 0; ok && i < k; ++i) {
+        const int64_t s = t.size(t.dim() - k + i);
+        ok = tail[i] < 0 || tail[i] == s;
+        n *= s;
+    }
+    TORCH_CHECK(ok && t.numel() == n, op, ": ", name, " must end in the sizes ", tail, " (-1: any; leading 1s allowed), got ", t.sizes());
+    return p;
+}
+
+static void check_map_size(int64_t H, int64_t W, const char* op, const char* name, int64_t least = 1)
+{
+    TORCH_CHECK(H >= least && W >= least && H * W <= 0x7fffffffLL, op, ": ", name, " must be at least ", least, " x ", least,
+                " (and H * W < 2^31), got ", H, " x ", W);
+}
+
+// a float32 tensor on the operator's device that holds exactly (at_least: at least) n floats, whatever its shape; strided: the base of
+// wider records, which need not be contiguous
+static const float* floats_ptr(const Tensor& t, int64_t n, const char* op, const char* name, bool at_least = false, bool strided = false)
+{
+    const float* p = fptr(t, name, !strided, op);
+    TORCH_CHECK(at_least ? t.numel() >= n : t.numel() == n, op, ": ", name, " must hold ", at_least ? "at least " : "exactly ", n,
+                " floats, got ", t.numel());
+    return p;
+}
+
+// a float32 tensor of whole 32-float records (voxels) and nothing else -> their number
+static int64_t records(const Tensor& t, const char* op, const char* name)
+{
+    const int64_t n_vox = t.defined() ? t.numel() / 32 : 0;
+    floats_ptr(t, n_vox * 32, op, name);
+    return n_vox;
+}
+
+// an optional vector (a per-channel scale, shift or bias; a second pose): nothing, or exactly n floats
+static const float* opt_floats_ptr(const OptTensor& t, int64_t n, const char* op, const char* name)
+{
+    return (t.has_value() && t->defined()) ? floats_ptr(*t, n, op, name) : nullptr;
+}
+
+// a list of float32 tensors on the operator's device, each of `first`'s shape
+static std::vector<const float*> like_ptrs(at::TensorList ts, const Tensor& first, const char* op, const char* name)
+{
+    std::vector<const float*> ptrs(ts.size());
+    for (size_t i = 0; i < ts.size(); ++i) {
+        const std::string item = std::string(name) + "[" + std::to_string(i) + "]";
+        ptrs[i] = fptr(ts[i], item.c_str(), true, op);
+        TORCH_CHECK(ts[i].sizes() == first.sizes(), op, ": ", item, " has another shape than the first tensor: ", ts[i].sizes(), " for ", first.sizes());
+    }
+    return ptrs;
+}
+
+// bn_act_nhwc_'s tensors: float32 [N,C,H,W] in channels_last memory on the operator's device (like: and of that tensor's shape)
+static float* channels_last_ptr(const Tensor& t, const char* op, const char* name, const Tensor* like = nullptr)
+{
+    const float* p = fptr(t, name, false, op);
+    TORCH_CHECK(t.dim() == 4 && t.is_contiguous(at::MemoryFormat::ChannelsLast), op, ": ", name, " must be [N,C,H,W] in channels_last memory, got ",
+                t.sizes(), " with the strides ", t.strides());
+    TORCH_CHECK(!like || t.sizes() == like->sizes(), op, ": ", name, " must have the shape ", like ? like->sizes() : t.sizes(), ", got ", t.sizes());
+    return mut(p);
+}
+
+// a count (tensors of a list, a window, a stride the front end divides by) within lo..hi
+static void check_count(int64_t v, int64_t lo, int64_t hi, const char* op, const char* name)
+{
+    TORCH_CHECK(v >= lo && v <= hi, op, ": ", name, ": at least ", lo, " and at most ", hi, " expected, got ", v);
+}
+
+// a contiguous integer vector (int64 unless I says otherwise) on `like`'s device, of `size` elements (< 0: any number)
+template <class I = int64_t>
+static const I* lptr(const Tensor& t, const char* op, const char* name, const Tensor& like, int64_t size)
+{
+    TORCH_CHECK(t.defined() && t.dim() == 1 && t.scalar_type() == c10::CppTypeToScalarType<I>::value && t.is_contiguous() &&
+                t.device() == like.device() && (size < 0 || t.size(0) == size), op, ": ", name, " must be a contiguous ",
+                c10::CppTypeToScalarType<I>::value, " vector of the right length on the operator's device");
+    return t.data_ptr<I>();
+}
+
+// the four rules for a scalar that a kernel takes as fp32 -> the fp32 value
+static float positive_f32(double v, const char* op, const char* name)
+{
+    TORCH_CHECK(std::isfinite(v) && (float)v > 0.f, op, ": ", name, " must be positive and finite, got ", v);
+    return (float)v;
+}
+static float not_negative_f32(double v, const char* op, const char* name)
+{
+    TORCH_CHECK(std::isfinite(v) && v >= 0, op, ": ", name, " must be finite and not negative, got ", v);
+    return (float)v;
+}
+static float not_nan_f32(double v, const char* op, const char* name)
+{
+    TORCH_CHECK(v == v, op, ": ", name, " must not be NaN");
+    return (float)v;
+}
+// positive and finite, and its square finite in fp32 (square_positive: and not rounded to 0)
+static float positive_square_f32(double v, const char* op, const char* name, bool square_positive = false)
+{
+    const float f = (float)v, sq = f * f;
+    TORCH_CHECK(std::isfinite(v) && f > 0.f && std::isfinite(sq) && (sq > 0.f || !square_positive),
+                op, ": ", name, " (and its square in fp32) must be positive and finite, got ", v);
+    return f;
+}
+
+// Every entry point takes the stream last: one launch on the current stream of the operator's device, its status translated.
+#define ESTD_LAUNCH(entry, ...) check_status(entry(__VA_ARGS__, cur_stream()), #entry)
 
 // ------------------------------------------------------------------------------------------------ camera algebra
 Tensor cam_pair_proj(const Tensor& src_proj, const Tensor& ref_proj)
 {
+    const char* op = "cam_pair_proj";
     const OpScope scope(src_proj);
-    TORCH_CHECK(src_proj.numel() == 16 && ref_proj.numel() == 16, "cam_pair_proj: 4x4 projection matrices expected");
+    const float *sp = floats_ptr(src_proj, 16, op, "src_proj"), *rp = floats_ptr(ref_proj, 16, op, "ref_proj");
     Tensor out = new_f32({12}, src_proj);
-    check_status(estd_cam_pair_proj(fptr(src_proj, "src_proj"), fptr(ref_proj, "ref_proj"), out.data_ptr<float>(), cur_stream()),
-                 "estd_cam_pair_proj");
+    ESTD_LAUNCH(estd_cam_pair_proj, sp, rp, out.data_ptr<float>());
     return out;
 }
 
 Tensor cam_sweep_proj(const Tensor& ref_pose, const Tensor& src_pose, const Tensor& intr)
 {
+    const char* op = "cam_sweep_proj";
     const OpScope scope(ref_pose);
-    TORCH_CHECK(ref_pose.numel() == 16 && src_pose.numel() == 16 && intr.numel() == 9, "cam_sweep_proj: 4x4 poses and 3x3 intrinsics expected");
+    const float *rp = floats_ptr(ref_pose, 16, op, "ref_pose"), *sp = floats_ptr(src_pose, 16, op, "src_pose");
+    const float* k = floats_ptr(intr, 9, op, "intr");
     Tensor out = new_f32({12}, ref_pose);
-    check_status(estd_cam_sweep_proj(fptr(ref_pose, "ref_pose"), fptr(src_pose, "src_pose"), fptr(intr, "cam_intr"),
-                                     out.data_ptr<float>(), cur_stream()), "estd_cam_sweep_proj");
+    ESTD_LAUNCH(estd_cam_sweep_proj, rp, sp, k, out.data_ptr<float>());
     return out;
 }
 
 void cam_volume_mats(const Tensor& pose_j, const OptTensor& pose_i, const Tensor& intr, Tensor out)
 {
+    const char* op = "cam_volume_mats";
     const OpScope scope(pose_j);
-    TORCH_CHECK(pose_j.numel() == 16 && intr.numel() == 9, "cam_volume_mats: 4x4 pose and 3x3 intrinsics expected");
-    TORCH_CHECK(out.numel() == 30, "cam_volume_mats: out must hold 30 floats");
-    check_status(estd_cam_volume_mats(fptr(pose_j, "pose_j"), opt_fptr(pose_i, "pose_i"), fptr(intr, "cam_intr"),
-                                      fptr_mut(out, "mats30"), cur_stream()), "estd_cam_volume_mats");
+    const float *pj = floats_ptr(pose_j, 16, op, "pose_j"), *pi = opt_floats_ptr(pose_i, 16, op, "pose_i");
+    const float* k = floats_ptr(intr, 9, op, "intr");
+    ESTD_LAUNCH(estd_cam_volume_mats, pj, pi, k, mut(floats_ptr(out, 30, op, "out")));
 }
 
 // ------------------------------------------------------------------------------------------------ plane sweep
-Tensor homo_warping(const Tensor& src_chw, const Tensor& proj12, const Tensor& depth_values, int64_t D)
+// The body of homo_warping (depth: at least D plane depths) and homo_warping_px (per_pixel: depth is [D,H,W], which gives D).
+template <class Launch>
+static Tensor homo_warp(const char* op, Launch launch, const char* what, const Tensor& src_chw, const Tensor& proj12, const Tensor& depth, bool per_pixel, int64_t D)
 {
     const OpScope scope(src_chw);
-    TORCH_CHECK(src_chw.dim() == 3, "homo_warping: src_fea must be [C,H,W]");
-    TORCH_CHECK(depth_values.numel() >= D && proj12.numel() == 12, "homo_warping: depth_values / proj12 size");
-    const int64_t C = src_chw.size(0), H = src_chw.size(1), W = src_chw.size(2);
+    const float* src = map_ptr(src_chw, {-1, -1, -1}, op, "src_chw");
+    const int64_t C = src_chw.size(-3), H = src_chw.size(-2), W = src_chw.size(-1);
+    const float* P = floats_ptr(proj12, 12, op, "proj12");
+    const float* dv = per_pixel ? map_ptr(depth, {-1, H, W}, op, "depth_dhw") : floats_ptr(depth, D, op, "depth_values", true);
+    if (per_pixel) D = depth.size(-3);
     Tensor out = new_f32({C, D, H, W}, src_chw);
-    check_status(estd_homo_warping(fptr(src_chw, "src_fea"), fptr(proj12, "proj12"), fptr(depth_values, "depth_values"),
-                                   out.data_ptr<float>(), (int)C, (int)D, (int)H, (int)W, cur_stream()), "estd_homo_warping");
+    check_status(launch(src, P, dv, out.data_ptr<float>(), (int)C, (int)D, (int)H, (int)W, cur_stream()), what);
     return out;
+}
+
+Tensor homo_warping(const Tensor& src_chw, const Tensor& proj12, const Tensor& depth_values, int64_t D)
+{
+    return homo_warp("homo_warping", estd_homo_warping, "estd_homo_warping", src_chw, proj12, depth_values, false, D);
 }
 
 Tensor homo_warping_px(const Tensor& src_chw, const Tensor& proj12, const Tensor& depth_dhw)
 {
-    const OpScope scope(src_chw);
-    TORCH_CHECK(src_chw.dim() == 3 && depth_dhw.dim() == 3, "homo_warping_px: src_fea [C,H,W], depth [D,H,W]");
-    const int64_t C = src_chw.size(0), H = src_chw.size(1), W = src_chw.size(2), D = depth_dhw.size(0);
-    TORCH_CHECK(depth_dhw.size(1) == H && depth_dhw.size(2) == W && proj12.numel() == 12, "homo_warping_px: depth / proj12 size");
-    Tensor out = new_f32({C, D, H, W}, src_chw);
-    check_status(estd_homo_warping_px(fptr(src_chw, "src_fea"), fptr(proj12, "proj12"), fptr(depth_dhw, "depth_values"),
-                                      out.data_ptr<float>(), (int)C, (int)D, (int)H, (int)W, cur_stream()), "estd_homo_warping_px");
-    return out;
+    return homo_warp("homo_warping_px", estd_homo_warping_px, "estd_homo_warping_px", src_chw, proj12, depth_dhw, true, 0);
 }
 
 Tensor mix1x1(const Tensor& in_chw, const Tensor& w, const OptTensor& bias)
 {
+    const char* op = "mix1x1";
     const OpScope scope(in_chw);
-    TORCH_CHECK(in_chw.dim() == 3 && w.dim() == 2 && w.size(1) == in_chw.size(0), "mix1x1: in [Cin,H,W], w [Cout,Cin]");
-    const int64_t Cin = in_chw.size(0), H = in_chw.size(1), W = in_chw.size(2), Cout = w.size(0);
+    const float* in = map_ptr(in_chw, {-1, -1, -1}, op, "in_chw");
+    const int64_t Cin = in_chw.size(-3), H = in_chw.size(-2), W = in_chw.size(-1);
+    const float* wp = map_ptr(w, {-1, Cin}, op, "w");
+    const int64_t Cout = w.size(-2);
+    const float* b = opt_floats_ptr(bias, Cout, op, "bias");
     Tensor out = new_f32({H, W, Cout}, in_chw);
-    check_status(estd_mix1x1_chw_to_hwc(fptr(in_chw, "feature"), fptr(w, "mix weight"), opt_fptr(bias, "mix bias"),
-                                        out.data_ptr<float>(), (int)Cin, (int)Cout, (int)(H * W), cur_stream()), "estd_mix1x1_chw_to_hwc");
+    ESTD_LAUNCH(estd_mix1x1_chw_to_hwc, in, wp, b, out.data_ptr<float>(), (int)Cin, (int)Cout, (int)(H * W));
     return out;
 }
 
 void homo_warp_costvol(const Tensor& src_mix, const Tensor& ref_mix, const Tensor& proj12, const Tensor& depth_values,
                        int64_t D, Tensor out)
 {
+    const char* op = "homo_warp_costvol";
     const OpScope scope(src_mix);
-    TORCH_CHECK(src_mix.dim() == 3 && src_mix.size(2) == 32 && ref_mix.sizes() == src_mix.sizes(),
-                "homo_warp_costvol: src_mix / ref_mix must be [H,W,32] of one shape");
-    TORCH_CHECK(depth_values.numel() >= D && D >= 1 && proj12.numel() == 12, "homo_warp_costvol: depth_values / proj12 size");
-    const int64_t H = src_mix.size(0), W = src_mix.size(1);
-    TORCH_CHECK(out.numel() == D * H * W * 32, "homo_warp_costvol: out must be [D,H,W,32]");
-    check_status(estd_homo_warp_costvol(fptr(src_mix, "src_mix"), fptr(ref_mix, "ref_mix"), fptr(proj12, "proj12"),
-                                        fptr(depth_values, "depth_values"), fptr_mut(out, "out"), (int)D, (int)H, (int)W, cur_stream()),
-                 "estd_homo_warp_costvol");
+    const float* src = map_ptr(src_mix, {-1, -1, 32}, op, "src_mix");
+    const int64_t H = src_mix.size(-3), W = src_mix.size(-2);
+    const float* ref = map_ptr(ref_mix, {H, W, 32}, op, "ref_mix");
+    const float* P = floats_ptr(proj12, 12, op, "proj12");
+    const float* dv = floats_ptr(depth_values, D, op, "depth_values", true);
+    ESTD_LAUNCH(estd_homo_warp_costvol, src, ref, P, dv, mut(floats_ptr(out, D * H * W * 32, op, "out")), (int)D, (int)H, (int)W);
 }
 
 // ------------------------------------------------------------------------------------------------ conv3d / conv2d
@@ -287,147 +444,63 @@ Tensor conv2d_k3(const Tensor& x_nhwc, const OptTensor& w, const OptTensor& w_al
 Tensor groupnorm_finalize(const Tensor& partials, int64_t n_blocks, double count, double eps)
 {
     const OpScope scope(partials);
-    TORCH_CHECK(partials.is_cuda() && partials.scalar_type() == at::kDouble && partials.is_contiguous() && partials.numel() >= n_blocks * 4,
+    TORCH_CHECK(partials.defined() && partials.is_cuda() && partials.scalar_type() == at::kDouble && partials.is_contiguous() &&
+                partials.numel() >= n_blocks * 4,
                 "groupnorm_finalize: partials must be a contiguous float64 ROCm tensor with 4 doubles per block");
-    Tensor out = at::empty({4}, partials.options().dtype(at::kFloat));
-    check_status(estd_groupnorm_finalize(partials.data_ptr<double>(), (int)n_blocks, count, (float)eps, out.data_ptr<float>(), cur_stream()),
-                 "estd_groupnorm_finalize");
+    Tensor out = new_f32({4}, partials);
+    ESTD_LAUNCH(estd_groupnorm_finalize, partials.data_ptr<double>(), (int)n_blocks, count, (float)eps, out.data_ptr<float>());
     return out;
 }
 
 // ------------------------------------------------------------------------------------------------ soft-argmin
 std::tuple<Tensor, Tensor> softargmin_up(const Tensor& logits, const Tensor& depth_values, int64_t scale)
 {
+    const char* op = "softargmin_up";
     const OpScope scope(logits);
-    TORCH_CHECK(logits.dim() == 4, "softargmin_up: logits must be [N,D,H,W]");
-    const int64_t N = logits.size(0), D = logits.size(1), H = logits.size(2), W = logits.size(3);
-    TORCH_CHECK(depth_values.numel() >= D, "softargmin_up: one depth value per plane expected");
+    const float* lg = map_ptr(logits, {-1, -1, -1, -1}, op, "logits");
+    const int64_t N = logits.size(-4), D = logits.size(-3), H = logits.size(-2), W = logits.size(-1);
+    const float* dv = floats_ptr(depth_values, D, op, "depth_values", true);
     Tensor depth = new_f32({N, 1, H * scale, W * scale}, logits);
     Tensor prob = at::empty_like(depth);
-    check_status(estd_softargmin_up(fptr(logits, "logits"), fptr(depth_values, "depth_values"), depth.data_ptr<float>(),
-                                    prob.data_ptr<float>(), (int)N, (int)D, (int)H, (int)W, (int)scale, cur_stream()), "estd_softargmin_up");
+    ESTD_LAUNCH(estd_softargmin_up, lg, dv, depth.data_ptr<float>(), prob.data_ptr<float>(), (int)N, (int)D, (int)H, (int)W, (int)scale);
     return {depth, prob};
 }
 
 // ------------------------------------------------------------------------------------------------ EST fusion
-Tensor warp_volume(const Tensor& vol, const Tensor& mats30, const Tensor& depth_values, double depth_min, double depth_interval)
+// The body of warp_volume and warp_volume_ex: `launch` takes the checked pointers and sizes and passes the operator's own scalars on.
+template <class Launch>
+static Tensor warp_vol(const char* op, const char* what, const Tensor& vol, const Tensor& mats30, const Tensor& depth, bool depth_per_voxel,
+                       Launch launch)
 {
     const OpScope scope(vol);
-    TORCH_CHECK(vol.dim() == 4 && mats30.numel() == 30, "warp_volume: vol [C,D,H,W], mats30 [30]");
-    TORCH_CHECK(depth_values.numel() >= vol.size(1), "warp_volume: one depth value per plane expected");
+    const float* v = map_ptr(vol, {-1, -1, -1, -1}, op, "vol");
+    const int64_t C = vol.size(-4), D = vol.size(-3), H = vol.size(-2), W = vol.size(-1);
+    const float* m = floats_ptr(mats30, 30, op, "mats30");
+    const float* dv = floats_ptr(depth, depth_per_voxel ? D * H * W : D, op, "depth", true);
     Tensor out = at::empty_like(vol);
-    check_status(estd_warp_volume(fptr(vol, "feat_volume"), fptr(mats30, "mats30"), fptr(depth_values, "depth"), (float)depth_min,
-                                  (float)depth_interval, out.data_ptr<float>(), (int)vol.size(0), (int)vol.size(1), (int)vol.size(2),
-                                  (int)vol.size(3), cur_stream()), "estd_warp_volume");
+    check_status(launch(v, m, dv, out.data_ptr<float>(), (int)C, (int)D, (int)H, (int)W), what);
     return out;
+}
+
+Tensor warp_volume(const Tensor& vol, const Tensor& mats30, const Tensor& depth_values, double depth_min, double depth_interval)
+{
+    return warp_vol("warp_volume", "estd_warp_volume", vol, mats30, depth_values, false,
+                    [&](const float* v, const float* m, const float* dv, float* out, int C, int D, int H, int W) {
+                        return estd_warp_volume(v, m, dv, (float)depth_min, (float)depth_interval, out, C, D, H, W, cur_stream());
+                    });
 }
 
 Tensor warp_volume_ex(const Tensor& vol, const Tensor& mats30, const Tensor& depth, bool depth_per_voxel, double depth_min,
                       double depth_interval, bool use_disp, double disp_min, double disp_interval, bool border, double padding_value)
 {
-    const OpScope scope(vol);
-    TORCH_CHECK(vol.dim() == 4 && mats30.numel() == 30, "warp_volume: vol [C,D,H,W], mats30 [30]");
-    const int64_t need = depth_per_voxel ? vol.size(1) * vol.size(2) * vol.size(3) : vol.size(1);
-    TORCH_CHECK(depth.numel() >= need, "warp_volume: depth must hold ", need, " values");
     estd_warp_volume_opts o{};
     o.depth_per_voxel = depth_per_voxel; o.use_disp = use_disp; o.border = border;
     o.depth_min = (float)depth_min; o.depth_interval = (float)depth_interval;
     o.disp_min = (float)disp_min; o.disp_interval = (float)disp_interval; o.padding_value = (float)padding_value;
-    Tensor out = at::empty_like(vol);
-    check_status(estd_warp_volume_ex(fptr(vol, "feat_volume"), fptr(mats30, "mats30"), fptr(depth, "depth"), &o, out.data_ptr<float>(),
-                                     (int)vol.size(0), (int)vol.size(1), (int)vol.size(2), (int)vol.size(3), cur_stream()),
-                 "estd_warp_volume_ex");
-    return out;
-}
-
-// ------------------------------------------------------------------------------------------------ reconstruction operators: argument checks
-// One helper per kind of check for the operators below (estdepth_amd/ops.py has the same set for the ctypes binding); each takes the
-// operator's and the argument's name for its message.
-
-// the volume argument: two float32 planes (0 = D, 1 = Wt), contiguous, on the operator's device, X % 4 == 0
-struct VolumeArg { int64_t Z, Y, X; float* tsdf; float* weight; };
-static VolumeArg check_volume(const Tensor& volume, const char* op)
-{
-    TORCH_CHECK(volume.dim() == 4 && volume.size(0) == 2, op, ": volume must be [2,Z,Y,X] (D plane, weight plane)");
-    float* vol = fptr_mut(volume, "volume");
-    const int64_t Z = volume.size(1), Y = volume.size(2), X = volume.size(3);
-    TORCH_CHECK(X % 4 == 0, op, ": X must be a multiple of 4, got ", X);
-    return {Z, Y, X, vol, vol + Z * Y * X};
-}
-
-static float* check_color_planes(const Tensor& color, const Tensor& volume, const char* op)
-{
-    TORCH_CHECK(color.dim() == 4 && color.size(0) == 3 && color.size(1) == volume.size(1) && color.size(2) == volume.size(2) &&
-                color.size(3) == volume.size(3), op, ": color must be [3,Z,Y,X] with the volume's Z, Y, X");
-    TORCH_CHECK(color.device() == volume.device(), op, ": color and the volume are on different devices");
-    return fptr_mut(color, "color");
-}
-
-// host values of the launch arguments: exactly n of them (finite: none NaN or infinite)
-static const float* host_values(const Tensor& t, int64_t n, const char* op, const char* name, const char* shape, bool finite = false)
-{
-    TORCH_CHECK(t.defined() && t.device().is_cpu() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.numel() == n,
-                op, ": ", name, " must be a contiguous CPU float32 tensor ", shape);
-    const float* v = t.data_ptr<float>();
-    for (int64_t i = 0; finite && i < n; ++i) TORCH_CHECK(std::isfinite(v[i]), op, ": ", name, " holds a value that is not finite");
-    return v;
-}
-
-// a float32 map on the operator's device whose last sizes are `tail` (-1: any size), leading 1s allowed
-static const float* map_ptr(const Tensor& t, at::IntArrayRef tail, const char* op, const char* name)
-{
-    const float* p = fptr(t, name);
-    const int64_t k = (int64_t)tail.size();
-    bool ok = t.dim() >= k;
-    int64_t n = 1;
-    for (int64_t i = 0; ok && i < k; ++i) {
-        const int64_t s = t.size(t.dim() - k + i);
-        ok = tail[i] < 0 || tail[i] == s;
-        n *= s;
-    }
-    TORCH_CHECK(ok && t.numel() == n, op, ": ", name, " must end in the sizes ", tail, " (-1: any; leading 1s allowed), got ", t.sizes());
-    return p;
-}
-
-static void check_map_size(int64_t H, int64_t W, const char* op, const char* name, int64_t least = 1)
-{
-    TORCH_CHECK(H >= least && W >= least && H * W <= 0x7fffffffLL, op, ": ", name, " must be at least ", least, " x ", least,
-                " (and H * W < 2^31), got ", H, " x ", W);
-}
-
-// a contiguous integer vector (int64 unless I says otherwise) on `like`'s device, of `size` elements (< 0: any number)
-template <class I = int64_t>
-static const I* lptr(const Tensor& t, const char* op, const char* name, const Tensor& like, int64_t size)
-{
-    TORCH_CHECK(t.defined() && t.dim() == 1 && t.scalar_type() == c10::CppTypeToScalarType<I>::value && t.is_contiguous() &&
-                t.device() == like.device() && (size < 0 || t.size(0) == size), op, ": ", name, " must be a contiguous ",
-                c10::CppTypeToScalarType<I>::value, " vector of the right length on the operator's device");
-    return t.data_ptr<I>();
-}
-
-// the four rules for a scalar that a kernel takes as fp32 -> the fp32 value
-static float positive_f32(double v, const char* op, const char* name)
-{
-    TORCH_CHECK(std::isfinite(v) && (float)v > 0.f, op, ": ", name, " must be positive and finite, got ", v);
-    return (float)v;
-}
-static float not_negative_f32(double v, const char* op, const char* name)
-{
-    TORCH_CHECK(std::isfinite(v) && v >= 0, op, ": ", name, " must be finite and not negative, got ", v);
-    return (float)v;
-}
-static float not_nan_f32(double v, const char* op, const char* name)
-{
-    TORCH_CHECK(v == v, op, ": ", name, " must not be NaN");
-    return (float)v;
-}
-// positive and finite, and its square finite in fp32 (square_positive: and not rounded to 0)
-static float positive_square_f32(double v, const char* op, const char* name, bool square_positive = false)
-{
-    const float f = (float)v, sq = f * f;
-    TORCH_CHECK(std::isfinite(v) && f > 0.f && std::isfinite(sq) && (sq > 0.f || !square_positive),
-                op, ": ", name, " (and its square in fp32) must be positive and finite, got ", v);
-    return f;
+    return warp_vol("warp_volume_ex", "estd_warp_volume_ex", vol, mats30, depth, depth_per_voxel,
+                    [&](const float* v, const float* m, const float* dv, float* out, int C, int D, int H, int W) {
+                        return estd_warp_volume_ex(v, m, dv, &o, out, C, D, H, W, cur_stream());
+                    });
 }
 
 // ------------------------------------------------------------------------------------------------ TSDF fusion (csrc/tsdf.hip)
@@ -682,309 +755,311 @@ std::tuple<Tensor, Tensor> cloud_cell_centroids(const Tensor& points, const Tens
     return {out, out_attrs};
 }
 
+// ------------------------------------------------------------------------------------------------ EST fusion: attention, ConvGRU glue
 Tensor warp_attention(const Tensor& kv_target, at::TensorList kv_sources, const Tensor& mats, const Tensor& depth_values,
                       double depth_min, double depth_interval)
 {
+    const char* op = "warp_attention";
     const OpScope scope(kv_target);
-    TORCH_CHECK(kv_target.dim() == 4 && kv_target.size(3) == 32, "warp_attention: kv volumes must be [D,H,W,32]");
-    const int64_t D = kv_target.size(0), H = kv_target.size(1), W = kv_target.size(2);
-    const int n = (int)kv_sources.size();
-    TORCH_CHECK(n >= 1, "warp_attention: at least one source volume");
-    TORCH_CHECK(n <= ESTD_MAX_ATTENTION_SOURCES, "warp_attention: at most ", ESTD_MAX_ATTENTION_SOURCES, " source volumes, got ", n);
-    TORCH_CHECK(mats.numel() == (int64_t)n * 30, "warp_attention: mats must be [n_src,30]");
-    TORCH_CHECK(depth_values.numel() >= D, "warp_attention: one depth value per plane expected");
-    std::vector<const float*> ptrs(n);
-    for (int j = 0; j < n; ++j) {
-        TORCH_CHECK(kv_sources[j].sizes() == kv_target.sizes(), "warp_attention: source ", j, " has another shape than the target");
-        ptrs[j] = fptr(kv_sources[j], "kv source");
-    }
+    const float* kv = map_ptr(kv_target, {-1, -1, -1, 32}, op, "kv_target");
+    const int64_t D = kv_target.size(-4), H = kv_target.size(-3), W = kv_target.size(-2), n = (int64_t)kv_sources.size();
+    check_count(n, 1, ESTD_MAX_ATTENTION_SOURCES, op, "kv_sources");
+    const std::vector<const float*> srcs = like_ptrs(kv_sources, kv_target, op, "kv_sources");
+    const float* m = floats_ptr(mats, n * 30, op, "mats");
+    const float* dv = floats_ptr(depth_values, D, op, "depth_values", true);
     Tensor xh = at::empty_like(kv_target);
-    check_status(estd_warp_attention(fptr(kv_target, "kv target"), ptrs.data(), fptr(mats, "mats"), n, fptr(depth_values, "depth_values"),
-                                     (float)depth_min, (float)depth_interval, xh.data_ptr<float>(), (int)D, (int)H, (int)W, cur_stream()),
-                 "estd_warp_attention");
+    ESTD_LAUNCH(estd_warp_attention, kv, srcs.data(), m, (int)n, dv, (float)depth_min, (float)depth_interval, xh.data_ptr<float>(), (int)D, (int)H,
+                (int)W);
     return xh;
 }
 
 Tensor attention_prewarped(const Tensor& kv_target, at::TensorList kv_sources)
 {
+    const char* op = "attention_prewarped";
     const OpScope scope(kv_target);
-    const int n = (int)kv_sources.size();
-    TORCH_CHECK(n >= 1 && n <= ESTD_MAX_ATTENTION_SOURCES, "attention_prewarped: 1..", ESTD_MAX_ATTENTION_SOURCES, " pre-warped source volumes");
-    TORCH_CHECK(kv_target.numel() % 32 == 0, "attention_prewarped: kv volumes hold 32 floats per voxel");
-    std::vector<const float*> ptrs(n);
-    for (int j = 0; j < n; ++j) {
-        TORCH_CHECK(kv_sources[j].numel() == kv_target.numel(), "attention_prewarped: source ", j, " has another size than the target");
-        ptrs[j] = fptr(kv_sources[j], "kv source");
-    }
+    const int64_t n_vox = records(kv_target, op, "kv_target"), n = (int64_t)kv_sources.size();
+    check_count(n, 1, ESTD_MAX_ATTENTION_SOURCES, op, "kv_sources");
+    const std::vector<const float*> srcs = like_ptrs(kv_sources, kv_target, op, "kv_sources");
     Tensor xh = at::empty_like(kv_target);
-    check_status(estd_attention_prewarped(fptr(kv_target, "kv target"), ptrs.data(), n, xh.data_ptr<float>(), kv_target.numel() / 32,
-                                          cur_stream()), "estd_attention_prewarped");
+    ESTD_LAUNCH(estd_attention_prewarped, kv_target.data_ptr<float>(), srcs.data(), (int)n, xh.data_ptr<float>(), n_vox);
     return xh;
 }
 
 Tensor gru_reset_apply(const Tensor& xh, const Tensor& ru, const Tensor& stats4, const Tensor& gamma_r, const Tensor& beta_r)
 {
+    const char* op = "gru_reset_apply";
     const OpScope scope(xh);
-    TORCH_CHECK(xh.numel() == ru.numel() && xh.numel() % 32 == 0, "gru_reset_apply: xh and ru are [D,H,W,32] volumes");
-    TORCH_CHECK(stats4.numel() == 4 && gamma_r.numel() == 16 && beta_r.numel() == 16, "gru_reset_apply: stats [4], affine [16]");
+    const int64_t n_vox = records(xh, op, "xh");
+    const float *x = xh.data_ptr<float>(), *r = floats_ptr(ru, n_vox * 32, op, "ru");
+    const float *st = floats_ptr(stats4, 4, op, "stats4"), *ga = floats_ptr(gamma_r, 16, op, "gamma_r"), *be = floats_ptr(beta_r, 16, op, "beta_r");
     Tensor xrh = at::empty_like(xh);
-    check_status(estd_gru_reset_apply(fptr(xh, "xh"), fptr(ru, "ru"), fptr(stats4, "stats"), fptr(gamma_r, "gamma"), fptr(beta_r, "beta"),
-                                      xrh.data_ptr<float>(), xh.numel() / 32, cur_stream()), "estd_gru_reset_apply");
+    ESTD_LAUNCH(estd_gru_reset_apply, x, r, st, ga, be, xrh.data_ptr<float>(), n_vox);
     return xrh;
 }
 
 void gru_blend(const Tensor& xh, const Tensor& ru, const Tensor& o_raw, const Tensor& stats_ru, const Tensor& stats_o,
                const Tensor& gamma_u, const Tensor& beta_u, const Tensor& gamma_o, const Tensor& beta_o, Tensor out_value, int64_t out_stride)
 {
+    const char* op = "gru_blend";
     const OpScope scope(xh);
-    const int64_t n_vox = xh.numel() / 32;
-    TORCH_CHECK(xh.numel() == ru.numel() && o_raw.numel() == n_vox * 16, "gru_blend: xh, ru [D,H,W,32]; o_raw [D,H,W,16]");
-    TORCH_CHECK(stats_ru.numel() == 4 && stats_o.numel() == 4 && gamma_u.numel() == 16 && beta_u.numel() == 16 &&
-                gamma_o.numel() == 16 && beta_o.numel() == 16, "gru_blend: stats [4], affine [16]");
-    TORCH_CHECK(out_value.numel() >= (n_vox - 1) * out_stride + 16, "gru_blend: out_value must hold (n_vox - 1) * out_stride + 16 floats");
-    check_status(estd_gru_blend(fptr(xh, "xh"), fptr(ru, "ru"), fptr(o_raw, "o_raw"), fptr(stats_ru, "stats_ru"), fptr(stats_o, "stats_o"),
-                                fptr(gamma_u, "gamma_u"), fptr(beta_u, "beta_u"), fptr(gamma_o, "gamma_o"), fptr(beta_o, "beta_o"),
-                                fptr_mut(out_value, "out_value", false), (int)out_stride, n_vox, cur_stream()), "estd_gru_blend");
+    const int64_t n_vox = records(xh, op, "xh");
+    const float *x = xh.data_ptr<float>(), *r = floats_ptr(ru, n_vox * 32, op, "ru"), *o = floats_ptr(o_raw, n_vox * 16, op, "o_raw");
+    const float *sr = floats_ptr(stats_ru, 4, op, "stats_ru"), *so = floats_ptr(stats_o, 4, op, "stats_o");
+    const float *gu = floats_ptr(gamma_u, 16, op, "gamma_u"), *bu = floats_ptr(beta_u, 16, op, "beta_u");
+    const float *go = floats_ptr(gamma_o, 16, op, "gamma_o"), *bo = floats_ptr(beta_o, 16, op, "beta_o");
+    const float* out = floats_ptr(out_value, (n_vox - 1) * out_stride + 16, op, "out_value", true, true);
+    ESTD_LAUNCH(estd_gru_blend, x, r, o, sr, so, gu, bu, go, bo, mut(out), (int)out_stride, n_vox);
 }
 
 // ------------------------------------------------------------------------------------------------ 2D backbone epilogues, layouts
 Tensor bn_act_nhwc_(Tensor x, const Tensor& scale, const Tensor& shift, bool relu, const OptTensor& residual)
 {
+    const char* op = "bn_act_nhwc_";
     const OpScope scope(x);
-    TORCH_CHECK(x.dim() == 4 && x.is_cuda() && x.scalar_type() == at::kFloat && x.is_contiguous(at::MemoryFormat::ChannelsLast),
-                "bn_act_nhwc_: expected a float32 ROCm tensor in channels_last memory (no CPU path)");
+    float* xp = channels_last_ptr(x, op, "x");
     const int64_t n = x.size(0), c = x.size(1), h = x.size(2), w = x.size(3);
-    const float* res = nullptr;
-    if (residual.has_value() && residual->defined()) {
-        TORCH_CHECK(residual->sizes() == x.sizes() && residual->is_contiguous(at::MemoryFormat::ChannelsLast) &&
-                    residual->scalar_type() == at::kFloat && residual->is_cuda(), "bn_act_nhwc_: residual must match x (shape, channels_last)");
-        res = residual->data_ptr<float>();
-    }
-    TORCH_CHECK(scale.numel() == c && shift.numel() == c, "bn_act_nhwc_: scale/shift must have C entries");
-    check_status(estd_bn_act_nhwc(x.data_ptr<float>(), fptr(scale, "scale"), fptr(shift, "shift"), res, relu ? 1 : 0, n * h * w, (int)c,
-                                  cur_stream()), "estd_bn_act_nhwc");
+    const float *sc = floats_ptr(scale, c, op, "scale"), *sh = floats_ptr(shift, c, op, "shift");
+    const float* res = (residual.has_value() && residual->defined()) ? channels_last_ptr(*residual, op, "residual", &x) : nullptr;
+    ESTD_LAUNCH(estd_bn_act_nhwc, xp, sc, sh, res, relu ? 1 : 0, n * h * w, (int)c);
     return x;
 }
 
 Tensor spp_upsample_cat(const Tensor& raw, const Tensor& skip, at::TensorList branches)
 {
+    const char* op = "spp_upsample_cat";
     const OpScope scope(raw);
-    const int nb = (int)branches.size();
-    TORCH_CHECK(raw.dim() == 4 && skip.dim() == 4 && nb >= 1 && nb <= 4, "spp_upsample_cat: NHWC raw/skip and 1..4 branches");
-    const int64_t n = raw.size(0), h = raw.size(1), w = raw.size(2), cr = raw.size(3), cs = skip.size(3), cb = branches[0].size(3);
+    const float* rp = map_ptr(raw, {-1, -1, -1, -1}, op, "raw");
+    const int64_t n = raw.size(-4), h = raw.size(-3), w = raw.size(-2), cr = raw.size(-1), nb = (int64_t)branches.size();
+    const float* sp = map_ptr(skip, {n, h, w, -1}, op, "skip");
+    const int64_t cs = skip.size(-1);
+    check_count(nb, 1, 4, op, "branches");
     std::vector<const float*> ptrs(nb);
     std::vector<int> bh(nb), bw(nb);
-    for (int k = 0; k < nb; ++k) {
-        TORCH_CHECK(branches[k].dim() == 4 && branches[k].size(0) == n && branches[k].size(3) == cb, "spp_upsample_cat: branch shape");
-        ptrs[k] = fptr(branches[k], "spp branch"); bh[k] = (int)branches[k].size(1); bw[k] = (int)branches[k].size(2);
+    int64_t cb = -1;                                           // the first branch's channel count is every branch's
+    for (int64_t k = 0; k < nb; ++k) {
+        const std::string item = "branches[" + std::to_string(k) + "]";
+        ptrs[k] = map_ptr(branches[k], {n, -1, -1, cb}, op, item.c_str());
+        bh[k] = (int)branches[k].size(-3); bw[k] = (int)branches[k].size(-2); cb = branches[k].size(-1);
     }
     Tensor out = new_f32({n, h, w, cr + cs + nb * cb}, raw);
-    check_status(estd_spp_upsample_cat(fptr(raw, "raw"), (int)cr, fptr(skip, "skip"), (int)cs, ptrs.data(), bh.data(), bw.data(), nb, (int)cb,
-                                       out.data_ptr<float>(), (int)n, (int)h, (int)w, cur_stream()), "estd_spp_upsample_cat");
+    ESTD_LAUNCH(estd_spp_upsample_cat, rp, (int)cr, sp, (int)cs, ptrs.data(), bh.data(), bw.data(), (int)nb, (int)cb, out.data_ptr<float>(), (int)n,
+                (int)h, (int)w);
+    return out;
+}
+
+// The body of conv1x1_nhwc and conv2d_taps_nhwc: `d` arrives with the operator's own fields (stride; ksize, pad) set, `w_tail` are the
+// weight's sizes around cout ([cout,cin] / [k*k,cout,cin]: cout is w.size(-2)), ho x wo the output map.
+template <class Desc>
+static Tensor desc_conv(const char* op, int (*launch)(const Desc*, estd_stream_t), const char* what, Desc d, const Tensor& x, const Tensor& w,
+                        at::IntArrayRef w_tail, int64_t ho, int64_t wo, const OptTensor& scale, const OptTensor& shift, bool relu,
+                        const OptTensor& residual)
+{
+    d.w = map_ptr(w, w_tail, op, "w");
+    const int64_t n = x.size(-4), cout = w.size(-2);
+    d.N = (int)n; d.H = (int)x.size(-3); d.W = (int)x.size(-2); d.cin = (int)x.size(-1); d.cout = (int)cout; d.relu = relu ? 1 : 0;
+    d.in = x.data_ptr<float>();
+    d.scale = opt_floats_ptr(scale, cout, op, "scale"); d.shift = opt_floats_ptr(shift, cout, op, "shift");
+    if (residual.has_value() && residual->defined()) d.residual = map_ptr(*residual, {n, ho, wo, cout}, op, "residual");
+    Tensor out = new_f32({n, ho, wo, cout}, x);
+    d.out = out.data_ptr<float>();
+    check_status(launch(&d, cur_stream()), what);
     return out;
 }
 
 Tensor conv1x1_nhwc(const Tensor& x, const Tensor& w2, const OptTensor& scale, const OptTensor& shift, int64_t stride, bool relu,
                     const OptTensor& residual)
 {
+    const char* op = "conv1x1_nhwc";
     const OpScope scope(x);
-    TORCH_CHECK(x.dim() == 4 && w2.dim() == 2 && w2.size(1) == x.size(3), "conv1x1_nhwc: NHWC x [N,H,W,cin] and w [cout,cin] expected");
-    TORCH_CHECK(stride == 1 || stride == 2, "conv1x1_nhwc: stride 1 or 2");
-    const int64_t n = x.size(0), h = x.size(1), w = x.size(2), cin = x.size(3), cout = w2.size(0);
-    const int64_t ho = (h - 1) / stride + 1, wo = (w - 1) / stride + 1;
+    map_ptr(x, {-1, -1, -1, -1}, op, "x");
+    check_count(stride, 1, 2, op, "stride");
     estd_conv1x1_desc d{};
-    d.N = (int)n; d.H = (int)h; d.W = (int)w; d.cin = (int)cin; d.cout = (int)cout; d.stride = (int)stride; d.relu = relu ? 1 : 0;
-    d.in = fptr(x, "x"); d.w = fptr(w2, "w");
-    d.scale = opt_fptr(scale, "scale"); d.shift = opt_fptr(shift, "shift");
-    if (d.scale) TORCH_CHECK(scale->numel() == cout, "conv1x1_nhwc: scale [cout] expected");
-    if (d.shift) TORCH_CHECK(shift->numel() == cout, "conv1x1_nhwc: shift [cout] expected");
-    d.residual = opt_fptr(residual, "residual");
-    if (d.residual) TORCH_CHECK(residual->numel() == n * ho * wo * cout, "conv1x1_nhwc: residual must be NHWC [N,Ho,Wo,cout]");
-    Tensor out = new_f32({n, ho, wo, cout}, x);
-    d.out = out.data_ptr<float>();
-    check_status(estd_conv1x1_nhwc(&d, cur_stream()), "estd_conv1x1_nhwc");
-    return out;
+    d.stride = (int)stride;
+    return desc_conv(op, estd_conv1x1_nhwc, "estd_conv1x1_nhwc", d, x, w2, {-1, x.size(-1)}, (x.size(-3) - 1) / stride + 1,
+                     (x.size(-2) - 1) / stride + 1, scale, shift, relu, residual);
 }
 
 Tensor conv2d_taps_nhwc(const Tensor& x, const Tensor& w_taps, const OptTensor& scale, const OptTensor& shift, int64_t ksize, int64_t stride,
                         int64_t pad, bool relu, const OptTensor& residual)
 {
+    const char* op = "conv2d_taps_nhwc";
     const OpScope scope(x);
-    TORCH_CHECK(x.dim() == 4 && w_taps.dim() == 3 && w_taps.size(0) == ksize * ksize && w_taps.size(2) == x.size(3),
-                "conv2d_taps_nhwc: NHWC x [N,H,W,cin] and w [k*k,cout,cin] expected");
-    TORCH_CHECK((stride == 1 || stride == 2) && pad >= 0, "conv2d_taps_nhwc: stride 1 or 2, pad >= 0");
-    const int64_t n = x.size(0), h = x.size(1), w = x.size(2), cin = x.size(3), cout = w_taps.size(1);
-    TORCH_CHECK(h + 2 * pad >= ksize && w + 2 * pad >= ksize, "conv2d_taps_nhwc: map smaller than the kernel");
-    const int64_t ho = (h + 2 * pad - ksize) / stride + 1, wo = (w + 2 * pad - ksize) / stride + 1;
+    map_ptr(x, {-1, -1, -1, -1}, op, "x");
+    check_count(stride, 1, 2, op, "stride");
     estd_conv2d_taps_desc d{};
-    d.N = (int)n; d.H = (int)h; d.W = (int)w; d.cin = (int)cin; d.cout = (int)cout;
-    d.ksize = (int)ksize; d.stride = (int)stride; d.pad = (int)pad; d.relu = relu ? 1 : 0;
-    d.in = fptr(x, "x"); d.w = fptr(w_taps, "w");
-    d.scale = opt_fptr(scale, "scale"); d.shift = opt_fptr(shift, "shift");
-    if (d.scale) TORCH_CHECK(scale->numel() == cout, "conv2d_taps_nhwc: scale [cout] expected");
-    if (d.shift) TORCH_CHECK(shift->numel() == cout, "conv2d_taps_nhwc: shift [cout] expected");
-    d.residual = opt_fptr(residual, "residual");
-    if (d.residual) TORCH_CHECK(residual->numel() == n * ho * wo * cout, "conv2d_taps_nhwc: residual must be NHWC [N,Ho,Wo,cout]");
-    Tensor out = new_f32({n, ho, wo, cout}, x);
-    d.out = out.data_ptr<float>();
-    check_status(estd_conv2d_taps_nhwc(&d, cur_stream()), "estd_conv2d_taps_nhwc");
+    d.ksize = (int)ksize; d.stride = (int)stride; d.pad = (int)pad;
+    return desc_conv(op, estd_conv2d_taps_nhwc, "estd_conv2d_taps_nhwc", d, x, w_taps, {ksize * ksize, -1, x.size(-1)},
+                     (x.size(-3) + 2 * pad - ksize) / stride + 1, (x.size(-2) + 2 * pad - ksize) / stride + 1, scale, shift, relu, residual);
+}
+
+// The body of the four "NHWC in, packed weights, scale / shift [cout], NHWC out" convolutions: x and the weights `w` have been checked,
+// `launch` takes the five pointers and passes the operator's own sizes on.
+template <class Launch>
+static Tensor packed_conv(const char* op, const char* what, const Tensor& x, const float* w, const Tensor& scale, const Tensor& shift,
+                          at::IntArrayRef out_shape, Launch launch)
+{
+    const float *sc = floats_ptr(scale, out_shape[3], op, "scale"), *sh = floats_ptr(shift, out_shape[3], op, "shift");
+    Tensor out = new_f32(out_shape, x);
+    check_status(launch(x.data_ptr<float>(), w, sc, sh, out.data_ptr<float>()), what);
     return out;
 }
 
 Tensor stem7x7s2_nhwc(const Tensor& x, const Tensor& w_packed, const Tensor& scale, const Tensor& shift)
 {
+    const char* op = "stem7x7s2_nhwc";
     const OpScope scope(x);
-    TORCH_CHECK(x.dim() == 4 && x.size(3) == 3 && w_packed.numel() == 7 * 6 * 4 * 64 && scale.numel() == 64 && shift.numel() == 64,
-                "stem7x7s2_nhwc: NHWC x [N,H,W,3], packed weights [7,6,4,64], scale/shift [64] expected");
-    const int64_t n = x.size(0), h = x.size(1), w = x.size(2);
-    Tensor out = new_f32({n, (h - 1) / 2 + 1, (w - 1) / 2 + 1, 64}, x);
-    check_status(estd_stem7x7s2_nhwc(fptr(x, "x"), fptr(w_packed, "packed weights"), fptr(scale, "scale"), fptr(shift, "shift"), out.data_ptr<float>(),
-                                     (int)n, (int)h, (int)w, cur_stream()), "estd_stem7x7s2_nhwc");
-    return out;
+    map_ptr(x, {-1, -1, -1, 3}, op, "x");
+    const int n = (int)x.size(-4), h = (int)x.size(-3), w = (int)x.size(-2);
+    return packed_conv(op, "estd_stem7x7s2_nhwc", x, floats_ptr(w_packed, 7 * 6 * 4 * 64, op, "w_packed"), scale, shift,
+                       {n, (h - 1) / 2 + 1, (w - 1) / 2 + 1, 64},
+                       [&](auto... p) { return estd_stem7x7s2_nhwc(p..., n, h, w, cur_stream()); });
+}
+
+Tensor stem3x3s2_nhwc(const Tensor& x, const Tensor& weight, const Tensor& scale, const Tensor& shift)
+{
+    const char* op = "stem3x3s2_nhwc";
+    const OpScope scope(x);
+    map_ptr(x, {-1, -1, -1, 3}, op, "x");
+    const int n = (int)x.size(-4), h = (int)x.size(-3), w = (int)x.size(-2);
+    return packed_conv(op, "estd_stem3x3s2_nhwc", x, map_ptr(weight, {32, 3, 3, 3}, op, "weight"), scale, shift,
+                       {n, (h - 1) / 2 + 1, (w - 1) / 2 + 1, 32},
+                       [&](auto... p) { return estd_stem3x3s2_nhwc(p..., n, h, w, cur_stream()); });
+}
+
+Tensor conv2d_small_nhwc(const Tensor& x, const Tensor& w_packed, const Tensor& scale, const Tensor& shift, int64_t cout, int64_t ksize,
+                         int64_t stride, bool relu)
+{
+    const char* op = "conv2d_small_nhwc";
+    const OpScope scope(x);
+    map_ptr(x, {-1, -1, -1, -1}, op, "x");
+    const int64_t n = x.size(-4), h = x.size(-3), w = x.size(-2), cin = x.size(-1);
+    // (the weight count below divides by these)
+    TORCH_CHECK((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2) && cout > 0 && cout % 16 == 0 && cin % 16 == 0,
+                "conv2d_small_nhwc: ksize 1|3, stride 1|2, the channel counts of x and cout multiples of 16");
+    const float* wp = floats_ptr(w_packed, cout / 16 * ksize * ksize * (cin / 16) * 256, op, "w_packed");
+    const int64_t pad = ksize / 2;
+    return packed_conv(op, "estd_conv2d_small_nhwc", x, wp, scale, shift, {n, (h + 2 * pad - ksize) / stride + 1, (w + 2 * pad - ksize) / stride + 1, cout},
+                       [&](auto... p) {
+                           return estd_conv2d_small_nhwc(p..., (int)n, (int)h, (int)w, (int)cin, (int)cout, (int)ksize, (int)stride, relu ? 1 : 0,
+                                                         cur_stream());
+                       });
+}
+
+Tensor conv2d_k3_to16_nhwc(const Tensor& x, const Tensor& w_packed, const Tensor& scale, const Tensor& shift, bool upsample)
+{
+    const char* op = "conv2d_k3_to16_nhwc";
+    const OpScope scope(x);
+    map_ptr(x, {-1, -1, -1, -1}, op, "x");
+    const int64_t n = x.size(-4), c = x.size(-1), h = (upsample ? 2 : 1) * x.size(-3), w = (upsample ? 2 : 1) * x.size(-2);
+    TORCH_CHECK(c == 16 || c == 32, "conv2d_k3_to16_nhwc: x must have 16 or 32 channels, got ", c);      // (the weight count depends on it)
+    const float* wp = floats_ptr(w_packed, 9 * (c / 16) * 256, op, "w_packed");
+    return packed_conv(op, "estd_conv2d_k3_to16_nhwc", x, wp, scale, shift, {n, h, w, 16}, [&](auto... p) {
+        return estd_conv2d_k3_to16_nhwc(p..., (int)n, (int)h, (int)w, (int)c, upsample ? 1 : 0, cur_stream());
+    });
 }
 
 Tensor maxpool3x3s2_nhwc(const Tensor& x)
 {
     const OpScope scope(x);
-    TORCH_CHECK(x.dim() == 4 && x.size(3) % 4 == 0, "maxpool3x3s2_nhwc: NHWC x [N,H,W,C], C a multiple of 4, expected");
-    const int64_t n = x.size(0), h = x.size(1), w = x.size(2), c = x.size(3);
+    const float* xp = map_ptr(x, {-1, -1, -1, -1}, "maxpool3x3s2_nhwc", "x");
+    const int64_t n = x.size(-4), h = x.size(-3), w = x.size(-2), c = x.size(-1);
     Tensor out = new_f32({n, (h - 1) / 2 + 1, (w - 1) / 2 + 1, c}, x);
-    check_status(estd_maxpool3x3s2_nhwc(fptr(x, "x"), out.data_ptr<float>(), (int)n, (int)h, (int)w, (int)c, cur_stream()), "estd_maxpool3x3s2_nhwc");
+    ESTD_LAUNCH(estd_maxpool3x3s2_nhwc, xp, out.data_ptr<float>(), (int)n, (int)h, (int)w, (int)c);
     return out;
 }
 
 Tensor avgpool_nhwc(const Tensor& x, int64_t k)
 {
     const OpScope scope(x);
-    TORCH_CHECK(x.dim() == 4 && x.size(3) % 4 == 0 && k >= 1 && k <= x.size(1) && k <= x.size(2),
-                "avgpool_nhwc: NHWC x [N,H,W,C], C a multiple of 4, 1 <= k <= min(H, W) expected");
-    const int64_t n = x.size(0), h = x.size(1), w = x.size(2), c = x.size(3);
+    const float* xp = map_ptr(x, {-1, -1, -1, -1}, "avgpool_nhwc", "x");
+    const int64_t n = x.size(-4), h = x.size(-3), w = x.size(-2), c = x.size(-1);
+    check_count(k, 1, std::min(h, w), "avgpool_nhwc", "k");                      // (the output size divides by it)
     Tensor out = new_f32({n, h / k, w / k, c}, x);
-    check_status(estd_avgpool_nhwc(fptr(x, "x"), out.data_ptr<float>(), (int)n, (int)h, (int)w, (int)c, (int)k, cur_stream()), "estd_avgpool_nhwc");
-    return out;
-}
-
-Tensor conv2d_small_nhwc(const Tensor& x, const Tensor& w_packed, const Tensor& scale, const Tensor& shift, int64_t cout, int64_t ksize,
-                         int64_t stride, bool relu)
-{
-    const OpScope scope(x);
-    TORCH_CHECK(x.dim() == 4, "conv2d_small_nhwc: NHWC x expected");
-    const int64_t n = x.size(0), h = x.size(1), w = x.size(2), cin = x.size(3);
-    TORCH_CHECK((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2) && cout > 0 && cout % 16 == 0 && cin % 16 == 0,
-                "conv2d_small_nhwc: ksize 1|3, stride 1|2, channel counts multiples of 16");
-    TORCH_CHECK(w_packed.numel() == cout / 16 * ksize * ksize * (cin / 16) * 256 && scale.numel() == cout && shift.numel() == cout,
-                "conv2d_small_nhwc: packed weights [cout/16][taps][cin/16][64][4] and scale/shift [cout] expected");
-    const int64_t pad = ksize / 2, ho = (h + 2 * pad - ksize) / stride + 1, wo = (w + 2 * pad - ksize) / stride + 1;
-    Tensor out = new_f32({n, ho, wo, cout}, x);
-    check_status(estd_conv2d_small_nhwc(fptr(x, "x"), fptr(w_packed, "packed weights"), fptr(scale, "scale"), fptr(shift, "shift"),
-                                        out.data_ptr<float>(), (int)n, (int)h, (int)w, (int)cin, (int)cout, (int)ksize, (int)stride, relu ? 1 : 0,
-                                        cur_stream()), "estd_conv2d_small_nhwc");
-    return out;
-}
-
-Tensor conv2d_k3_to16_nhwc(const Tensor& x, const Tensor& w_packed, const Tensor& scale, const Tensor& shift, bool upsample)
-{
-    const OpScope scope(x);
-    TORCH_CHECK(x.dim() == 4 && (x.size(3) == 16 || x.size(3) == 32), "conv2d_k3_to16_nhwc: NHWC x with 16 or 32 channels expected");
-    const int64_t n = x.size(0), c = x.size(3), h = (upsample ? 2 : 1) * x.size(1), w = (upsample ? 2 : 1) * x.size(2);
-    TORCH_CHECK(w_packed.numel() == 9 * (c / 16) * 64 * 4 && scale.numel() == 16 && shift.numel() == 16,
-                "conv2d_k3_to16_nhwc: packed weights [9][cin/16][64][4] and scale/shift [16] expected");
-    Tensor out = new_f32({n, h, w, 16}, x);
-    check_status(estd_conv2d_k3_to16_nhwc(fptr(x, "x"), fptr(w_packed, "packed weights"), fptr(scale, "scale"), fptr(shift, "shift"),
-                                          out.data_ptr<float>(), (int)n, (int)h, (int)w, (int)c, upsample ? 1 : 0, cur_stream()),
-                 "estd_conv2d_k3_to16_nhwc");
+    ESTD_LAUNCH(estd_avgpool_nhwc, xp, out.data_ptr<float>(), (int)n, (int)h, (int)w, (int)c, (int)k);
     return out;
 }
 
 Tensor normalise_nhwc(const Tensor& imgs)
 {
     const OpScope scope(imgs);
-    TORCH_CHECK(imgs.dim() == 4 && imgs.size(1) == 3, "normalise_nhwc: [N,3,H,W] images expected");
-    const int64_t n = imgs.size(0), h = imgs.size(2), w = imgs.size(3);
+    const float* in = map_ptr(imgs, {-1, 3, -1, -1}, "normalise_nhwc", "imgs");
+    const int64_t n = imgs.size(-4), h = imgs.size(-2), w = imgs.size(-1);
     Tensor out = new_f32({n, h, w, 3}, imgs);
-    check_status(estd_normalise_nhwc(fptr(imgs, "imgs"), out.data_ptr<float>(), (int)n, h * w, cur_stream()), "estd_normalise_nhwc");
-    return out;
-}
-
-Tensor stem3x3s2_nhwc(const Tensor& x, const Tensor& weight, const Tensor& scale, const Tensor& shift)
-{
-    const OpScope scope(x);
-    TORCH_CHECK(x.dim() == 4 && x.size(3) == 3 && weight.dim() == 4 && weight.size(0) == 32 && weight.size(1) == 3 && weight.size(2) == 3 &&
-                weight.size(3) == 3 && scale.numel() == 32 && shift.numel() == 32,
-                "stem3x3s2_nhwc: NHWC x [N,H,W,3], weight [32,3,3,3], scale/shift [32] expected");
-    const int64_t n = x.size(0), h = x.size(1), w = x.size(2);
-    Tensor out = new_f32({n, (h - 1) / 2 + 1, (w - 1) / 2 + 1, 32}, x);
-    check_status(estd_stem3x3s2_nhwc(fptr(x, "x"), fptr(weight, "weight"), fptr(scale, "scale"), fptr(shift, "shift"), out.data_ptr<float>(), (int)n,
-                                     (int)h, (int)w, cur_stream()), "estd_stem3x3s2_nhwc");
+    ESTD_LAUNCH(estd_normalise_nhwc, in, out.data_ptr<float>(), (int)n, h * w);
     return out;
 }
 
 Tensor nhwc_to_planes(const Tensor& x)
 {
     const OpScope scope(x);
-    TORCH_CHECK(x.dim() == 4, "nhwc_to_planes: NHWC x [N,H,W,C] expected");
-    const int64_t n = x.size(0), h = x.size(1), w = x.size(2), c = x.size(3);
+    const float* xp = map_ptr(x, {-1, -1, -1, -1}, "nhwc_to_planes", "x");
+    const int64_t n = x.size(-4), h = x.size(-3), w = x.size(-2), c = x.size(-1);
     Tensor out = new_f32({n, c, h, w}, x);
-    check_status(estd_nhwc_to_planes(fptr(x, "x"), (int)c, out.data_ptr<float>(), (int)n, h * w, cur_stream()), "estd_nhwc_to_planes");
+    ESTD_LAUNCH(estd_nhwc_to_planes, xp, (int)c, out.data_ptr<float>(), (int)n, h * w);
     return out;
 }
 
 Tensor planes_cat_nhwc(const Tensor& a, const Tensor& b, bool relu_b)
 {
+    const char* op = "planes_cat_nhwc";
     const OpScope scope(a);
-    TORCH_CHECK(a.dim() == 4 && b.dim() == 4 && a.size(0) == b.size(0) && a.size(2) == b.size(2) && a.size(3) == b.size(3),
-                "planes_cat_nhwc: two NCHW stacks of the same N, H, W expected");
-    const int64_t n = a.size(0), ca = a.size(1), cb = b.size(1), h = a.size(2), w = a.size(3);
+    const float* ap = map_ptr(a, {-1, -1, -1, -1}, op, "a");
+    const int64_t n = a.size(-4), ca = a.size(-3), h = a.size(-2), w = a.size(-1);
+    const float* bp = map_ptr(b, {n, -1, h, w}, op, "b");
+    const int64_t cb = b.size(-3);
     Tensor out = new_f32({n, h, w, ca + cb}, a);
-    check_status(estd_planes_cat_nhwc(fptr(a, "a"), (int)ca, fptr(b, "b"), (int)cb, relu_b ? 1 : 0, out.data_ptr<float>(), (int)n, h * w,
-                                      cur_stream()), "estd_planes_cat_nhwc");
+    ESTD_LAUNCH(estd_planes_cat_nhwc, ap, (int)ca, bp, (int)cb, relu_b ? 1 : 0, out.data_ptr<float>(), (int)n, h * w);
     return out;
 }
 
 Tensor upsample2_cat_nhwc(const Tensor& x, const Tensor& skip)
 {
+    const char* op = "upsample2_cat_nhwc";
     const OpScope scope(x);
-    TORCH_CHECK(x.dim() == 4 && skip.dim() == 4 && x.size(0) == skip.size(0) && 2 * x.size(1) == skip.size(1) && 2 * x.size(2) == skip.size(2),
-                "upsample2_cat_nhwc: NHWC x [N,H/2,W/2,Cx] and skip [N,H,W,Cs] expected");
-    const int64_t n = skip.size(0), h = skip.size(1), w = skip.size(2), cx = x.size(3), cs = skip.size(3);
+    const float* xp = map_ptr(x, {-1, -1, -1, -1}, op, "x");
+    const int64_t n = x.size(-4), h = 2 * x.size(-3), w = 2 * x.size(-2), cx = x.size(-1);
+    const float* sp = map_ptr(skip, {n, h, w, -1}, op, "skip");
+    const int64_t cs = skip.size(-1);
     Tensor out = new_f32({n, h, w, cx + cs}, x);
-    check_status(estd_upsample2_cat_nhwc(fptr(x, "x"), (int)cx, fptr(skip, "skip"), (int)cs, out.data_ptr<float>(), (int)n, (int)h, (int)w,
-                                         cur_stream()), "estd_upsample2_cat_nhwc");
+    ESTD_LAUNCH(estd_upsample2_cat_nhwc, xp, (int)cx, sp, (int)cs, out.data_ptr<float>(), (int)n, (int)h, (int)w);
     return out;
 }
 
 Tensor disp_head_nhwc(const Tensor& x, const Tensor& weight, const Tensor& bias, double depth_max, int64_t upscale)
 {
+    const char* op = "disp_head_nhwc";
     const OpScope scope(x);
-    TORCH_CHECK(x.dim() == 4 && weight.dim() == 4 && weight.size(0) == 1 && weight.size(1) == x.size(3) && weight.size(2) == 3 &&
-                weight.size(3) == 3 && bias.numel() == 1, "disp_head_nhwc: NHWC x [N,H,W,C], weight [1,C,3,3], bias [1] expected");
-    TORCH_CHECK(upscale == 1 || upscale == 2, "disp_head_nhwc: upscale must be 1 or 2");
-    const int64_t n = x.size(0), h = x.size(1), w = x.size(2), c = x.size(3);
+    const float* xp = map_ptr(x, {-1, -1, -1, -1}, op, "x");
+    const int64_t n = x.size(-4), h = x.size(-3), w = x.size(-2), c = x.size(-1);
+    const float *wp = map_ptr(weight, {1, c, 3, 3}, op, "weight"), *bp = floats_ptr(bias, 1, op, "bias");
     Tensor out = new_f32({n, 1, upscale * h, upscale * w}, x);
-    check_status(estd_disp_head_nhwc(fptr(x, "x"), fptr(weight, "weight"), fptr(bias, "bias"), (float)depth_max, out.data_ptr<float>(), (int)n,
-                                     (int)h, (int)w, (int)c, (int)upscale, cur_stream()), "estd_disp_head_nhwc");
+    ESTD_LAUNCH(estd_disp_head_nhwc, xp, wp, bp, (float)depth_max, out.data_ptr<float>(), (int)n, (int)h, (int)w, (int)c, (int)upscale);
     return out;
 }
 
+// ------------------------------------------------------------------------------------------------ layout converters
 void cdhw_to_vol(const Tensor& src, Tensor dst, int64_t dst_stride, int64_t dst_off)
 {
+    const char* op = "cdhw_to_vol";
     const OpScope scope(src);
-    TORCH_CHECK(src.dim() >= 2, "cdhw_to_vol: src must be [C, ...]");
+    const float* sp = fptr(src, "src", true, op);
+    TORCH_CHECK(src.dim() >= 2 && src.size(0) >= 1, op, ": src must be [C, ...] with C >= 1, got ", src.sizes());
     const int64_t C = src.size(0), S = src.numel() / C;
-    TORCH_CHECK(dst.numel() >= S * dst_stride, "cdhw_to_vol: destination too small");
-    check_status(estd_cdhw_to_vol(fptr(src, "volume"), fptr_mut(dst, "destination", false), (int)C, S, (int)dst_stride, (int)dst_off, cur_stream()),
-                 "estd_cdhw_to_vol");
+    check_count(dst_off, 0, dst_stride, op, "dst_off");                      // (estd_cdhw_to_vol checks its upper end only)
+    const float* dp = floats_ptr(dst, S * dst_stride, op, "dst", true, true);
+    ESTD_LAUNCH(estd_cdhw_to_vol, sp, mut(dp), (int)C, S, (int)dst_stride, (int)dst_off);
 }
 
 Tensor vol_to_cdhw(const Tensor& src, int64_t C, at::IntArrayRef dims, int64_t src_stride, int64_t src_off)
 {
+    const char* op = "vol_to_cdhw";
     const OpScope scope(src);
-    TORCH_CHECK(dims.size() == 3, "vol_to_cdhw: dims = (D, H, W)");
+    check_count((int64_t)dims.size(), 3, 3, op, "dims");
     const int64_t S = dims[0] * dims[1] * dims[2];
-    TORCH_CHECK(src.numel() >= S * src_stride, "vol_to_cdhw: source too small");
+    check_count(src_off, 0, src_stride, op, "src_off");                      // (estd_vol_to_cdhw checks its upper end only)
+    const float* sp = floats_ptr(src, S * src_stride, op, "src", true, true);
     Tensor out = new_f32({C, dims[0], dims[1], dims[2]}, src);
-    check_status(estd_vol_to_cdhw(fptr(src, "source", false), out.data_ptr<float>(), (int)C, S, (int)src_stride, (int)src_off, cur_stream()),
-                 "estd_vol_to_cdhw");
+    ESTD_LAUNCH(estd_vol_to_cdhw, sp, out.data_ptr<float>(), (int)C, S, (int)src_stride, (int)src_off);
     return out;
 }
 
@@ -1098,11 +1173,11 @@ int64_t conv3d_grid(int64_t N, int64_t D, int64_t H, int64_t W)
 TORCH_LIBRARY(estdepth_hip, m)
 {
     m.def("cam_pair_proj(Tensor src_proj, Tensor ref_proj) -> Tensor");
-    m.def("cam_sweep_proj(Tensor ref_pose, Tensor src_pose, Tensor cam_intr) -> Tensor");
-    m.def("cam_volume_mats(Tensor pose_j, Tensor? pose_i, Tensor cam_intr, Tensor(a!) out) -> ()");
-    m.def("homo_warping(Tensor src_fea, Tensor proj12, Tensor depth_values, int D) -> Tensor");
-    m.def("homo_warping_px(Tensor src_fea, Tensor proj12, Tensor depth_dhw) -> Tensor");
-    m.def("mix1x1(Tensor feature, Tensor weight, Tensor? bias) -> Tensor");
+    m.def("cam_sweep_proj(Tensor ref_pose, Tensor src_pose, Tensor intr) -> Tensor");
+    m.def("cam_volume_mats(Tensor pose_j, Tensor? pose_i, Tensor intr, Tensor(a!) out) -> ()");
+    m.def("homo_warping(Tensor src_chw, Tensor proj12, Tensor depth_values, int D) -> Tensor");
+    m.def("homo_warping_px(Tensor src_chw, Tensor proj12, Tensor depth_dhw) -> Tensor");
+    m.def("mix1x1(Tensor in_chw, Tensor w, Tensor? bias) -> Tensor");
     m.def("homo_warp_costvol(Tensor src_mix, Tensor ref_mix, Tensor proj12, Tensor depth_values, int D, Tensor(a!) out) -> ()");
     m.def("conv3d_k3(Tensor x, Tensor? x_extra, Tensor? w_main, Tensor? w_extra, Tensor? w_xout, Tensor? w_alt, Tensor scale, Tensor shift, "
           "int[] dims, int cin_main, int in_stride, int n_tiles, int act_a, int act_b, int act_split, Tensor(a!)? out, int out_stride, "
@@ -1113,8 +1188,8 @@ TORCH_LIBRARY(estdepth_hip, m)
           "bool relu_before_residual, bool relu_after_residual, Tensor? residual, int variant) -> Tensor");
     m.def("groupnorm_finalize(Tensor partials, int n_blocks, float count, float eps) -> Tensor");
     m.def("softargmin_up(Tensor logits, Tensor depth_values, int scale) -> (Tensor, Tensor)");
-    m.def("warp_volume(Tensor feat_volume, Tensor mats30, Tensor depth_values, float depth_min, float depth_interval) -> Tensor");
-    m.def("warp_volume_ex(Tensor feat_volume, Tensor mats30, Tensor depth, bool depth_per_voxel, float depth_min, float depth_interval, "
+    m.def("warp_volume(Tensor vol, Tensor mats30, Tensor depth, float depth_min, float depth_interval) -> Tensor");
+    m.def("warp_volume_ex(Tensor vol, Tensor mats30, Tensor depth, bool depth_per_voxel, float depth_min, float depth_interval, "
           "bool use_disp, float disp_min, float disp_interval, bool border, float padding_value) -> Tensor");
     m.def("warp_attention(Tensor kv_target, Tensor[] kv_sources, Tensor mats, Tensor depth_values, float depth_min, float depth_interval) -> Tensor");
     m.def("attention_prewarped(Tensor kv_target, Tensor[] kv_sources) -> Tensor");

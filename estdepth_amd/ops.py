@@ -1,6 +1,11 @@
 """Torch-tensor front-end of the C ABI (device memory, streams and allocation are PyTorch-ROCm's;
 the arithmetic is libestd_hip.so's).  Every function enqueues on the current HIP stream and
 returns tensors owned by the caching allocator.  CUDA(ROCm)-only: CPU tensors raise RuntimeError.
+
+Arguments are checked before anything is launched, by one helper per kind of rule ("argument checks" below); csrc/torch_ops.cpp has the
+same helpers and every operator outside the convolution plans calls them in the same order under both bindings, so a call either runs
+under both or raises RuntimeError, naming the operator and the argument, under both.  Value rules the C ABI enforces itself (strides,
+channel multiples, 32-bit limits) come back as its status, a RuntimeError as well.
 """
 import collections
 import ctypes
@@ -14,10 +19,11 @@ from . import packing
 
 # Binding of the hot-path operators:
 #   "torch"  (default) -- PyTorch custom operators torch.ops.estdepth_hip.* registered with TORCH_LIBRARY by
-#             csrc/torch_ops.cpp (libestd_torch_ops.so): dispatcher, TORCH_CHECK validation, at::empty outputs, current
-#             HIP stream taken in C++;
+#             csrc/torch_ops.cpp (libestd_torch_ops.so): dispatcher, argument checks and at::empty outputs in C++, on the current
+#             HIP stream of the first tensor's device;
 #   "ctypes" -- the torch-free C ABI of libestd_hip.so called directly with raw device pointers (what a non-PyTorch host
-#             would bind; kept as the second test path: ESTD_BINDING=ctypes).
+#             would bind; kept as the second test path: ESTD_BINDING=ctypes), after the same argument checks in Python, under
+#             torch.cuda.device(<the first tensor's device>).
 # Both end in the same extern "C" entry points; there is no CPU / eager fallback under either.
 BINDING = os.environ.get("ESTD_BINDING", "torch")
 _TORCH_OPS_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libestd_torch_ops.so")
@@ -52,7 +58,8 @@ PROFILE = None
 
 
 class _Prof:
-    """HIP-event pair around one launch (events are recorded on torch's CURRENT stream = the launch stream)."""
+    """HIP-event pair around one launch (events are recorded on torch's CURRENT stream = the launch stream).  ``amount``: a number, or
+    a function that gives it once the launch has returned (it may read shapes the operator has checked by then)."""
     __slots__ = ("group", "amount", "e0")
 
     def __init__(self, group, amount):
@@ -65,10 +72,10 @@ class _Prof:
         return self
 
     def __exit__(self, *exc):
-        if self.e0 is not None and PROFILE is not None:
+        if self.e0 is not None and PROFILE is not None and exc[0] is None:
             e1 = torch.cuda.Event(enable_timing=True)
             e1.record(torch.cuda.current_stream())
-            PROFILE.append((self.group, float(self.amount), self.e0, e1))
+            PROFILE.append((self.group, float(self.amount() if callable(self.amount) else self.amount), self.e0, e1))
         return False
 
 # Arithmetic of the plain 32->32 3x3x3 convolutions: "f32" = v_mfma_f32_16x16x4_f32 (csrc/conv3d_mfma.hip),
@@ -103,14 +110,20 @@ def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def _chk(t, name, dtype=torch.float32):
+def _chk(t, name, dtype=torch.float32, op=None, dev=None, contiguous=True):
+    """``t`` is a contiguous ``dtype`` tensor on a device (``dev``: on that one) -> t; ``op``: the operator's name, put in front of the
+    message (the helpers of the argument checks pass it).  csrc/torch_ops.cpp: fptr()."""
+    if op is not None:
+        name = "%s: %s" % (op, name)
     if not isinstance(t, torch.Tensor):
         raise RuntimeError("%s must be a tensor" % name)
     if not t.is_cuda:
         raise RuntimeError("%s must live on a ROCm device (estdepth_amd has no CPU path); got %s" % (name, t.device))
+    if dev is not None and t.device != dev:
+        raise RuntimeError("%s is on %s but the operator runs on %s" % (name, t.device, dev))
     if t.dtype != dtype:
         raise RuntimeError("%s must be %s, got %s" % (name, dtype, t.dtype))
-    if not t.is_contiguous():
+    if contiguous and not t.is_contiguous():
         raise RuntimeError("%s must be contiguous" % name)
     return t
 
@@ -142,94 +155,224 @@ def profile_mark(idx):
     N.check(N.lib().estd_profile_mark(int(idx), _stream()), "estd_profile_mark")
 
 
+# ---------------------------------------------------------------------------------- argument checks
+# One helper per kind of check for the ctypes front ends of every operator but the convolution plans' (csrc/torch_ops.cpp has the same
+# set for the torch binding, and each operator calls them in the same order there); each takes the operator's and the argument's name
+# for its message.
+def _volume(volume, op):
+    """the volume argument: two float32 planes (D, weight), contiguous, on a device, X % 4 == 0 -> (Z, Y, X, address of the weight plane)"""
+    _need(isinstance(volume, torch.Tensor) and volume.dim() == 4 and volume.shape[0] == 2, "%s: volume must be [2,Z,Y,X] (D plane, weight plane)" % op)
+    _chk(volume, "volume", op=op)
+    Z, Y, X = volume.shape[1:]
+    _need(X % 4 == 0, "%s: X must be a multiple of 4, got %d" % (op, X))
+    return Z, Y, X, volume.data_ptr() + 4 * Z * Y * X
+
+
+def _color_planes(color, volume, op):
+    _need(isinstance(color, torch.Tensor) and color.dim() == 4 and color.shape[0] == 3 and tuple(color.shape[1:]) == tuple(volume.shape[1:]),
+          "%s: color must be [3,Z,Y,X] with the volume's Z, Y, X" % op)
+    _chk(color, "color", op=op)
+    _need(color.device == volume.device, "%s: color is on %s but the volume on %s" % (op, color.device, volume.device))
+
+
+def _host_values(t, n, op, name, shape, finite=False):
+    """host values of the launch arguments: exactly ``n`` of them (``finite``: none NaN or infinite) -> the values as a list"""
+    _need(isinstance(t, torch.Tensor) and not t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n,
+          "%s: %s must be a contiguous CPU float32 tensor %s" % (op, name, shape))
+    flat = t.reshape(-1).tolist()
+    _need(not finite or all(math.isfinite(v) for v in flat), "%s: %s holds a value that is not finite" % (op, name))
+    return flat
+
+
+def _map(t, tail, op, name, dev=None):
+    """``t`` is a float32 device map whose last sizes are ``tail`` (-1: any size), leading 1s allowed, on ``dev`` -> its last sizes"""
+    _chk(t, name, op=op, dev=dev)
+    got = tuple(t.shape[-len(tail):])
+    _need(t.dim() >= len(tail) and all(w < 0 or w == g for w, g in zip(tail, got)) and t.numel() == math.prod(got),
+          "%s: %s must end in the sizes %s (-1: any; leading 1s allowed), got %s" % (op, name, tail, tuple(t.shape)))
+    return got
+
+
+def _map_size(H, W, op, name, least=1):
+    _need(H >= least and W >= least and H * W <= 0x7fffffff, "%s: %s must be at least %d x %d (and H * W < 2^31), got %d x %d" % (op, name, least, least, H, W))
+
+
+def _floats(t, n, op, name, dev=None, at_least=False, strided=False):
+    """``t`` is a float32 tensor on ``dev`` that holds exactly (``at_least``: at least) ``n`` floats, whatever its shape; ``strided``: the
+    base of wider records, which need not be contiguous -> t"""
+    _chk(t, name, op=op, dev=dev, contiguous=not strided)
+    _need(t.numel() >= n if at_least else t.numel() == n,
+          "%s: %s must hold %s %d floats, got %d" % (op, name, "at least" if at_least else "exactly", n, t.numel()))
+    return t
+
+
+def _records(t, op, name):
+    """``t`` is a float32 device tensor of whole 32-float records (voxels) and nothing else -> their number"""
+    n_vox = t.numel() // 32 if isinstance(t, torch.Tensor) else 0
+    _floats(t, n_vox * 32, op, name)
+    return n_vox
+
+
+def _opt_floats(t, n, op, name, dev):
+    """an optional vector (a per-channel scale, shift or bias; a second pose): None, or exactly ``n`` floats -> t"""
+    return None if t is None else _floats(t, n, op, name, dev)
+
+
+def _like(ts, first, op, name, dev):
+    """a list of float32 tensors on ``dev``, each of ``first``'s shape -> their addresses"""
+    for i, t in enumerate(ts):
+        _chk(t, "%s[%d]" % (name, i), op=op, dev=dev)
+        _need(t.shape == first.shape, "%s: %s[%d] has another shape than the first tensor: %s for %s" % (op, name, i, tuple(t.shape), tuple(first.shape)))
+    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+def _channels_last(t, op, name, dev=None, like=None):
+    """bn_act_nhwc_'s tensors: float32 [N,C,H,W] in channels_last memory on ``dev`` (``like``: and of that tensor's shape) -> (N, C, H, W)"""
+    _chk(t, name, op=op, dev=dev, contiguous=False)
+    _need(t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last),
+          "%s: %s must be [N,C,H,W] in channels_last memory, got %s with the strides %s" % (op, name, tuple(t.shape), t.stride()))
+    _need(like is None or t.shape == like.shape, "%s: %s must have the shape %s, got %s" % (op, name, like is not None and tuple(like.shape), tuple(t.shape)))
+    return tuple(t.shape)
+
+
+def _count(v, lo, hi, op, name):
+    """a count (tensors of a list, a window, a stride the front end divides by) within lo..hi"""
+    _need(lo <= v <= hi, "%s: %s: at least %d and at most %d expected, got %r" % (op, name, lo, hi, v))
+
+
+def _ivec(t, op, name, dev, size=None, dtype=torch.int64):
+    _need(isinstance(t, torch.Tensor) and t.dim() == 1 and t.dtype == dtype and t.is_contiguous() and t.device == dev
+          and (size is None or t.shape[0] == size),
+          "%s: %s must be a contiguous %s vector%s on the operator's device" % (op, name, dtype, "" if size is None else " [%d]" % size))
+
+
+# the four rules for a scalar that a kernel takes as fp32
+def _positive(v, op, name):
+    _need(math.isfinite(v) and ctypes.c_float(v).value > 0, "%s: %s must be positive and finite, got %r" % (op, name, v))
+
+
+def _not_negative(v, op, name):
+    _need(math.isfinite(v) and v >= 0, "%s: %s must be finite and not negative, got %r" % (op, name, v))
+
+
+def _not_nan(v, op, name):
+    _need(v == v, "%s: %s must not be NaN" % (op, name))
+
+
+def _positive_square(v, op, name, square_positive=False):
+    """positive and finite, and its square finite in fp32 (``square_positive``: and not rounded to 0)"""
+    v32 = ctypes.c_float(v).value if math.isfinite(v) else float("nan")
+    sq = ctypes.c_float(v32 * v32).value
+    _need(v32 > 0 and math.isfinite(sq) and (sq > 0 or not square_positive),
+          "%s: %s (and its square in fp32) must be positive and finite, got %r" % (op, name, v))
+
+
+def _launch(dev, entry, *args):
+    """Every entry point takes the stream last: one launch of ``entry`` (a function of N.lib()) on the current stream of ``dev``, the
+    operator's device (not of whatever device is current), its status translated."""
+    with torch.cuda.device(dev):
+        N.check(entry(*args, _stream()), entry.__name__)
+
+
 # ---------------------------------------------------------------------------------- camera algebra
 def cam_pair_proj(src_proj, ref_proj):
     """rot|trans of src_proj @ inverse(ref_proj) for one batch element -> [12]."""
     if _use_torch():
         return T().cam_pair_proj(src_proj, ref_proj)
-    out = torch.empty(12, device=src_proj.device, dtype=torch.float32)
-    N.check(N.lib().estd_cam_pair_proj(_p(_chk(src_proj, "src_proj")), _p(_chk(ref_proj, "ref_proj")), _p(out), _stream()),
-            "estd_cam_pair_proj")
+    op = "cam_pair_proj"
+    dev = _floats(src_proj, 16, op, "src_proj").device
+    _floats(ref_proj, 16, op, "ref_proj", dev)
+    out = torch.empty(12, device=dev)
+    _launch(dev, N.lib().estd_cam_pair_proj, _p(src_proj), _p(ref_proj), _p(out))
     return out
 
 
 def cam_sweep_proj(ref_pose, src_pose, intr):
     if _use_torch():
         return T().cam_sweep_proj(ref_pose, src_pose, intr)
-    out = torch.empty(12, device=ref_pose.device, dtype=torch.float32)
-    N.check(N.lib().estd_cam_sweep_proj(_p(_chk(ref_pose, "ref_pose")), _p(_chk(src_pose, "src_pose")),
-                                        _p(_chk(intr, "cam_intr")), _p(out), _stream()), "estd_cam_sweep_proj")
+    op = "cam_sweep_proj"
+    dev = _floats(ref_pose, 16, op, "ref_pose").device
+    _floats(src_pose, 16, op, "src_pose", dev)
+    _floats(intr, 9, op, "intr", dev)
+    out = torch.empty(12, device=dev)
+    _launch(dev, N.lib().estd_cam_sweep_proj, _p(ref_pose), _p(src_pose), _p(intr), _p(out))
     return out
 
 
 def cam_volume_mats(pose_j, pose_i, intr, out=None):
+    op = "cam_volume_mats"
     if out is None:
-        out = torch.empty(30, device=pose_j.device, dtype=torch.float32)
+        out = torch.empty(30, device=_chk(pose_j, "pose_j", op=op).device)
     if _use_torch():
         T().cam_volume_mats(pose_j, pose_i, intr, out)
         return out
-    N.check(N.lib().estd_cam_volume_mats(_p(_chk(pose_j, "pose_j")), _p(_chk(pose_i, "pose_i")) if pose_i is not None else None,
-                                         _p(_chk(intr, "cam_intr")), _p(out), _stream()), "estd_cam_volume_mats")
+    dev = _floats(pose_j, 16, op, "pose_j").device
+    _opt_floats(pose_i, 16, op, "pose_i", dev)
+    _floats(intr, 9, op, "intr", dev)
+    _floats(out, 30, op, "out", dev)
+    _launch(dev, N.lib().estd_cam_volume_mats, _p(pose_j), _p(pose_i), _p(intr), _p(out))
     return out
 
 
 # ---------------------------------------------------------------------------------- plane sweep
+def _homo_warp(op, entry, src_chw, proj12, depth, per_pixel, D):
+    """homo_warping_chw (``depth``: at least D plane depths) and homo_warping_px_chw (``per_pixel``: ``depth`` is [D,H,W], which gives D)
+    under the ctypes binding"""
+    C, H, W = _map(src_chw, (-1, -1, -1), op, "src_chw")
+    dev = src_chw.device
+    _floats(proj12, 12, op, "proj12", dev)
+    if per_pixel:
+        D = _map(depth, (-1, H, W), op, "depth_dhw", dev)[0]
+    else:
+        _floats(depth, D, op, "depth_values", dev, at_least=True)
+    out = torch.empty((C, D, H, W), device=dev)
+    _launch(dev, entry, _p(src_chw), _p(proj12), _p(depth), _p(out), C, D, H, W)
+    return out
+
+
 def homo_warping_chw(src_chw, proj12, depth_values, D):
     if _use_torch():
         return T().homo_warping(src_chw, proj12, depth_values, D)
-    _need(src_chw.dim() == 3, "homo_warping: src_fea must be [C,H,W]")
-    _need(depth_values.numel() >= D and _chk(proj12, "proj12").numel() == 12, "homo_warping: depth_values / proj12 size")
-    C, H, W = src_chw.shape
-    out = torch.empty((C, D, H, W), device=src_chw.device, dtype=torch.float32)
-    N.check(N.lib().estd_homo_warping(_p(_chk(src_chw, "src_fea")), _p(proj12), _p(_chk(depth_values, "depth_values")),
-                                      _p(out), C, D, H, W, _stream()), "estd_homo_warping")
-    return out
+    return _homo_warp("homo_warping", N.lib().estd_homo_warping, src_chw, proj12, depth_values, False, D)
 
 
 def homo_warping_px_chw(src_chw, proj12, depth_dhw):
     """per-pixel depth hypotheses [D,H,W] (homo_utils.py:462)."""
     if _use_torch():
         return T().homo_warping_px(src_chw, proj12, depth_dhw)
-    _need(src_chw.dim() == 3 and depth_dhw.dim() == 3, "homo_warping_px: src_fea [C,H,W], depth [D,H,W]")
-    C, H, W = src_chw.shape
-    D = depth_dhw.shape[0]
-    _need(tuple(depth_dhw.shape[1:]) == (H, W) and _chk(proj12, "proj12").numel() == 12, "homo_warping_px: depth / proj12 size")
-    out = torch.empty((C, D, H, W), device=src_chw.device, dtype=torch.float32)
-    N.check(N.lib().estd_homo_warping_px(_p(_chk(src_chw, "src_fea")), _p(proj12), _p(_chk(depth_dhw, "depth_values")),
-                                         _p(out), C, D, H, W, _stream()), "estd_homo_warping_px")
-    return out
+    return _homo_warp("homo_warping_px", N.lib().estd_homo_warping_px, src_chw, proj12, depth_dhw, True, 0)
 
 
 def mix1x1(in_chw, w, bias):
     """[Cin,H,W] -> [H,W,Cout] channel mix."""
     if _use_torch():
         return T().mix1x1(in_chw, w, bias)
-    _need(in_chw.dim() == 3 and w.dim() == 2 and w.shape[1] == in_chw.shape[0], "mix1x1: in [Cin,H,W], w [Cout,Cin]")
-    Cin, H, W = in_chw.shape
-    Cout = w.shape[0]
-    _need(bias is None or _chk(bias, "mix bias").numel() == Cout, "mix1x1: bias [Cout]")
-    out = torch.empty((H, W, Cout), device=in_chw.device, dtype=torch.float32)
-    N.check(N.lib().estd_mix1x1_chw_to_hwc(_p(_chk(in_chw, "feature")), _p(_chk(w, "mix weight")),
-                                           _p(bias) if bias is not None else None, _p(out), Cin, Cout, H * W, _stream()),
-            "estd_mix1x1_chw_to_hwc")
+    op = "mix1x1"
+    Cin, H, W = _map(in_chw, (-1, -1, -1), op, "in_chw")
+    dev = in_chw.device
+    Cout = _map(w, (-1, Cin), op, "w", dev)[0]
+    _opt_floats(bias, Cout, op, "bias", dev)
+    out = torch.empty((H, W, Cout), device=dev)
+    _launch(dev, N.lib().estd_mix1x1_chw_to_hwc, _p(in_chw), _p(w), _p(bias), _p(out), Cin, Cout, H * W)
     return out
 
 
 def homo_warp_costvol(src_mix, ref_mix, proj12, depth_values, D, out=None):
-    H, W, _ = src_mix.shape
+    op = "homo_warp_costvol"
     if out is None:
-        out = torch.empty((D, H, W, 32), device=src_mix.device, dtype=torch.float32)
-    with _Prof("homo_warp_costvol", 4.0 * 32 * H * W * (2 + D)):          # SURVEY §8d: src map + ref map + one volume
+        H, W, _ = _map(src_mix, (-1, -1, 32), op, "src_mix")
+        out = torch.empty((D, H, W, 32), device=src_mix.device)
+    with _Prof(op, lambda: 4.0 * src_mix.numel() * (2 + D)):          # SURVEY §8d: src map + ref map + one volume
         if _use_torch():
             T().homo_warp_costvol(src_mix, ref_mix, proj12, depth_values, D, out)
             return out
-        _need(src_mix.dim() == 3 and src_mix.shape[2] == 32 and ref_mix.shape == src_mix.shape,
-              "homo_warp_costvol: src_mix / ref_mix must be [H,W,32] of one shape")
-        _need(depth_values.numel() >= D and D >= 1 and _chk(proj12, "proj12").numel() == 12, "homo_warp_costvol: depth_values / proj12 size")
-        _need(_chk(out, "out").numel() == D * H * W * 32, "homo_warp_costvol: out must be [D,H,W,32]")
-        N.check(N.lib().estd_homo_warp_costvol(_p(_chk(src_mix, "src_mix")), _p(_chk(ref_mix, "ref_mix")), _p(proj12),
-                                               _p(_chk(depth_values, "depth_values")), _p(out), D, H, W, _stream()),
-                "estd_homo_warp_costvol")
+        H, W, _ = _map(src_mix, (-1, -1, 32), op, "src_mix")
+        dev = src_mix.device
+        _map(ref_mix, (H, W, 32), op, "ref_mix", dev)
+        _floats(proj12, 12, op, "proj12", dev)
+        _floats(depth_values, D, op, "depth_values", dev, at_least=True)
+        _floats(out, D * H * W * 32, op, "out", dev)
+        _launch(dev, N.lib().estd_homo_warp_costvol, _p(src_mix), _p(ref_mix), _p(proj12), _p(depth_values), _p(out), D, H, W)
     return out
 
 
@@ -585,41 +728,46 @@ def conv3d_grid(Nn, D, H, W):
 def groupnorm_finalize(partials, n_blocks, count, eps=1e-5):
     if _use_torch():
         return T().groupnorm_finalize(partials, n_blocks, float(count), float(eps))
-    _need(_chk(partials, "partials", torch.float64).numel() >= n_blocks * 4,
+    _need(_chk(partials, "partials", torch.float64, op="groupnorm_finalize").numel() >= n_blocks * 4,
           "groupnorm_finalize: partials must be a contiguous float64 ROCm tensor with 4 doubles per block")
     out = torch.empty(4, device=partials.device, dtype=torch.float32)
-    N.check(N.lib().estd_groupnorm_finalize(_p(partials), n_blocks, float(count), float(eps), _p(out), _stream()),
-            "estd_groupnorm_finalize")
+    _launch(partials.device, N.lib().estd_groupnorm_finalize, _p(partials), n_blocks, float(count), float(eps), _p(out))
     return out
 
 
 # ---------------------------------------------------------------------------------- soft-argmin
 def softargmin_up(logits, depth_values, scale=4):
     """logits [N,D,H,W] -> (depth, prob) each [N,1,scale*H,scale*W]."""
-    Nn, D, H, W = logits.shape
-    with _Prof("softargmin", 4.0 * Nn * H * W * (D + 2 * scale * scale)):       # logits in, depth + prob maps out
+    op = "softargmin_up"
+    with _Prof("softargmin", lambda: 4.0 * (logits.numel() // logits.shape[-3]) * (logits.shape[-3] + 2 * scale * scale)):   # logits in, depth + prob maps out
         if _use_torch():
             return T().softargmin_up(logits, depth_values, scale)
-        _need(depth_values.numel() >= D, "softargmin_up: one depth value per plane expected")
-        depth = torch.empty((Nn, 1, H * scale, W * scale), device=logits.device, dtype=torch.float32)
+        Nn, D, H, W = _map(logits, (-1, -1, -1, -1), op, "logits")
+        dev = logits.device
+        _floats(depth_values, D, op, "depth_values", dev, at_least=True)
+        depth = torch.empty((Nn, 1, H * scale, W * scale), device=dev)
         prob = torch.empty_like(depth)
-        N.check(N.lib().estd_softargmin_up(_p(_chk(logits, "logits")), _p(_chk(depth_values, "depth_values")), _p(depth), _p(prob),
-                                           Nn, D, H, W, scale, _stream()), "estd_softargmin_up")
+        _launch(dev, N.lib().estd_softargmin_up, _p(logits), _p(depth_values), _p(depth), _p(prob), Nn, D, H, W, scale)
     return depth, prob
 
 
 # ---------------------------------------------------------------------------------- EST fusion
+def _warp_vol(op, entry, vol, mats30, depth, depth_per_voxel, *scalars):
+    """warp_volume_cdhw and warp_volume_ex_cdhw under the ctypes binding; ``scalars``: the entry point's own arguments between the depths
+    and the output"""
+    C, D, H, W = _map(vol, (-1, -1, -1, -1), op, "vol")
+    dev = vol.device
+    _floats(mats30, 30, op, "mats30", dev)
+    _floats(depth, D * H * W if depth_per_voxel else D, op, "depth", dev, at_least=True)
+    out = torch.empty_like(vol)
+    _launch(dev, entry, _p(vol), _p(mats30), _p(depth), *scalars, _p(out), C, D, H, W)
+    return out
+
+
 def warp_volume_cdhw(vol, mats30, depth_values, depth_min, depth_interval):
     if _use_torch():
         return T().warp_volume(vol, mats30, depth_values, float(depth_min), float(depth_interval))
-    _need(vol.dim() == 4 and _chk(mats30, "mats30").numel() == 30, "warp_volume: vol [C,D,H,W], mats30 [30]")
-    C, D, H, W = vol.shape
-    _need(depth_values.numel() >= D, "warp_volume: one depth value per plane expected")
-    out = torch.empty_like(vol)
-    N.check(N.lib().estd_warp_volume(_p(_chk(vol, "feat_volume")), _p(mats30), _p(_chk(depth_values, "depth")),
-                                     float(depth_min), float(depth_interval), _p(out), C, D, H, W, _stream()),
-            "estd_warp_volume")
-    return out
+    return _warp_vol("warp_volume", N.lib().estd_warp_volume, vol, mats30, depth_values, False, float(depth_min), float(depth_interval))
 
 
 def warp_volume_ex_cdhw(vol, mats30, depth, depth_per_voxel, depth_min, depth_interval, disp_min=None, disp_interval=None,
@@ -633,75 +781,76 @@ def warp_volume_ex_cdhw(vol, mats30, depth, depth_per_voxel, depth_min, depth_in
     if _use_torch():
         return T().warp_volume_ex(vol, mats30, depth, bool(depth_per_voxel), float(depth_min), float(depth_interval), use_disp,
                                   dmin_, dint_, bool(border), float(padding_value))
-    _need(vol.dim() == 4 and _chk(mats30, "mats30").numel() == 30, "warp_volume: vol [C,D,H,W], mats30 [30]")
-    C, D, H, W = vol.shape
-    _need(depth.numel() >= (D * H * W if depth_per_voxel else D), "warp_volume: depth must hold one value per %s" %
-          ("voxel" if depth_per_voxel else "plane"))
-    out = torch.empty_like(vol)
     o = N.WarpVolumeOpts(int(bool(depth_per_voxel)), int(use_disp), int(bool(border)), float(depth_min), float(depth_interval),
                          dmin_, dint_, float(padding_value))
-    N.check(N.lib().estd_warp_volume_ex(_p(_chk(vol, "feat_volume")), _p(mats30), _p(_chk(depth, "depth")), ctypes.byref(o),
-                                        _p(out), C, D, H, W, _stream()), "estd_warp_volume_ex")
-    return out
+    return _warp_vol("warp_volume_ex", N.lib().estd_warp_volume_ex, vol, mats30, depth, depth_per_voxel, ctypes.byref(o))
 
 
 def warp_attention(kv_target, kv_sources, mats, depth_values, depth_min, depth_interval):
     """kv_target [D,H,W,32]; kv_sources list of the same; mats [n,30] -> xh [D,H,W,32] = [V_t | h]."""
-    D, H, W, _ = kv_target.shape
-    n = len(kv_sources)
-    with _Prof("warp_attention", 4.0 * 16 * D * H * W * (2 + 2 * n)):          # K_t, h out, K_j and V_j of every source
+    op = "warp_attention"
+    kv_sources = list(kv_sources)
+    with _Prof(op, lambda: 4.0 * 16 * (kv_target.numel() // 32) * (2 + 2 * len(kv_sources))):   # K_t, h out, K_j and V_j of every source
         if _use_torch():
-            return T().warp_attention(kv_target, list(kv_sources), mats, depth_values, float(depth_min), float(depth_interval))
-        _need(kv_target.dim() == 4 and kv_target.shape[3] == 32, "warp_attention: kv volumes must be [D,H,W,32]")
-        _need(all(k.shape == kv_target.shape for k in kv_sources), "warp_attention: a source has another shape than the target")
-        _need(_chk(mats, "mats").numel() == n * 30, "warp_attention: mats must be [n_src,30]")
-        _need(depth_values.numel() >= D, "warp_attention: one depth value per plane expected")
-        arr = (ctypes.c_void_p * n)(*[_chk(k, "kv source").data_ptr() for k in kv_sources])
-        xh = torch.empty((D, H, W, 32), device=kv_target.device, dtype=torch.float32)
-        N.check(N.lib().estd_warp_attention(_p(_chk(kv_target, "kv target")), arr, _p(_chk(mats, "mats")), n,
-                                            _p(_chk(depth_values, "depth_values")), float(depth_min), float(depth_interval),
-                                            _p(xh), D, H, W, _stream()), "estd_warp_attention")
+            return T().warp_attention(kv_target, kv_sources, mats, depth_values, float(depth_min), float(depth_interval))
+        D, H, W, _ = _map(kv_target, (-1, -1, -1, 32), op, "kv_target")
+        dev, n = kv_target.device, len(kv_sources)
+        _count(n, 1, MAX_ATTENTION_SOURCES, op, "kv_sources")
+        srcs = _like(kv_sources, kv_target, op, "kv_sources", dev)
+        _floats(mats, n * 30, op, "mats", dev)
+        _floats(depth_values, D, op, "depth_values", dev, at_least=True)
+        xh = torch.empty_like(kv_target)
+        _launch(dev, N.lib().estd_warp_attention, _p(kv_target), srcs, _p(mats), n, _p(depth_values), float(depth_min), float(depth_interval),
+                _p(xh), D, H, W)
     return xh
 
 
 def attention_prewarped(kv_target, kv_sources):
+    kv_sources = list(kv_sources)
     if _use_torch():
-        return T().attention_prewarped(kv_target, list(kv_sources))
-    n = len(kv_sources)
-    arr = (ctypes.c_void_p * n)(*[_chk(k, "kv source").data_ptr() for k in kv_sources])
+        return T().attention_prewarped(kv_target, kv_sources)
+    op = "attention_prewarped"
+    n_vox = _records(kv_target, op, "kv_target")
+    dev, n = kv_target.device, len(kv_sources)
+    _count(n, 1, MAX_ATTENTION_SOURCES, op, "kv_sources")
+    srcs = _like(kv_sources, kv_target, op, "kv_sources", dev)
     xh = torch.empty_like(kv_target)
-    N.check(N.lib().estd_attention_prewarped(_p(_chk(kv_target, "kv target")), arr, n, _p(xh), kv_target.numel() // 32,
-                                             _stream()), "estd_attention_prewarped")
+    _launch(dev, N.lib().estd_attention_prewarped, _p(kv_target), srcs, n, _p(xh), n_vox)
     return xh
 
 
 def gru_reset_apply(xh, ru, stats4, gamma_r, beta_r):
-    n_vox = xh.numel() // 32
-    with _Prof("gru_elementwise", 4.0 * 16 * n_vox * 2):       # SURVEY §8d K11+K13 = 5 x 16 channels per voxel: r, h here
+    op = "gru_reset_apply"
+    with _Prof("gru_elementwise", lambda: 4.0 * 16 * (xh.numel() // 32) * 2):       # SURVEY §8d K11+K13 = 5 x 16 channels per voxel: r, h here
         if _use_torch():
             return T().gru_reset_apply(xh, ru, stats4, gamma_r, beta_r)
-        _need(_chk(xh, "xh").numel() == _chk(ru, "ru").numel() and xh.numel() % 32 == 0, "gru_reset_apply: xh and ru are [D,H,W,32] volumes")
-        _need(_chk(stats4, "stats").numel() == 4 and _chk(gamma_r, "gamma").numel() == 16 and _chk(beta_r, "beta").numel() == 16,
-              "gru_reset_apply: stats [4], affine [16]")
+        n_vox = _records(xh, op, "xh")
+        dev = xh.device
+        _floats(ru, n_vox * 32, op, "ru", dev)
+        _floats(stats4, 4, op, "stats4", dev)
+        _floats(gamma_r, 16, op, "gamma_r", dev)
+        _floats(beta_r, 16, op, "beta_r", dev)
         xrh = torch.empty_like(xh)
-        N.check(N.lib().estd_gru_reset_apply(_p(xh), _p(ru), _p(stats4), _p(gamma_r), _p(beta_r), _p(xrh), n_vox, _stream()),
-                "estd_gru_reset_apply")
+        _launch(dev, N.lib().estd_gru_reset_apply, _p(xh), _p(ru), _p(stats4), _p(gamma_r), _p(beta_r), _p(xrh), n_vox)
     return xrh
 
 
 def gru_blend(xh, ru, o_raw, stats_ru, stats_o, gamma_u, beta_u, gamma_o, beta_o, out_value, out_stride):
-    n_vox = xh.numel() // 32
-    with _Prof("gru_elementwise", 4.0 * 16 * n_vox * 3):       # ... u, o_raw, out here (h counted once, in the reset pass)
+    op = "gru_blend"
+    with _Prof("gru_elementwise", lambda: 4.0 * 16 * (xh.numel() // 32) * 3):       # ... u, o_raw, out here (h counted once, in the reset pass)
         if _use_torch():
             return T().gru_blend(xh, ru, o_raw, stats_ru, stats_o, gamma_u, beta_u, gamma_o, beta_o, out_value, out_stride)
-        _need(_chk(xh, "xh").numel() == _chk(ru, "ru").numel() and _chk(o_raw, "o_raw").numel() == n_vox * 16,
-              "gru_blend: xh, ru [D,H,W,32]; o_raw [D,H,W,16]")
-        _need(all(_chk(t, "gru stats").numel() == 4 for t in (stats_ru, stats_o)) and
-              all(_chk(t, "gru affine").numel() == 16 for t in (gamma_u, beta_u, gamma_o, beta_o)), "gru_blend: stats [4], affine [16]")
-        _need(out_value.is_cuda and out_value.dtype == torch.float32 and out_value.numel() >= (n_vox - 1) * out_stride + 16,
-              "gru_blend: out_value must hold (n_vox - 1) * out_stride + 16 floats")
-        N.check(N.lib().estd_gru_blend(_p(xh), _p(ru), _p(o_raw), _p(stats_ru), _p(stats_o), _p(gamma_u), _p(beta_u),
-                                       _p(gamma_o), _p(beta_o), _p(out_value), out_stride, n_vox, _stream()), "estd_gru_blend")
+        n_vox = _records(xh, op, "xh")
+        dev = xh.device
+        _floats(ru, n_vox * 32, op, "ru", dev)
+        _floats(o_raw, n_vox * 16, op, "o_raw", dev)
+        for name, t in (("stats_ru", stats_ru), ("stats_o", stats_o)):
+            _floats(t, 4, op, name, dev)
+        for name, t in (("gamma_u", gamma_u), ("beta_u", beta_u), ("gamma_o", gamma_o), ("beta_o", beta_o)):
+            _floats(t, 16, op, name, dev)
+        _floats(out_value, (n_vox - 1) * out_stride + 16, op, "out_value", dev, at_least=True, strided=True)
+        _launch(dev, N.lib().estd_gru_blend, _p(xh), _p(ru), _p(o_raw), _p(stats_ru), _p(stats_o), _p(gamma_u), _p(beta_u), _p(gamma_o), _p(beta_o),
+                _p(out_value), out_stride, n_vox)
 
 
 # ---------------------------------------------------------------------------------- 2D backbone epilogues
@@ -709,43 +858,54 @@ def bn_act_nhwc_(x, scale, shift, relu, residual=None):
     """in place on an NCHW-shaped tensor in channels_last memory: x = act(x*scale[c] + shift[c] (+ residual))."""
     if _use_torch():
         return T().bn_act_nhwc_(x, scale, shift, bool(relu), residual)
-    if not x.is_cuda or x.dtype != torch.float32 or not x.is_contiguous(memory_format=torch.channels_last):
-        raise RuntimeError("bn_act_nhwc_: expected a float32 CUDA tensor in channels_last memory (no CPU path)")
-    n, c, h, w = x.shape
-    if residual is not None and (residual.shape != x.shape or not residual.is_contiguous(memory_format=torch.channels_last)):
-        raise RuntimeError("bn_act_nhwc_: residual must match x (shape, channels_last)")
-    N.check(N.lib().estd_bn_act_nhwc(_p(x), _p(scale), _p(shift), _p(residual) if residual is not None else None,
-                                     1 if relu else 0, n * h * w, c, _stream()), "estd_bn_act_nhwc")
+    op = "bn_act_nhwc_"
+    n, c, h, w = _channels_last(x, op, "x")
+    dev = x.device
+    _floats(scale, c, op, "scale", dev)
+    _floats(shift, c, op, "shift", dev)
+    if residual is not None:
+        _channels_last(residual, op, "residual", dev, like=x)
+    _launch(dev, N.lib().estd_bn_act_nhwc, _p(x), _p(scale), _p(shift), _p(residual), 1 if relu else 0, n * h * w, c)
     return x
 
 
-def _need_f32_cuda(name, *ts):
-    for t in ts:
-        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-            raise RuntimeError("%s: contiguous float32 ROCm tensors expected (no CPU path)" % name)
-
-
-def _need_vec(name, n, **vs):
-    """optional per-output-channel vectors (scale / shift): float32 ROCm tensors of n entries"""
-    for k, v in vs.items():
-        if v is not None:
-            _need_f32_cuda(name, v)
-            if v.numel() != n:
-                raise RuntimeError("%s: %s [%d] expected, got %d entries" % (name, k, n, v.numel()))
-
-
-def conv2d_k3_to16_nhwc(x, w_packed, scale, shift, upsample=False):
-    """3x3 conv (cin 16|32 -> 16) + folded BN + ReLU on an NHWC map, optionally on its nearest-x2 upsampling (never materialised)."""
+def spp_upsample_cat(raw, skip, branches):
+    """NHWC tensors: raw [N,H,W,Cr], skip [N,H,W,Cs], branches [N,hk,wk,Cb] -> [N,H,W,Cr+Cs+nb*Cb] =
+    cat(raw, skip, bilinear_up(branches...)) in one pass (psm_submodule.py:100-116)."""
+    branches = list(branches)
     if _use_torch():
-        return T().conv2d_k3_to16_nhwc(x, w_packed, scale, shift, bool(upsample))
-    _need_f32_cuda("conv2d_k3_to16_nhwc", x, w_packed, scale, shift)
-    n, h, w, c = x.shape
-    if c not in (16, 32) or w_packed.numel() != 9 * (c // 16) * 256 or scale.numel() != 16 or shift.numel() != 16:
-        raise RuntimeError("conv2d_k3_to16_nhwc: NHWC x with 16|32 channels, packed weights [9][cin/16][64][4], scale/shift [16] expected")
-    u = 2 if upsample else 1
-    out = torch.empty((n, u * h, u * w, 16), device=x.device, dtype=torch.float32)
-    N.check(N.lib().estd_conv2d_k3_to16_nhwc(_p(x), _p(w_packed), _p(scale), _p(shift), _p(out), n, u * h, u * w, c, int(bool(upsample)), _stream()),
-            "estd_conv2d_k3_to16_nhwc")
+        return T().spp_upsample_cat(raw, skip, branches)
+    op = "spp_upsample_cat"
+    n, h, w, cr = _map(raw, (-1, -1, -1, -1), op, "raw")
+    dev, nb = raw.device, len(branches)
+    cs = _map(skip, (n, h, w, -1), op, "skip", dev)[3]
+    _count(nb, 1, 4, op, "branches")
+    bh, bw, cb = [], [], -1                                   # the first branch's channel count is every branch's
+    for k, b in enumerate(branches):
+        _, hk, wk, cb = _map(b, (n, -1, -1, cb), op, "branches[%d]" % k, dev)
+        bh.append(hk)
+        bw.append(wk)
+    out = torch.empty((n, h, w, cr + cs + nb * cb), device=dev)
+    _launch(dev, N.lib().estd_spp_upsample_cat, _p(raw), cr, _p(skip), cs, (ctypes.c_void_p * nb)(*[b.data_ptr() for b in branches]),
+            (ctypes.c_int * nb)(*bh), (ctypes.c_int * nb)(*bw), nb, cb, _p(out), n, h, w)
+    return out
+
+
+def _desc_conv(op, entry, d, x, w, w_tail, ho, wo, scale, shift, relu, residual):
+    """conv1x1_nhwc and conv2d_taps_nhwc under the ctypes binding: ``d`` arrives with the operator's own fields (stride; ksize, pad) set,
+    ``w_tail`` are the weight's sizes around cout ([cout,cin] / [k*k,cout,cin]), ho x wo the output map."""
+    n, h, wd, cin = x.shape[-4:]
+    dev = x.device
+    cout = _map(w, w_tail, op, "w", dev)[-2]
+    d.N, d.H, d.W, d.cin, d.cout, d.relu = n, h, wd, cin, cout, int(bool(relu))
+    d.in_, d.w = x.data_ptr(), w.data_ptr()
+    d.scale, d.shift = _p(_opt_floats(scale, cout, op, "scale", dev)), _p(_opt_floats(shift, cout, op, "shift", dev))
+    if residual is not None:
+        _map(residual, (n, ho, wo, cout), op, "residual", dev)
+        d.residual = residual.data_ptr()
+    out = torch.empty((n, ho, wo, cout), device=dev)
+    d.out = out.data_ptr()
+    _launch(dev, entry, ctypes.byref(d))
     return out
 
 
@@ -754,26 +914,12 @@ def conv1x1_nhwc(x, w2, scale, shift, stride=1, relu=False, residual=None):
     x [N,H,W,cin]; w2 [cout,cin] (the Conv2d weight as it lies); scale / shift [cout] or None -> NHWC [N,Ho,Wo,cout]."""
     if _use_torch():
         return T().conv1x1_nhwc(x, w2, scale, shift, int(stride), bool(relu), residual)
-    _need_f32_cuda("conv1x1_nhwc", x, w2)
-    if x.dim() != 4 or w2.dim() != 2 or w2.shape[1] != x.shape[3]:
-        raise RuntimeError("conv1x1_nhwc: NHWC x [N,H,W,cin] and w [cout,cin] expected")
-    n, h, w, c = x.shape
-    cout = w2.shape[0]
-    _need_vec("conv1x1_nhwc", cout, scale=scale, shift=shift)
-    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
-    out = torch.empty((n, ho, wo, cout), device=x.device, dtype=torch.float32)
+    op = "conv1x1_nhwc"
+    n, h, w, c = _map(x, (-1, -1, -1, -1), op, "x")
+    _count(stride, 1, 2, op, "stride")
     d = N.Conv1x1Desc()
-    d.N, d.H, d.W, d.cin, d.cout, d.stride, d.relu = n, h, w, c, cout, int(stride), int(bool(relu))
-    d.in_, d.w = _chk(x, "x").data_ptr(), _chk(w2, "w").data_ptr()
-    d.scale = scale.data_ptr() if scale is not None else None
-    d.shift = shift.data_ptr() if shift is not None else None
-    if residual is not None:
-        if tuple(residual.shape) != (n, ho, wo, cout):
-            raise RuntimeError("conv1x1_nhwc: residual must be NHWC [%d,%d,%d,%d]" % (n, ho, wo, cout))
-        d.residual = _chk(residual, "residual").data_ptr()
-    d.out = out.data_ptr()
-    N.check(N.lib().estd_conv1x1_nhwc(ctypes.byref(d), _stream()), "estd_conv1x1_nhwc")
-    return out
+    d.stride = int(stride)
+    return _desc_conv(op, N.lib().estd_conv1x1_nhwc, d, x, w2, (-1, c), (h - 1) // stride + 1, (w - 1) // stride + 1, scale, shift, relu, residual)
 
 
 def conv2d_taps_nhwc(x, w_taps, scale, shift, ksize, stride=1, pad=None, relu=False, residual=None):
@@ -782,26 +928,23 @@ def conv2d_taps_nhwc(x, w_taps, scale, shift, ksize, stride=1, pad=None, relu=Fa
     pad = ksize // 2 if pad is None else pad
     if _use_torch():
         return T().conv2d_taps_nhwc(x, w_taps, scale, shift, int(ksize), int(stride), int(pad), bool(relu), residual)
-    _need_f32_cuda("conv2d_taps_nhwc", x, w_taps)
-    n, h, w, c = x.shape
-    if w_taps.dim() != 3 or w_taps.shape[0] != ksize * ksize or w_taps.shape[2] != c:
-        raise RuntimeError("conv2d_taps_nhwc: NHWC x [N,H,W,cin] and w [k*k,cout,cin] expected")
-    cout = w_taps.shape[1]
-    _need_vec("conv2d_taps_nhwc", cout, scale=scale, shift=shift)
-    ho, wo = (h + 2 * pad - ksize) // stride + 1, (w + 2 * pad - ksize) // stride + 1
-    out = torch.empty((n, ho, wo, cout), device=x.device, dtype=torch.float32)
+    op = "conv2d_taps_nhwc"
+    n, h, w, c = _map(x, (-1, -1, -1, -1), op, "x")
+    _count(stride, 1, 2, op, "stride")
     d = N.Conv2dTapsDesc()
-    d.N, d.H, d.W, d.cin, d.cout = n, h, w, c, cout
-    d.ksize, d.stride, d.pad, d.relu = int(ksize), int(stride), int(pad), int(bool(relu))
-    d.in_, d.w = _chk(x, "x").data_ptr(), _chk(w_taps, "w").data_ptr()
-    d.scale = scale.data_ptr() if scale is not None else None
-    d.shift = shift.data_ptr() if shift is not None else None
-    if residual is not None:
-        if tuple(residual.shape) != (n, ho, wo, cout):
-            raise RuntimeError("conv2d_taps_nhwc: residual must be NHWC [%d,%d,%d,%d]" % (n, ho, wo, cout))
-        d.residual = _chk(residual, "residual").data_ptr()
-    d.out = out.data_ptr()
-    N.check(N.lib().estd_conv2d_taps_nhwc(ctypes.byref(d), _stream()), "estd_conv2d_taps_nhwc")
+    d.ksize, d.stride, d.pad = int(ksize), int(stride), int(pad)
+    return _desc_conv(op, N.lib().estd_conv2d_taps_nhwc, d, x, w_taps, (ksize * ksize, -1, c), (h + 2 * pad - ksize) // stride + 1,
+                      (w + 2 * pad - ksize) // stride + 1, scale, shift, relu, residual)
+
+
+def _packed_conv(op, entry, x, w, scale, shift, out_shape, *sizes):
+    """the four "NHWC in, packed weights, scale / shift [cout], NHWC out" convolutions under the ctypes binding: x and the weights ``w``
+    have been checked, ``sizes`` are the entry point's own arguments after the five pointers"""
+    dev = x.device
+    _floats(scale, out_shape[3], op, "scale", dev)
+    _floats(shift, out_shape[3], op, "shift", dev)
+    out = torch.empty(out_shape, device=dev)
+    _launch(dev, entry, _p(x), _p(w), _p(scale), _p(shift), _p(out), *sizes)
     return out
 
 
@@ -810,35 +953,21 @@ def stem7x7s2_nhwc(x, w_packed, scale, shift):
     (torchvision ResNet conv1 / bn1 / relu, hybrid_models/resnet_encoder.py:42-44); w_packed: packing.pack_stem7x7."""
     if _use_torch():
         return T().stem7x7s2_nhwc(x, w_packed, scale, shift)
-    _need_f32_cuda("stem7x7s2_nhwc", x, w_packed, scale, shift)
-    n, h, w, c = x.shape
-    if c != 3 or w_packed.numel() != 7 * 6 * 4 * 64 or scale.numel() != 64 or shift.numel() != 64:
-        raise RuntimeError("stem7x7s2_nhwc: NHWC x [N,H,W,3], packed weights [7,6,4,64], scale/shift [64] expected")
-    out = torch.empty((n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, 64), device=x.device, dtype=torch.float32)
-    N.check(N.lib().estd_stem7x7s2_nhwc(_p(x), _p(w_packed), _p(scale), _p(shift), _p(out), n, h, w, _stream()), "estd_stem7x7s2_nhwc")
-    return out
+    op = "stem7x7s2_nhwc"
+    n, h, w, _ = _map(x, (-1, -1, -1, 3), op, "x")
+    _floats(w_packed, 7 * 6 * 4 * 64, op, "w_packed", x.device)
+    return _packed_conv(op, N.lib().estd_stem7x7s2_nhwc, x, w_packed, scale, shift, (n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, 64), n, h, w)
 
 
-def maxpool3x3s2_nhwc(x):
-    """MaxPool2d(3, 2, 1) of an NHWC map [N,H,W,C] (C % 4 == 0) -> [N,(H-1)//2+1,(W-1)//2+1,C]."""
+def stem3x3s2_nhwc(x, weight, scale, shift):
+    """Conv2d(3, 32, 3, stride 2, padding 1) + folded BatchNorm2d + ReLU on an NHWC image batch [N,H,W,3] -> [N,Ho,Wo,32]
+    (networks/psm_submodule.py:47)."""
     if _use_torch():
-        return T().maxpool3x3s2_nhwc(x)
-    _need_f32_cuda("maxpool3x3s2_nhwc", x)
-    n, h, w, c = x.shape
-    out = torch.empty((n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c), device=x.device, dtype=torch.float32)
-    N.check(N.lib().estd_maxpool3x3s2_nhwc(_p(x), _p(out), n, h, w, c, _stream()), "estd_maxpool3x3s2_nhwc")
-    return out
-
-
-def avgpool_nhwc(x, k):
-    """AvgPool2d(k, k) of an NHWC map [N,H,W,C] (C % 4 == 0) -> [N,H//k,W//k,C]."""
-    if _use_torch():
-        return T().avgpool_nhwc(x, int(k))
-    _need_f32_cuda("avgpool_nhwc", x)
-    n, h, w, c = x.shape
-    out = torch.empty((n, h // k, w // k, c), device=x.device, dtype=torch.float32)
-    N.check(N.lib().estd_avgpool_nhwc(_p(x), _p(out), n, h, w, c, int(k), _stream()), "estd_avgpool_nhwc")
-    return out
+        return T().stem3x3s2_nhwc(x, weight, scale, shift)
+    op = "stem3x3s2_nhwc"
+    n, h, w, _ = _map(x, (-1, -1, -1, 3), op, "x")
+    _map(weight, (32, 3, 3, 3), op, "weight", x.device)
+    return _packed_conv(op, N.lib().estd_stem3x3s2_nhwc, x, weight, scale, shift, (n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, 32), n, h, w)
 
 
 SMALL_CONV_SHAPES = {(32, 3, 2), (32, 1, 2), (32, 1, 1), (64, 1, 1), (128, 1, 1)}      # (cin, ksize, stride) instances of estd_conv2d_small_nhwc
@@ -848,19 +977,48 @@ def conv2d_small_nhwc(x, w_packed, scale, shift, cout, ksize, stride, relu):
     """small PSM convolutions (3x3 stride 2, 1x1 stride 1|2) + folded BN [+ ReLU] on an NHWC map -> NHWC [N,Ho,Wo,cout]."""
     if _use_torch():
         return T().conv2d_small_nhwc(x, w_packed, scale, shift, int(cout), int(ksize), int(stride), bool(relu))
-    _need_f32_cuda("conv2d_small_nhwc", x, w_packed, scale, shift)
-    if x.dim() != 4:
-        raise RuntimeError("conv2d_small_nhwc: NHWC x expected")
-    n, h, w, c = x.shape
-    if ksize not in (1, 3) or stride not in (1, 2) or cout <= 0 or cout % 16 or c % 16:
-        raise RuntimeError("conv2d_small_nhwc: ksize 1|3, stride 1|2, channel counts multiples of 16")
-    if w_packed.numel() != cout // 16 * ksize * ksize * (c // 16) * 256 or scale.numel() != cout or shift.numel() != cout:
-        raise RuntimeError("conv2d_small_nhwc: packed weights [cout/16][taps][cin/16][64][4] and scale/shift [cout] expected")
+    op = "conv2d_small_nhwc"
+    n, h, w, c = _map(x, (-1, -1, -1, -1), op, "x")
+    # (the weight count below divides by these)
+    _need(ksize in (1, 3) and stride in (1, 2) and cout > 0 and cout % 16 == 0 and c % 16 == 0,
+          "conv2d_small_nhwc: ksize 1|3, stride 1|2, the channel counts of x and cout multiples of 16")
+    _floats(w_packed, cout // 16 * ksize * ksize * (c // 16) * 256, op, "w_packed", x.device)
     pad = ksize // 2
-    ho, wo = (h + 2 * pad - ksize) // stride + 1, (w + 2 * pad - ksize) // stride + 1
-    out = torch.empty((n, ho, wo, cout), device=x.device, dtype=torch.float32)
-    N.check(N.lib().estd_conv2d_small_nhwc(_p(x), _p(w_packed), _p(scale), _p(shift), _p(out), n, h, w, c, int(cout), int(ksize), int(stride),
-                                           int(bool(relu)), _stream()), "estd_conv2d_small_nhwc")
+    return _packed_conv(op, N.lib().estd_conv2d_small_nhwc, x, w_packed, scale, shift,
+                        (n, (h + 2 * pad - ksize) // stride + 1, (w + 2 * pad - ksize) // stride + 1, cout),
+                        n, h, w, c, int(cout), int(ksize), int(stride), int(bool(relu)))
+
+
+def conv2d_k3_to16_nhwc(x, w_packed, scale, shift, upsample=False):
+    """3x3 conv (cin 16|32 -> 16) + folded BN + ReLU on an NHWC map, optionally on its nearest-x2 upsampling (never materialised)."""
+    if _use_torch():
+        return T().conv2d_k3_to16_nhwc(x, w_packed, scale, shift, bool(upsample))
+    op = "conv2d_k3_to16_nhwc"
+    n, h, w, c = _map(x, (-1, -1, -1, -1), op, "x")
+    _need(c in (16, 32), "conv2d_k3_to16_nhwc: x must have 16 or 32 channels, got %d" % c)      # (the weight count depends on it)
+    _floats(w_packed, 9 * (c // 16) * 256, op, "w_packed", x.device)
+    u = 2 if upsample else 1
+    return _packed_conv(op, N.lib().estd_conv2d_k3_to16_nhwc, x, w_packed, scale, shift, (n, u * h, u * w, 16), n, u * h, u * w, c, int(bool(upsample)))
+
+
+def maxpool3x3s2_nhwc(x):
+    """MaxPool2d(3, 2, 1) of an NHWC map [N,H,W,C] (C % 4 == 0) -> [N,(H-1)//2+1,(W-1)//2+1,C]."""
+    if _use_torch():
+        return T().maxpool3x3s2_nhwc(x)
+    n, h, w, c = _map(x, (-1, -1, -1, -1), "maxpool3x3s2_nhwc", "x")
+    out = torch.empty((n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c), device=x.device)
+    _launch(x.device, N.lib().estd_maxpool3x3s2_nhwc, _p(x), _p(out), n, h, w, c)
+    return out
+
+
+def avgpool_nhwc(x, k):
+    """AvgPool2d(k, k) of an NHWC map [N,H,W,C] (C % 4 == 0) -> [N,H//k,W//k,C]."""
+    if _use_torch():
+        return T().avgpool_nhwc(x, int(k))
+    n, h, w, c = _map(x, (-1, -1, -1, -1), "avgpool_nhwc", "x")
+    _count(k, 1, min(h, w), "avgpool_nhwc", "k")                      # (the output size divides by it)
+    out = torch.empty((n, h // k, w // k, c), device=x.device)
+    _launch(x.device, N.lib().estd_avgpool_nhwc, _p(x), _p(out), n, h, w, c, int(k))
     return out
 
 
@@ -868,26 +1026,9 @@ def normalise_nhwc(imgs):
     """[N,3,H,W] images in 0..255 -> 2 * (imgs / 255) - 1 as an NHWC batch [N,H,W,3] (model_hybrid.py:119)."""
     if _use_torch():
         return T().normalise_nhwc(imgs)
-    _need_f32_cuda("normalise_nhwc", imgs)
-    n, c, h, w = imgs.shape
-    if c != 3:
-        raise RuntimeError("normalise_nhwc: [N,3,H,W] images expected")
-    out = torch.empty((n, h, w, 3), device=imgs.device, dtype=torch.float32)
-    N.check(N.lib().estd_normalise_nhwc(_p(imgs), _p(out), n, h * w, _stream()), "estd_normalise_nhwc")
-    return out
-
-
-def stem3x3s2_nhwc(x, weight, scale, shift):
-    """Conv2d(3, 32, 3, stride 2, padding 1) + folded BatchNorm2d + ReLU on an NHWC image batch [N,H,W,3] -> [N,Ho,Wo,32]
-    (networks/psm_submodule.py:47)."""
-    if _use_torch():
-        return T().stem3x3s2_nhwc(x, weight, scale, shift)
-    _need_f32_cuda("stem3x3s2_nhwc", x, weight, scale, shift)
-    n, h, w, c = x.shape
-    if c != 3 or tuple(weight.shape) != (32, 3, 3, 3) or scale.numel() != 32 or shift.numel() != 32:
-        raise RuntimeError("stem3x3s2_nhwc: NHWC x [N,H,W,3], weight [32,3,3,3], scale/shift [32] expected")
-    out = torch.empty((n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, 32), device=x.device, dtype=torch.float32)
-    N.check(N.lib().estd_stem3x3s2_nhwc(_p(x), _p(weight), _p(scale), _p(shift), _p(out), n, h, w, _stream()), "estd_stem3x3s2_nhwc")
+    n, _, h, w = _map(imgs, (-1, 3, -1, -1), "normalise_nhwc", "imgs")
+    out = torch.empty((n, h, w, 3), device=imgs.device)
+    _launch(imgs.device, N.lib().estd_normalise_nhwc, _p(imgs), _p(out), n, h * w)
     return out
 
 
@@ -895,10 +1036,9 @@ def nhwc_to_planes(x):
     """NHWC map [N,H,W,C] -> contiguous NCHW planes [N,C,H,W] (hybrid_depth_decoder.py:162-184: the plane scores as scalar volumes)."""
     if _use_torch():
         return T().nhwc_to_planes(x)
-    _need_f32_cuda("nhwc_to_planes", x)
-    n, h, w, c = x.shape
-    out = torch.empty((n, c, h, w), device=x.device, dtype=torch.float32)
-    N.check(N.lib().estd_nhwc_to_planes(_p(x), c, _p(out), n, h * w, _stream()), "estd_nhwc_to_planes")
+    n, h, w, c = _map(x, (-1, -1, -1, -1), "nhwc_to_planes", "x")
+    out = torch.empty((n, c, h, w), device=x.device)
+    _launch(x.device, N.lib().estd_nhwc_to_planes, _p(x), c, _p(out), n, h * w)
     return out
 
 
@@ -906,13 +1046,11 @@ def planes_cat_nhwc(a, b, relu_b=False):
     """torch.cat([a, relu?(b)], 1) of NCHW stacks -> NHWC map [N,H,W,Ca+Cb] (hybrid_depth_decoder.py:268)."""
     if _use_torch():
         return T().planes_cat_nhwc(a, b, bool(relu_b))
-    _need_f32_cuda("planes_cat_nhwc", a, b)
-    n, ca, h, w = a.shape
-    cb = b.shape[1]
-    if tuple(b.shape) != (n, cb, h, w):
-        raise RuntimeError("planes_cat_nhwc: two NCHW stacks of the same N, H, W expected")
-    out = torch.empty((n, h, w, ca + cb), device=a.device, dtype=torch.float32)
-    N.check(N.lib().estd_planes_cat_nhwc(_p(a), ca, _p(b), cb, int(bool(relu_b)), _p(out), n, h * w, _stream()), "estd_planes_cat_nhwc")
+    op = "planes_cat_nhwc"
+    n, ca, h, w = _map(a, (-1, -1, -1, -1), op, "a")
+    cb = _map(b, (n, -1, h, w), op, "b", a.device)[1]
+    out = torch.empty((n, h, w, ca + cb), device=a.device)
+    _launch(a.device, N.lib().estd_planes_cat_nhwc, _p(a), ca, _p(b), cb, int(bool(relu_b)), _p(out), n, h * w)
     return out
 
 
@@ -920,13 +1058,12 @@ def upsample2_cat_nhwc(x, skip):
     """torch.cat([nearest_x2(x), skip], 1) on NHWC maps: x [N,H/2,W/2,Cx], skip [N,H,W,Cs] -> [N,H,W,Cx+Cs] (:269-272)."""
     if _use_torch():
         return T().upsample2_cat_nhwc(x, skip)
-    _need_f32_cuda("upsample2_cat_nhwc", x, skip)
-    n, h, w, cs = skip.shape
-    if tuple(x.shape[:3]) != (n, h // 2, w // 2) or h % 2 or w % 2:
-        raise RuntimeError("upsample2_cat_nhwc: NHWC x [N,H/2,W/2,Cx] and skip [N,H,W,Cs] expected")
-    cx = x.shape[3]
-    out = torch.empty((n, h, w, cx + cs), device=x.device, dtype=torch.float32)
-    N.check(N.lib().estd_upsample2_cat_nhwc(_p(x), cx, _p(skip), cs, _p(out), n, h, w, _stream()), "estd_upsample2_cat_nhwc")
+    op = "upsample2_cat_nhwc"
+    n, hx, wx, cx = _map(x, (-1, -1, -1, -1), op, "x")
+    h, w = 2 * hx, 2 * wx
+    cs = _map(skip, (n, h, w, -1), op, "skip", x.device)[3]
+    out = torch.empty((n, h, w, cx + cs), device=x.device)
+    _launch(x.device, N.lib().estd_upsample2_cat_nhwc, _p(x), cx, _p(skip), cs, _p(out), n, h, w)
     return out
 
 
@@ -934,32 +1071,12 @@ def disp_head_nhwc(x, weight, bias, depth_max, upscale=1):
     """depth_max * sigmoid(Conv2d(C,1,3,padding=1,bias)(x)) on an NHWC map, optionally nearest x2 -> [N,1,uH,uW] (:274, :279)."""
     if _use_torch():
         return T().disp_head_nhwc(x, weight, bias, float(depth_max), int(upscale))
-    _need_f32_cuda("disp_head_nhwc", x, weight, bias)
-    n, h, w, c = x.shape
-    if tuple(weight.shape) != (1, c, 3, 3) or bias.numel() != 1:
-        raise RuntimeError("disp_head_nhwc: NHWC x [N,H,W,C], weight [1,C,3,3], bias [1] expected")
-    out = torch.empty((n, 1, upscale * h, upscale * w), device=x.device, dtype=torch.float32)
-    N.check(N.lib().estd_disp_head_nhwc(_p(x), _p(weight), _p(bias), float(depth_max), _p(out), n, h, w, c, int(upscale), _stream()),
-            "estd_disp_head_nhwc")
-    return out
-
-
-def spp_upsample_cat(raw, skip, branches):
-    """NHWC tensors: raw [N,H,W,Cr], skip [N,H,W,Cs], branches [N,hk,wk,Cb] -> [N,H,W,Cr+Cs+nb*Cb] =
-    cat(raw, skip, bilinear_up(branches...)) in one pass (psm_submodule.py:100-116)."""
-    if _use_torch():
-        return T().spp_upsample_cat(raw, skip, list(branches))
-    n, h, w, cr = raw.shape
-    cs, cb, nb = skip.shape[3], branches[0].shape[3], len(branches)
-    for t in [raw, skip] + list(branches):
-        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
-            raise RuntimeError("spp_upsample_cat: contiguous float32 NHWC CUDA tensors expected (no CPU path)")
-    out = torch.empty((n, h, w, cr + cs + nb * cb), device=raw.device, dtype=torch.float32)
-    arr = (ctypes.c_void_p * nb)(*[b.data_ptr() for b in branches])
-    bh = (ctypes.c_int * nb)(*[b.shape[1] for b in branches])
-    bw = (ctypes.c_int * nb)(*[b.shape[2] for b in branches])
-    N.check(N.lib().estd_spp_upsample_cat(_p(raw), cr, _p(skip), cs, arr, bh, bw, nb, cb, _p(out), n, h, w, _stream()),
-            "estd_spp_upsample_cat")
+    op = "disp_head_nhwc"
+    n, h, w, c = _map(x, (-1, -1, -1, -1), op, "x")
+    _map(weight, (1, c, 3, 3), op, "weight", x.device)
+    _floats(bias, 1, op, "bias", x.device)
+    out = torch.empty((n, 1, upscale * h, upscale * w), device=x.device)
+    _launch(x.device, N.lib().estd_disp_head_nhwc, _p(x), _p(weight), _p(bias), float(depth_max), _p(out), n, h, w, c, int(upscale))
     return out
 
 
@@ -968,90 +1085,28 @@ def cdhw_to_vol(src, dst, dst_stride, dst_off):
     """src [C,D,H,W] contiguous -> channels dst_off.. of the channels-last records of dst."""
     if _use_torch():
         return T().cdhw_to_vol(src, dst, dst_stride, dst_off)
-    _need(src.dim() >= 2, "cdhw_to_vol: src must be [C, ...]")
+    op = "cdhw_to_vol"
+    _chk(src, "src", op=op)
+    _need(src.dim() >= 2 and src.shape[0] >= 1, "%s: src must be [C, ...] with C >= 1, got %s" % (op, tuple(src.shape)))
     C = src.shape[0]
     S = src.numel() // C
-    _need(dst.is_cuda and dst.dtype == torch.float32 and dst.numel() >= S * dst_stride, "cdhw_to_vol: destination too small")
-    N.check(N.lib().estd_cdhw_to_vol(_p(_chk(src, "volume")), _p(dst), C, S, dst_stride, dst_off, _stream()), "estd_cdhw_to_vol")
+    _count(dst_off, 0, dst_stride, op, "dst_off")                      # (estd_cdhw_to_vol checks its upper end only)
+    _floats(dst, S * dst_stride, op, "dst", src.device, at_least=True, strided=True)
+    _launch(src.device, N.lib().estd_cdhw_to_vol, _p(src), _p(dst), C, S, dst_stride, dst_off)
 
 
 def vol_to_cdhw(src, C, dims, src_stride, src_off):
+    dims = list(dims)
     if _use_torch():
-        return T().vol_to_cdhw(src, C, list(dims), src_stride, src_off)
+        return T().vol_to_cdhw(src, C, dims, src_stride, src_off)
+    op = "vol_to_cdhw"
+    _count(len(dims), 3, 3, op, "dims")
     D, H, W = dims
-    _need(src.is_cuda and src.dtype == torch.float32 and src.numel() >= D * H * W * src_stride, "vol_to_cdhw: source too small")
-    out = torch.empty((C, D, H, W), device=src.device, dtype=torch.float32)
-    N.check(N.lib().estd_vol_to_cdhw(_p(src), _p(out), C, D * H * W, src_stride, src_off, _stream()), "estd_vol_to_cdhw")
+    _count(src_off, 0, src_stride, op, "src_off")                      # (estd_vol_to_cdhw checks its upper end only)
+    _floats(src, D * H * W * src_stride, op, "src", at_least=True, strided=True)
+    out = torch.empty((C, D, H, W), device=src.device)
+    _launch(src.device, N.lib().estd_vol_to_cdhw, _p(src), _p(out), C, D * H * W, src_stride, src_off)
     return out
-
-
-# ---------------------------------------------------------------------------------- reconstruction operators: argument checks
-# One helper per kind of check for the ctypes front ends below (csrc/torch_ops.cpp has the same set for the torch binding); each takes
-# the operator's and the argument's name for its message.
-def _volume(volume, op):
-    """the volume argument: two float32 planes (D, weight), contiguous, on a device, X % 4 == 0 -> (Z, Y, X, address of the weight plane)"""
-    _need(isinstance(volume, torch.Tensor) and volume.dim() == 4 and volume.shape[0] == 2, "%s: volume must be [2,Z,Y,X] (D plane, weight plane)" % op)
-    _chk(volume, "volume")
-    Z, Y, X = volume.shape[1:]
-    _need(X % 4 == 0, "%s: X must be a multiple of 4, got %d" % (op, X))
-    return Z, Y, X, volume.data_ptr() + 4 * Z * Y * X
-
-
-def _color_planes(color, volume, op):
-    _need(isinstance(color, torch.Tensor) and color.dim() == 4 and color.shape[0] == 3 and tuple(color.shape[1:]) == tuple(volume.shape[1:]),
-          "%s: color must be [3,Z,Y,X] with the volume's Z, Y, X" % op)
-    _chk(color, "color")
-    _need(color.device == volume.device, "%s: color is on %s but the volume on %s" % (op, color.device, volume.device))
-
-
-def _host_values(t, n, op, name, shape, finite=False):
-    """host values of the launch arguments: exactly ``n`` of them (``finite``: none NaN or infinite) -> the values as a list"""
-    _need(isinstance(t, torch.Tensor) and not t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n,
-          "%s: %s must be a contiguous CPU float32 tensor %s" % (op, name, shape))
-    flat = t.reshape(-1).tolist()
-    _need(not finite or all(math.isfinite(v) for v in flat), "%s: %s holds a value that is not finite" % (op, name))
-    return flat
-
-
-def _map(t, tail, op, name, dev=None):
-    """``t`` is a float32 device map whose last sizes are ``tail`` (-1: any size), leading 1s allowed, on ``dev`` -> its last sizes"""
-    _chk(t, name)
-    got = tuple(t.shape[-len(tail):])
-    _need(t.dim() >= len(tail) and all(w in (-1, g) for w, g in zip(tail, got)) and t.numel() == math.prod(got),
-          "%s: %s must end in the sizes %s (-1: any; leading 1s allowed), got %s" % (op, name, tail, tuple(t.shape)))
-    _need(dev is None or t.device == dev, "%s: %s is on %s but the operator runs on %s" % (op, name, t.device, dev))
-    return got
-
-
-def _map_size(H, W, op, name, least=1):
-    _need(H >= least and W >= least and H * W <= 0x7fffffff, "%s: %s must be at least %d x %d (and H * W < 2^31), got %d x %d" % (op, name, least, least, H, W))
-
-
-def _ivec(t, op, name, dev, size=None, dtype=torch.int64):
-    _need(isinstance(t, torch.Tensor) and t.dim() == 1 and t.dtype == dtype and t.is_contiguous() and t.device == dev
-          and (size is None or t.shape[0] == size),
-          "%s: %s must be a contiguous %s vector%s on the operator's device" % (op, name, dtype, "" if size is None else " [%d]" % size))
-
-
-# the four rules for a scalar that a kernel takes as fp32
-def _positive(v, op, name):
-    _need(math.isfinite(v) and ctypes.c_float(v).value > 0, "%s: %s must be positive and finite, got %r" % (op, name, v))
-
-
-def _not_negative(v, op, name):
-    _need(math.isfinite(v) and v >= 0, "%s: %s must be finite and not negative, got %r" % (op, name, v))
-
-
-def _not_nan(v, op, name):
-    _need(v == v, "%s: %s must not be NaN" % (op, name))
-
-
-def _positive_square(v, op, name, square_positive=False):
-    """positive and finite, and its square finite in fp32 (``square_positive``: and not rounded to 0)"""
-    v32 = ctypes.c_float(v).value if math.isfinite(v) else float("nan")
-    sq = ctypes.c_float(v32 * v32).value
-    _need(v32 > 0 and math.isfinite(sq) and (sq > 0 or not square_positive),
-          "%s: %s (and its square in fp32) must be positive and finite, got %r" % (op, name, v))
 
 
 # ---------------------------------------------------------------------------------- TSDF fusion (csrc/tsdf.hip)

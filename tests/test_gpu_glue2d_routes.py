@@ -21,7 +21,9 @@ import pytest
 import torch
 
 import glue2d_ref as R
+from test_gpu_conv2d_routes import KERNEL_RE as CONV_KERNEL_RE
 from test_gpu_conv2d_routes import SENT32, _guarded, _Switches, _untouched
+from test_gpu_sweep_fusion_routes import _as_tuple, _malformed, _sent, _short
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -342,14 +344,22 @@ def test_normalise_route(N, H, W):
 
 
 # ---------------------------------------------------------------------------------------------------------------- refused shapes
-def _refused(call, match=None):
-    """the call raises and launches none of the suite's kernels"""
+def _refused(call, match=None, after=None):
+    """the call (or every call of a list, under one trace) raises and launches none of the kernels of the 2D suites; ``after(i, message)``
+    looks at the i-th refusal before the next call -> the messages"""
+    calls = call if isinstance(call, list) else [call]
+    messages = []
     with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CUDA]) as prof:
-        with pytest.raises(RuntimeError, match=match):
-            call()
+        for i, c in enumerate(calls):
+            with pytest.raises(RuntimeError, match=match) as e:
+                c()
+            messages.append(str(e.value))
+            if after is not None:
+                after(i, messages[-1])
         torch.cuda.synchronize()
-    ran = [e.key for e in prof.key_averages() if KERNEL_RE.search(e.key)]
+    ran = [e.key for e in prof.key_averages() if KERNEL_RE.search(e.key) or CONV_KERNEL_RE.search(e.key)]
     assert not ran, ran
+    return messages
 
 
 @pytest.mark.parametrize("binding", ["torch", "ctypes"])
@@ -373,6 +383,105 @@ def test_upsample2_cat_refuses_an_odd_map(binding, H, W):
         _refused(lambda: ops.upsample2_cat_nhwc(x, skip))
     out = torch.zeros(1, H, W, 8, device=DEV)
     assert _lib().estd_upsample2_cat_nhwc(_p(x), 4, _p(skip), 4, _p(out), 1, H, W, _stream()) == -1
+
+
+# ------------------------------------------------------------------------------------------------------------ malformed arguments
+def _arg_table():
+    """The 2D operators in the form of test_gpu_sweep_fusion_routes._arg_table: (the operator's name in messages, call(**args), valid() ->
+    its arguments by name, the argument it writes or None, [(label, the argument replaced, its malformed value[, the name the message
+    gives it])]).  Maps of a few pixels, no two sizes of a tensor equal; weights are random floats of the packed size (the checks and the
+    parity of the bindings do not depend on their values)."""
+    from estdepth_amd import ops
+    r = lambda *s: _rand(s, 11 + sum(s))                                        # noqa: E731
+    cl = lambda t: t.contiguous(memory_format=torch.channels_last)              # noqa: E731
+    f64 = lambda t: t.double()                                                  # noqa: E731
+    x16, x32, img, pool = r(1, 3, 5, 16), r(1, 3, 5, 32), r(1, 5, 7, 3), r(1, 4, 6, 4)
+    s16, s32, s64 = r(16), r(32), r(64)
+    br = lambda n: [r(1, 1, 2, 4) + k for k in range(n)]                        # noqa: E731
+    spp = lambda n: (lambda: dict(raw=pool, skip=r(1, 4, 6, 8), branches=br(n)))  # noqa: E731
+    w_taps, w_small, w_to16, w_stem7 = r(9, 32, 16), r(512), r(9 * 256), r(7 * 6 * 4 * 64)
+    return [
+        ("bn_act_nhwc_", ops.bn_act_nhwc_, lambda: dict(x=cl(r(1, 8, 3, 5)), scale=r(8), shift=r(8), relu=True, residual=cl(r(1, 8, 3, 5) + 1)), "x", [
+            ("a 7-float scale", "scale", _short(r(8), 7)), ("a 7-float shift", "shift", _short(r(8), 7)), ("float64 scale", "scale", f64(r(8))), ("x [C,H,W]", "x", _sent(8, 3, 5)), ("x in NCHW memory", "x", _sent(1, 8, 3, 5)),
+            ("residual [N,C,W,H]", "residual", cl(r(1, 8, 5, 3))), ("residual in NCHW memory", "residual", r(1, 8, 3, 5)),
+            ("float64 residual", "residual", cl(f64(r(1, 8, 3, 5)))), ("a list for scale", "scale", [1.0] * 8)]),
+        ("bn_act_nhwc_", ops.bn_act_nhwc_, lambda: dict(x=cl(r(1, 8, 3, 5)), scale=r(8), shift=r(8), relu=False, residual=None), "x", []),
+        ("spp_upsample_cat", ops.spp_upsample_cat, spp(2), None, [
+            ("no branch", "branches", []), ("five branches", "branches", br(5)), ("skip [N,W,H,C]", "skip", r(1, 6, 4, 8)),
+            ("skip of two images", "skip", r(2, 4, 6, 8)), ("skip [H,W,C]", "skip", r(4, 6, 8)), ("raw [H,W,C]", "raw", r(4, 6, 4)),
+            ("a branch of two images", "branches", [r(1, 1, 2, 4), r(2, 1, 2, 4)]), ("a branch of 8 channels", "branches", [r(1, 1, 2, 4), r(1, 1, 2, 8)]),
+            ("a branch [H,W,C]", "branches", [r(1, 2, 4), r(1, 1, 2, 4)]), ("a float64 branch", "branches", [r(1, 1, 2, 4), f64(r(1, 1, 2, 4))])]),
+        ("spp_upsample_cat", ops.spp_upsample_cat, spp(1), None, []),
+        ("spp_upsample_cat", ops.spp_upsample_cat, spp(3), None, []),
+        ("spp_upsample_cat", ops.spp_upsample_cat, spp(4), None, []),
+        ("conv1x1_nhwc", ops.conv1x1_nhwc, lambda: dict(x=x16, w2=r(32, 16), scale=s32, shift=s32 + 1, stride=1, relu=True, residual=r(1, 3, 5, 32)), None, [
+            ("w [cin,cout]", "w2", r(16, 32), "w"), ("a 31-float scale", "scale", _short(s32, 31)), ("a 31-float shift", "shift", _short(s32, 31)),
+            ("stride 0", "stride", 0), ("stride 3", "stride", 3), ("residual [N,W,H,C]", "residual", r(1, 5, 3, 32)), ("x [H,W,C]", "x", r(3, 5, 16)),
+            ("float64 w", "w2", f64(r(32, 16)), "w")]),
+        ("conv1x1_nhwc", ops.conv1x1_nhwc, lambda: dict(x=x16, w2=r(32, 16), scale=None, shift=None, stride=2), None, []),
+        ("conv2d_taps_nhwc", ops.conv2d_taps_nhwc, lambda: dict(x=x16, w_taps=w_taps, scale=s32, shift=s32 + 1, ksize=3, stride=1, pad=1, relu=True,
+                                                              residual=r(1, 3, 5, 32)), None, [
+            ("x [H,W,C]", "x", r(3, 5, 16)), ("w of 8 taps", "w_taps", _short(w_taps, 8 * 32 * 16).view(8, 32, 16), "w"),
+            ("w [taps,cin,cout]", "w_taps", r(9, 16, 32), "w"), ("a 31-float scale", "scale", _short(s32, 31)),
+            ("a 31-float shift", "shift", _short(s32, 31)), ("stride 0", "stride", 0), ("residual [N,W,H,C]", "residual", r(1, 5, 3, 32))]),
+        ("conv2d_small_nhwc", ops.conv2d_small_nhwc, lambda: dict(x=x32, w_packed=w_small, scale=s16, shift=s16 + 1, cout=16, ksize=1, stride=1, relu=True),
+         None, [
+            ("w one float short", "w_packed", _short(w_small, 511)), ("a 15-float scale", "scale", _short(s16, 15)),
+            ("a 15-float shift", "shift", _short(s16, 15)), ("x [H,W,C]", "x", r(3, 5, 32)), ("ksize 2", "ksize", 2), ("float64 x", "x", f64(x32))]),
+        ("conv2d_k3_to16_nhwc", ops.conv2d_k3_to16_nhwc, lambda: dict(x=x16, w_packed=w_to16, scale=s16, shift=s16 + 1, upsample=False), None, [
+            ("w one float short", "w_packed", _short(w_to16, 9 * 256 - 1)), ("a 15-float scale", "scale", _short(s16, 15)),
+            ("a 15-float shift", "shift", _short(s16, 15)), ("x of 8 channels", "x", r(1, 3, 5, 8)), ("x [H,W,C]", "x", r(3, 5, 16))]),
+        ("conv2d_k3_to16_nhwc", ops.conv2d_k3_to16_nhwc, lambda: dict(x=r(1, 2, 3, 16), w_packed=w_to16, scale=s16, shift=s16 + 1, upsample=True), None, []),
+        ("stem7x7s2_nhwc", ops.stem7x7s2_nhwc, lambda: dict(x=img, w_packed=w_stem7, scale=s64, shift=s64 + 1), None, [
+            ("x [N,3,H,W]", "x", r(1, 3, 5, 7)), ("x of 4 channels", "x", r(1, 5, 7, 4)), ("w one float short", "w_packed", _short(w_stem7, 10751)),
+            ("a 63-float scale", "scale", _short(s64, 63)), ("a 63-float shift", "shift", _short(s64, 63))]),
+        ("stem3x3s2_nhwc", ops.stem3x3s2_nhwc, lambda: dict(x=img, weight=r(32, 3, 3, 3), scale=s32, shift=s32 + 1), None, [
+            ("x of 4 channels", "x", r(1, 5, 7, 4)), ("weight [3,3,3,32]", "weight", r(3, 3, 3, 32)), ("a 31-float scale", "scale", _short(s32, 31)),
+            ("a 31-float shift", "shift", _short(s32, 31))]),
+        ("maxpool3x3s2_nhwc", ops.maxpool3x3s2_nhwc, lambda: dict(x=pool), None, [
+            ("x [H,W,C]", "x", r(4, 6, 4)), ("float64 x", "x", f64(pool)), ("a list", "x", [[[[1.0] * 4]]])]),
+        ("avgpool_nhwc", ops.avgpool_nhwc, lambda: dict(x=pool, k=2), None, [
+            ("k = 0", "k", 0), ("k = 5 on a 4 x 6 map", "k", 5), ("x [H,W,C]", "x", r(4, 6, 4))]),
+        ("normalise_nhwc", ops.normalise_nhwc, lambda: dict(imgs=r(1, 3, 5, 7)), None, [
+            ("imgs [N,H,W,3]", "imgs", img), ("imgs [3,H,W]", "imgs", r(3, 5, 7)), ("float64 imgs", "imgs", f64(r(1, 3, 5, 7)))]),
+        ("nhwc_to_planes", ops.nhwc_to_planes, lambda: dict(x=pool), None, [("x [H,W,C]", "x", r(4, 6, 4)), ("float64 x", "x", f64(pool))]),
+        ("planes_cat_nhwc", ops.planes_cat_nhwc, lambda: dict(a=r(1, 2, 3, 5), b=r(1, 4, 3, 5), relu_b=True), None, [
+            ("b [N,C,W,H]", "b", r(1, 4, 5, 3)), ("b of two stacks", "b", r(2, 4, 3, 5)), ("a [C,H,W]", "a", r(2, 3, 5)),
+            ("b [C,H,W]", "b", r(4, 3, 5)), ("float64 b", "b", f64(r(1, 4, 3, 5)))]),
+        ("upsample2_cat_nhwc", ops.upsample2_cat_nhwc, lambda: dict(x=r(1, 2, 3, 4), skip=r(1, 4, 6, 8)), None, [
+            ("skip [N,W,H,C]", "skip", r(1, 6, 4, 8)), ("skip of two images", "skip", r(2, 4, 6, 8)), ("skip of 5 rows", "skip", r(1, 5, 6, 8)),
+            ("x [H,W,C]", "x", r(2, 3, 4)), ("skip [H,W,C]", "skip", r(4, 6, 8))]),
+        ("disp_head_nhwc", ops.disp_head_nhwc, lambda: dict(x=x16, weight=r(1, 16, 3, 3), bias=r(1), depth_max=10.0, upscale=1), None, [
+            ("weight [C,1,3,3]", "weight", r(16, 1, 3, 3)), ("weight for 32 channels", "weight", r(1, 32, 3, 3)), ("a 2-float bias", "bias", r(2)),
+            ("x [H,W,C]", "x", r(3, 5, 16))]),
+    ]
+
+
+def test_the_valid_call_of_every_2d_operator_runs_alike_under_both_bindings():
+    """the rule set refuses nothing it should accept: bit-identical outputs"""
+    for op, fn, valid, _, _ in _arg_table():
+        outs = []
+        for binding in ("torch", "ctypes"):
+            with _Switches(None, binding):
+                outs.append(_as_tuple(fn(**valid())))
+        torch.cuda.synchronize()
+        assert len(outs[0]) == len(outs[1]) and all(_bits_equal(a, b) for a, b in zip(*outs)), op
+
+
+@pytest.mark.parametrize("binding", ["torch", "ctypes"])
+def test_malformed_2d_arguments_raise_before_any_launch(binding):
+    """every malformed call of the table is a RuntimeError under both bindings with the operator's and the argument's name in the message,
+    launches no kernel of the 2D suites and leaves the tensor bn_act_nhwc_ writes untouched"""
+    cases = _malformed(_arg_table(), fill_dest=True)
+    assert len(cases) >= 75 and len({c[0] for c in cases}) == len(cases)
+
+    def after(i, message):
+        label, op, arg, _, dest = cases[i]
+        assert op in message and arg in message, "%s / %s: the message names neither %s nor %s: %s" % (binding, label, op, arg, message)
+        if dest is not None and dest.is_cuda:
+            assert bool((dest.view(torch.int32) == SENT32).all()), "%s / %s wrote into its destination" % (binding, label)
+    with _Switches(None, binding):
+        _refused([c[3] for c in cases], after=after)
 
 
 def test_sentinel_is_a_nan_no_kernel_computes():

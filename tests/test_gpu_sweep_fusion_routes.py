@@ -856,46 +856,164 @@ def test_gru_fast_transcendentals():
 
 
 # ----------------------------------------------------------------------------------------------------------- malformed arguments
-def _malformed():
-    """(name, call) pairs with one wrong-sized argument each"""
+def _sent(*shape):
+    return torch.full(shape, SENT32, dtype=torch.int32, device=DEV).view(torch.float32)
+
+
+def _short(t, n):
+    """the first n elements of a full-sized tensor: were it wrongly accepted, the kernel would still read and write memory the test owns"""
+    return t.reshape(-1)[:n]
+
+
+def _arg_table():
+    """One entry per operator: (the operator's name in messages, call(**args) -> outputs, valid() -> its arguments by name, the argument
+    it writes or None, [(label, the argument replaced, its malformed value[, the name the message gives it])]).  Every malformed call
+    differs from the valid one in that one argument.  Volumes are D x H x W = 2 x 3 x 5 (the smallest the warps accept, no two sizes
+    equal, 30 voxels)."""
     from estdepth_amd import ops
-    z = lambda *s: torch.zeros(*s, device=DEV)                                 # noqa: E731
-    P = z(12)
-    mix, vol = z(8, 8, 32), z(4, 4, 8, 32)
-    xh, st, aff = z(4, 4, 8, 32), z(4), z(16)
+    r = lambda *s: _rand(s, 7 + sum(s))                                         # noqa: E731
+    eye = torch.eye(4, device=DEV)
+    K = torch.tensor([[50.0, 0.0, 2.5], [0.0, 50.0, 1.5], [0.0, 0.0, 1.0]], device=DEV)
+    dv = torch.tensor([1.0, 2.0], device=DEV)
+    P, M30, st, aff = r(12), r(30), torch.tensor([0.1, 0.9, -0.2, 1.1], device=DEV), r(16)
+    kv, kv16, vol, mix = r(2, 3, 5, 32), r(2, 3, 5, 16), r(4, 2, 3, 5), r(3, 5, 32)
+    f64 = lambda t: t.double()                                                  # noqa: E731
+    blend = dict(xh=kv, ru=r(2, 3, 5, 32), o_raw=kv16, stats_ru=st, stats_o=st, gamma_u=aff, beta_u=aff, gamma_o=aff, beta_o=aff, out_stride=32)
+
+    def void(fn, dest):                                  # an operator that returns nothing: its output is the argument it writes
+        return lambda **a: (fn(**a), a[dest])[1]
     return [
-        ("costvol src_mix channels", lambda: ops.homo_warp_costvol(z(8, 8, 16), mix, P, z(4), 4)),
-        ("costvol ref_mix shape", lambda: ops.homo_warp_costvol(mix, z(8, 7, 32), P, z(4), 4)),
-        ("costvol short proj12", lambda: ops.homo_warp_costvol(mix, mix, z(9), z(4), 4)),
-        ("costvol short depth_values", lambda: ops.homo_warp_costvol(mix, mix, P, z(3), 4)),
-        ("costvol short out", lambda: ops.homo_warp_costvol(mix, mix, P, z(4), 4, out=z(3, 8, 8, 32))),
-        ("warp_attention source shape", lambda: ops.warp_attention(vol, [vol, z(4, 4, 7, 32)], z(2, 30), z(4), 0.5, 0.1)),
-        ("warp_attention mats", lambda: ops.warp_attention(vol, [vol, vol], z(1, 30), z(4), 0.5, 0.1)),
-        ("warp_attention short depth_values", lambda: ops.warp_attention(vol, [vol], z(1, 30), z(3), 0.5, 0.1)),
-        ("softargmin short depth_values", lambda: ops.softargmin_up(z(1, 8, 4, 4), z(7), 4)),
-        ("gru_reset ru size", lambda: ops.gru_reset_apply(xh, z(4, 4, 7, 32), st, aff, aff)),
-        ("gru_reset stats", lambda: ops.gru_reset_apply(xh, xh, z(2), aff, aff)),
-        ("gru_reset affine", lambda: ops.gru_reset_apply(xh, xh, st, z(8), aff)),
-        ("gru_blend o_raw size", lambda: ops.gru_blend(xh, xh, z(4, 4, 7, 16), st, st, aff, aff, aff, aff, z(4, 4, 8, 32), 32)),
-        ("gru_blend ru size", lambda: ops.gru_blend(xh, z(4, 4, 4, 32), z(4, 4, 8, 16), st, st, aff, aff, aff, aff, z(4, 4, 8, 32), 32)),
-        ("gru_blend stats", lambda: ops.gru_blend(xh, xh, z(4, 4, 8, 16), z(3), st, aff, aff, aff, aff, z(4, 4, 8, 32), 32)),
-        ("gru_blend affine", lambda: ops.gru_blend(xh, xh, z(4, 4, 8, 16), st, st, aff, aff, z(15), aff, z(4, 4, 8, 32), 32)),
-        ("gru_blend short out_value", lambda: ops.gru_blend(xh, xh, z(4, 4, 8, 16), st, st, aff, aff, aff, aff, z(127 * 32 + 15), 32)),
-        ("mix1x1 w shape", lambda: ops.mix1x1(z(32, 4, 4), z(16, 64), None)),
-        ("homo_warping short depth_values", lambda: ops.homo_warping_chw(z(4, 6, 8), P, z(3), 4)),
-        ("cdhw_to_vol short destination", lambda: ops.cdhw_to_vol(z(16, 2, 3, 4), z(23, 32), 32, 0)),
-        ("vol_to_cdhw short source", lambda: ops.vol_to_cdhw(z(23, 32), 16, (2, 3, 4), 32, 0)),
+        ("cam_pair_proj", ops.cam_pair_proj, lambda: dict(src_proj=eye * 2, ref_proj=eye), None, [
+            ("a 12-float src_proj", "src_proj", _short(eye, 12)), ("a 12-float ref_proj", "ref_proj", _short(eye, 12)),
+            ("float64", "src_proj", f64(eye)), ("a list", "src_proj", [1.0] * 16), ("None", "ref_proj", None)]),
+        ("cam_sweep_proj", ops.cam_sweep_proj, lambda: dict(ref_pose=eye, src_pose=eye * 2, intr=K), None, [
+            ("a 12-float ref_pose", "ref_pose", _short(eye, 12)), ("a 12-float src_pose", "src_pose", _short(eye, 12)),
+            ("6-float intrinsics", "intr", _short(K, 6)), ("float64 intrinsics", "intr", f64(K))]),
+        ("cam_volume_mats", void(ops.cam_volume_mats, "out"), lambda: dict(pose_j=eye * 2, pose_i=eye, intr=K, out=_sent(30)), "out", [
+            ("a 12-float pose_j", "pose_j", _short(eye, 12)), ("a 12-float pose_i", "pose_i", _short(eye, 12)),
+            ("6-float intrinsics", "intr", _short(K, 6)), ("a 24-float out", "out", _short(_sent(30), 24))]),
+        ("cam_volume_mats", void(ops.cam_volume_mats, "out"), lambda: dict(pose_j=eye * 2, pose_i=None, intr=K, out=_sent(30)), "out", []),
+        ("homo_warping", ops.homo_warping_chw, lambda: dict(src_chw=r(4, 3, 5), proj12=P, depth_values=dv, D=2), None, [
+            ("src_chw [C,HW]", "src_chw", r(4, 15)), ("src_chw [2,C,H,W]", "src_chw", r(2, 4, 3, 5)), ("9-float proj12", "proj12", _short(P, 9)),
+            ("one depth for two planes", "depth_values", _short(dv, 1)), ("float64 depths", "depth_values", f64(dv))]),
+        ("homo_warping_px", ops.homo_warping_px_chw, lambda: dict(src_chw=r(4, 3, 5), proj12=P, depth_dhw=r(2, 3, 5).abs() + 1), None, [
+            ("depth_dhw [D,W,H]", "depth_dhw", r(2, 5, 3)), ("depth_dhw [D,HW]", "depth_dhw", r(2, 15)), ("9-float proj12", "proj12", _short(P, 9)),
+            ("src_chw [C,HW]", "src_chw", r(4, 15))]),
+        ("mix1x1", ops.mix1x1, lambda: dict(in_chw=r(8, 3, 5), w=r(4, 8), bias=r(4)), None, [
+            ("w [Cin,Cout]", "w", r(8, 4)), ("w for another Cin", "w", r(4, 6)), ("a 3-float bias", "bias", _short(r(4), 3)),
+            ("in_chw [Cin,HW]", "in_chw", r(8, 15))]),
+        ("mix1x1", ops.mix1x1, lambda: dict(in_chw=r(8, 3, 5), w=r(4, 8), bias=None), None, []),
+        ("homo_warp_costvol", ops.homo_warp_costvol, lambda: dict(src_mix=mix, ref_mix=r(3, 5, 32), proj12=P, depth_values=dv, D=2, out=_sent(2, 3, 5, 32)),
+         "out", [
+            ("16-channel src_mix", "src_mix", r(3, 5, 16)), ("ref_mix [W,H,32]", "ref_mix", r(5, 3, 32)), ("9-float proj12", "proj12", _short(P, 9)),
+            ("one depth for two planes", "depth_values", _short(dv, 1)), ("out one plane short", "out", _short(_sent(2, 3, 5, 32), 3 * 5 * 32)),
+            ("float64 ref_mix", "ref_mix", f64(mix)), ("None for src_mix", "src_mix", None)]),
+        ("softargmin_up", ops.softargmin_up, lambda: dict(logits=r(1, 2, 3, 5), depth_values=dv, scale=4), None, [
+            ("logits [D,H,W]", "logits", r(2, 3, 5)),
+            ("one depth for two planes", "depth_values", _short(dv, 1)), ("a list of depths", "depth_values", [1.0, 2.0]), ("None", "logits", None)]),
+        ("warp_volume", ops.warp_volume_cdhw, lambda: dict(vol=vol, mats30=M30, depth_values=dv, depth_min=0.5, depth_interval=0.1), None, [
+            ("vol [C,D,HW]", "vol", r(4, 2, 15)), ("24-float mats30", "mats30", _short(M30, 24)),
+            ("one depth for two planes", "depth_values", _short(dv, 1), "depth"), ("float64 vol", "vol", f64(vol))]),
+        ("warp_volume_ex", ops.warp_volume_ex_cdhw, lambda: dict(vol=vol, mats30=M30, depth=r(2, 3, 5).abs() + 1, depth_per_voxel=True, depth_min=0.5,
+                                                               depth_interval=0.1), None, [
+            ("per-voxel depth one short", "depth", _short(r(2, 3, 5), 29)), ("per-plane depth for per-voxel", "depth", dv),
+            ("24-float mats30", "mats30", _short(M30, 24)), ("vol [C,D,HW]", "vol", r(4, 2, 15))]),
+        ("warp_attention", ops.warp_attention, lambda: dict(kv_target=kv, kv_sources=[r(2, 3, 5, 32), kv], mats=r(2, 30), depth_values=dv, depth_min=0.5,
+                                                          depth_interval=0.1), None, [
+            ("16-channel kv_target", "kv_target", kv16), ("a source [D,W,H,32]", "kv_sources", [kv, r(2, 5, 3, 32)]),
+            ("a 16-channel source", "kv_sources", [kv16, kv]), ("no source", "kv_sources", []), ("17 sources", "kv_sources", [kv] * 17),
+            ("a float64 source", "kv_sources", [kv, f64(kv)]),
+            ("mats for one source", "mats", _short(r(2, 30), 30)), ("one depth for two planes", "depth_values", _short(dv, 1))]),
+        ("attention_prewarped", ops.attention_prewarped, lambda: dict(kv_target=kv, kv_sources=[r(2, 3, 5, 32), kv]), None, [
+            ("no source", "kv_sources", []), ("17 sources", "kv_sources", [kv] * 17), ("a source [D,W,H,32]", "kv_sources", [kv, r(2, 5, 3, 32)]),
+            ("a source one voxel short", "kv_sources", [_short(kv, 29 * 32), kv]), ("a float64 source", "kv_sources", [f64(kv), kv]),
+            ("a target of 29.97 voxels", "kv_target", _short(kv, 959))]),
+        ("gru_reset_apply", ops.gru_reset_apply, lambda: dict(xh=kv, ru=r(2, 3, 5, 32), stats4=st, gamma_r=aff, beta_r=aff), None, [
+            ("ru one voxel short", "ru", _short(kv, 29 * 32)), ("xh of 29.97 voxels", "xh", _short(kv, 959)), ("2-float stats", "stats4", _short(st, 2)),
+            ("8-float gamma", "gamma_r", _short(aff, 8)), ("15-float beta", "beta_r", _short(aff, 15)), ("float64 ru", "ru", f64(kv))]),
+        ("gru_blend", void(ops.gru_blend, "out_value"), lambda: dict(blend, out_value=_sent(2, 3, 5, 32)), "out_value", [
+            ("ru one voxel short", "ru", _short(kv, 29 * 32)), ("o_raw one voxel short", "o_raw", _short(kv16, 29 * 16)),
+            ("32-channel o_raw", "o_raw", kv), ("3-float stats_ru", "stats_ru", _short(st, 3)), ("3-float stats_o", "stats_o", _short(st, 3)),
+            ("15-float gamma_u", "gamma_u", _short(aff, 15)), ("15-float beta_u", "beta_u", _short(aff, 15)),
+            ("15-float gamma_o", "gamma_o", _short(aff, 15)), ("15-float beta_o", "beta_o", _short(aff, 15)),
+            ("out_value one float short", "out_value", _short(_sent(2, 3, 5, 32), 29 * 32 + 15))]),
+        ("groupnorm_finalize", ops.groupnorm_finalize, lambda: dict(partials=r(3, 4).double(), n_blocks=3, count=48.0), None, [
+            ("float32 partials", "partials", r(3, 4)), ("partials one block short", "partials", r(2, 4).double())]),
+        ("cdhw_to_vol", void(ops.cdhw_to_vol, "dst"), lambda: dict(src=r(16, 2, 3, 5), dst=_sent(31, 32)[1:], dst_stride=32, dst_off=16), "dst", [      # (dst, src below: views with a record in front)
+            ("dst one record short", "dst", _short(_sent(31, 32)[1:], 29 * 32)), ("a negative offset", "dst_off", -16), ("src without channels", "src", r(480)),
+            ("float64 src", "src", f64(r(16, 2, 3, 5)))]),
+        ("vol_to_cdhw", ops.vol_to_cdhw, lambda: dict(src=r(31, 32)[1:], C=16, dims=(2, 3, 5), src_stride=32, src_off=16), None, [
+            ("src one record short", "src", _short(r(31, 32)[1:], 29 * 32)), ("a negative offset", "src_off", -16), ("two dims", "dims", (6, 5)),
+            ("float64 src", "src", f64(r(30, 32)))]),
     ]
+
+
+def _malformed(table=None, fill_dest=False):
+    """(label, operator's name in messages, argument's name in messages, call, the tensor the call would write or None) of every malformed
+    call of ``table`` (_arg_table() unless given, whose destinations hold the sentinel already); ``fill_dest``: a copy of the tensor the
+    operator writes is filled with the sentinel first.  No malformed argument is a CPU tensor: a kernel that got one would fault."""
+    out = []
+    for op, fn, valid, dest, bad in (_arg_table() if table is None else table):
+        for label, arg, value, *msg_name in bad:
+            args = dict(valid(), **{arg: value})
+            if fill_dest and dest is not None and arg != dest:
+                args[dest] = torch.full_like(args[dest].view(torch.int32), SENT32).view(torch.float32)
+            out.append(("%s: %s" % (op, label), op, msg_name[0] if msg_name else arg, lambda fn=fn, args=args: fn(**args), args.get(dest)))
+    return out
+
+
+def _as_tuple(o):
+    return tuple(o) if isinstance(o, (tuple, list)) else (o,)
+
+
+def test_the_valid_call_of_every_operator_runs_alike_under_both_bindings():
+    """the rule set refuses nothing it should accept: bit-identical outputs"""
+    for op, fn, valid, _, _ in _arg_table():
+        outs = []
+        for binding in ("torch", "ctypes"):
+            with _Binding(binding):
+                outs.append(_as_tuple(fn(**valid())))
+        torch.cuda.synchronize()
+        assert len(outs[0]) == len(outs[1]) and all(torch.equal(_bits(a), _bits(b)) for a, b in zip(*outs)), op
 
 
 @pytest.mark.parametrize("binding", ["torch", "ctypes"])
 def test_malformed_arguments_raise_before_any_launch(binding):
-    """the ctypes front end checks what the torch binding checks -- and raises before anything is launched"""
-    for name, call in _malformed():
-        with _Binding(binding):
-            with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CUDA]) as prof:
-                with pytest.raises(RuntimeError):
+    """the ctypes front end checks what the torch binding checks -- and raises before anything is launched: RuntimeError under both bindings
+    with the operator's and the argument's name in the message, no kernel of the suite in the trace, the destination of an operator that
+    writes into a caller's buffer untouched"""
+    cases = _malformed()
+    assert len(cases) >= 80 and len({c[0] for c in cases}) == len(cases)
+    with _Binding(binding):
+        with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CUDA]) as prof:
+            for label, op, arg, call, dest in cases:
+                with pytest.raises(RuntimeError) as e:
                     call()
-                torch.cuda.synchronize()
-        ran = [e.key for e in prof.key_averages() if KERNEL_RE.search(e.key)]
-        assert not ran, "%s / %s launched %s" % (binding, name, ran)
+                assert op in str(e.value) and arg in str(e.value), "%s / %s: the message names neither %s nor %s: %s" % (binding, label, op, arg, e.value)
+                if dest is not None and dest.is_cuda:
+                    assert bool((dest.view(torch.int32) == SENT32).all()), "%s / %s wrote into its destination" % (binding, label)
+            torch.cuda.synchronize()
+    ran = [e.key for e in prof.key_averages() if KERNEL_RE.search(e.key)]
+    assert not ran, "%s: a refused call launched %s" % (binding, ran)
+
+
+def test_a_tensor_on_another_device_is_refused():
+    """every operator runs on its first tensor's device: a later tensor on another one is refused with the same message under both bindings"""
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two devices")
+    from estdepth_amd import ops
+    other = torch.device("cuda:1")
+    eye, dv = torch.eye(4, device=DEV), torch.tensor([1.0, 2.0], device=DEV)
+    kv = _rand((2, 3, 5, 32), 3)
+    for binding in ("torch", "ctypes"):
+        with _Binding(binding):
+            for arg, call in (("ref_proj", lambda: ops.cam_pair_proj(eye, eye.to(other))),
+                              ("depth_values", lambda: ops.softargmin_up(_rand((1, 2, 3, 5), 4), dv.to(other), 4)),
+                              ("kv_sources[1]", lambda: ops.attention_prewarped(kv, [kv, kv.to(other)])),
+                              ("b", lambda: ops.planes_cat_nhwc(_rand((1, 2, 3, 5), 5), _rand((1, 4, 3, 5), 6).to(other)))):
+                with pytest.raises(RuntimeError, match=r"%s is on cuda:1 but the operator runs on cuda:0" % re.escape(arg)):
+                    call()
+            # ... and an operator whose tensors all live on the other device runs there, whatever device is current
+            out = ops.cam_pair_proj((eye * 2).to(other), eye.to(other))
+            assert out.device == other and torch.equal(out.cpu(), ops.cam_pair_proj(eye * 2, eye).cpu())
+
