@@ -79,12 +79,12 @@ inline Tensor new_f32(at::IntArrayRef shape, const Tensor& like) { return at::em
 
 // the volume argument: two float32 planes (0 = D, 1 = Wt), contiguous, on the operator's device, X % 4 == 0
 struct VolumeArg { int64_t Z, Y, X; float* tsdf; float* weight; };
-static VolumeArg check_volume(const Tensor& volume, const char* op)
+static VolumeArg check_volume(const Tensor& volume, const char* op, bool any_x = false)      // any_x: the mesh kernels take any X
 {
     TORCH_CHECK(volume.dim() == 4 && volume.size(0) == 2, op, ": volume must be [2,Z,Y,X] (D plane, weight plane)");
     float* vol = mut(fptr(volume, "volume", true, op));
     const int64_t Z = volume.size(1), Y = volume.size(2), X = volume.size(3);
-    TORCH_CHECK(X % 4 == 0, op, ": X must be a multiple of 4, got ", X);
+    TORCH_CHECK(any_x || X % 4 == 0, op, ": X must be a multiple of 4, got ", X);
     return {Z, Y, X, vol, vol + Z * Y * X};
 }
 
@@ -638,6 +638,52 @@ Tensor tsdf_edge_colors(const Tensor& volume, const Tensor& color, const Tensor&
         check_status(estd_tsdf_edge_colors(v.tsdf, col, (int)v.Z, (int)v.Y, (int)v.X, reinterpret_cast<const long long*>(ids), (long long)n,
                                            out.data_ptr<float>(), cur_stream()), "estd_tsdf_edge_colors");
     return out;
+}
+
+// ------------------------------------------------------------------------------------------------ surface nets
+// csrc/mesh/tsdf_mesh.hip -> (count [1] int64 on the device = TOTAL vertices, cell [capacity] int64, xyz [capacity,3], normal [capacity,3],
+// weight [capacity], colour [capacity,3] with colour planes, else [0,3]); capacity 0 counts only.  origin: CPU float32 [3].
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> tsdf_mesh_vertices(const Tensor& volume, const OptTensor& color, double voxel_size,
+                                                                              const Tensor& origin, double w_min, int64_t capacity)
+{
+    const char* op = "tsdf_mesh_vertices";
+    const OpScope scope(volume);
+    const VolumeArg v = check_volume(volume, op, true);
+    const bool has_color = color.has_value() && color->defined();
+    const float* col = has_color ? check_color_planes(*color, volume, op) : nullptr;
+    TORCH_CHECK(capacity >= 0, op, ": capacity must not be negative");
+    const float voxel = positive_f32(voxel_size, op, "voxel_size"), wm = not_nan_f32(w_min, op, "w_min");
+    const float* org = host_values(origin, 3, op, "origin", "[3]", true);
+    Tensor count = at::zeros({1}, volume.options().dtype(at::kLong));
+    Tensor cell = at::empty({capacity}, volume.options().dtype(at::kLong));
+    Tensor xyz = new_f32({capacity, 3}, volume), normal = new_f32({capacity, 3}, volume), weight = new_f32({capacity}, volume);
+    Tensor rgb = new_f32({has_color ? capacity : 0, 3}, volume);
+    check_status(estd_tsdf_mesh_vertices(v.tsdf, v.weight, col, (int)v.Z, (int)v.Y, (int)v.X, voxel, org, wm,
+                                         reinterpret_cast<unsigned long long*>(count.data_ptr<int64_t>()), (long long)capacity,
+                                         capacity ? reinterpret_cast<long long*>(cell.data_ptr<int64_t>()) : nullptr,
+                                         capacity ? xyz.data_ptr<float>() : nullptr, capacity ? normal.data_ptr<float>() : nullptr,
+                                         capacity ? weight.data_ptr<float>() : nullptr,
+                                         capacity && has_color ? rgb.data_ptr<float>() : nullptr, cur_stream()),
+                 "estd_tsdf_mesh_vertices");
+    return {count, cell, xyz, normal, weight, rgb};
+}
+
+// -> (count [1] int64 on the device = TOTAL quads, edge [capacity] int64, quad [capacity,4] int32: cell ids in winding order)
+std::tuple<Tensor, Tensor, Tensor> tsdf_mesh_faces(const Tensor& volume, double w_min, int64_t capacity)
+{
+    const char* op = "tsdf_mesh_faces";
+    const OpScope scope(volume);
+    const VolumeArg v = check_volume(volume, op, true);
+    TORCH_CHECK(capacity >= 0, op, ": capacity must not be negative");
+    const float wm = not_nan_f32(w_min, op, "w_min");
+    Tensor count = at::zeros({1}, volume.options().dtype(at::kLong));
+    Tensor edge = at::empty({capacity}, volume.options().dtype(at::kLong));
+    Tensor quad = at::empty({capacity, 4}, volume.options().dtype(at::kInt));
+    check_status(estd_tsdf_mesh_faces(v.tsdf, v.weight, (int)v.Z, (int)v.Y, (int)v.X, wm,
+                                      reinterpret_cast<unsigned long long*>(count.data_ptr<int64_t>()), (long long)capacity,
+                                      capacity ? reinterpret_cast<long long*>(edge.data_ptr<int64_t>()) : nullptr,
+                                      capacity ? quad.data_ptr<int32_t>() : nullptr, cur_stream()), "estd_tsdf_mesh_faces");
+    return {count, edge, quad};
 }
 
 // ------------------------------------------------------------------------------------------------ cross-view consistency
@@ -1222,6 +1268,9 @@ TORCH_LIBRARY(estdepth_hip, m)
     m.def("tsdf_integrate_color_(Tensor(a!) volume, Tensor(b!) color, Tensor[] depths, Tensor[] confs, Tensor[] images, Tensor mats, float trunc, "
           "float z_near, float conf_min, bool weighted, float w_max, bool no_skip) -> Tensor(a!)");
     m.def("tsdf_edge_colors(Tensor volume, Tensor color, Tensor edge) -> Tensor");
+    m.def("tsdf_mesh_vertices(Tensor volume, Tensor? color, float voxel_size, Tensor origin, float w_min, int capacity) -> "
+          "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("tsdf_mesh_faces(Tensor volume, float w_min, int capacity) -> (Tensor, Tensor, Tensor)");
     m.def("tsdf_raycast_color(Tensor volume, Tensor color, Tensor mat, int H, int W, float t_min, float dt, int n_steps, float w_min) -> "
           "(Tensor, Tensor, Tensor, Tensor)");
     m.def("depth_consistency(Tensor target, Tensor[] sources, Tensor mats, float px_max, float rel_max, float z_near) -> "
@@ -1281,6 +1330,8 @@ TORCH_LIBRARY_IMPL(estdepth_hip, CUDA, m)
     m.impl("tsdf_raycast", tsdf_raycast);
     m.impl("tsdf_integrate_color_", tsdf_integrate_color_);
     m.impl("tsdf_edge_colors", tsdf_edge_colors);
+    m.impl("tsdf_mesh_vertices", tsdf_mesh_vertices);
+    m.impl("tsdf_mesh_faces", tsdf_mesh_faces);
     m.impl("tsdf_raycast_color", tsdf_raycast_color);
     m.impl("depth_consistency", depth_consistency);
     m.impl("cloud_cell_keys", cloud_cell_keys);

@@ -9,6 +9,7 @@
     vol.save_ply("scene.ply")
     maps = vol.render(pose, K, (H, W))                              # depth / normal / weight of the fused surface in any camera
     out = vol.track(depth, pose_guess, K)                           # the guess refined against the fused surface before the frame is fused
+    mesh = vol.extract_mesh()                                       # the fused surface as triangles (surface nets); vol.save_mesh("scene_mesh.ply")
 
 Colour: ``TSDFVolume(..., color=True)`` keeps the frames' colour beside the distances -- pass ``imgs=clip.imgs`` to ``integrate_outputs`` (or
 ``images=`` to ``integrate``); ``extract_points`` and ``render`` then return a ``"color"`` entry and ``save_ply`` writes red / green / blue.
@@ -317,6 +318,30 @@ class TSDFVolume:
         write_ply(path, rec.numpy(), rgb)
         return rec.shape[0]
 
+    def extract_mesh(self, w_min=1.0):
+        """The fused surface as a triangle mesh by naive surface nets (csrc/mesh/tsdf_mesh.hip; the contract: include/estd_hip.h,
+        estd_tsdf_mesh_vertices / estd_tsdf_mesh_faces): one vertex per cell whose eight corner voxels have weight >= ``w_min`` and differ
+        in sign, one quad = two triangles per sign-changing voxel edge whose four cells are observed -> dict(xyz [V,3], normal [V,3] (towards
+        the free space; the triangles are counter-clockwise seen from there), weight [V], cell [V] int64, faces [F,3] int32, edge [F/2]
+        int64, count = V) on the device, and ``color`` [V,3] for a colour volume.  Vertices come in ascending cell id, quads in ascending
+        edge id (= 3 * voxel + axis, the ids of ``extract_points``) with their two triangles consecutive: the result is the same from
+        call to call, bit for bit.  A vertex no face references is kept.  Both kernels count first, the outputs are allocated exactly.
+        Known limit: a cell that two separate sheets cross gets one vertex, so the sheets pinch together there."""
+        return sorted_mesh(ops.tsdf_mesh_vertices, ops.tsdf_mesh_faces, self.volume, self.color, self.voxel_size, self.origin, w_min)
+
+    def save_mesh(self, path, w_min=1.0, color_scale=1.0, color_offset=0.0):
+        """``extract_mesh`` as a binary little-endian PLY with normals and a face element (host side); colour as in ``save_ply``.
+        -> (vertices, triangles)"""
+        m = self.extract_mesh(w_min=w_min)
+        rec = torch.cat([m["xyz"], m["normal"]], 1).cpu().contiguous()
+        rgb = None
+        if self.color is not None:
+            c = m["color"].cpu().numpy().astype(np.float64) * _three(color_scale, "color_scale") + _three(color_offset, "color_offset")
+            rgb = np.clip(np.rint(np.nan_to_num(c)), 0, 255).astype(np.uint8)
+        faces = m["faces"].cpu().numpy()
+        write_ply(path, rec.numpy(), rgb, faces=faces)
+        return rec.shape[0], faces.shape[0]
+
     def compare(self, other, threshold=0.05, w_min=1.0, max_dist=None, downsample=None, cell=None):
         """The 3D scores (``cloud_metrics.compare_clouds``: accuracy, completeness, chamfer, precision / recall / F-score at ``threshold``
         metres, ...) of this volume's surface as the prediction against ``other`` as the ground truth: another ``TSDFVolume`` -- both sides
@@ -393,10 +418,54 @@ def render_plan(dims, voxel_size, origin, z_near, cam_pose, cam_intr, image_hw, 
     return mats, (H, W), t_min, dt, n_steps, stacked
 
 
-def write_ply(path, xyz_normal, rgb=None):
+def sorted_mesh(vertices_op, faces_op, volume, color, voxel_size, origin, w_min):
+    """The host ordering of ``TSDFVolume.extract_mesh`` over the two operators (ops.tsdf_mesh_vertices / ops.tsdf_mesh_faces): count,
+    allocate exactly, sort the vertex records by cell id and the quads by edge id, turn the quads' cell ids into vertex indices by a
+    binary search in the sorted cell ids, and split every quad into its triangles (0, 1, 2), (0, 2, 3)."""
+    n_v = int(vertices_op(volume, color, voxel_size, origin, w_min, 0)[0].item())
+    n_q = int(faces_op(volume, w_min, 0)[0].item())
+    _, cell, xyz, normal, weight, rgb = vertices_op(volume, color, voxel_size, origin, w_min, n_v)
+    _, edge, quad = faces_op(volume, w_min, n_q)
+    cell, order = torch.sort(cell)
+    edge, q_order = torch.sort(edge)
+    index = torch.searchsorted(cell, quad[q_order].to(torch.int64))
+    faces = index[:, [0, 1, 2, 0, 2, 3]].reshape(-1, 3).to(torch.int32)
+    out = {"xyz": xyz[order], "normal": normal[order], "weight": weight[order], "cell": cell, "faces": faces, "edge": edge, "count": n_v}
+    if rgb is not None:
+        out["color"] = rgb[order]
+    return out
+
+
+def mesh_edge_stats(faces):
+    """``faces`` [F,3] integer tensor (any device) -> dict(boundary, manifold, non_manifold: the mesh edges shared by one, by two and by
+    more than two triangles; euler: referenced vertices - edges + faces), by a ``unique`` over int64 keys lo * (max + 1) + hi."""
+    f = faces.to(torch.int64)
+    if f.shape[0] == 0:
+        return dict(boundary=0, manifold=0, non_manifold=0, euler=0)
+    e = torch.cat([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]])
+    key = e.min(1).values * (int(f.max().item()) + 1) + e.max(1).values
+    counts = torch.unique(key, return_counts=True)[1]
+    used = int(torch.unique(f).shape[0])
+    return dict(boundary=int((counts == 1).sum().item()), manifold=int((counts == 2).sum().item()), non_manifold=int((counts > 2).sum().item()),
+                euler=used - int(counts.shape[0]) + int(f.shape[0]))
+
+
+def write_ply(path, xyz_normal, rgb=None, faces=None):
     """xyz_normal: float32 array [N,6] -> binary little-endian PLY (x y z nx ny nz); ``rgb``: uint8 array [N,3] appends uchar red green
-    blue to every vertex (27 bytes per record)"""
+    blue to every vertex (27 bytes per record); ``faces``: integer array [F,3] appends a face element (``property list uchar int
+    vertex_indices``, 13 bytes per triangle).  Without ``faces`` the file is what it was before the argument existed, byte for byte."""
     n = int(xyz_normal.shape[0])
+    tail, face_body = "", b""
+    if faces is not None:
+        faces = np.asarray(faces)
+        if faces.ndim != 2 or faces.shape[1] != 3 or faces.dtype.kind not in "iu":
+            raise RuntimeError("write_ply: faces must be an integer array [F,3], got %s %s" % (faces.dtype, faces.shape))
+        if faces.size and (int(faces.min()) < 0 or int(faces.max()) >= n):
+            raise RuntimeError("write_ply: a face names a vertex outside 0..%d" % (n - 1))
+        tail = "element face %d\nproperty list uchar int vertex_indices\n" % faces.shape[0]
+        frec = np.empty(faces.shape[0], dtype=[("n", "u1"), ("v", "<i4", (3,))])
+        frec["n"], frec["v"] = 3, faces
+        face_body = frec.tobytes()
     head = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
             "property float nx\nproperty float ny\nproperty float nz\n" % n)
     if rgb is None:
@@ -410,20 +479,23 @@ def write_ply(path, xyz_normal, rgb=None):
         rec["v"], rec["c"] = xyz_normal, rgb
         body = rec.tobytes()
     with open(path, "wb") as f:
-        f.write((head + "end_header\n").encode("ascii"))
+        f.write((head + tail + "end_header\n").encode("ascii"))
         f.write(body)
+        f.write(face_body)
 
 
 _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
               "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
 
 
-def read_ply(path):
+def read_ply(path, faces=False):
     """The counterpart of ``write_ply`` -> dict(xyz float32 [N,3], normal float32 [N,3] or None, rgb uint8 [N,3] or None) as numpy arrays.
     Reads what ``write_ply`` writes and any ``binary_little_endian`` or ``ascii`` file whose vertex element has float x y z, optionally
     float nx ny nz and uchar red green blue; other vertex properties are skipped by their declared size, other elements (faces) are
     ignored -- the vertex element must come first in a binary file unless the elements before it have no list property.  A big-endian or
-    malformed file raises RuntimeError."""
+    malformed file raises RuntimeError.  ``faces=True`` adds ``faces`` int32 [F,3] from the face element's one list property
+    (``vertex_indices`` / ``vertex_index``; [0,3] without a face element): triangles only, a list of any other length raises RuntimeError,
+    and so does an index outside the vertices."""
     def bad(why):
         raise RuntimeError("read_ply: %s: %s" % (path, why))
     with open(path, "rb") as f:
@@ -437,7 +509,7 @@ def read_ply(path):
     except UnicodeDecodeError:
         bad("the header is not ASCII")
     body = data[stop + 1:]
-    fmt, elements = None, []                                   # elements: [name, count, [(property, dtype or None for a list)]]
+    fmt, elements, lists = None, [], {}                        # elements: [name, count, [(property, dtype or None for a list)]]
     for w in lines[1:]:
         if not w or w[0] in ("comment", "obj_info"):
             continue
@@ -449,6 +521,7 @@ def read_ply(path):
             elements[-1][2].append((w[2], _PLY_TYPES[w[1]]))
         elif w[0] == "property" and elements and len(w) == 5 and w[1] == "list" and w[2] in _PLY_TYPES and w[3] in _PLY_TYPES:
             elements[-1][2].append((w[4], None))
+            lists[(len(elements) - 1, w[4])] = (_PLY_TYPES[w[2]], _PLY_TYPES[w[3]])     # (type of the length, type of the items)
         else:
             bad("header line %r not understood" % " ".join(w))
     if fmt not in ("binary_little_endian", "ascii"):
@@ -490,8 +563,46 @@ def read_ply(path):
             bad("%d vertices of %d bytes declared, the file holds %d bytes" % (n, dt.itemsize, len(body) - offset))
         rec = np.frombuffer(body, dtype=dt, count=n, offset=offset)
         col = lambda keys, dt_: np.ascontiguousarray(np.stack([rec[k] for k in keys], 1).astype(dt_)) if n else np.zeros((0, 3), dt_)
-    return dict(xyz=col(("x", "y", "z"), np.float32), normal=col(("nx", "ny", "nz"), np.float32) if has_normal else None,
-                rgb=col(("red", "green", "blue"), np.uint8) if has_rgb else None)
+    out = dict(xyz=col(("x", "y", "z"), np.float32), normal=col(("nx", "ny", "nz"), np.float32) if has_normal else None,
+               rgb=col(("red", "green", "blue"), np.uint8) if has_rgb else None)
+    if not faces:
+        return out
+    fat = [i for i, e in enumerate(elements) if e[0] == "face"]
+    if len(fat) > 1:
+        bad("more than one face element")
+    tri = np.zeros((0, 3), np.int32)
+    if fat:
+        _, nf, fprops = elements[fat[0]]
+        if len(fprops) != 1 or fprops[0][1] is not None or fprops[0][0] not in ("vertex_indices", "vertex_index"):
+            bad("the face element needs exactly one property, the list vertex_indices")
+        if any(t is None for e in elements[:fat[0]] for _, t in e[2]):
+            bad("a list property in front of the face element")
+        ct, it = lists[(fat[0], fprops[0][0])]
+        if fmt == "ascii":
+            skip = sum(e[1] for e in elements[:fat[0]])
+            if len(rows) < skip + nf:
+                bad("%d face lines declared, the file ends early" % nf)
+            try:
+                table = [[int(v) for v in r.split()] for r in rows[skip:skip + nf]]
+            except ValueError:
+                bad("a face line is not a list of integers")
+            if any(len(r) != 4 or r[0] != 3 for r in table):
+                bad("a face is not a triangle (only lists of three indices are read)")
+            tri = np.array([r[1:] for r in table], dtype=np.int64).reshape(nf, 3)
+        else:
+            offset = sum(e[1] * sum(np.dtype(t).itemsize for _, t in e[2]) for e in elements[:fat[0]])
+            fdt = np.dtype([("n", "<" + ct), ("v", "<" + it, (3,))])
+            have = min(nf, max(len(body) - offset, 0) // fdt.itemsize)
+            frec = np.frombuffer(body, dtype=fdt, count=have, offset=offset)
+            if np.any(frec["n"] != 3):
+                bad("a face is not a triangle (only lists of three indices are read)")
+            if have < nf:
+                bad("%d faces of %d bytes declared, the file holds %d bytes" % (nf, fdt.itemsize, len(body) - offset))
+            tri = frec["v"].astype(np.int64)
+        if tri.size and (tri.min() < 0 or tri.max() >= n):
+            bad("a face names a vertex outside 0..%d" % (n - 1))
+    out["faces"] = np.ascontiguousarray(tri.astype(np.int32))
+    return out
 
 
 def frustum_volume(cam_pose, cam_intr, image_hw, depth_min, depth_max, dims, voxel_size):

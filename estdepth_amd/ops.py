@@ -159,12 +159,13 @@ def profile_mark(idx):
 # One helper per kind of check for the ctypes front ends of every operator but the convolution plans' (csrc/torch_ops.cpp has the same
 # set for the torch binding, and each operator calls them in the same order there); each takes the operator's and the argument's name
 # for its message.
-def _volume(volume, op):
-    """the volume argument: two float32 planes (D, weight), contiguous, on a device, X % 4 == 0 -> (Z, Y, X, address of the weight plane)"""
+def _volume(volume, op, any_x=False):
+    """the volume argument: two float32 planes (D, weight), contiguous, on a device, X % 4 == 0 (``any_x``: the mesh kernels move one
+    voxel per lane and take any X) -> (Z, Y, X, address of the weight plane)"""
     _need(isinstance(volume, torch.Tensor) and volume.dim() == 4 and volume.shape[0] == 2, "%s: volume must be [2,Z,Y,X] (D plane, weight plane)" % op)
     _chk(volume, "volume", op=op)
     Z, Y, X = volume.shape[1:]
-    _need(X % 4 == 0, "%s: X must be a multiple of 4, got %d" % (op, X))
+    _need(any_x or X % 4 == 0, "%s: X must be a multiple of 4, got %d" % (op, X))
     return Z, Y, X, volume.data_ptr() + 4 * Z * Y * X
 
 
@@ -1261,6 +1262,60 @@ def tsdf_raycast_color(volume, color, mat, H, W, t_min, dt, n_steps, w_min):
     _need(color is not None, "tsdf_raycast_color: color must be a tensor")
     out = _tsdf_raycast("tsdf_raycast_color", volume, color, mat, H, W, t_min, dt, n_steps, w_min, False)
     return out[:3] + out[4:]
+
+
+# ---------------------------------------------------------------------------------- surface nets (csrc/mesh/tsdf_mesh.hip)
+def tsdf_mesh_vertices(volume, color, voxel_size, origin, w_min, capacity):
+    """The surface-net vertices of ``volume`` [2,Z,Y,X] (any X), one per active cell -> (count [1] int64 on the device: the TOTAL number,
+    cell [capacity] int64, xyz [capacity,3], normal [capacity,3], weight [capacity], color [capacity,3] or None); ``color``: the colour
+    planes [3,Z,Y,X] or None; ``capacity`` 0 counts only; records come in no fixed order (sort by ``cell``).  ``origin``: CPU float32
+    [3].  The contract is spelled out in include/estd_hip.h (estd_tsdf_mesh_vertices)."""
+    capacity = int(capacity)
+    if _use_torch():
+        out = T().tsdf_mesh_vertices(volume, color, float(voxel_size), origin, float(w_min), capacity)
+        return tuple(out[:5]) + (out[5] if color is not None else None,)
+    op = "tsdf_mesh_vertices"
+    Z, Y, X, weight = _volume(volume, op, any_x=True)
+    if color is not None:
+        _color_planes(color, volume, op)
+    _need(capacity >= 0, "%s: capacity must not be negative" % op)
+    _positive(voxel_size, op, "voxel_size")
+    _not_nan(w_min, op, "w_min")
+    org = (ctypes.c_float * 3)(*_host_values(origin, 3, op, "origin", "[3]", True))
+    dev = volume.device
+    with torch.cuda.device(dev):
+        count = torch.zeros(1, device=dev, dtype=torch.int64)
+        cell = torch.empty(capacity, device=dev, dtype=torch.int64)
+        xyz, normal, weight_out = torch.empty((capacity, 3), device=dev), torch.empty((capacity, 3), device=dev), torch.empty(capacity, device=dev)
+        rgb = torch.empty((capacity, 3), device=dev) if color is not None else None
+        pp = (lambda t: _p(t)) if capacity else (lambda t: None)
+        N.check(N.lib().estd_tsdf_mesh_vertices(_p(volume), ctypes.c_void_p(weight), _p(color), Z, Y, X, float(voxel_size), org, float(w_min),
+                                                _p(count), capacity, pp(cell), pp(xyz), pp(normal), pp(weight_out), pp(rgb), _stream()),
+                "estd_tsdf_mesh_vertices")
+    return count, cell, xyz, normal, weight_out, rgb
+
+
+def tsdf_mesh_faces(volume, w_min, capacity):
+    """The surface-net quads of ``volume`` [2,Z,Y,X] (any X), one per crossing edge whose four cells exist and are observed -> (count [1]
+    int64 on the device: the TOTAL number, edge [capacity] int64 = 3 * voxel + axis, quad [capacity,4] int32: the four cell ids in winding
+    order, triangles (0, 1, 2) and (0, 2, 3)); ``capacity`` 0 counts only; no fixed order (sort by ``edge``).  include/estd_hip.h,
+    estd_tsdf_mesh_faces."""
+    capacity = int(capacity)
+    if _use_torch():
+        return tuple(T().tsdf_mesh_faces(volume, float(w_min), capacity))
+    op = "tsdf_mesh_faces"
+    Z, Y, X, weight = _volume(volume, op, any_x=True)
+    _need(capacity >= 0, "%s: capacity must not be negative" % op)
+    _not_nan(w_min, op, "w_min")
+    dev = volume.device
+    with torch.cuda.device(dev):
+        count = torch.zeros(1, device=dev, dtype=torch.int64)
+        edge = torch.empty(capacity, device=dev, dtype=torch.int64)
+        quad = torch.empty((capacity, 4), device=dev, dtype=torch.int32)
+        pp = (lambda t: _p(t)) if capacity else (lambda t: None)
+        N.check(N.lib().estd_tsdf_mesh_faces(_p(volume), ctypes.c_void_p(weight), Z, Y, X, float(w_min), _p(count), capacity, pp(edge), pp(quad),
+                                             _stream()), "estd_tsdf_mesh_faces")
+    return count, edge, quad
 
 
 # ---------------------------------------------------------------------------------- cross-view consistency (csrc/depth_consistency.hip)

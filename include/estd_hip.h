@@ -728,6 +728,44 @@ typedef struct estd_frame_align_desc {
 long long estd_frame_align_partials(int H, int W);
 int estd_frame_align(const estd_frame_align_desc* desc, estd_stream_t stream);
 
+/* The fused surface as a triangle mesh by naive surface nets (csrc/mesh/tsdf_mesh.hip; float64 form: tests/tsdf_mesh_ref.py): one vertex
+ * per surface cell, one quad (two triangles) per sign-changing voxel edge -- the edges the point extraction ids as 3 * voxel + axis.
+ * There is no case table: every topological decision compares stored fp32 values (D < 0, Wt >= w_min), so the vertex set and the face
+ * list are defined to the integer; only the vertex attributes carry rounding.  The volume is [Z][Y][X] as above, ANY X >= 1 here.
+ *
+ * Cells.  Cell c = (cz, cy, cx), 0 <= c < dims - 1, has the eight voxels c + {0,1}^3 as corners (corner order: x fastest, then y, then
+ *   z) and the linear voxel index of its lowest corner as id.  OBSERVED: all eight corner weights >= w_min (the ray caster's predicate).
+ *   ACTIVE: observed, with a corner D < 0 and a corner that is not.
+ * Crossings.  An edge with D0 at its lower-index end crosses when exactly one of D0 < 0, D1 < 0 holds; s = D0 / (D0 - D1) (IEEE division).
+ * Vertex of an active cell.  Its twelve edges in a fixed order: the four x-edges, then the y-, then the z-edges; within an axis by the
+ *   offsets (0/1) of the edge on the two other axes, the lower axis fastest: (0,0), (1,0), (0,1), (1,1).  Every crossing gives the
+ *   cell-local point with s on the edge's axis and the edge's offsets on the other two; the points are added in that order, starting
+ *   from 0, and divided by their number n:  xyz_k = fma((float)c_k + 0.5f + sum_k / n, voxel_size, origin_k)     (k = x, y, z)
+ *   normal: g_k = the sum over the four k-edges, in the same order and from 0, of D1 - D0; normal = g / sqrt(fma(gz, gz, fma(gy, gy,
+ *           gx gx))), the zero vector when that length is 0.  Points towards increasing D = the free space.
+ *   weight: the eight corner weights added in corner order from 0, times 0.125.
+ *   colour (color != NULL; [3][Z][Y][X]): per channel the sum over the crossings, same order, of fma(s, C1 - C0, C0), divided by n.
+ * Faces.  For a voxel v and an axis a whose +a edge crosses, with (b, c) the next two axes cyclically (x: y z; y: z x; z: x y): the four
+ *   cells round the edge are q0 = v - e_b - e_c, q1 = v - e_c, q2 = v, q3 = v - e_b.  All four must exist and be observed, else there
+ *   is no face.  The record is {edge = 3 * index of v + a, quad}: quad = (q0, q1, q2, q3) when D0 < 0 (free space on the +a side), else
+ *   (q3, q2, q1, q0); its triangles are (quad0, quad1, quad2), (quad0, quad2, quad3): counter-clockwise seen from the free side.  Every
+ *   cell of a record is active, so it is among the vertices.
+ * Known limit: a cell two separate sheets cross gets ONE vertex, the sheets pinch together there (marching cubes would keep them apart).
+ *
+ * Protocol of both calls (the point extraction's): `counter` (device, zeroed by the caller) ends at the TOTAL number of records -- one
+ * integer increment per wave (ballot + population count; no float atomics); records whose slot is >= capacity are dropped;
+ * capacity == 0 counts only (the output pointers may then be NULL).  Order unspecified: sort by cell / by edge.  origin3 is a HOST pointer.
+ * cell [capacity] (int64), xyz, normal, vertex_color [capacity][3], vertex_weight [capacity]; edge [capacity] (int64), quad
+ * [capacity][4] (int32, 16-byte aligned).  A dimension of 1 has no cells: ESTD_OK, nothing is launched or written.
+ * ESTD_ERR_ARG (before any launch): a null tsdf, weight, origin3 or counter, an output pointer null with capacity > 0 (vertex_color:
+ * only with color), capacity < 0, voxel_size not positive and finite, w_min NaN, a dimension <= 0.  ESTD_ERR_UNSUPPORTED: Z > 65535,
+ * Y > 262140, X > 2^20, or more than 2^31 - 1 voxels (the ids in `quad` are 32-bit). */
+int estd_tsdf_mesh_vertices(const float* tsdf, const float* weight, const float* color, int Z, int Y, int X, float voxel_size,
+                            const float* origin3, float w_min, unsigned long long* counter, long long capacity, long long* cell,
+                            float* xyz, float* normal, float* vertex_weight, float* vertex_color, estd_stream_t stream);
+int estd_tsdf_mesh_faces(const float* tsdf, const float* weight, int Z, int Y, int X, float w_min, unsigned long long* counter,
+                         long long capacity, long long* edge, int* quad, estd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,9 @@ ground-truth depth.  Needs an MI355X (the model has no CPU path).
     python tools/run_stream.py --synthetic 8 --out /tmp/eval --fuse /tmp/eval/scene.ply --color --render-fused
         # + colour: every target's 0..255 RGB frame is fused beside its depth; scene.ply gets red / green / blue and --render-fused also
         # writes <out>/fused_rgb/<stem>.png
+    python tools/run_stream.py --synthetic 8 --out /tmp/eval --fuse /tmp/eval/scene.ply --mesh /tmp/eval/scene_mesh.ply
+        # + the fused surface as a triangle mesh (TSDFVolume.save_mesh: surface nets; red / green / blue with --color) and a "mesh" block in
+        # metrics.json: vertices, faces and the mesh edges shared by one / two / more than two triangles
     python tools/run_stream.py --synthetic 8 --out /tmp/eval --fuse /tmp/eval/scene.ply --render-fused
         # + the fused volume ray-cast at every target's pose (TSDFVolume.render): <out>/fused_depth/*.npy beside refined_depth/ (float16,
         # same layout) and the fused depth scored against the same ground truth (errors_fused, fused_coverage, errors_on_covered)
@@ -105,6 +108,8 @@ def parse(argv=None):
     ap.add_argument("--no-feature-cache", action="store_true")
     ap.add_argument("--fuse", metavar="PATH.ply", help="fuse every target's depth / fused_prob into a TSDF volume on the device "
                                                        "(estdepth_amd.fusion3d) and write its surface points here")
+    ap.add_argument("--mesh", metavar="MESH.ply", help="with --fuse: also write the fused surface as a triangle mesh (TSDFVolume.save_mesh; "
+                    "with --color the vertices get red / green / blue) and report its size and edge statistics")
     ap.add_argument("--render-fused", action="store_true", help="with --fuse: after the stream, render the volume at every target's pose, "
                     "write the fused depth maps to <out>/fused_depth and score them against the ground truth")
     ap.add_argument("--color", action="store_true", help="with --fuse: fuse every target's frame (the reader's 0..255 RGB, whatever the model is "
@@ -133,6 +138,8 @@ def parse(argv=None):
     args = ap.parse_args(argv)
     if args.render_fused and not args.fuse:
         ap.error("--render-fused needs --fuse PATH.ply")
+    if args.mesh and not args.fuse:
+        ap.error("--mesh needs --fuse PATH.ply")
     if args.color and not args.fuse:
         ap.error("--color needs --fuse PATH.ply")
     if args.score_3d is not None and not args.fuse:
@@ -314,6 +321,13 @@ def run(args):
         os.makedirs(os.path.dirname(os.path.abspath(args.fuse)), exist_ok=True)
         report.update(fused_voxels=volume.fused_voxels(), points=volume.save_ply(args.fuse),
                       mean_fuse_ms=float(np.mean(fuse_ms[1:] or fuse_ms)))
+    if volume is not None and args.mesh:
+        from estdepth_amd.fusion3d import mesh_edge_stats
+        os.makedirs(os.path.dirname(os.path.abspath(args.mesh)), exist_ok=True)
+        n_vertices, n_faces = volume.save_mesh(args.mesh)
+        stats = mesh_edge_stats(volume.extract_mesh()["faces"])
+        report["mesh"] = {"path": args.mesh, "vertices": n_vertices, "faces": n_faces, "boundary_edges": stats["boundary"],
+                          "manifold_edges": stats["manifold"], "non_manifold_edges": stats["non_manifold"]}
     if args.track and volume is not None:
         report["tracking"] = {"frames": tracked, "dist_max": args.track_dist if args.track_dist is not None else volume.trunc,
                               "max_iter": args.track_iters, "mean_track_ms": float(np.mean(track_ms[1:] or track_ms or [0.0]))}

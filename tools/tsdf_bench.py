@@ -20,7 +20,13 @@ whose weights / whose D values were read per ray), beside the fuse + extract pas
 
 times the colour path beside the plain one on the 256^3 volume: the T = 3 fuse with and without colour (estd_tsdf_integrate_color: five
 planes per touched group instead of two), the edge colours of the extracted points, and the 640 x 480 render with and without a colour map
-from the held-out pose.  The two plain figures are the ones to hold against another commit's."""
+from the held-out pose.  The two plain figures are the ones to hold against another commit's.
+
+    python tools/tsdf_bench.py --mesh [--reps 200] [--out profiles/tsdf_mesh_bench.txt]
+
+times TSDFVolume.extract_mesh (csrc/mesh/tsdf_mesh.hip: surface nets) on the 256^3 volume after the T = 3 fuse, beside extract_points:
+the four kernel launches (cells and faces, each counting and then filling) and the host ordering behind them (two sorts, the binary
+search of the cell ids, the triangle split) separately, each between device events, and the whole call with its two count read-backs."""
 import argparse
 import os
 import sys
@@ -59,10 +65,13 @@ def main():
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--out")
     ap.add_argument("--raycast", action="store_true", help="time the ray caster (csrc/tsdf_raycast.hip) instead of integrate / extract")
+    ap.add_argument("--mesh", action="store_true", help="time extract_mesh (kernels and host ordering apart) beside extract_points")
     ap.add_argument("--color", action="store_true", help="time the colour fuse, the edge colours and the colour render beside the plain figures")
     args = ap.parse_args()
     if args.raycast:
         return raycast_main(args)
+    if args.mesh:
+        return mesh_main(args)
     if args.color:
         return color_main(args)
     import tsdf_ref as R
@@ -114,6 +123,60 @@ def main():
             "  (a) beside the %.1f ms Joint step it follows: %.1f %% of the step" % (JOINT_STEP_MS, 100.0 * t_a / JOINT_STEP_MS),
             "  (a) back to back, no cache flush between calls: %.3f ms" % t_a_warm,
         ]
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        open(args.out, "w").write(text + "\n")
+
+
+def mesh_main(args):
+    import tsdf_ref as R
+    from estdepth_amd import ops
+    from estdepth_amd.fusion3d import TSDFVolume, frustum_volume, mesh_edge_stats
+    assert torch.cuda.is_available(), "tools/tsdf_bench.py needs a ROCm device"
+    dev = torch.device("cuda:0")
+    H, W, T, vox, dmin, dmax, dims = 480, 640, 3, 0.03, 0.1, 10.0, (256, 256, 256)
+    K = R.intrinsics(H, W)
+    poses = R.scene_poses(T, seed=1)
+    depths = torch.from_numpy(np.stack([R.raycast_scene(P, K, H, W) for P in poses]).astype(np.float32)).to(dev)
+    flush = torch.empty(256 << 20, device=dev)          # 1 GiB
+    origin = frustum_volume(torch.from_numpy(poses[0]), torch.from_numpy(K), (H, W), dmin, dmax, dims, vox)
+    vol = TSDFVolume(dims, vox, origin, device=dev)
+    vol.integrate(depths, torch.from_numpy(poses), torch.from_numpy(K))
+    m = vol.extract_mesh()
+    pts = vol.extract_points()
+    n_v, n_q = m["count"], int(m["edge"].shape[0])
+    stats = mesh_edge_stats(m["faces"])
+    v, o = vol.volume, vol.origin
+    t_pts = timed(lambda: ops.tsdf_extract_points(v, vox, o, 1.0, pts["count"]), args.reps, flush)
+    t_vc = timed(lambda: ops.tsdf_mesh_vertices(v, None, vox, o, 1.0, 0), args.reps, flush)
+    t_vf = timed(lambda: ops.tsdf_mesh_vertices(v, None, vox, o, 1.0, n_v), args.reps, flush)
+    t_fc = timed(lambda: ops.tsdf_mesh_faces(v, 1.0, 0), args.reps, flush)
+    t_ff = timed(lambda: ops.tsdf_mesh_faces(v, 1.0, n_q), args.reps, flush)
+    _, cell, xyz, normal, weight, _ = ops.tsdf_mesh_vertices(v, None, vox, o, 1.0, n_v)
+    _, edge, quad = ops.tsdf_mesh_faces(v, 1.0, n_q)
+
+    def order():
+        c, perm = torch.sort(cell)
+        e, q_perm = torch.sort(edge)
+        index = torch.searchsorted(c, quad[q_perm].to(torch.int64))
+        return xyz[perm], normal[perm], weight[perm], index[:, [0, 1, 2, 0, 2, 3]].reshape(-1, 3).to(torch.int32), e
+
+    t_order = timed(order, args.reps)
+    t_all = timed(lambda: vol.extract_mesh(), args.reps, flush)
+    t_all_warm = timed(lambda: vol.extract_mesh(), args.reps)
+    lines = ["tsdf_bench --mesh: %d x %d maps, T = %d, voxel %.3f m, %d repetitions per figure, %s" % (W, H, T, vox, args.reps, torch.cuda.get_device_name(0)),
+             "volume %d x %d x %d (Z Y X), origin (%.2f, %.2f, %.2f): %d vertices, %d triangles; mesh edges shared by 1 / 2 / more triangles: %d / %d / %d"
+             % (dims + origin + (n_v, 2 * n_q, stats["boundary"], stats["manifold"], stats["non_manifold"])),
+             "  extract_points kernel (the parent's read-out)      %8.3f ms with %d records" % (t_pts, pts["count"]),
+             "  cell kernel                                        %8.3f ms count only, %.3f ms with %d records" % (t_vc, t_vf, n_v),
+             "  face kernel                                        %8.3f ms count only, %.3f ms with %d records" % (t_fc, t_ff, n_q),
+             "  the four launches of extract_mesh                  %8.3f ms (sum of the above)" % (t_vc + t_vf + t_fc + t_ff),
+             "  host ordering (2 sorts, searchsorted, split)       %8.3f ms, volume-independent, inputs in cache" % t_order,
+             "  extract_mesh, whole call                           %8.3f ms after a cache flush, %.3f ms back to back (two count read-backs included)"
+             % (t_all, t_all_warm),
+             "  every kernel figure: a 1 GiB buffer is rewritten (untimed) in front of the call, so the volume comes from HBM"]
     text = "\n".join(lines)
     print(text)
     if args.out:
