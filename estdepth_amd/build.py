@@ -31,7 +31,7 @@ AB_SOURCES = ["conv3d_wino.hip", "conv3d_split_bf16.hip", "conv2d_wino.hip", "co
 BUILD_AB = os.environ.get("ESTD_BUILD_AB", "0") == "1"
 if BUILD_AB:
     SOURCES = SOURCES + AB_SOURCES
-HEADERS = [os.path.join(ROOT, "include", "estd_hip.h"), os.path.join(CSRC, "estd_common.h")]
+HEADERS = [os.path.join(ROOT, "include", "estd_hip.h"), os.path.join(CSRC, "estd_common.h"), os.path.join(CSRC, "estd_device.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
          "-I" + os.path.join(ROOT, "include"), "-I" + CSRC] + (["-DESTD_BUILD_AB=1"] if BUILD_AB else [])
 MODE_STAMP = os.path.join(OUT_DIR, ".build_mode" + os.environ.get("ESTD_LIB_SUFFIX", ""))

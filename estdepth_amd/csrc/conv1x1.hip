@@ -22,18 +22,9 @@
 
 #include "estd_hip.h"
 #include "estd_common.h"
+#include "estd_device.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((__vector_size__(16)));
-constexpr unsigned OOB_OFFSET = 0xFFFFFF00u;
-
-__device__ __forceinline__ float4 as_float4(u32x4 v) { float4 f; __builtin_memcpy(&f, &v, 16); return f; }
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float* base, size_t bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)bytes, 0x00020000);
-}
 
 // SK = 1: the four waves of a workgroup own four neighbouring blocks.  SK = 4 (K-heavy layers on small maps: few blocks, long K): the
 // four waves of a workgroup share ONE block and split its input channels into four contiguous ranges; waves 1..3 hand their partial
@@ -53,8 +44,8 @@ __global__ __launch_bounds__(256) void conv1x1_nhwc_kernel(const estd_conv1x1_de
     const int Mtot = p.N * Ho * Wo;
     const int cin = p.cin, cout = p.cout;
 
-    const __amdgpu_buffer_rsrc_t rs_x = make_rsrc(p.in, (size_t)p.N * p.H * p.W * cin * 4);
-    const __amdgpu_buffer_rsrc_t rs_w = make_rsrc(p.w, (size_t)cout * cin * 4);
+    const __amdgpu_buffer_rsrc_t rs_x = make_rsrc_bytes(p.in, (size_t)p.N * p.H * p.W * cin * 4);
+    const __amdgpu_buffer_rsrc_t rs_w = make_rsrc_bytes(p.w, (size_t)cout * cin * 4);
     unsigned xoff[TM], woff[TN];
 #pragma unroll
     for (int t = 0; t < TM; ++t) {
@@ -129,8 +120,8 @@ __global__ __launch_bounds__(256) void conv1x1_nhwc_kernel(const estd_conv1x1_de
     }
 
     // ---- epilogue: folded BatchNorm, + residual, ReLU; 16-byte stores ----
-    const __amdgpu_buffer_rsrc_t rs_o = make_rsrc(p.out, (size_t)Mtot * cout * 4);
-    const __amdgpu_buffer_rsrc_t rs_r = make_rsrc(p.residual ? p.residual : p.out, (size_t)Mtot * cout * 4);
+    const __amdgpu_buffer_rsrc_t rs_o = make_rsrc_bytes(p.out, (size_t)Mtot * cout * 4);
+    const __amdgpu_buffer_rsrc_t rs_r = make_rsrc_bytes(p.residual ? p.residual : p.out, (size_t)Mtot * cout * 4);
     const float floor_ = p.relu ? 0.0f : ESTD_NO_FLOOR;
 #pragma unroll
     for (int a = 0; a < TN; ++a) {
@@ -323,8 +314,8 @@ __global__ __launch_bounds__(256) void conv1x1_lds_kernel(const estd_conv1x1_des
     }
 
     // ---- epilogue: folded BatchNorm, + residual, ReLU; 16-byte stores (as in the direct form) ----
-    const __amdgpu_buffer_rsrc_t rs_o = make_rsrc(p.out, (size_t)Mtot * cout * 4);
-    const __amdgpu_buffer_rsrc_t rs_r = make_rsrc(p.residual ? p.residual : p.out, (size_t)Mtot * cout * 4);
+    const __amdgpu_buffer_rsrc_t rs_o = make_rsrc_bytes(p.out, (size_t)Mtot * cout * 4);
+    const __amdgpu_buffer_rsrc_t rs_r = make_rsrc_bytes(p.residual ? p.residual : p.out, (size_t)Mtot * cout * 4);
     const float floor_ = p.relu ? 0.0f : ESTD_NO_FLOOR;
     const int mw = m0 + wm * TM * 16, nw = n0 + wn * TN * 16;
 #pragma unroll

@@ -18,27 +18,11 @@
 
 #include "estd_hip.h"
 #include "estd_common.h"
+#include "estd_device.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((__vector_size__(16)));
-typedef unsigned int u32x2 __attribute__((__vector_size__(8)));
-constexpr unsigned OOB_OFFSET = 0xFFFFFF00u;
-
 constexpr int TH = 8, TW = 16, MT = 2;
-
-__device__ __forceinline__ float4 as_float4(u32x4 v) { float4 f; __builtin_memcpy(&f, &v, 16); return f; }
-__device__ __forceinline__ u32x4 as_u32x4(float4 f) { u32x4 v; __builtin_memcpy(&v, &f, 16); return v; }
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float* base, size_t elems)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)(elems * 4), 0x00020000);
-}
-
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-__device__ __forceinline__ int lds_chunk_off(int v, int c) { return v * 128 + ((c ^ ((v >> 1) & 7)) << 4); }
 
 template <int NT, int DIL>
 __global__ __launch_bounds__(256, 2) void conv2d_k3_kernel(const estd_conv2d_desc p, int tiles_w, int tiles_h, int total_items)
@@ -103,7 +87,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_k3_kernel(const estd_conv2d_des
 #pragma unroll
     for (int it = 0; it < SIT; ++it) {
         const int e = tid + it * 256;
-        loff[it] = e < NEL ? lds_chunk_off(e >> 3, e & 7) : -1;
+        loff[it] = e < NEL ? lds_chunk_off<32>(e >> 3, e & 7) : -1;
     }
 
     // current item
@@ -111,7 +95,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_k3_kernel(const estd_conv2d_des
     decode(u, grp, n, th0, tw0);
     unsigned voff[SIT];
     brick_offsets(th0, tw0, voff);
-    __amdgpu_buffer_rsrc_t rs_in = make_rsrc(p.in + (size_t)n * img_in, img_in);
+    __amdgpu_buffer_rsrc_t rs_in = make_rsrc_f32(p.in + (size_t)n * img_in, img_in);
     float4 pf[SIT];
 #pragma unroll
     for (int it = 0; it < SIT; ++it) pf[it] = as_float4(__builtin_amdgcn_raw_buffer_load_b128(rs_in, voff[it], 0, 0));
@@ -119,7 +103,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_k3_kernel(const estd_conv2d_des
     int k = 0;                                              // global chunk counter -> LDS slot
     while (true) {
         const size_t wgrp_elems = (size_t)nchunks * 10 * QN * 256;          // packed floats per output group
-        const __amdgpu_buffer_rsrc_t rs_w = make_rsrc(p.w + (size_t)grp * wgrp_elems, wgrp_elems);
+        const __amdgpu_buffer_rsrc_t rs_w = make_rsrc_f32(p.w + (size_t)grp * wgrp_elems, wgrp_elems);
 
         f32x4 acc[MT][NT];
 #pragma unroll
@@ -150,7 +134,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_k3_kernel(const estd_conv2d_des
                 pf_soff = (c + 1) * 128;                                   // next 32-channel chunk of the same pixels
             } else if (has_next_item) {
                 brick_offsets(nth0, ntw0, nvoff);
-                if (nn_ != n) rs_in = make_rsrc(p.in + (size_t)nn_ * img_in, img_in);
+                if (nn_ != n) rs_in = make_rsrc_f32(p.in + (size_t)nn_ * img_in, img_in);
             }
 
             float4 bcur[QN], bnext[QN];
@@ -169,7 +153,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_k3_kernel(const estd_conv2d_des
 #pragma unroll
                 for (int m = 0; m < MT; ++m) {
                     const int vs = (row0 + m + kh * DIL) * IN_W + kw * DIL + pi;
-                    const int off0 = lds_chunk_off(vs, g);
+                    const int off0 = lds_chunk_off<32>(vs, g);
                     const float4 a0 = *reinterpret_cast<const float4*>(slot + off0);
                     const float4 a1 = *reinterpret_cast<const float4*>(slot + (off0 ^ 64));
                     const float av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
@@ -200,8 +184,8 @@ __global__ __launch_bounds__(256, 2) void conv2d_k3_kernel(const estd_conv2d_des
             float sc[NT], sh[NT];
 #pragma unroll
             for (int nn = 0; nn < NT; ++nn) { sc[nn] = p.scale[cb + nn]; sh[nn] = p.shift[cb + nn]; }
-            const __amdgpu_buffer_rsrc_t rs_out = make_rsrc(p.out + (size_t)n * img_out, img_out);
-            const __amdgpu_buffer_rsrc_t rs_res = make_rsrc((p.residual ? p.residual : p.out) + (size_t)n * img_out, img_out);
+            const __amdgpu_buffer_rsrc_t rs_out = make_rsrc_f32(p.out + (size_t)n * img_out, img_out);
+            const __amdgpu_buffer_rsrc_t rs_res = make_rsrc_f32((p.residual ? p.residual : p.out) + (size_t)n * img_out, img_out);
 #pragma unroll
             for (int m = 0; m < MT; ++m) {
                 const int y = th0 + row0 + m;
@@ -255,12 +239,10 @@ int launch2d(const estd_conv2d_desc& d, hipStream_t stream)
     const int groups = d.cout / (16 * NT);
     const int total = groups * d.N * tiles_h * tiles_w;
     const size_t lds = (size_t)2 * IN_H * IN_W * 128;
-    const int slots = estd_persistent_wgs(2);
-    int grid = total < slots ? total : slots;
-    if (grid >= 8) grid &= ~7;
+    const int grid = estd_persistent_grid(total, 2);
     estd_allow_dynamic_lds<conv2d_k3_kernel<NT, DIL>>((int)lds);
     hipLaunchKernelGGL((conv2d_k3_kernel<NT, DIL>), dim3(grid), dim3(256), lds, stream, d, tiles_w, tiles_h, total);
-    return hipGetLastError() == hipSuccess ? ESTD_OK : ESTD_ERR_LAUNCH;
+    return ESTD_LAUNCH_CHECK();
 }
 
 }  // namespace

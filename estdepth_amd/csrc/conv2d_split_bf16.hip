@@ -23,18 +23,12 @@
 
 #include "estd_hip.h"
 #include "estd_common.h"
+#include "estd_device.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((__vector_size__(16)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((__vector_size__(16)));
-typedef unsigned int u32x2 __attribute__((__vector_size__(8)));
-
 constexpr int TH = 8;
 constexpr int WREC_BYTES = 512 * 16;           // weight record of one (group, chunk, tap); 6144 used
-constexpr unsigned OOB_OFFSET = 0xFFFFFF00u;
 
 // Geometry of one instance: dilation 1 -> 8 x 32-pixel tiles (two 16-pixel M tiles per wave), brick 10 x 34;
 //                           dilation 2 -> 8 x 16-pixel tiles (one M tile per wave), brick 12 x 20 (two brick slots must fit LDS)
@@ -54,49 +48,6 @@ template <int DIL> struct Geo {
     static constexpr int LDS_DUMP = LDS_W + 2 * WREC_BYTES;
     static constexpr int LDS_TOTAL = LDS_DUMP + (512 - LAST_FULL) * 16;
 };
-
-__device__ __forceinline__ float4 as_float4(u32x4 v) { float4 f; __builtin_memcpy(&f, &v, 16); return f; }
-__device__ __forceinline__ float2 as_float2(u32x2 v) { float2 f; __builtin_memcpy(&f, &v, 8); return f; }
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, size_t bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-__device__ __forceinline__ void split2(float x0, float x1, unsigned& h, unsigned& m, unsigned& l)
-{
-    const bf16x2 hb = {(__bf16)x0, (__bf16)x1};
-    h = __builtin_bit_cast(unsigned, hb);
-    float r0 = x0 - __builtin_bit_cast(float, h << 16);
-    float r1 = x1 - __builtin_bit_cast(float, h & 0xffff0000u);
-    const bf16x2 mb = {(__bf16)r0, (__bf16)r1};
-    m = __builtin_bit_cast(unsigned, mb);
-    r0 -= __builtin_bit_cast(float, m << 16);
-    r1 -= __builtin_bit_cast(float, m & 0xffff0000u);
-    const bf16x2 lb = {(__bf16)r0, (__bf16)r1};
-    l = __builtin_bit_cast(unsigned, lb);
-}
-
-__device__ __forceinline__ void fill_item(char* smem, int o0, int o1, int o2, float4 a, float4 b)
-{
-    u32x4 h, m, l;
-    unsigned th, tm, tl;
-    split2(a.x, a.y, th, tm, tl); h[0] = th; m[0] = tm; l[0] = tl;
-    split2(a.z, a.w, th, tm, tl); h[1] = th; m[1] = tm; l[1] = tl;
-    split2(b.x, b.y, th, tm, tl); h[2] = th; m[2] = tm; l[2] = tl;
-    split2(b.z, b.w, th, tm, tl); h[3] = th; m[3] = tm; l[3] = tl;
-    *reinterpret_cast<u32x4*>(smem + o0) = h;
-    *reinterpret_cast<u32x4*>(smem + o1) = m;
-    *reinterpret_cast<u32x4*>(smem + o2) = l;
-}
-
-template <typename F, int... I>
-__device__ __forceinline__ void for_each_tap(F&& f, std::integer_sequence<int, I...>)
-{
-    (f(std::integral_constant<int, I>{}), ...);
-}
 
 template <int TAP, int MT>
 __device__ __forceinline__ void tap_pipeline()
@@ -143,10 +94,10 @@ __global__ __launch_bounds__(512, 1) void conv2d_k3_split_kernel(const estd_conv
     const int nsteps = (u_end - u0) * nchunks;
 
     const size_t in_bytes = (size_t)p.N * H * W * Cin * 4, out_bytes = (size_t)p.N * H * W * Cout * 4;
-    const __amdgpu_buffer_rsrc_t rs_in = make_rsrc(p.in, in_bytes);
-    const __amdgpu_buffer_rsrc_t rs_out = make_rsrc(p.out, out_bytes);
-    const __amdgpu_buffer_rsrc_t rs_res = make_rsrc(p.residual ? p.residual : p.out, p.residual ? out_bytes : 0);
-    const __amdgpu_buffer_rsrc_t rs_w = make_rsrc(p.w_split, (size_t)(Cout >> 5) * nchunks * 9 * WREC_BYTES);
+    const __amdgpu_buffer_rsrc_t rs_in = make_rsrc_bytes(p.in, in_bytes);
+    const __amdgpu_buffer_rsrc_t rs_out = make_rsrc_bytes(p.out, out_bytes);
+    const __amdgpu_buffer_rsrc_t rs_res = make_rsrc_bytes(p.residual ? p.residual : p.out, p.residual ? out_bytes : 0);
+    const __amdgpu_buffer_rsrc_t rs_w = make_rsrc_bytes(p.w_split, (size_t)(Cout >> 5) * nchunks * 9 * WREC_BYTES);
     const float floor_before = p.relu_before_residual ? 0.0f : -__builtin_huge_valf();
     const float floor_after = p.relu_after_residual ? 0.0f : -__builtin_huge_valf();
 
@@ -376,12 +327,10 @@ int launch_split2d(const estd_conv2d_desc& d, hipStream_t stream)
     const int tiles_w = (d.W + G_::TW - 1) / G_::TW, tiles_h = (d.H + TH - 1) / TH;
     const long long total = (long long)(d.cout >> 5) * d.N * tiles_h * tiles_w;
     if (total > 0x7fffffffLL) return ESTD_ERR_ARG;
-    const int slots = estd_persistent_wgs(1);
-    int grid = total < slots ? (int)total : slots;
-    if (grid >= 8) grid &= ~7;
+    const int grid = estd_persistent_grid(total, 1);
     estd_allow_dynamic_lds<conv2d_k3_split_kernel<DIL, RES>>((int)G_::LDS_TOTAL);
     hipLaunchKernelGGL((conv2d_k3_split_kernel<DIL, RES>), dim3(grid), dim3(512), G_::LDS_TOTAL, stream, d, tiles_w, tiles_h, (int)total);
-    return hipGetLastError() == hipSuccess ? ESTD_OK : ESTD_ERR_LAUNCH;
+    return ESTD_LAUNCH_CHECK();
 }
 
 }  // namespace

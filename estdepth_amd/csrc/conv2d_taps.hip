@@ -22,19 +22,9 @@
 
 #include "estd_hip.h"
 #include "estd_common.h"
+#include "estd_device.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((__vector_size__(16)));
-typedef unsigned int u32x3 __attribute__((__vector_size__(12)));
-constexpr unsigned OOB_OFFSET = 0xFFFFFF00u;
-
-__device__ __forceinline__ float4 as_float4(u32x4 v) { float4 f; __builtin_memcpy(&f, &v, 16); return f; }
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float* base, size_t bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)bytes, 0x00020000);
-}
 
 template <int TM, int TN, int PF, int SK>
 __global__ __launch_bounds__(256) void conv2d_taps_kernel(const estd_conv2d_taps_desc p, int Ho, int Wo, int tiles_m, int tiles_n)
@@ -50,8 +40,8 @@ __global__ __launch_bounds__(256) void conv2d_taps_kernel(const estd_conv2d_taps
     const int Mtot = p.N * Ho * Wo;
     const int cin = p.cin, cout = p.cout, ks = p.ksize;
 
-    const __amdgpu_buffer_rsrc_t rs_x = make_rsrc(p.in, (size_t)p.N * p.H * p.W * cin * 4);
-    const __amdgpu_buffer_rsrc_t rs_w = make_rsrc(p.w, (size_t)ks * ks * cout * cin * 4);
+    const __amdgpu_buffer_rsrc_t rs_x = make_rsrc_bytes(p.in, (size_t)p.N * p.H * p.W * cin * 4);
+    const __amdgpu_buffer_rsrc_t rs_w = make_rsrc_bytes(p.w, (size_t)ks * ks * cout * cin * 4);
     int xbase[TM];                                              // byte offset of the window's first pixel (negative in the padding: used with a valid tap only)
     unsigned xmask[TM], woff[TN];                               // bit (ky * ks + kx): that tap reads a pixel inside the map
 #pragma unroll
@@ -146,8 +136,8 @@ __global__ __launch_bounds__(256) void conv2d_taps_kernel(const estd_conv2d_taps
     }
 
     // ---- epilogue: folded BatchNorm, + residual, ReLU; 16-byte stores ----
-    const __amdgpu_buffer_rsrc_t rs_o = make_rsrc(p.out, (size_t)Mtot * cout * 4);
-    const __amdgpu_buffer_rsrc_t rs_r = make_rsrc(p.residual ? p.residual : p.out, (size_t)Mtot * cout * 4);
+    const __amdgpu_buffer_rsrc_t rs_o = make_rsrc_bytes(p.out, (size_t)Mtot * cout * 4);
+    const __amdgpu_buffer_rsrc_t rs_r = make_rsrc_bytes(p.residual ? p.residual : p.out, (size_t)Mtot * cout * 4);
     const float floor_ = p.relu ? 0.0f : ESTD_NO_FLOOR;
 #pragma unroll
     for (int a = 0; a < TN; ++a) {

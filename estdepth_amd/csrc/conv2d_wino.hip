@@ -28,6 +28,7 @@
 
 #include "estd_hip.h"
 #include "estd_common.h"
+#include "estd_device.h"
 
 #ifndef ESTD_W2ABL
 #define ESTD_W2ABL 0    // timing ablations only (wrong results when != 0): 1 no output stores, 2 no transform writes, 8 no weight stream,
@@ -44,25 +45,8 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((__vector_size__(16)));
-typedef unsigned int u32x2 __attribute__((__vector_size__(8)));
-constexpr unsigned OOB_OFFSET = 0xFFFFFF00u;
-
 constexpr int TH = 8, TW = 16;
 constexpr int TROWS = 16;                            // 4 row pairs x 4 transformed rows
-
-__device__ __forceinline__ float4 as_float4(u32x4 v) { float4 f; __builtin_memcpy(&f, &v, 16); return f; }
-__device__ __forceinline__ u32x4 as_u32x4(float4 f) { u32x4 v; __builtin_memcpy(&v, &f, 16); return v; }
-__device__ __forceinline__ float4 f4_sub(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
-__device__ __forceinline__ float4 f4_add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float* base, size_t elems)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)(elems * 4), 0x00020000);
-}
-
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 #if ESTD_C2TIME
 #define C2STAMP(slot) do { if (lane == 0 && blockIdx.x < 16 && item_no < 8)                                                       \
@@ -71,8 +55,6 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 #else
 #define C2STAMP(slot) do { } while (0)
 #endif
-
-__device__ __forceinline__ int lds_chunk_off(int v, int c) { return v * 128 + ((c ^ ((v >> 1) & 7)) << 4); }
 
 // DIL = 2: rows of equal parity form the F(2,3) sequences -- wave w owns output rows a, a + 2 with a = (w & 1) + 4 (w >> 1),
 // fed by brick rows a, a+2, a+4, a+6; column taps are two pixels apart.
@@ -142,13 +124,13 @@ __global__ __launch_bounds__(256, 2) void conv2d_wino_kernel(const estd_conv2d_d
 #pragma unroll
     for (int w = 0; w < 4; ++w)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) loff[w][i] = lds_chunk_off((w * 4 + i) * IN_W + (loader ? lzx : 0), lc);
+        for (int i = 0; i < 4; ++i) loff[w][i] = lds_chunk_off<32>((w * 4 + i) * IN_W + (loader ? lzx : 0), lc);
 
     int grp, n, th0, tw0;
     decode(u, grp, n, th0, tw0);
     unsigned voff[IN_H];
     brick_offsets(th0, tw0, voff, true);
-    __amdgpu_buffer_rsrc_t rs_in = make_rsrc(p.in + (size_t)n * img_in, img_in);
+    __amdgpu_buffer_rsrc_t rs_in = make_rsrc_f32(p.in + (size_t)n * img_in, img_in);
     float4 pf[IN_H];
 #pragma unroll
     for (int zy = 0; zy < IN_H; ++zy) pf[zy] = as_float4(__builtin_amdgcn_raw_buffer_load_b128(rs_in, voff[zy], 0, 0));
@@ -160,7 +142,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_wino_kernel(const estd_conv2d_d
     const size_t wgrp_elems = (size_t)nchunks * 13 * QN * 256;          // packed floats per output group (12 taps + 1 pad)
     float4 bq[WR][QN];
     {
-        const __amdgpu_buffer_rsrc_t rs_w0 = make_rsrc(p.w_wino + (size_t)grp * wgrp_elems, wgrp_elems);
+        const __amdgpu_buffer_rsrc_t rs_w0 = make_rsrc_f32(p.w_wino + (size_t)grp * wgrp_elems, wgrp_elems);
 #pragma unroll
         for (int t = 0; t < WD; ++t)
 #pragma unroll
@@ -173,7 +155,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_wino_kernel(const estd_conv2d_d
     int item_no = 0;
     while (true) {
         C2STAMP(0);
-        const __amdgpu_buffer_rsrc_t rs_w = make_rsrc(p.w_wino + (size_t)grp * wgrp_elems, wgrp_elems);
+        const __amdgpu_buffer_rsrc_t rs_w = make_rsrc_f32(p.w_wino + (size_t)grp * wgrp_elems, wgrp_elems);
 
         // folded BatchNorm of this lane's channels: requested HERE, a whole item ahead of the epilogue that uses it (requested there,
         // every item ended with an exposed L2 round trip: 900 cycles alone, 4 000-7 000 next to a busy memory pipeline)
@@ -187,7 +169,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_wino_kernel(const estd_conv2d_d
         const bool has_next_item = (u + 1 < u_end);
         int ngrp = grp, nn_ = n, nth0 = th0, ntw0 = tw0;
         if (has_next_item) decode(u + 1, ngrp, nn_, nth0, ntw0);
-        const __amdgpu_buffer_rsrc_t rs_wni = make_rsrc(p.w_wino + (size_t)ngrp * wgrp_elems, wgrp_elems);
+        const __amdgpu_buffer_rsrc_t rs_wni = make_rsrc_f32(p.w_wino + (size_t)ngrp * wgrp_elems, wgrp_elems);
 
         auto chunk_body = [&](auto first_c, const int c) {
             constexpr bool FIRST = decltype(first_c)::value;
@@ -214,7 +196,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_wino_kernel(const estd_conv2d_d
             int pf_soff = (c + 1) * 128;
             if (last_chunk) {
                 brick_offsets(nth0, ntw0, voff, has_next_item);
-                if (nn_ != n) rs_in = make_rsrc(p.in + (size_t)nn_ * img_in, img_in);
+                if (nn_ != n) rs_in = make_rsrc_f32(p.in + (size_t)nn_ * img_in, img_in);
                 pf_soff = 0;
             }
             const int wbase = c * 13 * QN;                                 // quads of this chunk's first tap
@@ -224,7 +206,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_wino_kernel(const estd_conv2d_d
             // A fragment of (transformed row i, column tap kw): two 16-byte LDS reads (channels 4g.., 16+4g..)
             auto load_a = [&](int tap, float4& a0, float4& a1) {
                 const int i = tap / 3, kw = tap % 3;
-                const int off0 = lds_chunk_off((wave * 4 + i) * IN_W + kw * DIL + pcol, g);
+                const int off0 = lds_chunk_off<32>((wave * 4 + i) * IN_W + kw * DIL + pcol, g);
                 a0 = *reinterpret_cast<const float4*>(slot + off0);
                 a1 = *reinterpret_cast<const float4*>(slot + (off0 ^ 64));
             };
@@ -291,8 +273,8 @@ __global__ __launch_bounds__(256, 2) void conv2d_wino_kernel(const estd_conv2d_d
         auto epilogue = [&](auto has_res_c) {
             constexpr bool HAS_RES = decltype(has_res_c)::value;
             const int cb = grp * 16 * NT + NT * col;
-            const __amdgpu_buffer_rsrc_t rs_out = make_rsrc(p.out + (size_t)n * img_out, img_out);
-            const __amdgpu_buffer_rsrc_t rs_res = make_rsrc((HAS_RES ? p.residual : p.out) + (size_t)n * img_out, img_out);
+            const __amdgpu_buffer_rsrc_t rs_out = make_rsrc_f32(p.out + (size_t)n * img_out, img_out);
+            const __amdgpu_buffer_rsrc_t rs_res = make_rsrc_f32((HAS_RES ? p.residual : p.out) + (size_t)n * img_out, img_out);
             const float floor_1 = HAS_RES ? floor_b : fmaxf(floor_b, floor_a);
             unsigned eo[2][4];
 #pragma unroll
@@ -366,12 +348,10 @@ int launch2d(const estd_conv2d_desc& d, hipStream_t stream)
     const int total = groups * d.N * tiles_h * tiles_w;
     const size_t lds = (size_t)2 * TROWS * (TW + 2 * DIL) * 128;      // two slots: 72 KB / 80 KB -> two workgroups per CU
     static const int grid_mult = [] { const char* e = getenv("ESTD_C2_GRID_MULT"); const int v = e ? atoi(e) : 1; return v >= 1 ? v : 1; }();
-    const int slots = estd_persistent_wgs(2) * grid_mult;   // > 1: more workgroups than fit at once, the hardware dispatcher balances
-    int grid = total < slots ? total : slots;
-    if (grid >= 8) grid &= ~7;
+    const int grid = estd_persistent_grid(total, 2 * grid_mult);   // > 1: more workgroups than fit at once, the hardware dispatcher balances
     estd_allow_dynamic_lds<conv2d_wino_kernel<NT, DIL>>((int)lds);
     hipLaunchKernelGGL((conv2d_wino_kernel<NT, DIL>), dim3(grid), dim3(256), lds, stream, d, tiles_w, tiles_h, total);
-    return hipGetLastError() == hipSuccess ? ESTD_OK : ESTD_ERR_LAUNCH;
+    return ESTD_LAUNCH_CHECK();
 }
 
 }  // namespace

@@ -37,17 +37,13 @@
 
 #include "estd_hip.h"
 #include "estd_common.h"
+#include "estd_device.h"
 
 #ifndef ESTD_C2W2ABL
 #define ESTD_C2W2ABL 0   // timing ablations only (wrong results when != 0): 1 no output stores, 2 no transform writes, 8 no weight stream, 128 no column transform
 #endif
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((__vector_size__(16)));
-constexpr unsigned OOB_OFFSET = 0xFFFFFF00u;
 
 constexpr int TH = 8, TW = 16;
 constexpr int TROWS = 16;                            // 4 transforms x 4 row pairs
@@ -84,16 +80,6 @@ constexpr int NSTEP = 8;                             // steps per 32-channel chu
 #define ESTD_C2W2_SPLIT 1   // work decomposition: 1 operand-reuse items (4 x 16 x 64) for Cout % 64 == 0, 2 for every Cout, 0 the round-6 items
 #endif
 constexpr int WD = ESTD_C2W2_WD, WR = 4;             // weight stream: WD steps ahead, ring slot = step % WR (8 % WR == 0, WD < WR)
-
-__device__ __forceinline__ float4 as_float4(u32x4 v) { float4 f; __builtin_memcpy(&f, &v, 16); return f; }
-__device__ __forceinline__ u32x4 as_u32x4(float4 f) { u32x4 v; __builtin_memcpy(&v, &f, 16); return v; }
-__device__ __forceinline__ float4 f4_sub(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
-__device__ __forceinline__ float4 f4_add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float* base, size_t elems)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)(elems * 4), 0x00020000);
-}
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // DIL = 2 (PSM layer4, networks/psm_submodule.py:58): pixels of equal parity form the F(2,3) sequences on both axes -- a block is the
 // outputs (a, a+2) x (b, b+2) with a in {0,1,4,5}, b in {0,1,4,5,8,9,12,13} of the tile, fed by brick rows a, a+2, a+4, a+6 and columns b,
@@ -171,7 +157,7 @@ __device__ __forceinline__ void wino2_rpp_nt(const estd_conv2d_desc& p, int tile
     decode(u, grp, n, th0, tw0);
     unsigned voff[IN_H];
     brick_offsets(th0, tw0, voff, true);
-    __amdgpu_buffer_rsrc_t rs_in = make_rsrc(p.in + (size_t)n * img_in, img_in);
+    __amdgpu_buffer_rsrc_t rs_in = make_rsrc_f32(p.in + (size_t)n * img_in, img_in);
     float4 pf[IN_H];
 #pragma unroll
     for (int zy = 0; zy < IN_H; ++zy) pf[zy] = as_float4(__builtin_amdgcn_raw_buffer_load_b128(rs_in, voff[zy], 0, 0));
@@ -180,7 +166,7 @@ __device__ __forceinline__ void wino2_rpp_nt(const estd_conv2d_desc& p, int tile
     const size_t wgrp_elems = (size_t)nchunks * NSTEP * 4 * 2 * 256;          // packed floats per group of 32 output channels
     float4 bq[WR][4];
     {
-        const __amdgpu_buffer_rsrc_t rs_w0 = make_rsrc(p.w_wino + (size_t)grp * wgrp_elems, wgrp_elems);
+        const __amdgpu_buffer_rsrc_t rs_w0 = make_rsrc_f32(p.w_wino + (size_t)grp * wgrp_elems, wgrp_elems);
 #pragma unroll
         for (int s = 0; s < WD; ++s)
 #pragma unroll
@@ -204,7 +190,7 @@ __device__ __forceinline__ void wino2_rpp_nt(const estd_conv2d_desc& p, int tile
         }
     }
     while (true) {
-        const __amdgpu_buffer_rsrc_t rs_w = make_rsrc(p.w_wino + (size_t)grp * wgrp_elems, wgrp_elems);
+        const __amdgpu_buffer_rsrc_t rs_w = make_rsrc_f32(p.w_wino + (size_t)grp * wgrp_elems, wgrp_elems);
         // folded BatchNorm of this lane's four channels, requested an item ahead of the epilogue that uses it
         const int cbase = grp * 32 + nt * 16 + 4 * g;
         const float4 sc4 = *reinterpret_cast<const float4*>(p.scale + cbase), sh4 = *reinterpret_cast<const float4*>(p.shift + cbase);
@@ -213,7 +199,7 @@ __device__ __forceinline__ void wino2_rpp_nt(const estd_conv2d_desc& p, int tile
         const bool has_next_item = (u + 1 < u_end);
         int ngrp = grp, nn_ = n, nth0 = th0, ntw0 = tw0;
         if (has_next_item) decode(u + 1, ngrp, nn_, nth0, ntw0);
-        const __amdgpu_buffer_rsrc_t rs_wni = make_rsrc(p.w_wino + (size_t)ngrp * wgrp_elems, wgrp_elems);
+        const __amdgpu_buffer_rsrc_t rs_wni = make_rsrc_f32(p.w_wino + (size_t)ngrp * wgrp_elems, wgrp_elems);
 
         // row transform of row pairs w0 .. w1 - 1 of the brick in pf, written to ``slot`` (row = 4 sh + row pair)
         auto write_rows = [&](char* slot, int w0, int w1) {
@@ -252,7 +238,7 @@ __device__ __forceinline__ void wino2_rpp_nt(const estd_conv2d_desc& p, int tile
             int pf_soff = (c + 1) * 128;
             if (last_chunk) {
                 brick_offsets(nth0, ntw0, voff, has_next_item);
-                if (nn_ != n) rs_in = make_rsrc(p.in + (size_t)nn_ * img_in, img_in);
+                if (nn_ != n) rs_in = make_rsrc_f32(p.in + (size_t)nn_ * img_in, img_in);
                 pf_soff = 0;
             }
             const int wbase_q = c * NSTEP * 4;                              // tap quads (2 KB each) in front of this chunk
@@ -401,8 +387,8 @@ __device__ __forceinline__ void wino2_rpp_nt(const estd_conv2d_desc& p, int tile
         // ---- output transform A^T m A, then the epilogue: lane (g, i) = channels cbase .. cbase + 3 of the four pixels of block i ----
         auto epilogue = [&](auto has_res_c) {
             constexpr bool HAS_RES = decltype(has_res_c)::value;
-            const __amdgpu_buffer_rsrc_t rs_out = make_rsrc(p.out + (size_t)n * img_out, img_out);
-            const __amdgpu_buffer_rsrc_t rs_res = make_rsrc((HAS_RES ? p.residual : p.out) + (size_t)n * img_out, img_out);
+            const __amdgpu_buffer_rsrc_t rs_out = make_rsrc_f32(p.out + (size_t)n * img_out, img_out);
+            const __amdgpu_buffer_rsrc_t rs_res = make_rsrc_f32((HAS_RES ? p.residual : p.out) + (size_t)n * img_out, img_out);
             const float floor_1 = HAS_RES ? floor_b : fmaxf(floor_b, floor_a);
             unsigned eo[2][2];
 #pragma unroll
@@ -535,14 +521,14 @@ __device__ __forceinline__ void wino2_split(const estd_conv2d_desc& p, int tiles
     decode(u, grp, n, th0, tw0);
     unsigned voff[IN_H];
     brick_offsets(th0, tw0, voff, true);
-    __amdgpu_buffer_rsrc_t rs_in = make_rsrc(p.in + (size_t)n * img_in, img_in);
+    __amdgpu_buffer_rsrc_t rs_in = make_rsrc_f32(p.in + (size_t)n * img_in, img_in);
     float4 pf[IN_H];
 #pragma unroll
     for (int zy = 0; zy < IN_H; ++zy) pf[zy] = as_float4(__builtin_amdgcn_raw_buffer_load_b128(rs_in, voff[zy], 0, 0));
 
     // weights: the packing's groups of 32 output channels; this wave's = the item's group (narrow) or its half sel of the 64 (WIDE)
     const size_t wgrp_elems = (size_t)nchunks * NSTEP * 4 * 2 * 256;
-    auto wgrp_rsrc = [&](int grp_) { return make_rsrc(p.w_wino + (size_t)(WIDE ? 2 * grp_ + sel : grp_) * wgrp_elems, wgrp_elems); };
+    auto wgrp_rsrc = [&](int grp_) { return make_rsrc_f32(p.w_wino + (size_t)(WIDE ? 2 * grp_ + sel : grp_) * wgrp_elems, wgrp_elems); };
     float4 bw[2][4][2];                                          // [step & 1][sw][output tile]
     {
         const __amdgpu_buffer_rsrc_t rs_w0 = wgrp_rsrc(grp);
@@ -593,7 +579,7 @@ __device__ __forceinline__ void wino2_split(const estd_conv2d_desc& p, int tiles
             int pf_soff = (c + 1) * 128;
             if (last_chunk) {
                 brick_offsets(nth0, ntw0, voff, has_next_item);
-                if (nn_ != n) rs_in = make_rsrc(p.in + (size_t)nn_ * img_in, img_in);
+                if (nn_ != n) rs_in = make_rsrc_f32(p.in + (size_t)nn_ * img_in, img_in);
                 pf_soff = 0;
             }
             const int wrec = c * NSTEP * 4 + srec;                              // (step, sw) records of this chunk's step 4 shp
@@ -702,8 +688,8 @@ __device__ __forceinline__ void wino2_split(const estd_conv2d_desc& p, int tiles
 
         auto epilogue = [&](auto has_res_c) {
             constexpr bool HAS_RES = decltype(has_res_c)::value;
-            const __amdgpu_buffer_rsrc_t rs_out = make_rsrc(p.out + (size_t)n * img_out, img_out);
-            const __amdgpu_buffer_rsrc_t rs_res = make_rsrc((HAS_RES ? p.residual : p.out) + (size_t)n * img_out, img_out);
+            const __amdgpu_buffer_rsrc_t rs_out = make_rsrc_f32(p.out + (size_t)n * img_out, img_out);
+            const __amdgpu_buffer_rsrc_t rs_res = make_rsrc_f32((HAS_RES ? p.residual : p.out) + (size_t)n * img_out, img_out);
             const float floor_1 = HAS_RES ? floor_b : fmaxf(floor_b, floor_a);
             const int y = th0 + row_a + DIL * shp;
             unsigned eo[2][2];
@@ -775,9 +761,7 @@ extern "C" int estd_conv2d_k3_wino2(const estd_conv2d_desc* dp, estd_stream_t s)
     const int groups = d.cout / (wide ? 64 : 32);
     const long long total = (long long)groups * d.N * tiles_h * tiles_w;
     if (total > 0x7fffffffLL) return ESTD_ERR_ARG;
-    const int slots = estd_persistent_wgs(2);
-    int grid = total < slots ? (int)total : slots;
-    if (grid >= 8) grid &= ~7;
+    const int grid = estd_persistent_grid(total, 2);
     // two slots of transformed rows (+ the 16 KB wave-pair exchange for the 64-channel items); two workgroups per CU
     const size_t rows = wide ? TROWS / 2 : TROWS, xchg = wide ? 16384 : 0;
     if (d.dilation == 1) {

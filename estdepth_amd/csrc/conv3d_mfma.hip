@@ -31,6 +31,7 @@
 
 #include "estd_hip.h"
 #include "estd_common.h"
+#include "estd_device.h"
 
 #ifdef ESTD_TIMELINE
 #define ESTD_STATS_ON 0
@@ -46,66 +47,11 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int TH = 8;    // tile rows
 constexpr int TW = 16;   // tile columns (= one MFMA M tile)
 constexpr int IN_D = 3, IN_H = TH + 2, IN_W = TW + 2;
 constexpr int NVOX_IN = IN_D * IN_H * IN_W;   // 540
 constexpr int MT = 2;    // M tiles (rows) per wave: 4 waves x 2 = 8 rows
-
-// sum over the 16 lanes of a DPP row (every lane gets the total): two quad permutations + two row rotations, all folded into v_add_f32
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float v)
-{
-    return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float row16_sum(float v)
-{
-    v = dpp_add<0xB1>(v);      // quad_perm [1,0,3,2]
-    v = dpp_add<0x4E>(v);      // quad_perm [2,3,0,1]
-    v = dpp_add<0x124>(v);     // row_ror:4
-    v = dpp_add<0x128>(v);     // row_ror:8
-    return v;
-}
-
-__device__ __forceinline__ float act_apply(float v, int act) {
-    if (act == ESTD_ACT_RELU) return v > 0.0f ? v : 0.0f;
-    if (act == ESTD_ACT_TANH) return tanhf(v);
-    return v;
-}
-
-// byte offset of 16-byte chunk c of LDS voxel record v
-template <int CM>
-__device__ __forceinline__ int lds_chunk_off(int v, int c) {
-    if (CM == 32) return v * 128 + ((c ^ ((v >> 1) & 7)) << 4);
-    else          return v * 64 + ((c ^ ((v >> 2) & 3)) << 4);
-}
-
-typedef unsigned int u32x4 __attribute__((__vector_size__(16)));   // the type raw_buffer_load_b128 returns (GCC vector)
-typedef unsigned int u32x2 __attribute__((__vector_size__(8)));
-constexpr unsigned OOB_OFFSET = 0xFFFFFF00u;    // beyond num_records of any descriptor: loads return 0, stores are dropped
-
-__device__ __forceinline__ float4 as_float4(u32x4 v)
-{
-    // NB: __builtin_bit_cast(float, v[i]) on a vector element is miscompiled by this clang (every lane reads
-    // element 0); a whole-object copy is the safe form.
-    float4 f;
-    __builtin_memcpy(&f, &v, 16);
-    return f;
-}
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float* base, size_t elems)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)(elems * 4), 0x00020000);
-}
-
-// Workgroup barrier that only orders LDS traffic.  __syncthreads() would also drain vmcnt, i.e. wait for the
-// previous tile's output stores (and the in-flight prefetch) to complete on every tile.
-__device__ __forceinline__ void lds_barrier()
-{
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
 
 constexpr int SL_VOX = IN_H * IN_W;     // 180 voxels per input slice (one depth plane of the brick, with halo)
 
@@ -173,7 +119,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_kernel(const estd_conv3d_des
                            act_u != ESTD_ACT_TANH && !(ESTD_ABL & 128);
     const float head_floor = act_u == ESTD_ACT_RELU ? 0.f : ESTD_NO_FLOOR;
 
-    const __amdgpu_buffer_rsrc_t rs_w = make_rsrc(p.w_main, (size_t)28 * QN * 256);
+    const __amdgpu_buffer_rsrc_t rs_w = make_rsrc_f32(p.w_main, (size_t)28 * QN * 256);
     // 16 -> 16 (stereo heads): one weight quad per lane and tap, 27 quads = 108 registers -- the whole filter stays in registers, no
     // weight stream at all (a tap is only 8 MFMAs = 256 matrix cycles, less than an L2 round trip next to another stream's kernels)
     constexpr bool WREG = (CM == 16 && NT == 1 && !EXTRA && !XOUT && !(ESTD_ABL & 64));
@@ -184,7 +130,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_kernel(const estd_conv3d_des
     }
     // 33rd OUTPUT channel (dres2): a GEMV, 1/16 efficient on MFMA -> computed on the VALU in the MFMA shadow from the
     // A fragments already in registers: w_xout = [28 taps][2 quads][64 lanes][4] + [2][64][4] extra-input taps
-    const __amdgpu_buffer_rsrc_t rs_wxo = make_rsrc(XOUT ? p.w_xout : p.w_main, (size_t)(28 * 2 + 2) * 256);
+    const __amdgpu_buffer_rsrc_t rs_wxo = make_rsrc_f32(XOUT ? p.w_xout : p.w_main, (size_t)(28 * 2 + 2) * 256);
     const size_t vol = (size_t)D * H * W;
     const int HW = H * W;
     const int row0 = wave * MT;   // first tile row of this wave
@@ -199,9 +145,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_kernel(const estd_conv3d_des
         const int tw0 = twi * TW, th0 = thi * TH;
         const int seg_end = min(u_end, (col + 1) * D);
 
-        const __amdgpu_buffer_rsrc_t rs_in = make_rsrc(p.in_main + (size_t)n * vol * p.in_stride, vol * p.in_stride);
+        const __amdgpu_buffer_rsrc_t rs_in = make_rsrc_f32(p.in_main + (size_t)n * vol * p.in_stride, vol * p.in_stride);
         __amdgpu_buffer_rsrc_t rs_ex = rs_in;
-        if (EXTRA) rs_ex = make_rsrc(p.in_extra + (size_t)n * vol, vol);
+        if (EXTRA) rs_ex = make_rsrc_f32(p.in_extra + (size_t)n * vol, vol);
 
         // per-thread slice-element constants of this segment (validity in y/x does not depend on d)
         unsigned voff[SIT];
@@ -230,9 +176,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_kernel(const estd_conv3d_des
 
         // output descriptors and per-lane output offsets of this segment (bytes inside one depth plane)
         __amdgpu_buffer_rsrc_t rs_out = rs_in, rs_res = rs_in, rs_res2 = rs_in;
-        if (p.out_main) rs_out = make_rsrc(p.out_main + (size_t)n * vol * p.out_stride, vol * p.out_stride);
-        if (p.residual) rs_res = make_rsrc(p.residual + (size_t)n * vol * p.out_stride, vol * p.out_stride);
-        if (p.residual2) rs_res2 = make_rsrc(p.residual2 + (size_t)n * vol * p.out_stride, vol * p.out_stride);
+        if (p.out_main) rs_out = make_rsrc_f32(p.out_main + (size_t)n * vol * p.out_stride, vol * p.out_stride);
+        if (p.residual) rs_res = make_rsrc_f32(p.residual + (size_t)n * vol * p.out_stride, vol * p.out_stride);
+        if (p.residual2) rs_res2 = make_rsrc_f32(p.residual2 + (size_t)n * vol * p.out_stride, vol * p.out_stride);
         const int out_plane_bytes = HW * p.out_stride * 4;
         unsigned eoff[MT][4];
 #pragma unroll
@@ -248,7 +194,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_kernel(const estd_conv3d_des
         __amdgpu_buffer_rsrc_t rs_head = rs_in;
         unsigned hoff = OOB_OFFSET;
         if (NT == 1 && head_only) {
-            rs_head = make_rsrc(p.out_head + (size_t)n * vol, vol);
+            rs_head = make_rsrc_f32(p.out_head + (size_t)n * vol, vol);
             const int y = ey0 + ((i >> 2) & 1), x = ex0 + 2 * (i & 3);
             hoff = (i < 4 * MT && y < H && x < W) ? (unsigned)(y * W + x) * 4u : OOB_OFFSET;
         }
@@ -507,7 +453,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_kernel(const estd_conv3d_des
 
             // ---- extra scalar input channel: its 27 taps form one more K chunk (28 = 7 x 4) ----
             if (EXTRA) {
-                const __amdgpu_buffer_rsrc_t rs_wx = make_rsrc(p.w_extra, (size_t)XQ * 256);
+                const __amdgpu_buffer_rsrc_t rs_wx = make_rsrc_f32(p.w_extra, (size_t)XQ * 256);
                 float4 wxx[2];
                 if (XOUT) {
 #pragma unroll
@@ -563,20 +509,16 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_kernel(const estd_conv3d_des
     }
 }
 
-constexpr int PERSISTENT_WGS = 512;     // 256 CUs x 2 resident workgroups (LDS-limited)
-
 template <int CM, int NT, bool EXTRA, bool XOUT>
 int launch(const estd_conv3d_desc& d, hipStream_t stream)
 {
     const int tiles_w = (d.W + TW - 1) / TW, tiles_h = (d.H + TH - 1) / TH;
     const int total = d.N * d.D * tiles_h * tiles_w;
-    const int slots = estd_persistent_wgs(PERSISTENT_WGS / 256);
-    int grid = total < slots ? total : slots;
-    if (grid >= 8) grid &= ~7;
+    const int grid = estd_persistent_grid(total, 2);     // 2 resident workgroups per CU (LDS-limited)
     const size_t lds = (size_t)3 * SL_VOX * CM * 4 + (EXTRA ? 3 * SL_VOX * 4 : 0) + 128;
     estd_allow_dynamic_lds<conv3d_k3_kernel<CM, NT, EXTRA, XOUT>>((int)lds);
     hipLaunchKernelGGL((conv3d_k3_kernel<CM, NT, EXTRA, XOUT>), dim3(grid), dim3(256), lds, stream, d, tiles_w, tiles_h, total);
-    return hipGetLastError() == hipSuccess ? ESTD_OK : ESTD_ERR_LAUNCH;
+    return ESTD_LAUNCH_CHECK();
 }
 
 }  // namespace
@@ -603,11 +545,7 @@ extern "C" int estd_conv3d_k3(const estd_conv3d_desc* dp, estd_stream_t s)
     if (extra && !d.w_extra) return ESTD_ERR_ARG;
     if (d.n_tiles == 3 && (!d.out_extra || !d.w_xout)) return ESTD_ERR_ARG;
     if ((long long)d.N * d.D * ((d.H + TH - 1) / TH) * ((d.W + TW - 1) / TW) > 0x7fffffffLL) return ESTD_ERR_ARG;
-    {   // buffer descriptors address one volume of the batch with 32-bit byte offsets
-        const long long vox = (long long)d.D * d.H * d.W;
-        const int widest = d.in_stride > d.out_stride ? d.in_stride : d.out_stride;
-        if (vox * widest * 4 >= 0x7fffff00LL) return ESTD_ERR_UNSUPPORTED;
-    }
+    if (!estd_conv3d_volume_fits_rsrc(d)) return ESTD_ERR_UNSUPPORTED;
 
     if (d.cin_main == 32 && d.n_tiles == 2 && !extra) return launch<32, 2, false, false>(d, stream);
     if (d.cin_main == 32 && d.n_tiles == 2 && extra)  return launch<32, 2, true, false>(d, stream);

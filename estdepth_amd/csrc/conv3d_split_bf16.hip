@@ -39,6 +39,7 @@
 
 #include "estd_hip.h"
 #include "estd_common.h"
+#include "estd_device.h"
 
 #ifdef ESTD_TIMELINE
 #define ESTD_SPLIT_STATS_ON 0   // debug build: stats_partials receives per-tile time stamps instead of GroupNorm sums
@@ -53,12 +54,6 @@
 #endif
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((__vector_size__(16)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((__vector_size__(16)));
-typedef unsigned int u32x2 __attribute__((__vector_size__(8)));
 
 constexpr int TH = 8, TW = 32;
 constexpr int IN_H = TH + 2, IN_W = TW + 2;
@@ -80,67 +75,6 @@ constexpr int LDS_RED = LDS_XRING + 4096;
 constexpr int LDS_TOTAL = LDS_RED + 8 * 4 * 8;         // 158720 of 163840
 constexpr int FILL_E = SL_VOX * 4;             // (voxel, chunk) items per slice: 1360
 constexpr int FIT = 3;                         // items per thread (512 threads)
-constexpr unsigned OOB_OFFSET = 0xFFFFFF00u;
-
-__device__ __forceinline__ float4 as_float4(u32x4 v)
-{
-    float4 f;
-    __builtin_memcpy(&f, &v, 16);
-    return f;
-}
-
-__device__ __forceinline__ float2 as_float2(u32x2 v)
-{
-    float2 f;
-    __builtin_memcpy(&f, &v, 8);
-    return f;
-}
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, size_t bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-
-__device__ __forceinline__ void lds_barrier()
-{
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-// x0, x1 -> three packed bf16 pairs with x = h + m + l (exact unless x is within 2^-24 of the bf16 range limits)
-__device__ __forceinline__ void split2(float x0, float x1, unsigned& h, unsigned& m, unsigned& l)
-{
-    const bf16x2 hb = {(__bf16)x0, (__bf16)x1};
-    h = __builtin_bit_cast(unsigned, hb);
-    float r0 = x0 - __builtin_bit_cast(float, h << 16);
-    float r1 = x1 - __builtin_bit_cast(float, h & 0xffff0000u);
-    const bf16x2 mb = {(__bf16)r0, (__bf16)r1};
-    m = __builtin_bit_cast(unsigned, mb);
-    r0 -= __builtin_bit_cast(float, m << 16);
-    r1 -= __builtin_bit_cast(float, m & 0xffff0000u);
-    const bf16x2 lb = {(__bf16)r0, (__bf16)r1};
-    l = __builtin_bit_cast(unsigned, lb);
-}
-
-// 8 channels (two float4) of one voxel -> LDS, one 16-byte write per piece (o1 - o0 = o2 - o1 = PIECE_BYTES for real items)
-__device__ __forceinline__ void fill_item(char* smem, int o0, int o1, int o2, float4 a, float4 b)
-{
-    u32x4 h, m, l;
-    unsigned th, tm, tl;
-    split2(a.x, a.y, th, tm, tl); h[0] = th; m[0] = tm; l[0] = tl;
-    split2(a.z, a.w, th, tm, tl); h[1] = th; m[1] = tm; l[1] = tl;
-    split2(b.x, b.y, th, tm, tl); h[2] = th; m[2] = tm; l[2] = tl;
-    split2(b.z, b.w, th, tm, tl); h[3] = th; m[3] = tm; l[3] = tl;
-    *reinterpret_cast<u32x4*>(smem + o0) = h;
-    *reinterpret_cast<u32x4*>(smem + o1) = m;
-    *reinterpret_cast<u32x4*>(smem + o2) = l;
-}
-
-// compile-time tap index: a "#pragma unroll" loop gets peeled (some taps are special) and is then no longer fully unrolled
-template <typename F, int... I>
-__device__ __forceinline__ void for_each_tap(F&& f, std::integer_sequence<int, I...>)
-{
-    (f(std::integral_constant<int, I>{}), ...);
-}
 
 // Issue order of one tap: one MFMA, then a few of the other instructions of the tap (IGroupLP pipeline).
 //   0x008 MFMA   0x100 DS read   0x200 DS write   0x020 VMEM read   0x040 VMEM write   0x002 VALU   0x004 SALU
@@ -196,7 +130,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_k3_split_kernel(const estd_conv
     float sc2 = 0.f, sh2 = 0.f, relu_floor2 = 0.f;
     if (NT == 3) { sc2 = p.scale[32]; sh2 = p.shift[32]; relu_floor2 = p.act_b == ESTD_ACT_RELU ? 0.0f : -__builtin_huge_valf(); }
 
-    const __amdgpu_buffer_rsrc_t rs_w = make_rsrc(p.w_split, (size_t)NTAPS * WTAP_BYTES);
+    const __amdgpu_buffer_rsrc_t rs_w = make_rsrc_bytes(p.w_split, (size_t)NTAPS * WTAP_BYTES);
     const size_t vol = (size_t)D * H * W;
     const int HW = H * W;
     const int tiles_w16 = (W + 15) / 16;                 // GroupNorm partials keep the 8x16-tile numbering of estd_conv3d_k3_grid
@@ -232,13 +166,13 @@ __global__ __launch_bounds__(512, 1) void conv3d_k3_split_kernel(const estd_conv
 
         // absent optional operands get an EMPTY descriptor: every load returns 0, so the epilogue needs no branches
         const size_t out_bytes = vol * p.out_stride * 4;
-        const __amdgpu_buffer_rsrc_t rs_in = make_rsrc(p.in_main + (size_t)n * vol * p.in_stride, vol * p.in_stride * 4);
-        const __amdgpu_buffer_rsrc_t rs_ex = make_rsrc(EXTRA ? p.in_extra + (size_t)n * vol : p.in_main, EXTRA ? vol * 4 : 0);
-        const __amdgpu_buffer_rsrc_t rs_out = make_rsrc(p.out_main + (size_t)n * vol * p.out_stride, out_bytes);
-        const __amdgpu_buffer_rsrc_t rs_xout = make_rsrc(NT == 3 ? p.out_extra + (size_t)n * vol : p.out_main, NT == 3 ? vol * 4 : 0);
-        const __amdgpu_buffer_rsrc_t rs_res = make_rsrc(p.residual ? p.residual + (size_t)n * vol * p.out_stride : p.out_main, p.residual ? out_bytes : 0);
-        const __amdgpu_buffer_rsrc_t rs_res2 = make_rsrc(p.residual2 ? p.residual2 + (size_t)n * vol * p.out_stride : p.out_main, p.residual2 ? out_bytes : 0);
-        const __amdgpu_buffer_rsrc_t rs_acc = make_rsrc(p.out_main + (size_t)n * vol * p.out_stride, p.accumulate ? out_bytes : 0);
+        const __amdgpu_buffer_rsrc_t rs_in = make_rsrc_bytes(p.in_main + (size_t)n * vol * p.in_stride, vol * p.in_stride * 4);
+        const __amdgpu_buffer_rsrc_t rs_ex = make_rsrc_bytes(EXTRA ? p.in_extra + (size_t)n * vol : p.in_main, EXTRA ? vol * 4 : 0);
+        const __amdgpu_buffer_rsrc_t rs_out = make_rsrc_bytes(p.out_main + (size_t)n * vol * p.out_stride, out_bytes);
+        const __amdgpu_buffer_rsrc_t rs_xout = make_rsrc_bytes(NT == 3 ? p.out_extra + (size_t)n * vol : p.out_main, NT == 3 ? vol * 4 : 0);
+        const __amdgpu_buffer_rsrc_t rs_res = make_rsrc_bytes(p.residual ? p.residual + (size_t)n * vol * p.out_stride : p.out_main, p.residual ? out_bytes : 0);
+        const __amdgpu_buffer_rsrc_t rs_res2 = make_rsrc_bytes(p.residual2 ? p.residual2 + (size_t)n * vol * p.out_stride : p.out_main, p.residual2 ? out_bytes : 0);
+        const __amdgpu_buffer_rsrc_t rs_acc = make_rsrc_bytes(p.out_main + (size_t)n * vol * p.out_stride, p.accumulate ? out_bytes : 0);
         const int in_slice_bytes = HW * p.in_stride * 4;
         const int out_plane_bytes = HW * p.out_stride * 4;
 
@@ -591,12 +525,10 @@ __global__ __launch_bounds__(512, 1) void conv3d_k3_split_kernel(const estd_conv
 template <int NT, bool EXTRA, bool TANH, bool STATS, bool RES>
 int launch_inst(const estd_conv3d_desc& d, hipStream_t stream, int tiles_w, int tiles_h, int total)
 {
-    const int slots = estd_persistent_wgs(1);      // one workgroup per CU (LDS-limited)
-    int grid = total < slots ? total : slots;
-    if (grid >= 8) grid &= ~7;
+    const int grid = estd_persistent_grid(total, 1);      // one workgroup per CU (LDS-limited)
     estd_allow_dynamic_lds<conv3d_k3_split_kernel<NT, EXTRA, TANH, STATS, RES>>((int)LDS_TOTAL);
     hipLaunchKernelGGL((conv3d_k3_split_kernel<NT, EXTRA, TANH, STATS, RES>), dim3(grid), dim3(512), LDS_TOTAL, stream, d, tiles_w, tiles_h, total);
-    return hipGetLastError() == hipSuccess ? ESTD_OK : ESTD_ERR_LAUNCH;
+    return ESTD_LAUNCH_CHECK();
 }
 
 template <int NT, bool EXTRA, bool TANH, bool STATS>
@@ -625,11 +557,7 @@ extern "C" int estd_conv3d_k3_split(const estd_conv3d_desc* dp, estd_stream_t s)
     const int tiles_w = (d.W + TW - 1) / TW, tiles_h = (d.H + TH - 1) / TH;
     const long long total = (long long)d.N * d.D * tiles_h * tiles_w;
     if (total > 0x7fffffffLL) return ESTD_ERR_ARG;
-    {
-        const long long vox = (long long)d.D * d.H * d.W;
-        const int widest = d.in_stride > d.out_stride ? d.in_stride : d.out_stride;
-        if (vox * widest * 4 >= 0x7fffff00LL) return ESTD_ERR_UNSUPPORTED;
-    }
+    if (!estd_conv3d_volume_fits_rsrc(d)) return ESTD_ERR_UNSUPPORTED;
     const bool tanh_used = (d.act_split > 0 && d.act_a == ESTD_ACT_TANH) || d.act_b == ESTD_ACT_TANH;
     const bool stats = d.stats_partials != nullptr;
     const bool extra = d.in_extra != nullptr;

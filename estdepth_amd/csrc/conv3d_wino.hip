@@ -39,6 +39,7 @@
 
 #include "estd_hip.h"
 #include "estd_common.h"
+#include "estd_device.h"
 
 #ifndef ESTD_WABL
 #define ESTD_WABL 0     // timing ablations only (results are wrong for 1..16): 1 no output stores, 2 no transform writes,
@@ -50,10 +51,6 @@
 #endif
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((__vector_size__(16)));
 
 constexpr int TH = 8, TW = 16;
 constexpr int IN_H = TH + 2, IN_W = TW + 2;
@@ -75,37 +72,6 @@ constexpr int WXO_BYTES = (36 * 2 + 3) * 64;        // the 33rd output channel's
 constexpr int WLDS_TAPS = ESTD_WLDS_TAPS;
 constexpr int WLDS_BYTES = WLDS_TAPS * 4096;         // [tap][2 halves][2 quads][64 lanes][4]
 constexpr int LDS_BYTES = 4 * SLICE_BYTES + XSL_BYTES + RED_BYTES + WXO_BYTES + WLDS_BYTES;
-constexpr unsigned OOB_OFFSET = 0xFFFFFF00u;        // beyond num_records of any descriptor: loads return 0, stores are dropped
-
-__device__ __forceinline__ float4 as_float4(u32x4 v)
-{
-    float4 f;
-    __builtin_memcpy(&f, &v, 16);
-    return f;
-}
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float* base, size_t elems)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)(elems * 4), 0x00020000);
-}
-
-// workgroup barrier that only orders LDS traffic (no vmcnt drain: prefetches and output stores stay in flight)
-__device__ __forceinline__ void lds_barrier()
-{
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-__device__ __forceinline__ int lds_chunk_off(int v, int c) { return v * 128 + ((c ^ ((v >> 1) & 7)) << 4); }
-
-__device__ __forceinline__ float act_apply(float v, int act)
-{
-    if (act == ESTD_ACT_RELU) return v > 0.0f ? v : 0.0f;
-    if (act == ESTD_ACT_TANH) return tanhf(v);
-    return v;
-}
-
-__device__ __forceinline__ float4 f4_sub(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
-__device__ __forceinline__ float4 f4_add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 
 // EXTRA: a scalar 33rd INPUT channel (the semantic plane scores of dres2, the 33rd channel of its output for key||value): its
 //        3x3 taps per transform form three more k-steps (lane group g multiplies tap 4s+g; taps 9..11 carry zero weights).
@@ -161,11 +127,11 @@ __global__ __launch_bounds__(NTHREADS, 1) void conv3d_wino_kernel(const estd_con
                            p.act_a != ESTD_ACT_TANH && p.act_b != ESTD_ACT_TANH && !(ESTD_WABL & 64);
     const float act_floor = act0 == ESTD_ACT_RELU ? 0.f : ESTD_NO_FLOOR;
     // packed weights: [37 taps (36 + 1 the prefetch may read)][2 halves][2 quads][64 lanes][4]
-    const __amdgpu_buffer_rsrc_t rs_w = make_rsrc(p.w_wino, (size_t)37 * 2 * 2 * 256);
+    const __amdgpu_buffer_rsrc_t rs_w = make_rsrc_f32(p.w_wino, (size_t)37 * 2 * 2 * 256);
     const int wlane = lane * 16 + nh * 2048;
     const int row0 = 2 * rp;
     // scalar-channel weights: [2 halves][3 quads][64 lanes][4], element 3 s + k of lane (g, j) = U_s[16 nh + j][extra][tap 4 k + g]
-    const __amdgpu_buffer_rsrc_t rs_wx = make_rsrc(EXTRA ? p.w_extra : p.w_wino, (size_t)2 * 3 * 256);
+    const __amdgpu_buffer_rsrc_t rs_wx = make_rsrc_f32(EXTRA ? p.w_extra : p.w_wino, (size_t)2 * 3 * 256);
     // this lane's taps of the scalar channel: k-step k covers tap 4k + g (clamped: taps 9..11 have zero weights)
     int xtap_off[3];
 #pragma unroll
@@ -183,9 +149,9 @@ __global__ __launch_bounds__(NTHREADS, 1) void conv3d_wino_kernel(const estd_con
         const int tw0 = twi * TW, th0 = thi * TH;
         const int seg_end = min(u_end, (col + 1) * dpairs);
 
-        const __amdgpu_buffer_rsrc_t rs_in = make_rsrc(p.in_main + (size_t)n * vol * p.in_stride, vol * p.in_stride);
+        const __amdgpu_buffer_rsrc_t rs_in = make_rsrc_f32(p.in_main + (size_t)n * vol * p.in_stride, vol * p.in_stride);
         __amdgpu_buffer_rsrc_t rs_ex = rs_in;
-        if (EXTRA) rs_ex = make_rsrc(p.in_extra + (size_t)n * vol, vol);
+        if (EXTRA) rs_ex = make_rsrc_f32(p.in_extra + (size_t)n * vol, vol);
         unsigned voffx = OOB_OFFSET;                 // this thread's voxel of a scalar slice (threads 0..179)
         if (EXTRA) {
             const int zy = tid / IN_W, zx = tid % IN_W;
@@ -196,9 +162,9 @@ __global__ __launch_bounds__(NTHREADS, 1) void conv3d_wino_kernel(const estd_con
             return (unsigned)pd < (unsigned)D ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_ex, voffx, pd * HW * 4, 0)) : 0.0f;
         };
         __amdgpu_buffer_rsrc_t rs_out = rs_in, rs_res = rs_in, rs_res2 = rs_in;
-        rs_out = make_rsrc(p.out_main + (size_t)n * vol * p.out_stride, vol * p.out_stride);
-        if (p.residual) rs_res = make_rsrc(p.residual + (size_t)n * vol * p.out_stride, vol * p.out_stride);
-        if (p.residual2) rs_res2 = make_rsrc(p.residual2 + (size_t)n * vol * p.out_stride, vol * p.out_stride);
+        rs_out = make_rsrc_f32(p.out_main + (size_t)n * vol * p.out_stride, vol * p.out_stride);
+        if (p.residual) rs_res = make_rsrc_f32(p.residual + (size_t)n * vol * p.out_stride, vol * p.out_stride);
+        if (p.residual2) rs_res2 = make_rsrc_f32(p.residual2 + (size_t)n * vol * p.out_stride, vol * p.out_stride);
         const int in_slice_bytes = HW * p.in_stride * 4;
         const int out_plane_bytes = HW * p.out_stride * 4;
 
@@ -213,7 +179,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void conv3d_wino_kernel(const estd_con
             const int gy = th0 - 1 + zy, gx = tw0 - 1 + zx;
             const bool ok = e < SL_CHUNKS && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
             voff[it] = ok ? (unsigned)((gy * W + gx) * p.in_stride + c * 4) * 4u : OOB_OFFSET;
-            loff[it] = e < SL_CHUNKS ? lds_chunk_off(vs, c) : -1;
+            loff[it] = e < SL_CHUNKS ? lds_chunk_off<32>(vs, c) : -1;
         }
         auto load_plane = [&](int pd, float4 (&dst)[SIT]) {
             const bool pv = (unsigned)pd < (unsigned)D;        // wave-uniform; planes outside the volume are zero padding
@@ -406,7 +372,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void conv3d_wino_kernel(const estd_con
 #pragma unroll
                 for (int m = 0; m < 2; ++m) {
                     const int vs = (row0 + m + kh) * IN_W + kw + pi;
-                    const int off0 = s * SLICE_BYTES + lds_chunk_off(vs, g);
+                    const int off0 = s * SLICE_BYTES + lds_chunk_off<32>(vs, g);
                     a0[m] = *reinterpret_cast<const float4*>(smem + off0);
                     a1[m] = *reinterpret_cast<const float4*>(smem + (off0 ^ 64));
                 }
@@ -519,7 +485,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void conv3d_wino_kernel(const estd_con
                     const int s_ = it / 9, kh = (it / 3) % 3, kw = it % 3;
                     const char* wrow = lds_wxo + ((s_ * 9 + kh * 3) * 2) * 64 + gx_ * 16;
                     const int vs = (row0 + nh + kh) * IN_W + kw + ix;
-                    const int off0 = s_ * SLICE_BYTES + lds_chunk_off(vs, gx_);
+                    const int off0 = s_ * SLICE_BYTES + lds_chunk_off<32>(vs, gx_);
                     buf[0] = *reinterpret_cast<const float4*>(smem + off0);
                     buf[1] = *reinterpret_cast<const float4*>(smem + (off0 ^ 64));
                     buf[2] = *reinterpret_cast<const float4*>(wrow + (kw * 2 + 0) * 64);
@@ -573,8 +539,6 @@ __global__ __launch_bounds__(NTHREADS, 1) void conv3d_wino_kernel(const estd_con
     }
 }
 
-constexpr int PERSISTENT_WGS = 256;     // one 512-thread workgroup per CU (LDS-limited)
-
 }  // namespace
 
 extern "C" int estd_conv3d_k3_wino(const estd_conv3d_desc* dp, estd_stream_t s)
@@ -595,14 +559,8 @@ extern "C" int estd_conv3d_k3_wino(const estd_conv3d_desc* dp, estd_stream_t s)
     const int tiles_w = (d.W + TW - 1) / TW, tiles_h = (d.H + TH - 1) / TH, dpairs = (d.D + 1) / 2;
     const long long total = (long long)d.N * dpairs * tiles_h * tiles_w;
     if (total > 0x7fffffffLL) return ESTD_ERR_ARG;
-    {   // buffer descriptors address one volume of the batch with 32-bit byte offsets
-        const long long vox = (long long)d.D * d.H * d.W;
-        const int widest = d.in_stride > d.out_stride ? d.in_stride : d.out_stride;
-        if (vox * widest * 4 >= 0x7fffff00LL) return ESTD_ERR_UNSUPPORTED;
-    }
-    const int slots = estd_persistent_wgs(PERSISTENT_WGS / 256);
-    int grid = total < slots ? (int)total : slots;
-    if (grid >= 8) grid &= ~7;
+    if (!estd_conv3d_volume_fits_rsrc(d)) return ESTD_ERR_UNSUPPORTED;
+    const int grid = estd_persistent_grid(total, 1);     // one 512-thread workgroup per CU (LDS-limited)
 #define ESTD_WINO_LAUNCH(E, X)                                                                                                   \
     do {                                                                                                                         \
         estd_allow_dynamic_lds<conv3d_wino_kernel<E, X>>(LDS_BYTES);                                                             \

@@ -32,6 +32,7 @@
 
 #include "estd_hip.h"
 #include "estd_common.h"
+#include "estd_device.h"
 
 #ifndef ESTD_W2PRIO
 #define ESTD_W2PRIO 2   // 0: none; 1: per-step alternating s_setprio between the two waves of a SIMD (slower); 2: static priority 1 for waves 4..7 (default: -1.2 % at sustained clocks)
@@ -81,10 +82,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((__vector_size__(16)));
-
 constexpr int TH = 8, TW = 16;
 constexpr int IN_H = TH + 2, IN_W = TW + 2;
 constexpr int SL_VOX = IN_H * IN_W;                 // 180 voxels per input slice (with halo)
@@ -119,73 +116,10 @@ constexpr int XOUT_W_BYTES = (24 * 4 * 4 + 4 * 4) * 16;
 constexpr int XOUT_XCH_BYTES = 2 * 4 * 64 * 4;
 constexpr int XOUT_LDS_BYTES = 4 * SLICE_BYTES + RED_BYTES + SS_BYTES + VTAB_BYTES + XSL_BYTES + XOUT_WLDS_TAPS * 4096 + XOUT_W_BYTES + XOUT_XCH_BYTES;
 static_assert(XOUT_LDS_BYTES <= 160 * 1024, "LDS budget (XOUT)");
-constexpr unsigned OOB_OFFSET = 0xFFFFFF00u;        // beyond num_records of any descriptor: loads return 0, stores are dropped
-
-__device__ __forceinline__ float4 as_float4(u32x4 v)
-{
-    float4 f;
-    __builtin_memcpy(&f, &v, 16);
-    return f;
-}
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float* base, size_t elems)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)(elems * 4), 0x00020000);
-}
-
-// workgroup barrier that only orders LDS traffic (no vmcnt drain: prefetches and output stores stay in flight)
-// sum of a double over the 16 lanes of a DPP row, every lane gets the total: two quad permutations + two row rotations of the two
-// dwords (v_mov_b32 with a DPP modifier: no LDS round trip) and one v_add_f64 per level
-template <int CTRL>
-__device__ __forceinline__ double dpp_add_f64(double v)
-{
-    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)b, CTRL, 0xf, 0xf, false);
-    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(b >> 32), CTRL, 0xf, 0xf, false);
-    return v + __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-__device__ __forceinline__ double row16_sum_f64(double v)
-{
-    v = dpp_add_f64<0xB1>(v);      // quad_perm [1,0,3,2]
-    v = dpp_add_f64<0x4E>(v);      // quad_perm [2,3,0,1]
-    v = dpp_add_f64<0x124>(v);     // row_ror:4
-    v = dpp_add_f64<0x128>(v);     // row_ror:8
-    return v;
-}
-
-__device__ __forceinline__ void lds_barrier()
-{
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-__device__ __forceinline__ int lds_chunk_off(int v, int c) { return v * 128 + ((c ^ ((v >> 1) & 7)) << 4); }
-// ESTD_W2COLKEY (round 4): the swizzle key is taken from the COLUMN of the haloed slice only -- (col >> 1) & 7; IN_W is even, so the
-// bank half (voxel & 1) is the column's parity and the 8 even / 8 odd columns a fragment read touches still have 8 distinct keys --
-// which makes the byte offset of (row, col, chunk) = row * IN_W * 128 + f(col, chunk): the fragment reads of a tap loop then need one
-// address register per (column tap, channel chunk) and immediates for the halo row and the depth slice, instead of one register per
-// (row, column tap) plus an XOR per second-chunk read.
+// ESTD_W2COLKEY (round 4): the swizzle key is taken from the COLUMN of the haloed slice only (lds_colkey_off, csrc/estd_device.h)
 #ifndef ESTD_W2COLKEY
 #define ESTD_W2COLKEY 1
 #endif
-__device__ __forceinline__ int lds_colkey_off(int col, int c) { return col * 128 + ((c ^ ((col >> 1) & 7)) << 4); }
-
-// tanh x = 1 - 2 / (exp(2x) + 1) on the transcendental units (v_exp_f32, v_rcp_f32: 1 ulp each; five instructions instead of the device
-// library's ~30).  Absolute error <= 2e-7 over the whole range (cancellation near 0 costs relative, not absolute accuracy); +-inf -> +-1.
-__device__ __forceinline__ float tanh_fast(float x)
-{
-    const float t = __builtin_amdgcn_exp2f(x * 2.8853900817779268f);
-    return 1.0f - 2.0f * __builtin_amdgcn_rcpf(t + 1.0f);
-}
-
-__device__ __forceinline__ float act_apply(float v, int act)
-{
-    if (act == ESTD_ACT_RELU) return v > 0.0f ? v : 0.0f;
-    if (act == ESTD_ACT_TANH) return tanhf(v);
-    return v;
-}
-
-__device__ __forceinline__ float4 f4_sub(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
-__device__ __forceinline__ float4 f4_add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 
 // NW = 8: 512 threads, two waves per SIMD (256 registers each), wave = (row pair rp, channel half nh).
 // NW = 4: 256 threads, ONE wave per SIMD (512 registers: the accumulators of both channel halves), wave = row pair rp: every
@@ -284,7 +218,7 @@ __global__ __launch_bounds__(64 * NW, 1) void conv3d_wino2_kernel(const estd_con
         reinterpret_cast<float4*>(lds_w)[e] = reinterpret_cast<const float4*>(p.w_wino2)[WT0 * (TAP_BYTES / 16) + e];
 
     // packed weights: [48 taps][2 halves][2 quads][64 lanes][4]
-    const __amdgpu_buffer_rsrc_t rs_w = make_rsrc(p.w_wino2, (size_t)NTAPS * (O16 ? 1 : 2) * 2 * 256);
+    const __amdgpu_buffer_rsrc_t rs_w = make_rsrc_f32(p.w_wino2, (size_t)NTAPS * (O16 ? 1 : 2) * 2 * 256);
     const int wlane = lane * 16 + nh0 * 2048;
     const int row0 = 2 * rp;
     int rbase[3][2];                     // column-keyed swizzle: byte offset of (halo row row0, column kw + pi, chunk g + 4c) of slice 0
@@ -323,15 +257,15 @@ __global__ __launch_bounds__(64 * NW, 1) void conv3d_wino2_kernel(const estd_con
         const int tw0 = twi * TW, th0 = thi * TH;
         const int seg_end = min(u_end, (col + 1) * dpairs);
 
-        const __amdgpu_buffer_rsrc_t rs_in = make_rsrc(p.in_main + (size_t)n * vol * p.in_stride, vol * p.in_stride);
+        const __amdgpu_buffer_rsrc_t rs_in = make_rsrc_f32(p.in_main + (size_t)n * vol * p.in_stride, vol * p.in_stride);
         __amdgpu_buffer_rsrc_t rs_out = rs_in, rs_res = rs_in, rs_res2 = rs_in;
-        rs_out = make_rsrc(p.out_main + (size_t)n * vol * p.out_stride, vol * p.out_stride);
-        if (p.residual) rs_res = make_rsrc(p.residual + (size_t)n * vol * p.out_stride, vol * p.out_stride);
-        if (p.residual2) rs_res2 = make_rsrc(p.residual2 + (size_t)n * vol * p.out_stride, vol * p.out_stride);
+        rs_out = make_rsrc_f32(p.out_main + (size_t)n * vol * p.out_stride, vol * p.out_stride);
+        if (p.residual) rs_res = make_rsrc_f32(p.residual + (size_t)n * vol * p.out_stride, vol * p.out_stride);
+        if (p.residual2) rs_res2 = make_rsrc_f32(p.residual2 + (size_t)n * vol * p.out_stride, vol * p.out_stride);
         const int in_slice_bytes = HW * p.in_stride * 4;
         const int out_plane_bytes = HW * p.out_stride * 4;
         __amdgpu_buffer_rsrc_t rs_ex = rs_in;
-        if (EXTRA) rs_ex = make_rsrc(p.in_extra + (size_t)n * vol, vol);
+        if (EXTRA) rs_ex = make_rsrc_f32(p.in_extra + (size_t)n * vol, vol);
 
         // per-thread slice elements (validity in y / x does not depend on d): chunk it of a slice = chunk tid + it * NTHREADS.
         // Global offsets are held per column segment; the LDS offset of chunk it is loff0 + it * NTHREADS * 16 exactly (the
@@ -364,7 +298,7 @@ __global__ __launch_bounds__(64 * NW, 1) void conv3d_wino2_kernel(const estd_con
             const int l = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
             return lds_vt[it * NTHREADS + wave * 64 + l];
         };
-        const int loff0 = lds_chunk_off(tid >> 3, tid & 7);
+        const int loff0 = lds_chunk_off<32>(tid >> 3, tid & 7);
         int loffk[SIT];                                  // column-keyed swizzle: the key changes with the chunk's column
 #pragma unroll
         for (int it = 0; it < SIT; ++it) {
@@ -381,7 +315,7 @@ __global__ __launch_bounds__(64 * NW, 1) void conv3d_wino2_kernel(const estd_con
         };
 
         __amdgpu_buffer_rsrc_t rs_gate = rs_in;
-        if (GATE) rs_gate = make_rsrc(p.gate_r + (size_t)n * vol * 32, vol * 32);
+        if (GATE) rs_gate = make_rsrc_f32(p.gate_r + (size_t)n * vol * 32, vol * 32);
         // GATE: the r chunk that belongs to this thread's h chunk lies 64 bytes in front of it in a record of the same stride (in_stride = 32)
         auto gate_voff = [&](unsigned vo) { return gate_lane ? vo - 64u : OOB_OFFSET; };
         auto load_plane_r = [&](int pd, float4 (&dst)[SIT]) {
@@ -687,7 +621,7 @@ __global__ __launch_bounds__(64 * NW, 1) void conv3d_wino2_kernel(const estd_con
                 if (ESTD_W2COLKEY)
                     return *reinterpret_cast<const float4*>(smem + rbase[kw][c] + sd * SLICE_BYTES + r * (IN_W * 128));
                 const int vs = (row0 + r) * IN_W + kw + pi;
-                int off = sd * SLICE_BYTES + lds_chunk_off(vs, g);
+                int off = sd * SLICE_BYTES + lds_chunk_off<32>(vs, g);
                 if (c) off ^= 64;
                 return *reinterpret_cast<const float4*>(smem + off);
             };
@@ -926,7 +860,7 @@ __global__ __launch_bounds__(64 * NW, 1) void conv3d_wino2_kernel(const estd_con
             // ---- the scalar input channel: one more k-step per product (lane group g = column tap kw = g) ----
             if (EXTRA) {
                 // weights: [4 sd][2 halves][64 lanes][4 sh] (packing.pack_conv3d_wino2_extra), L2-resident
-                const __amdgpu_buffer_rsrc_t rs_wx = make_rsrc(p.w_extra, (size_t)4 * 2 * 256);
+                const __amdgpu_buffer_rsrc_t rs_wx = make_rsrc_f32(p.w_extra, (size_t)4 * 2 * 256);
                 const int kwc = g < 3 ? g : 2;               // (g = 3 carries zero weights: any in-slice address)
 #pragma unroll
                 for (int s = 0; s < 4; ++s) {
@@ -1078,8 +1012,6 @@ __global__ __launch_bounds__(64 * NW, 1) void conv3d_wino2_kernel(const estd_con
     }
 }
 
-constexpr int PERSISTENT_WGS = 256;     // one 512-thread workgroup per CU (LDS-limited)
-
 }  // namespace
 
 extern "C" int estd_conv3d_k3_wino2(const estd_conv3d_desc* dp, estd_stream_t s)
@@ -1112,18 +1044,12 @@ extern "C" int estd_conv3d_k3_wino2(const estd_conv3d_desc* dp, estd_stream_t s)
     const int tiles_w = (d.W + TW - 1) / TW, tiles_h = (d.H + TH - 1) / TH, dpairs = (d.D + 1) / 2;
     const long long total = (long long)d.N * dpairs * tiles_h * tiles_w;
     if (total > 0x7fffffffLL) return ESTD_ERR_ARG;
-    {   // buffer descriptors address one volume of the batch with 32-bit byte offsets
-        const long long vox = (long long)d.D * d.H * d.W;
-        const int widest = d.in_stride > d.out_stride ? d.in_stride : d.out_stride;
-        if (vox * widest * 4 >= 0x7fffff00LL) return ESTD_ERR_UNSUPPORTED;
-    }
-    const int slots = estd_persistent_wgs(PERSISTENT_WGS / 256);
-    int grid = total < slots ? (int)total : slots;
-    if (grid >= 8) grid &= ~7;
+    if (!estd_conv3d_volume_fits_rsrc(d)) return ESTD_ERR_UNSUPPORTED;
+    const int grid = estd_persistent_grid(total, 1);     // one 512-thread workgroup per CU (LDS-limited)
     static const int nw = [] { const char* e = getenv("ESTD_WINO2_WAVES"); return (e && atoi(e) == 4) ? 4 : 8; }();
     // read-back kind of the launch (the scale multiply lives in the residual instances)
     const bool res_any = d.residual || d.residual2 || d.out_scale != 1.0f;
-    const int rbk = (!res_any && !d.accumulate) ? 0 : (!res_any ? 1 : (!d.accumulate ? 2 : 3));
+    const int rbk = estd_conv3d_readback_kind(res_any, d.accumulate);
     const bool rb = rbk != 0;
 #define ESTD_W2_LAUNCH(NWV, RBV, EXV, OV)                                                                                            \
     do {                                                                                                                             \

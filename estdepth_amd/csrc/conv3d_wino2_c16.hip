@@ -24,16 +24,13 @@
 
 #include "estd_hip.h"
 #include "estd_common.h"
+#include "estd_device.h"
 
 #ifndef ESTD_C16ABL
 #define ESTD_C16ABL 0   // timing ablations only (results wrong): 1 no stores, 2 no slice writes, 16 no plane prefetch, 128 no row transform
 #endif
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((__vector_size__(16)));
 
 constexpr int TH = 16, TW = 16;
 constexpr int IN_H = TH + 2, IN_W = TW + 2;
@@ -49,19 +46,8 @@ constexpr int W_OFF = 4 * SLICE_BYTES + SS_BYTES + VTAB_BYTES;
 constexpr int LDS_BYTES = W_OFF + NTAPS * TAP_BYTES;            // 138 496
 static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 static_assert(3 * SLICE_BYTES < 65536 && (NTAPS - 1) * TAP_BYTES < 65536, "ds_read immediate offsets");
-constexpr unsigned OOB_OFFSET = 0xFFFFFF00u;
 constexpr int NSTEPS = 12;                          // (sd, kw)
 constexpr int RB_STEP = 7;                          // slices 0..2 are rewritten in front of this step (rows of step 8 = (sd 2, kw 2) are fetched at the end of step 6)
-
-__device__ __forceinline__ float4 as_float4(u32x4 v) { float4 f; __builtin_memcpy(&f, &v, 16); return f; }
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float* base, size_t elems)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)(elems * 4), 0x00020000);
-}
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-__device__ __forceinline__ int lds_chunk_off(int v, int c) { return v * 64 + ((c ^ ((v >> 2) & 3)) << 4); }
-__device__ __forceinline__ float4 f4_sub(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
-__device__ __forceinline__ float4 f4_add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 
 __global__ __launch_bounds__(NTHREADS, 1) void conv3d_wino2_c16_kernel(const estd_conv3d_desc p, int tiles_w, int tiles_h, int dpairs, int total_tiles)
 {
@@ -103,7 +89,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void conv3d_wino2_c16_kernel(const est
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
-        for (int kw = 0; kw < 3; ++kw) roff[r][kw] = lds_chunk_off((row0 + r) * IN_W + kw + pi, g);
+        for (int kw = 0; kw < 3; ++kw) roff[r][kw] = lds_chunk_off<16>((row0 + r) * IN_W + kw + pi, g);
     const int woff = W_OFF + lane * 16;
 
     while (u < u_end) {
@@ -115,8 +101,8 @@ __global__ __launch_bounds__(NTHREADS, 1) void conv3d_wino2_c16_kernel(const est
         const int tw0 = twi * TW, th0 = thi * TH;
         const int seg_end = min(u_end, (col + 1) * dpairs);
 
-        const __amdgpu_buffer_rsrc_t rs_in = make_rsrc(p.in_main + (size_t)n * vol * p.in_stride, vol * p.in_stride);
-        const __amdgpu_buffer_rsrc_t rs_head = make_rsrc(p.out_head + (size_t)n * vol, vol);
+        const __amdgpu_buffer_rsrc_t rs_in = make_rsrc_f32(p.in_main + (size_t)n * vol * p.in_stride, vol * p.in_stride);
+        const __amdgpu_buffer_rsrc_t rs_head = make_rsrc_f32(p.out_head + (size_t)n * vol, vol);
         const int in_slice_bytes = HW * p.in_stride * 4;
 
         // chunk it of a slice for this thread = chunk tid + it * 512: voxel vs = e >> 2, 16-byte chunk e & 3.  Its LDS offset is
@@ -134,7 +120,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void conv3d_wino2_c16_kernel(const est
             const int l = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
             return lds_vt[it * NTHREADS + wave * 64 + l];
         };
-        const int loff0 = lds_chunk_off(tid >> 2, tid & 3);
+        const int loff0 = lds_chunk_off<16>(tid >> 2, tid & 3);
         const bool last_ok = tid + (SIT - 1) * NTHREADS < SL_CHUNKS;
         auto load_plane = [&](int pd, float4 (&dst)[SIT]) {
             const bool pv = (unsigned)pd < (unsigned)D;        // wave-uniform; planes outside the volume are zero padding
@@ -351,9 +337,7 @@ int estd_wino2_c16_launch(const estd_conv3d_desc& d, hipStream_t stream)
     const long long total = (long long)d.N * dpairs * tiles_h * tiles_w;
     if (total > 0x7fffffffLL) return ESTD_ERR_ARG;
     if ((long long)d.D * d.H * d.W * d.in_stride * 4 >= 0x7fffff00LL) return ESTD_ERR_UNSUPPORTED;   // 32-bit byte offsets inside one volume
-    const int slots = estd_persistent_wgs(1);
-    int grid = total < slots ? (int)total : slots;
-    if (grid >= 8) grid &= ~7;
+    const int grid = estd_persistent_grid(total, 1);
     estd_allow_dynamic_lds<conv3d_wino2_c16_kernel>(LDS_BYTES);
     hipLaunchKernelGGL(conv3d_wino2_c16_kernel, dim3(grid), dim3(NTHREADS), LDS_BYTES, stream, d, tiles_w, tiles_h, dpairs, (int)total);
     return ESTD_LAUNCH_CHECK();

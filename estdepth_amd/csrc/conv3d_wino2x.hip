@@ -34,6 +34,7 @@
 
 #include "estd_hip.h"
 #include "estd_common.h"
+#include "estd_device.h"
 
 #ifndef ESTD_W2X_TOUCH
 #define ESTD_W2X_TOUCH 0     // measured: +5 % (0.869 -> 0.913 ms): the touch loads themselves sit in the in-order return queue in front of the next tile's weights
@@ -54,9 +55,6 @@
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((__vector_size__(16)));
 
 constexpr int TH = 8, TW = 16, IN_W = TW + 2;
 constexpr int ROW_B = IN_W * 128;              // one transformed row: 18 voxels x 32 channels
@@ -70,41 +68,7 @@ constexpr int LDS_BYTES = SL_BYTES + SS_BYTES + RED_BYTES;
 static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 constexpr int ITEMS = 2 * IN_W * 8;            // (row pair, column, piece) per wave: 288
 constexpr int ROUNDS = 5;                      // of 64 items (the last one half full)
-constexpr unsigned OOB_OFFSET = 0xFFFFFF00u;   // beyond num_records of any descriptor: loads return 0, stores are dropped
 constexpr int HALF_W_BYTES = 4 * 1024;         // weights of one half step: [4 sh][64 lanes][4]
-
-__device__ __forceinline__ float4 as_float4(u32x4 v)
-{
-    float4 f;
-    __builtin_memcpy(&f, &v, 16);
-    return f;
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float* base, size_t elems)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)(elems * 4), 0x00020000);
-}
-__device__ __forceinline__ void lds_barrier()
-{
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-__device__ __forceinline__ int colkey_off(int col, int piece) { return col * 128 + ((piece ^ ((col >> 1) & 7)) << 4); }
-
-template <int CTRL>
-__device__ __forceinline__ double dpp_add_f64(double v)
-{
-    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)b, CTRL, 0xf, 0xf, false);
-    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(b >> 32), CTRL, 0xf, 0xf, false);
-    return v + __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-__device__ __forceinline__ double row16_sum_f64(double v)
-{
-    v = dpp_add_f64<0xB1>(v);      // quad_perm [1,0,3,2]
-    v = dpp_add_f64<0x4E>(v);      // quad_perm [2,3,0,1]
-    v = dpp_add_f64<0x124>(v);     // row_ror:4
-    v = dpp_add_f64<0x128>(v);     // row_ror:8
-    return v;
-}
 
 // RBK: read-back streams of the epilogue.  0 none; 1 running sum (out += result); 2 residual(s) + scale; 3 both.
 // STATS: GroupNorm(1 group per 16 channels) partial sums of the raw outputs (the ConvGRU gate convolution).
@@ -152,7 +116,7 @@ __global__ __launch_bounds__(256, 1) void conv3d_wino2x_kernel(const estd_conv3d
 #pragma unroll
         for (int c = 0; c < 2; ++c)
 #pragma unroll
-            for (int q = 0; q < 2; ++q) rd[kw][c][q] = wbase + rpl * BLK_B + colkey_off(pi + kw, 4 * c + 2 * q + k2);
+            for (int q = 0; q < 2; ++q) rd[kw][c][q] = wbase + rpl * BLK_B + lds_colkey_off(pi + kw, 4 * c + 2 * q + k2);
     // operand production: item = (row pair, column, piece); lane's item of round t
     int wr[ROUNDS];
 #pragma unroll
@@ -160,11 +124,11 @@ __global__ __launch_bounds__(256, 1) void conv3d_wino2x_kernel(const estd_conv3d
         int id = t * 64 + lane;
         if (id >= ITEMS) id -= 32;              // the idle lanes of the last round repeat lanes 0..31 (same value to the same address)
         const int rp_i = id >= 144 ? 1 : 0, rem = id - 144 * rp_i;
-        wr[t] = wbase + rp_i * BLK_B + colkey_off(rem >> 3, rem & 7);
+        wr[t] = wbase + rp_i * BLK_B + lds_colkey_off(rem >> 3, rem & 7);
     }
 
     // packed weights [4 sd][3 kw][2 c][2 q][4 sh][64 lanes][4] (packing.pack_conv3d_wino2x)
-    const __amdgpu_buffer_rsrc_t rs_w = make_rsrc(p.w_wino2, (size_t)4 * 3 * 2 * 8 * 256);
+    const __amdgpu_buffer_rsrc_t rs_w = make_rsrc_f32(p.w_wino2, (size_t)4 * 3 * 2 * 8 * 256);
     const __amdgpu_buffer_rsrc_t rs_null = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w_wino2), 0, 0, 0x00020000);
     const int wlane = lane * 16;
     const int w_wave = sdh * (2 * 3 * 2 * 2 * HALF_W_BYTES);
@@ -186,7 +150,7 @@ __global__ __launch_bounds__(256, 1) void conv3d_wino2x_kernel(const estd_conv3d
             const int c2 = col / tiles_w;
             pthi = c2 % tiles_h;
             pn = c2 / tiles_h;
-            rs_in = make_rsrc(p.in_main + (size_t)pn * vol * p.in_stride, vol * p.in_stride);
+            rs_in = make_rsrc_f32(p.in_main + (size_t)pn * vol * p.in_stride, vol * p.in_stride);
             const int th0 = pthi * TH, tw0 = ptwi * TW;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
@@ -453,14 +417,14 @@ __global__ __launch_bounds__(256, 1) void conv3d_wino2x_kernel(const estd_conv3d
         // ---- epilogue of plane d0 + sdh: rows 4 rpp + 2 rpl + m, column pi, channels 8 qq + 4 k2 .. + 3 ----
         const int dd = d0 + sdh;
         const bool plane_ok = dd < D;                                   // (odd D: the last pair has one plane)
-        const __amdgpu_buffer_rsrc_t rs_out = plane_ok ? make_rsrc(p.out_main + (size_t)cn * vol * p.out_stride, vol * p.out_stride) : rs_null;
+        const __amdgpu_buffer_rsrc_t rs_out = plane_ok ? make_rsrc_f32(p.out_main + (size_t)cn * vol * p.out_stride, vol * p.out_stride) : rs_null;
         const int so = plane_ok ? dd * out_plane_bytes : 0;
         // read-back streams: decided by the INSTANCE (no runtime flag inside: a conditionally loaded register array becomes a loop-carried
         // value with a select per element); an absent second residual reads through the null descriptor (zeros, no memory access)
         float4 r1[2][4], r2[2][4], ro[2][4];
         if (RB_RES) {
-            const __amdgpu_buffer_rsrc_t rs_res = (plane_ok && p.residual) ? make_rsrc(p.residual + (size_t)cn * vol * p.out_stride, vol * p.out_stride) : rs_null;
-            const __amdgpu_buffer_rsrc_t rs_res2 = (plane_ok && p.residual2) ? make_rsrc(p.residual2 + (size_t)cn * vol * p.out_stride, vol * p.out_stride) : rs_null;
+            const __amdgpu_buffer_rsrc_t rs_res = (plane_ok && p.residual) ? make_rsrc_f32(p.residual + (size_t)cn * vol * p.out_stride, vol * p.out_stride) : rs_null;
+            const __amdgpu_buffer_rsrc_t rs_res2 = (plane_ok && p.residual2) ? make_rsrc_f32(p.residual2 + (size_t)cn * vol * p.out_stride, vol * p.out_stride) : rs_null;
 #pragma unroll
             for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -576,16 +540,10 @@ extern "C" int estd_conv3d_k3_wino2x(const estd_conv3d_desc* dp, estd_stream_t s
     const int tiles_w = (d.W + TW - 1) / TW, tiles_h = (d.H + TH - 1) / TH, dpairs = (d.D + 1) / 2;
     const long long total = (long long)d.N * dpairs * tiles_h * tiles_w;
     if (total > 0x7fffffffLL) return ESTD_ERR_ARG;
-    {
-        const long long vox = (long long)d.D * d.H * d.W;
-        const int widest = d.in_stride > d.out_stride ? d.in_stride : d.out_stride;
-        if (vox * widest * 4 >= 0x7fffff00LL) return ESTD_ERR_UNSUPPORTED;
-    }
-    const int slots = estd_persistent_wgs(1);
-    int grid = total < slots ? (int)total : slots;
-    if (grid >= 8) grid &= ~7;
+    if (!estd_conv3d_volume_fits_rsrc(d)) return ESTD_ERR_UNSUPPORTED;
+    const int grid = estd_persistent_grid(total, 1);
     const bool res_any = d.residual || d.residual2 || d.out_scale != 1.0f;
-    const int rbk = (!res_any && !d.accumulate) ? 0 : (!res_any ? 1 : (!d.accumulate ? 2 : 3));
+    const int rbk = estd_conv3d_readback_kind(res_any, d.accumulate);
 #define ESTD_W2X_LAUNCH(RBV, STV)                                                                                               \
     do {                                                                                                                        \
         estd_allow_dynamic_lds<conv3d_wino2x_kernel<RBV, STV>>(LDS_BYTES);                                                      \

@@ -37,6 +37,7 @@
 
 #include "estd_hip.h"
 #include "estd_common.h"
+#include "estd_device.h"
 
 #ifndef ESTD_W3BD
 #define ESTD_W3BD 4         // weight buffers in flight (half-sub-steps of 8 MFMAs): 4 = requested three half-sub-steps (~800 cycles) ahead
@@ -74,10 +75,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((__vector_size__(16)));
-
 constexpr int TH = 8, TW = 16;
 constexpr int IN_H = TH + 2, IN_W = TW + 2;
 constexpr int SL_VOX = IN_H * IN_W;                 // 180 records per input slice (with halo)
@@ -111,51 +108,6 @@ constexpr int WL_N = 3;
 constexpr int WL_BYTES = 2 * WL_N * 4096;
 constexpr int LDS_BYTES_EXTRA = LDS_BASE_BYTES + XSL_BYTES + XW_BYTES, LDS_BYTES_PLAIN = LDS_BASE_BYTES + (ESTD_W3_WLDS ? WL_BYTES : 0);
 static_assert(LDS_BYTES_EXTRA <= 160 * 1024 && LDS_BYTES_PLAIN <= 160 * 1024, "LDS budget");
-constexpr unsigned OOB_OFFSET = 0xFFFFFF00u;        // beyond num_records of any descriptor: loads return 0, stores are dropped
-
-__device__ __forceinline__ float4 as_float4(u32x4 v)
-{
-    float4 f;
-    __builtin_memcpy(&f, &v, 16);
-    return f;
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float* base, size_t elems)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)(elems * 4), 0x00020000);
-}
-// sum of a double over the 16 lanes of a DPP row, every lane gets the total (as in csrc/conv3d_wino2.hip)
-template <int CTRL>
-__device__ __forceinline__ double dpp_add_f64(double v)
-{
-    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)b, CTRL, 0xf, 0xf, false);
-    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(b >> 32), CTRL, 0xf, 0xf, false);
-    return v + __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-__device__ __forceinline__ double row16_sum_f64(double v)
-{
-    v = dpp_add_f64<0xB1>(v);      // quad_perm [1,0,3,2]
-    v = dpp_add_f64<0x4E>(v);      // quad_perm [2,3,0,1]
-    v = dpp_add_f64<0x124>(v);     // row_ror:4
-    v = dpp_add_f64<0x128>(v);     // row_ror:8
-    return v;
-}
-// workgroup barrier that only orders LDS traffic (no vmcnt drain: prefetches and output stores stay in flight)
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-__device__ __forceinline__ int lds_colkey_off(int col, int c) { return col * 128 + ((c ^ ((col >> 1) & 7)) << 4); }
-__device__ __forceinline__ float tanh_fast(float x)
-{
-    const float t = __builtin_amdgcn_exp2f(x * 2.8853900817779268f);
-    return 1.0f - 2.0f * __builtin_amdgcn_rcpf(t + 1.0f);
-}
-__device__ __forceinline__ float act_apply(float v, int act)
-{
-    if (act == ESTD_ACT_RELU) return v > 0.0f ? v : 0.0f;
-    if (act == ESTD_ACT_TANH) return tanh_fast(v);
-    return v;
-}
-__device__ __forceinline__ float4 f4_sub(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
-__device__ __forceinline__ float4 f4_add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 
 // RBK: read-back streams of the epilogue.  0 none; 1 = running sum only (out += result); 2 = residual (+ residual2) + scale; 3 = both.
 // Absent streams of a kind (no residual2) read through a null descriptor (zeros, no memory access): the tap loop has no branch.
@@ -225,7 +177,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void conv3d_wino3_kernel(const estd_co
     }
     const int xbase = ((4 * rq + 2 * rpl) * IN_W + 2 * cb) * 4 + g * (SL_VOX * 4);       // byte offset of the block's patch origin in the scalar slice sd = g (the lane group's k index)
 
-    const __amdgpu_buffer_rsrc_t rs_w = make_rsrc(p.w_wino2, (size_t)NTAPS * 1024);
+    const __amdgpu_buffer_rsrc_t rs_w = make_rsrc_f32(p.w_wino2, (size_t)NTAPS * 1024);
     const int wlane = lane * 16 + nh * 2048;
     // byte offset of (halo row 4rq + 2rpl, halo column 2cb + j, chunk g + 4cc) of slice 0
     // + the channel pair of half-sub-step half hh: 8 bytes further for hh ^ (g & 1) -- lane groups g, g + 1 read opposite 8-byte halves of their
@@ -250,12 +202,12 @@ __global__ __launch_bounds__(NTHREADS, 1) void conv3d_wino3_kernel(const estd_co
         const int tw0 = twi * TW, th0 = thi * TH;
         const int seg_end = min(u_end, (col + 1) * dpairs);
 
-        const __amdgpu_buffer_rsrc_t rs_in = make_rsrc(p.in_main + (size_t)n * vol * p.in_stride, vol * p.in_stride);
+        const __amdgpu_buffer_rsrc_t rs_in = make_rsrc_f32(p.in_main + (size_t)n * vol * p.in_stride, vol * p.in_stride);
         __amdgpu_buffer_rsrc_t rs_res = rs_in, rs_res2 = rs_in;
-        const __amdgpu_buffer_rsrc_t rs_out = make_rsrc(p.out_main + (size_t)n * vol * p.out_stride, vol * p.out_stride);
-        rs_res = (RB_RES && p.residual) ? make_rsrc(p.residual + (size_t)n * vol * p.out_stride, vol * p.out_stride) : rs_null;
-        rs_res2 = (RB_RES && p.residual2) ? make_rsrc(p.residual2 + (size_t)n * vol * p.out_stride, vol * p.out_stride) : rs_null;
-        const __amdgpu_buffer_rsrc_t rs_ex = EXTRA ? make_rsrc(p.in_extra + (size_t)n * vol, vol) : rs_null;
+        const __amdgpu_buffer_rsrc_t rs_out = make_rsrc_f32(p.out_main + (size_t)n * vol * p.out_stride, vol * p.out_stride);
+        rs_res = (RB_RES && p.residual) ? make_rsrc_f32(p.residual + (size_t)n * vol * p.out_stride, vol * p.out_stride) : rs_null;
+        rs_res2 = (RB_RES && p.residual2) ? make_rsrc_f32(p.residual2 + (size_t)n * vol * p.out_stride, vol * p.out_stride) : rs_null;
+        const __amdgpu_buffer_rsrc_t rs_ex = EXTRA ? make_rsrc_f32(p.in_extra + (size_t)n * vol, vol) : rs_null;
         // EXTRA: thread t < 180 owns voxel t of the scalar channel's haloed slices
         unsigned xoff = OOB_OFFSET;
         if (EXTRA && tid < SL_VOX) {
@@ -326,10 +278,10 @@ __global__ __launch_bounds__(NTHREADS, 1) void conv3d_wino3_kernel(const estd_co
                 else { v.x = u0; v.y = u1; v.z = u2; v.w = u3; }
                 return;
             }
-            v.x = act_apply(a[0] * sc4.x + sh4.x, chb + 0 < p.act_split ? p.act_a : p.act_b);
-            v.y = act_apply(a[1] * sc4.y + sh4.y, chb + 1 < p.act_split ? p.act_a : p.act_b);
-            v.z = act_apply(a[2] * sc4.z + sh4.z, chb + 2 < p.act_split ? p.act_a : p.act_b);
-            v.w = act_apply(a[3] * sc4.w + sh4.w, chb + 3 < p.act_split ? p.act_a : p.act_b);
+            v.x = act_apply_fast(a[0] * sc4.x + sh4.x, chb + 0 < p.act_split ? p.act_a : p.act_b);
+            v.y = act_apply_fast(a[1] * sc4.y + sh4.y, chb + 1 < p.act_split ? p.act_a : p.act_b);
+            v.z = act_apply_fast(a[2] * sc4.z + sh4.z, chb + 2 < p.act_split ? p.act_a : p.act_b);
+            v.w = act_apply_fast(a[3] * sc4.w + sh4.w, chb + 3 < p.act_split ? p.act_a : p.act_b);
         };
         // epilogue of this wave's plane (2 x 2 voxels x 4 channels per lane) in two halves m = block row: the read-back loads of a half back to back,
         // waited for once.  The descriptors are arguments: the deferred form passes null descriptors when there is no previous tile.
@@ -721,8 +673,6 @@ __global__ __launch_bounds__(NTHREADS, 1) void conv3d_wino3_kernel(const estd_co
     }
 }
 
-constexpr int PERSISTENT_WGS = 256;     // one 512-thread workgroup per CU (LDS-limited)
-
 }  // namespace
 
 extern "C" int estd_conv3d_k3_wino3(const estd_conv3d_desc* dp, estd_stream_t s)
@@ -740,17 +690,11 @@ extern "C" int estd_conv3d_k3_wino3(const estd_conv3d_desc* dp, estd_stream_t s)
     const int tiles_w = (d.W + TW - 1) / TW, tiles_h = (d.H + TH - 1) / TH, dpairs = (d.D + 1) / 2;
     const long long total = (long long)d.N * dpairs * tiles_h * tiles_w;
     if (total > 0x7fffffffLL) return ESTD_ERR_ARG;
-    {   // buffer descriptors address one volume of the batch with 32-bit byte offsets
-        const long long vox = (long long)d.D * d.H * d.W;
-        const int widest = d.in_stride > d.out_stride ? d.in_stride : d.out_stride;
-        if (vox * widest * 4 >= 0x7fffff00LL) return ESTD_ERR_UNSUPPORTED;
-    }
-    const int slots = estd_persistent_wgs(PERSISTENT_WGS / 256);
-    int grid = total < slots ? (int)total : slots;
-    if (grid >= 8) grid &= ~7;
+    if (!estd_conv3d_volume_fits_rsrc(d)) return ESTD_ERR_UNSUPPORTED;
+    const int grid = estd_persistent_grid(total, 1);     // one 512-thread workgroup per CU (LDS-limited)
     // read-back kind of the launch (the scale multiply lives in the residual instances)
     const bool res_any = d.residual || d.residual2 || d.out_scale != 1.0f;
-    const int rbk = (!res_any && !d.accumulate) ? 0 : (!res_any ? 1 : (!d.accumulate ? 2 : 3));
+    const int rbk = estd_conv3d_readback_kind(res_any, d.accumulate);
     if (d.stats_partials && rbk != 0) return ESTD_ERR_UNSUPPORTED;       // GroupNorm partial sums: without read-back streams (the gate convolution has none)
 #define ESTD_W3_LAUNCH(RBV, STV, EXV)                                                                                                           \
     do {                                                                                                                             \

@@ -24,12 +24,10 @@
 
 #include "estd_hip.h"
 #include "estd_common.h"
+#include "estd_device.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((__vector_size__(16)));
-constexpr unsigned OOB_OFFSET = 0xFFFFFF00u;
 #ifndef ESTD_XOUT_TW
 #define ESTD_XOUT_TW 16      // tile width: 16 (256 threads, 21 column groups over 4 waves) | 32 (512 threads, 39 groups over 8 waves; A/B: 0.170 vs 0.175 ms, within noise in dres2)
 #endif
@@ -38,12 +36,6 @@ constexpr int NT = TH * TW, NWAVES = NT / 64;                                   
 constexpr int GROUPS = (HALO + 15) / 16;                                                // 21 (39) groups of 16 MFMA columns
 constexpr int PITCH = 33;                                                               // floats per voxel of P (27 taps used)
 constexpr int DSEG = 32;                                                                // output planes per workgroup (+ 2 halo planes)
-
-__device__ __forceinline__ float4 as_float4(u32x4 v) { float4 f; __builtin_memcpy(&f, &v, 16); return f; }
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float* base, size_t elems)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)(elems * 4), 0x00020000);
-}
 
 __global__ __launch_bounds__(NT) void conv3d_xout_kernel(const estd_conv3d_desc p, int tiles_w, int tiles_h, int dsegs)
 {
@@ -60,9 +52,9 @@ __global__ __launch_bounds__(NT) void conv3d_xout_kernel(const estd_conv3d_desc 
     const int h0 = thi * TH, w0 = twi * TW, d0 = ds * DSEG, d1 = min(D, d0 + DSEG);
 
     const size_t vol = (size_t)D * HW;
-    const __amdgpu_buffer_rsrc_t rs_in = make_rsrc(p.in_main + (size_t)n * vol * p.in_stride, vol * p.in_stride);
-    const __amdgpu_buffer_rsrc_t rs_ex = make_rsrc(p.in_extra + (size_t)n * vol, vol);
-    const __amdgpu_buffer_rsrc_t rs_out = make_rsrc(p.out_extra + (size_t)n * vol, vol);
+    const __amdgpu_buffer_rsrc_t rs_in = make_rsrc_f32(p.in_main + (size_t)n * vol * p.in_stride, vol * p.in_stride);
+    const __amdgpu_buffer_rsrc_t rs_ex = make_rsrc_f32(p.in_extra + (size_t)n * vol, vol);
+    const __amdgpu_buffer_rsrc_t rs_out = make_rsrc_f32(p.out_extra + (size_t)n * vol, vol);
 
     // weights of this lane: [chunk][tap tile] quads (taps 16 t + i, channels 16 c + 4 g ..) + the scalar channel's (lane group 0 only)
     const float4* wq = reinterpret_cast<const float4*>(p.w_xout);

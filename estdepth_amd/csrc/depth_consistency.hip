@@ -21,6 +21,7 @@
 // the loop's index -- unrolled, 8 x 24 matrix values would not fit the scalar registers.  The gathers go through the ordinary cached path;
 // pixel offsets are 64-bit.  A lane outside the image, an invalid pixel and a skipped source only mask lanes: no lane leaves the loop early.
 #include "estd_common.h"
+#include "estd_device.h"
 
 namespace {
 
@@ -36,13 +37,6 @@ struct ConsistencyParams {
     float F[ESTD_CONSISTENCY_MAX_SOURCES][12];
     float B[ESTD_CONSISTENCY_MAX_SOURCES][12];
 };
-
-__device__ inline float lerpf(float a, float b, float f) { return fmaf(f, b - a, a); }
-
-// row j of a 3x4 matrix applied to (x, y, 1) z + column 3:  fma(z, fma(M0, x, fma(M1, y, M2)), M3)
-__device__ inline float project_row(const float* m, float x, float y, float z) { return fmaf(z, fmaf(m[0], x, fmaf(m[1], y, m[2])), m[3]); }
-
-__device__ inline bool depth_ok(float d, float z_near) { return d > z_near && d < __builtin_inff(); }          // false for a NaN
 
 __global__ __launch_bounds__(256) void depth_consistency_kernel(const ConsistencyParams p)
 {

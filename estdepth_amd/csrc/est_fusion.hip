@@ -18,6 +18,7 @@
 #include <cstdlib>
 
 #include "estd_common.h"
+#include "estd_device.h"
 
 namespace {
 
@@ -203,8 +204,6 @@ struct WarpAttnArgs {
 // its value chunk and its key chunk (immediate +64) -- instead of two 64-bit flat addresses per corner: a third of the address arithmetic
 // (PMC: 3 % fewer VALU instructions, CU-busy cycles -5.4 % at 3 sources; the texture-address unit's busy cycles do not move: -2 %).
 // Volumes of 2 GiB and more take the pointer form.
-typedef unsigned int wa_u32x4 __attribute__((__vector_size__(16)));
-__device__ __forceinline__ float4 wa_as_float4(wa_u32x4 v) { float4 f; __builtin_memcpy(&f, &v, 16); return f; }
 
 template <int NS, bool BUF>
 __global__ __launch_bounds__(256) void warp_attention_kernel(const float* __restrict__ kv_t, WarpAttnArgs srcs,
@@ -255,8 +254,8 @@ __global__ __launch_bounds__(256) void warp_attention_kernel(const float* __rest
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {          // all 16 gathers of this source before any is used
                     const int vo = t.off[k] * 128 + sub * 16;
-                    cv[k] = wa_as_float4(__builtin_amdgcn_raw_buffer_load_b128(rs, vo, 0, 0));
-                    ck[k] = wa_as_float4(__builtin_amdgcn_raw_buffer_load_b128(rs, vo + 64, 0, 0));
+                    cv[k] = as_float4(__builtin_amdgcn_raw_buffer_load_b128(rs, vo, 0, 0));
+                    ck[k] = as_float4(__builtin_amdgcn_raw_buffer_load_b128(rs, vo + 64, 0, 0));
                 }
             } else {
 #if WA_SHARE
@@ -432,9 +431,7 @@ __device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + expf
 // where expf + an IEEE division and the device library's tanhf take ~20 and ~30; absolute error <= 2e-7).  Measured NEUTRAL on MI355X
 // (gru_blend 92.9 vs 94.8 us, gru_reset 79.0 vs 80.0 us stand-alone; Joint step 17.40-17.42 vs 17.40 ms, profiles/r4_graph_memory_ab.txt):
 // both kernels are bound by their memory access pattern (64-byte halves of 128-byte records), not by the VALU -- so the default keeps
-// the library functions the oracle uses.
-__device__ __forceinline__ float sigmoid_fast(float v) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.4426950408889634f)); }
-__device__ __forceinline__ float tanh_fast_(float v) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(v * 2.8853900817779268f) + 1.0f); }
+// the library functions the oracle uses.  sigmoid_fast and tanh_fast: csrc/estd_device.h.
 
 // xrh = [x, sigmoid(GN(r_raw)) * h]; one lane per float4 of the 16-channel halves
 template <bool FAST>
@@ -485,7 +482,7 @@ __global__ __launch_bounds__(256) void gru_blend_kernel(const float* __restrict_
     auto one = [&](float hv, float uv, float ov, float guv, float buv, float gov, float bov) {
         const float ua = (uv - mu) * ru_ * guv + buv, oa = (ov - mo) * ro * gov + bov;
         const float uu = FAST ? sigmoid_fast(ua) : sigmoidf_(ua);
-        const float yy = FAST ? tanh_fast_(oa) : tanhf(oa);
+        const float yy = FAST ? tanh_fast(oa) : tanhf(oa);
         return uu * hv + (1.0f - uu) * yy;
     };
     float4 r;

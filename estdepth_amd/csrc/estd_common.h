@@ -44,6 +44,32 @@ static inline int estd_persistent_wgs(int per_cu)
     const int cus = estd_device_cus() - estd_get_reserved_cus();
     return (cus > 8 ? cus : 8) * per_cu;
 }
+// grid of a persistent kernel over `total` work items: one workgroup per item up to the resident ones; from 8 on a multiple of 8, which the
+// kernels' XCD-aware blockIdx -> item mapping needs (a grid that is no multiple of 8 takes their plain mapping)
+static inline int estd_persistent_grid(long long total, int per_cu)
+{
+    const int slots = estd_persistent_wgs(per_cu);
+    int grid = total < slots ? (int)total : slots;
+    if (grid >= 8) grid &= ~7;
+    return grid;
+}
+
+// the buffer descriptors of the 3x3x3 kernels address ONE volume of the batch with 32-bit byte offsets: its widest record has to fit
+static inline bool estd_conv3d_volume_fits_rsrc(const estd_conv3d_desc& d)
+{
+    const long long vox = (long long)d.D * d.H * d.W;
+    const int widest = d.in_stride > d.out_stride ? d.in_stride : d.out_stride;
+    return vox * widest * 4 < 0x7fffff00LL;
+}
+
+// read-back streams of a 3x3x3 epilogue (the kernels' RBK): 0 none; 1 = running sum only (out += result); 2 = residual (+ residual2) + scale; 3 = both
+static inline int estd_conv3d_readback_kind(bool res_any, bool accumulate)
+{
+    return (!res_any && !accumulate) ? 0 : (!res_any ? 1 : (!accumulate ? 2 : 3));
+}
+
+// a positive finite float (false for a NaN)
+static inline bool finite_pos(float v) { return v > 0.f && v < __builtin_inff(); }
 
 // csrc/conv3d_wino2_c16.hip: the 16 -> 16 + head instance behind estd_conv3d_k3_wino2 (arguments validated by the caller)
 int estd_wino2_c16_launch(const estd_conv3d_desc& d, hipStream_t stream);

@@ -1,0 +1,175 @@
+// Device-side primitives shared by the kernel sources of libestd_hip.so (gfx950 only): each one is written here once, at global scope.
+// Every function is __forceinline__, so a kernel compiles to the same code as with a private copy.  A helper that only one file uses
+// stays in that file, and so do the kernel-specific constants (tile sizes, LDS budgets, the ESTD_* A/B switches and their notes).
+// tests/test_kernel_helpers_cpu.py keeps the .hip files from defining any of these names again.
+#ifndef ESTD_DEVICE_H
+#define ESTD_DEVICE_H
+
+#include <hip/hip_runtime.h>
+
+#include <type_traits>
+#include <utility>
+
+#include "estd_hip.h"
+
+// ---- vector types ----
+typedef float f32x4 __attribute__((ext_vector_type(4)));            // an MFMA accumulator
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x4 __attribute__((__vector_size__(16)));    // the type raw_buffer_load_b128 returns (GCC vector)
+typedef unsigned int u32x3 __attribute__((__vector_size__(12)));
+typedef unsigned int u32x2 __attribute__((__vector_size__(8)));
+typedef __bf16 bf16x8 __attribute__((__vector_size__(16)));         // the bf16 MFMA operand of the operand-split kernels
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+
+constexpr unsigned OOB_OFFSET = 0xFFFFFF00u;    // beyond num_records of any descriptor: loads return 0, stores are dropped
+
+// ---- casts ----
+__device__ __forceinline__ float4 as_float4(u32x4 v)
+{
+    // NB: __builtin_bit_cast(float, v[i]) on a vector element is miscompiled by this clang (every lane reads
+    // element 0); a whole-object copy is the safe form.
+    float4 f;
+    __builtin_memcpy(&f, &v, 16);
+    return f;
+}
+__device__ __forceinline__ float2 as_float2(u32x2 v) { float2 f; __builtin_memcpy(&f, &v, 8); return f; }
+__device__ __forceinline__ u32x4 as_u32x4(float4 f) { u32x4 v; __builtin_memcpy(&v, &f, 16); return v; }
+
+// ---- buffer descriptors: the name states the unit of the extent (a descriptor sized in the wrong unit either reaches past the
+// buffer, where the hardware no longer clamps, or returns zeros for loads that are in range) ----
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc_f32(const float* base, size_t elems)
+{
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)(elems * 4), 0x00020000);
+}
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc_bytes(const void* base, size_t bytes)
+{
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
+}
+
+// Workgroup barrier that only orders LDS traffic.  __syncthreads() would also drain vmcnt, i.e. wait for the
+// previous tile's output stores (and the in-flight prefetch) to complete on every tile.
+__device__ __forceinline__ void lds_barrier()
+{
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
+// ---- LDS swizzles ----
+// byte offset of 16-byte chunk c of LDS voxel record v; CM = channels of a record: 32 -> 128-byte records, key (v >> 1) & 7;
+// 16 -> 64-byte records, key (v >> 2) & 3
+template <int CM>
+__device__ __forceinline__ int lds_chunk_off(int v, int c)
+{
+    if (CM == 32) return v * 128 + ((c ^ ((v >> 1) & 7)) << 4);
+    else          return v * 64 + ((c ^ ((v >> 2) & 3)) << 4);
+}
+// The swizzle key taken from the COLUMN of the haloed slice only -- (col >> 1) & 7; IN_W is even, so the bank half (voxel & 1) is the
+// column's parity and the 8 even / 8 odd columns a fragment read touches still have 8 distinct keys -- which makes the byte offset of
+// (row, col, chunk) = row * IN_W * 128 + f(col, chunk): the fragment reads of a tap loop then need one address register per (column
+// tap, channel chunk) and immediates for the halo row and the depth slice, instead of one register per (row, column tap) plus an XOR
+// per second-chunk read.
+__device__ __forceinline__ int lds_colkey_off(int col, int c) { return col * 128 + ((c ^ ((col >> 1) & 7)) << 4); }
+
+// ---- DPP row sums ----
+// sum over the 16 lanes of a DPP row (every lane gets the total): two quad permutations + two row rotations, all folded into v_add_f32
+template <int CTRL>
+__device__ __forceinline__ float dpp_add(float v)
+{
+    return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float row16_sum(float v)
+{
+    v = dpp_add<0xB1>(v);      // quad_perm [1,0,3,2]
+    v = dpp_add<0x4E>(v);      // quad_perm [2,3,0,1]
+    v = dpp_add<0x124>(v);     // row_ror:4
+    v = dpp_add<0x128>(v);     // row_ror:8
+    return v;
+}
+// sum of a double over the 16 lanes of a DPP row, every lane gets the total: two quad permutations + two row rotations of the two
+// dwords (v_mov_b32 with a DPP modifier: no LDS round trip) and one v_add_f64 per level
+template <int CTRL>
+__device__ __forceinline__ double dpp_add_f64(double v)
+{
+    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)b, CTRL, 0xf, 0xf, false);
+    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(b >> 32), CTRL, 0xf, 0xf, false);
+    return v + __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ double row16_sum_f64(double v)
+{
+    v = dpp_add_f64<0xB1>(v);      // quad_perm [1,0,3,2]
+    v = dpp_add_f64<0x4E>(v);      // quad_perm [2,3,0,1]
+    v = dpp_add_f64<0x124>(v);     // row_ror:4
+    v = dpp_add_f64<0x128>(v);     // row_ror:8
+    return v;
+}
+
+// ---- activations ----
+// tanh x = 1 - 2 / (exp(2x) + 1) on the transcendental units (v_exp_f32, v_rcp_f32: 1 ulp each; five instructions instead of the device
+// library's ~30).  Absolute error <= 2e-7 over the whole range (cancellation near 0 costs relative, not absolute accuracy); +-inf -> +-1.
+__device__ __forceinline__ float tanh_fast(float x)
+{
+    const float t = __builtin_amdgcn_exp2f(x * 2.8853900817779268f);
+    return 1.0f - 2.0f * __builtin_amdgcn_rcpf(t + 1.0f);
+}
+// sigmoid the same way: four instructions where expf + an IEEE division take ~20
+__device__ __forceinline__ float sigmoid_fast(float v) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.4426950408889634f)); }
+// the activation of an epilogue that branches per output element; tanh is the device library's, as in the oracle ...
+__device__ __forceinline__ float act_apply(float v, int act)
+{
+    if (act == ESTD_ACT_RELU) return v > 0.0f ? v : 0.0f;
+    if (act == ESTD_ACT_TANH) return tanhf(v);
+    return v;
+}
+// ... and with tanh_fast (csrc/conv3d_wino3.hip): a call site chooses its numerics by name
+__device__ __forceinline__ float act_apply_fast(float v, int act)
+{
+    if (act == ESTD_ACT_RELU) return v > 0.0f ? v : 0.0f;
+    if (act == ESTD_ACT_TANH) return tanh_fast(v);
+    return v;
+}
+
+__device__ __forceinline__ float4 f4_sub(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
+__device__ __forceinline__ float4 f4_add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+
+// ---- 3 x bf16 operand split (csrc/conv3d_split_bf16.hip, csrc/conv2d_split_bf16.hip) ----
+// x0, x1 -> three packed bf16 pairs with x = h + m + l (exact unless x is within 2^-24 of the bf16 range limits)
+__device__ __forceinline__ void split2(float x0, float x1, unsigned& h, unsigned& m, unsigned& l)
+{
+    const bf16x2 hb = {(__bf16)x0, (__bf16)x1};
+    h = __builtin_bit_cast(unsigned, hb);
+    float r0 = x0 - __builtin_bit_cast(float, h << 16);
+    float r1 = x1 - __builtin_bit_cast(float, h & 0xffff0000u);
+    const bf16x2 mb = {(__bf16)r0, (__bf16)r1};
+    m = __builtin_bit_cast(unsigned, mb);
+    r0 -= __builtin_bit_cast(float, m << 16);
+    r1 -= __builtin_bit_cast(float, m & 0xffff0000u);
+    const bf16x2 lb = {(__bf16)r0, (__bf16)r1};
+    l = __builtin_bit_cast(unsigned, lb);
+}
+// 8 channels (two float4) of one voxel -> LDS, one 16-byte write per piece (o1 - o0 = o2 - o1 = PIECE_BYTES for real items)
+__device__ __forceinline__ void fill_item(char* smem, int o0, int o1, int o2, float4 a, float4 b)
+{
+    u32x4 h, m, l;
+    unsigned th, tm, tl;
+    split2(a.x, a.y, th, tm, tl); h[0] = th; m[0] = tm; l[0] = tl;
+    split2(a.z, a.w, th, tm, tl); h[1] = th; m[1] = tm; l[1] = tl;
+    split2(b.x, b.y, th, tm, tl); h[2] = th; m[2] = tm; l[2] = tl;
+    split2(b.z, b.w, th, tm, tl); h[3] = th; m[3] = tm; l[3] = tl;
+    *reinterpret_cast<u32x4*>(smem + o0) = h;
+    *reinterpret_cast<u32x4*>(smem + o1) = m;
+    *reinterpret_cast<u32x4*>(smem + o2) = l;
+}
+// compile-time tap index: a "#pragma unroll" loop gets peeled (some taps are special) and is then no longer fully unrolled
+template <typename F, int... I>
+__device__ __forceinline__ void for_each_tap(F&& f, std::integer_sequence<int, I...>)
+{
+    (f(std::integral_constant<int, I>{}), ...);
+}
+
+// ---- reconstruction kernels ----
+__device__ __forceinline__ float lerpf(float a, float b, float f) { return fmaf(f, b - a, a); }
+// row j of a 3x4 matrix applied to (x, y, 1) z + column 3:  fma(z, fma(M0, x, fma(M1, y, M2)), M3)
+__device__ __forceinline__ float project_row(const float* m, float x, float y, float z) { return fmaf(z, fmaf(m[0], x, fmaf(m[1], y, m[2])), m[3]); }
+__device__ __forceinline__ bool depth_ok(float d, float z_near) { return d > z_near && d < __builtin_inff(); }          // false for a NaN
+
+#endif

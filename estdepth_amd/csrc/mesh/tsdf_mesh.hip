@@ -236,8 +236,6 @@ __global__ __launch_bounds__(256) void surface_net_faces_kernel(const FaceParams
     }
 }
 
-inline bool finite_pos(float v) { return v > 0.f && v < __builtin_inff(); }
-
 // any X; the launch grids bound each dimension and the 32-bit cell ids the number of voxels
 inline int check_dims(int Z, int Y, int X)
 {

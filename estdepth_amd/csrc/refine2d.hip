@@ -21,6 +21,7 @@
 #include "estd_hip.h"
 
 #include "estd_common.h"
+#include "estd_device.h"
 
 namespace {
 
@@ -142,8 +143,6 @@ __global__ __launch_bounds__(256) void disp_head_nhwc_kernel(const float* __rest
 // One wave = a strip of ROWS output rows x 16 output pixels.  MFMA 16x16x4 f32, issued transposed (weights as A, pixels as B):
 // lane (g, i) loads channels 16 q + 4 g .. + 3 of input pixel i (one 16-byte load per tap and 16-channel half) as the k-steps
 // ks = 0..3 (K order permuted, weights packed to match) and ends up holding output channels 4 g .. 4 g + 3 of pixel i.
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4_t __attribute__((__vector_size__(16)));
 constexpr int TO16_ROWS = 8;
 
 template <int CIN, bool UP>
@@ -180,7 +179,7 @@ __global__ __launch_bounds__(256) void conv2d_k3_to16_kernel(const float* __rest
     for (int r = 0; r < TO16_ROWS; ++r) {
         const int y = strip * TO16_ROWS + r;
         if (y >= H) break;                                    // wave-uniform
-        f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky) {
             const int yy = y + ky - 1;
@@ -190,7 +189,7 @@ __global__ __launch_bounds__(256) void conv2d_k3_to16_kernel(const float* __rest
             for (int kx = 0; kx < 3; ++kx) {
 #pragma unroll
                 for (int q = 0; q < Q; ++q) {
-                    const u32x4_t raw = __builtin_amdgcn_raw_buffer_load_b128(rs_in, coloff[kx], rowoff + q * 64, 0);
+                    const u32x4 raw = __builtin_amdgcn_raw_buffer_load_b128(rs_in, coloff[kx], rowoff + q * 64, 0);
                     float4 a;
                     __builtin_memcpy(&a, &raw, 16);
                     const float4 wq = wr[ky * 3 + kx][q];
@@ -260,9 +259,9 @@ __global__ __launch_bounds__(256) void conv2d_small_kernel(const float* __restri
     for (int r = 0; r < rows; ++r) {
         const int y = strip * rows + r;
         if (y >= Ho) break;                                   // wave-uniform
-        f32x4_t acc[NTW][2];                                  // two chains per tile: no MFMA waits for its own predecessor
+        f32x4 acc[NTW][2];                                    // two chains per tile: no MFMA waits for its own predecessor
 #pragma unroll
-        for (int u = 0; u < NTW; ++u) { acc[u][0] = (f32x4_t){0.f, 0.f, 0.f, 0.f}; acc[u][1] = (f32x4_t){0.f, 0.f, 0.f, 0.f}; }
+        for (int u = 0; u < NTW; ++u) { acc[u][0] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc[u][1] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
 #pragma unroll
         for (int ky = 0; ky < KS; ++ky) {
             const int yy = y * STRIDE + ky - PAD;
@@ -272,7 +271,7 @@ __global__ __launch_bounds__(256) void conv2d_small_kernel(const float* __restri
             for (int kx = 0; kx < KS; ++kx) {
 #pragma unroll
                 for (int q = 0; q < Q; ++q) {
-                    const u32x4_t raw = __builtin_amdgcn_raw_buffer_load_b128(rs_in, coloff[kx], rowoff + q * 64, 0);
+                    const u32x4 raw = __builtin_amdgcn_raw_buffer_load_b128(rs_in, coloff[kx], rowoff + q * 64, 0);
                     float4 a;
                     __builtin_memcpy(&a, &raw, 16);
 #pragma unroll

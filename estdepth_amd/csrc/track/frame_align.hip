@@ -21,6 +21,7 @@
 // adds the partials: workgroup k owns term k, lane l adds partials l, l + 64, l + 128, ... in ascending order, and the same butterfly
 // joins the lanes.  The matrices, pointers and constants are kernel arguments; pixel offsets are 64-bit.
 #include "estd_common.h"
+#include "estd_device.h"
 
 namespace {
 
@@ -39,13 +40,8 @@ struct AlignParams {
     float L[12], F[12], B[12];
 };
 
-// row j of a 3x4 matrix applied to (x, y, 1) z + column 3:  fma(z, fma(M0, x, fma(M1, y, M2)), M3)
-__device__ inline float project_row(const float* m, float x, float y, float z) { return fmaf(z, fmaf(m[0], x, fmaf(m[1], y, m[2])), m[3]); }
-
 // row j of a 3x4 matrix applied to the point (x, y, z, 1):  fma(M0, x, fma(M1, y, fma(M2, z, M3)))
 __device__ inline float point_row(const float* m, float x, float y, float z) { return fmaf(m[0], x, fmaf(m[1], y, fmaf(m[2], z, m[3]))); }
-
-__device__ inline bool depth_ok(float d, float z_near) { return d > z_near && d < __builtin_inff(); }          // false for a NaN
 
 // the sum of x over the 64 lanes, the same bits in every lane
 __device__ inline double wave_sum(double x)

@@ -300,8 +300,6 @@ __global__ __launch_bounds__(256) void tsdf_edge_colors_kernel(const EdgeColorPa
     for (int j = 0; j < 3; ++j) p.out[i * 3 + j] = c[j];
 }
 
-inline bool finite_pos(float v) { return v > 0.f && v < __builtin_inff(); }
-
 inline int check_dims(int Z, int Y, int X)
 {
     if (Z <= 0 || Y <= 0 || X <= 0 || (X & 3)) return ESTD_ERR_ARG;

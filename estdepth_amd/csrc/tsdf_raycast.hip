@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "estd_common.h"
+#include "estd_device.h"
 
 namespace {
 
@@ -49,8 +50,6 @@ struct RaycastColorParams : RaycastParams {
     const float* C;
     float* color;
 };
-
-__device__ inline float lerpf(float a, float b, float f) { return fmaf(f, b - a, a); }
 
 // the trilinear blend (x, then y, then z: the nesting of Wb) of one plane at the cell whose first corner is c
 __device__ inline float blend_cell(const float* c, long long sy, long long sz, float fx, float fy, float fz)

@@ -78,5 +78,39 @@ def main(files):
         print()
 
 
+def device_code_hashes(ab=False):
+    """-> [(source, sha256 of its gfx950 code object, sha256 of that object's .text)] for every source of the library (``ab``: the A/B sources too,
+    with -DESTD_BUILD_AB=1).  The sources are named relative to csrc/ with csrc/ as the working directory, so the hashes do not depend on where the
+    checkout lies: two commits whose lines agree run the same device code.  The compilation-unit id, which names a symbol of the code object,
+    is set to the source's name: the compiler's default hashes its whole command line, the absolute -I and -o paths included."""
+    import hashlib
+    from concurrent.futures import ThreadPoolExecutor
+    sys.path.insert(0, ROOT)
+    from estdepth_amd import build
+    sources = list(build.SOURCES) + ([s for s in build.AB_SOURCES if s not in build.SOURCES] if ab else [])
+    flags = FLAGS + (["-DESTD_BUILD_AB=1"] if ab else []) + ["--offload-device-only", "--no-gpu-bundle-output"]
+
+    def sha(path):
+        return hashlib.sha256(open(path, "rb").read()).hexdigest()
+
+    def one(src):
+        with tempfile.TemporaryDirectory() as tmp:
+            co, text = os.path.join(tmp, "a.co"), os.path.join(tmp, "a.text")
+            for cmd in (["/opt/rocm/bin/hipcc"] + flags + ["-cuid=" + src, "-c", src, "-o", co],
+                        ["/opt/rocm/llvm/bin/llvm-objcopy", "-O", "binary", "--only-section=.text", co, text]):
+                r = subprocess.run(cmd, capture_output=True, text=True, cwd=CSRC)
+                if r.returncode != 0:
+                    raise RuntimeError("%s failed on %s:\n%s" % (os.path.basename(cmd[0]), src, r.stderr[-2000:]))
+            return src, sha(co), sha(text)
+
+    with ThreadPoolExecutor(max_workers=16) as ex:
+        return list(ex.map(one, sources))
+
+
 if __name__ == "__main__":
-    main(sys.argv[1:] or FILES)
+    if "--hash" in sys.argv[1:]:
+        print("# %-28s %-64s %s" % ("source", "sha256(code object)", "sha256(.text)"))
+        for src, co, text in device_code_hashes(ab="--ab" in sys.argv[1:]):
+            print("%-30s %s %s" % (src, co, text))
+    else:
+        main(sys.argv[1:] or FILES)
