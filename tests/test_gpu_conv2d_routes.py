@@ -12,7 +12,8 @@ A route is one kernel instance, reached through the op or switch that reaches it
     the input or the residual would show as NaN in the output).  The three results must be bit-identical;
   * runs shapes at the tile edges (1x1 maps; just below / at / above the 8 x 16 tiles of the 3x3 kernels and the 16-pixel rows of the
     refine / stem kernels; odd maps for stride 2; batches 1-3; 1, 2, 4 and odd counts of 16-channel chunks; cout 320 on the 128-wide
-    tiles), the full-size layers of each family at the benchmark's 5 x 480 x 640 (reference at sampled pixels) and the 32-bit limits:
+    tiles), the two persistent 3x3 kernels over ranges of several work items per workgroup (many thin images, two grid sizes:
+    tests/tile_ranges_ref.py), the full-size layers of each family at the benchmark's 5 x 480 x 640 (reference at sampled pixels) and the 32-bit limits:
     conv1x1 / taps just below 0x7fffff00 bytes over the batch (and at / above it: refused by both bindings), and one batch of more than
     2^31 bytes through each per-image kernel.
 ESTD_C1X1_CFG / ESTD_CTAPS_CFG / ESTD_C1X1_LDS are latched at the first call: each forced configuration runs its cases in a child process
@@ -34,10 +35,11 @@ DEV = torch.device("cuda:0")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # per-element bound constants, in units of 2^-24 A: at least 3 x the worst ratio measured on an MI355X over every case of the route
-# (in the comments).
+# (in the comments).  The many-item cases added later (test_conv2d_plan_over_multi_item_ranges) are held to the same constants; their worst
+# ratios, over every pixel of 20 - 192 images, are in brackets.
 C_ROUTE = {
-    "wino2": 8.0,             # measured 2.50 (full-plan-resnet-layer2)
-    "k3": 17.0,               # measured 5.49 (plan-k3-nt4-d2-res-relu_after)
+    "wino2": 8.0,             # measured 2.50 (full-plan-resnet-layer2) [2.99: plan-wino2-d2-cout192]
+    "k3": 17.0,               # measured 5.49 (plan-k3-nt4-d2-res-relu_after) [7.02: plan-k3-nt2-d2-res]
     "wino": 17.0,             # not measured (ESTD_BUILD_AB=1 builds only): the direct kernel's constant
     "k3_split": 17.0,         # not measured (ESTD_BUILD_AB=1 builds only): the direct kernel's constant
     "conv1x1": 19.0,          # measured 6.06 (full-lds0-11: 2048 -> 512 at 15 x 20 on the direct form)
@@ -159,26 +161,33 @@ WINO2 = dict(CONV2D_ALGO="wino2", CONV2D_NT="auto", C2W2_DIL2=True)
 DIRECT2, DIRECT4 = dict(CONV2D_ALGO="direct", CONV2D_NT="2"), dict(CONV2D_ALGO="direct", CONV2D_NT="4")
 
 
+# Many work items on few pixels (tests/tile_ranges_ref.py): ``many`` images of 9 x 17 (2 x 2 tiles, three of them ragged; 3 x 2 of the
+# 64-channel items of conv2d_wino2) give every workgroup of the reserve-128 grid a range of three or four items, of which the kernel prefetches
+# the next one while it works: another tile of the image, the next image, the next output-channel group.  ``many`` is the smallest batch that
+# does it for the case's cout (tile_ranges_ref.batch2d; tests/test_tile_ranges_cpu.py).
+MANY_HW = (9, 17)
+
+
 def K(cid, fam, route, shapes, **kw):
     return dict(id=cid, fam=fam, route=route, shapes=[list(s) for s in shapes], **kw)
 
 
 PLAN_CASES = [
     # Conv2dPlan: every instance of the two NHWC 3x3 kernels (ops.CONV2D_ALGO / CONV2D_NT / C2W2_DIL2), every epilogue
-    K("plan-wino2-d1-relu_before", "plan", "wino2", PLAN_EDGE, cin=32, cout=64, dil=1, rb=True, kern="conv2d_wino2_kernel<1>"),
-    K("plan-wino2-d1-res-relu_after", "plan", "wino2", PLAN_EDGE, cin=96, cout=32, dil=1, res=True, ra=True, kern="conv2d_wino2_kernel<1>"),
-    K("plan-wino2-d1-res", "plan", "wino2", PLAN_EDGE, cin=64, cout=320, dil=1, res=True, kern="conv2d_wino2_kernel<1>"),
-    K("plan-wino2-d2-relu_before", "plan", "wino2", PLAN_EDGE, cin=32, cout=32, dil=2, rb=True, kern="conv2d_wino2_kernel<2>"),
-    K("plan-wino2-d2-res-relu_after", "plan", "wino2", PLAN_EDGE, cin=64, cout=64, dil=2, res=True, ra=True, kern="conv2d_wino2_kernel<2>"),
-    K("plan-k3-nt2-d1-relu_before", "plan", "k3", PLAN_EDGE, cin=32, cout=64, dil=1, rb=True, sw=DIRECT2, kern="conv2d_k3_kernel<2, 1>"),
-    K("plan-k3-nt4-d1-res-relu_after", "plan", "k3", PLAN_EDGE, cin=96, cout=128, dil=1, res=True, ra=True, sw=DIRECT4,
+    K("plan-wino2-d1-relu_before", "plan", "wino2", PLAN_EDGE, many=129, cin=32, cout=64, dil=1, rb=True, kern="conv2d_wino2_kernel<1>"),
+    K("plan-wino2-d1-res-relu_after", "plan", "wino2", PLAN_EDGE, many=192, cin=96, cout=32, dil=1, res=True, ra=True, kern="conv2d_wino2_kernel<1>"),
+    K("plan-wino2-d1-res", "plan", "wino2", PLAN_EDGE, many=26, cin=64, cout=320, dil=1, res=True, kern="conv2d_wino2_kernel<1>"),
+    K("plan-wino2-d2-relu_before", "plan", "wino2", PLAN_EDGE, many=192, cin=32, cout=32, dil=2, rb=True, kern="conv2d_wino2_kernel<2>"),
+    K("plan-wino2-d2-res-relu_after", "plan", "wino2", PLAN_EDGE, many=129, cin=64, cout=64, dil=2, res=True, ra=True, kern="conv2d_wino2_kernel<2>"),
+    K("plan-k3-nt2-d1-relu_before", "plan", "k3", PLAN_EDGE, many=96, cin=32, cout=64, dil=1, rb=True, sw=DIRECT2, kern="conv2d_k3_kernel<2, 1>"),
+    K("plan-k3-nt4-d1-res-relu_after", "plan", "k3", PLAN_EDGE, many=96, cin=96, cout=128, dil=1, res=True, ra=True, sw=DIRECT4,
       kern="conv2d_k3_kernel<4, 1>"),
-    K("plan-k3-nt2-d2-res", "plan", "k3", PLAN_EDGE, cin=64, cout=64, dil=2, res=True, sw=dict(WINO2, C2W2_DIL2=False),
+    K("plan-k3-nt2-d2-res", "plan", "k3", PLAN_EDGE, many=96, cin=64, cout=64, dil=2, res=True, sw=dict(WINO2, C2W2_DIL2=False),
       kern="conv2d_k3_kernel<2, 2>", kern_ab="conv2d_wino_kernel<2, 2>"),
-    K("plan-k3-nt4-d2-res-relu_after", "plan", "k3", PLAN_EDGE, cin=32, cout=320, dil=2, res=True, ra=True, sw=DIRECT4,
+    K("plan-k3-nt4-d2-res-relu_after", "plan", "k3", PLAN_EDGE, many=39, cin=32, cout=320, dil=2, res=True, ra=True, sw=DIRECT4,
       kern="conv2d_k3_kernel<4, 2>"),
-    K("plan-k3-nt2-d1-cout320", "plan", "k3", PLAN_EDGE, cin=32, cout=320, dil=1, ra=True, sw=DIRECT2, kern="conv2d_k3_kernel<2, 1>"),
-    # the ESTD_BUILD_AB=1 kernels (skipped in the default build)
+    K("plan-k3-nt2-d1-cout320", "plan", "k3", PLAN_EDGE, many=20, cin=32, cout=320, dil=1, ra=True, sw=DIRECT2, kern="conv2d_k3_kernel<2, 1>"),
+    # the ESTD_BUILD_AB=1 kernels (skipped in the default build; no many-item shape)
     K("plan-wino-ab", "plan", "wino", PLAN_EDGE, cin=32, cout=64, dil=1, res=True, ra=True, sw=dict(CONV2D_ALGO="wino", CONV2D_NT="4"),
       kern="conv2d_wino_kernel<4, 1>", ab=True),
     K("plan-k3-split-ab", "plan", "k3_split", PLAN_EDGE, cin=32, cout=64, dil=1, res=True, sw=dict(CONV2D_ARITH="bf16x3"),
@@ -193,6 +202,16 @@ PLAN_CASES = [
     # per-image descriptors: one batch of more than 2^31 bytes per tensor
     K("big-plan-wino2", "plan", "wino2", [(56, 480, 640)], cin=32, cout=32, dil=1, res=True, ra=True, kern="conv2d_wino2_kernel<1>"),
     K("big-plan-k3", "plan", "k3", [(56, 480, 640)], cin=32, cout=32, dil=1, rb=True, sw=DIRECT2, kern="conv2d_k3_kernel<2, 1>"),
+]
+
+# only on the many-item shape: a cout of three groups for the instances whose cases above have one or two (the boundary between TWO groups is
+# always a boundary between two ranges as well: the grid is even)
+RANGE_CASES = [
+    K("plan-wino2-d1-cout96", "plan", "wino2", [], many=64, cin=32, cout=96, dil=1, res=True, ra=True, kern="conv2d_wino2_kernel<1>"),
+    K("plan-wino2-d2-cout96", "plan", "wino2", [], many=64, cin=64, cout=96, dil=2, rb=True, kern="conv2d_wino2_kernel<2>"),
+    K("plan-wino2-d2-cout192", "plan", "wino2", [], many=43, cin=32, cout=192, dil=2, res=True, kern="conv2d_wino2_kernel<2>"),
+    K("plan-k3-nt4-d1-cout192", "plan", "k3", [], many=64, cin=32, cout=192, dil=1, res=True, sw=DIRECT4, kern="conv2d_k3_kernel<4, 1>"),
+    K("plan-k3-nt2-d2-cout96", "plan", "k3", [], many=64, cin=32, cout=96, dil=2, ra=True, sw=DIRECT2, kern="conv2d_k3_kernel<2, 2>"),
 ]
 
 # (N, H, W, cin, cout, stride, relu, residual, affine): tile edges of both 1x1 forms -- 1x1 maps, ragged pixel tiles, odd maps at stride 2,
@@ -493,42 +512,62 @@ def _expected_kernel(case, shape):
     return taps_kernel(int(os.environ.get("ESTD_CTAPS_CFG", "0")), N, H, W, cin, cout, case["k"], case["stride"], case["pad"], cus)
 
 
-def run_case(case):
-    """all shapes of one case -> (worst ratio, the kernel instances that ran)"""
+def _three_runs(case, m, want, what):
+    """steps 1-3 of a case on one shape -> the op's output, the kernel instances that ran"""
+    # 1. the torch binding, under the profiler
+    with _Switches(case.get("sw"), "torch"):
+        with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CUDA]) as prof:
+            out_t = _op(case, m, m["x"], m["res"])
+            torch.cuda.synchronize()
+    ran = {mm.group(1) + (mm.group(2) or "") for e in prof.key_averages() for mm in [KERNEL_RE.search(e.key)] if mm}
+    assert ran == {want}, "%s: ran %s, expected %s" % (what, sorted(ran), want)
+    assert tuple(out_t.shape) == tuple(m["out_shape"]), (what, tuple(out_t.shape))
+    # 2. the ctypes binding: bit-identical
+    with _Switches(case.get("sw"), "ctypes"):
+        out_c = _op(case, m, m["x"], m["res"])
+        torch.cuda.synchronize()
+    assert torch.equal(out_t.view(torch.int32), out_c.view(torch.int32)), "%s: the bindings differ" % what
+    del out_c
+    # 3. the C ABI on guarded buffers: nothing written outside the output, nothing read outside the input / residual
+    xb, xg, _ = _guarded(m["x_shape"], m["x"])
+    rg = _guarded(m["out_shape"], m["res"])[1] if m["res"] is not None else None
+    ob, og, (lo, hi) = _guarded(m["out_shape"])
+    with _Switches(case.get("sw"), "ctypes"):
+        status = _raw(case, m, xg, rg, og)
+        torch.cuda.synchronize()
+    assert status == 0, "%s: estd status %d" % (what, status)
+    assert _untouched(ob, lo, hi) == 0, "%s: written outside the output" % what
+    assert torch.equal(og.view(torch.int32), out_t.view(torch.int32)), "%s: the guarded launch differs from the op" % what
+    return out_t, ran
+
+
+def run_case(case, shapes=None, reserves=(None,)):
+    """all shapes of one case -> (worst ratio, the kernel instances that ran).  ``reserves``: run steps 1-3 once per
+    ops.set_reserved_cus value (None: the setting as it is); the outputs of all of them must be bit-identical."""
+    from estdepth_amd import ops
     worst, seen = 0.0, set()
     seed = sum(map(ord, case["id"]))
     big = case["id"].startswith(BIG_IDS) or case["id"].startswith("full-")
-    for shape in case["shapes"]:
+    for shape in case["shapes"] if shapes is None else shapes:
         shape = tuple(shape)
         m = _make(case, shape, seed + sum(shape))
         want = _expected_kernel(case, shape)
         what = "%s %s" % (case["id"], shape)
-        # 1. the torch binding, under the profiler
-        with _Switches(case.get("sw"), "torch"):
-            with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CUDA]) as prof:
-                out_t = _op(case, m, m["x"], m["res"])
-                torch.cuda.synchronize()
-        ran = {mm.group(1) + (mm.group(2) or "") for e in prof.key_averages() for mm in [KERNEL_RE.search(e.key)] if mm}
-        assert ran == {want}, "%s: ran %s, expected %s" % (what, sorted(ran), want)
-        seen |= ran
-        assert tuple(out_t.shape) == tuple(m["out_shape"]), (what, tuple(out_t.shape))
-        # 2. the ctypes binding: bit-identical
-        with _Switches(case.get("sw"), "ctypes"):
-            out_c = _op(case, m, m["x"], m["res"])
-            torch.cuda.synchronize()
-        assert torch.equal(out_t.view(torch.int32), out_c.view(torch.int32)), "%s: the bindings differ" % what
-        del out_c
-        # 3. the C ABI on guarded buffers: nothing written outside the output, nothing read outside the input / residual
-        xb, xg, _ = _guarded(m["x_shape"], m["x"])
-        rg = _guarded(m["out_shape"], m["res"])[1] if m["res"] is not None else None
-        ob, og, (lo, hi) = _guarded(m["out_shape"])
-        with _Switches(case.get("sw"), "ctypes"):
-            status = _raw(case, m, xg, rg, og)
-            torch.cuda.synchronize()
-        assert status == 0, "%s: estd status %d" % (what, status)
-        assert _untouched(ob, lo, hi) == 0, "%s: written outside the output" % what
-        assert torch.equal(og.view(torch.int32), out_t.view(torch.int32)), "%s: the guarded launch differs from the op" % what
-        del xb, xg, rg, ob, og
+        out_t = None
+        prev = ops.get_reserved_cus()
+        try:
+            for r in reserves:
+                if r is not None:
+                    assert ops.set_reserved_cus(r) == r
+                out_r, ran = _three_runs(case, m, want, what if r is None else "%s reserve %d" % (what, r))
+                seen |= ran
+                if out_t is None:
+                    out_t = out_r
+                else:
+                    assert torch.equal(out_t.view(torch.int32), out_r.view(torch.int32)), "%s: reserve %s changes the result" % (what, r)
+                del out_r
+        finally:
+            ops.set_reserved_cus(prev)
         # 4. the fp64 reference
         os_ = m["out_shape"]
         points = _sample_points(os_[0], *(os_[2:] if case["fam"] == "disp" else os_[1:3]), torch.Generator().manual_seed(seed)) if big else None
@@ -570,6 +609,22 @@ def test_conv2d_route_against_fp64(case):
         pytest.skip("ESTD_BUILD_AB=1 kernels are not in this build")
     ratio, kernels = run_case(case)
     print("ROUTE-RATIO %s %s %.3f %s" % (_route(kernels[0]), case["id"], ratio, " ".join(kernels)))
+
+
+@pytest.mark.parametrize("case", [c for c in PLAN_CASES if "many" in c] + RANGE_CASES, ids=lambda c: c["id"])
+def test_conv2d_plan_over_multi_item_ranges(case):
+    """every instance of conv2d_wino2 / conv2d_k3 on its many-item shape, all elements against the fp64 reference, under the full grid and
+    under set_reserved_cus(128): the same protocol per grid, and the two grids bit-identical"""
+    import tile_ranges_ref as TR
+    shape = (case["many"],) + MANY_HW
+    ratio, kernels = run_case(case, shapes=[shape], reserves=TR.RESERVES)
+    print("ROUTE-RATIO %s %s-ranges %.3f %s" % (_route(kernels[0]), case["id"], ratio, " ".join(kernels)))
+    if kernels[0].startswith(("conv2d_wino2_kernel", "conv2d_k3_kernel")):      # (ESTD_BUILD_AB=1: conv2d_wino_kernel takes plan-k3-nt2-d2-res)
+        cus = torch.cuda.get_device_properties(DEV).multi_processor_count
+        fam = TR.family2d(kernels[0], case["cout"])
+        counts = [TR.classes2d(fam, shape, case["cout"], cus, r) for r in TR.RESERVES]
+        print("TILE-RANGES %s %s" % (case["id"], " | ".join("G=%d len %d-%d same=%d image=%d group=%d" % (
+            c["G"], c["len_min"], c["len_max"], c["same_image"], c["next_image"], c["next_group"]) for c in counts)))
 
 
 # ------------------------------------------------------------------------------------------- forced configurations (child processes)

@@ -10,7 +10,9 @@ One case per (route, plan, activation, epilogue, strides, switches).  Each case
     sentinel, bit for bit;
   * runs small shapes at the tile edges of the kernels (8 x 16 tiles of the direct / Winograd kernels, 16 x 16 of the channel-32 pass and
     the stereo-head kernel, its 32-plane depth segments, the Winograd depth pairs), a full-size volume per route family and one batch whose
-    total size crosses 2^31 bytes (64-bit batch offsets; the reference then at sampled voxels only).
+    total size crosses 2^31 bytes (64-bit batch offsets; the reference then at sampled voxels only);
+  * runs every small-shape case again where each workgroup of the persistent grid walks a range of several tiles (thin columns, a large batch,
+    two grid sizes: test_conv3d_route_over_multi_tile_ranges).
 Both bindings launch from one wiring (ops.CONV3D_ROUTES): one small-shape case of every route, and the reset-gate cases, run under both and
 must agree bit for bit."""
 import re
@@ -20,20 +22,23 @@ import pytest
 import torch
 
 import conv3d_ref as R
+import tile_ranges_ref as TR
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 
 # per-element bound constants, in units of 2^-24 A: the worst ratio measured on an MI355X over every case and output of the route
 # (in the comments), times at least 3.  The Winograd routes sit BELOW the direct kernel: their transforms shorten the fp32 sums.
+# The many-tile cases added later (test_conv3d_route_over_multi_tile_ranges) are held to the same constants; their sums have the same 27 x cin
+# terms, their worst ratios (in brackets, over 2 x 90 k voxels per case instead of a few thousand) are the tail of the same distribution.
 C_ROUTE = {
-    "direct": 18.0,           # measured 5.79 (33 -> 33, out_main)
-    "wino3": 7.0,             # measured 2.25 (32 -> 32, out_main)
-    "wino2": 8.0,             # measured 2.47 (32 -> 32 + statistics, out_main)
-    "wino2_xout": 7.0,        # measured 2.16 (out_main; channel 32: 0.70)
-    "wino2_o16": 5.0,         # measured 1.63 (with statistics, out_main)
-    "wino2_c16": 2.0,         # measured 0.63 (head)
-    "wino3+xout": 7.0,        # measured 2.26 (out_main; channel 32: 0.93)
+    "direct": 18.0,           # measured 5.79 (33 -> 33, out_main) [6.43: 33 -> 32]
+    "wino3": 7.0,             # measured 2.25 (32 -> 32, out_main) [2.29: 33 -> 32]
+    "wino2": 8.0,             # measured 2.47 (32 -> 32 + statistics, out_main) [2.55]
+    "wino2_xout": 7.0,        # measured 2.16 (out_main; channel 32: 0.70) [3.15; channel 32: 0.91]
+    "wino2_o16": 5.0,         # measured 1.63 (with statistics, out_main) [1.83]
+    "wino2_c16": 2.0,         # measured 0.63 (head) [0.71]
+    "wino3+xout": 7.0,        # measured 2.26 (out_main; channel 32: 0.93) [2.33]
 }
 KERNELS = {
     "direct": {"conv3d_k3_kernel"},
@@ -267,17 +272,26 @@ def _finalize(bufs, dims):
     return ops.groupnorm_finalize(buf[lo:hi], (hi - lo) // 4, 16.0 * N * D * H * W)
 
 
-def _compare(case, pa, dims, x, kw, before, bufs, worst, what):
-    route = case["route"]
-    c = C_ROUTE[route]
-    N, D, H, W = dims
+def _reference(pa, dims, x, kw, before):
+    """the fp64 reference of one launch -> (conv3d_ref's dict, the sampled voxels or None)"""
     points = None
     if dims in FULL or dims in BIG:
         points = _sample_points(dims, torch.Generator().manual_seed(sum(dims)))
     ref_kw = dict(kw)
     if before is not None:
         ref_kw["out"] = before
-    ref = R.conv3d_ref(**pa, x=x, dims=dims, points=points, **ref_kw)
+    return R.conv3d_ref(**pa, x=x, dims=dims, points=points, **ref_kw), points
+
+
+def _compare(case, pa, dims, x, kw, before, bufs, worst, what):
+    _check(case, dims, _reference(pa, dims, x, kw, before), bufs, worst, what)
+
+
+def _check(case, dims, reference, bufs, worst, what):
+    route = case["route"]
+    c = C_ROUTE[route]
+    N, D, H, W = dims
+    ref, points = reference
     at = (lambda t: R._at(t, points)) if points is not None else (lambda t: t)     # noqa: E731
     for key in ("out", "extra", "head"):
         if key not in bufs:
@@ -324,3 +338,60 @@ def test_conv3d_route_against_fp64(case):
         del got
         torch.cuda.empty_cache()
     print("ROUTE-RATIO %s %s %s" % (case["route"], case["plan"], " ".join("%s=%.2f" % kv for kv in sorted(worst.items()))))
+
+
+def _written_blocks(bufs):
+    """the 4-double GroupNorm partial blocks a launch wrote completely (the rest keeps the sentinel)"""
+    buf, (lo, hi), _, _ = bufs["stats"]
+    return int((buf[lo:hi].view(torch.int64).view(-1, 4) != SENT64).all(1).sum())
+
+
+@pytest.mark.parametrize("case", [p for p in CASES if p.values[0]["shapes"] is SMALL])
+def test_conv3d_route_over_multi_tile_ranges(case, request):
+    """Every tile-edge case once more on the many-tile shapes of tests/tile_ranges_ref.py (thin columns, a large batch: ranges of 4-12 tiles
+    per workgroup with middle tiles, whole columns inside a range, ranges across batch elements and starts on the odd last depth pair),
+    under the full grid and under set_reserved_cus(128): every element of every output against one fp64 reference per shape, the same
+    bound, sentinel bands and kernel names, and the outputs of the two grids (and of both bindings, where the case runs both) bit-identical.
+    The GroupNorm partials are indexed by the canonical 8 x 16 tile (n, d, h-tile, w-tile), not by workgroup: each grid writes exactly
+    ops.conv3d_grid(...) blocks -- the direct kernel's tile count, which the model reproduces -- and the same bits."""
+    from estdepth_amd import ops
+    family = TR.ROUTE_FAMILY[case["route"]]
+    cus = torch.cuda.get_device_properties(DEV).multi_processor_count
+    seed = sum(map(ord, case["route"] + case["plan"]))
+    pa = _plan_args(case["plan"], case["acts"], seed)
+    plan = ops.Conv3dPlan(device=DEV, **pa)
+    worst = {}
+    prev = ops.get_reserved_cus()
+    try:
+        for dims in TR.ranges3d(family):
+            assert TR.geometry3d("direct", dims)[3] == ops.conv3d_grid(*dims), dims
+            counts = [TR.classes3d(family, dims, cus, r) for r in TR.RESERVES]
+            assert max(c["len_min"] for c in counts) >= 3 and counts[0]["G"] != counts[1]["G"], (dims, counts)
+            reference, x0, got = None, None, {}
+            for r in TR.RESERVES:
+                assert ops.set_reserved_cus(r) == r
+                for binding in ("torch", "ctypes") if case["both"] else ("torch",):
+                    kernels, x, kw, before, bufs = _launch(case, plan, dims, binding, seed + sum(dims))
+                    if reference is None:
+                        reference, x0 = _reference(pa, dims, x, kw, before), x
+                    assert torch.equal(x, x0)                                   # (one reference serves every launch of the shape)
+                    what = "%s/%s reserve %d" % (case["route"], binding, r)
+                    _check(case, dims, reference, bufs, worst, what)
+                    assert kernels == KERNELS[case["route"]], "%s %s: ran %s" % (what, dims, sorted(kernels))
+                    if "stats" in bufs:
+                        assert _written_blocks(bufs) == TR.geometry3d("direct", dims)[3], "%s %s: partial blocks written" % (what, dims)
+                    got[r, binding] = {k: v[0].clone() for k, v in bufs.items()}
+                    del x, kw, before, bufs
+            first = got.pop((TR.RESERVES[0], "torch"))
+            for key, other in got.items():
+                for k in first:
+                    assert torch.equal(first[k].view(torch.int8), other[k].view(torch.int8)), "%s differs on %s (%s)" % (key, k, dims)
+            print("TILE-RANGES %s %s %s" % (request.node.callspec.id, dims, " | ".join(
+                "G=%d len %d-%d middle=%d whole=%d cross_n=%d" % (c["G"], c["len_min"], c["len_max"], c["middle"], c["whole_inside"], c["cross_n"])
+                for c in counts)))
+            del got, first, reference, x0
+            torch.cuda.empty_cache()
+    finally:
+        ops.set_reserved_cus(prev)
+    print("ROUTE-RATIO %s %s ranges[%s] %s" % (case["route"], case["plan"], request.node.callspec.id,
+                                               " ".join("%s=%.2f" % kv for kv in sorted(worst.items()))))
