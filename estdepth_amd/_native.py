@@ -229,6 +229,8 @@ _SIGNATURES = {
                                                ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, c_stream]),
     "estd_tsdf_mesh_faces": (ctypes.c_int, [c_float_p, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_void_p,
                                             ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, c_stream]),
+    "estd_mesh_components": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p, c_stream]),
 }
 
 # the superseded A/B kernels: exported only by a library built with ESTD_BUILD_AB=1 (estdepth_amd/build.py)

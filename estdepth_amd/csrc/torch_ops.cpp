@@ -686,6 +686,31 @@ std::tuple<Tensor, Tensor, Tensor> tsdf_mesh_faces(const Tensor& volume, double 
     return {count, edge, quad};
 }
 
+// ------------------------------------------------------------------------------------------------ mesh components
+// a triangle list: int32 [F,3], contiguous, on a device
+static const int32_t* faces_ptr(const Tensor& t, const char* op, const char* name)
+{
+    TORCH_CHECK(t.defined() && t.is_cuda() && t.scalar_type() == at::kInt && t.dim() == 2 && t.size(1) == 3 && t.is_contiguous(),
+                op, ": ", name, " must be a contiguous int32 tensor [F,3] on a ROCm device");
+    return t.data_ptr<int32_t>();
+}
+
+// csrc/mesh/mesh_components.hip -> (label [V] int32, triangles [V] int32, invalid [1] int64 on the device)
+std::tuple<Tensor, Tensor, Tensor> mesh_components(const Tensor& faces, int64_t n_vertices)
+{
+    const char* op = "mesh_components";
+    const int32_t* f = faces_ptr(faces, op, "faces");
+    const OpScope scope(faces);
+    check_count(n_vertices, 0, 0x7fffffffLL, op, "n_vertices");
+    const int64_t n_faces = faces.size(0);
+    Tensor label = at::empty({n_vertices}, faces.options()), triangles = at::empty({n_vertices}, faces.options());
+    Tensor invalid = at::empty({1}, faces.options().dtype(at::kLong));
+    check_status(estd_mesh_components(n_faces ? f : nullptr, (long long)n_faces, (long long)n_vertices,
+                                      n_vertices ? label.data_ptr<int32_t>() : nullptr, n_vertices ? triangles.data_ptr<int32_t>() : nullptr,
+                                      reinterpret_cast<long long*>(invalid.data_ptr<int64_t>()), cur_stream()), "estd_mesh_components");
+    return {label, triangles, invalid};
+}
+
 // ------------------------------------------------------------------------------------------------ cross-view consistency
 // csrc/depth_consistency.hip: target [H,W] and 1..8 sources of the same size, mats: CPU float32 [S,2,12] (F_s, B_s: host values of the
 // launch arguments) -> (views, visible, depth, rel_err), each [H,W]
@@ -1271,6 +1296,7 @@ TORCH_LIBRARY(estdepth_hip, m)
     m.def("tsdf_mesh_vertices(Tensor volume, Tensor? color, float voxel_size, Tensor origin, float w_min, int capacity) -> "
           "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("tsdf_mesh_faces(Tensor volume, float w_min, int capacity) -> (Tensor, Tensor, Tensor)");
+    m.def("mesh_components(Tensor faces, int n_vertices) -> (Tensor, Tensor, Tensor)");
     m.def("tsdf_raycast_color(Tensor volume, Tensor color, Tensor mat, int H, int W, float t_min, float dt, int n_steps, float w_min) -> "
           "(Tensor, Tensor, Tensor, Tensor)");
     m.def("depth_consistency(Tensor target, Tensor[] sources, Tensor mats, float px_max, float rel_max, float z_near) -> "
@@ -1332,6 +1358,7 @@ TORCH_LIBRARY_IMPL(estdepth_hip, CUDA, m)
     m.impl("tsdf_edge_colors", tsdf_edge_colors);
     m.impl("tsdf_mesh_vertices", tsdf_mesh_vertices);
     m.impl("tsdf_mesh_faces", tsdf_mesh_faces);
+    m.impl("mesh_components", mesh_components);
     m.impl("tsdf_raycast_color", tsdf_raycast_color);
     m.impl("depth_consistency", depth_consistency);
     m.impl("cloud_cell_keys", cloud_cell_keys);

@@ -318,7 +318,7 @@ class TSDFVolume:
         write_ply(path, rec.numpy(), rgb)
         return rec.shape[0]
 
-    def extract_mesh(self, w_min=1.0):
+    def extract_mesh(self, w_min=1.0, min_component=0):
         """The fused surface as a triangle mesh by naive surface nets (csrc/mesh/tsdf_mesh.hip; the contract: include/estd_hip.h,
         estd_tsdf_mesh_vertices / estd_tsdf_mesh_faces): one vertex per cell whose eight corner voxels have weight >= ``w_min`` and differ
         in sign, one quad = two triangles per sign-changing voxel edge whose four cells are observed -> dict(xyz [V,3], normal [V,3] (towards
@@ -326,13 +326,16 @@ class TSDFVolume:
         int64, count = V) on the device, and ``color`` [V,3] for a colour volume.  Vertices come in ascending cell id, quads in ascending
         edge id (= 3 * voxel + axis, the ids of ``extract_points``) with their two triangles consecutive: the result is the same from
         call to call, bit for bit.  A vertex no face references is kept.  Both kernels count first, the outputs are allocated exactly.
-        Known limit: a cell that two separate sheets cross gets one vertex, so the sheets pinch together there."""
-        return sorted_mesh(ops.tsdf_mesh_vertices, ops.tsdf_mesh_faces, self.volume, self.color, self.voxel_size, self.origin, w_min)
+        Known limit: a cell that two separate sheets cross gets one vertex, so the sheets pinch together there.
+        ``min_component=N`` > 0 passes the mesh through ``filter_mesh(min_triangles=N)``: connected components of fewer than N triangles and
+        the unreferenced vertices are dropped, and the dict gains ``components`` and ``dropped``; with the default nothing more is launched."""
+        mesh = sorted_mesh(ops.tsdf_mesh_vertices, ops.tsdf_mesh_faces, self.volume, self.color, self.voxel_size, self.origin, w_min)
+        return filter_mesh(mesh, min_triangles=min_component) if min_component else mesh
 
-    def save_mesh(self, path, w_min=1.0, color_scale=1.0, color_offset=0.0):
-        """``extract_mesh`` as a binary little-endian PLY with normals and a face element (host side); colour as in ``save_ply``.
-        -> (vertices, triangles)"""
-        m = self.extract_mesh(w_min=w_min)
+    def save_mesh(self, path, w_min=1.0, color_scale=1.0, color_offset=0.0, min_component=0):
+        """``extract_mesh`` as a binary little-endian PLY with normals and a face element (host side); colour as in ``save_ply``;
+        ``min_component`` as in ``extract_mesh``.  -> (vertices, triangles)"""
+        m = self.extract_mesh(w_min=w_min, min_component=min_component)
         rec = torch.cat([m["xyz"], m["normal"]], 1).cpu().contiguous()
         rgb = None
         if self.color is not None:
@@ -448,6 +451,104 @@ def mesh_edge_stats(faces):
     used = int(torch.unique(f).shape[0])
     return dict(boundary=int((counts == 1).sum().item()), manifold=int((counts == 2).sum().item()), non_manifold=int((counts > 2).sum().item()),
                 euler=used - int(counts.shape[0]) + int(f.shape[0]))
+
+
+def _faces_arg(faces, what, device=None):
+    """the triangle list of ``mesh_components`` / ``filter_mesh``: a device tensor (int32 [F,3]) as it is, or a numpy integer array [F,3]
+    (e.g. from ``read_ply(faces=True)``), which is moved to ``device`` (default: the current ROCm device).  The rules a host array can be
+    held to are checked before anything touches a device."""
+    if isinstance(faces, np.ndarray):
+        if faces.ndim != 2 or faces.shape[1] != 3 or faces.dtype.kind not in "iu":
+            raise RuntimeError("%s: faces must be an integer array [F,3], got %s %s" % (what, faces.dtype, faces.shape))
+        if faces.size and (int(faces.min()) < -0x80000000 or int(faces.max()) > 0x7fffffff):
+            raise RuntimeError("%s: a face index does not fit int32" % what)
+        return torch.from_numpy(np.ascontiguousarray(faces, dtype=np.int32)).to(device if device is not None else "cuda")
+    if not isinstance(faces, torch.Tensor):
+        raise RuntimeError("%s: faces must be a device tensor or a numpy array [F,3], got %s" % (what, type(faces).__name__))
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise RuntimeError("%s: faces must be [F,3], got %s" % (what, tuple(faces.shape)))
+    if not faces.is_cuda:
+        raise RuntimeError("%s: a faces tensor must live on a ROCm device (a host array is passed as numpy); got %s" % (what, faces.device))
+    return faces.contiguous()
+
+
+def mesh_components(faces, n_vertices=None, device=None):
+    """The connected components of a triangle mesh (csrc/mesh/mesh_components.hip; the contract: include/estd_hip.h,
+    estd_mesh_components).  ``faces``: int32 [F,3] on the device, or a numpy integer array, which is moved to ``device``; ``n_vertices``:
+    default the largest index + 1.  -> dict(label [V] int32: the smallest vertex index of each vertex's component, roots [C] int64
+    ascending, triangles [C] int32 and vertices [C] int64: the size of the component of each root, count = C) on the device.  Components
+    are ordered by root; a vertex no face uses is a component of its own with 0 triangles.  A face that names a vertex outside
+    0..n_vertices-1 raises RuntimeError with the number of such faces."""
+    if n_vertices is not None and int(n_vertices) < 0:
+        raise RuntimeError("mesh_components: n_vertices must not be negative, got %r" % (n_vertices,))
+    faces = _faces_arg(faces, "mesh_components", device)
+    if n_vertices is None:
+        n_vertices = int(faces.max().item()) + 1 if faces.shape[0] else 0
+    label, triangles, invalid = ops.mesh_components(faces, int(n_vertices))
+    bad = int(invalid.item())
+    if bad:
+        raise RuntimeError("mesh_components: %d of %d faces name a vertex outside 0..%d" % (bad, faces.shape[0], int(n_vertices) - 1))
+    wide = label.to(torch.int64)
+    roots = torch.nonzero(wide == torch.arange(wide.shape[0], device=wide.device)).reshape(-1)
+    return dict(label=label, roots=roots, triangles=triangles[roots], vertices=torch.bincount(wide, minlength=wide.shape[0])[roots],
+                count=int(roots.shape[0]))
+
+
+PER_VERTEX = ("xyz", "normal", "weight", "cell", "color", "rgb")      # the entries of a mesh dict with one row per vertex
+
+
+def filter_mesh(mesh, min_triangles=1, keep_largest=None):
+    """``mesh`` (any dict with ``xyz`` [V,3] and ``faces`` [F,3]: what ``extract_mesh`` returns, or ``read_ply(faces=True)``) without its
+    small connected components: those with at least ``min_triangles`` triangles are kept, and with ``keep_largest=k`` only the k of them
+    with the most triangles (ties go to the smaller root).  -> a dict with the input's keys on the device: the per-vertex entries (xyz,
+    normal, weight, cell, color / rgb where present) filtered with their order kept, ``faces`` re-indexed (int32, order kept), ``edge``
+    (one id per quad = two consecutive triangles, which always share a component) filtered by quad, ``count`` = the new V,
+    ``components`` = the components kept and ``dropped`` = dict(vertices, faces, components: those with at least one triangle; a vertex
+    no face uses counts under vertices only).  The default ``min_triangles=1`` drops exactly the unreferenced vertices.  The labelling
+    is the kernels' (``mesh_components``); the compaction (a mask, a running sum, indexing) is torch glue as in ``sorted_mesh``."""
+    if not isinstance(mesh, dict) or mesh.get("xyz") is None or mesh.get("faces") is None:
+        raise RuntimeError("filter_mesh: the mesh must be a dict with 'xyz' and 'faces'")
+    if int(min_triangles) != min_triangles or min_triangles < 0:
+        raise RuntimeError("filter_mesh: min_triangles must be an integer that is not negative, got %r" % (min_triangles,))
+    if keep_largest is not None and (int(keep_largest) != keep_largest or keep_largest < 0):
+        raise RuntimeError("filter_mesh: keep_largest must be None or an integer that is not negative, got %r" % (keep_largest,))
+    n_v = int(mesh["xyz"].shape[0])
+    edge = mesh.get("edge")
+    if edge is not None and 2 * int(edge.shape[0]) != int(mesh["faces"].shape[0]):
+        raise RuntimeError("filter_mesh: %d edge ids for %d faces (one per two triangles expected)" % (edge.shape[0], mesh["faces"].shape[0]))
+    for k in PER_VERTEX:
+        if mesh.get(k) is not None and int(mesh[k].shape[0]) != n_v:
+            raise RuntimeError("filter_mesh: %s has %d rows for %d vertices" % (k, mesh[k].shape[0], n_v))
+    devs = [v.device for v in mesh.values() if isinstance(v, torch.Tensor) and v.is_cuda]
+    faces = _faces_arg(mesh["faces"], "filter_mesh", devs[0] if devs else None)
+    dev = faces.device
+    comp = mesh_components(faces, n_v)
+    with_faces = comp["triangles"] > 0
+    keep = with_faces & (comp["triangles"] >= int(min_triangles)) if min_triangles > 0 else torch.ones_like(with_faces)
+    if keep_largest is not None:
+        at = torch.nonzero(keep).reshape(-1)                                     # by ascending root: the stable sort settles ties that way
+        order = torch.sort(comp["triangles"][at].to(torch.int64), descending=True, stable=True)[1]
+        keep = torch.zeros_like(keep)
+        keep[at[order[:int(keep_largest)]]] = True
+    root_kept = torch.zeros(n_v, dtype=torch.bool, device=dev)
+    root_kept[comp["roots"][keep]] = True
+    v_mask = root_kept[comp["label"].to(torch.int64)]
+    new_index = torch.cumsum(v_mask, 0) - 1
+    f_mask = v_mask[faces[:, 0].to(torch.int64)]
+    out = {}
+    for k, v in mesh.items():
+        if k in PER_VERTEX and v is not None:
+            out[k] = (torch.from_numpy(np.ascontiguousarray(v)) if isinstance(v, np.ndarray) else v).to(dev)[v_mask]
+        else:
+            out[k] = v
+    out["faces"] = new_index[faces[f_mask].to(torch.int64)].to(torch.int32)
+    if edge is not None:
+        out["edge"] = (torch.from_numpy(np.ascontiguousarray(edge)) if isinstance(edge, np.ndarray) else edge).to(dev)[f_mask[0::2]]
+    out["count"] = int(v_mask.sum().item())
+    out["components"] = int(keep.sum().item())
+    out["dropped"] = dict(vertices=n_v - out["count"], faces=int(faces.shape[0] - out["faces"].shape[0]),
+                          components=int((with_faces & ~keep).sum().item()))
+    return out
 
 
 def write_ply(path, xyz_normal, rgb=None, faces=None):

@@ -1318,6 +1318,35 @@ def tsdf_mesh_faces(volume, w_min, capacity):
     return count, edge, quad
 
 
+# ---------------------------------------------------------------------------------- mesh components (csrc/mesh/mesh_components.hip)
+def _faces(t, op, name):
+    """a triangle list: int32 [F,3], contiguous, on a device -> F"""
+    _need(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.dim() == 2 and t.shape[1] == 3 and t.is_contiguous(),
+          "%s: %s must be a contiguous int32 tensor [F,3] on a ROCm device" % (op, name))
+    return t.shape[0]
+
+
+def mesh_components(faces, n_vertices):
+    """The connected components of the triangles ``faces`` [F,3] int32 over ``n_vertices`` vertices -> (label [V] int32: the smallest
+    vertex index of the vertex's component, triangles [V] int32: at a root the component's triangles, 0 elsewhere, invalid [1] int64 on
+    the device: the triangles with an index outside [0, V), which are ignored).  include/estd_hip.h, estd_mesh_components."""
+    n_vertices = int(n_vertices)
+    if _use_torch():
+        return tuple(T().mesh_components(faces, n_vertices))
+    op = "mesh_components"
+    n_faces = _faces(faces, op, "faces")
+    _count(n_vertices, 0, 0x7fffffff, op, "n_vertices")
+    dev = faces.device
+    with torch.cuda.device(dev):
+        label = torch.empty(n_vertices, device=dev, dtype=torch.int32)
+        triangles = torch.empty(n_vertices, device=dev, dtype=torch.int32)
+        invalid = torch.empty(1, device=dev, dtype=torch.int64)
+        pp = (lambda t: _p(t)) if n_vertices else (lambda t: None)
+        N.check(N.lib().estd_mesh_components(_p(faces) if n_faces else None, n_faces, n_vertices, pp(label), pp(triangles), _p(invalid), _stream()),
+                "estd_mesh_components")
+    return label, triangles, invalid
+
+
 # ---------------------------------------------------------------------------------- cross-view consistency (csrc/depth_consistency.hip)
 CONSISTENCY_MAX_SOURCES = N.CONSISTENCY_MAX_SOURCES
 

@@ -766,6 +766,26 @@ int estd_tsdf_mesh_vertices(const float* tsdf, const float* weight, const float*
 int estd_tsdf_mesh_faces(const float* tsdf, const float* weight, int Z, int Y, int X, float w_min, unsigned long long* counter,
                          long long capacity, long long* edge, int* quad, estd_stream_t stream);
 
+/* The connected components of a triangle mesh (csrc/mesh/mesh_components.hip; numpy form: tests/mesh_components_ref.py): a lock-free
+ * union-find over all workgroups, every output defined to the integer and independent of the order of the faces and of scheduling.
+ *
+ * Input.  faces [n_faces][3] int32, contiguous: vertex indices; n_vertices = V.  Two vertices are in one component when a chain of
+ *   triangles links them; a triangle links its three vertices.  A triangle with repeated indices is a triangle like any other.
+ *   A triangle with an index outside [0, V) is INVALID: it is ignored entirely -- its indices are never used as an address, it links
+ *   nothing and is counted in `invalid` only.
+ * Outputs (all device memory).
+ *   label [V] int32: label[v] = the smallest vertex index of v's component; a vertex in no (valid) triangle has label[v] = v.  While the
+ *     call runs the array is the parent forest of the union-find; no other scratch is needed.
+ *   triangles [V] int32: at a root (label[r] == r) the number of valid triangles whose vertices carry label r, 0 everywhere else.
+ *   invalid [1] int64: the number of invalid triangles.  Always written (the caller need not zero it).
+ * Launches.  mesh_cc_init_kernel always (it defines label, triangles and invalid when there are no faces or no vertices); with V > 0
+ *   and n_faces > 0 also mesh_cc_hook_kernel, mesh_cc_flatten_kernel and mesh_cc_count_kernel, in this order on `stream`.  The count
+ *   uses integer atomics only, one per wave and distinct root.
+ * ESTD_ERR_ARG (before any launch): n_faces < 0 or n_vertices < 0, a null `invalid`, a null `faces` with n_faces > 0, a null `label` or
+ *   `triangles` with n_vertices > 0.  ESTD_ERR_UNSUPPORTED: n_vertices or 3 * n_faces beyond 2^31 - 1. */
+int estd_mesh_components(const int* faces, long long n_faces, long long n_vertices, int* label, int* triangles, long long* invalid,
+                         estd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,10 @@ ground-truth depth.  Needs an MI355X (the model has no CPU path).
     python tools/run_stream.py --synthetic 8 --out /tmp/eval --fuse /tmp/eval/scene.ply --mesh /tmp/eval/scene_mesh.ply
         # + the fused surface as a triangle mesh (TSDFVolume.save_mesh: surface nets; red / green / blue with --color) and a "mesh" block in
         # metrics.json: vertices, faces and the mesh edges shared by one / two / more than two triangles
+    python tools/run_stream.py --synthetic 8 --out /tmp/eval --fuse /tmp/eval/scene.ply --mesh /tmp/eval/scene_mesh.ply --mesh-min-component 100
+        # + the mesh without its floaters: connected components of fewer than 100 triangles and the vertices no face uses are dropped
+        # (fusion3d.filter_mesh over the GPU union-find of csrc/mesh/mesh_components.hip) before the file is written and the edges are
+        # counted; the "mesh" block gains components, components_kept, vertices_dropped and faces_dropped
     python tools/run_stream.py --synthetic 8 --out /tmp/eval --fuse /tmp/eval/scene.ply --render-fused
         # + the fused volume ray-cast at every target's pose (TSDFVolume.render): <out>/fused_depth/*.npy beside refined_depth/ (float16,
         # same layout) and the fused depth scored against the same ground truth (errors_fused, fused_coverage, errors_on_covered)
@@ -110,6 +114,8 @@ def parse(argv=None):
                                                        "(estdepth_amd.fusion3d) and write its surface points here")
     ap.add_argument("--mesh", metavar="MESH.ply", help="with --fuse: also write the fused surface as a triangle mesh (TSDFVolume.save_mesh; "
                     "with --color the vertices get red / green / blue) and report its size and edge statistics")
+    ap.add_argument("--mesh-min-component", type=int, metavar="N", help="with --mesh: drop the connected components of fewer than N triangles "
+                    "and the vertices no face uses (fusion3d.filter_mesh) before the mesh is written and its edges are counted")
     ap.add_argument("--render-fused", action="store_true", help="with --fuse: after the stream, render the volume at every target's pose, "
                     "write the fused depth maps to <out>/fused_depth and score them against the ground truth")
     ap.add_argument("--color", action="store_true", help="with --fuse: fuse every target's frame (the reader's 0..255 RGB, whatever the model is "
@@ -140,6 +146,10 @@ def parse(argv=None):
         ap.error("--render-fused needs --fuse PATH.ply")
     if args.mesh and not args.fuse:
         ap.error("--mesh needs --fuse PATH.ply")
+    if args.mesh_min_component is not None and not args.mesh:
+        ap.error("--mesh-min-component needs --mesh MESH.ply")
+    if args.mesh_min_component is not None and args.mesh_min_component < 1:
+        ap.error("--mesh-min-component must be at least 1")
     if args.color and not args.fuse:
         ap.error("--color needs --fuse PATH.ply")
     if args.score_3d is not None and not args.fuse:
@@ -324,10 +334,14 @@ def run(args):
     if volume is not None and args.mesh:
         from estdepth_amd.fusion3d import mesh_edge_stats
         os.makedirs(os.path.dirname(os.path.abspath(args.mesh)), exist_ok=True)
-        n_vertices, n_faces = volume.save_mesh(args.mesh)
-        stats = mesh_edge_stats(volume.extract_mesh()["faces"])
+        n_vertices, n_faces = volume.save_mesh(args.mesh, min_component=args.mesh_min_component or 0)
+        mesh = volume.extract_mesh(min_component=args.mesh_min_component or 0)
+        stats = mesh_edge_stats(mesh["faces"])
         report["mesh"] = {"path": args.mesh, "vertices": n_vertices, "faces": n_faces, "boundary_edges": stats["boundary"],
                           "manifold_edges": stats["manifold"], "non_manifold_edges": stats["non_manifold"]}
+        if args.mesh_min_component is not None:       # the file and the edge statistics above are the filtered mesh's
+            report["mesh"].update(components=mesh["components"] + mesh["dropped"]["components"], components_kept=mesh["components"],
+                                  vertices_dropped=mesh["dropped"]["vertices"], faces_dropped=mesh["dropped"]["faces"])
     if args.track and volume is not None:
         report["tracking"] = {"frames": tracked, "dist_max": args.track_dist if args.track_dist is not None else volume.trunc,
                               "max_iter": args.track_iters, "mean_track_ms": float(np.mean(track_ms[1:] or track_ms or [0.0]))}

@@ -26,7 +26,14 @@ from the held-out pose.  The two plain figures are the ones to hold against anot
 
 times TSDFVolume.extract_mesh (csrc/mesh/tsdf_mesh.hip: surface nets) on the 256^3 volume after the T = 3 fuse, beside extract_points:
 the four kernel launches (cells and faces, each counting and then filling) and the host ordering behind them (two sorts, the binary
-search of the cell ids, the triangle split) separately, each between device events, and the whole call with its two count read-backs."""
+search of the cell ids, the triangle split) separately, each between device events, and the whole call with its two count read-backs.
+
+    python tools/tsdf_bench.py --mesh-components [--reps 100] [--out profiles/mesh_components_bench.txt]
+
+times the connected components of that mesh (csrc/mesh/mesh_components.hip) and fusion3d.filter_mesh: the operator (its four launches)
+and the whole filter between device events, each call behind the cache flush, the four kernels one by one from the profiler's device
+times over the same calls, beside the yardstick -- the same labels by scipy.sparse.csgraph.connected_components on the host, the copies
+included, or where scipy is missing a min-label propagation loop in torch on the device."""
 import argparse
 import os
 import sys
@@ -66,12 +73,15 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--raycast", action="store_true", help="time the ray caster (csrc/tsdf_raycast.hip) instead of integrate / extract")
     ap.add_argument("--mesh", action="store_true", help="time extract_mesh (kernels and host ordering apart) beside extract_points")
+    ap.add_argument("--mesh-components", action="store_true", help="time the mesh components and filter_mesh beside a host / torch yardstick")
     ap.add_argument("--color", action="store_true", help="time the colour fuse, the edge colours and the colour render beside the plain figures")
     args = ap.parse_args()
     if args.raycast:
         return raycast_main(args)
     if args.mesh:
         return mesh_main(args)
+    if args.mesh_components:
+        return components_main(args)
     if args.color:
         return color_main(args)
     import tsdf_ref as R
@@ -177,6 +187,114 @@ def mesh_main(args):
              "  extract_mesh, whole call                           %8.3f ms after a cache flush, %.3f ms back to back (two count read-backs included)"
              % (t_all, t_all_warm),
              "  every kernel figure: a 1 GiB buffer is rewritten (untimed) in front of the call, so the volume comes from HBM"]
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        open(args.out, "w").write(text + "\n")
+
+
+def components_main(args):
+    import re
+    import time
+    import tsdf_ref as R
+    from estdepth_amd import ops
+    from estdepth_amd.fusion3d import TSDFVolume, filter_mesh, frustum_volume
+    assert torch.cuda.is_available(), "tools/tsdf_bench.py needs a ROCm device"
+    dev = torch.device("cuda:0")
+    H, W, T, vox, dmin, dmax, dims = 480, 640, 3, 0.03, 0.1, 10.0, (256, 256, 256)
+    reps = min(args.reps, 100)
+    K = R.intrinsics(H, W)
+    poses = R.scene_poses(T, seed=1)
+    depths = torch.from_numpy(np.stack([R.raycast_scene(P, K, H, W) for P in poses]).astype(np.float32)).to(dev)
+    flush = torch.empty(256 << 20, device=dev)          # 1 GiB
+    origin = frustum_volume(torch.from_numpy(poses[0]), torch.from_numpy(K), (H, W), dmin, dmax, dims, vox)
+    vol = TSDFVolume(dims, vox, origin, device=dev)
+    vol.integrate(depths, torch.from_numpy(poses), torch.from_numpy(K))
+    m = vol.extract_mesh()
+    faces, n_v = m["faces"].contiguous(), m["count"]
+    label, triangles, _ = ops.mesh_components(faces, n_v)
+    roots = torch.nonzero(label == torch.arange(n_v, device=dev, dtype=torch.int32)).reshape(-1)
+    sizes = torch.sort(triangles[roots], descending=True)[0]
+    n_big = int((sizes >= 100).sum().item())
+    t_op = timed(lambda: ops.mesh_components(faces, n_v), reps, flush)
+    t_op_warm = timed(lambda: ops.mesh_components(faces, n_v), reps)
+    t_filter = timed(lambda: filter_mesh(m, min_triangles=100), reps, flush)
+    t_extract = timed(lambda: vol.extract_mesh(), reps, flush)
+    # the four kernels one by one: the profiler's device time over the same flushed calls (one entry point launches all four)
+    def kernel_times(f, v):
+        with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CUDA]) as prof:
+            for i in range(reps):
+                flush.fill_(float(i))
+                ops.mesh_components(f, v)
+            torch.cuda.synchronize()
+        out = {}
+        for e in prof.key_averages():
+            k = re.search(r"mesh_cc_\w+_kernel", e.key)
+            if k:
+                out[k.group(0)] = (getattr(e, "device_time_total", None) or getattr(e, "cuda_time_total", 0.0)) / max(e.count, 1) / 1e3
+        return out
+    per_kernel = kernel_times(faces, n_v)
+    # a mesh large enough to fill the device: the 204 800-triangle grid of the tests, five islands, vertex ids permuted, faces shuffled
+    import mesh_components_ref as C
+    grid_np, grid_v = C.build_case("grid-320")
+    grid = torch.from_numpy(grid_np.copy()).to(dev)
+    assert np.array_equal(ops.mesh_components(grid, grid_v)[0].cpu().numpy(), C.reference("grid-320")["label"])
+    t_grid = timed(lambda: ops.mesh_components(grid, grid_v), reps, flush)
+    grid_kernels = kernel_times(grid, grid_v)
+    # the yardstick
+    want = label.cpu().numpy()
+    try:
+        from scipy.sparse import coo_matrix
+        from scipy.sparse.csgraph import connected_components
+
+        def yard():
+            f = faces.cpu().numpy().astype(np.int64)
+            g = coo_matrix((np.ones(2 * f.shape[0], np.int8), (np.r_[f[:, 0], f[:, 0]], np.r_[f[:, 1], f[:, 2]])), shape=(n_v, n_v))
+            lab = connected_components(g, directed=False)[1]
+            smallest = np.full(int(lab.max()) + 1 if n_v else 0, n_v, np.int64)
+            np.minimum.at(smallest, lab, np.arange(n_v))
+            return torch.from_numpy(smallest[lab].astype(np.int32)).to(dev)
+        yard_name = "scipy.sparse.csgraph.connected_components on the host, with the copy of the faces down and of the labels up"
+    except ImportError:
+        def yard():
+            f = faces.to(torch.int64)
+            lab = torch.arange(n_v, device=dev)
+            while True:
+                best = lab[f].min(1).values
+                new = lab.clone()
+                for k in range(3):
+                    new.scatter_reduce_(0, f[:, k], best, "amin")
+                new = new[new]
+                if torch.equal(new, lab):
+                    return lab.to(torch.int32)
+                lab = new
+        yard_name = "a min-label propagation loop in torch on the device (scipy is not installed)"
+    assert np.array_equal(yard().cpu().numpy(), want), "the yardstick and the kernels disagree"
+    torch.cuda.synchronize()
+    n_yard = 5
+    t0 = time.perf_counter()
+    for _ in range(n_yard):
+        yard()
+        torch.cuda.synchronize()
+    t_yard = (time.perf_counter() - t0) / n_yard * 1e3
+    lines = ["tsdf_bench --mesh-components: %d x %d maps, T = %d, voxel %.3f m, mean of %d calls per figure, %s" % (W, H, T, vox, reps, torch.cuda.get_device_name(0)),
+             "volume %d x %d x %d (Z Y X): mesh of %d vertices, %d triangles; %d components with faces (largest: %s triangles), %d of them with at "
+             "least 100 triangles, %d vertices no face uses" % (dims + (n_v, faces.shape[0], int((sizes > 0).sum().item()),
+                                                                " / ".join(str(int(x)) for x in sizes[:4].tolist()), n_big, int((sizes == 0).sum().item())))]
+    for k in ("mesh_cc_init_kernel", "mesh_cc_hook_kernel", "mesh_cc_flatten_kernel", "mesh_cc_count_kernel"):
+        lines.append("  %-26s %8.4f ms (profiler device time, mean of %d)" % (k, per_kernel.get(k, float("nan")), reps))
+    lines += ["  mesh_components operator   %8.4f ms between device events after a cache flush (four launches, three allocations), %.4f ms back to back"
+              % (t_op, t_op_warm),
+              "  filter_mesh, whole call    %8.4f ms after a cache flush (operator + torch glue: roots, bincount, masks, cumsum, re-indexing; read-backs included)" % t_filter,
+              "  extract_mesh beside it     %8.4f ms after a cache flush (the call the filter follows)" % t_extract,
+              "  yardstick                  %8.3f ms: %s (wall clock, mean of %d); operator / yardstick = 1 / %.0f"
+              % (t_yard, yard_name, n_yard, t_yard / t_op),
+              "  a larger mesh, the permuted and shuffled grid of tests/mesh_components_ref.py (%d triangles, %d vertices, 5 components): operator "
+              "%.4f ms after a cache flush; %s" % (grid.shape[0], grid_v, t_grid, ", ".join(
+                  "%s %.4f" % (k[8:-7], grid_kernels.get(k, float("nan"))) for k in ("mesh_cc_init_kernel", "mesh_cc_hook_kernel",
+                                                                                    "mesh_cc_flatten_kernel", "mesh_cc_count_kernel"))),
+              "  the labels of the yardstick and of the kernels are equal; no bar is set (the parent has nothing comparable)"]
     text = "\n".join(lines)
     print(text)
     if args.out:
