@@ -231,6 +231,11 @@ _SIGNATURES = {
                                             ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, c_stream]),
     "estd_mesh_components": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.c_void_p, c_stream]),
+    "estd_mesh_face_area": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_void_p, c_stream]),
+    "estd_mesh_sample": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
+                                        ctypes.c_ulonglong] + [ctypes.c_void_p] * 5 + [c_stream]),
 }
 
 # the superseded A/B kernels: exported only by a library built with ESTD_BUILD_AB=1 (estdepth_amd/build.py)

@@ -241,3 +241,33 @@ def compare_clouds(pred, gt, threshold=0.05, max_dist=None, downsample=None, pre
                          pairs(attrs["gt_color"], attrs["pred_color"], d_gp, i_gp, l1, near)) if x is not None]
         out["color_l1"] = sum(v) / len(v) if v else 0.0
     return out
+
+
+def compare_meshes(pred, gt, density, threshold=0.05, max_dist=None, downsample=None, seed=0, cell=None):
+    """The 3D scores of the SURFACE ``pred`` against the surface ``gt``: both triangle meshes (dicts with ``xyz`` and ``faces``: what
+    ``extract_mesh``, ``filter_mesh`` or ``read_ply(faces=True)`` return) are sampled by area at ``density`` points per square metre
+    (``fusion3d.sample_mesh``, face normals), and the two clouds go to ``compare_clouds`` unchanged -> its dict plus ``sampled`` =
+    dict(density, n_pred, n_gt, area_pred, area_gt, invalid_pred, invalid_gt).  A side without ``faces`` is a plain cloud (``xyz``,
+    optionally ``normal`` / ``color``) and is used as it is: its area is None.  A decimated mesh -- a wall as two triangles -- then counts
+    by its area, not by its vertices, and the distance to it is the distance to its surface, not to its nearest corner."""
+    _need(isinstance(density, (int, float)) and math.isfinite(density) and density > 0, "compare_meshes: density must be positive and finite, got %r" % (density,))
+    from . import fusion3d
+    _need(all(isinstance(x, dict) and x.get("xyz") is not None for x in (pred, gt)), "compare_meshes: pred and gt must be dicts with 'xyz'")
+    devs = [v.device for x in (pred, gt) for v in x.values() if isinstance(v, torch.Tensor) and v.is_cuda]
+    dev = devs[0] if devs else torch.device("cuda")
+
+    def side(x):
+        if x.get("faces") is not None:
+            s = fusion3d.sample_mesh(x, density=density, seed=seed)
+            return s, s["total"], s["invalid"]
+        color = x.get("color") if x.get("color") is not None else x.get("rgb")
+        out = {k: fusion3d._on_device(v, dev) for k, v in (("xyz", x["xyz"]), ("normal", x.get("normal")), ("color", color)) if v is not None}
+        return out, None, 0
+    (a, area_a, bad_a), (b, area_b, bad_b) = side(pred), side(gt)
+    both = lambda k: k in a and k in b
+    out = compare_clouds(a["xyz"], b["xyz"], threshold=threshold, max_dist=max_dist, downsample=downsample,
+                         pred_normal=a["normal"] if both("normal") else None, gt_normal=b["normal"] if both("normal") else None,
+                         pred_color=a["color"] if both("color") else None, gt_color=b["color"] if both("color") else None, cell=cell)
+    out["sampled"] = dict(density=float(density), n_pred=int(a["xyz"].shape[0]), n_gt=int(b["xyz"].shape[0]), area_pred=area_a, area_gt=area_b,
+                          invalid_pred=bad_a, invalid_gt=bad_b)
+    return out

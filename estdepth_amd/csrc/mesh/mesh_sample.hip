@@ -1,0 +1,163 @@
+// mesh_sample.hip -- an evenly spread point cloud on a triangle mesh: per-triangle areas in float64, then stratified (systematic) sampling
+// along the cumulative area.  The contract: include/estd_hip.h (estd_mesh_face_area, estd_mesh_sample); its numpy form:
+// tests/mesh_sample_ref.py.  Between the two kernels the host layer (estdepth_amd/ops.py, mesh_sample) quantises the areas with a power
+// of two and forms their int64 prefix sums `cum`: given the bits of `area`, everything after it is integer arithmetic.
+//
+// Two launches, 256 lanes per workgroup, 64-bit offsets throughout:
+//   mesh_face_area_kernel  one lane per triangle: area = 0.5 |(b - a) x (c - a)| in float64 (uncontracted, in the order the header
+//                          states), the unit normal rounded once to fp32; a triangle with an index outside [0, V) gets area +0 and is
+//                          counted in `invalid` -- one integer atomic add per wave (ballot + population count), no float atomics
+//   mesh_sample_kernel     one lane per sample i: the target t_i = i w + (h64(seed, i, 0) mod w), its triangle = the first f with
+//                          cum[f] > t_i (an upper-bound search over the prefix sums), the barycentric pair from two more streams of the
+//                          mixer, position and attributes by two fmas each
+//
+// The mixer is counter based and holds no state: sample i is a function of (seed, i) and the mesh alone, whatever the launch shape.
+#include "../estd_common.h"
+
+namespace {
+
+constexpr int WG = 256;
+
+__device__ __forceinline__ bool in_range(int i, int V) { return (unsigned)i < (unsigned)V; }
+
+// the finaliser of SplitMix64 (Steele, Lea, Flood 2014)
+__device__ __forceinline__ unsigned long long mix64(unsigned long long z)
+{
+    z ^= z >> 30;
+    z *= 0xbf58476d1ce4e5b9ull;
+    z ^= z >> 27;
+    z *= 0x94d049bb133111ebull;
+    z ^= z >> 31;
+    return z;
+}
+
+// two rounds over (seed, i, stream), all arithmetic modulo 2^64; h32 is the upper half
+__device__ __forceinline__ unsigned long long h64(unsigned long long seed, unsigned long long i, unsigned long long stream)
+{
+    return mix64(mix64(seed + (i + 1ull) * 0x9e3779b97f4a7c15ull) + (stream + 1ull) * 0xd1b54a32d192ed03ull);
+}
+
+__global__ __launch_bounds__(WG) void mesh_face_area_kernel(const float* xyz, int V, const int* faces, long long F, double* area,
+                                                            float* face_normal, unsigned long long* invalid)
+{
+#pragma clang fp contract(off)
+    const int lane = (int)threadIdx.x & 63;
+    const long long f = (long long)blockIdx.x * WG + threadIdx.x;
+    bool bad = false;
+    if (f < F) {
+        const int v0 = faces[3 * f], v1 = faces[3 * f + 1], v2 = faces[3 * f + 2];
+        double A = 0.0;
+        float n0 = 0.f, n1 = 0.f, n2 = 0.f;
+        if (in_range(v0, V) && in_range(v1, V) && in_range(v2, V)) {
+            const float* a = xyz + 3ll * v0;
+            const float* b = xyz + 3ll * v1;
+            const float* c = xyz + 3ll * v2;
+            const double ax = a[0], ay = a[1], az = a[2];
+            const double e1x = (double)b[0] - ax, e1y = (double)b[1] - ay, e1z = (double)b[2] - az;
+            const double e2x = (double)c[0] - ax, e2y = (double)c[1] - ay, e2z = (double)c[2] - az;
+            const double nx = e1y * e2z - e1z * e2y;
+            const double ny = e1z * e2x - e1x * e2z;
+            const double nz = e1x * e2y - e1y * e2x;
+            const double len = sqrt((nx * nx + ny * ny) + nz * nz);
+            A = 0.5 * len;
+            if (len > 0.0) {
+                n0 = (float)(nx / len);
+                n1 = (float)(ny / len);
+                n2 = (float)(nz / len);
+            }
+        } else {
+            bad = true;                                                         // never an address
+        }
+        area[f] = A;
+        face_normal[3 * f] = n0;
+        face_normal[3 * f + 1] = n1;
+        face_normal[3 * f + 2] = n2;
+    }
+    const unsigned long long b_bad = __ballot(bad);
+    if (b_bad != 0ull && lane == 0) atomicAdd(invalid, (unsigned long long)__popcll(b_bad));
+}
+
+__global__ __launch_bounds__(WG) void mesh_sample_kernel(const float* xyz, int V, const int* faces, long long F, const float* attrs, int C,
+                                                         const long long* cum, const float* face_normal, long long n, long long first,
+                                                         long long w, unsigned long long seed, float* out_xyz, int* out_face,
+                                                         float* out_bary, float* out_normal, float* out_attrs)
+{
+    const long long j = (long long)blockIdx.x * WG + threadIdx.x;
+    if (j >= n) return;
+    const unsigned long long i = (unsigned long long)(first + j);
+    const long long t = (long long)(i * (unsigned long long)w + h64(seed, i, 0ull) % (unsigned long long)w);
+    // the first f with cum[f] > t.  The host layer guarantees t < cum[F - 1]; a foreign caller's prefix sums may not, hence the clamp.
+    long long lo = 0, len = F;
+    while (len > 0) {
+        const long long half = len >> 1;
+        if (cum[lo + half] <= t) {
+            lo += half + 1;
+            len -= half + 1;
+        } else {
+            len = half;
+        }
+    }
+    const long long f = lo < F ? lo : F - 1;
+    // the fold in integers: iu + iv > 2^24 <=> u + v > 1, and 2^24 - iu is 1 - u exactly
+    unsigned iu = (unsigned)(h64(seed, i, 1ull) >> 40), iv = (unsigned)(h64(seed, i, 2ull) >> 40);
+    if (iu + iv > (1u << 24)) {
+        iu = (1u << 24) - iu;
+        iv = (1u << 24) - iv;
+    }
+    const float u = (float)iu * 0x1p-24f, v = (float)iv * 0x1p-24f;
+    const int v0 = faces[3 * f], v1 = faces[3 * f + 1], v2 = faces[3 * f + 2];
+    const bool ok = in_range(v0, V) && in_range(v1, V) && in_range(v2, V);     // false only for prefix sums that are not this mesh's
+    out_face[j] = ok ? (int)f : -1;
+    out_bary[2 * j] = u;
+    out_bary[2 * j + 1] = v;
+    for (int k = 0; k < 3; ++k) {
+        float p = 0.f;
+        if (ok) {
+            const float a = xyz[3ll * v0 + k], b = xyz[3ll * v1 + k], c = xyz[3ll * v2 + k];
+            p = fmaf(v, c - a, fmaf(u, b - a, a));
+        }
+        out_xyz[3 * j + k] = p;
+        out_normal[3 * j + k] = ok ? face_normal[3 * f + k] : 0.f;
+    }
+    for (int k = 0; k < C; ++k) {
+        float p = 0.f;
+        if (ok) {
+            const float a = attrs[(long long)C * v0 + k], b = attrs[(long long)C * v1 + k], c = attrs[(long long)C * v2 + k];
+            p = fmaf(v, c - a, fmaf(u, b - a, a));
+        }
+        out_attrs[(long long)C * j + k] = p;
+    }
+}
+
+}  // namespace
+
+extern "C" int estd_mesh_face_area(const float* xyz, long long n_vertices, const int* faces, long long n_faces, double* area,
+                                   float* face_normal, long long* invalid, estd_stream_t s)
+{
+    if (n_faces < 0 || n_vertices < 0 || !invalid) return ESTD_ERR_ARG;
+    if ((n_vertices > 0 && !xyz) || (n_faces > 0 && (!faces || !area || !face_normal))) return ESTD_ERR_ARG;
+    if (n_vertices > 0x7fffffffLL || n_faces > 0x7fffffffLL / 3) return ESTD_ERR_UNSUPPORTED;
+    if (hipMemsetAsync(invalid, 0, sizeof(long long), estd_stream(s)) != hipSuccess) return ESTD_ERR_LAUNCH;
+    if (n_faces > 0)
+        hipLaunchKernelGGL(mesh_face_area_kernel, dim3((unsigned)((n_faces + WG - 1) / WG)), dim3(WG), 0, estd_stream(s), xyz, (int)n_vertices,
+                           faces, n_faces, area, face_normal, reinterpret_cast<unsigned long long*>(invalid));
+    return ESTD_LAUNCH_CHECK();
+}
+
+extern "C" int estd_mesh_sample(const float* xyz, long long n_vertices, const int* faces, long long n_faces, const float* attrs, int C,
+                                const long long* cum, const float* face_normal, long long n_samples, long long first, long long w,
+                                unsigned long long seed, float* out_xyz, int* out_face, float* out_bary, float* out_normal, float* out_attrs,
+                                estd_stream_t s)
+{
+    if (n_faces < 0 || n_vertices < 0 || n_samples < 0 || first < 0 || C < 0 || C > ESTD_CLOUD_MAX_ATTRS) return ESTD_ERR_ARG;
+    if (n_vertices > 0x7fffffffLL || n_faces > 0x7fffffffLL / 3 || n_samples > 0x7fffffffLL || first > 0x7fffffffLL - n_samples)
+        return ESTD_ERR_UNSUPPORTED;
+    if (n_samples == 0) return ESTD_OK;
+    if (n_faces == 0 || n_vertices == 0 || w < 1 || w > (1LL << 62) / (first + n_samples)) return ESTD_ERR_ARG;
+    if (!xyz || !faces || !cum || !face_normal || !out_xyz || !out_face || !out_bary || !out_normal) return ESTD_ERR_ARG;
+    if (C > 0 && (!attrs || !out_attrs)) return ESTD_ERR_ARG;
+    hipLaunchKernelGGL(mesh_sample_kernel, dim3((unsigned)((n_samples + WG - 1) / WG)), dim3(WG), 0, estd_stream(s), xyz, (int)n_vertices,
+                       faces, n_faces, attrs, C, cum, face_normal, n_samples, first, w, seed, out_xyz, out_face, out_bary, out_normal,
+                       out_attrs);
+    return ESTD_LAUNCH_CHECK();
+}

@@ -711,6 +711,86 @@ std::tuple<Tensor, Tensor, Tensor> mesh_components(const Tensor& faces, int64_t 
     return {label, triangles, invalid};
 }
 
+// ------------------------------------------------------------------------------------------------ mesh sampling (csrc/mesh/mesh_sample.hip)
+// the vertices float32 [V,3] and the triangles int32 [F,3] of one mesh on one device
+static const float* check_cloud(const Tensor& t, const char* op, const char* name, int64_t cols);      // with the point clouds below
+struct MeshArg { const float* xyz; const int32_t* faces; int64_t V, F; };
+static MeshArg check_mesh(const Tensor& xyz, const Tensor& faces, const char* op)
+{
+    MeshArg m{};
+    m.faces = faces_ptr(faces, op, "faces");
+    m.xyz = check_cloud(xyz, op, "xyz", 3);
+    TORCH_CHECK(xyz.device() == faces.device(), op, ": xyz is on ", xyz.device(), " but faces on ", faces.device());
+    m.V = xyz.size(0); m.F = faces.size(0);
+    return m;
+}
+
+static std::tuple<Tensor, Tensor, Tensor> face_area(const MeshArg& m, const Tensor& faces)
+{
+    Tensor area = at::empty({m.F}, faces.options().dtype(at::kDouble)), normal = at::empty({m.F, 3}, faces.options().dtype(at::kFloat));
+    Tensor invalid = at::empty({1}, faces.options().dtype(at::kLong));
+    check_status(estd_mesh_face_area(m.V ? m.xyz : nullptr, (long long)m.V, m.F ? m.faces : nullptr, (long long)m.F,
+                                     m.F ? area.data_ptr<double>() : nullptr, m.F ? normal.data_ptr<float>() : nullptr,
+                                     reinterpret_cast<long long*>(invalid.data_ptr<int64_t>()), cur_stream()), "estd_mesh_face_area");
+    return {area, normal, invalid};
+}
+
+// -> (area [F] float64, face_normal [F,3], invalid [1] int64 on the device)
+std::tuple<Tensor, Tensor, Tensor> mesh_face_area(const Tensor& xyz, const Tensor& faces)
+{
+    const OpScope scope(faces);
+    return face_area(check_mesh(xyz, faces, "mesh_face_area"), faces);
+}
+
+// -> (xyz [N,3], face [N] int32, bary [N,2], normal [N,3], attrs [N,C] (C = 0 without), area [F] float64, invalid [1] int64); the glue
+// between the two launches is the one of include/estd_hip.h, as in estdepth_amd/ops.py
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> mesh_sample(const Tensor& xyz, const Tensor& faces, const OptTensor& attrs,
+                                                                               int64_t n_samples, int64_t seed)
+{
+    const char* op = "mesh_sample";
+    const OpScope scope(faces);
+    const MeshArg m = check_mesh(xyz, faces, op);
+    int64_t C = 0;
+    const float* att = nullptr;
+    if (attrs.has_value() && attrs->defined()) {
+        att = fptr(*attrs, "attrs", true, op);
+        TORCH_CHECK(attrs->dim() == 2 && attrs->size(0) == m.V && attrs->size(1) >= 1 && attrs->size(1) <= ESTD_CLOUD_MAX_ATTRS,
+                    op, ": attrs must be [", m.V, ",C] with 1 <= C <= ", ESTD_CLOUD_MAX_ATTRS);
+        C = attrs->size(1);
+    }
+    check_count(n_samples, 0, 0x7fffffffLL, op, "n_samples");
+    auto [area, face_normal, invalid] = face_area(m, faces);
+    const int64_t n = m.F ? n_samples : 0;
+    int64_t w = 0;
+    Tensor cum;
+    if (n) {
+        const double amax = area.max().item<double>();
+        TORCH_CHECK(std::isfinite(amax) && amax >= 0, "mesh_sample: xyz holds a coordinate that is not finite (the largest area is ", amax, ")");
+        int e = 0, k = 0;
+        if (amax > 0) {
+            (void)std::frexp(amax, &k);
+            int b = 0;
+            while (((int64_t)1 << b) < m.F) ++b;
+            e = std::min(1000, 62 - b - k);
+        }
+        cum = at::cumsum(at::floor(area * std::ldexp(1.0, e)).to(at::kLong), 0);
+        const int64_t total = cum[m.F - 1].item<int64_t>();
+        TORCH_CHECK(total > 0, "mesh_sample: the mesh has no area to put n_samples = ", n, " samples on");
+        w = total / n;
+        TORCH_CHECK(w >= ESTD_MESH_SAMPLE_MIN_STRATUM, "mesh_sample: n_samples = ", n, " leaves strata of ", w, " units of area, fewer than ",
+                    ESTD_MESH_SAMPLE_MIN_STRATUM, ": too many samples for this mesh");
+    }
+    Tensor out_xyz = new_f32({n, 3}, xyz), face = at::empty({n}, faces.options()), bary = new_f32({n, 2}, xyz), normal = new_f32({n, 3}, xyz);
+    Tensor out_attrs = new_f32({n, C}, xyz);
+    if (n)
+        check_status(estd_mesh_sample(m.xyz, (long long)m.V, m.faces, (long long)m.F, C ? att : nullptr, (int)C,
+                                      reinterpret_cast<const long long*>(cum.data_ptr<int64_t>()), face_normal.data_ptr<float>(), (long long)n, 0LL,
+                                      (long long)w, (unsigned long long)seed, out_xyz.data_ptr<float>(), face.data_ptr<int32_t>(),
+                                      bary.data_ptr<float>(), normal.data_ptr<float>(), C ? out_attrs.data_ptr<float>() : nullptr, cur_stream()),
+                     "estd_mesh_sample");
+    return {out_xyz, face, bary, normal, out_attrs, area, invalid};
+}
+
 // ------------------------------------------------------------------------------------------------ cross-view consistency
 // csrc/depth_consistency.hip: target [H,W] and 1..8 sources of the same size, mats: CPU float32 [S,2,12] (F_s, B_s: host values of the
 // launch arguments) -> (views, visible, depth, rel_err), each [H,W]
@@ -1297,6 +1377,8 @@ TORCH_LIBRARY(estdepth_hip, m)
           "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("tsdf_mesh_faces(Tensor volume, float w_min, int capacity) -> (Tensor, Tensor, Tensor)");
     m.def("mesh_components(Tensor faces, int n_vertices) -> (Tensor, Tensor, Tensor)");
+    m.def("mesh_face_area(Tensor xyz, Tensor faces) -> (Tensor, Tensor, Tensor)");
+    m.def("mesh_sample(Tensor xyz, Tensor faces, Tensor? attrs, int n_samples, int seed) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("tsdf_raycast_color(Tensor volume, Tensor color, Tensor mat, int H, int W, float t_min, float dt, int n_steps, float w_min) -> "
           "(Tensor, Tensor, Tensor, Tensor)");
     m.def("depth_consistency(Tensor target, Tensor[] sources, Tensor mats, float px_max, float rel_max, float z_near) -> "
@@ -1359,6 +1441,8 @@ TORCH_LIBRARY_IMPL(estdepth_hip, CUDA, m)
     m.impl("tsdf_mesh_vertices", tsdf_mesh_vertices);
     m.impl("tsdf_mesh_faces", tsdf_mesh_faces);
     m.impl("mesh_components", mesh_components);
+    m.impl("mesh_face_area", mesh_face_area);
+    m.impl("mesh_sample", mesh_sample);
     m.impl("tsdf_raycast_color", tsdf_raycast_color);
     m.impl("depth_consistency", depth_consistency);
     m.impl("cloud_cell_keys", cloud_cell_keys);

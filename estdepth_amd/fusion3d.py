@@ -345,14 +345,22 @@ class TSDFVolume:
         write_ply(path, rec.numpy(), rgb, faces=faces)
         return rec.shape[0], faces.shape[0]
 
-    def compare(self, other, threshold=0.05, w_min=1.0, max_dist=None, downsample=None, cell=None):
+    def compare(self, other, threshold=0.05, w_min=1.0, max_dist=None, downsample=None, cell=None, sample=None, seed=0):
         """The 3D scores (``cloud_metrics.compare_clouds``: accuracy, completeness, chamfer, precision / recall / F-score at ``threshold``
         metres, ...) of this volume's surface as the prediction against ``other`` as the ground truth: another ``TSDFVolume`` -- both sides
         go through ``extract_points(w_min)`` -- or a dict with ``xyz`` [N,3] and optionally ``normal`` / ``color`` (device tensors or numpy
-        arrays, e.g. what ``read_ply`` returns).  Normals are compared when both sides have them, colours when both have a ``color``."""
+        arrays, e.g. what ``read_ply`` returns).  Normals are compared when both sides have them, colours when both have a ``color``.
+        ``sample=density`` (points per square metre) scores surfaces instead of vertices: a ``TSDFVolume`` side goes through
+        ``extract_mesh(w_min)`` and ``sample_mesh(density=sample, seed=seed)``, a dict side with ``faces`` through ``sample_mesh``, a
+        dict without faces stays the cloud it is; with the default None nothing of this runs."""
         from . import cloud_metrics
 
         def side(x):
+            if sample is not None:
+                if isinstance(x, TSDFVolume):
+                    x = x.extract_mesh(w_min=w_min)
+                if isinstance(x, dict) and x.get("faces") is not None:
+                    x = sample_mesh(x, density=sample, seed=seed)
             pts = x.extract_points(w_min=w_min) if isinstance(x, TSDFVolume) else x
             if isinstance(x, TSDFVolume):                      # records come back in no fixed order: sorted by edge, so that which of two equally
                 order = torch.argsort(pts["edge"])             # near neighbours is the nearest (its normal, its colour) does not change from run to run
@@ -548,6 +556,75 @@ def filter_mesh(mesh, min_triangles=1, keep_largest=None):
     out["components"] = int(keep.sum().item())
     out["dropped"] = dict(vertices=n_v - out["count"], faces=int(faces.shape[0] - out["faces"].shape[0]),
                           components=int((with_faces & ~keep).sum().item()))
+    return out
+
+
+def _on_device(v, dev, dtype=torch.float32):
+    """a per-vertex entry of a mesh dict (numpy array or tensor) as a contiguous ``dtype`` tensor on ``dev``"""
+    t = torch.from_numpy(np.ascontiguousarray(v)) if isinstance(v, np.ndarray) else v
+    return t.to(device=dev, dtype=dtype).contiguous()
+
+
+def _mesh_arg(mesh, what):
+    """the ``xyz`` and ``faces`` of a mesh dict on one device -> (xyz float32 [V,3], finite; faces int32 [F,3])"""
+    from .cloud_metrics import _check_cloud
+    if not isinstance(mesh, dict) or mesh.get("xyz") is None or mesh.get("faces") is None:
+        raise RuntimeError("%s: the mesh must be a dict with 'xyz' and 'faces'" % what)
+    devs = [v.device for v in mesh.values() if isinstance(v, torch.Tensor) and v.is_cuda]
+    faces = _faces_arg(mesh["faces"], what, devs[0] if devs else None)
+    return _check_cloud(_on_device(mesh["xyz"], faces.device), "xyz", what, faces.device), faces
+
+
+def mesh_area(mesh):
+    """The area of a triangle mesh (csrc/mesh/mesh_sample.hip; the contract: include/estd_hip.h, estd_mesh_face_area).  ``mesh``: a dict
+    with ``xyz`` [V,3] and ``faces`` [F,3] (what ``extract_mesh``, ``filter_mesh`` or ``read_ply(faces=True)`` return; numpy arrays are
+    moved to the device) -> dict(total: float, the sum in float64; area [F] float64 on the device; invalid: the faces that name a vertex
+    outside the mesh, which have area 0)."""
+    xyz, faces = _mesh_arg(mesh, "mesh_area")
+    area, _, invalid = ops.mesh_face_area(xyz, faces)
+    return dict(total=float(area.sum().item()), area=area, invalid=int(invalid.item()))
+
+
+def sample_mesh(mesh, n=None, density=None, seed=0, normals="face"):
+    """An evenly spread point cloud on a triangle mesh: ``n`` points, or ``density`` points per square metre (n = ceil(density x area)),
+    stratified along the cumulative area (csrc/mesh/mesh_sample.hip; the contract: include/estd_hip.h, estd_mesh_sample) -- every
+    triangle holds its share of the points within +-2, whatever its size, and a triangle without area none.  ``mesh`` as in ``mesh_area``;
+    uint8 ``rgb`` counts as float32 ``color``.  -> dict(xyz [n,3], normal [n,3], color [n,3] (if the mesh has one), face [n] int32: the
+    triangle of each point, bary [n,2]: its barycentric pair, area [F] float64, total: their sum, n, invalid) on the device.
+    ``normals="face"`` (the default: ground-truth files usually carry no normals) gives the triangle's unit normal, ``"vertex"`` the
+    mesh's vertex normals interpolated and normalised.  The result is a function of (mesh, n, seed): the same bits from every call."""
+    what = "sample_mesh"
+    if not isinstance(mesh, dict) or mesh.get("xyz") is None or mesh.get("faces") is None:
+        raise RuntimeError("%s: the mesh must be a dict with 'xyz' and 'faces'" % what)
+    if (n is None) == (density is None):
+        raise RuntimeError("%s: exactly one of n and density must be given, got n = %r and density = %r" % (what, n, density))
+    if n is not None and (not isinstance(n, (int, np.integer)) or not 0 <= n < 2 ** 31):
+        raise RuntimeError("%s: n must be an integer in 0 .. 2^31 - 1, got %r" % (what, n))
+    if density is not None and not (isinstance(density, (int, float)) and math.isfinite(density) and density > 0):
+        raise RuntimeError("%s: density must be positive and finite (points per square metre), got %r" % (what, density))
+    if normals not in ("face", "vertex"):
+        raise RuntimeError("%s: normals must be 'face' or 'vertex', got %r" % (what, normals))
+    if normals == "vertex" and mesh.get("normal") is None:
+        raise RuntimeError("%s: normals='vertex' needs a mesh with vertex normals ('normal')" % what)
+    xyz, faces = _mesh_arg(mesh, what)
+    dev, n_v = faces.device, int(xyz.shape[0])
+    color = mesh.get("color") if mesh.get("color") is not None else mesh.get("rgb")
+    cols = [_on_device(v, dev) for v in ((mesh["normal"] if normals == "vertex" else None), color) if v is not None]
+    for c in cols:
+        if c.dim() != 2 or c.shape[0] != n_v or c.shape[1] != 3:
+            raise RuntimeError("%s: normal and color must be [%d,3], got %s" % (what, n_v, tuple(c.shape)))
+    if n is None:
+        total = float(ops.mesh_face_area(xyz, faces)[0].sum().item())
+        n = int(math.ceil(float(density) * total))
+        if n >= 2 ** 31:
+            raise RuntimeError("%s: density %r over %.6g square metres asks for %d points (at most 2^31 - 1)" % (what, density, total, n))
+    p, face, bary, normal, attrs, area, invalid = ops.mesh_sample(xyz, faces, torch.cat(cols, 1) if cols else None, int(n), seed)
+    out = dict(xyz=p, normal=normal, face=face, bary=bary, area=area, total=float(area.sum().item()), n=int(p.shape[0]),
+               invalid=int(invalid.item()))
+    if normals == "vertex":
+        out["normal"] = torch.nn.functional.normalize(attrs[:, :3], dim=1)
+    if color is not None:
+        out["color"] = attrs[:, -3:].contiguous()
     return out
 
 

@@ -1347,6 +1347,95 @@ def mesh_components(faces, n_vertices):
     return label, triangles, invalid
 
 
+# ---------------------------------------------------------------------------------- mesh sampling (csrc/mesh/mesh_sample.hip)
+MESH_SAMPLE_MIN_STRATUM = 1 << 20      # ESTD_MESH_SAMPLE_MIN_STRATUM (include/estd_hip.h)
+
+
+def _mesh(xyz, faces, op):
+    """the vertices float32 [V,3] and the triangles int32 [F,3] of one mesh on one device -> (V, F)"""
+    n_faces = _faces(faces, op, "faces")
+    _cloud(xyz, op, "xyz")
+    _need(xyz.device == faces.device, "%s: xyz is on %s but faces on %s" % (op, xyz.device, faces.device))
+    return xyz.shape[0], n_faces
+
+
+def mesh_sample_scale(n_faces, area_max):
+    """The exponent e of the power of two that quantises the areas (include/estd_hip.h, "The glue"): with ``area_max`` = m 2^k,
+    0.5 <= m < 1, e = 62 - ceil(log2 n_faces) - k, so that the sum of the n_faces values floor(area 2^e) stays below 2^62.  Needs no
+    device.  A largest area that is not finite means a vertex that is not: refused."""
+    _need(math.isfinite(area_max) and area_max >= 0, "mesh_sample: xyz holds a coordinate that is not finite (the largest area is %r)" % (area_max,))
+    if n_faces <= 0 or area_max == 0:
+        return 0
+    return min(1000, 62 - (int(n_faces) - 1).bit_length() - math.frexp(area_max)[1])
+
+
+def mesh_sample_stratum(total, n_samples):
+    """The stratum w = total // n_samples of ``n_samples`` > 0 samples over ``total`` units of quantised area; refused without area and
+    below 2^20 units.  Needs no device."""
+    _need(total > 0, "mesh_sample: the mesh has no area to put n_samples = %d samples on" % n_samples)
+    w = int(total) // int(n_samples)
+    _need(w >= MESH_SAMPLE_MIN_STRATUM, "mesh_sample: n_samples = %d leaves strata of %d units of area, fewer than %d: too many samples for this mesh"
+          % (n_samples, w, MESH_SAMPLE_MIN_STRATUM))
+    return w
+
+
+def mesh_face_area(xyz, faces):
+    """Per-triangle areas of the mesh ``xyz`` [V,3] float32 / ``faces`` [F,3] int32 -> (area [F] float64, face_normal [F,3] float32,
+    invalid [1] int64 on the device: the triangles with an index outside [0, V), whose area is 0).  include/estd_hip.h,
+    estd_mesh_face_area."""
+    if _use_torch():
+        return tuple(T().mesh_face_area(xyz, faces))
+    n_vertices, n_faces = _mesh(xyz, faces, "mesh_face_area")
+    dev = faces.device
+    with torch.cuda.device(dev):
+        area = torch.empty(n_faces, device=dev, dtype=torch.float64)
+        normal = torch.empty((n_faces, 3), device=dev)
+        invalid = torch.empty(1, device=dev, dtype=torch.int64)
+        pp = (lambda t: _p(t)) if n_faces else (lambda t: None)
+        N.check(N.lib().estd_mesh_face_area(_p(xyz) if n_vertices else None, n_vertices, pp(faces), n_faces, pp(area), pp(normal), _p(invalid),
+                                            _stream()), "estd_mesh_face_area")
+    return area, normal, invalid
+
+
+def mesh_sample(xyz, faces, attrs, n_samples, seed=0):
+    """``n_samples`` points spread evenly by area over the mesh ``xyz`` [V,3] float32 / ``faces`` [F,3] int32, with the vertex attributes
+    ``attrs`` [V,C] (1 <= C <= 6, or None) interpolated -> (xyz [N,3], face [N] int32, bary [N,2], normal [N,3] (the triangle's), attrs
+    [N,C] or None, area [F] float64, invalid [1] int64).  Stratified along the cumulative area, a function of (mesh, n_samples, seed) alone;
+    ``seed``: any integer, taken modulo 2^64.  Without faces or with n_samples = 0 the sample arrays are empty.  The contract:
+    include/estd_hip.h (estd_mesh_face_area, the glue, estd_mesh_sample)."""
+    n_samples, seed = int(n_samples), int(seed) & 0xffffffffffffffff
+    if _use_torch():
+        out = list(T().mesh_sample(xyz, faces, attrs, n_samples, seed - (1 << 64) if seed >> 63 else seed))
+        out[4] = out[4] if attrs is not None else None
+        return tuple(out)
+    op = "mesh_sample"
+    n_vertices, n_faces = _mesh(xyz, faces, op)
+    dev = faces.device
+    C = 0
+    if attrs is not None:
+        _chk(attrs, "attrs", op=op, dev=dev)
+        _need(attrs.dim() == 2 and attrs.shape[0] == n_vertices and 1 <= attrs.shape[1] <= CLOUD_MAX_ATTRS,
+              "%s: attrs must be [%d,C] with 1 <= C <= %d" % (op, n_vertices, CLOUD_MAX_ATTRS))
+        C = attrs.shape[1]
+    _count(n_samples, 0, 0x7fffffff, op, "n_samples")
+    area, face_normal, invalid = mesh_face_area(xyz, faces)
+    n = n_samples if n_faces else 0
+    w = 0
+    if n:
+        scale = 2.0 ** mesh_sample_scale(n_faces, float(area.max().item()))
+        cum = torch.cumsum(torch.floor(area * scale).to(torch.int64), 0)
+        w = mesh_sample_stratum(int(cum[-1].item()), n)
+    with torch.cuda.device(dev):
+        out_xyz, face, bary = torch.empty((n, 3), device=dev), torch.empty(n, device=dev, dtype=torch.int32), torch.empty((n, 2), device=dev)
+        normal = torch.empty((n, 3), device=dev)
+        out_attrs = torch.empty((n, C), device=dev) if C else None
+        if n:
+            N.check(N.lib().estd_mesh_sample(_p(xyz), n_vertices, _p(faces), n_faces, _p(attrs) if C else None, C, _p(cum), _p(face_normal), n, 0, w,
+                                             seed, _p(out_xyz), _p(face), _p(bary), _p(normal), _p(out_attrs) if C else None, _stream()),
+                    "estd_mesh_sample")
+    return out_xyz, face, bary, normal, out_attrs, area, invalid
+
+
 # ---------------------------------------------------------------------------------- cross-view consistency (csrc/depth_consistency.hip)
 CONSISTENCY_MAX_SOURCES = N.CONSISTENCY_MAX_SOURCES
 

@@ -786,6 +786,51 @@ int estd_tsdf_mesh_faces(const float* tsdf, const float* weight, int Z, int Y, i
 int estd_mesh_components(const int* faces, long long n_faces, long long n_vertices, int* label, int* triangles, long long* invalid,
                          estd_stream_t stream);
 
+/* An evenly spread point cloud on a triangle mesh (csrc/mesh/mesh_sample.hip; numpy form: tests/mesh_sample_ref.py): per-triangle areas,
+ * then stratified sampling along the cumulative area.  Two entry points with integer glue between them, which the host layers
+ * (estdepth_amd/ops.py, mesh_sample) own; a foreign host repeats it as written here.
+ *
+ * estd_mesh_face_area (mesh_face_area_kernel, one lane per triangle).  xyz [V][3] float32, faces [F][3] int32, both contiguous.
+ *   A triangle with an index outside [0, V) is INVALID (estd_mesh_components' rule): its indices are never used as an address, its
+ *   area is +0, its normal 0 0 0, and it is counted in invalid [1] int64, which the call zeroes first (a memset on `stream`) and
+ *   raises with ONE integer atomic add per wave.  Otherwise, with a, b, c the vertices widened to float64 and every operation below
+ *   one IEEE float64 operation in this order, never contracted into an fma:
+ *     e1 = b - a;  e2 = c - a;
+ *     nx = e1y * e2z - e1z * e2y;  ny = e1z * e2x - e1x * e2z;  nz = e1x * e2y - e1y * e2x;
+ *     len = sqrt((nx * nx + ny * ny) + nz * nz);   area[f] = 0.5 * len;
+ *     face_normal[f] = ((float)(nx / len), (float)(ny / len), (float)(nz / len)), or 0 0 0 when len == 0.
+ *   area [F] float64 and face_normal [F][3] float32 are written with plain stores: two calls give the same bits.  F == 0: the memset
+ *   alone.  ESTD_ERR_ARG: a negative size, a null `invalid`, a null xyz with V > 0, a null faces / area / face_normal with F > 0.
+ *   ESTD_ERR_UNSUPPORTED: V or 3 F beyond 2^31 - 1.
+ *
+ * The glue.  scale = 2^e with e = 62 - ceil(log2 F) - k, where max(area) = m 2^k, 0.5 <= m < 1 (e = 0 without area, and at most
+ *   1000); q_f = (int64) floor(area_f * scale), exact because scale is a power of two; cum = the running sum of q in int64, exact in
+ *   any order; Q = cum[F - 1] < 2^62.  For N samples the stratum is w = Q / N (integer division); the host layers refuse Q == 0 and
+ *   w < 2^20 (ESTD_MESH_SAMPLE_MIN_STRATUM: the Q mod N units no sample can reach are below 2^-20 of a stratum each).
+ *
+ * estd_mesh_sample (mesh_sample_kernel, one lane per sample).  Sample i = first + j, j < n_samples, all unsigned arithmetic mod 2^64:
+ *     mix(z):  z ^= z >> 30;  z *= 0xbf58476d1ce4e5b9;  z ^= z >> 27;  z *= 0x94d049bb133111eb;  z ^= z >> 31;
+ *     h64(seed, i, s) = mix(mix(seed + (i + 1) * 0x9e3779b97f4a7c15) + (s + 1) * 0xd1b54a32d192ed03);   h32 = h64 >> 32;
+ *     t_i = i * w + (h64(seed, i, 0) mod w);   f_i = the first f with cum[f] > t_i (F - 1 should there be none);
+ *     iu = h32(seed, i, 1) >> 8;  iv = h32(seed, i, 2) >> 8;  when iu + iv > 2^24:  iu = 2^24 - iu, iv = 2^24 - iv;
+ *     u = iu * 2^-24,  v = iv * 2^-24 (exact in fp32: the fold to 1 - u, 1 - v when u + v > 1, with no rounding and no square root);
+ *     with a, b, c the vertices of f_i, per coordinate in fp32:  p = fmaf(v, c - a, fmaf(u, b - a, a)).
+ *   A triangle of q_f = 0 (no area, or invalid) is never chosen; triangle f holds, within +-2, N q_f / Q samples; the samples come
+ *   in ascending i, hence in non-decreasing f.  Outputs, row j: out_xyz [n][3], out_face [n] int32 = f_i, out_bary [n][2] = (u, v),
+ *   out_normal [n][3] = face_normal[f_i], out_attrs [n][C] = the expression of p on the rows of attrs [V][C] (0 <= C <=
+ *   ESTD_CLOUD_MAX_ATTRS; C == 0: both attribute pointers are ignored), not renormalised.  Plain stores, no atomics: the result does
+ *   not depend on the launch shape, and a call split at any `first` gives the same rows.  Should cum not belong to this mesh and f_i
+ *   name a vertex outside [0, V), that row is face -1 and zeros: still never an address.
+ *   n_samples == 0 launches nothing.  ESTD_ERR_ARG: a negative size or `first`, C outside 0..6, and with n_samples > 0: V == 0 or
+ *   F == 0, w < 1 or (first + n_samples) * w > 2^62, a null pointer.  ESTD_ERR_UNSUPPORTED: V, 3 F or first + n_samples beyond 2^31 - 1. */
+#define ESTD_MESH_SAMPLE_MIN_STRATUM (1 << 20)
+int estd_mesh_face_area(const float* xyz, long long n_vertices, const int* faces, long long n_faces, double* area, float* face_normal,
+                        long long* invalid, estd_stream_t stream);
+int estd_mesh_sample(const float* xyz, long long n_vertices, const int* faces, long long n_faces, const float* attrs, int C,
+                     const long long* cum, const float* face_normal, long long n_samples, long long first, long long w,
+                     unsigned long long seed, float* out_xyz, int* out_face, float* out_bary, float* out_normal, float* out_attrs,
+                     estd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,11 @@ ground-truth depth.  Needs an MI355X (the model has no CPU path).
         # + the 3D scores of the fused scene (estdepth_amd.cloud_metrics): the ground-truth depth maps of the same targets are fused into a
         # second volume of the same geometry and the two surfaces compared -- accuracy, completeness, chamfer, precision / recall / F-score;
         # --score-3d GT.ply compares against that cloud instead; metrics.json gains recon_3d
+    python tools/run_stream.py --synthetic 8 --out /tmp/eval --fuse /tmp/eval/scene.ply --score-3d GT.ply --score-sample 2500
+        # + surfaces instead of vertices: GT.ply is read with its faces and, like the fused side's own triangle mesh (after
+        # --mesh-min-component when given), sampled by area at 2500 points per square metre (fusion3d.sample_mesh on
+        # csrc/mesh/mesh_sample.hip) before the two are compared; recon_3d gains sampled: density, n_pred, n_gt, area_pred, area_gt,
+        # invalid_pred, invalid_gt.  A GT.ply without faces is scored as the cloud it is (area_gt: null)
     python tools/run_stream.py --synthetic 8 --out /tmp/eval --fuse /tmp/eval/scene.ply --track
         # + frame-to-model tracking (estdepth_amd.tracking): from the second fused target on, every target's pose is refined against the
         # volume (TSDFVolume.track: point-to-plane alignment of its depth map with the ray-cast model) before the target is fused -- the
@@ -130,6 +135,9 @@ def parse(argv=None):
                     "ground-truth depth maps of the same targets fused into a second volume of the same geometry (no confidence gating)")
     ap.add_argument("--score-threshold", type=float, default=0.05, help="with --score-3d: the precision / recall / F-score threshold in metres")
     ap.add_argument("--score-max-dist", type=float, default=None, help="with --score-3d: distances are clamped here (default: 20 thresholds)")
+    ap.add_argument("--score-sample", type=float, default=None, metavar="DENSITY", help="with --score-3d: score surfaces instead of vertices -- the "
+                    "fused side is its triangle mesh (after --mesh-min-component when given), a GT.ply with faces is read as a mesh, and both are "
+                    "sampled by area at DENSITY points per square metre (fusion3d.sample_mesh); recon_3d gains a sampled block")
     ap.add_argument("--score-downsample", type=float, default=None, help="with --score-3d: voxel-grid down-sampling of both clouds first (metres)")
     ap.add_argument("--track", action="store_true", help="with --fuse: refine every target's pose against the fused volume before the target is "
                     "fused (TSDFVolume.track), from the second fused target on")
@@ -154,6 +162,10 @@ def parse(argv=None):
         ap.error("--color needs --fuse PATH.ply")
     if args.score_3d is not None and not args.fuse:
         ap.error("--score-3d needs --fuse PATH.ply")
+    if args.score_sample is not None and args.score_3d is None:
+        ap.error("--score-sample needs --score-3d")
+    if args.score_sample is not None and not (args.score_sample > 0 and args.score_sample < float("inf")):
+        ap.error("--score-sample must be a positive density in points per square metre")
     if args.track and not args.fuse:
         ap.error("--track needs --fuse PATH.ply")
     if not args.scene_dir and not args.synthetic:
@@ -357,7 +369,20 @@ def run(args):
         max_dist = args.score_max_dist if args.score_max_dist is not None else 20.0 * args.score_threshold
         torch.cuda.synchronize()
         t0 = time.time()
-        scores = volume.compare(other, threshold=args.score_threshold, max_dist=max_dist, downsample=args.score_downsample)
+        if args.score_sample is None:
+            scores = volume.compare(other, threshold=args.score_threshold, max_dist=max_dist, downsample=args.score_downsample)
+        else:
+            # surfaces, not vertices: both sides as triangle meshes sampled by area at the same density (csrc/mesh/mesh_sample.hip); a
+            # ground-truth file without faces stays the cloud it is
+            from estdepth_amd.cloud_metrics import compare_meshes
+            if volume_gt is not None:
+                other = volume_gt.extract_mesh()
+            else:
+                faces = read_ply(args.score_3d, faces=True)["faces"]
+                if faces.shape[0]:
+                    other["faces"] = faces
+            scores = compare_meshes(volume.extract_mesh(min_component=args.mesh_min_component or 0), other, args.score_sample,
+                                    threshold=args.score_threshold, max_dist=max_dist, downsample=args.score_downsample)
         torch.cuda.synchronize()
         report["recon_3d"] = dict(scores, threshold=args.score_threshold, max_dist=max_dist, downsample=args.score_downsample, ground_truth=gt_name,
                                   compare_ms=1e3 * (time.time() - t0))

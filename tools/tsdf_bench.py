@@ -33,7 +33,13 @@ search of the cell ids, the triangle split) separately, each between device even
 times the connected components of that mesh (csrc/mesh/mesh_components.hip) and fusion3d.filter_mesh: the operator (its four launches)
 and the whole filter between device events, each call behind the cache flush, the four kernels one by one from the profiler's device
 times over the same calls, beside the yardstick -- the same labels by scipy.sparse.csgraph.connected_components on the host, the copies
-included, or where scipy is missing a min-label propagation loop in torch on the device."""
+included, or where scipy is missing a min-label propagation loop in torch on the device.
+
+    python tools/tsdf_bench.py --mesh-sample [--reps 100] [--out profiles/mesh_sample_bench.txt]
+
+times the mesh sampling (csrc/mesh/mesh_sample.hip) on that mesh and on the 204 800-triangle grid of tests/mesh_components_ref.py: the
+area kernel, the sample kernel at 10^5 and 10^6 samples and the whole fusion3d.sample_mesh, between device events, behind the cache flush
+and back to back, beside the same sampling formed with torch operators on the same prefix sums."""
 import argparse
 import os
 import sys
@@ -74,6 +80,7 @@ def main():
     ap.add_argument("--raycast", action="store_true", help="time the ray caster (csrc/tsdf_raycast.hip) instead of integrate / extract")
     ap.add_argument("--mesh", action="store_true", help="time extract_mesh (kernels and host ordering apart) beside extract_points")
     ap.add_argument("--mesh-components", action="store_true", help="time the mesh components and filter_mesh beside a host / torch yardstick")
+    ap.add_argument("--mesh-sample", action="store_true", help="time the mesh sampling (csrc/mesh/mesh_sample.hip) beside the same sampling with torch operators")
     ap.add_argument("--color", action="store_true", help="time the colour fuse, the edge colours and the colour render beside the plain figures")
     args = ap.parse_args()
     if args.raycast:
@@ -82,6 +89,8 @@ def main():
         return mesh_main(args)
     if args.mesh_components:
         return components_main(args)
+    if args.mesh_sample:
+        return sample_main(args)
     if args.color:
         return color_main(args)
     import tsdf_ref as R
@@ -295,6 +304,80 @@ def components_main(args):
                   "%s %.4f" % (k[8:-7], grid_kernels.get(k, float("nan"))) for k in ("mesh_cc_init_kernel", "mesh_cc_hook_kernel",
                                                                                     "mesh_cc_flatten_kernel", "mesh_cc_count_kernel"))),
               "  the labels of the yardstick and of the kernels are equal; no bar is set (the parent has nothing comparable)"]
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        open(args.out, "w").write(text + "\n")
+
+
+def sample_main(args):
+    import ctypes
+    import tsdf_ref as R
+    import mesh_components_ref as C
+    from estdepth_amd import _native, ops
+    from estdepth_amd.fusion3d import TSDFVolume, frustum_volume, sample_mesh
+    assert torch.cuda.is_available(), "tools/tsdf_bench.py needs a ROCm device"
+    dev = torch.device("cuda:0")
+    H, W, T, vox, dmin, dmax, dims = 480, 640, 3, 0.03, 0.1, 10.0, (256, 256, 256)
+    reps = min(args.reps, 100)
+    K = R.intrinsics(H, W)
+    poses = R.scene_poses(T, seed=1)
+    depths = torch.from_numpy(np.stack([R.raycast_scene(P, K, H, W) for P in poses]).astype(np.float32)).to(dev)
+    flush = torch.empty(256 << 20, device=dev)          # 1 GiB
+    origin = frustum_volume(torch.from_numpy(poses[0]), torch.from_numpy(K), (H, W), dmin, dmax, dims, vox)
+    vol = TSDFVolume(dims, vox, origin, device=dev)
+    vol.integrate(depths, torch.from_numpy(poses), torch.from_numpy(K))
+    m = vol.extract_mesh()
+    grid_np, grid_v = C.build_case("grid-320")
+    grid_xyz = torch.from_numpy(np.random.default_rng(0).uniform(0.0, 4.0, (grid_v, 3)).astype(np.float32)).to(dev)
+    meshes = [("the mesh of the %d x %d x %d volume" % dims, m["xyz"].contiguous(), m["faces"].contiguous()),
+              ("the grid of tests/mesh_components_ref.py (permuted ids, vertices uniform in a 4 m box)", grid_xyz, torch.from_numpy(grid_np.copy()).to(dev))]
+    lib = _native.lib()
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    stream = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    lines = ["tsdf_bench --mesh-sample: mean of %d calls per figure between device events, 'cold' = behind a 1 GiB cache flush, 'warm' = back to back, %s"
+             % (reps, torch.cuda.get_device_name(0))]
+    for name, xyz, faces in meshes:
+        V, F = xyz.shape[0], faces.shape[0]
+        area, fnormal, invalid = ops.mesh_face_area(xyz, faces)
+        cum = torch.cumsum(torch.floor(area * 2.0 ** ops.mesh_sample_scale(F, float(area.max().item()))).to(torch.int64), 0)
+        total = int(cum[-1].item())
+
+        def kernel_a():
+            assert lib.estd_mesh_face_area(p(xyz), V, p(faces), F, p(area), p(fnormal), p(invalid), stream()) == 0
+        lines.append("%s: %d vertices, %d triangles, %.3f m2" % (name, V, F, float(area.sum().item())))
+        lines.append("  mesh_face_area_kernel (+ the 8-byte memset)    %8.4f ms cold  %8.4f ms warm" % (timed(kernel_a, reps, flush), timed(kernel_a, reps)))
+        for n in (10 ** 5, 10 ** 6):
+            w = ops.mesh_sample_stratum(total, n)
+            out = [torch.empty((n, 3), device=dev), torch.empty(n, device=dev, dtype=torch.int32), torch.empty((n, 2), device=dev), torch.empty((n, 3), device=dev)]
+
+            def kernel_b():
+                assert lib.estd_mesh_sample(p(xyz), V, p(faces), F, None, 0, p(cum), p(fnormal), n, 0, w, 7, p(out[0]), p(out[1]), p(out[2]), p(out[3]),
+                                            None, stream()) == 0
+
+            def yard():
+                # the same sampling with torch operators on the same prefix sums: three random draws, the search, the gathers, the arithmetic
+                t = torch.arange(n, device=dev, dtype=torch.int64) * w + torch.randint(0, w, (n,), device=dev, dtype=torch.int64)
+                f = torch.searchsorted(cum, t, right=True)
+                uv = torch.rand((n, 2), device=dev)
+                uv = torch.where((uv.sum(1) > 1.0)[:, None], 1.0 - uv, uv)
+                tri = faces[f].to(torch.int64)
+                a, b, c = xyz[tri[:, 0]], xyz[tri[:, 1]], xyz[tri[:, 2]]
+                return torch.addcmul(torch.addcmul(a, uv[:, :1], b - a), uv[:, 1:], c - a), f, uv, fnormal[f]
+            kernel_b()
+            got, ref = torch.bincount(out[1].to(torch.int64), minlength=F), torch.bincount(yard()[1], minlength=F)
+            assert int((got - ref).abs().max().item()) <= 4, "the yardstick and the kernel spread the samples differently"
+            whole = lambda: sample_mesh(dict(xyz=xyz, faces=faces), n=n, seed=7)
+            t_b, t_bw, t_y, t_yw, t_all, t_allw = (timed(kernel_b, reps, flush), timed(kernel_b, reps), timed(yard, reps, flush), timed(yard, reps),
+                                                   timed(whole, reps, flush), timed(whole, reps))
+            lines += ["  N = %d (stratum %d units, about %d dependent 8-byte loads per lane):" % (n, w, max(1, F).bit_length()),
+                      "    mesh_sample_kernel, plain upper-bound search %8.4f ms cold  %8.4f ms warm  (%.2f G samples/s warm)" % (t_b, t_bw, n / t_bw / 1e6),
+                      "    yardstick: torch randint / rand / searchsorted / gathers / addcmul %8.4f ms cold  %8.4f ms warm  (kernel / yardstick = 1 / %.1f cold)"
+                      % (t_y, t_yw, t_y / t_b),
+                      "    sample_mesh, whole call (finite check, area kernel, max and total read-backs, cumsum, sample kernel) %8.4f ms cold  %8.4f ms warm"
+                      % (t_all, t_allw)]
+    lines.append("  no bar is set (the parent has nothing comparable); a search narrowed per wave was not built and is not measured")
     text = "\n".join(lines)
     print(text)
     if args.out:
