@@ -226,6 +226,22 @@ def tsdf_ray_matrix(cam_pose, cam_intr, origin, voxel_size):
     return out
 
 
+def mesh_raster_matrix(cam_pose, cam_intr):
+    """World -> pixel matrices of estd_mesh_raster: M = K [R^T | -R^T c] per view with R, c from the camera-to-world pose, so that the third
+    component of M (x, 1) is the z-depth of the world point x and the first two over the third its pixel.  Formed in float64 on the host
+    and KEPT in float64 (the rasteriser's arithmetic is float64 throughout) -> CPU float64 [12] for one pose [4,4], [V,12] for [V,4,4]
+    (3x4 row-major).  cam_intr [3,3] or [V,3,3] in pixels of the rendered image."""
+    P = cam_pose.detach().to(device="cpu", dtype=torch.float64).reshape(-1, 4, 4)
+    K = cam_intr.detach().to(device="cpu", dtype=torch.float64).reshape(-1, 3, 3)
+    if K.shape[0] not in (1, P.shape[0]):
+        raise RuntimeError("mesh_raster_matrix: cam_intr must be [3,3] or one [3,3] per pose, got %s for %d poses" % (tuple(cam_intr.shape), P.shape[0]))
+    out = torch.empty(P.shape[0], 12, dtype=torch.float64)
+    for t in range(P.shape[0]):
+        Rt = P[t, :3, :3].t()
+        out[t] = (K[t if K.shape[0] > 1 else 0] @ torch.cat([Rt, -(Rt @ P[t, :3, 3])[:, None]], 1)).reshape(-1)
+    return out[0].contiguous() if cam_pose.dim() == 2 else out
+
+
 # ------------------------------------------------------------------------------------------------ cross-view consistency
 def consistency_matrices(pose_t, K_t, poses_s, K_s):
     """The matrices of estd_depth_consistency for one target and S sources: per source F_s = [K_s R_st K_t^-1 | K_s t_st], which takes a

@@ -243,13 +243,39 @@ def compare_clouds(pred, gt, threshold=0.05, max_dist=None, downsample=None, pre
     return out
 
 
-def compare_meshes(pred, gt, density, threshold=0.05, max_dist=None, downsample=None, seed=0, cell=None):
+VISIBLE_KEYS = ("cam_poses", "cam_intr", "image_hw", "min_views", "tol", "depth_max", "z_near")
+
+
+def restrict_to_visible(mesh, cloud, visible, threshold, op):
+    """The samples ``cloud`` (a dict of per-point tensors with ``xyz``) of the ground-truth ``mesh`` that at least ``min_views`` of the
+    cameras in ``visible`` saw (mesh_render.visible_mask) -> (the restricted dict, n before, n after).  ``tol`` defaults to ``threshold``:
+    a point hidden less than the matching distance behind another surface is one the metric would match anyway."""
+    from . import mesh_render
+    _need(isinstance(visible, dict) and all(k in visible for k in VISIBLE_KEYS[:3]) and all(k in VISIBLE_KEYS for k in visible),
+          "%s: visible must be a dict with cam_poses, cam_intr, image_hw and optionally min_views, tol, depth_max, z_near" % op)
+    _need(isinstance(mesh, dict) and mesh.get("faces") is not None,
+          "%s: visible= needs a ground truth with faces (a triangle mesh): a point cloud cannot be rendered" % op)
+    tol = visible.get("tol")
+    keep, _ = mesh_render.visible_mask(mesh, cloud["xyz"], visible["cam_poses"], visible["cam_intr"], visible["image_hw"],
+                                       min_views=visible.get("min_views", 1), tol=float(threshold if tol is None else tol),
+                                       depth_max=visible.get("depth_max"), z_near=visible.get("z_near", 1e-3))
+    n = int(cloud["xyz"].shape[0])
+    out = {k: (v[keep].contiguous() if isinstance(v, torch.Tensor) and v.dim() >= 1 and v.shape[0] == n else v) for k, v in cloud.items()}
+    return out, n, int(out["xyz"].shape[0])
+
+
+def compare_meshes(pred, gt, density, threshold=0.05, max_dist=None, downsample=None, seed=0, cell=None, visible=None):
     """The 3D scores of the SURFACE ``pred`` against the surface ``gt``: both triangle meshes (dicts with ``xyz`` and ``faces``: what
     ``extract_mesh``, ``filter_mesh`` or ``read_ply(faces=True)`` return) are sampled by area at ``density`` points per square metre
     (``fusion3d.sample_mesh``, face normals), and the two clouds go to ``compare_clouds`` unchanged -> its dict plus ``sampled`` =
     dict(density, n_pred, n_gt, area_pred, area_gt, invalid_pred, invalid_gt).  A side without ``faces`` is a plain cloud (``xyz``,
     optionally ``normal`` / ``color``) and is used as it is: its area is None.  A decimated mesh -- a wall as two triangles -- then counts
-    by its area, not by its vertices, and the distance to it is the distance to its surface, not to its nearest corner."""
+    by its area, not by its vertices, and the distance to it is the distance to its surface, not to its nearest corner.
+    ``visible=dict(cam_poses [T,4,4], cam_intr, image_hw, min_views=1, tol=None, depth_max=None)`` scores only the ground truth the
+    cameras saw: the ground-truth mesh is rendered in every view (csrc/mesh/mesh_raster.hip) and its samples seen by fewer than
+    ``min_views`` views are dropped before the comparison (``tol`` defaults to ``threshold``); ``sampled`` gains n_gt_visible and
+    visible_share.  The predicted side is untouched.  A ground truth without faces cannot be rendered and is refused.  With the default
+    None nothing of this runs."""
     _need(isinstance(density, (int, float)) and math.isfinite(density) and density > 0, "compare_meshes: density must be positive and finite, got %r" % (density,))
     from . import fusion3d
     _need(all(isinstance(x, dict) and x.get("xyz") is not None for x in (pred, gt)), "compare_meshes: pred and gt must be dicts with 'xyz'")
@@ -264,10 +290,15 @@ def compare_meshes(pred, gt, density, threshold=0.05, max_dist=None, downsample=
         out = {k: fusion3d._on_device(v, dev) for k, v in (("xyz", x["xyz"]), ("normal", x.get("normal")), ("color", color)) if v is not None}
         return out, None, 0
     (a, area_a, bad_a), (b, area_b, bad_b) = side(pred), side(gt)
+    n_gt = int(b["xyz"].shape[0])
+    if visible is not None:
+        b, n_gt, _ = restrict_to_visible(gt, b, visible, threshold, "compare_meshes")
     both = lambda k: k in a and k in b
     out = compare_clouds(a["xyz"], b["xyz"], threshold=threshold, max_dist=max_dist, downsample=downsample,
                          pred_normal=a["normal"] if both("normal") else None, gt_normal=b["normal"] if both("normal") else None,
                          pred_color=a["color"] if both("color") else None, gt_color=b["color"] if both("color") else None, cell=cell)
-    out["sampled"] = dict(density=float(density), n_pred=int(a["xyz"].shape[0]), n_gt=int(b["xyz"].shape[0]), area_pred=area_a, area_gt=area_b,
+    out["sampled"] = dict(density=float(density), n_pred=int(a["xyz"].shape[0]), n_gt=n_gt, area_pred=area_a, area_gt=area_b,
                           invalid_pred=bad_a, invalid_gt=bad_b)
+    if visible is not None:
+        out["sampled"].update(n_gt_visible=int(b["xyz"].shape[0]), visible_share=int(b["xyz"].shape[0]) / n_gt if n_gt else 0.0)
     return out

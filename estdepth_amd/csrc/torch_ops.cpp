@@ -791,6 +791,43 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> mesh_sample(c
     return {out_xyz, face, bary, normal, out_attrs, area, invalid};
 }
 
+// ------------------------------------------------------------------------------------------------ mesh rasteriser (csrc/mesh/mesh_raster.hip)
+// host values a kernel takes as float64: exactly n of them, all finite
+static const double* host_doubles(const Tensor& t, int64_t n, const char* op, const char* name, const char* shape)
+{
+    TORCH_CHECK(t.defined() && t.device().is_cpu() && t.scalar_type() == at::kDouble && t.is_contiguous() && t.numel() == n,
+                op, ": ", name, " must be a contiguous CPU float64 tensor ", shape);
+    const double* v = t.data_ptr<double>();
+    for (int64_t i = 0; i < n; ++i) TORCH_CHECK(std::isfinite(v[i]), op, ": ", name, " holds a value that is not finite");
+    return v;
+}
+
+// mat: CPU float64 [12] -> (depth [H,W], face [H,W] int32, bary [H,W,2], facing [H,W] int32, invalid [1] int64 on the device); the key
+// buffer lives here and is cleared by the first entry point with a memset on the stream
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mesh_raster(const Tensor& xyz, const Tensor& faces, const Tensor& mat, int64_t H, int64_t W,
+                                                               double z_near, bool preload)
+{
+    const char* op = "mesh_raster";
+    const OpScope scope(faces);
+    const MeshArg m = check_mesh(xyz, faces, op);
+    const double* M = host_doubles(mat, 12, op, "mat", "[12] (3x4 row-major)");
+    check_map_size(H, W, op, "the image");
+    const float zn = not_negative_f32(z_near, op, "z_near");
+    Tensor keys = at::empty({H, W}, faces.options().dtype(at::kLong));
+    Tensor depth = new_f32({H, W}, xyz), face = at::empty({H, W}, faces.options()), bary = new_f32({H, W, 2}, xyz);
+    Tensor facing = at::empty({H, W}, faces.options()), invalid = at::empty({1}, faces.options().dtype(at::kLong));
+    const float* px = m.V ? m.xyz : nullptr;
+    const int32_t* pf = m.F ? m.faces : nullptr;
+    auto* k = reinterpret_cast<unsigned long long*>(keys.data_ptr<int64_t>());
+    check_status(estd_mesh_raster(px, (long long)m.V, pf, (long long)m.F, 0LL, (long long)m.F, M, (int)H, (int)W, zn,
+                                  ESTD_MESH_RASTER_CLEAR | (preload ? ESTD_MESH_RASTER_PRELOAD : 0), k,
+                                  reinterpret_cast<long long*>(invalid.data_ptr<int64_t>()), cur_stream()), "estd_mesh_raster");
+    check_status(estd_mesh_raster_resolve(px, (long long)m.V, pf, (long long)m.F, M, (int)H, (int)W, k, depth.data_ptr<float>(),
+                                          face.data_ptr<int32_t>(), bary.data_ptr<float>(), facing.data_ptr<int32_t>(), cur_stream()),
+                 "estd_mesh_raster_resolve");
+    return {depth, face, bary, facing, invalid};
+}
+
 // ------------------------------------------------------------------------------------------------ cross-view consistency
 // csrc/depth_consistency.hip: target [H,W] and 1..8 sources of the same size, mats: CPU float32 [S,2,12] (F_s, B_s: host values of the
 // launch arguments) -> (views, visible, depth, rel_err), each [H,W]
@@ -1379,6 +1416,7 @@ TORCH_LIBRARY(estdepth_hip, m)
     m.def("mesh_components(Tensor faces, int n_vertices) -> (Tensor, Tensor, Tensor)");
     m.def("mesh_face_area(Tensor xyz, Tensor faces) -> (Tensor, Tensor, Tensor)");
     m.def("mesh_sample(Tensor xyz, Tensor faces, Tensor? attrs, int n_samples, int seed) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("mesh_raster(Tensor xyz, Tensor faces, Tensor mat, int H, int W, float z_near, bool preload) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("tsdf_raycast_color(Tensor volume, Tensor color, Tensor mat, int H, int W, float t_min, float dt, int n_steps, float w_min) -> "
           "(Tensor, Tensor, Tensor, Tensor)");
     m.def("depth_consistency(Tensor target, Tensor[] sources, Tensor mats, float px_max, float rel_max, float z_near) -> "
@@ -1443,6 +1481,7 @@ TORCH_LIBRARY_IMPL(estdepth_hip, CUDA, m)
     m.impl("mesh_components", mesh_components);
     m.impl("mesh_face_area", mesh_face_area);
     m.impl("mesh_sample", mesh_sample);
+    m.impl("mesh_raster", mesh_raster);
     m.impl("tsdf_raycast_color", tsdf_raycast_color);
     m.impl("depth_consistency", depth_consistency);
     m.impl("cloud_cell_keys", cloud_cell_keys);

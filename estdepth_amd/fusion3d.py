@@ -345,15 +345,19 @@ class TSDFVolume:
         write_ply(path, rec.numpy(), rgb, faces=faces)
         return rec.shape[0], faces.shape[0]
 
-    def compare(self, other, threshold=0.05, w_min=1.0, max_dist=None, downsample=None, cell=None, sample=None, seed=0):
+    def compare(self, other, threshold=0.05, w_min=1.0, max_dist=None, downsample=None, cell=None, sample=None, seed=0, visible=None):
         """The 3D scores (``cloud_metrics.compare_clouds``: accuracy, completeness, chamfer, precision / recall / F-score at ``threshold``
         metres, ...) of this volume's surface as the prediction against ``other`` as the ground truth: another ``TSDFVolume`` -- both sides
         go through ``extract_points(w_min)`` -- or a dict with ``xyz`` [N,3] and optionally ``normal`` / ``color`` (device tensors or numpy
         arrays, e.g. what ``read_ply`` returns).  Normals are compared when both sides have them, colours when both have a ``color``.
         ``sample=density`` (points per square metre) scores surfaces instead of vertices: a ``TSDFVolume`` side goes through
         ``extract_mesh(w_min)`` and ``sample_mesh(density=sample, seed=seed)``, a dict side with ``faces`` through ``sample_mesh``, a
-        dict without faces stays the cloud it is; with the default None nothing of this runs."""
+        dict without faces stays the cloud it is; with the default None nothing of this runs.
+        ``visible=dict(cam_poses, cam_intr, image_hw, min_views=1, tol=None, depth_max=None)`` (needs ``sample``) drops the ground-truth
+        samples the cameras did not see, as ``cloud_metrics.compare_meshes`` documents it; the result gains ``n_gt`` / ``n_gt_visible``."""
         from . import cloud_metrics
+        if visible is not None and sample is None:
+            raise RuntimeError("compare: visible= needs sample=density (the ground-truth surface is sampled, then restricted)")
 
         def side(x):
             if sample is not None:
@@ -374,10 +378,16 @@ class TSDFVolume:
                     out[k] = (torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)) if isinstance(v, np.ndarray) else v).to(self.device).contiguous()
             return out
         a, b = side(self), side(other)
-        return cloud_metrics.compare_clouds(a["xyz"], b["xyz"], threshold=threshold, max_dist=max_dist, downsample=downsample,
-                                            pred_normal=a.get("normal") if "normal" in b else None, gt_normal=b.get("normal") if "normal" in a else None,
-                                            pred_color=a.get("color") if "color" in b else None, gt_color=b.get("color") if "color" in a else None,
-                                            cell=cell)
+        seen = None
+        if visible is not None:
+            gt_mesh = other.extract_mesh(w_min=w_min) if isinstance(other, TSDFVolume) else other
+            b, n_gt, n_seen = cloud_metrics.restrict_to_visible(gt_mesh, b, visible, threshold, "compare")
+            seen = dict(n_gt=n_gt, n_gt_visible=n_seen)
+        out = cloud_metrics.compare_clouds(a["xyz"], b["xyz"], threshold=threshold, max_dist=max_dist, downsample=downsample,
+                                           pred_normal=a.get("normal") if "normal" in b else None, gt_normal=b.get("normal") if "normal" in a else None,
+                                           pred_color=a.get("color") if "color" in b else None, gt_color=b.get("color") if "color" in a else None,
+                                           cell=cell)
+        return out if seen is None else dict(out, **seen)
 
     def reset(self):
         self.volume.zero_()

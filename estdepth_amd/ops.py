@@ -1436,6 +1436,50 @@ def mesh_sample(xyz, faces, attrs, n_samples, seed=0):
     return out_xyz, face, bary, normal, out_attrs, area, invalid
 
 
+# ---------------------------------------------------------------------------------- mesh rasteriser (csrc/mesh/mesh_raster.hip)
+MESH_RASTER_PRELOAD, MESH_RASTER_CLEAR = 1, 2      # ESTD_MESH_RASTER_PRELOAD, ESTD_MESH_RASTER_CLEAR (include/estd_hip.h)
+
+
+def _host_doubles(t, n, op, name, shape):
+    """host values a kernel takes as float64: exactly ``n`` of them, all finite -> a ctypes array"""
+    _need(isinstance(t, torch.Tensor) and not t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == n,
+          "%s: %s must be a contiguous CPU float64 tensor %s" % (op, name, shape))
+    flat = t.reshape(-1).tolist()
+    _need(all(math.isfinite(v) for v in flat), "%s: %s holds a value that is not finite" % (op, name))
+    return (ctypes.c_double * n)(*flat)
+
+
+def mesh_raster(xyz, faces, mat, H, W, z_near, preload=False):
+    """Rasterise the mesh ``xyz`` [V,3] float32 / ``faces`` [F,3] int32 with the host matrix ``mat`` (CPU float64 [12],
+    camera.mesh_raster_matrix) into an ``H`` x ``W`` image -> (depth [H,W] float32: the z-depth of the nearest triangle, 0 = nothing; face
+    [H,W] int32: its index, -1 = nothing; bary [H,W,2]: the perspective-correct weights of its second and third vertex; facing [H,W]
+    int32: +1 counter-clockwise seen from the camera, -1 clockwise, 0 = nothing; invalid [1] int64 on the device: the triangles with an
+    index outside [0, V), which cover nothing).  Defined to the bit: include/estd_hip.h (estd_mesh_raster, estd_mesh_raster_resolve).
+    ``preload=True`` puts a load in front of the atomic minimum (faster where thousands of triangles share pixels; the same bits).  The key buffer is
+    allocated here and cleared by the first entry point with a memset on the stream (ESTD_MESH_RASTER_CLEAR)."""
+    H, W, z_near = int(H), int(W), float(z_near)
+    if _use_torch():
+        return tuple(T().mesh_raster(xyz, faces, mat, H, W, z_near, bool(preload)))
+    op = "mesh_raster"
+    n_vertices, n_faces = _mesh(xyz, faces, op)
+    m = _host_doubles(mat, 12, op, "mat", "[12] (3x4 row-major)")
+    _map_size(H, W, op, "the image")
+    _not_negative(z_near, op, "z_near")
+    dev = faces.device
+    with torch.cuda.device(dev):
+        keys = torch.empty((H, W), device=dev, dtype=torch.int64)
+        depth, face, bary = torch.empty((H, W), device=dev), torch.empty((H, W), device=dev, dtype=torch.int32), torch.empty((H, W, 2), device=dev)
+        facing = torch.empty((H, W), device=dev, dtype=torch.int32)
+        invalid = torch.empty(1, device=dev, dtype=torch.int64)
+        px, pf = _p(xyz) if n_vertices else None, _p(faces) if n_faces else None
+        N.check(N.lib().estd_mesh_raster(px, n_vertices, pf, n_faces, 0, n_faces, m, H, W, z_near, MESH_RASTER_CLEAR | (MESH_RASTER_PRELOAD if preload else 0), _p(keys),
+                                         _p(invalid),
+                                         _stream()), "estd_mesh_raster")
+        N.check(N.lib().estd_mesh_raster_resolve(px, n_vertices, pf, n_faces, m, H, W, _p(keys), _p(depth), _p(face), _p(bary), _p(facing),
+                                                 _stream()), "estd_mesh_raster_resolve")
+    return depth, face, bary, facing, invalid
+
+
 # ---------------------------------------------------------------------------------- cross-view consistency (csrc/depth_consistency.hip)
 CONSISTENCY_MAX_SOURCES = N.CONSISTENCY_MAX_SOURCES
 

@@ -831,6 +831,62 @@ int estd_mesh_sample(const float* xyz, long long n_vertices, const int* faces, l
                      unsigned long long seed, float* out_xyz, int* out_face, float* out_bary, float* out_normal, float* out_attrs,
                      estd_stream_t stream);
 
+/* A z-buffer rasteriser for triangle lists (csrc/mesh/mesh_raster.hip; numpy form: tests/mesh_raster_ref.py): which triangle a camera
+ * sees in every pixel, at which depth, where on the triangle and from which side.  Conventions of the TSDF ray-cast and integration:
+ * pixel centres on integers, depth = the z-depth along the optical axis, poses camera-to-world.  Two entry points, rasterise and
+ * resolve, with a key buffer between them that the caller owns.
+ *
+ * Inputs of both: xyz [V][3] float32, faces [F][3] int32, contiguous, on the device; mat: 12 DOUBLES ON THE HOST, 3 x 4 row-major,
+ *   M = K [R^T | -R^T c] formed in float64 (estdepth_amd/camera.py, mesh_raster_matrix), so that the third component of M (x, 1) is the
+ *   z-depth and pixel (u, v) is the ray direction (u, v, 1) of that space; H, W: the image.
+ *
+ * The arithmetic.  Every operation below is ONE IEEE float64 operation in the order written, never contracted into an fma.
+ *   per vertex, widened to float64:   q_j = ((M_j0 * x + M_j1 * y) + M_j2 * z) + M_j3,   j = 0, 1, 2
+ *   per triangle (q0, q1, q2):        n0 = q1 x q2,  n1 = q2 x q0,  n2 = q0 x q1,  each component a_y * b_z - a_z * b_y (two rounded
+ *                                     products, one difference);   det = (n0x * q0x + n0y * q0y) + n0z * q0z
+ *   per pixel (u, v), as doubles:     E_k = (n_kx * u + n_ky * v) + n_kz;   S = (E_0 + E_1) + E_2
+ *     the triangle COVERS the pixel iff  E_0, E_1, E_2 >= 0 and S > 0,  or  E_0, E_1, E_2 <= 0 and S < 0  (both windings are drawn);
+ *     c = det / S;  d = (float) c;  the triangle CONTRIBUTES iff d is finite and d > z_near.
+ *   The cross product is exactly antisymmetric, so two triangles that share an edge see the same edge function with opposite sign
+ *   and no pixel falls between them; a pixel on the edge belongs to both.  No clipping: the test is a ray-triangle test, a triangle
+ *   that crosses the camera plane is drawn where its hit lies in front of z_near.  A comparison with a NaN is false: a triangle with
+ *   a vertex that is not finite covers nothing, one of no area (S = 0 everywhere) neither.
+ *   The winner of a pixel: key = ((uint64) bits(d) << 32) | f, the smallest key over all contributing triangles f -- d is a positive
+ *   finite float32, whose bit pattern orders like its value, so the nearest surface wins and among equal depths the smallest face
+ *   index.  A minimum does not depend on the order of arrival: the maps are bit-identical across calls, bindings, face ranges and
+ *   launch shapes.
+ *   The kernel may skip pixels it can prove uncovered (it sweeps the projections' bounding box with a one-pixel margin when all three
+ *   q_z > z_near, the whole image otherwise) and triangles whose det is 0 or not finite (c is then 0, infinite or a NaN).
+ *
+ * estd_mesh_raster (mesh_raster_kernel, one wave per triangle): merges the triangles face_first .. face_first + face_count - 1 into
+ *   keys [H][W] uint64 with 64-bit unsigned atomic minima at agent scope.  keys must be all ones before the first call: the flag
+ *   ESTD_MESH_RASTER_CLEAR makes the call set it so first (a memset with 0xff on `stream`, no kernel); without the flag the call
+ *   accumulates into the buffer as it is, and a mesh rendered in two face ranges gives the bits of one call.  A triangle with an index outside [0, V) is INVALID (estd_mesh_components' rule): never an address, covers
+ *   nothing, and is counted in invalid [1] int64, which the call zeroes first (a memset on `stream`) and raises with one integer
+ *   atomic add per wave: the count of THIS call's range.  flags: ESTD_MESH_RASTER_CLEAR, and ESTD_MESH_RASTER_PRELOAD -- with it a relaxed load stands
+ *   in front of the atomic and skips it when key >= the value read (keys only decrease, so a value read is never smaller than the
+ *   current one and the skip never loses a winner): faster where thousands of triangles want the same pixels, slower elsewhere
+ *   (DESIGN 3.14).  The bits are the same.  face_count == 0 (F == 0
+ *   included): the memsets alone.
+ * estd_mesh_raster_resolve (mesh_resolve_kernel, one lane per pixel, a later launch on the same stream): unpacks keys and recomputes
+ *   the winner's E_k and S (the same operations, the same bits).  Every pixel of every map is written by every call:
+ *     depth [H][W] float32 = d, 0 = nothing;   face [H][W] int32 = f, -1 = nothing;
+ *     bary [H][W][2] float32 = ((float)(E_1 / S), (float)(E_2 / S)): E_k / S is the 3D barycentric coordinate, so these are the
+ *       perspective-correct weights of the second and third vertex and the point is a + b1 (b - a) + b2 (c - a);  0 0 = nothing;
+ *     facing [H][W] int32 = +1 where S < 0, -1 where S > 0, 0 = nothing: +1 is a triangle whose vertices run counter-clockwise seen
+ *       from the camera (in a right-handed world), i.e. the triangles of estd_tsdf_mesh_faces seen from the free side give +1.
+ *   A key that names no face of this mesh (a foreign buffer) gives the empty pixel: still never an address.
+ * ESTD_ERR_ARG, before any launch and with no device needed: a negative size, H or W <= 0, a null mat or one with an element that is
+ *   not finite, a null xyz with V > 0 or faces with F > 0, a null keys / invalid / output map, z_near negative or not finite, an
+ *   unknown flag, a face range outside [0, F].  ESTD_ERR_UNSUPPORTED: H * W, V or 3 F beyond 2^31 - 1. */
+#define ESTD_MESH_RASTER_PRELOAD 1
+#define ESTD_MESH_RASTER_CLEAR 2
+int estd_mesh_raster(const float* xyz, long long n_vertices, const int* faces, long long n_faces, long long face_first, long long face_count,
+                     const double* mat, int H, int W, float z_near, int flags, unsigned long long* keys, long long* invalid,
+                     estd_stream_t stream);
+int estd_mesh_raster_resolve(const float* xyz, long long n_vertices, const int* faces, long long n_faces, const double* mat, int H, int W,
+                             const unsigned long long* keys, float* depth, int* face, float* bary, int* facing, estd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,13 @@ ground-truth depth.  Needs an MI355X (the model has no CPU path).
         # --mesh-min-component when given), sampled by area at 2500 points per square metre (fusion3d.sample_mesh on
         # csrc/mesh/mesh_sample.hip) before the two are compared; recon_3d gains sampled: density, n_pred, n_gt, area_pred, area_gt,
         # invalid_pred, invalid_gt.  A GT.ply without faces is scored as the cloud it is (area_gt: null)
+    python tools/run_stream.py --synthetic 8 --out /tmp/eval --fuse /tmp/eval/scene.ply --score-3d GT.ply --score-sample 2500 --score-visible
+        # + only the ground truth the cameras saw: GT.ply's mesh is rendered at the pose, intrinsics and size of every fused target
+        # (estdepth_amd.mesh_render on csrc/mesh/mesh_raster.hip) and its samples that no target (--score-visible N: fewer than N targets)
+        # saw within --depth-max are dropped before the comparison; recon_3d.sampled gains n_gt_visible and visible_share
+    python tools/run_stream.py --synthetic 8 --out /tmp/eval --fuse /tmp/eval/scene.ply --score-3d GT.ply --render-gt-mesh
+        # + ground-truth depth from the mesh: the same renders go to <out>/gt_mesh_depth/<stem>.npy, and the predictions are scored against
+        # them (errors_vs_gt_mesh, gt_mesh_coverage, errors_on_gt_mesh_covered): the 2D protocol of scenes that ship a mesh and no depth
     python tools/run_stream.py --synthetic 8 --out /tmp/eval --fuse /tmp/eval/scene.ply --track
         # + frame-to-model tracking (estdepth_amd.tracking): from the second fused target on, every target's pose is refined against the
         # volume (TSDFVolume.track: point-to-plane alignment of its depth map with the ray-cast model) before the target is fused -- the
@@ -99,6 +106,18 @@ class GroundTruthStream:
         return outputs, None, None
 
 
+def ply_face_count(path):
+    """the number of faces a PLY header announces (0 without a face element)"""
+    with open(path, "rb") as f:
+        for _ in range(200):
+            line = f.readline().strip()
+            if line.startswith(b"element face"):
+                return int(line.split()[2])
+            if not line or line == b"end_header":
+                break
+    return 0
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--scene-dir")
@@ -138,6 +157,12 @@ def parse(argv=None):
     ap.add_argument("--score-sample", type=float, default=None, metavar="DENSITY", help="with --score-3d: score surfaces instead of vertices -- the "
                     "fused side is its triangle mesh (after --mesh-min-component when given), a GT.ply with faces is read as a mesh, and both are "
                     "sampled by area at DENSITY points per square metre (fusion3d.sample_mesh); recon_3d gains a sampled block")
+    ap.add_argument("--score-visible", type=int, nargs="?", const=1, default=None, metavar="MIN_VIEWS", help="with --score-3d GT.ply (a mesh) and "
+                    "--score-sample: render the ground-truth mesh at every fused target's pose, intrinsics and size and drop its samples that "
+                    "fewer than MIN_VIEWS (default 1) targets saw within --depth_max (mesh_render.visible_mask); recon_3d.sampled gains "
+                    "n_gt_visible and visible_share")
+    ap.add_argument("--render-gt-mesh", action="store_true", help="with --score-3d GT.ply (a mesh): write its depth at every fused target's pose "
+                    "to <out>/gt_mesh_depth and score the predictions against it: errors_vs_gt_mesh, gt_mesh_coverage, errors_on_gt_mesh_covered")
     ap.add_argument("--score-downsample", type=float, default=None, help="with --score-3d: voxel-grid down-sampling of both clouds first (metres)")
     ap.add_argument("--track", action="store_true", help="with --fuse: refine every target's pose against the fused volume before the target is "
                     "fused (TSDFVolume.track), from the second fused target on")
@@ -166,6 +191,15 @@ def parse(argv=None):
         ap.error("--score-sample needs --score-3d")
     if args.score_sample is not None and not (args.score_sample > 0 and args.score_sample < float("inf")):
         ap.error("--score-sample must be a positive density in points per square metre")
+    for flag, on in (("--score-visible", args.score_visible is not None), ("--render-gt-mesh", args.render_gt_mesh)):
+        if on and not isinstance(args.score_3d, str):
+            ap.error("%s needs --score-3d GT.ply (a triangle mesh to render)" % flag)
+        if on and os.path.exists(args.score_3d) and ply_face_count(args.score_3d) == 0:
+            ap.error("%s needs a GT.ply with faces: %s has none, and a point cloud cannot be rendered" % (flag, args.score_3d))
+    if args.score_visible is not None and args.score_sample is None:
+        ap.error("--score-visible needs --score-sample DENSITY (the samples of the ground-truth surface are what is restricted)")
+    if args.score_visible is not None and args.score_visible < 1:
+        ap.error("--score-visible must be at least 1")
     if args.track and not args.fuse:
         ap.error("--track needs --fuse PATH.ply")
     if not args.scene_dir and not args.synthetic:
@@ -224,6 +258,7 @@ def run(args):
         geo = ConsistencyWindow(radius=args.geo_filter, min_views=args.geo_min_views, px_max=args.geo_px, rel_max=args.geo_rel)
 
     tracked, track_ms, fused_at = [], [], []
+    seen_by = {}                     # --score-visible / --render-gt-mesh: frame name -> (intrinsics, image size, prediction, ground truth)
 
     def refined_pose(name, dmap, pose, intr):
         """--track: the pose to fuse a target at -- its own until something is fused, then the one TSDFVolume.track finds against the volume"""
@@ -329,6 +364,8 @@ def run(args):
             rec = geo.push(dmap, target["cam_pose"].reshape(4, 4), intr, extra={"rgb": rgb, "gt": gt, "name": target["img_path"]})
             if rec is not None:
                 take_filtered(rec)
+        if args.score_visible is not None or args.render_gt_mesh:
+            seen_by[target["img_path"]] = (s["cam_intr"].reshape(3, 3).clone(), tuple(s["img"].shape[-2:]), pred, gt)
         if args.render_fused:
             targets.append((target["img_path"], target["cam_pose"].reshape(4, 4), s["cam_intr"].reshape(3, 3), tuple(s["img"].shape[-2:]), pred, gt))
     if geo is not None:
@@ -381,11 +418,37 @@ def run(args):
                 faces = read_ply(args.score_3d, faces=True)["faces"]
                 if faces.shape[0]:
                     other["faces"] = faces
+            visible = None
+            if args.score_visible is not None:                               # only the ground truth some fused target saw
+                visible = dict(cam_poses=torch.stack([p for _, p in fused_at]), cam_intr=torch.stack([seen_by[n][0] for n, _ in fused_at]),
+                               image_hw=seen_by[fused_at[0][0]][1], min_views=args.score_visible, depth_max=args.depth_max)
             scores = compare_meshes(volume.extract_mesh(min_component=args.mesh_min_component or 0), other, args.score_sample,
-                                    threshold=args.score_threshold, max_dist=max_dist, downsample=args.score_downsample)
+                                    threshold=args.score_threshold, max_dist=max_dist, downsample=args.score_downsample, visible=visible)
         torch.cuda.synchronize()
         report["recon_3d"] = dict(scores, threshold=args.score_threshold, max_dist=max_dist, downsample=args.score_downsample, ground_truth=gt_name,
                                   compare_ms=1e3 * (time.time() - t0))
+    if volume is not None and args.render_gt_mesh:
+        # the ground-truth mesh in every fused target's camera: depth maps for a scene that ships a mesh and no depth
+        from estdepth_amd.fusion3d import read_ply
+        from estdepth_amd.mesh_render import render_mesh
+        from estdepth_amd.metrics import compute_valid_depth_mask
+        gt_mesh = read_ply(args.score_3d, faces=True)
+        gt_mesh = {"xyz": gt_mesh["xyz"], "faces": gt_mesh["faces"]}
+        errs_mesh, errs_depth, n_px, n_hit = RunningErrors(), RunningErrors(), 0, 0
+        out_dir = os.path.join(args.out, "gt_mesh_depth")
+        os.makedirs(out_dir, exist_ok=True)
+        for name, pose in fused_at:
+            intr, hw, pred, gt = seen_by[name]
+            depth = render_mesh(gt_mesh, pose, intr, hw, normals=None, color=False)["depth"].cpu().numpy()
+            np.save(os.path.join(out_dir, os.path.splitext(os.path.basename(str(name)))[0] + ".npy"), depth[None])
+            depth = to_gt_grid(depth.astype(np.float64), gt.shape)
+            hit = compute_valid_depth_mask(depth)
+            both = hit & compute_valid_depth_mask(gt) & compute_valid_depth_mask(pred)             # ONE pixel set for both scores
+            n_px += depth.size
+            n_hit += int((depth > 0).sum())
+            errs_mesh.add(np.where(both, pred, 0.0), np.where(both, depth, 0.0))
+            errs_depth.add(np.where(both, pred, 0.0), gt)
+        report.update(errors_vs_gt_mesh=errs_mesh.mean(), gt_mesh_coverage=n_hit / max(n_px, 1), errors_on_gt_mesh_covered=errs_depth.mean())
     if volume is not None and args.render_fused:
         # the fused model in every target's camera, on the pixel grid and in the units of the per-frame predictions
         from estdepth_amd.metrics import compute_valid_depth_mask

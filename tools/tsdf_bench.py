@@ -39,7 +39,15 @@ included, or where scipy is missing a min-label propagation loop in torch on the
 
 times the mesh sampling (csrc/mesh/mesh_sample.hip) on that mesh and on the 204 800-triangle grid of tests/mesh_components_ref.py: the
 area kernel, the sample kernel at 10^5 and 10^6 samples and the whole fusion3d.sample_mesh, between device events, behind the cache flush
-and back to back, beside the same sampling formed with torch operators on the same prefix sums."""
+and back to back, beside the same sampling formed with torch operators on the same prefix sums.
+
+    python tools/tsdf_bench.py --mesh-raster [--reps 100] [--out profiles/mesh_raster_bench.txt]
+
+times the mesh rasteriser (csrc/mesh/mesh_raster.hip) at 640 x 480: the raster kernel with and without the load in front of its atomic,
+the resolve kernel and the whole mesh_render.render_mesh, between device events, behind the cache flush and back to back -- for that
+mesh from the held-out pose of the ray-cast bench, for a 204 800-triangle grid that fills the image, for a two-triangle wall that fills
+it (the large-box regime) and for 4096 coincident small triangles (the contention regime) -- beside TSDFVolume.render of the same volume
+from the same pose."""
 import argparse
 import os
 import sys
@@ -81,6 +89,7 @@ def main():
     ap.add_argument("--mesh", action="store_true", help="time extract_mesh (kernels and host ordering apart) beside extract_points")
     ap.add_argument("--mesh-components", action="store_true", help="time the mesh components and filter_mesh beside a host / torch yardstick")
     ap.add_argument("--mesh-sample", action="store_true", help="time the mesh sampling (csrc/mesh/mesh_sample.hip) beside the same sampling with torch operators")
+    ap.add_argument("--mesh-raster", action="store_true", help="time the mesh rasteriser (csrc/mesh/mesh_raster.hip) beside TSDFVolume.render")
     ap.add_argument("--color", action="store_true", help="time the colour fuse, the edge colours and the colour render beside the plain figures")
     args = ap.parse_args()
     if args.raycast:
@@ -91,6 +100,8 @@ def main():
         return components_main(args)
     if args.mesh_sample:
         return sample_main(args)
+    if args.mesh_raster:
+        return raster_main(args)
     if args.color:
         return color_main(args)
     import tsdf_ref as R
@@ -378,6 +389,91 @@ def sample_main(args):
                       "    sample_mesh, whole call (finite check, area kernel, max and total read-backs, cumsum, sample kernel) %8.4f ms cold  %8.4f ms warm"
                       % (t_all, t_allw)]
     lines.append("  no bar is set (the parent has nothing comparable); a search narrowed per wave was not built and is not measured")
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        open(args.out, "w").write(text + "\n")
+
+
+def raster_main(args):
+    import ctypes
+    import tsdf_ref as R
+    import tsdf_raycast_ref as RR
+    from estdepth_amd import _native, camera, ops
+    from estdepth_amd.fusion3d import TSDFVolume, frustum_volume
+    from estdepth_amd.mesh_render import render_mesh
+    assert torch.cuda.is_available(), "tools/tsdf_bench.py needs a ROCm device"
+    dev = torch.device("cuda:0")
+    H, W, T, vox, dmin, dmax, dims = 480, 640, 3, 0.03, 0.1, 10.0, (256, 256, 256)
+    reps = min(args.reps, 100)
+    K = R.intrinsics(H, W)
+    poses = R.scene_poses(T, seed=1)
+    depths = torch.from_numpy(np.stack([R.raycast_scene(P, K, H, W) for P in poses]).astype(np.float32)).to(dev)
+    flush = torch.empty(256 << 20, device=dev)          # 1 GiB
+    origin = frustum_volume(torch.from_numpy(poses[0]), torch.from_numpy(K), (H, W), dmin, dmax, dims, vox)
+    vol = TSDFVolume(dims, vox, origin, device=dev)
+    vol.integrate(depths, torch.from_numpy(poses), torch.from_numpy(K))
+    m = vol.extract_mesh()
+    pose = RR.HELD_OUT_POSE
+    eye = np.eye(4)
+    Ki = np.linalg.inv(K)
+    corner = lambda u, v, z: tuple((Ki @ np.asarray([u, v, 1.0])) * z)                     # the point of pixel (u, v) at depth z, camera at the origin
+    n = 320                                                                                 # 2 n^2 = 204 800 triangles over the whole image
+    gu, gv = np.meshgrid(np.linspace(-2.0, W + 1.0, n + 1), np.linspace(-2.0, H + 1.0, n + 1))
+    grid_xyz = np.stack([np.asarray(corner(u, v, 2.5 + 0.3 * np.sin(0.01 * u + 0.02 * v))) for u, v in zip(gu.ravel(), gv.ravel())]).astype(np.float32)
+    i, j = np.meshgrid(np.arange(n), np.arange(n))
+    a = (j * (n + 1) + i).ravel()
+    grid_faces = np.concatenate([np.stack([a, a + 1, a + n + 2], 1), np.stack([a, a + n + 2, a + n + 1], 1)]).astype(np.int32)
+    grid_faces = grid_faces[np.random.default_rng(0).permutation(grid_faces.shape[0])]      # no order in memory or on the screen
+    wall_xyz = np.asarray([corner(-8, -8, 2.0), corner(W + 8, -8, 2.0), corner(W + 8, H + 8, 2.5), corner(-8, H + 8, 2.5)], np.float32)
+    small = np.asarray([corner(300, 200, 2.0), corner(306, 201, 2.0), corner(302, 207, 2.0)], np.float32)     # about 20 pixels
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+    cases = [("the mesh of the %d x %d x %d volume from the held-out pose" % dims, m["xyz"].contiguous(), m["faces"].contiguous(), pose),
+             ("a 320 x 320 grid of quads over the whole image, triangles in shuffled order (about 1.5 pixels each)", t(grid_xyz), t(grid_faces), eye),
+             ("a wall of two triangles that fills the image (4800 blocks of 8 x 8 pixels each, dealt to 64 waves)", t(wall_xyz),
+              t(np.asarray([(0, 1, 2), (0, 2, 3)], np.int32)), eye),
+             ("4096 coincident triangles of about 20 pixels (every wave wants the same keys)", t(small), t(np.asarray([(0, 1, 2)] * 4096, np.int32)), eye)]
+    lib = _native.lib()
+    p = lambda x: ctypes.c_void_p(x.data_ptr())
+    stream = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    lines = ["tsdf_bench --mesh-raster: %d x %d, mean of %d calls per figure between device events, 'cold' = behind a 1 GiB cache flush, 'warm' = back to "
+             "back, %s" % (W, H, reps, torch.cuda.get_device_name(0))]
+    keys = torch.empty((H, W), device=dev, dtype=torch.int64)
+    invalid = torch.empty(1, device=dev, dtype=torch.int64)
+    out = [torch.empty((H, W), device=dev), torch.empty((H, W), device=dev, dtype=torch.int32), torch.empty((H, W, 2), device=dev),
+           torch.empty((H, W), device=dev, dtype=torch.int32)]
+    for name, xyz, faces, P in cases:
+        V, F = xyz.shape[0], faces.shape[0]
+        mat = camera.mesh_raster_matrix(torch.from_numpy(P), torch.from_numpy(K))
+        cm = (ctypes.c_double * 12)(*mat.tolist())
+
+        def raster(flags):
+            assert lib.estd_mesh_raster(p(xyz), V, p(faces), F, 0, F, cm, H, W, 1e-3, flags | ops.MESH_RASTER_CLEAR, p(keys), p(invalid), stream()) == 0
+
+        def resolve():
+            assert lib.estd_mesh_raster_resolve(p(xyz), V, p(faces), F, cm, H, W, p(keys), p(out[0]), p(out[1]), p(out[2]), p(out[3]), stream()) == 0
+        clear = lambda: keys.fill_(-1)
+        whole = lambda: render_mesh(dict(xyz=xyz, faces=faces), P, K, (H, W))
+        bare = lambda: render_mesh(dict(xyz=xyz, faces=faces), P, K, (H, W), normals=None, color=False)
+        raster(0)
+        resolve()
+        covered = int((out[1] >= 0).sum().item())
+        figs = [timed(lambda: raster(ops.MESH_RASTER_PRELOAD), reps, flush), timed(lambda: raster(ops.MESH_RASTER_PRELOAD), reps), timed(lambda: raster(0), reps, flush),
+                timed(lambda: raster(0), reps), timed(resolve, reps, flush), timed(resolve, reps), timed(clear, reps),
+                timed(whole, reps, flush), timed(whole, reps), timed(bare, reps, flush), timed(bare, reps)]
+        lines += ["%s: %d vertices, %d triangles, %d of %d pixels covered" % (name, V, F, covered, H * W),
+                  "  mesh_raster_kernel<1>, load in front of the atomic (+ the two memsets)  %8.4f ms cold  %8.4f ms warm" % (figs[0], figs[1]),
+                  "  mesh_raster_kernel<0>, atomic alone, the default (+ the two memsets)    %8.4f ms cold  %8.4f ms warm" % (figs[2], figs[3]),
+                  "  mesh_resolve_kernel                                                    %8.4f ms cold  %8.4f ms warm" % (figs[4], figs[5]),
+                  "  (a fill of the 2.4 MB key buffer alone, warm: %.4f ms)" % figs[6],
+                  "  render_mesh, whole call with face normals (matrix on the host, area kernel, gathers, one read-back) %8.4f ms cold  %8.4f ms warm"
+                  % (figs[7], figs[8]),
+                  "  render_mesh(normals=None, color=False): depth, face, bary, facing alone %8.4f ms cold  %8.4f ms warm" % (figs[9], figs[10])]
+    cast = lambda: vol.render(torch.from_numpy(pose), torch.from_numpy(K), (H, W))
+    lines += ["yardstick: TSDFVolume.render of the same volume from the held-out pose (ray casting, csrc/tsdf_raycast.hip), whole call  %8.4f ms cold  "
+              "%8.4f ms warm" % (timed(cast, reps, flush), timed(cast, reps)),
+              "no bar is set (the parent has nothing comparable)"]
     text = "\n".join(lines)
     print(text)
     if args.out:
