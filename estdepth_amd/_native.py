@@ -130,6 +130,17 @@ class CloudNearestDesc(ctypes.Structure):
     ]
 
 
+class MeshNearestDesc(ctypes.Structure):
+    """Mirror of struct estd_mesh_nearest_desc (include/estd_hip.h)."""
+    _fields_ = [
+        ("M", ctypes.c_longlong), ("B", ctypes.c_longlong), ("P", ctypes.c_longlong),
+        ("query", ctypes.c_void_p), ("order", ctypes.c_void_p), ("big_records", ctypes.c_void_p), ("records", ctypes.c_void_p),
+        ("cell_start", ctypes.c_void_p), ("dist", ctypes.c_void_p), ("face", ctypes.c_void_p), ("bary", ctypes.c_void_p),
+        ("closest", ctypes.c_void_p),
+        ("lo", ctypes.c_float * 3), ("cell", ctypes.c_float), ("max_dist", ctypes.c_float), ("dims", ctypes.c_int * 3),
+    ]
+
+
 class FrameAlignDesc(ctypes.Structure):
     """Mirror of struct estd_frame_align_desc (include/estd_hip.h)."""
     _fields_ = [
@@ -241,6 +252,13 @@ _SIGNATURES = {
                                         ctypes.c_void_p, c_stream]),
     "estd_mesh_raster_resolve": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_double),
                                                 ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5 + [c_stream]),
+    "estd_mesh_tri_bins": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_float),
+                                          ctypes.c_float, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, c_stream]),
+    "estd_mesh_tri_fill": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_float),
+                                          ctypes.c_float, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong,
+                                          ctypes.c_void_p, ctypes.c_void_p, c_stream]),
+    "estd_mesh_nearest": (ctypes.c_int, [ctypes.POINTER(MeshNearestDesc), c_stream]),
 }
 
 # the superseded A/B kernels: exported only by a library built with ESTD_BUILD_AB=1 (estdepth_amd/build.py)

@@ -10,6 +10,10 @@ precision / recall / F-score at a threshold.  The clouds are what ``TSDFVolume.e
     grid = PointGrid(target, max_dist=1.0)                             # sort and cell table once ...
     dist, index = grid.query(points)                                   # ... any number of queries
 
+    tri = TriangleGrid(dict(xyz=xyz, faces=faces), max_dist=1.0)       # the same for a triangle mesh (csrc/mesh/mesh_distance.hip):
+    dist, face, bary = tri.query(points, bary=True)                    # the distance to the SURFACE, the face and where on it
+    scores = compare_meshes(pred_mesh, gt_mesh, 1111.0, exact=True)    # surfaces scored against surfaces, not against samples
+
 The nearest-neighbour result is defined to the bit (include/estd_hip.h, estd_cloud_nearest): per query the smallest fp32
 ``d2 = fma(dx, dx, fma(dy, dy, dz * dz))`` over ALL targets, the smallest original index attaining it, found iff ``d2 <= max_dist^2``;
 ``dist = sqrt(d2)`` or ``max_dist``, ``index`` or -1.  The uniform grid behind it only decides which targets are looked at first; the cell
@@ -139,6 +143,120 @@ def nearest(query, target, max_dist, cell=None):
     return PointGrid(target, max_dist, cell).query(query)
 
 
+MAX_PAIRS = ops.MESH_DISTANCE_MAX_PAIRS      # the (cell, face) pairs of a TriangleGrid
+BIG_CELLS = ops.MESH_DISTANCE_BIG_CELLS      # a triangle whose box covers more cells goes on the big list
+
+
+class TriangleGrid:
+    """The search structure of one triangle mesh for point-to-SURFACE distances (csrc/mesh/mesh_distance.hip; the contract:
+    include/estd_hip.h, estd_mesh_nearest): every valid triangle registered in the cells its bounding box covers, the 48-byte records in
+    cell order, and the big list of the triangles whose box covers more than ``big_cells`` cells, which every query tests in full.
+    ``mesh``: a dict with ``xyz`` [V,3] and ``faces`` [F,3] (device tensors or numpy arrays).  A face with an index outside [0, V), with a
+    vertex that is not finite or without area in fp32 is ignored and counted: ``.invalid``; ``.faces_valid`` are the others.
+    ``cell``: the cell edge; None: ``sqrt(2 x the median area)`` of the triangles with an area -- about their edge, and the median so
+    that two wall-sized triangles among thousands of small ones do not set it: they go on the big list -- and not below
+    ``max_dist / 32``; ``math.inf``: no grid, every valid triangle on the big list.  ``big_cells``: None for the default (64), 0 forces
+    the big list as well, "grid" forces every triangle into the grid.  The caps of ``grid_plan`` hold, and at most 2^23 pairs: a cell
+    edge that exceeds one grows in steps of 1/8.  None of this changes a bit of a result: the structure only decides what is looked at
+    first."""
+
+    def __init__(self, mesh, max_dist, cell=None, big_cells=None):
+        from . import fusion3d
+        op = "TriangleGrid"
+        self.max_dist = _check_max_dist(max_dist, op)
+        _need(cell is None or (isinstance(cell, (int, float)) and not math.isnan(cell) and cell > 0), "%s: cell must be positive (math.inf: the big list only), got %r" % (op, cell))
+        _need(big_cells is None or big_cells == "grid" or (isinstance(big_cells, int) and 0 <= big_cells < 2 ** 31),
+              "%s: big_cells must be None, 'grid' or a count in 0 .. 2^31 - 1, got %r" % (op, big_cells))
+        _need(isinstance(mesh, dict) and mesh.get("xyz") is not None and mesh.get("faces") is not None, "%s: the mesh must be a dict with 'xyz' and 'faces'" % op)
+        devs = [v.device for v in mesh.values() if isinstance(v, torch.Tensor) and v.is_cuda]
+        faces = fusion3d._faces_arg(mesh["faces"], op, devs[0] if devs else None)
+        _need(faces.dtype == torch.int32, "%s: faces must be int32, got %s" % (op, faces.dtype))
+        xyz = fusion3d._on_device(mesh["xyz"], faces.device)
+        _need(xyz.dim() == 2 and xyz.shape[1] == 3 and xyz.shape[0] < 2 ** 31, "%s: xyz must be [V,3] with V < 2^31, got %s" % (op, tuple(xyz.shape)))
+        _need(faces.shape[0] <= (2 ** 31 - 1) // 3, "%s: at most %d faces, got %d" % (op, (2 ** 31 - 1) // 3, faces.shape[0]))
+        self.device, self.xyz, self.faces = faces.device, xyz, faces
+        dev, V, F = self.device, int(xyz.shape[0]), int(faces.shape[0])
+        self.cell, self.dims, self.lo = float(np.float32(self.max_dist)), (1, 1, 1), torch.zeros(3)
+        self.big_cells = 0 if (cell is not None and math.isinf(cell)) else BIG_CELLS if big_cells is None else big_cells
+        self.records = self.big_records = torch.empty((0, 12), device=dev)
+        self.cell_start = torch.zeros(2, device=dev, dtype=torch.int32)
+        self.invalid, self.faces_valid, self.n_pairs, self.n_big = F, 0, 0, 0
+        # the box and the mean area of the faces that can be valid (indices in range, finite vertices): tuning only, by torch
+        ok = ((faces >= 0) & (faces < V)).all(1) if F else torch.zeros(0, device=dev, dtype=torch.bool)
+        tri = xyz[faces[ok].long()] if F else xyz.new_empty((0, 3, 3))                              # [K,3,3]
+        tri = tri[torch.isfinite(tri).all(2).all(1)]
+        if tri.shape[0] == 0:
+            if F:
+                self.invalid = int(ops.mesh_tri_bins(xyz, faces, self.lo, self.cell, self.dims, 0)[2].item())
+                self.faces_valid = F - self.invalid
+            return
+        lo, hi = tri.amin((0, 1)).cpu(), tri.amax((0, 1)).cpu()
+        self.lo = lo.contiguous()
+        if cell is not None and math.isinf(cell):
+            cell = None
+        if cell is None:
+            area = 0.5 * torch.linalg.cross(tri[:, 1].double() - tri[:, 0].double(), tri[:, 2].double() - tri[:, 0].double()).norm(dim=1)
+            area = area[torch.isfinite(area) & (area > 0)]
+            typical = float(area.median().item()) if area.shape[0] else 0.0
+            cell = max(math.sqrt(2.0 * typical), self.max_dist / RINGS_MAX, float(np.finfo(np.float32).tiny))
+            cell = min(cell, float(np.finfo(np.float32).max) / 4)
+        big = MAX_CELLS if self.big_cells == "grid" else int(self.big_cells)
+        self.cell, self.dims = grid_plan(lo.tolist(), hi.tolist(), 1, self.max_dist, cell)
+        while True:
+            count, flag, invalid = ops.mesh_tri_bins(xyz, faces, self.lo, self.cell, self.dims, big)
+            cum = torch.cumsum(count.to(torch.int64), 0)
+            pairs = int(cum[-1].item())
+            if pairs <= MAX_PAIRS:
+                break
+            _need(self.dims != (1, 1, 1), "%s: %d triangles for the grid, at most %d pairs" % (op, pairs, MAX_PAIRS))
+            self.cell, self.dims = grid_plan(lo.tolist(), hi.tolist(), 1, self.max_dist, self.cell * 1.125)
+        self.invalid = int(invalid.item())
+        self.faces_valid = F - self.invalid
+        self.n_pairs = pairs
+        big_faces = torch.nonzero(flag == 2).reshape(-1)
+        self.n_big = int(big_faces.shape[0])
+        self.big_records = self._records(big_faces)
+        if pairs:
+            keys, pair_face = ops.mesh_tri_fill(xyz, faces, self.lo, self.cell, self.dims, big, (cum - count).contiguous(), pairs)
+            sorted_keys, order = torch.sort(keys, stable=True)
+            cells = self.dims[0] * self.dims[1] * self.dims[2]
+            self.cell_start = torch.searchsorted(sorted_keys, torch.arange(cells + 1, device=dev, dtype=torch.int64), out_int32=True).contiguous()
+            self.records = self._records(pair_face[order].long())
+        else:
+            self.cell, self.dims = float(np.float32(self.max_dist)), (1, 1, 1)                    # no grid: phase B does not run
+
+    def _records(self, face):
+        """the 48-byte records of the faces ``face`` (int64, all valid), gathered here once: the search loads a candidate with three
+        16-byte loads and follows no index"""
+        rec = torch.zeros((face.shape[0], 12), device=self.device, dtype=torch.int32)
+        if face.shape[0]:
+            rec[:, :9] = self.xyz[self.faces[face].long()].reshape(-1, 9).view(torch.int32)
+            rec[:, 9] = face.to(torch.int32)
+        return rec.view(torch.float32)
+
+    def query(self, points, bary=False, closest=False):
+        """``points`` [M,3] (finite) -> (dist [M] float32, face [M] int32[, bary [M,2]][, closest [M,3]]): the distance to the nearest
+        point of the mesh within ``max_dist`` and the face it lies on, the barycentric pair (v, w) of that point (it is
+        a + v (b - a) + w (c - a)) and the point; ``max_dist``, -1 and zeros where there is none."""
+        points = _check_cloud(points, "points", "TriangleGrid.query", self.device)
+        M = int(points.shape[0])
+        if M == 0 or self.faces_valid == 0:                       # nothing to search: no launch
+            out = (torch.full((M,), float(np.float32(self.max_dist)), device=self.device), torch.full((M,), -1, device=self.device, dtype=torch.int32))
+            return out + ((torch.zeros((M, 2), device=self.device),) if bary else ()) + ((torch.zeros((M, 3), device=self.device),) if closest else ())
+        if self.n_pairs:
+            order = torch.sort(ops.cloud_cell_keys(points, self.lo, self.cell, self.dims), stable=True)[1]
+        else:
+            order = torch.arange(M, device=self.device, dtype=torch.int64)
+        dist, face, b, c = ops.mesh_nearest(points, order, self.big_records, self.records, self.cell_start, self.lo, self.cell, self.dims,
+                                            self.max_dist, bary=bary, closest=closest)
+        return (dist, face) + ((b,) if bary else ()) + ((c,) if closest else ())
+
+
+def point_mesh_distance(points, mesh, max_dist, cell=None):
+    """One-shot form of ``TriangleGrid(mesh, max_dist, cell).query(points)`` -> (dist [M], face [M])."""
+    return TriangleGrid(mesh, max_dist, cell).query(points)
+
+
 def voxel_downsample(points, cell, attrs=None):
     """Voxel-grid down-sampling: one point per occupied cell of edge ``cell`` (the grid starts at the cloud's bounding-box minimum), the mean
     of the cell's points -> (points [K,3], attrs [K,C] or None, counts [K] int64), cells in ascending key order (z, then y, then x).
@@ -264,13 +382,84 @@ def restrict_to_visible(mesh, cloud, visible, threshold, op):
     return out, n, int(out["xyz"].shape[0])
 
 
-def compare_meshes(pred, gt, density, threshold=0.05, max_dist=None, downsample=None, seed=0, cell=None, visible=None):
+def _exact_scores(a, b, pred, gt, dev, threshold, max_dist, downsample, cell):
+    """compare_meshes(exact=True) behind the sampling: the clouds ``a`` (of pred) and ``b`` (of gt, already restricted) are the QUERIES,
+    the meshes the targets -> the dict of compare_clouds plus ``exact``"""
+    from . import fusion3d
+    _need(isinstance(threshold, (int, float)) and math.isfinite(threshold) and threshold > 0, "compare_meshes: threshold must be positive and finite, got %r" % (threshold,))
+    max_dist = _check_max_dist(20.0 * threshold if max_dist is None else max_dist, "compare_meshes")
+    _need(threshold <= max_dist, "compare_meshes: threshold %g must not exceed max_dist %g" % (threshold, max_dist))
+    _need(downsample is None or (isinstance(downsample, (int, float)) and math.isfinite(downsample) and downsample > 0),
+          "compare_meshes: downsample must be a positive voxel edge, got %r" % (downsample,))
+    both = lambda k: k in a and k in b
+    dev = a["xyz"].device
+    clouds = []
+    for s in (a, b):
+        q = {k: s[k] for k in ("xyz", "normal", "color") if k in s and (k == "xyz" or both(k))}
+        q["xyz"] = _check_cloud(q["xyz"], "xyz", "compare_meshes", dev)
+        if downsample is not None:
+            names = [k for k in ("normal", "color") if k in q]
+            pts, att, _ = voxel_downsample(q["xyz"], downsample, torch.cat([q[k] for k in names], 1) if names else None)
+            q = dict(xyz=pts, **{k: att[:, 3 * j:3 * j + 3].contiguous() for j, k in enumerate(names)})
+        clouds.append(q)
+    qa, qb = clouds
+
+    def towards(query, cloud, mesh):
+        """the distances of ``query`` to the target (its mesh where it has faces, else its cloud) -> (dist, index, the target's normal and
+        colour at the nearest point or None, the grid)"""
+        if mesh.get("faces") is None:
+            dist, index = PointGrid(cloud["xyz"], max_dist, cell).query(query["xyz"])
+            at = lambda k: cloud[k][index.clamp(min=0)] if k in cloud else None
+            return dist, index, at("normal"), at("color"), None
+        grid = TriangleGrid(mesh, max_dist, cell)
+        dist, face, bary = grid.query(query["xyz"], bary=True)
+        f = face.clamp(min=0).long()
+        normal = ops.mesh_face_area(grid.xyz, grid.faces)[1][f] if "normal" in query else None      # sample_mesh(normals="face")'s normal
+        color = None
+        if "color" in query:
+            c = mesh.get("color") if mesh.get("color") is not None else mesh.get("rgb")
+            c = fusion3d._on_device(c, dev)[grid.faces[f].clamp(0, max(grid.xyz.shape[0] - 1, 0)).long()]      # [M,3,3]: the three vertices' colours
+            color = c[:, 0] + bary[:, :1] * (c[:, 1] - c[:, 0]) + bary[:, 1:] * (c[:, 2] - c[:, 0])
+        return dist, face, normal, color, grid
+    d_pg, i_pg, n_pg, c_pg, grid_gt = towards(qa, b, gt)
+    d_gp, i_gp, n_gp, c_gp, grid_pred = towards(qb, a, pred)
+    thr32 = float(np.float32(threshold))
+    sa, sc = _side(d_pg, i_pg, max_dist, thr32), _side(d_gp, i_gp, max_dist, thr32)
+    P, R = sa["share"], sc["share"]
+    out = dict(accuracy=sa["mean"], completeness=sc["mean"], chamfer=0.5 * (sa["mean"] + sc["mean"]), precision=P, recall=R,
+               fscore=2.0 * P * R / (P + R) if P + R > 0 else 0.0, accuracy_median=sa["median"], completeness_median=sc["median"],
+               n_pred=int(qa["xyz"].shape[0]), n_gt=int(qb["xyz"].shape[0]), clamped_pred=sa["clamped"], clamped_gt=sc["clamped"])
+
+    def pairs(src, dst, keep, fn):
+        return float(fn(src[keep].double(), dst[keep].double()).mean().item()) if bool(keep.any()) else None
+    if both("normal"):
+        dot = lambda x, y: (x * y).sum(1).abs()
+        v = [x for x in (pairs(qa["normal"], n_pg, i_pg >= 0, dot), pairs(qb["normal"], n_gp, i_gp >= 0, dot)) if x is not None]
+        out["normal_consistency"] = sum(v) / len(v) if v else 0.0
+    if both("color"):
+        l1 = lambda x, y: (x - y).abs().mean(1)
+        v = [x for x in (pairs(qa["color"], c_pg, (i_pg >= 0) & (d_pg < thr32), l1), pairs(qb["color"], c_gp, (i_gp >= 0) & (d_gp < thr32), l1)) if x is not None]
+        out["color_l1"] = sum(v) / len(v) if v else 0.0
+    out["exact"] = dict(faces_pred=None if grid_pred is None else grid_pred.faces_valid, faces_gt=None if grid_gt is None else grid_gt.faces_valid,
+                        invalid_pred=0 if grid_pred is None else grid_pred.invalid, invalid_gt=0 if grid_gt is None else grid_gt.invalid)
+    return out
+
+
+def compare_meshes(pred, gt, density, threshold=0.05, max_dist=None, downsample=None, seed=0, cell=None, visible=None, exact=False):
     """The 3D scores of the SURFACE ``pred`` against the surface ``gt``: both triangle meshes (dicts with ``xyz`` and ``faces``: what
     ``extract_mesh``, ``filter_mesh`` or ``read_ply(faces=True)`` return) are sampled by area at ``density`` points per square metre
     (``fusion3d.sample_mesh``, face normals), and the two clouds go to ``compare_clouds`` unchanged -> its dict plus ``sampled`` =
     dict(density, n_pred, n_gt, area_pred, area_gt, invalid_pred, invalid_gt).  A side without ``faces`` is a plain cloud (``xyz``,
     optionally ``normal`` / ``color``) and is used as it is: its area is None.  A decimated mesh -- a wall as two triangles -- then counts
-    by its area, not by its vertices, and the distance to it is the distance to its surface, not to its nearest corner.
+    by its area, not by its vertices.  By default every distance is the distance to the nearest SAMPLE of the other surface, not to the
+    surface: for a point on it about ``1 / (2 sqrt(density))`` instead of 0, a floor that moves with ``density``.
+    ``exact=True`` scores against the surfaces themselves (``TriangleGrid``; csrc/mesh/mesh_distance.hip): accuracy and precision from the
+    distances of the predicted samples to the ground-truth MESH, completeness and recall from the ground-truth samples' distances to the
+    predicted MESH; a side without ``faces`` keeps the nearest-sample search for the direction that targets it; ``downsample`` applies
+    to the query clouds; ``visible`` restricts the ground-truth samples as below while accuracy still looks at the whole ground-truth
+    mesh; normal_consistency takes the face normal of the nearest face (``sample_mesh(normals="face")``'s), color_l1 the vertex colours
+    interpolated at the nearest point; the result gains ``exact`` = dict(faces_pred, faces_gt: the valid faces searched, None for a
+    side without faces; invalid_pred, invalid_gt: the faces ignored).  With the default False nothing of this runs.
     ``visible=dict(cam_poses [T,4,4], cam_intr, image_hw, min_views=1, tol=None, depth_max=None)`` scores only the ground truth the
     cameras saw: the ground-truth mesh is rendered in every view (csrc/mesh/mesh_raster.hip) and its samples seen by fewer than
     ``min_views`` views are dropped before the comparison (``tol`` defaults to ``threshold``); ``sampled`` gains n_gt_visible and
@@ -294,9 +483,12 @@ def compare_meshes(pred, gt, density, threshold=0.05, max_dist=None, downsample=
     if visible is not None:
         b, n_gt, _ = restrict_to_visible(gt, b, visible, threshold, "compare_meshes")
     both = lambda k: k in a and k in b
-    out = compare_clouds(a["xyz"], b["xyz"], threshold=threshold, max_dist=max_dist, downsample=downsample,
-                         pred_normal=a["normal"] if both("normal") else None, gt_normal=b["normal"] if both("normal") else None,
-                         pred_color=a["color"] if both("color") else None, gt_color=b["color"] if both("color") else None, cell=cell)
+    if exact:
+        out = _exact_scores(a, b, pred, gt, dev, threshold, max_dist, downsample, cell)
+    else:
+        out = compare_clouds(a["xyz"], b["xyz"], threshold=threshold, max_dist=max_dist, downsample=downsample,
+                             pred_normal=a["normal"] if both("normal") else None, gt_normal=b["normal"] if both("normal") else None,
+                             pred_color=a["color"] if both("color") else None, gt_color=b["color"] if both("color") else None, cell=cell)
     out["sampled"] = dict(density=float(density), n_pred=int(a["xyz"].shape[0]), n_gt=n_gt, area_pred=area_a, area_gt=area_b,
                           invalid_pred=bad_a, invalid_gt=bad_b)
     if visible is not None:

@@ -917,6 +917,86 @@ std::tuple<Tensor, Tensor, Tensor> cloud_nearest(const Tensor& query, const Tens
     return {dist, index, st};
 }
 
+// ------------------------------------------------------------------------------------------------ point-to-mesh distance (csrc/mesh/mesh_distance.hip)
+// the grid of the three operators: the rules of check_cloud_grid, at most ESTD_CLOUD_MAX_CELLS cells, big_cells not negative
+static int64_t check_tri_grid(const Tensor& lo, double cell, at::IntArrayRef dims, int64_t big_cells, const char* op)
+{
+    check_cloud_grid(lo, cell, dims, op, ESTD_CLOUD_MAX_DIM);
+    const int64_t cells = dims[0] * dims[1] * dims[2];
+    TORCH_CHECK(cells <= ESTD_CLOUD_MAX_CELLS, op, ": ", cells, " cells, at most ", ESTD_CLOUD_MAX_CELLS);
+    check_count(big_cells, 0, 0x7fffffffLL, op, "big_cells");
+    return cells;
+}
+
+// -> (count [F] int32, flag [F] int32, invalid [1] int64 on the device)
+std::tuple<Tensor, Tensor, Tensor> mesh_tri_bins(const Tensor& xyz, const Tensor& faces, const Tensor& lo, double cell, at::IntArrayRef dims,
+                                                 int64_t big_cells)
+{
+    const char* op = "mesh_tri_bins";
+    const OpScope scope(faces);
+    const MeshArg m = check_mesh(xyz, faces, op);
+    check_tri_grid(lo, cell, dims, big_cells, op);
+    Tensor count = at::empty({m.F}, faces.options()), flag = at::empty({m.F}, faces.options());
+    Tensor invalid = at::empty({1}, faces.options().dtype(at::kLong));
+    const int d3[3] = {(int)dims[0], (int)dims[1], (int)dims[2]};
+    check_status(estd_mesh_tri_bins(m.V ? m.xyz : nullptr, (long long)m.V, m.F ? m.faces : nullptr, (long long)m.F, lo.data_ptr<float>(), (float)cell,
+                                    d3, (int)big_cells, m.F ? count.data_ptr<int32_t>() : nullptr, m.F ? flag.data_ptr<int32_t>() : nullptr,
+                                    reinterpret_cast<long long*>(invalid.data_ptr<int64_t>()), cur_stream()), "estd_mesh_tri_bins");
+    return {count, flag, invalid};
+}
+
+// offset int64 [F] (the exclusive prefix sum of count) -> (keys int64 [n_pairs], pair_face int32 [n_pairs])
+std::tuple<Tensor, Tensor> mesh_tri_fill(const Tensor& xyz, const Tensor& faces, const Tensor& lo, double cell, at::IntArrayRef dims,
+                                         int64_t big_cells, const Tensor& offset, int64_t n_pairs)
+{
+    const char* op = "mesh_tri_fill";
+    const OpScope scope(faces);
+    const MeshArg m = check_mesh(xyz, faces, op);
+    check_tri_grid(lo, cell, dims, big_cells, op);
+    const auto* off = reinterpret_cast<const long long*>(lptr(offset, op, "offset", faces, m.F));
+    check_count(n_pairs, 0, ESTD_MESH_DISTANCE_MAX_PAIRS, op, "n_pairs");
+    Tensor keys = at::empty({n_pairs}, faces.options().dtype(at::kLong)), pair_face = at::empty({n_pairs}, faces.options());
+    const int d3[3] = {(int)dims[0], (int)dims[1], (int)dims[2]};
+    if (n_pairs && m.F)
+        check_status(estd_mesh_tri_fill(m.xyz, (long long)m.V, m.faces, (long long)m.F, lo.data_ptr<float>(), (float)cell, d3, (int)big_cells, off,
+                                        (long long)n_pairs, reinterpret_cast<long long*>(keys.data_ptr<int64_t>()), pair_face.data_ptr<int32_t>(),
+                                        cur_stream()), "estd_mesh_tri_fill");
+    return {keys, pair_face};
+}
+
+// query [M,3], order int64 [M], big_records [B,12], records [P,12], cell_start int32 [cells + 1] -> (dist [M], face int32 [M],
+// bary [M,2] and closest [M,3] when asked for, else [0,2] and [0,3])
+std::tuple<Tensor, Tensor, Tensor, Tensor> mesh_nearest(const Tensor& query, const Tensor& order, const Tensor& big_records, const Tensor& records,
+                                                        const Tensor& cell_start, const Tensor& lo, double cell, at::IntArrayRef dims,
+                                                        double max_dist, bool bary, bool closest)
+{
+    const char* op = "mesh_nearest";
+    const OpScope scope(query);
+    estd_mesh_nearest_desc d{};
+    d.query = check_cloud(query, op, "query", 3);
+    d.big_records = check_cloud(big_records, op, "big_records", 12);
+    d.records = check_cloud(records, op, "records", 12);
+    const int64_t M = query.size(0), B = big_records.size(0), P = records.size(0);
+    TORCH_CHECK(big_records.device() == query.device() && records.device() == query.device(), op, ": the records are not on the query's device");
+    check_count(B, 0, ESTD_MESH_DISTANCE_MAX_PAIRS, op, "big records");
+    check_count(P, 0, ESTD_MESH_DISTANCE_MAX_PAIRS, op, "records");
+    d.order = reinterpret_cast<const long long*>(lptr(order, op, "order", query, M));
+    d.max_dist = positive_square_f32(max_dist, op, "max_dist");
+    const int64_t cells = check_tri_grid(lo, cell, dims, 0, op);
+    d.cell_start = lptr<int32_t>(cell_start, op, "cell_start (cells + 1)", query, cells + 1);
+    Tensor dist = new_f32({M}, query), face = at::empty({M}, query.options().dtype(at::kInt));
+    Tensor bar = new_f32({bary ? M : 0, 2}, query), clo = new_f32({closest ? M : 0, 3}, query);
+    if (M) {
+        d.M = (long long)M; d.B = (long long)B; d.P = (long long)P;
+        d.dist = dist.data_ptr<float>(); d.face = face.data_ptr<int32_t>();
+        d.bary = bary ? bar.data_ptr<float>() : nullptr; d.closest = closest ? clo.data_ptr<float>() : nullptr;
+        d.cell = (float)cell;
+        for (int j = 0; j < 3; ++j) { d.lo[j] = lo.data_ptr<float>()[j]; d.dims[j] = (int)dims[j]; }
+        check_status(estd_mesh_nearest(&d, cur_stream()), "estd_mesh_nearest");
+    }
+    return {dist, face, bar, clo};
+}
+
 // points [n,3], attrs [n,C] (C = 0: none), order int64 [n], segments int64 [K + 1] -> (points [K,3], attrs [K,C])
 std::tuple<Tensor, Tensor> cloud_cell_centroids(const Tensor& points, const Tensor& attrs, const Tensor& order, const Tensor& segments)
 {
@@ -1425,6 +1505,11 @@ TORCH_LIBRARY(estdepth_hip, m)
     m.def("cloud_nearest(Tensor query, Tensor order, Tensor records, Tensor cell_start, Tensor lo, float cell, int[] dims, float max_dist, "
           "bool stats) -> (Tensor, Tensor, Tensor)");
     m.def("cloud_cell_centroids(Tensor points, Tensor attrs, Tensor order, Tensor segments) -> (Tensor, Tensor)");
+    m.def("mesh_tri_bins(Tensor xyz, Tensor faces, Tensor lo, float cell, int[] dims, int big_cells) -> (Tensor, Tensor, Tensor)");
+    m.def("mesh_tri_fill(Tensor xyz, Tensor faces, Tensor lo, float cell, int[] dims, int big_cells, Tensor offset, int n_pairs) -> "
+          "(Tensor, Tensor)");
+    m.def("mesh_nearest(Tensor query, Tensor order, Tensor big_records, Tensor records, Tensor cell_start, Tensor lo, float cell, int[] dims, "
+          "float max_dist, bool bary, bool closest) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("frame_align(Tensor depth, Tensor? conf, Tensor m_depth, Tensor m_normal, Tensor mats, float dist_max, float z_near, float conf_min) -> "
           "(Tensor, Tensor, Tensor)");
     m.def("profile_mark(int id) -> ()");
@@ -1487,6 +1572,9 @@ TORCH_LIBRARY_IMPL(estdepth_hip, CUDA, m)
     m.impl("cloud_cell_keys", cloud_cell_keys);
     m.impl("cloud_nearest", cloud_nearest);
     m.impl("cloud_cell_centroids", cloud_cell_centroids);
+    m.impl("mesh_tri_bins", mesh_tri_bins);
+    m.impl("mesh_tri_fill", mesh_tri_fill);
+    m.impl("mesh_nearest", mesh_nearest);
     m.impl("frame_align", frame_align);
 }
 

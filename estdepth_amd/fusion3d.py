@@ -345,7 +345,7 @@ class TSDFVolume:
         write_ply(path, rec.numpy(), rgb, faces=faces)
         return rec.shape[0], faces.shape[0]
 
-    def compare(self, other, threshold=0.05, w_min=1.0, max_dist=None, downsample=None, cell=None, sample=None, seed=0, visible=None):
+    def compare(self, other, threshold=0.05, w_min=1.0, max_dist=None, downsample=None, cell=None, sample=None, seed=0, visible=None, exact=False):
         """The 3D scores (``cloud_metrics.compare_clouds``: accuracy, completeness, chamfer, precision / recall / F-score at ``threshold``
         metres, ...) of this volume's surface as the prediction against ``other`` as the ground truth: another ``TSDFVolume`` -- both sides
         go through ``extract_points(w_min)`` -- or a dict with ``xyz`` [N,3] and optionally ``normal`` / ``color`` (device tensors or numpy
@@ -354,10 +354,18 @@ class TSDFVolume:
         ``extract_mesh(w_min)`` and ``sample_mesh(density=sample, seed=seed)``, a dict side with ``faces`` through ``sample_mesh``, a
         dict without faces stays the cloud it is; with the default None nothing of this runs.
         ``visible=dict(cam_poses, cam_intr, image_hw, min_views=1, tol=None, depth_max=None)`` (needs ``sample``) drops the ground-truth
-        samples the cameras did not see, as ``cloud_metrics.compare_meshes`` documents it; the result gains ``n_gt`` / ``n_gt_visible``."""
+        samples the cameras did not see, as ``cloud_metrics.compare_meshes`` documents it; the result gains ``n_gt`` / ``n_gt_visible``.
+        ``exact=True`` (needs ``sample``) hands both sides as meshes to ``cloud_metrics.compare_meshes(exact=True)``: distances to the
+        surfaces themselves (csrc/mesh/mesh_distance.hip), and its result (with ``sampled`` and ``exact``) comes back as it is."""
         from . import cloud_metrics
         if visible is not None and sample is None:
             raise RuntimeError("compare: visible= needs sample=density (the ground-truth surface is sampled, then restricted)")
+        if exact:                                                  # the surfaces themselves: cloud_metrics.compare_meshes owns that path
+            if sample is None:
+                raise RuntimeError("compare: exact=True needs sample=density (the query points are samples of the two surfaces)")
+            mesh = lambda x: x.extract_mesh(w_min=w_min) if isinstance(x, TSDFVolume) else x
+            return cloud_metrics.compare_meshes(mesh(self), mesh(other), sample, threshold=threshold, max_dist=max_dist, downsample=downsample,
+                                                seed=seed, cell=cell, visible=visible, exact=True)
 
         def side(x):
             if sample is not None:

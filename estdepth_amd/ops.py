@@ -1625,6 +1625,101 @@ def cloud_cell_centroids(points, attrs, order, segments):
     return out, out_attrs
 
 
+# ---------------------------------------------------------------------------------- point-to-mesh distance (csrc/mesh/mesh_distance.hip)
+MESH_DISTANCE_MAX_PAIRS = 1 << 23      # ESTD_MESH_DISTANCE_MAX_PAIRS (include/estd_hip.h)
+MESH_DISTANCE_BIG_CELLS = 64           # ESTD_MESH_DISTANCE_BIG_CELLS
+
+
+def _tri_grid(lo, cell, dims, big_cells, op):
+    """the grid of the three operators: the rules of _cloud_grid, at most CLOUD_MAX_CELLS cells, big_cells not negative -> (lo3, dims, cells)"""
+    lo3, dims = _cloud_grid(lo, cell, dims, op, CLOUD_MAX_DIM)
+    cells = dims[0] * dims[1] * dims[2]
+    _need(cells <= CLOUD_MAX_CELLS, "%s: %d cells, at most %d" % (op, cells, CLOUD_MAX_CELLS))
+    _count(big_cells, 0, 0x7fffffff, op, "big_cells")
+    return lo3, dims, cells
+
+
+def mesh_tri_bins(xyz, faces, lo, cell, dims, big_cells=MESH_DISTANCE_BIG_CELLS):
+    """Per triangle of the mesh ``xyz`` [V,3] float32 / ``faces`` [F,3] int32 the cells of the grid (``lo`` CPU float32 [3], ``cell``,
+    ``dims``) its bounding box covers -> (count [F] int32: the (cell, face) pairs it owns, flag [F] int32: 0 invalid, 1 grid, 2 big list
+    (more than ``big_cells`` cells), invalid [1] int64 on the device).  include/estd_hip.h, estd_mesh_tri_bins."""
+    cell, dims, big_cells = float(cell), [int(v) for v in dims], int(big_cells)
+    if _use_torch():
+        return tuple(T().mesh_tri_bins(xyz, faces, lo, cell, dims, big_cells))
+    op = "mesh_tri_bins"
+    n_vertices, n_faces = _mesh(xyz, faces, op)
+    lo3, dims, _ = _tri_grid(lo, cell, dims, big_cells, op)
+    dev = faces.device
+    with torch.cuda.device(dev):
+        count, flag = torch.empty(n_faces, device=dev, dtype=torch.int32), torch.empty(n_faces, device=dev, dtype=torch.int32)
+        invalid = torch.empty(1, device=dev, dtype=torch.int64)
+        pp = (lambda t: _p(t)) if n_faces else (lambda t: None)
+        N.check(N.lib().estd_mesh_tri_bins(_p(xyz) if n_vertices else None, n_vertices, pp(faces), n_faces, (ctypes.c_float * 3)(*lo3), cell,
+                                           (ctypes.c_int * 3)(*dims), big_cells, pp(count), pp(flag), _p(invalid), _stream()),
+                "estd_mesh_tri_bins")
+    return count, flag, invalid
+
+
+def mesh_tri_fill(xyz, faces, lo, cell, dims, big_cells, offset, n_pairs):
+    """The (cell key, face) pairs of the grid triangles, each triangle's at ``offset`` [F] int64 (the exclusive prefix sum of
+    mesh_tri_bins' count) -> (keys [n_pairs] int64, pair_face [n_pairs] int32).  include/estd_hip.h, estd_mesh_tri_fill."""
+    cell, dims, big_cells, n_pairs = float(cell), [int(v) for v in dims], int(big_cells), int(n_pairs)
+    if _use_torch():
+        return tuple(T().mesh_tri_fill(xyz, faces, lo, cell, dims, big_cells, offset, n_pairs))
+    op = "mesh_tri_fill"
+    n_vertices, n_faces = _mesh(xyz, faces, op)
+    lo3, dims, _ = _tri_grid(lo, cell, dims, big_cells, op)
+    dev = faces.device
+    _ivec(offset, op, "offset", dev, n_faces)
+    _count(n_pairs, 0, MESH_DISTANCE_MAX_PAIRS, op, "n_pairs")
+    with torch.cuda.device(dev):
+        keys, pair_face = torch.empty(n_pairs, device=dev, dtype=torch.int64), torch.empty(n_pairs, device=dev, dtype=torch.int32)
+        if n_pairs and n_faces:
+            N.check(N.lib().estd_mesh_tri_fill(_p(xyz), n_vertices, _p(faces), n_faces, (ctypes.c_float * 3)(*lo3), cell, (ctypes.c_int * 3)(*dims),
+                                               big_cells, _p(offset), n_pairs, _p(keys), _p(pair_face), _stream()), "estd_mesh_tri_fill")
+    return keys, pair_face
+
+
+def mesh_nearest(query, order, big_records, records, cell_start, lo, cell, dims, max_dist, bary=False, closest=False):
+    """The nearest triangle of every row of ``query`` [M,3] -> (dist [M] float32, face [M] int32, bary [M,2] or None, closest [M,3] or
+    None) on the query's device.  ``big_records`` [B,12] / ``records`` [P,12] with ``cell_start`` int32 [cells + 1]: the 48-byte records
+    of the big list and of the (cell, face) pairs in cell order (cloud_metrics.TriangleGrid builds them), ``order`` int64 [M]: the order the
+    queries are taken in.  Not found within ``max_dist``: dist = max_dist, face = -1, zeros.  The contract is spelled out in
+    include/estd_hip.h (estd_mesh_nearest)."""
+    cell, max_dist, dims = float(cell), float(max_dist), [int(v) for v in dims]
+    if _use_torch():
+        dist, face, b, c = T().mesh_nearest(query, order, big_records, records, cell_start, lo, cell, dims, max_dist, bool(bary), bool(closest))
+        return dist, face, (b if bary else None), (c if closest else None)
+    op = "mesh_nearest"
+    _cloud(query, op, "query")
+    _cloud(big_records, op, "big_records", cols=12)
+    _cloud(records, op, "records", cols=12)
+    M, B, P, dev = query.shape[0], big_records.shape[0], records.shape[0], query.device
+    _need(big_records.device == dev and records.device == dev, "%s: the records are not on the query's device" % op)
+    _count(B, 0, MESH_DISTANCE_MAX_PAIRS, op, "big records")
+    _count(P, 0, MESH_DISTANCE_MAX_PAIRS, op, "records")
+    _ivec(order, op, "order", dev, M)
+    _positive_square(max_dist, op, "max_dist")
+    lo3, dims, cells = _tri_grid(lo, cell, dims, 0, op)
+    _ivec(cell_start, op, "cell_start (cells + 1)", dev, cells + 1, torch.int32)
+    with torch.cuda.device(dev):
+        dist, face = torch.empty(M, device=dev), torch.empty(M, device=dev, dtype=torch.int32)
+        b = torch.empty((M, 2), device=dev) if bary else None
+        c = torch.empty((M, 3), device=dev) if closest else None
+        if M:
+            d = N.MeshNearestDesc()
+            d.M, d.B, d.P = M, B, P
+            d.query, d.order, d.cell_start = query.data_ptr(), order.data_ptr(), cell_start.data_ptr()
+            d.big_records = big_records.data_ptr() if B else None
+            d.records = records.data_ptr() if P else None
+            d.dist, d.face = dist.data_ptr(), face.data_ptr()
+            d.bary, d.closest = (b.data_ptr() if bary else None), (c.data_ptr() if closest else None)
+            d.cell, d.max_dist = cell, max_dist
+            d.lo[:], d.dims[:] = lo3, dims
+            N.check(N.lib().estd_mesh_nearest(ctypes.byref(d), _stream()), "estd_mesh_nearest")
+    return dist, face, b, c
+
+
 # ---------------------------------------------------------------------------------- frame-to-model alignment (csrc/track/frame_align.hip)
 FRAME_ALIGN_SUMS = 29           # ESTD_FRAME_ALIGN_SUMS (include/estd_hip.h)
 

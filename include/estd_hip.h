@@ -887,6 +887,99 @@ int estd_mesh_raster(const float* xyz, long long n_vertices, const int* faces, l
 int estd_mesh_raster_resolve(const float* xyz, long long n_vertices, const int* faces, long long n_faces, const double* mat, int H, int W,
                              const unsigned long long* keys, float* depth, int* face, float* bary, int* facing, estd_stream_t stream);
 
+/* The distance from a point to a triangle mesh (csrc/mesh/mesh_distance.hip; numpy form: tests/mesh_distance_ref.py): per query the
+ * nearest point of the nearest triangle.  What compare_meshes(exact=True) of estdepth_amd/cloud_metrics.py scores with: the distance
+ * to a surface, not to its nearest sample.
+ *
+ * Inputs.  q [M][3] float32, every coordinate finite (the host layers refuse others); the mesh xyz [V][3] float32, faces [F][3] int32,
+ *   contiguous; max_dist, positive and finite with r2 = max_dist * max_dist (one fp32 product, formed once by the entry point) finite.
+ *
+ * Invalid faces.  Face f = (i0, i1, i2) with a = xyz[i0], b = xyz[i1], c = xyz[i2] is INVALID when an index is outside [0, V), when one
+ *   of the nine coordinates is not finite, or when the fp32 normal is zero: with ab = b - a, ac = c - a (componentwise),
+ *     nx = ab.y * ac.z - ab.z * ac.y;  ny = ab.z * ac.x - ab.x * ac.z;  nz = ab.x * ac.y - ab.y * ac.x;
+ *     degenerate iff fmaf(nx, nx, fmaf(ny, ny, nz * nz)) == 0
+ *   -- each component two ROUNDED products and their difference, not contracted: a face that names a vertex twice has ab == ac or a
+ *   zero edge and gives exactly 0, which an fma (one product unrounded) would not.
+ *   An invalid face is ignored, counted in `invalid`, and its indices are never used as an address (estd_mesh_components' rule; the
+ *   coordinates are read only after the three indices were found in range).
+ *
+ * The pair.  tri_closest(q, a, b, c), every operation ONE fp32 operation as written, nothing contracted, dot(x, y) =
+ *   fmaf(x0, y0, fmaf(x1, y1, x2 * y2)); the region tests of Ericson, Real-Time Collision Detection, 5.1.5, taken in this order:
+ *     ab = b - a;  ac = c - a;  ap = q - a;  bp = q - b;  cp = q - c;
+ *     d1 = dot(ab, ap);  d2 = dot(ac, ap);  d3 = dot(ab, bp);  d4 = dot(ac, bp);  d5 = dot(ab, cp);  d6 = dot(ac, cp);
+ *     vc = fmaf(d1, d4, -(d3 * d2));  vb = fmaf(d5, d2, -(d1 * d6));  va = fmaf(d3, d6, -(d5 * d4));  e43 = d4 - d3;  e56 = d5 - d6;
+ *     vertex A    if d1 <= 0 and d2 <= 0:                     v = 0, w = 0
+ *     vertex B    else if d3 >= 0 and d4 <= d3:               v = 1, w = 0
+ *     edge AB     else if vc <= 0 and d1 >= 0 and d3 <= 0:    v = d1 / (d1 - d3), w = 0
+ *     vertex C    else if d6 >= 0 and d5 <= d6:               v = 0, w = 1
+ *     edge AC     else if vb <= 0 and d2 >= 0 and d6 <= 0:    v = 0, w = d2 / (d2 - d6)
+ *     edge BC     else if va <= 0 and e43 >= 0 and e56 >= 0:  w = e43 / (e43 + e56), v = 1 - w
+ *     interior    else:                                       denom = 1 / ((va + vb) + vc);  v = vb * denom;  w = vc * denom
+ *     p = fmaf(w, ac, fmaf(v, ab, a)) per component;   d = q - p;   d2(q, f) = fmaf(d.x, d.x, fmaf(d.y, d.y, d.z * d.z)).
+ *   Divisions are IEEE correctly rounded.  A comparison with a NaN is false: a pair whose d2 is a NaN (coordinates whose products
+ *   leave fp32) never wins.
+ *
+ * The result of a query, defined to the bit and independent of the grid, the cell edge, the launch shape and the binding:
+ *     d2min = the smallest d2(q, f) over ALL valid faces f;   face = the SMALLEST f attaining it;   found iff d2min <= r2;
+ *     dist[q] = the IEEE correctly rounded square root of d2min, or max_dist when not found;   face[q] = face, or -1;
+ *     bary[q] = (v, w) and closest[q] = p of tri_closest(q, face) (optional outputs), zeros when not found.
+ *   Every element of every output is written by every call with plain vector stores: two calls give the same bits.
+ *
+ * The structure (tuning only).  A grid as estd_cloud_cell_keys defines it (lo3, cell, dims3: host pointers / values, dims_j <=
+ *   ESTD_CLOUD_MAX_DIM, at most ESTD_CLOUD_MAX_CELLS cells).  A valid face covers the cells c0_j .. c1_j per axis, c0 / c1 the cell
+ *   coordinates of the componentwise minimum / maximum of its three vertices, n = the product of (c1_j - c0_j + 1) cells.  With
+ *   n <= big_cells it is a GRID face and owns n (key, face) pairs, key = (z dims[1] + y) dims[0] + x, in ascending z, then y, then x;
+ *   with n > big_cells it is a BIG face and owns none: every query tests it.  big_cells = 0 puts every valid face on the big list,
+ *   big_cells >= the number of cells none.
+ * estd_mesh_tri_bins (mesh_tri_bins_kernel, one lane per face): count [F] int32 = the pairs face f owns (0 for invalid and big
+ *   faces), flag [F] int32 = 0 invalid, 1 grid, 2 big; invalid [1] int64 = the number of invalid faces, zeroed by the call (a memset
+ *   on `stream`) and raised with ONE integer atomic add per wave.  F == 0: the memset alone.
+ * estd_mesh_tri_fill (mesh_tri_fill_kernel, one lane per face): offset [F] int64 is the exclusive prefix sum of count (the host
+ *   forms it); grid face f writes its pairs to keys [n_pairs] int64 / pair_face [n_pairs] int32 at offset[f] .. offset[f] + n - 1
+ *   with plain stores, no atomics: the same bits for every launch.  A position outside [0, n_pairs) is dropped, never written.
+ *   n_pairs == 0 or F == 0 launches nothing.
+ * The host sorts the pairs by key (stable), forms cell_start [cells + 1] int32 (cell_start[k] = the pairs with a key < k) and
+ *   gathers one 48-byte RECORD per pair in that order: twelve 32-bit words a.x a.y a.z b.x b.y b.z c.x c.y c.z, the bits of f, 0, 0;
+ *   the big faces give records of the same form, in any order.  Both arrays are 16-byte aligned.
+ * estd_mesh_nearest (mesh_nearest_kernel, one lane per query): tests every one of the B big records (the record's address is the
+ *   same in every lane: scalar loads), then walks the cell table in rings around the query's (clamped) cell as estd_cloud_nearest
+ *   does and stops in front of ring r >= 2 once (1 - 2^-5) ((r - 1) cell)^2 exceeds the smallest d2 so far (at most r2).  Every point
+ *   of a triangle lies in the box of its vertices, hence in a cell the triangle is registered in, and cell coordinates are off by less
+ *   than 2^-12 cells, so a triangle not met in rings 0 .. r - 1 is further than that bound: no face that could win or tie is skipped
+ *   PROVIDED the vertices of all grid faces lie inside the grid's box [lo, lo + dims * cell) -- the caller's duty; the host layers
+ *   take the box from the valid faces.  A face met in several cells is tested again; the minimum does not notice.  `order` as in
+ *   estd_cloud_nearest.  Records are only read as coordinates and as the face index to report: nothing in them becomes an address.
+ *   M == 0 launches nothing.  B == 0 and P == 0: nothing is found.
+ * ESTD_ERR_ARG (before any launch, no device needed): a negative size or big_cells, a null `invalid`, a null pointer that the sizes
+ *   make necessary (xyz with V > 0; faces, count, flag with F > 0; everything of estd_mesh_tri_fill with n_pairs > 0 and F > 0; query,
+ *   dist, face with M > 0; big_records with B > 0; records and cell_start with P > 0), a misaligned record array, a grid
+ *   estd_cloud_nearest would refuse (estd_mesh_nearest: only with P > 0), max_dist not finite or <= 0 or with a square that leaves
+ *   fp32.  ESTD_ERR_UNSUPPORTED: V, 3 F or M beyond 2^31 - 1, n_pairs, B or P beyond ESTD_MESH_DISTANCE_MAX_PAIRS. */
+#define ESTD_MESH_DISTANCE_MAX_PAIRS (1 << 23)
+#define ESTD_MESH_DISTANCE_BIG_CELLS 64       /* the host layers' default for big_cells */
+int estd_mesh_tri_bins(const float* xyz, long long n_vertices, const int* faces, long long n_faces, const float* lo3, float cell,
+                       const int* dims3, int big_cells, int* count, int* flag, long long* invalid, estd_stream_t stream);
+int estd_mesh_tri_fill(const float* xyz, long long n_vertices, const int* faces, long long n_faces, const float* lo3, float cell,
+                       const int* dims3, int big_cells, const long long* offset, long long n_pairs, long long* keys, int* pair_face,
+                       estd_stream_t stream);
+typedef struct estd_mesh_nearest_desc {
+    long long M, B, P;                            /* queries, big records, grid records */
+    const float* query;                           /* [M][3] */
+    const long long* order;                       /* [M] or NULL */
+    const float* big_records;                     /* [B][12] */
+    const float* records;                         /* [P][12], in cell order */
+    const int* cell_start;                        /* [dims[0] dims[1] dims[2] + 1] */
+    float* dist;                                  /* [M] */
+    int* face;                                    /* [M] */
+    float* bary;                                  /* NULL, or [M][2] */
+    float* closest;                               /* NULL, or [M][3] */
+    float lo[3];                                  /* host values, copied into the launch arguments */
+    float cell;
+    float max_dist;
+    int dims[3];
+} estd_mesh_nearest_desc;
+int estd_mesh_nearest(const estd_mesh_nearest_desc* desc, estd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -161,6 +161,9 @@ def parse(argv=None):
                     "--score-sample: render the ground-truth mesh at every fused target's pose, intrinsics and size and drop its samples that "
                     "fewer than MIN_VIEWS (default 1) targets saw within --depth_max (mesh_render.visible_mask); recon_3d.sampled gains "
                     "n_gt_visible and visible_share")
+    ap.add_argument("--score-exact", action="store_true", help="with --score-3d GT.ply (a mesh) and --score-sample: every distance is the distance "
+                    "to the other SURFACE (cloud_metrics.compare_meshes(exact=True) on csrc/mesh/mesh_distance.hip), not to its nearest sample; "
+                    "recon_3d gains an exact block: faces_pred, faces_gt, invalid_pred, invalid_gt")
     ap.add_argument("--render-gt-mesh", action="store_true", help="with --score-3d GT.ply (a mesh): write its depth at every fused target's pose "
                     "to <out>/gt_mesh_depth and score the predictions against it: errors_vs_gt_mesh, gt_mesh_coverage, errors_on_gt_mesh_covered")
     ap.add_argument("--score-downsample", type=float, default=None, help="with --score-3d: voxel-grid down-sampling of both clouds first (metres)")
@@ -196,6 +199,11 @@ def parse(argv=None):
             ap.error("%s needs --score-3d GT.ply (a triangle mesh to render)" % flag)
         if on and os.path.exists(args.score_3d) and ply_face_count(args.score_3d) == 0:
             ap.error("%s needs a GT.ply with faces: %s has none, and a point cloud cannot be rendered" % (flag, args.score_3d))
+    if args.score_exact:
+        if not isinstance(args.score_3d, str) or args.score_sample is None:
+            ap.error("--score-exact needs --score-3d GT.ply (a triangle mesh) and --score-sample DENSITY")
+        if os.path.exists(args.score_3d) and ply_face_count(args.score_3d) == 0:
+            ap.error("--score-exact needs a GT.ply with faces: %s has none, and the distance to a point cloud is the sampled one" % args.score_3d)
     if args.score_visible is not None and args.score_sample is None:
         ap.error("--score-visible needs --score-sample DENSITY (the samples of the ground-truth surface are what is restricted)")
     if args.score_visible is not None and args.score_visible < 1:
@@ -423,7 +431,8 @@ def run(args):
                 visible = dict(cam_poses=torch.stack([p for _, p in fused_at]), cam_intr=torch.stack([seen_by[n][0] for n, _ in fused_at]),
                                image_hw=seen_by[fused_at[0][0]][1], min_views=args.score_visible, depth_max=args.depth_max)
             scores = compare_meshes(volume.extract_mesh(min_component=args.mesh_min_component or 0), other, args.score_sample,
-                                    threshold=args.score_threshold, max_dist=max_dist, downsample=args.score_downsample, visible=visible)
+                                    threshold=args.score_threshold, max_dist=max_dist, downsample=args.score_downsample, visible=visible,
+                                    **(dict(exact=True) if args.score_exact else {}))
         torch.cuda.synchronize()
         report["recon_3d"] = dict(scores, threshold=args.score_threshold, max_dist=max_dist, downsample=args.score_downsample, ground_truth=gt_name,
                                   compare_ms=1e3 * (time.time() - t0))

@@ -47,7 +47,14 @@ times the mesh rasteriser (csrc/mesh/mesh_raster.hip) at 640 x 480: the raster k
 the resolve kernel and the whole mesh_render.render_mesh, between device events, behind the cache flush and back to back -- for that
 mesh from the held-out pose of the ray-cast bench, for a 204 800-triangle grid that fills the image, for a two-triangle wall that fills
 it (the large-box regime) and for 4096 coincident small triangles (the contention regime) -- beside TSDFVolume.render of the same volume
-from the same pose."""
+from the same pose.
+
+    python tools/tsdf_bench.py --mesh-distance [--reps 20] [--out profiles/mesh_distance_bench.txt]
+
+times the point-to-mesh distance (csrc/mesh/mesh_distance.hip): the two binning kernels, the whole TriangleGrid build and the search at
+10^5 and 10^6 queries against that mesh and a 204 800-triangle height field, the 170-triangle ground truth of the run-stream tests on the big
+list alone, and cloud_metrics.compare_meshes with and without exact=True -- medians between device events after a warm-up -- beside the
+same minimum formed with torch operators (a chunked brute force over all triangles)."""
 import argparse
 import os
 import sys
@@ -90,6 +97,8 @@ def main():
     ap.add_argument("--mesh-components", action="store_true", help="time the mesh components and filter_mesh beside a host / torch yardstick")
     ap.add_argument("--mesh-sample", action="store_true", help="time the mesh sampling (csrc/mesh/mesh_sample.hip) beside the same sampling with torch operators")
     ap.add_argument("--mesh-raster", action="store_true", help="time the mesh rasteriser (csrc/mesh/mesh_raster.hip) beside TSDFVolume.render")
+    ap.add_argument("--mesh-distance", action="store_true", help="time the point-to-mesh distance (csrc/mesh/mesh_distance.hip) beside a torch "
+                    "brute force; writes profiles/mesh_distance_bench.txt unless --out says otherwise")
     ap.add_argument("--color", action="store_true", help="time the colour fuse, the edge colours and the colour render beside the plain figures")
     args = ap.parse_args()
     if args.raycast:
@@ -102,6 +111,9 @@ def main():
         return sample_main(args)
     if args.mesh_raster:
         return raster_main(args)
+    if args.mesh_distance:
+        args.out = args.out or os.path.join(ROOT, "profiles", "mesh_distance_bench.txt")
+        return distance_main(args)
     if args.color:
         return color_main(args)
     import tsdf_ref as R
@@ -389,6 +401,139 @@ def sample_main(args):
                       "    sample_mesh, whole call (finite check, area kernel, max and total read-backs, cumsum, sample kernel) %8.4f ms cold  %8.4f ms warm"
                       % (t_all, t_allw)]
     lines.append("  no bar is set (the parent has nothing comparable); a search narrowed per wave was not built and is not measured")
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        open(args.out, "w").write(text + "\n")
+
+
+def median_ms(fn, reps, warmup=5):
+    """median ms per call over ``reps`` calls, each between its own pair of device events, after ``warmup`` untimed calls"""
+    for _ in range(warmup):
+        fn()
+    pairs = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        pairs.append((e0, e1))
+    torch.cuda.synchronize()
+    return float(np.median([a.elapsed_time(b) for a, b in pairs]))
+
+
+def distance_main(args):
+    """--mesh-distance: the binning kernels, the build and the search of csrc/mesh/mesh_distance.hip for 10^5 and 10^6 queries against
+    the mesh of the 256^3 bench volume and a 204 800-triangle height field, the 170-triangle ground truth of the run-stream tests on the big
+    list alone, and compare_meshes with and without exact=True; the yardstick is the same minimum by torch operators (chunked brute
+    force over all triangles, the closest point by clamped barycentric projection and the three edges)."""
+    import tempfile
+    import mesh_sample_ref as MS
+    import run_stream_ref as RS
+    import tsdf_ref as R
+    from estdepth_amd import cloud_metrics, ops
+    from estdepth_amd.cloud_metrics import TriangleGrid
+    from estdepth_amd.fusion3d import TSDFVolume, frustum_volume
+    assert torch.cuda.is_available(), "tools/tsdf_bench.py needs a ROCm device"
+    dev = torch.device("cuda:0")
+    H, W, T, vox, dmin, dmax, dims = 480, 640, 3, 0.03, 0.1, 10.0, (256, 256, 256)
+    reps = min(args.reps, 20)
+    K = R.intrinsics(H, W)
+    poses = R.scene_poses(T, seed=1)
+    depths = torch.from_numpy(np.stack([R.raycast_scene(P, K, H, W) for P in poses]).astype(np.float32)).to(dev)
+    origin = frustum_volume(torch.from_numpy(poses[0]), torch.from_numpy(K), (H, W), dmin, dmax, dims, vox)
+    vol = TSDFVolume(dims, vox, origin, device=dev)
+    vol.integrate(depths, torch.from_numpy(poses), torch.from_numpy(K))
+    m = vol.extract_mesh()
+    # 204 800 triangles as a surface: a 320 x 320 grid of quads over a 4 m square, a gentle height field (the grid of
+    # tests/mesh_components_ref.py has that many triangles too, but no geometry: its bench scatters the vertices)
+    u = np.linspace(0.0, 4.0, 321)
+    gx, gy = np.meshgrid(u, u, indexing="xy")
+    grid_xyz = torch.from_numpy(np.stack([gx, gy, 0.2 * np.sin(1.7 * gx) * np.cos(1.3 * gy)], -1).reshape(-1, 3).astype(np.float32)).to(dev)
+    i, j = np.meshgrid(np.arange(320), np.arange(320), indexing="xy")
+    v00 = (j * 321 + i).reshape(-1)
+    grid_np = np.concatenate([np.stack([v00, v00 + 1, v00 + 322], 1), np.stack([v00, v00 + 322, v00 + 321], 1)]).astype(np.int32)
+    with tempfile.TemporaryDirectory() as d:
+        RS.write_scene(d, RS.N_FRAMES, seed=5)
+        rb = RS.read_back(d)
+    tg = RS.targets_of(RS.N_FRAMES)
+    gt_xyz, gt_faces = MS.scene_mesh(rb["depths"][tg], rb["poses"][tg], rb["K"])
+    max_dist = 1.0
+
+    def edge_d2(q, a, b):
+        ab, aq = b - a, q - a
+        t = ((aq * ab).sum(-1) / (ab * ab).sum(-1).clamp_min(1e-30)).clamp(0, 1)
+        return ((aq - t[..., None] * ab) ** 2).sum(-1)
+
+    def yard(q, tri, chunk):
+        """torch operators only: per chunk of queries the distance to every triangle -- the plane distance where the projection falls
+        inside, else the nearest of the three edges -- and the minimum"""
+        a, b, c = tri[None, :, 0], tri[None, :, 1], tri[None, :, 2]
+        n = torch.linalg.cross(b - a, c - a)
+        nn = (n * n).sum(-1)
+        out = []
+        for i in range(0, q.shape[0], chunk):
+            p = q[i:i + chunk, None, :]
+            ap = p - a
+            inside = ((torch.linalg.cross(b - a, ap) * n).sum(-1) >= 0) & ((torch.linalg.cross(c - b, p - b) * n).sum(-1) >= 0) & \
+                     ((torch.linalg.cross(a - c, p - c) * n).sum(-1) >= 0)
+            plane = (ap * n).sum(-1) ** 2 / nn
+            edges = torch.minimum(torch.minimum(edge_d2(p, a, b), edge_d2(p, b, c)), edge_d2(p, c, a))
+            out.append(torch.where(inside, plane, edges).min(1)[0])
+        return torch.cat(out).sqrt().clamp(max=max_dist)
+
+    lines = ["tsdf_bench --mesh-distance: median of %d calls per figure between device events after 5 warm-up calls, max_dist %.1f m, %s"
+             % (reps, max_dist, torch.cuda.get_device_name(0))]
+    meshes = [("the mesh of the %d x %d x %d volume" % dims, m["xyz"].contiguous(), m["faces"].contiguous(), None),
+              ("a 320 x 320 grid of quads over a 4 m square, a gentle height field", grid_xyz, torch.from_numpy(grid_np).to(dev), None),
+              ("the 170-triangle ground truth of the run-stream tests, big list only", torch.from_numpy(gt_xyz).to(dev), torch.from_numpy(gt_faces).to(dev), float("inf"))]
+    for name, xyz, faces, cell in meshes:
+        mesh = dict(xyz=xyz, faces=faces)
+        grid = TriangleGrid(mesh, max_dist, cell)
+        big = grid.big_cells
+        lines.append("%s: %d vertices, %d triangles (%d invalid); cell %.4g, dims %s, %d pairs + %d on the big list"
+                     % (name, xyz.shape[0], faces.shape[0], grid.invalid, grid.cell, grid.dims, grid.n_pairs, grid.n_big))
+        bins = lambda: ops.mesh_tri_bins(xyz, faces, grid.lo, grid.cell, grid.dims, big)
+        lines.append("  mesh_tri_bins (kernel + the 8-byte memset + three allocations) %8.4f ms" % median_ms(bins, reps))
+        if grid.n_pairs:
+            count = bins()[0]
+            offset = (torch.cumsum(count.long(), 0) - count).contiguous()
+            lines.append("  mesh_tri_fill (kernel + two allocations)                      %8.4f ms" % median_ms(lambda: ops.mesh_tri_fill(xyz, faces, grid.lo, grid.cell, grid.dims, big, offset, grid.n_pairs), reps))
+        lines.append("  TriangleGrid, whole build (box and median area by torch, bins, cumsum, fill, stable sort, searchsorted, record gather) %8.4f ms"
+                     % median_ms(lambda: TriangleGrid(mesh, max_dist, cell), reps))
+        tri = xyz[faces.long()]
+        for n in (10 ** 5, 10 ** 6):
+            # queries near the surface, as the samples of a reconstruction are: points of the triangles, moved by up to 5 cm
+            g = torch.Generator(device=dev).manual_seed(n)
+            f = torch.randint(0, faces.shape[0], (n,), device=dev, generator=g)
+            uv = torch.rand((n, 2), device=dev, generator=g)
+            uv = torch.where((uv.sum(1) > 1)[:, None], 1 - uv, uv)
+            q = tri[f, 0] + uv[:, :1] * (tri[f, 1] - tri[f, 0]) + uv[:, 1:] * (tri[f, 2] - tri[f, 0]) + (torch.rand((n, 3), device=dev, generator=g) - 0.5) * 0.1
+            q = q.contiguous()
+            order = torch.sort(ops.cloud_cell_keys(q, grid.lo, grid.cell, grid.dims), stable=True)[1] if grid.n_pairs else torch.arange(n, device=dev)
+            search = lambda: ops.mesh_nearest(q, order, grid.big_records, grid.records, grid.cell_start, grid.lo, grid.cell, grid.dims, max_dist)
+            t_s, t_q = median_ms(search, reps), median_ms(lambda: grid.query(q), reps)
+            ny = min(n, 20000)                                 # the yardstick on the first ny queries, scaled: its cost is linear in them
+            chunk = max(1, min(ny, (1 << 24) // max(1, faces.shape[0])))
+            t_y = median_ms(lambda: yard(q[:ny], tri, chunk), 3, warmup=1) * (n / ny)
+            worst = float((grid.query(q[:ny])[0] - yard(q[:ny], tri, chunk)).abs().max().item())
+            lines += ["  M = %d queries within 5 cm of the surface:" % n,
+                      "    mesh_nearest_kernel                     %9.4f ms  (%.1f M queries/s)" % (t_s, n / t_s / 1e3),
+                      "    TriangleGrid.query (finite check, keys, sort, search) %9.4f ms" % t_q,
+                      "    yardstick: torch brute force over all triangles, %d queries timed and scaled to M: %9.1f ms (search / yardstick = 1 / %.0f); "
+                      "largest |difference| on those queries %.2g m" % (ny, t_y, t_y / t_s, worst)]
+    # compare_meshes on the run-stream ground truth against a copy moved by 2 mm, with and without exact
+    gt = dict(xyz=torch.from_numpy(gt_xyz).to(dev), faces=torch.from_numpy(gt_faces).to(dev))
+    pred = dict(xyz=gt["xyz"] + 0.002, faces=gt["faces"])
+    for density in (1111.0, 2500.0):
+        t_a = median_ms(lambda: cloud_metrics.compare_meshes(pred, gt, density), reps)
+        t_b = median_ms(lambda: cloud_metrics.compare_meshes(pred, gt, density, exact=True), reps)
+        a, b = cloud_metrics.compare_meshes(pred, gt, density), cloud_metrics.compare_meshes(pred, gt, density, exact=True)
+        lines.append("compare_meshes, the 170-triangle ground truth against itself moved by (2, 2, 2) mm, density %g (%d + %d samples): sampled %8.3f ms "
+                     "(accuracy %.5f m), exact %8.3f ms (accuracy %.5f m)" % (density, a["n_pred"], a["n_gt"], t_a, a["accuracy"], t_b, b["accuracy"]))
+    lines.append("  no bar is set in advance; not measured: an indirection (face index -> vertices) at search time instead of the gathered 48-byte records, "
+                 "an LDS broadcast instead of scalar loads in phase A, other big_cells than 64, queries far from the surface")
     text = "\n".join(lines)
     print(text)
     if args.out:
