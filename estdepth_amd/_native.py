@@ -152,6 +152,18 @@ class FrameAlignDesc(ctypes.Structure):
     ]
 
 
+class RigidSystemDesc(ctypes.Structure):
+    """Mirror of struct estd_rigid_system_desc (include/estd_hip.h)."""
+    _fields_ = [
+        ("N", ctypes.c_longlong), ("Nt", ctypes.c_longlong), ("Nn", ctypes.c_longlong),
+        ("metric", ctypes.c_int), ("by_index", ctypes.c_int), ("two_sided", ctypes.c_int),
+        ("dist_max", ctypes.c_float), ("cos_min", ctypes.c_float),
+        ("moved", ctypes.c_void_p), ("moved_normal", ctypes.c_void_p), ("index", ctypes.c_void_p), ("target", ctypes.c_void_p),
+        ("normal", ctypes.c_void_p), ("residual", ctypes.c_void_p), ("match", ctypes.c_void_p), ("sums", ctypes.c_void_p),
+        ("partials", ctypes.c_void_p),
+    ]
+
+
 _SIGNATURES = {
     "estd_version": (ctypes.c_int, []),
     "estd_status_string": (ctypes.c_char_p, [ctypes.c_int]),
@@ -259,6 +271,10 @@ _SIGNATURES = {
                                           ctypes.c_float, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong,
                                           ctypes.c_void_p, ctypes.c_void_p, c_stream]),
     "estd_mesh_nearest": (ctypes.c_int, [ctypes.POINTER(MeshNearestDesc), c_stream]),
+    "estd_rigid_apply": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_float), ctypes.c_void_p,
+                                        ctypes.c_void_p, c_stream]),
+    "estd_rigid_system_partials": (ctypes.c_longlong, [ctypes.c_longlong]),
+    "estd_rigid_system": (ctypes.c_int, [ctypes.POINTER(RigidSystemDesc), c_stream]),
 }
 
 # the superseded A/B kernels: exported only by a library built with ESTD_BUILD_AB=1 (estdepth_amd/build.py)

@@ -102,7 +102,7 @@ class PointGrid:
         self.max_dist = _check_max_dist(max_dist, "PointGrid")
         _need(cell is None or (isinstance(cell, (int, float)) and math.isfinite(cell) and cell > 0), "PointGrid: cell must be positive and finite, got %r" % (cell,))
         target = _check_cloud(target, "target", "PointGrid")
-        self.device, self.n = target.device, int(target.shape[0])
+        self.device, self.n, self.target = target.device, int(target.shape[0]), target      # the cloud in its original order: ``index`` names its rows
         if self.n == 0:
             self.cell, self.dims, self.lo = float(np.float32(self.max_dist)), (1, 1, 1), torch.zeros(3)
             self.records = torch.empty((0, 4), device=self.device)
@@ -293,8 +293,26 @@ def _side(dist, index, max_dist, threshold):
                 share=float((dist < threshold).double().mean().item()) if n else 0.0, clamped=int((index < 0).sum().item()))
 
 
+ALIGN_KEYS = ("metric", "dist_max", "max_iter", "init")
+
+
+def _align(src, src_normal, target, target_normal, align, threshold, op):
+    """``align=dict(metric="plane", dist_max=(8, 4, 2) x threshold, max_iter=30, init=None)``: register the predicted points ``src`` to the
+    ground truth (registration.register) -> (T float64 [4,4] or None when the registration did not converge, the ``alignment`` block)"""
+    from . import registration
+    _need(isinstance(align, dict) and all(k in ALIGN_KEYS for k in align), "%s: align must be a dict with keys among %s" % (op, ", ".join(ALIGN_KEYS)))
+    _need(isinstance(threshold, (int, float)) and math.isfinite(threshold) and threshold > 0, "%s: threshold must be positive and finite, got %r" % (op, threshold))
+    dist = align.get("dist_max")
+    out = registration.register(src, target, init=align.get("init"), metric=align.get("metric", "plane"),
+                                dist_max=tuple(k * threshold for k in (8.0, 4.0, 2.0)) if dist is None else dist,
+                                max_iter=30 if align.get("max_iter") is None else align["max_iter"], target_normal=target_normal)
+    block = dict(T=[float(v) for v in out["T"].reshape(-1)], correction=[float(v) for v in out["correction"]], rmse=float(out["rmse"]),
+                 overlap=float(out["overlap"]), iterations=int(out["iterations"]), converged=bool(out["converged"]), reason=out["reason"])
+    return (out["T"] if out["converged"] else None), block
+
+
 def compare_clouds(pred, gt, threshold=0.05, max_dist=None, downsample=None, pred_normal=None, gt_normal=None, pred_color=None, gt_color=None,
-                   cell=None):
+                   cell=None, align=None):
     """The 3D scores of the cloud ``pred`` [P,3] against ``gt`` [G,3] (float32, one ROCm device, finite) -> dict of floats / ints:
 
     accuracy / completeness: the mean distance pred -> gt / gt -> pred, each distance clamped to ``max_dist`` (default 20 ``threshold``);
@@ -304,7 +322,11 @@ def compare_clouds(pred, gt, threshold=0.05, max_dist=None, downsample=None, pre
     |n_pred . n_gt[index]| over found pairs, both directions averaged.  With both colours: color_l1 = the mean absolute colour difference at
     the nearest neighbour over pairs with dist < ``threshold``, both directions averaged.  ``downsample``: a voxel edge -- both clouds (and
     their normals / colours) go through ``voxel_downsample`` first, as evaluation protocols do (2 cm in Atlas's).  An empty cloud gives
-    zeros for its own means and shares.  Means are float64 sums by torch; ``cell`` is the search grid's edge (None: the default)."""
+    zeros for its own means and shares.  Means are float64 sums by torch; ``cell`` is the search grid's edge (None: the default).
+    ``align=dict(metric="plane", dist_max=None, max_iter=30, init=None)`` registers ``pred`` to ``gt`` first (registration.register; the
+    plane metric needs ``gt_normal``; ``dist_max`` defaults to 8, 4 and 2 thresholds) and scores the moved prediction, its normals
+    rotated; the result gains ``alignment`` = dict(T: 16 numbers row by row, correction, rmse, overlap, iterations, converged, reason).  A
+    registration that did not converge is reported there and the UNMOVED prediction is scored.  With the default None nothing of this runs."""
     _need(isinstance(threshold, (int, float)) and math.isfinite(threshold) and threshold > 0, "compare_clouds: threshold must be positive and finite, got %r" % (threshold,))
     if max_dist is None:
         max_dist = 20.0 * threshold
@@ -321,6 +343,17 @@ def compare_clouds(pred, gt, threshold=0.05, max_dist=None, downsample=None, pre
             _need(isinstance(a, torch.Tensor) and a.dtype == torch.float32 and tuple(a.shape) == tuple(cloud.shape) and a.device == cloud.device,
                   "compare_clouds: %s must be float32 %s on the cloud's device" % (name, tuple(cloud.shape)))
             attrs[name] = a.contiguous()
+    alignment = None
+    if align is not None:
+        from . import registration
+        T, alignment = _align(pred, attrs.get("pred_normal"), PointGrid(gt, _align_reach(align, threshold)), attrs.get("gt_normal"), align, threshold,
+                              "compare_clouds")
+        if T is not None:
+            moved = registration.transform(pred, T, attrs.get("pred_normal"))
+            if "pred_normal" in attrs:
+                pred, attrs["pred_normal"] = moved
+            else:
+                pred = moved
     if downsample is not None:
         for side, cloud in (("pred", pred), ("gt", gt)):
             cols = [attrs[k] for k in (side + "_normal", side + "_color") if k in attrs]
@@ -358,7 +391,17 @@ def compare_clouds(pred, gt, threshold=0.05, max_dist=None, downsample=None, pre
         v = [x for x in (pairs(attrs["pred_color"], attrs["gt_color"], d_pg, i_pg, l1, near),
                          pairs(attrs["gt_color"], attrs["pred_color"], d_gp, i_gp, l1, near)) if x is not None]
         out["color_l1"] = sum(v) / len(v) if v else 0.0
+    if alignment is not None:
+        out["alignment"] = alignment
     return out
+
+
+def _align_reach(align, threshold):
+    """the largest distance the registration of ``align`` looks for partners at: what its search structure is built for"""
+    d = align.get("dist_max") if isinstance(align, dict) else None
+    if d is None:
+        return 8.0 * threshold
+    return float(d) if isinstance(d, (int, float)) else max(float(v) for v in d)
 
 
 VISIBLE_KEYS = ("cam_poses", "cam_intr", "image_hw", "min_views", "tol", "depth_max", "z_near")
@@ -445,7 +488,7 @@ def _exact_scores(a, b, pred, gt, dev, threshold, max_dist, downsample, cell):
     return out
 
 
-def compare_meshes(pred, gt, density, threshold=0.05, max_dist=None, downsample=None, seed=0, cell=None, visible=None, exact=False):
+def compare_meshes(pred, gt, density, threshold=0.05, max_dist=None, downsample=None, seed=0, cell=None, visible=None, exact=False, align=None):
     """The 3D scores of the SURFACE ``pred`` against the surface ``gt``: both triangle meshes (dicts with ``xyz`` and ``faces``: what
     ``extract_mesh``, ``filter_mesh`` or ``read_ply(faces=True)`` return) are sampled by area at ``density`` points per square metre
     (``fusion3d.sample_mesh``, face normals), and the two clouds go to ``compare_clouds`` unchanged -> its dict plus ``sampled`` =
@@ -464,7 +507,13 @@ def compare_meshes(pred, gt, density, threshold=0.05, max_dist=None, downsample=
     cameras saw: the ground-truth mesh is rendered in every view (csrc/mesh/mesh_raster.hip) and its samples seen by fewer than
     ``min_views`` views are dropped before the comparison (``tol`` defaults to ``threshold``); ``sampled`` gains n_gt_visible and
     visible_share.  The predicted side is untouched.  A ground truth without faces cannot be rendered and is refused.  With the default
-    None nothing of this runs."""
+    None nothing of this runs.
+    ``align=dict(metric="plane", dist_max=None, max_iter=30, init=None)`` registers the prediction to the ground truth first, as
+    evaluation protocols with a ground truth from another frame of reference do: the prediction's samples against the ground-truth
+    SURFACE (a ``TriangleGrid``; against its points where it has no faces), ``registration.register``; then the moved prediction is
+    scored -- its samples, their normals and, for ``exact``, its vertices moved by T.  The result gains ``alignment`` (see
+    ``compare_clouds``); a registration that did not converge is reported there and the unmoved prediction is scored.  With the
+    default None nothing of this runs."""
     _need(isinstance(density, (int, float)) and math.isfinite(density) and density > 0, "compare_meshes: density must be positive and finite, got %r" % (density,))
     from . import fusion3d
     _need(all(isinstance(x, dict) and x.get("xyz") is not None for x in (pred, gt)), "compare_meshes: pred and gt must be dicts with 'xyz'")
@@ -480,6 +529,21 @@ def compare_meshes(pred, gt, density, threshold=0.05, max_dist=None, downsample=
         return out, None, 0
     (a, area_a, bad_a), (b, area_b, bad_b) = side(pred), side(gt)
     n_gt = int(b["xyz"].shape[0])
+    alignment = None
+    if align is not None:
+        from . import registration
+        reach = _align_reach(align, threshold)
+        target = TriangleGrid(gt, reach) if gt.get("faces") is not None else PointGrid(_check_cloud(b["xyz"], "gt", "compare_meshes"), reach)
+        T, alignment = _align(a["xyz"], a.get("normal"), target, None if gt.get("faces") is not None else b.get("normal"), align, threshold,
+                              "compare_meshes")
+        if T is not None:
+            a = dict(a)
+            if a.get("normal") is not None:
+                a["xyz"], a["normal"] = registration.transform(a["xyz"], T, a["normal"])
+            else:
+                a["xyz"] = registration.transform(a["xyz"], T)
+            if exact and pred.get("faces") is not None:
+                pred = dict(pred, xyz=registration.transform(fusion3d._on_device(pred["xyz"], a["xyz"].device), T))
     if visible is not None:
         b, n_gt, _ = restrict_to_visible(gt, b, visible, threshold, "compare_meshes")
     both = lambda k: k in a and k in b
@@ -493,4 +557,6 @@ def compare_meshes(pred, gt, density, threshold=0.05, max_dist=None, downsample=
                           invalid_pred=bad_a, invalid_gt=bad_b)
     if visible is not None:
         out["sampled"].update(n_gt_visible=int(b["xyz"].shape[0]), visible_share=int(b["xyz"].shape[0]) / n_gt if n_gt else 0.0)
+    if alignment is not None:
+        out["alignment"] = alignment
     return out

@@ -1428,6 +1428,69 @@ std::tuple<Tensor, Tensor, Tensor> frame_align(const Tensor& depth, const OptTen
     return {residual, match, sums};
 }
 
+// ------------------------------------------------------------------------------------------------ rigid registration
+// csrc/track/rigid_align.hip: src [n,3] (+ optional normals [n,3]) moved by T, a CPU float32 [3,4] (host values of the launch arguments)
+// -> (moved [n,3], moved_normal [n,3], or [0,3] without normals)
+std::tuple<Tensor, Tensor> rigid_apply(const Tensor& src, const OptTensor& src_normal, const Tensor& T)
+{
+    const char* op = "rigid_apply";
+    const OpScope scope(src);
+    const float* sp = check_cloud(src, op, "src", 3);
+    const int64_t n = src.size(0);
+    const bool normals = src_normal.has_value() && src_normal->defined();
+    const float* np = nullptr;
+    if (normals) {
+        np = check_cloud(*src_normal, op, "src_normal", 3);
+        TORCH_CHECK(src_normal->size(0) == n && src_normal->device() == src.device(), op, ": src_normal must be [", n, ",3] on the points' device");
+    }
+    const float* t = host_values(T, 12, op, "T", "[3,4]", true);
+    Tensor moved = new_f32({n, 3}, src), moved_normal = new_f32({normals ? n : 0, 3}, src);
+    if (n)
+        check_status(estd_rigid_apply(sp, np, (long long)n, t, moved.data_ptr<float>(), normals ? moved_normal.data_ptr<float>() : nullptr, cur_stream()),
+                     "estd_rigid_apply");
+    return {moved, moved_normal};
+}
+
+// moved [N,3] (+ moved_normal [N,3]), index int64 [N], target [Nt,3], normal [Nn,3] or none -> (residual [N], match int64 [N], sums float64 [29])
+std::tuple<Tensor, Tensor, Tensor> rigid_system(const Tensor& moved, const OptTensor& moved_normal, const Tensor& index, const Tensor& target,
+                                                const OptTensor& normal, bool by_index, int64_t metric, double dist_max, double cos_min, bool two_sided)
+{
+    const char* op = "rigid_system";
+    const OpScope scope(moved);
+    estd_rigid_system_desc d{};
+    d.moved = check_cloud(moved, op, "moved", 3);
+    const int64_t N = moved.size(0);
+    if (moved_normal.has_value() && moved_normal->defined()) {
+        d.moved_normal = check_cloud(*moved_normal, op, "moved_normal", 3);
+        TORCH_CHECK(moved_normal->size(0) == N && moved_normal->device() == moved.device(), op, ": moved_normal must be [", N, ",3] on the points' device");
+    }
+    d.index = reinterpret_cast<const long long*>(lptr(index, op, "index", moved, N));
+    d.target = check_cloud(target, op, "target", 3);
+    const int64_t Nt = target.size(0);
+    TORCH_CHECK(target.device() == moved.device() && (by_index || Nt >= N), op, ": target must be on the points' device, and [n,3] with n >= ", N,
+                " when it is not read by index");
+    int64_t Nn = Nt;
+    if (normal.has_value() && normal->defined()) {
+        d.normal = check_cloud(*normal, op, "normal", 3);
+        TORCH_CHECK(normal->device() == moved.device(), op, ": normal must be on the points' device");
+        Nn = normal->size(0);
+    }
+    check_count(metric, ESTD_RIGID_PLANE, ESTD_RIGID_POINT, op, "metric");
+    d.dist_max = positive_square_f32(dist_max, op, "dist_max", true);
+    d.cos_min = d.moved_normal ? not_nan_f32(cos_min, op, "cos_min") : (float)cos_min;
+    TORCH_CHECK(d.normal || !(metric == ESTD_RIGID_PLANE || (d.moved_normal && std::isfinite(d.cos_min))), op,
+                ": the plane metric and the cosine gate need the target's normals");
+    d.N = (long long)N; d.Nt = (long long)Nt; d.Nn = (long long)Nn;
+    d.metric = (int)metric; d.by_index = by_index; d.two_sided = two_sided;
+    Tensor residual = new_f32({N}, moved), match = at::empty({N}, moved.options().dtype(at::kLong));
+    Tensor sums = at::empty({ESTD_RIGID_SYSTEM_SUMS}, moved.options().dtype(at::kDouble));
+    Tensor partials = at::empty({estd_rigid_system_partials((long long)N) / 8}, moved.options().dtype(at::kDouble));
+    d.residual = residual.data_ptr<float>(); d.match = reinterpret_cast<long long*>(match.data_ptr<int64_t>());
+    d.sums = sums.data_ptr<double>(); d.partials = N ? partials.data_ptr<double>() : nullptr;
+    check_status(estd_rigid_system(&d, cur_stream()), "estd_rigid_system");
+    return {residual, match, sums};
+}
+
 void profile_mark(int64_t id) { check_status(estd_profile_mark((int)id, cur_stream()), "estd_profile_mark"); }
 int64_t conv3d_grid(int64_t N, int64_t D, int64_t H, int64_t W)
 {
@@ -1512,6 +1575,9 @@ TORCH_LIBRARY(estdepth_hip, m)
           "float max_dist, bool bary, bool closest) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("frame_align(Tensor depth, Tensor? conf, Tensor m_depth, Tensor m_normal, Tensor mats, float dist_max, float z_near, float conf_min) -> "
           "(Tensor, Tensor, Tensor)");
+    m.def("rigid_apply(Tensor src, Tensor? src_normal, Tensor T) -> (Tensor, Tensor)");
+    m.def("rigid_system(Tensor moved, Tensor? moved_normal, Tensor index, Tensor target, Tensor? normal, bool by_index, int metric, float dist_max, "
+          "float cos_min, bool two_sided) -> (Tensor, Tensor, Tensor)");
     m.def("profile_mark(int id) -> ()");
     m.def("set_reserved_cus(int n) -> int");
     m.def("conv3d_grid(int N, int D, int H, int W) -> int");
@@ -1576,6 +1642,8 @@ TORCH_LIBRARY_IMPL(estdepth_hip, CUDA, m)
     m.impl("mesh_tri_fill", mesh_tri_fill);
     m.impl("mesh_nearest", mesh_nearest);
     m.impl("frame_align", frame_align);
+    m.impl("rigid_apply", rigid_apply);
+    m.impl("rigid_system", rigid_system);
 }
 
 TORCH_LIBRARY_IMPL(estdepth_hip, CPU, m)

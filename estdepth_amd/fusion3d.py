@@ -345,7 +345,8 @@ class TSDFVolume:
         write_ply(path, rec.numpy(), rgb, faces=faces)
         return rec.shape[0], faces.shape[0]
 
-    def compare(self, other, threshold=0.05, w_min=1.0, max_dist=None, downsample=None, cell=None, sample=None, seed=0, visible=None, exact=False):
+    def compare(self, other, threshold=0.05, w_min=1.0, max_dist=None, downsample=None, cell=None, sample=None, seed=0, visible=None, exact=False,
+                align=None):
         """The 3D scores (``cloud_metrics.compare_clouds``: accuracy, completeness, chamfer, precision / recall / F-score at ``threshold``
         metres, ...) of this volume's surface as the prediction against ``other`` as the ground truth: another ``TSDFVolume`` -- both sides
         go through ``extract_points(w_min)`` -- or a dict with ``xyz`` [N,3] and optionally ``normal`` / ``color`` (device tensors or numpy
@@ -356,16 +357,20 @@ class TSDFVolume:
         ``visible=dict(cam_poses, cam_intr, image_hw, min_views=1, tol=None, depth_max=None)`` (needs ``sample``) drops the ground-truth
         samples the cameras did not see, as ``cloud_metrics.compare_meshes`` documents it; the result gains ``n_gt`` / ``n_gt_visible``.
         ``exact=True`` (needs ``sample``) hands both sides as meshes to ``cloud_metrics.compare_meshes(exact=True)``: distances to the
-        surfaces themselves (csrc/mesh/mesh_distance.hip), and its result (with ``sampled`` and ``exact``) comes back as it is."""
+        surfaces themselves (csrc/mesh/mesh_distance.hip), and its result (with ``sampled`` and ``exact``) comes back as it is.
+        ``align=dict(metric=, dist_max=, max_iter=, init=)`` registers this volume's surface to ``other`` first and scores the moved
+        surface (``cloud_metrics.compare_clouds`` / ``compare_meshes`` document it; the result gains ``alignment``): with ``sample`` both
+        sides go to ``compare_meshes`` as meshes, so that the registration runs against the ground truth's surface; without, the two
+        clouds are registered.  With the default None nothing of this runs."""
         from . import cloud_metrics
         if visible is not None and sample is None:
             raise RuntimeError("compare: visible= needs sample=density (the ground-truth surface is sampled, then restricted)")
-        if exact:                                                  # the surfaces themselves: cloud_metrics.compare_meshes owns that path
-            if sample is None:
-                raise RuntimeError("compare: exact=True needs sample=density (the query points are samples of the two surfaces)")
+        if exact and sample is None:
+            raise RuntimeError("compare: exact=True needs sample=density (the query points are samples of the two surfaces)")
+        if exact or (align is not None and sample is not None):    # the surfaces themselves: cloud_metrics.compare_meshes owns that path
             mesh = lambda x: x.extract_mesh(w_min=w_min) if isinstance(x, TSDFVolume) else x
             return cloud_metrics.compare_meshes(mesh(self), mesh(other), sample, threshold=threshold, max_dist=max_dist, downsample=downsample,
-                                                seed=seed, cell=cell, visible=visible, exact=True)
+                                                seed=seed, cell=cell, visible=visible, exact=bool(exact), **({} if align is None else dict(align=align)))
 
         def side(x):
             if sample is not None:
@@ -394,7 +399,7 @@ class TSDFVolume:
         out = cloud_metrics.compare_clouds(a["xyz"], b["xyz"], threshold=threshold, max_dist=max_dist, downsample=downsample,
                                            pred_normal=a.get("normal") if "normal" in b else None, gt_normal=b.get("normal") if "normal" in a else None,
                                            pred_color=a.get("color") if "color" in b else None, gt_color=b.get("color") if "color" in a else None,
-                                           cell=cell)
+                                           cell=cell, **({} if align is None else dict(align=align)))
         return out if seen is None else dict(out, **seen)
 
     def reset(self):

@@ -1759,3 +1759,80 @@ def frame_align(depth, conf, m_depth, m_normal, mats, dist_max, z_near, conf_min
         d.L[:], d.Fm[:], d.Bm[:] = flat[:12], flat[12:24], flat[24:]
         N.check(N.lib().estd_frame_align(ctypes.byref(d), _stream()), "estd_frame_align")
     return residual, match, sums
+
+
+# ---------------------------------------------------------------------------------- rigid registration (csrc/track/rigid_align.hip)
+RIGID_SYSTEM_SUMS = 29          # ESTD_RIGID_SYSTEM_SUMS (include/estd_hip.h)
+RIGID_METRICS = {"plane": 0, "point": 1}      # ESTD_RIGID_PLANE, ESTD_RIGID_POINT
+
+
+def rigid_apply(src, src_normal, T12):
+    """``src`` [n,3] (and ``src_normal`` [n,3] or None) moved by the host matrix ``T12`` (CPU float32 [3,4], row-major) ->
+    (moved [n,3], moved_normal [n,3] or None) on the points' device: T p per point and R n per normal, every coordinate a chain of
+    fused multiply-adds (include/estd_hip.h, estd_rigid_apply)."""
+    if _use_torch():
+        moved, mn = T().rigid_apply(src, src_normal, T12)
+        return moved, (mn if src_normal is not None else None)
+    op = "rigid_apply"
+    _cloud(src, op, "src")
+    n, dev = src.shape[0], src.device
+    if src_normal is not None:
+        _cloud(src_normal, op, "src_normal")
+        _need(src_normal.shape[0] == n and src_normal.device == dev, "%s: src_normal must be [%d,3] on the points' device" % (op, n))
+    flat = _host_values(T12, 12, op, "T", "[3,4]", finite=True)
+    with torch.cuda.device(dev):
+        moved = torch.empty((n, 3), device=dev)
+        mn = torch.empty((n, 3), device=dev) if src_normal is not None else None
+        if n:
+            N.check(N.lib().estd_rigid_apply(_p(src), _p(src_normal), n, (ctypes.c_float * 12)(*flat), _p(moved), _p(mn), _stream()), "estd_rigid_apply")
+    return moved, mn
+
+
+def rigid_system(moved, moved_normal, index, target, normal, by_index=True, metric="plane", dist_max=0.1, cos_min=None, two_sided=False):
+    """The Gauss-Newton system of the moved cloud ``moved`` [N,3] against its partners: ``index`` int64 [N] names the partner of every
+    point (-1 or any value out of range: none), ``target`` [Nt,3] is read at index[i] (``by_index``) or at i (the ``closest`` array of
+    mesh_nearest), ``normal`` [Nn,3] at index[i] (target normals or face normals; None: the point metric without a cosine gate).
+    ``metric``: "plane" or "point"; partners farther than ``dist_max`` are left out, and with ``moved_normal`` [N,3] and ``cos_min`` those
+    whose normals' cosine is below it (``two_sided``: whose absolute cosine is).  -> (residual [N], match int64 [N], sums float64 [29]) on the
+    points' device.  The contract is spelled out in include/estd_hip.h (estd_rigid_system)."""
+    _need(metric in RIGID_METRICS, "rigid_system: metric must be one of %s, got %r" % (sorted(RIGID_METRICS), metric))
+    dist_max, cos_min = float(dist_max), (float("-inf") if cos_min is None else float(cos_min))
+    m, by_index, two_sided = RIGID_METRICS[metric], bool(by_index), bool(two_sided)
+    if _use_torch():
+        return tuple(T().rigid_system(moved, moved_normal, index, target, normal, by_index, m, dist_max, cos_min, two_sided))
+    op = "rigid_system"
+    _cloud(moved, op, "moved")
+    n, dev = moved.shape[0], moved.device
+    if moved_normal is not None:
+        _cloud(moved_normal, op, "moved_normal")
+        _need(moved_normal.shape[0] == n and moved_normal.device == dev, "%s: moved_normal must be [%d,3] on the points' device" % (op, n))
+    _ivec(index, op, "index", dev, n)
+    _cloud(target, op, "target")
+    n_target = target.shape[0]
+    _need(target.device == dev and (by_index or n_target >= n),
+          "%s: target must be on the points' device, and [n,3] with n >= %d when it is not read by index" % (op, n))
+    n_normal = n_target
+    if normal is not None:
+        _cloud(normal, op, "normal")
+        _need(normal.device == dev, "%s: normal must be on the points' device" % op)
+        n_normal = normal.shape[0]
+    _positive_square(dist_max, op, "dist_max", square_positive=True)
+    if moved_normal is not None:
+        _not_nan(cos_min, op, "cos_min")
+    _need(normal is not None or not (m == 0 or (moved_normal is not None and math.isfinite(cos_min))),
+          "%s: the plane metric and the cosine gate need the target's normals" % op)
+    with torch.cuda.device(dev):
+        residual, match = torch.empty(n, device=dev), torch.empty(n, device=dev, dtype=torch.int64)
+        sums = torch.empty((RIGID_SYSTEM_SUMS,), device=dev, dtype=torch.float64)
+        partials = torch.empty((N.lib().estd_rigid_system_partials(n) // 8,), device=dev, dtype=torch.float64)
+        d = N.RigidSystemDesc()
+        d.N, d.Nt, d.Nn = n, n_target, n_normal
+        d.metric, d.by_index, d.two_sided = m, int(by_index), int(two_sided)
+        d.dist_max, d.cos_min = dist_max, cos_min
+        d.moved, d.index, d.target = moved.data_ptr(), index.data_ptr(), target.data_ptr()
+        d.moved_normal = moved_normal.data_ptr() if moved_normal is not None else None
+        d.normal = normal.data_ptr() if normal is not None else None
+        d.residual, d.match, d.sums = residual.data_ptr(), match.data_ptr(), sums.data_ptr()
+        d.partials = partials.data_ptr() if n else None
+        N.check(N.lib().estd_rigid_system(ctypes.byref(d), _stream()), "estd_rigid_system")
+    return residual, match, sums

@@ -980,6 +980,83 @@ typedef struct estd_mesh_nearest_desc {
 } estd_mesh_nearest_desc;
 int estd_mesh_nearest(const estd_mesh_nearest_desc* desc, estd_stream_t stream);
 
+/* ---- rigid registration of a point cloud to a cloud or a mesh (csrc/track/rigid_align.hip; float64 form: tests/rigid_align_ref.py) ----
+ * One iteration of ICP is: move the cloud, find a partner for every moved point (estd_cloud_nearest: the nearest target point;
+ * estd_mesh_nearest with `closest`: the closest surface point and its face), form the 6 x 6 Gauss-Newton system.  The two entry points
+ * below are the first and the last step; estdepth_amd/registration.py strings them together.
+ *
+ * estd_rigid_apply (rigid_apply_kernel, one lane per point).  src [n][3] float32, T12: 12 floats ON THE HOST, 3 x 4 row-major, copied
+ *   into the launch arguments.  Per point p = (x, y, z) and row j:
+ *     moved[i][j] = fma(T_j0, x, fma(T_j1, y, fma(T_j2, z, T_j3)));
+ *   with src_normal [n][3] (both normal pointers or neither), for its rows (a, b, c):
+ *     moved_normal[i][j] = fma(T_j0, a, fma(T_j1, b, T_j2 c)).
+ *   Plain vector stores; every element is written by every call.  n == 0 launches nothing.
+ *   ESTD_ERR_ARG (before any launch, no device needed): n < 0, a null T12 or an element of it that is not finite, with n > 0 a null src
+ *   or moved or only one of the two normal pointers.  ESTD_ERR_UNSUPPORTED: n >= 2^31.
+ *
+ * estd_rigid_system (rigid_system_kernel, one lane per point, 256 points per workgroup; then rigid_reduce_kernel).  Inputs, all on the
+ *   device: moved [N][3]; moved_normal [N][3] or NULL; index [N] int64; target [Nt][3], read at index[i] when by_index is set and at i
+ *   otherwise (then Nt >= N: the `closest` array of estd_mesh_nearest as it is); normal [Nn][3], read at index[i] (target normals, or
+ *   face normals).  Per point i, with k = index[i], m = moved[i]:
+ *   1. SKIPPED unless 0 <= k < Nn, and k < Nt when by_index is set: an index outside is never turned into an address;
+ *   2. q = target[by_index ? k : i];  e = q - m (per component);  e2 = fma(e_x, e_x, fma(e_y, e_y, e_z e_z));  skipped unless
+ *      e2 <= dist_max^2 (dist_max * dist_max, formed once on the host in fp32; false for a NaN);
+ *   3. with moved_normal and a cos_min that is finite (pass -infinity for no test): n = normal[k], s = moved_normal[i],
+ *      c = fma(n_x, s_x, fma(n_y, s_y, n_z s_z));  skipped unless c >= cos_min, with two_sided unless fabsf(c) >= cos_min (a ground
+ *      truth of either winding; false for a NaN).
+ *   metric == ESTD_RIGID_PLANE (n = normal[k]):
+ *      r = fma(n_x, e_x, fma(n_y, e_y, n_z e_z));  J = (n_x, n_y, n_z, w_x, w_y, w_z) with w = q x n:
+ *        w_x = fma(q_y, n_z, -(q_z n_y)),  w_y = fma(q_z, n_x, -(q_x n_z)),  w_z = fma(q_x, n_y, -(q_y n_x));
+ *      the 29 per-point terms are frame_align's: J_i J_j for the upper triangle row by row, J_i r, r r, 1.   residual[i] = r.
+ *   metric == ESTD_RIGID_POINT: the residual is the vector e, linearised as e - (t + omega x q) = e - J xi with J = [I | -[q]x] (3 x 6).
+ *      The 29 slots hold J^T J, J^T e, |e|^2 and 1, each entry ONE fp32 expression; upper triangle row by row:
+ *        [0] 1   [1] 0   [2] 0   [3] 0      [4] q_z    [5] -q_y
+ *                [6] 1   [7] 0   [8] -q_z   [9] 0      [10] q_x
+ *                        [11] 1  [12] q_y   [13] -q_x  [14] 0
+ *                                [15] fma(q_y, q_y, q_z q_z)   [16] -(q_x q_y)   [17] -(q_x q_z)
+ *                                                   [18] fma(q_x, q_x, q_z q_z)   [19] -(q_y q_z)
+ *                                                                      [20] fma(q_x, q_x, q_y q_y)
+ *        [21..23] e_x, e_y, e_z;   [24] fma(q_y, e_z, -(q_z e_y))   [25] fma(q_z, e_x, -(q_x e_z))   [26] fma(q_x, e_y, -(q_y e_x));
+ *        [27] e2 (the gated value);   [28] 1.                          residual[i] = the correctly rounded square root of e2.
+ *   A skipped point contributes zeros to all 29 sums.  In both metrics r (e) ~ the partner minus the moved point, so the system belongs to
+ *   the LEFT update T <- Exp(xi) T with xi = (t, omega) in the target's axes and the Gauss-Newton step solves (sum J^T J) xi = sum J^T r:
+ *   sums[0..20] is the upper triangle of the matrix, sums[21..26] the right-hand side, sums[27] the sum of squares, sums[28] the count.
+ * Per-point outputs, every element written by every call with plain vector stores:
+ *   residual [N] float32 (0 where the point was skipped);   match [N] int64 = k, or -1 where it was skipped.
+ * sums [ESTD_RIGID_SYSTEM_SUMS = 29] float64 on the device.  Each per-point term is widened and added in float64, no atomics, in
+ *   frame_align's fixed order: the 64 lanes of a wave by an exclusive-or butterfly (lane distances 32 .. 1), the four waves of a
+ *   workgroup in wave order through LDS, one partial per workgroup and term; in the reduce kernel lane l adds the partials of workgroups
+ *   l, l + 64, ... in ascending order and the same butterfly joins the lanes.  Bit-identical across calls and bindings.
+ * partials: device scratch of estd_rigid_system_partials(N) BYTES (29 float64 per 256 points), owned by the caller; the function
+ *   returns 0 for sizes the entry point refuses, and for N == 0.  N == 0 runs the reduce kernel alone: the sums are +0.
+ * ESTD_ERR_ARG (before any launch, no device needed): a null descriptor, a negative size, an unknown metric, dist_max or its square not
+ *   a positive finite fp32, cos_min NaN with moved_normal, a null sums, with N > 0 a null moved / index / residual / match / partials,
+ *   a null target with Nt > 0, a null normal with Nn > 0 where step 3 or the plane metric reads it, Nt < N without by_index.
+ * ESTD_ERR_UNSUPPORTED: N, Nt or Nn >= 2^31. */
+#define ESTD_RIGID_SYSTEM_SUMS 29
+#define ESTD_RIGID_PLANE 0
+#define ESTD_RIGID_POINT 1
+typedef struct estd_rigid_system_desc {
+    long long N, Nt, Nn;                          /* moved points, target rows, normal rows */
+    int metric;                                   /* ESTD_RIGID_PLANE / ESTD_RIGID_POINT */
+    int by_index;                                 /* target is read at index[i] (else at i) */
+    int two_sided;
+    float dist_max, cos_min;
+    const float* moved;                           /* [N][3] */
+    const float* moved_normal;                    /* [N][3] or NULL */
+    const long long* index;                       /* [N] */
+    const float* target;                          /* [Nt][3] */
+    const float* normal;                          /* [Nn][3] */
+    float* residual;                              /* [N] */
+    long long* match;                             /* [N] */
+    double* sums;                                 /* [ESTD_RIGID_SYSTEM_SUMS] */
+    double* partials;                             /* estd_rigid_system_partials(N) bytes */
+} estd_rigid_system_desc;
+int estd_rigid_apply(const float* src, const float* src_normal, long long n, const float* T12, float* moved, float* moved_normal,
+                     estd_stream_t stream);
+long long estd_rigid_system_partials(long long N);
+int estd_rigid_system(const estd_rigid_system_desc* desc, estd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

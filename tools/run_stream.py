@@ -164,6 +164,15 @@ def parse(argv=None):
     ap.add_argument("--score-exact", action="store_true", help="with --score-3d GT.ply (a mesh) and --score-sample: every distance is the distance "
                     "to the other SURFACE (cloud_metrics.compare_meshes(exact=True) on csrc/mesh/mesh_distance.hip), not to its nearest sample; "
                     "recon_3d gains an exact block: faces_pred, faces_gt, invalid_pred, invalid_gt")
+    ap.add_argument("--score-align", nargs="?", const="plane", default=None, choices=("plane", "point"), metavar="plane|point", help="with "
+                    "--score-3d GT.ply: register the fused surface to the ground truth first (estdepth_amd.registration: ICP with the "
+                    "point-to-plane or point-to-point metric; against the ground truth's surface where the file has faces and --score-sample is "
+                    "given) and score the moved surface -- for a ground truth in another frame of reference; recon_3d gains an alignment "
+                    "block: T, correction, rmse, overlap, iterations, converged, reason.  A registration that does not converge is reported and "
+                    "the unmoved surface is scored")
+    ap.add_argument("--score-align-dist", type=float, nargs="+", default=None, metavar="D", help="with --score-align: partners farther than D "
+                    "metres are left out; several decreasing values run as stages (default: 8, 4 and 2 score thresholds)")
+    ap.add_argument("--score-align-iters", type=int, default=30, metavar="N", help="with --score-align: Gauss-Newton iterations per stage at most")
     ap.add_argument("--render-gt-mesh", action="store_true", help="with --score-3d GT.ply (a mesh): write its depth at every fused target's pose "
                     "to <out>/gt_mesh_depth and score the predictions against it: errors_vs_gt_mesh, gt_mesh_coverage, errors_on_gt_mesh_covered")
     ap.add_argument("--score-downsample", type=float, default=None, help="with --score-3d: voxel-grid down-sampling of both clouds first (metres)")
@@ -204,6 +213,15 @@ def parse(argv=None):
             ap.error("--score-exact needs --score-3d GT.ply (a triangle mesh) and --score-sample DENSITY")
         if os.path.exists(args.score_3d) and ply_face_count(args.score_3d) == 0:
             ap.error("--score-exact needs a GT.ply with faces: %s has none, and the distance to a point cloud is the sampled one" % args.score_3d)
+    if args.score_align is not None and not isinstance(args.score_3d, str):
+        ap.error("--score-align needs --score-3d GT.ply (a ground-truth file: the reader's own depth maps share the frame of the poses)")
+    if args.score_align is None and (args.score_align_dist is not None or args.score_align_iters != 30):
+        ap.error("--score-align-dist and --score-align-iters need --score-align")
+    if args.score_align_dist is not None and not (all(0 < d < float("inf") for d in args.score_align_dist)
+                                                  and all(a > b for a, b in zip(args.score_align_dist, args.score_align_dist[1:]))):
+        ap.error("--score-align-dist takes positive distances in decreasing order")
+    if args.score_align_iters < 0:
+        ap.error("--score-align-iters must not be negative")
     if args.score_visible is not None and args.score_sample is None:
         ap.error("--score-visible needs --score-sample DENSITY (the samples of the ground-truth surface are what is restricted)")
     if args.score_visible is not None and args.score_visible < 1:
@@ -412,10 +430,14 @@ def run(args):
             if args.color and ply["rgb"] is not None:                        # the volume keeps the reader's 0..255 RGB
                 other["color"] = ply["rgb"].astype(np.float32)
         max_dist = args.score_max_dist if args.score_max_dist is not None else 20.0 * args.score_threshold
+        align = {}
+        if args.score_align is not None:
+            align = dict(align=dict(metric=args.score_align, max_iter=args.score_align_iters,
+                                    dist_max=tuple(args.score_align_dist) if args.score_align_dist is not None else None))
         torch.cuda.synchronize()
         t0 = time.time()
         if args.score_sample is None:
-            scores = volume.compare(other, threshold=args.score_threshold, max_dist=max_dist, downsample=args.score_downsample)
+            scores = volume.compare(other, threshold=args.score_threshold, max_dist=max_dist, downsample=args.score_downsample, **align)
         else:
             # surfaces, not vertices: both sides as triangle meshes sampled by area at the same density (csrc/mesh/mesh_sample.hip); a
             # ground-truth file without faces stays the cloud it is
@@ -432,7 +454,7 @@ def run(args):
                                image_hw=seen_by[fused_at[0][0]][1], min_views=args.score_visible, depth_max=args.depth_max)
             scores = compare_meshes(volume.extract_mesh(min_component=args.mesh_min_component or 0), other, args.score_sample,
                                     threshold=args.score_threshold, max_dist=max_dist, downsample=args.score_downsample, visible=visible,
-                                    **(dict(exact=True) if args.score_exact else {}))
+                                    **(dict(exact=True) if args.score_exact else {}), **align)
         torch.cuda.synchronize()
         report["recon_3d"] = dict(scores, threshold=args.score_threshold, max_dist=max_dist, downsample=args.score_downsample, ground_truth=gt_name,
                                   compare_ms=1e3 * (time.time() - t0))

@@ -54,7 +54,13 @@ from the same pose.
 times the point-to-mesh distance (csrc/mesh/mesh_distance.hip): the two binning kernels, the whole TriangleGrid build and the search at
 10^5 and 10^6 queries against that mesh and a 204 800-triangle height field, the 170-triangle ground truth of the run-stream tests on the big
 list alone, and cloud_metrics.compare_meshes with and without exact=True -- medians between device events after a warm-up -- beside the
-same minimum formed with torch operators (a chunked brute force over all triangles)."""
+same minimum formed with torch operators (a chunked brute force over all triangles).
+
+    python tools/tsdf_bench.py --register [--reps 20] [--out profiles/rigid_align_bench.txt]
+
+times the rigid registration (csrc/track/rigid_align.hip) on 10^5 and 10^6 samples of that mesh against the mesh moved by a fixed twist:
+the apply, system and reduce kernels apart, one whole iteration split into search and system, and the same sums formed with torch
+operators (gathers, einsum, .sum() in float64) on the same device."""
 import argparse
 import os
 import sys
@@ -99,8 +105,13 @@ def main():
     ap.add_argument("--mesh-raster", action="store_true", help="time the mesh rasteriser (csrc/mesh/mesh_raster.hip) beside TSDFVolume.render")
     ap.add_argument("--mesh-distance", action="store_true", help="time the point-to-mesh distance (csrc/mesh/mesh_distance.hip) beside a torch "
                     "brute force; writes profiles/mesh_distance_bench.txt unless --out says otherwise")
+    ap.add_argument("--register", action="store_true", help="time the rigid registration (csrc/track/rigid_align.hip): its kernels, one whole "
+                    "iteration and the same sums with torch operators; writes profiles/rigid_align_bench.txt unless --out says otherwise")
     ap.add_argument("--color", action="store_true", help="time the colour fuse, the edge colours and the colour render beside the plain figures")
     args = ap.parse_args()
+    if args.register:
+        args.out = args.out or os.path.join(ROOT, "profiles", "rigid_align_bench.txt")
+        return register_main(args)
     if args.raycast:
         return raycast_main(args)
     if args.mesh:
@@ -534,6 +545,109 @@ def distance_main(args):
                      "(accuracy %.5f m), exact %8.3f ms (accuracy %.5f m)" % (density, a["n_pred"], a["n_gt"], t_a, a["accuracy"], t_b, b["accuracy"]))
     lines.append("  no bar is set in advance; not measured: an indirection (face index -> vertices) at search time instead of the gathered 48-byte records, "
                  "an LDS broadcast instead of scalar loads in phase A, other big_cells than 64, queries far from the surface")
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        open(args.out, "w").write(text + "\n")
+
+
+def register_main(args):
+    """--register: the three kernels of csrc/track/rigid_align.hip apart (device times from torch.profiler), one whole iteration of
+    registration.rigid_system split into search and system, and the same 29 sums formed with torch operators (gathers, einsum, .sum() in
+    float64) on the same device -- for 10^5 and 10^6 samples of the 256^3 bench volume's mesh against that mesh moved by a fixed twist."""
+    import time
+    import tsdf_ref as R
+    from estdepth_amd import ops, registration, tracking
+    from estdepth_amd.cloud_metrics import TriangleGrid
+    from estdepth_amd.fusion3d import TSDFVolume, frustum_volume, sample_mesh
+    assert torch.cuda.is_available(), "tools/tsdf_bench.py needs a ROCm device"
+    dev = torch.device("cuda:0")
+    H, W, T, vox, dmin, dmax, dims = 480, 640, 3, 0.03, 0.1, 10.0, (256, 256, 256)
+    reps = min(args.reps, 20)
+    K = R.intrinsics(H, W)
+    poses = R.scene_poses(T, seed=1)
+    depths = torch.from_numpy(np.stack([R.raycast_scene(P, K, H, W) for P in poses]).astype(np.float32)).to(dev)
+    origin = frustum_volume(torch.from_numpy(poses[0]), torch.from_numpy(K), (H, W), dmin, dmax, dims, vox)
+    vol = TSDFVolume(dims, vox, origin, device=dev)
+    vol.integrate(depths, torch.from_numpy(poses), torch.from_numpy(K))
+    m = vol.extract_mesh()
+    twist = np.array([0.006, -0.005, 0.006, 0.005, -0.004, 0.006])                       # about 1 cm and 0.5 degrees (tests/track_ref.py TWIST)
+    G = tracking.exp_se3(twist)
+    moved_mesh = dict(xyz=registration.transform(m["xyz"].contiguous(), G), faces=m["faces"].contiguous())
+    dist_max = 0.1
+    grid = TriangleGrid(moved_mesh, dist_max)
+    normal = ops.mesh_face_area(grid.xyz, grid.faces)[1]
+    T12 = torch.from_numpy(np.ascontiguousarray(np.eye(4)[:3, :4].astype(np.float32)))
+    lines = ["tsdf_bench --register: median of %d calls per figure between device events after 5 warm-up calls; kernel times: the mean device time "
+             "torch.profiler reports over the same calls; dist_max %.2f m, plane metric, %s" % (reps, dist_max, torch.cuda.get_device_name(0)),
+             "the mesh of the %d x %d x %d volume: %d vertices, %d triangles; the target is that mesh moved by Exp(%s)" % (dims + (m["xyz"].shape[0], m["faces"].shape[0], twist.tolist()))]
+
+    def kernel_us(fn, names):
+        with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CUDA]) as prof:
+            for _ in range(reps):
+                fn()
+            torch.cuda.synchronize()
+        out = {}
+        for e in prof.key_averages():
+            for n in names:
+                if n in e.key:
+                    total = getattr(e, "self_device_time_total", None)
+                    out[n] = (total if total is not None else e.self_cuda_time_total) / max(e.count, 1)
+        return [out.get(n, float("nan")) for n in names]
+
+    def yard(moved, index, target, nrm, d2):
+        """torch operators only: the gates, J and the 29 sums (as A, b, sum r^2, count) in float64"""
+        ok = index >= 0
+        n = nrm[index.clamp(min=0)]
+        e = target - moved
+        ok = ok & ((e * e).sum(1) <= d2)
+        r = torch.where(ok, (n * e).sum(1), torch.zeros((), device=dev)).double()
+        J = torch.where(ok[:, None], torch.cat([n, torch.linalg.cross(target, n)], 1), torch.zeros((), device=dev)).double()
+        return torch.einsum("ni,nj->ij", J, J), (J * r[:, None]).sum(0), (r * r).sum(), ok.sum()
+
+    for n in (10 ** 5, 10 ** 6):
+        s = sample_mesh(dict(xyz=m["xyz"], faces=m["faces"]), n=n, seed=0)
+        src, sn = s["xyz"].contiguous(), s["normal"].contiguous()
+        for _ in range(5):
+            ops.rigid_apply(src, sn, T12)
+        moved, mn = ops.rigid_apply(src, sn, T12)
+        _, face, closest = grid.query(moved, closest=True)
+        index = face.long()
+        system = lambda: ops.rigid_system(moved, None, index, closest, normal, False, "plane", dist_max)                         # noqa: E731
+        for _ in range(5):
+            system()
+        k_apply, = kernel_us(lambda: ops.rigid_apply(src, sn, T12), ["rigid_apply_kernel"])
+        k_sys, k_red = kernel_us(system, ["rigid_system_kernel", "rigid_reduce_kernel"])
+        t_apply = median_ms(lambda: ops.rigid_apply(src, sn, T12), reps)
+        t_search = median_ms(lambda: grid.query(moved, closest=True), reps)
+        t_system = median_ms(system, reps)
+        d2 = float(np.float32(dist_max) * np.float32(dist_max))
+        t_yard = median_ms(lambda: yard(moved, index, closest, normal, d2), reps)
+        tgt = registration._Target(grid, dist_max, None, "tsdf_bench")
+        whole = []
+        for _ in range(reps + 3):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = registration.rigid_system(src, np.eye(4), tgt, metric="plane", dist_max=dist_max)
+            whole.append(1e3 * (time.perf_counter() - t0))
+        t_whole = float(np.median(whole[3:]))
+        A, b, rr, cnt = yard(moved, index, closest, normal, d2)
+        sums = system()[2].cpu().numpy()
+        Ad, bd, rrd, cntd = tracking.unpack_sums(sums)
+        gap = max(float(np.abs(Ad - A.cpu().numpy()).max() / np.abs(Ad).max()), float(np.abs(bd - b.cpu().numpy()).max() / max(np.abs(bd).max(), 1e-300)))
+        lines += ["  N = %d samples (with normals); %d matched, rmse %.5f m:" % (n, out["count"], out["rmse"]),
+                  "    rigid_apply_kernel  %9.2f us   (points and normals: %d bytes moved, %.0f GB/s -- back to back, the arrays warm in the caches)" % (k_apply, 48 * n, 48 * n / k_apply / 1e3),
+                  "    rigid_system_kernel %9.2f us   rigid_reduce_kernel %9.2f us   (%d workgroups, %d bytes read per point)" % (k_sys, k_red, (n + 255) // 256, 44),
+                  "    ops.rigid_apply (kernel + two allocations) %9.4f ms;  ops.rigid_system (two kernels + four allocations) %9.4f ms" % (t_apply, t_system),
+                  "    one iteration, registration.rigid_system, host wall time with the 29-double read-back: %9.4f ms; of it the search "
+                  "(TriangleGrid.query with closest: finite check, keys, sort, mesh_nearest) %9.4f ms, apply + system %9.4f ms"
+                  % (t_whole, t_search, t_apply + t_system),
+                  "    yardstick: the same gates and sums with torch operators (gathers, cross, einsum, .sum() in float64): %9.4f ms "
+                  "(ops.rigid_system / yardstick = 1 / %.1f); count %d against %d, largest relative difference of A and b %.2g"
+                  % (t_yard, t_yard / t_system, int(cnt.item()), cntd, gap)]
+    lines.append("  no bar is set in advance; not measured: the search fused with the system kernel (one pass over the moved cloud instead of "
+                 "two, no closest / face arrays), and a device-side 6 x 6 solve that would spare the read-back of 29 doubles per iteration")
     text = "\n".join(lines)
     print(text)
     if args.out:
