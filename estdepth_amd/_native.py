@@ -271,6 +271,12 @@ _SIGNATURES = {
                                           ctypes.c_float, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong,
                                           ctypes.c_void_p, ctypes.c_void_p, c_stream]),
     "estd_mesh_nearest": (ctypes.c_int, [ctypes.POINTER(MeshNearestDesc), c_stream]),
+    "estd_mesh_cluster_faces": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_stream]),
+    "estd_mesh_cluster_quadrics": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
+                                                  ctypes.POINTER(ctypes.c_float), ctypes.c_float, ctypes.POINTER(ctypes.c_int), ctypes.c_double,
+                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_stream]),
     "estd_rigid_apply": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_float), ctypes.c_void_p,
                                         ctypes.c_void_p, c_stream]),
     "estd_rigid_system_partials": (ctypes.c_longlong, [ctypes.c_longlong]),

@@ -1023,6 +1023,74 @@ std::tuple<Tensor, Tensor> cloud_cell_centroids(const Tensor& points, const Tens
     return {out, out_attrs};
 }
 
+// ------------------------------------------------------------------------------------------------ mesh simplification (csrc/mesh/mesh_simplify.hip)
+// the clusters of a mesh's vertices: int32 [V] on the faces' device, K of them, none without a vertex -> (V, K)
+static const int32_t* check_clusters(const Tensor& cluster, int64_t n_clusters, const Tensor& faces, const char* op)
+{
+    const int32_t* c = lptr<int32_t>(cluster, op, "cluster", faces, -1);
+    check_count(cluster.size(0), 0, 0x7fffffffLL, op, "the number of vertices");
+    check_count(n_clusters, cluster.size(0) ? 1 : 0, cluster.size(0), op, "n_clusters");
+    return c;
+}
+
+// faces [F,3] int32, cluster [V] int32 -> (corner [3F] int32, triple [F,3] int32, counts [2] int64 on the device: invalid, collapsed)
+std::tuple<Tensor, Tensor, Tensor> mesh_cluster_faces(const Tensor& faces, const Tensor& cluster, int64_t n_clusters)
+{
+    const char* op = "mesh_cluster_faces";
+    const int32_t* f = faces_ptr(faces, op, "faces");
+    const OpScope scope(faces);
+    const int32_t* c = check_clusters(cluster, n_clusters, faces, op);
+    const int64_t F = faces.size(0), V = cluster.size(0);
+    TORCH_CHECK(F <= 0x7fffffffLL / 3, op, ": at most ", 0x7fffffffLL / 3, " faces, got ", F);
+    Tensor corner = at::empty({3 * F}, faces.options()), triple = at::empty({F, 3}, faces.options());
+    Tensor counts = at::empty({2}, faces.options().dtype(at::kLong));
+    check_status(estd_mesh_cluster_faces(F ? f : nullptr, (long long)F, (long long)V, V ? c : nullptr, (long long)n_clusters,
+                                         F ? corner.data_ptr<int32_t>() : nullptr, F ? triple.data_ptr<int32_t>() : nullptr,
+                                         reinterpret_cast<long long*>(counts.data_ptr<int64_t>()), cur_stream()), "estd_mesh_cluster_faces");
+    if (F && !n_clusters) {                                   // without vertices every face is invalid; the entry point launched nothing
+        corner.zero_();
+        triple.fill_(-1);
+        counts.select(0, 0).fill_(F);
+    }
+    return {corner, triple, counts};
+}
+
+// xyz [V,3], faces [F,3] int32, order int64 [3F], segments int64 [K + 1], cell_key int64 [K], mean [K,3], lo: CPU float32 [3] ->
+// (xyz [K,3], normal [K,3], placed [K] bool)
+std::tuple<Tensor, Tensor, Tensor> mesh_cluster_quadrics(const Tensor& xyz, const Tensor& faces, const Tensor& order, const Tensor& segments,
+                                                         const Tensor& cell_key, const Tensor& mean, const Tensor& lo, double cell,
+                                                         at::IntArrayRef dims, double reg)
+{
+    const char* op = "mesh_cluster_quadrics";
+    const OpScope scope(faces);
+    const MeshArg m = check_mesh(xyz, faces, op);
+    TORCH_CHECK(m.F <= 0x7fffffffLL / 3, op, ": at most ", 0x7fffffffLL / 3, " faces, got ", m.F);
+    const int64_t* ord = lptr(order, op, "order", faces, 3 * m.F);
+    const int64_t* seg = lptr(segments, op, "segments", faces, -1);
+    TORCH_CHECK(segments.size(0) >= 1 && segments.size(0) <= m.V + 1, op, ": segments must be [K + 1] with K <= ", m.V, " vertices");
+    const int64_t K = segments.size(0) - 1;
+    const int64_t* key = lptr(cell_key, op, "cell_key", faces, K);
+    const float* mu = check_cloud(mean, op, "mean", 3);
+    TORCH_CHECK(mean.size(0) == K && mean.device() == faces.device(), op, ": mean must be [", K, ",3] on the faces' device");
+    check_cloud_grid(lo, cell, dims, op, ESTD_CLOUD_KEY_MAX_DIM);
+    TORCH_CHECK(std::isfinite(reg) && reg >= 0, op, ": reg must be finite and not negative, got ", reg);
+    Tensor out = new_f32({K, 3}, xyz), normal = new_f32({K, 3}, xyz), placed = at::empty({K}, faces.options().dtype(at::kBool));
+    const int d3[3] = {(int)dims[0], (int)dims[1], (int)dims[2]};
+    check_status(estd_mesh_cluster_quadrics(m.V ? m.xyz : nullptr, (long long)m.V, m.F ? m.faces : nullptr, (long long)m.F,
+                                            m.F ? reinterpret_cast<const long long*>(ord) : nullptr, reinterpret_cast<const long long*>(seg),
+                                            K ? reinterpret_cast<const long long*>(key) : nullptr, (long long)K, K ? mu : nullptr,
+                                            lo.data_ptr<float>(), (float)cell, d3, reg, K ? out.data_ptr<float>() : nullptr,
+                                            K ? normal.data_ptr<float>() : nullptr,
+                                            K ? reinterpret_cast<unsigned char*>(placed.data_ptr<bool>()) : nullptr, cur_stream()),
+                 "estd_mesh_cluster_quadrics");
+    if (K && !m.F) {                                          // without faces: the means, zero normals, nothing placed; nothing was launched
+        out.copy_(mean);
+        normal.zero_();
+        placed.zero_();
+    }
+    return {out, normal, placed};
+}
+
 // ------------------------------------------------------------------------------------------------ EST fusion: attention, ConvGRU glue
 Tensor warp_attention(const Tensor& kv_target, at::TensorList kv_sources, const Tensor& mats, const Tensor& depth_values,
                       double depth_min, double depth_interval)
@@ -1571,6 +1639,9 @@ TORCH_LIBRARY(estdepth_hip, m)
     m.def("mesh_tri_bins(Tensor xyz, Tensor faces, Tensor lo, float cell, int[] dims, int big_cells) -> (Tensor, Tensor, Tensor)");
     m.def("mesh_tri_fill(Tensor xyz, Tensor faces, Tensor lo, float cell, int[] dims, int big_cells, Tensor offset, int n_pairs) -> "
           "(Tensor, Tensor)");
+    m.def("mesh_cluster_faces(Tensor faces, Tensor cluster, int n_clusters) -> (Tensor, Tensor, Tensor)");
+    m.def("mesh_cluster_quadrics(Tensor xyz, Tensor faces, Tensor order, Tensor segments, Tensor cell_key, Tensor mean, Tensor lo, float cell, "
+          "int[] dims, float reg) -> (Tensor, Tensor, Tensor)");
     m.def("mesh_nearest(Tensor query, Tensor order, Tensor big_records, Tensor records, Tensor cell_start, Tensor lo, float cell, int[] dims, "
           "float max_dist, bool bary, bool closest) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("frame_align(Tensor depth, Tensor? conf, Tensor m_depth, Tensor m_normal, Tensor mats, float dist_max, float z_near, float conf_min) -> "
@@ -1641,6 +1712,8 @@ TORCH_LIBRARY_IMPL(estdepth_hip, CUDA, m)
     m.impl("mesh_tri_bins", mesh_tri_bins);
     m.impl("mesh_tri_fill", mesh_tri_fill);
     m.impl("mesh_nearest", mesh_nearest);
+    m.impl("mesh_cluster_faces", mesh_cluster_faces);
+    m.impl("mesh_cluster_quadrics", mesh_cluster_quadrics);
     m.impl("frame_align", frame_align);
     m.impl("rigid_apply", rigid_apply);
     m.impl("rigid_system", rigid_system);

@@ -318,7 +318,7 @@ class TSDFVolume:
         write_ply(path, rec.numpy(), rgb)
         return rec.shape[0]
 
-    def extract_mesh(self, w_min=1.0, min_component=0):
+    def extract_mesh(self, w_min=1.0, min_component=0, simplify=None):
         """The fused surface as a triangle mesh by naive surface nets (csrc/mesh/tsdf_mesh.hip; the contract: include/estd_hip.h,
         estd_tsdf_mesh_vertices / estd_tsdf_mesh_faces): one vertex per cell whose eight corner voxels have weight >= ``w_min`` and differ
         in sign, one quad = two triangles per sign-changing voxel edge whose four cells are observed -> dict(xyz [V,3], normal [V,3] (towards
@@ -328,14 +328,22 @@ class TSDFVolume:
         call to call, bit for bit.  A vertex no face references is kept.  Both kernels count first, the outputs are allocated exactly.
         Known limit: a cell that two separate sheets cross gets one vertex, so the sheets pinch together there.
         ``min_component=N`` > 0 passes the mesh through ``filter_mesh(min_triangles=N)``: connected components of fewer than N triangles and
-        the unreferenced vertices are dropped, and the dict gains ``components`` and ``dropped``; with the default nothing more is launched."""
+        the unreferenced vertices are dropped, and the dict gains ``components`` and ``dropped``; with the default nothing more is launched.
+        ``simplify=cell`` (metres) passes the result through ``simplify_mesh(cell, origin=the volume's origin)`` -- after ``min_component``,
+        because clustering would weld floaters to the surface -- and returns its dict (no ``cell`` / ``edge``; ``components`` and
+        ``dropped`` are carried over); with the default None nothing more is launched and the mesh is the same bits."""
         mesh = sorted_mesh(ops.tsdf_mesh_vertices, ops.tsdf_mesh_faces, self.volume, self.color, self.voxel_size, self.origin, w_min)
-        return filter_mesh(mesh, min_triangles=min_component) if min_component else mesh
+        mesh = filter_mesh(mesh, min_triangles=min_component) if min_component else mesh
+        if simplify is None:
+            return mesh
+        out = simplify_mesh(mesh, simplify, origin=[float(v) for v in self.origin])
+        out.update({k: mesh[k] for k in ("components", "dropped") if k in mesh})
+        return out
 
-    def save_mesh(self, path, w_min=1.0, color_scale=1.0, color_offset=0.0, min_component=0):
+    def save_mesh(self, path, w_min=1.0, color_scale=1.0, color_offset=0.0, min_component=0, simplify=None):
         """``extract_mesh`` as a binary little-endian PLY with normals and a face element (host side); colour as in ``save_ply``;
-        ``min_component`` as in ``extract_mesh``.  -> (vertices, triangles)"""
-        m = self.extract_mesh(w_min=w_min, min_component=min_component)
+        ``min_component`` and ``simplify`` as in ``extract_mesh``.  -> (vertices, triangles)"""
+        m = self.extract_mesh(w_min=w_min, min_component=min_component, simplify=simplify)
         rec = torch.cat([m["xyz"], m["normal"]], 1).cpu().contiguous()
         rgb = None
         if self.color is not None:
@@ -606,6 +614,112 @@ def mesh_area(mesh):
     xyz, faces = _mesh_arg(mesh, "mesh_area")
     area, _, invalid = ops.mesh_face_area(xyz, faces)
     return dict(total=float(area.sum().item()), area=area, invalid=int(invalid.item()))
+
+
+def unique_faces(triple):
+    """The host glue behind ops.mesh_cluster_faces: ``triple`` [F,3] int32 (-1 -1 -1 = no face) -> (faces [F',3] int32, kept [F'] int64: the
+    input face of each).  The surviving triples; among equal triples the one with the smallest input face index; in ascending input face
+    index.  The same three clusters in the opposite winding are another triple and stay.  Three stable sorts, column by column: no packed
+    key that could leave int64."""
+    at = torch.nonzero(triple[:, 0] >= 0).reshape(-1)
+    t = triple[at]
+    order = torch.arange(t.shape[0], device=t.device)
+    for col in (2, 1, 0):
+        order = order[torch.sort(t[order, col], stable=True)[1]]
+    ts = t[order]
+    first = torch.ones(ts.shape[0], dtype=torch.bool, device=t.device)
+    first[1:] = (ts[1:] != ts[:-1]).any(1)
+    kept = torch.sort(order[first])[0]                         # equal triples stand in ascending input order: the first is the smallest
+    return t[kept].contiguous(), at[kept]
+
+
+def simplify_mesh(mesh, cell, origin=None, placement="quadric", reg=2.0 ** -12):
+    """``mesh`` simplified by vertex clustering (csrc/mesh/mesh_simplify.hip; the contract: include/estd_hip.h, estd_mesh_cluster_faces /
+    estd_mesh_cluster_quadrics): every vertex that falls in one cell of a uniform grid of edge ``cell`` becomes one vertex, triangles
+    that lose a corner disappear and duplicates are merged.  ``mesh`` as in ``mesh_area`` (numpy arrays are moved to the device).  The
+    grid is ``cloud_cell_keys``' and starts at ``origin`` (three values, none above the bounding box's minimum; default: that minimum,
+    as in ``voxel_downsample``).  ``placement="quadric"`` puts the new vertex where the summed plane quadrics of the cell's triangles
+    are smallest, regularised towards the cell's mean by ``reg`` times the trace, and falls back to the mean where that point is not
+    well defined or leaves the cell: edges and corners survive, which the mean rounds off.  ``placement="mean"`` is the mean throughout
+    (``voxel_downsample``'s bits) and launches the faces kernel only.
+    -> dict on the device: xyz [K,3]; normal [K,3] (quadric: the area-weighted normal of the cluster's faces; mean: the normalised mean
+    of the input's normals, where it has them); faces [F',3] int32, in ascending input face index; weight / color / rgb: the clusters'
+    means, where the input has them; cluster [V] int32: input vertex -> output vertex; cell_key [K] int64, ascending; placed [K] bool;
+    count = K; stats = dict(vertices_in, faces_in, vertices, faces, collapsed, duplicates, invalid, placed, fallback: the clusters the
+    quadric placement left at their mean).  The per-vertex ``cell`` and per-quad ``edge`` of a surface-net mesh no longer apply and are
+    dropped.  A face that names a vertex outside the mesh raises RuntimeError, as in ``mesh_components``.
+    Known limit: vertex clustering does not preserve topology.  Two sheets closer than a cell weld, and edges shared by more than two
+    triangles can appear; ``mesh_edge_stats`` reports them, nothing repairs them."""
+    from .cloud_metrics import _dims
+    what = "simplify_mesh"
+    if not (isinstance(cell, (int, float)) and math.isfinite(cell) and float(np.float32(cell)) > 0):
+        raise RuntimeError("%s: cell must be positive and finite, got %r" % (what, cell))
+    if placement not in ("quadric", "mean"):
+        raise RuntimeError("%s: placement must be 'quadric' or 'mean', got %r" % (what, placement))
+    if not (isinstance(reg, (int, float)) and math.isfinite(reg) and reg >= 0):
+        raise RuntimeError("%s: reg must be finite and not negative, got %r" % (what, reg))
+    xyz, faces = _mesh_arg(mesh, what)
+    dev, n_v, n_f = faces.device, int(xyz.shape[0]), int(faces.shape[0])
+    cell = float(np.float32(cell))
+    cols, names = [], []
+    for k in ("weight", "color", "rgb") + (("normal",) if placement == "mean" else ()):
+        if mesh.get(k) is not None:
+            width = 1 if k == "weight" else 3
+            if int(mesh[k].shape[0]) != n_v or int(np.prod(mesh[k].shape)) != n_v * width:
+                raise RuntimeError("%s: %s must be [%d%s], got %s" % (what, k, n_v, "" if width == 1 else ",3", tuple(mesh[k].shape)))
+            cols.append(_on_device(mesh[k], dev).reshape(n_v, width))
+            names.append(k)
+    if n_v:
+        lo, hi = xyz.amin(0).cpu(), xyz.amax(0).cpu()
+        if origin is not None:
+            org = torch.as_tensor(np.asarray(origin, dtype=np.float32).reshape(-1))
+            if org.numel() != 3 or not bool(torch.isfinite(org).all()) or bool((org > lo).any()):
+                raise RuntimeError("%s: origin must be three finite values, none above the bounding box's minimum %s, got %r" % (what, lo.tolist(), origin))
+            lo = org
+        dims = _dims((hi.double() - lo.double()).tolist(), cell)
+        if max(dims) > ops.CLOUD_KEY_MAX_DIM:
+            raise RuntimeError("%s: %r cells per axis (at most %d): the cell %g is too small for this mesh" % (what, dims, ops.CLOUD_KEY_MAX_DIM, cell))
+        keys = ops.cloud_cell_keys(xyz, lo.contiguous(), cell, dims)
+        sorted_keys, order = torch.sort(keys, stable=True)
+        cell_key, rank, counts = torch.unique_consecutive(sorted_keys, return_inverse=True, return_counts=True)
+        cluster = torch.empty(n_v, device=dev, dtype=torch.int32)
+        cluster[order] = rank.to(torch.int32)
+        segments = torch.zeros(counts.shape[0] + 1, device=dev, dtype=torch.int64)
+        segments[1:] = torch.cumsum(counts, 0)
+        order = order.contiguous()
+        attrs = torch.cat(cols, 1) if cols else None
+        mean, mean_attrs = ops.cloud_cell_centroids(xyz, attrs[:, :ops.CLOUD_MAX_ATTRS].contiguous() if cols else None, order, segments)
+        if cols and attrs.shape[1] > ops.CLOUD_MAX_ATTRS:      # more columns than one call takes
+            mean_attrs = torch.cat([mean_attrs, ops.cloud_cell_centroids(xyz, attrs[:, ops.CLOUD_MAX_ATTRS:].contiguous(), order, segments)[1]], 1)
+    else:
+        lo, dims = torch.zeros(3), (1, 1, 1)
+        cell_key = torch.empty(0, device=dev, dtype=torch.int64)
+        cluster = torch.empty(0, device=dev, dtype=torch.int32)
+        mean, mean_attrs = xyz, (torch.cat(cols, 1) if cols else None)
+    n_k = int(cell_key.shape[0])
+    corner, triple, counts = ops.mesh_cluster_faces(faces, cluster, n_k)
+    invalid, collapsed = (int(v) for v in counts.tolist())
+    if invalid:
+        raise RuntimeError("%s: %d of %d faces name a vertex outside 0..%d" % (what, invalid, n_f, n_v - 1))
+    new_faces, _ = unique_faces(triple)
+    out = {"faces": new_faces, "cluster": cluster, "cell_key": cell_key, "count": n_k}
+    if placement == "quadric":
+        rec_cluster, rec_order = torch.sort(corner, stable=True)
+        rec_segments = torch.searchsorted(rec_cluster, torch.arange(n_k + 1, device=dev, dtype=torch.int32))
+        out["xyz"], out["normal"], out["placed"] = ops.mesh_cluster_quadrics(xyz, faces, rec_order.contiguous(), rec_segments.contiguous(), cell_key,
+                                                                             mean, lo.contiguous(), cell, dims, float(reg))
+    else:
+        out["xyz"], out["placed"] = mean, torch.zeros(n_k, device=dev, dtype=torch.bool)
+    at = 0
+    for k, c in zip(names, cols):
+        v = mean_attrs[:, at:at + c.shape[1]]
+        at += c.shape[1]
+        out[k] = torch.nn.functional.normalize(v, dim=1) if k == "normal" else (v.reshape(-1) if k == "weight" else v.contiguous())
+    placed = int(out["placed"].sum().item())
+    n_out = int(new_faces.shape[0])
+    out["stats"] = dict(vertices_in=n_v, faces_in=n_f, vertices=n_k, faces=n_out, collapsed=collapsed, duplicates=n_f - invalid - collapsed - n_out,
+                        invalid=invalid, placed=placed, fallback=n_k - placed if placement == "quadric" else 0)
+    return out
 
 
 def sample_mesh(mesh, n=None, density=None, seed=0, normals="face"):

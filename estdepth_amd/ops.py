@@ -1625,6 +1625,87 @@ def cloud_cell_centroids(points, attrs, order, segments):
     return out, out_attrs
 
 
+# ---------------------------------------------------------------------------------- mesh simplification (csrc/mesh/mesh_simplify.hip)
+MESH_MAX_FACES = 0x7fffffff // 3      # 3 F stays within int32
+
+
+def _clusters(cluster, n_clusters, dev, op):
+    """the clusters of a mesh's vertices: int32 [V] on ``dev``, ``n_clusters`` of them, none without a vertex -> V"""
+    _ivec(cluster, op, "cluster", dev, dtype=torch.int32)
+    n_vertices = cluster.shape[0]
+    _count(n_vertices, 0, 0x7fffffff, op, "the number of vertices")
+    _count(n_clusters, 1 if n_vertices else 0, n_vertices, op, "n_clusters")
+    return n_vertices
+
+
+def mesh_cluster_faces(faces, cluster, n_clusters):
+    """The triangles ``faces`` [F,3] int32 carried over to the clusters ``cluster`` [V] int32 (values 0..n_clusters-1) of their vertices ->
+    (corner [3F] int32: the cluster of corner j of face f at 3 f + j, n_clusters for a face with an index outside [0, V); triple [F,3]
+    int32: the three clusters rotated so that the smallest comes first, the winding kept, or (-1, -1, -1) for such a face and for one
+    that collapses because two of its clusters are equal; counts [2] int64 on the device: the invalid and the collapsed faces).
+    The glue after it (fusion3d.simplify_mesh): keep the triples that are not (-1, -1, -1); among equal triples keep the one with the
+    smallest input face index; emit them in ascending input face index; the same clusters in the opposite winding are another face and
+    stay; stable sorts column by column, no packed key.  include/estd_hip.h, estd_mesh_cluster_faces."""
+    n_clusters = int(n_clusters)
+    if _use_torch():
+        return tuple(T().mesh_cluster_faces(faces, cluster, n_clusters))
+    op = "mesh_cluster_faces"
+    n_faces = _faces(faces, op, "faces")
+    dev = faces.device
+    n_vertices = _clusters(cluster, n_clusters, dev, op)
+    _need(n_faces <= MESH_MAX_FACES, "%s: at most %d faces, got %d" % (op, MESH_MAX_FACES, n_faces))
+    with torch.cuda.device(dev):
+        corner = torch.empty(3 * n_faces, device=dev, dtype=torch.int32)
+        triple = torch.empty((n_faces, 3), device=dev, dtype=torch.int32)
+        counts = torch.empty(2, device=dev, dtype=torch.int64)
+        pp = (lambda t: _p(t)) if n_faces else (lambda t: None)
+        N.check(N.lib().estd_mesh_cluster_faces(pp(faces), n_faces, n_vertices, _p(cluster) if n_vertices else None, n_clusters, pp(corner),
+                                                pp(triple), _p(counts), _stream()), "estd_mesh_cluster_faces")
+        if n_faces and not n_clusters:                       # without vertices every face is invalid; the entry point launched nothing
+            corner.zero_()
+            triple.fill_(-1)
+            counts[0] = n_faces
+    return corner, triple, counts
+
+
+def mesh_cluster_quadrics(xyz, faces, order, segments, cell_key, mean, lo, cell, dims, reg):
+    """The representative vertex of every cluster of the mesh ``xyz`` [V,3] float32 / ``faces`` [F,3] int32: ``order`` int64 [3F] (the
+    corner records of mesh_cluster_faces sorted by cluster, stable: sorted position -> record), ``segments`` int64 [K + 1], ``cell_key``
+    int64 [K] (the clusters' grid keys, ascending), ``mean`` [K,3] (cloud_cell_centroids' means), the grid ``lo`` CPU float32 [3] /
+    ``cell`` / ``dims`` of cloud_cell_keys, ``reg`` the regularisation as a double -> (xyz [K,3]: the minimiser of the summed plane
+    quadrics where it is well defined and inside its cell, else the mean's bits; normal [K,3]: the area-weighted normal of the cluster's
+    faces; placed [K] bool).  Defined to the bit: include/estd_hip.h, estd_mesh_cluster_quadrics."""
+    cell, dims, reg = float(cell), [int(v) for v in dims], float(reg)
+    if _use_torch():
+        return tuple(T().mesh_cluster_quadrics(xyz, faces, order, segments, cell_key, mean, lo, cell, dims, reg))
+    op = "mesh_cluster_quadrics"
+    n_vertices, n_faces = _mesh(xyz, faces, op)
+    dev = faces.device
+    _need(n_faces <= MESH_MAX_FACES, "%s: at most %d faces, got %d" % (op, MESH_MAX_FACES, n_faces))
+    _ivec(order, op, "order", dev, 3 * n_faces)
+    _ivec(segments, op, "segments", dev)
+    _need(1 <= segments.shape[0] <= n_vertices + 1, "%s: segments must be [K + 1] with K <= %d vertices" % (op, n_vertices))
+    K = segments.shape[0] - 1
+    _ivec(cell_key, op, "cell_key", dev, K)
+    _cloud(mean, op, "mean")
+    _need(mean.shape[0] == K and mean.device == dev, "%s: mean must be [%d,3] on the faces' device" % (op, K))
+    lo3, dims = _cloud_grid(lo, cell, dims, op, CLOUD_KEY_MAX_DIM)
+    _need(math.isfinite(reg) and reg >= 0, "%s: reg must be finite and not negative, got %r" % (op, reg))
+    with torch.cuda.device(dev):
+        out, normal = torch.empty((K, 3), device=dev), torch.empty((K, 3), device=dev)
+        placed = torch.empty(K, device=dev, dtype=torch.bool)
+        pk = (lambda t: _p(t)) if K else (lambda t: None)
+        N.check(N.lib().estd_mesh_cluster_quadrics(_p(xyz) if n_vertices else None, n_vertices, _p(faces) if n_faces else None, n_faces,
+                                                   _p(order) if n_faces else None, _p(segments), pk(cell_key), K, pk(mean),
+                                                   (ctypes.c_float * 3)(*lo3), cell, (ctypes.c_int * 3)(*dims), reg, pk(out), pk(normal),
+                                                   pk(placed), _stream()), "estd_mesh_cluster_quadrics")
+        if K and not n_faces:                                # without faces: the means, zero normals, nothing placed; nothing was launched
+            out.copy_(mean)
+            normal.zero_()
+            placed.zero_()
+    return out, normal, placed
+
+
 # ---------------------------------------------------------------------------------- point-to-mesh distance (csrc/mesh/mesh_distance.hip)
 MESH_DISTANCE_MAX_PAIRS = 1 << 23      # ESTD_MESH_DISTANCE_MAX_PAIRS (include/estd_hip.h)
 MESH_DISTANCE_BIG_CELLS = 64           # ESTD_MESH_DISTANCE_BIG_CELLS

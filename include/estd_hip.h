@@ -887,6 +887,72 @@ int estd_mesh_raster(const float* xyz, long long n_vertices, const int* faces, l
 int estd_mesh_raster_resolve(const float* xyz, long long n_vertices, const int* faces, long long n_faces, const double* mat, int H, int W,
                              const unsigned long long* keys, float* depth, int* face, float* bary, int* facing, estd_stream_t stream);
 
+/* Mesh simplification by vertex clustering with quadric placement (csrc/mesh/mesh_simplify.hip; numpy form: tests/mesh_simplify_ref.py):
+ * every vertex that falls in one cell of a uniform grid becomes one vertex (Rossignac-Borrel), triangles that lose a corner disappear,
+ * and the new vertex sits where the summed plane quadrics of the cell's triangles are smallest (Lindstrom 2000), which keeps the edges
+ * and corners that the mean of the cell's vertices rounds off.  Two entry points with integer glue between them, which the host layer
+ * (estdepth_amd/fusion3d.py, simplify_mesh) owns; a foreign host repeats it as written here.  Known limit: clustering does not preserve
+ * topology -- two sheets closer than a cell weld, and edges shared by more than two triangles can appear; nothing repairs them.
+ *
+ * Grid and clusters (host glue).  The grid is the one of estd_cloud_cell_keys (lo3, cell, dims3, the same limits) and the key of a
+ *   vertex is the key that entry point writes for it.  cell_key [K] int64 = the occupied keys in ascending order, cluster [V] int32 =
+ *   the rank of the vertex's key among them (a stable sort of the keys, the distinct values, their ranks).  mean [K][3] float32 = the
+ *   per-cluster mean of the vertices as estd_cloud_cell_centroids gives it for that sort.
+ *
+ * estd_mesh_cluster_faces (mesh_cluster_faces_kernel, one lane per input face).  faces [F][3] int32, cluster [V] int32.
+ *   A face with an index outside [0, V) is INVALID (the rule of estd_mesh_components): never an address, its three corner records get
+ *   cluster K, its triple is (-1, -1, -1), and it is counted in counts[0].  Otherwise corner[3 f + j] = cluster[faces[f][j]], taken
+ *   as it is.  The face COLLAPSES when two of its three clusters are equal: counted in counts[1], triple (-1, -1, -1).  Otherwise
+ *   triple[f] = the three clusters rotated so that the smallest comes first; the winding is kept.
+ *   counts [2] int64 is zeroed by the call (a memset on `stream`) and raised with ONE integer atomic add per wave and counter.
+ *   corner [3 F] int32 and triple [F][3] int32 are written with plain stores, every element by every call that launches.
+ *   The glue after it: keep the faces whose triple is not (-1, -1, -1); among equal triples keep the one with the smallest input face
+ *   index; emit the kept triples in ascending input face index.  The same three clusters in the opposite winding are a different
+ *   triple and stay.  Stable sorts column by column: no packed key that could leave int64.
+ *
+ * estd_mesh_cluster_quadrics (mesh_cluster_quadric_kernel, eight neighbouring lanes per cluster).  The host sorts the 3 F corner records
+ *   by cluster (stable, so a cluster's records ascend in r = 3 f + j) and passes order [3 F] int64 (sorted position -> r) and segments
+ *   [K + 1] int64 (cluster k owns the sorted positions segments[k] .. segments[k + 1] - 1; the records of invalid faces, cluster K, lie
+ *   behind segments[K]).  Every operation below is ONE IEEE float64 operation in the order written, never contracted into an fma.
+ *     g = the cell of cell_key[k]:  gz = key / (dims0 dims1),  gy = (key - gz dims0 dims1) / dims0,  gx = the rest;
+ *     centre_i = (double)lo_i + ((double)g_i + 0.5) * (double)cell.
+ *   Per record r = 3 f + j of the segment, with a, b, c the vertices of face f in the face's own order, widened to float64:
+ *     e1 = b - a;  e2 = c - a;
+ *     mx = e1y * e2z - e1z * e2y;  my = e1z * e2x - e1x * e2z;  mz = e1x * e2y - e1y * e2x;      (the order of estd_mesh_face_area)
+ *     p = a - centre;  delta = (mx * px + my * py) + mz * pz;
+ *     the twelve terms  mx mx, mx my, mx mz, my my, my mz, mz mz (A),  delta mx, delta my, delta mz (b),  mx, my, mz (n).
+ *   This weights a face's plane by its squared area: no square root and no division per face.  A face with two corners in the cluster
+ *   has two records there and counts twice.  A record outside [0, 3 F) or of an invalid face is skipped: never an address.
+ *   The order of the sum.  With the segment's records numbered i = 0, 1, ... in ascending r, chain l (l = 0..7) starts from 0.0 and
+ *   adds the terms of records l, l + 8, l + 16, ... in that order; then per accumulator  x_l += x_(l xor 4),  x_l += x_(l xor 2),
+ *   x_l += x_(l xor 1), i.e. ((c0 + c4) + (c2 + c6)) + ((c1 + c5) + (c3 + c7)).
+ *   After the sum:
+ *     t = (Axx + Ayy) + Azz;  lam = t * reg;  gbar_i = (double)mean[k][i] - centre_i;
+ *     M = A + lam I (lam added to the three diagonal entries);  rhs_i = b_i + lam * gbar_i;
+ *     d0 = M00;  l10 = M10 / d0;  l20 = M20 / d0;  d1 = M11 - l10 * M10;  u21 = M21 - l20 * M10;  l21 = u21 / d1;
+ *     d2 = (M22 - l20 * M20) - l21 * u21;
+ *     y0 = rhs0;  y1 = rhs1 - l10 * y0;  y2 = (rhs2 - l20 * y0) - l21 * y1;   z_i = y_i / d_i;
+ *     s2 = z2;  s1 = z1 - l21 * s2;  s0 = (z0 - l10 * s1) - l20 * s2.
+ *   The vertex is PLACED when t > 0, d0 > 0, d1 > 0, d2 > 0 and fabs(s_i) <= 0.5 * (double)cell for i = 0, 1, 2 (a NaN fails every
+ *   test): out_xyz[k][i] = (float)(centre_i + s_i).  Otherwise out_xyz[k] = the bits of mean[k], unchanged.
+ *     len = sqrt((nx * nx + ny * ny) + nz * nz);  out_normal[k] = ((float)(nx / len), (float)(ny / len), (float)(nz / len)), or 0 0 0 when
+ *     len == 0: the area-weighted normal of the cluster's faces.  placed [K] bytes: 1 placed, 0 not.
+ *   A cluster without records (a vertex no face uses) is not placed and has a zero normal.  out_xyz [K][3], out_normal [K][3] and
+ *   placed [K] are written with plain vector stores, every element by every call that launches; no float atomics; the result is
+ *   bit-identical across calls, bindings and launch shapes.
+ *
+ * Both: F == 0 or K == 0 returns ESTD_OK and launches no kernel (estd_mesh_cluster_faces still zeroes counts); the host layers fill in
+ *   what the definition gives then -- without faces the means, zero normals and nothing placed; without vertices every face invalid.
+ * ESTD_ERR_ARG, before any launch and with no device needed: a negative size, K > V, a null counts, a null pointer with work to do
+ *   (faces / corner / triple / order with F > 0, cluster / xyz with V > 0, the per-cluster arrays with K > 0), a grid
+ *   estd_cloud_cell_keys would refuse, reg negative or not finite.  ESTD_ERR_UNSUPPORTED: V or 3 F beyond 2^31 - 1. */
+int estd_mesh_cluster_faces(const int* faces, long long n_faces, long long n_vertices, const int* cluster, long long n_clusters, int* corner,
+                            int* triple, long long* counts, estd_stream_t stream);
+int estd_mesh_cluster_quadrics(const float* xyz, long long n_vertices, const int* faces, long long n_faces, const long long* order,
+                               const long long* segments, const long long* cell_key, long long n_clusters, const float* mean,
+                               const float* lo3, float cell, const int* dims3, double reg, float* out_xyz, float* out_normal,
+                               unsigned char* placed, estd_stream_t stream);
+
 /* The distance from a point to a triangle mesh (csrc/mesh/mesh_distance.hip; numpy form: tests/mesh_distance_ref.py): per query the
  * nearest point of the nearest triangle.  What compare_meshes(exact=True) of estdepth_amd/cloud_metrics.py scores with: the distance
  * to a surface, not to its nearest sample.

@@ -1,0 +1,356 @@
+"""Mesh simplification by vertex clustering with quadric placement (include/estd_hip.h: estd_mesh_cluster_faces,
+estd_mesh_cluster_quadrics; csrc/mesh/mesh_simplify.hip; estdepth_amd.fusion3d.simplify_mesh) in numpy: the same float64 operations in
+the same order (numpy's elementwise products, sums, quotients and square roots are single rounded operations, never fused; ``np.add.at``
+adds one element after the other in the order given).  Nothing here is a bound: ``compare`` asks for EQUALITY TO THE BIT of faces,
+triples, counts, placed, xyz and normal.
+
+The order of the sums is the kernel's: per cluster the records in ascending r = 3 f + j, record i of the segment goes to chain i mod 8,
+every chain starts from 0.0, and the eight chains are joined as ((c0 + c4) + (c2 + c6)) + ((c1 + c5) + (c3 + c7)).
+
+``CASES`` are the shapes of tests/test_gpu_mesh_simplify_routes.py; ``box`` and ``noisy_sphere`` the meshes of the public-layer tests."""
+import numpy as np
+
+GROUP = 8                 # lanes per cluster in mesh_cluster_quadric_kernel
+KEY_MAX_DIM = 1 << 20     # ESTD_CLOUD_KEY_MAX_DIM
+REG = 2.0 ** -12
+
+
+# ------------------------------------------------------------------------------------------------- the grid and the clusters
+def grid(xyz, cell, origin=None):
+    """-> (lo float32 [3], cell as the fp32 value the kernels receive, dims): fusion3d.simplify_mesh's plan"""
+    cell = float(np.float32(cell))
+    lo = xyz.min(0).astype(np.float32) if origin is None else np.asarray(origin, np.float32).reshape(3)
+    hi = xyz.max(0).astype(np.float32)
+    dims = tuple(int(np.floor((float(hi[j]) - float(lo[j])) / cell)) + 1 for j in range(3))
+    return lo, cell, dims
+
+
+def keys32(xyz, lo, cell, dims):
+    """the cell keys of estd_cloud_cell_keys in numpy fp32: a subtraction, a multiplication, a floor -- nothing to fuse"""
+    inv = np.float32(1.0) / np.float32(cell)
+    c = [np.clip(np.floor(((xyz[:, j] - lo[j]).astype(np.float32) * inv).astype(np.float32)), 0, dims[j] - 1).astype(np.int64) for j in range(3)]
+    return (c[2] * dims[1] + c[1]) * dims[0] + c[0]
+
+
+def clusters(xyz, keys, attrs=None):
+    """-> (cell_key [K] ascending, cluster [V] int32, mean float32 [K,3], mean_attrs float32 [K,C] or None, count [K]): the ranks of the
+    occupied keys, and estd_cloud_cell_centroids' means -- float64 sums in vertex order, one division, one rounding to fp32"""
+    cell_key, cluster, count = np.unique(keys, return_inverse=True, return_counts=True)
+    cluster = cluster.reshape(-1)
+
+    def mean(values):
+        s = np.zeros((cell_key.shape[0], values.shape[1]), np.float64)
+        np.add.at(s, cluster, values.astype(np.float64))
+        return (s / count[:, None].astype(np.float64)).astype(np.float32)
+    return cell_key.astype(np.int64), cluster.astype(np.int32), mean(xyz), (mean(attrs) if attrs is not None else None), count
+
+
+# ------------------------------------------------------------------------------------------------- the faces kernel and its glue
+def cluster_faces(faces, n_vertices, cluster, K):
+    """-> (corner [3F] int32, triple [F,3] int32, invalid, collapsed)"""
+    F = faces.shape[0]
+    f = faces.astype(np.int64)
+    ok = ((f >= 0) & (f < n_vertices)).all(1) if F else np.zeros(0, bool)
+    c = np.full((F, 3), K, np.int32)
+    c[ok] = cluster[f[ok]]
+    flat = ok & ((c[:, 0] == c[:, 1]) | (c[:, 1] == c[:, 2]) | (c[:, 2] == c[:, 0]))
+    triple = np.full((F, 3), -1, np.int32)
+    live = ok & ~flat
+    first = np.argmin(c[live], 1) if live.any() else np.zeros(0, np.int64)          # three different values: the smallest is unique
+    rows = np.nonzero(live)[0]
+    for j in range(3):
+        triple[rows, j] = c[rows, (first + j) % 3]
+    return c.reshape(-1), triple, int((~ok).sum()), int(flat.sum())
+
+
+def unique_faces(triple):
+    """the glue: surviving triples, among equal ones the smallest input face index, in ascending input face index -> (faces, kept)"""
+    at = np.nonzero(triple[:, 0] >= 0)[0]
+    if at.shape[0] == 0:
+        return np.zeros((0, 3), np.int32), at
+    _, first = np.unique(triple[at], axis=0, return_index=True)                      # the index of the first occurrence
+    kept = np.sort(first)
+    return triple[at][kept], at[kept]
+
+
+# ------------------------------------------------------------------------------------------------- the quadric kernel
+def centres(cell_key, lo, cell, dims):
+    plane = dims[0] * dims[1]
+    gz = cell_key // plane
+    rest = cell_key - gz * plane
+    gy = rest // dims[0]
+    gx = rest - gy * dims[0]
+    g = np.stack([gx, gy, gz], 1).astype(np.float64)
+    return lo.astype(np.float64)[None, :] + (g + 0.5) * np.float64(cell)
+
+
+def quadric_sums(xyz, faces, corner, cell_key, lo, cell, dims):
+    """-> (sums float64 [K,12]: Axx Axy Axz Ayy Ayz Azz bx by bz nx ny nz in the kernel's order of addition, centre [K,3])"""
+    K, V = cell_key.shape[0], xyz.shape[0]
+    centre = centres(cell_key, lo, cell, dims)
+    order = np.argsort(corner, kind="stable")
+    order = order[corner[order] < K]                                                  # the records of invalid faces lie behind segments[K]
+    k = corner[order].astype(np.int64)
+    f = faces[order // 3].astype(np.int64)
+    ok = ((f >= 0) & (f < V)).all(1)
+    start = np.searchsorted(k, np.arange(K))
+    chain = (np.arange(k.shape[0]) - start[k]) % GROUP
+    k, f, chain = k[ok], f[ok], chain[ok]
+    a, b, c = (xyz[f[:, j]].astype(np.float64) for j in range(3))
+    e1, e2 = b - a, c - a
+    mx = e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1]
+    my = e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2]
+    mz = e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]
+    p = a - centre[k]
+    delta = (mx * p[:, 0] + my * p[:, 1]) + mz * p[:, 2]
+    terms = np.stack([mx * mx, mx * my, mx * mz, my * my, my * mz, mz * mz, delta * mx, delta * my, delta * mz, mx, my, mz], 1)
+    chains = np.zeros((K, GROUP, 12), np.float64)
+    np.add.at(chains, (k, chain), terms)                                              # one after the other, in ascending r
+    c_ = [chains[:, l] for l in range(GROUP)]
+    return ((c_[0] + c_[4]) + (c_[2] + c_[6])) + ((c_[1] + c_[5]) + (c_[3] + c_[7])), centre
+
+
+def quadrics(xyz, faces, corner, cell_key, mean, lo, cell, dims, reg=REG):
+    """-> (xyz float32 [K,3], normal float32 [K,3], placed bool [K], s float64 [K,3], t float64 [K])"""
+    S, centre = quadric_sums(xyz, faces, corner, cell_key, lo, cell, dims)
+    with np.errstate(all="ignore"):
+        axx, axy, axz, ayy, ayz, azz = (S[:, i] for i in range(6))
+        b, n = S[:, 6:9], S[:, 9:12]
+        t = (axx + ayy) + azz
+        lam = t * np.float64(reg)
+        g = mean.astype(np.float64) - centre
+        M00, M11, M22, M10, M20, M21 = axx + lam, ayy + lam, azz + lam, axy, axz, ayz
+        r0, r1, r2 = b[:, 0] + lam * g[:, 0], b[:, 1] + lam * g[:, 1], b[:, 2] + lam * g[:, 2]
+        d0 = M00
+        l10, l20 = M10 / d0, M20 / d0
+        d1 = M11 - l10 * M10
+        u21 = M21 - l20 * M10
+        l21 = u21 / d1
+        d2 = (M22 - l20 * M20) - l21 * u21
+        y0 = r0
+        y1 = r1 - l10 * y0
+        y2 = (r2 - l20 * y0) - l21 * y1
+        z0, z1, z2 = y0 / d0, y1 / d1, y2 / d2
+        s2 = z2
+        s1 = z1 - l21 * s2
+        s0 = (z0 - l10 * s1) - l20 * s2
+        s = np.stack([s0, s1, s2], 1)
+        half = 0.5 * np.float64(cell)
+        placed = (t > 0) & (d0 > 0) & (d1 > 0) & (d2 > 0) & (np.abs(s) <= half).all(1)
+        out = np.where(placed[:, None], (centre + s).astype(np.float32), mean)
+        length = np.sqrt((n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1]) + n[:, 2] * n[:, 2])
+        normal = np.where((length == 0)[:, None], np.float32(0), (n / length[:, None]).astype(np.float32)).astype(np.float32)
+    return out.astype(np.float32), normal, placed, s, t
+
+
+def simplify(xyz, faces, cell, origin=None, placement="quadric", reg=REG, attrs=None):
+    """fusion3d.simplify_mesh on the host -> dict; a face outside the mesh is counted and ignored (the public layer raises)"""
+    xyz, faces = np.ascontiguousarray(xyz, np.float32), np.ascontiguousarray(faces, np.int32)
+    lo, cell, dims = grid(xyz, cell, origin)
+    assert max(dims) <= KEY_MAX_DIM
+    cell_key, cluster, mean, mean_attrs, count = clusters(xyz, keys32(xyz, lo, cell, dims), attrs)
+    K = cell_key.shape[0]
+    corner, triple, invalid, collapsed = cluster_faces(faces, xyz.shape[0], cluster, K)
+    new_faces, kept = unique_faces(triple)
+    out = dict(lo=lo, cell=cell, dims=dims, cell_key=cell_key, cluster=cluster, mean=mean, attrs=mean_attrs, counts=count, corner=corner, triple=triple,
+               faces=new_faces, kept=kept)
+    if placement == "quadric":
+        out["xyz"], out["normal"], out["placed"], out["s"], out["t"] = quadrics(xyz, faces, corner, cell_key, mean, lo, cell, dims, reg)
+    else:
+        out["xyz"], out["placed"] = mean, np.zeros(K, bool)
+    placed = int(out["placed"].sum())
+    out["stats"] = dict(vertices_in=int(xyz.shape[0]), faces_in=int(faces.shape[0]), vertices=K, faces=int(new_faces.shape[0]), collapsed=collapsed,
+                        duplicates=int(faces.shape[0]) - invalid - collapsed - int(new_faces.shape[0]), invalid=invalid, placed=placed,
+                        fallback=K - placed if placement == "quadric" else 0)
+    return out
+
+
+def bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view({4: np.uint32, 8: np.uint64, 1: np.uint8}[a.dtype.itemsize]) if a.dtype.kind == "f" else a
+
+
+def compare(got, want, what, keys=("corner", "triple", "faces", "xyz", "normal", "placed")):
+    """equality to the bit of every entry both sides have -> the number of values compared"""
+    n = 0
+    for k in keys:
+        if k not in got or k not in want:
+            continue
+        g, w = np.asarray(got[k]), np.asarray(want[k])
+        assert g.shape == w.shape and g.dtype == w.dtype, "%s: %s is %s %s, the reference's %s %s" % (what, k, g.dtype, g.shape, w.dtype, w.shape)
+        same = bits(g) == bits(w)
+        assert same.all(), "%s: %s differs from the reference in %d of %d values, first at %s: %r against %r" % (
+            what, k, int((~same).sum()), same.size, np.argwhere(~same)[0].tolist(), g[tuple(np.argwhere(~same)[0])], w[tuple(np.argwhere(~same)[0])])
+        n += same.size
+    return n
+
+
+def edge_stats(faces):
+    """-> dict(boundary, manifold, non_manifold, edges, euler): estdepth_amd.fusion3d.mesh_edge_stats on the host"""
+    f = np.asarray(faces, np.int64)
+    if f.shape[0] == 0:
+        return dict(boundary=0, manifold=0, non_manifold=0, edges=0, euler=0)
+    e = np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]])
+    counts = np.unique(np.sort(e, 1), axis=0, return_counts=True)[1]
+    return dict(boundary=int((counts == 1).sum()), manifold=int((counts == 2).sum()), non_manifold=int((counts > 2).sum()), edges=int(counts.shape[0]),
+                euler=int(np.unique(f).shape[0]) - int(counts.shape[0]) + int(f.shape[0]))
+
+
+# ------------------------------------------------------------------------------------------------- meshes
+BOX_LO, BOX_HI = np.asarray([0.13, 0.21, 0.17]), np.asarray([1.07, 0.93, 0.71])
+
+
+def box(lo=BOX_LO, hi=BOX_HI, step=0.02):
+    """the surface of an axis-aligned box tessellated at ``step``, counter-clockwise seen from outside -> (xyz float32, faces int32)"""
+    n = np.rint((np.asarray(hi) - np.asarray(lo)) / step).astype(int)
+    index, xyz, faces = {}, [], []
+
+    def vertex(i, j, k):
+        if (i, j, k) not in index:
+            index[(i, j, k)] = len(xyz)
+            xyz.append([lo[0] + i * step, lo[1] + j * step, lo[2] + k * step])
+        return index[(i, j, k)]
+    for axis in range(3):
+        u, v = (axis + 1) % 3, (axis + 2) % 3
+        for side in (0, 1):
+            for a in range(n[u]):
+                for b in range(n[v]):
+                    def at(da, db):
+                        c = [0, 0, 0]
+                        c[axis], c[u], c[v] = side * n[axis], a + da, b + db
+                        return vertex(*c)
+                    q = [at(0, 0), at(1, 0), at(1, 1), at(0, 1)]                      # counter-clockwise seen from +axis (u x v = axis)
+                    if side == 0:
+                        q = q[::-1]
+                    faces += [[q[0], q[1], q[2]], [q[0], q[2], q[3]]]
+    return np.asarray(xyz, np.float64).astype(np.float32), np.asarray(faces, np.int32)
+
+
+def box_distance(p, lo=BOX_LO, hi=BOX_HI):
+    """the distance of the points ``p`` [n,3] from the SURFACE of the box, float64"""
+    p = np.asarray(p, np.float64)
+    d = np.maximum(np.maximum(lo - p, p - hi), 0.0)
+    outside = np.sqrt((d * d).sum(1))
+    inside = np.minimum(p - lo, hi - p).min(1)
+    return np.where(outside > 0, outside, np.maximum(inside, 0.0))
+
+
+def uv_sphere(radius=0.37, bands=48, centre=(0.41, 0.43, 0.39)):
+    """a UV sphere of ``bands`` latitude bands and 2 ``bands`` meridians, counter-clockwise seen from outside"""
+    m = 2 * bands
+    xyz = [[0.0, 0.0, 1.0]]
+    for i in range(1, bands):
+        th = np.pi * i / bands
+        for j in range(m):
+            ph = 2 * np.pi * j / m
+            xyz.append([np.sin(th) * np.cos(ph), np.sin(th) * np.sin(ph), np.cos(th)])
+    xyz.append([0.0, 0.0, -1.0])
+    ring = lambda i, j: 1 + (i - 1) * m + j % m                                       # noqa: E731
+    faces = [[0, ring(1, j), ring(1, j + 1)] for j in range(m)]
+    for i in range(1, bands - 1):
+        for j in range(m):
+            a, b, c, d = ring(i, j), ring(i + 1, j), ring(i + 1, j + 1), ring(i, j + 1)
+            faces += [[a, b, c], [a, c, d]]
+    last = len(xyz) - 1
+    faces += [[last, ring(bands - 1, j + 1), ring(bands - 1, j)] for j in range(m)]
+    return (np.asarray(centre) + radius * np.asarray(xyz, np.float64)), np.asarray(faces, np.int32)
+
+
+def noisy_sphere(sigma=0.002, seed=1):
+    xyz, faces = uv_sphere()
+    return (xyz + np.random.RandomState(seed).normal(0.0, sigma, xyz.shape)).astype(np.float32), faces
+
+
+def patch(n_faces, seed=3):
+    """the first ``n_faces`` triangles of a bumpy height field with 3 cm spacing (about three vertices per 10 cm cell and axis)"""
+    side = 2
+    while 2 * (side - 1) ** 2 < n_faces:
+        side += 1
+    rng = np.random.RandomState(seed)
+    u, v = np.meshgrid(np.arange(side) * 0.03, np.arange(side) * 0.03, indexing="xy")
+    z = 0.08 * np.sin(7.0 * u) * np.cos(5.0 * v) + rng.normal(0, 0.002, u.shape)
+    xyz = np.stack([u + 0.211, v + 0.137, z + 0.5], -1).reshape(-1, 3)
+    faces = []
+    for r in range(side - 1):
+        for c in range(side - 1):
+            a = r * side + c
+            faces += [[a, a + 1, a + side + 1], [a, a + side + 1, a + side]]
+    return xyz.astype(np.float32), np.asarray(faces[:n_faces], np.int32).reshape(-1, 3)
+
+
+def fan(n):
+    """a shallow cone: the apex alone in its cell with ``n`` triangles round it, i.e. n records in the apex's cluster"""
+    ang = 2 * np.pi * np.arange(n + 1) / max(n + 1, 7)
+    rim = np.stack([0.55 + 0.3 * np.cos(ang), 0.55 + 0.3 * np.sin(ang), 0.5 + 0.01 * np.sin(3 * ang)], 1)
+    xyz = np.concatenate([[[0.55, 0.55, 0.53]], rim])
+    return xyz.astype(np.float32), np.asarray([[0, 1 + i, 2 + i] for i in range(n)], np.int32)
+
+
+def one_vertex_per_cell(nx=13, ny=5):
+    """nx * ny clusters of one vertex each: nothing collapses"""
+    rng = np.random.RandomState(5)
+    u, v = np.meshgrid(np.arange(nx), np.arange(ny), indexing="xy")
+    xyz = np.stack([0.05 + 0.1 * u + rng.uniform(-0.03, 0.03, u.shape), 0.05 + 0.1 * v + rng.uniform(-0.03, 0.03, u.shape),
+                    0.05 + rng.uniform(-0.03, 0.03, u.shape)], -1).reshape(-1, 3)
+    faces = []
+    for r in range(ny - 1):
+        for c in range(nx - 1):
+            a = r * nx + c
+            faces += [[a, a + 1, a + nx + 1], [a, a + nx + 1, a + nx]]
+    return xyz.astype(np.float32), np.asarray(faces, np.int32), (0.0, 0.0, 0.0)
+
+
+def build_case(name):
+    """-> (xyz float32 [V,3], faces int32 [F,3], cell, origin or None)"""
+    cell, origin = 0.1, None
+    if name.startswith("patch-"):
+        xyz, faces = patch(int(name.split("-")[1]))
+    elif name == "one-cluster":                                 # K = 1: nothing survives
+        xyz, faces = patch(8)
+        cell = 1.0
+    elif name == "clusters-65":
+        xyz, faces, origin = one_vertex_per_cell()
+    elif name.startswith("fan-"):
+        xyz, faces = fan(int(name.split("-")[1]))
+    elif name == "invalid":                                     # at the first position, the last, either side of the wave boundaries
+        xyz, faces = patch(257)
+        V = xyz.shape[0]
+        for at, bad in ((0, -1), (63, V), (64, 2 ** 31 - 1), (127, -2 ** 31), (128, V + 7), (256, -5)):
+            faces[at, at % 3] = bad
+    elif name == "odd-faces":                                   # a vertex named twice; the same face again, rotated and reversed
+        xyz, faces = patch(65)
+        side = int(round(xyz.shape[0] ** 0.5))
+        c00, c01, c10, c11 = 0, side - 1, side * (side - 1), side * side - 1
+        far = np.asarray([[c00, c01, c11], [c00, c11, c10], [c01, c11, c10]], np.int32)      # between the patch's corners: they survive the clustering
+        faces = np.concatenate([faces, far, far[:, [1, 2, 0]], far[:, [0, 2, 1]], far[:1], [[5, 5, 9], [7, 30, 7]]]).astype(np.int32)
+    elif name == "zero-area":                                   # collinear vertices: a cluster whose only faces have m = 0, hence t = 0
+        xyz, faces = patch(65)
+        line = np.asarray([[1.5, 1.5, 0.5], [1.7, 1.5, 0.5], [1.9, 1.5, 0.5]], np.float32)
+        V = xyz.shape[0]
+        xyz, faces = np.concatenate([xyz, line]), np.concatenate([faces, [[V, V + 1, V + 2], [V + 2, V + 1, V]]]).astype(np.int32)
+    elif name == "wedge":                                       # two shallow planes that meet at x = 0.2, outside the cell 0 <= x < 0.1
+        xyz = np.asarray([[0.02, 0.02, 0.05 * 0.02 + 0.03], [0.08, 0.03, 0.05 * 0.08 + 0.03], [0.04, 0.08, 0.05 * 0.04 + 0.03],
+                          [0.03, 0.03, -0.05 * 0.03 + 0.05], [0.07, 0.02, -0.05 * 0.07 + 0.05], [0.05, 0.07, -0.05 * 0.05 + 0.05]], np.float32)
+        faces, origin = np.asarray([[0, 1, 2], [3, 4, 5]], np.int32), (0.0, 0.0, 0.0)
+    elif name == "loose-vertex":                                # a vertex no face uses, alone in its cell
+        xyz, faces = patch(63)
+        xyz = np.concatenate([xyz, [[2.05, 0.15, 0.5]]]).astype(np.float32)
+    elif name == "offset-1000":
+        xyz, faces = patch(257)
+        xyz = (xyz.astype(np.float64) + 1000.0).astype(np.float32)
+    else:
+        raise KeyError(name)
+    return np.ascontiguousarray(xyz, np.float32), np.ascontiguousarray(faces, np.int32), cell, origin
+
+
+CASES = ["patch-0", "patch-1", "patch-63", "patch-64", "patch-65", "patch-257", "one-cluster", "clusters-65", "fan-1", "fan-64", "fan-65", "fan-300",
+         "invalid", "odd-faces", "zero-area", "wedge", "loose-vertex", "offset-1000"]
+_EXPECTED = {}
+
+
+def expected(name):
+    """the reference's result for a case, computed once and shared (callers leave it unchanged)"""
+    if name not in _EXPECTED:
+        xyz, faces, cell, origin = build_case(name)
+        _EXPECTED[name] = simplify(xyz, faces, cell, origin)
+    return _EXPECTED[name]

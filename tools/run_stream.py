@@ -17,6 +17,11 @@ ground-truth depth.  Needs an MI355X (the model has no CPU path).
         # + the mesh without its floaters: connected components of fewer than 100 triangles and the vertices no face uses are dropped
         # (fusion3d.filter_mesh over the GPU union-find of csrc/mesh/mesh_components.hip) before the file is written and the edges are
         # counted; the "mesh" block gains components, components_kept, vertices_dropped and faces_dropped
+    python tools/run_stream.py --synthetic 8 --out /tmp/eval --fuse /tmp/eval/scene.ply --mesh /tmp/eval/scene_mesh.ply --mesh-simplify 0.08
+        # + the mesh simplified: every vertex in one 8 cm cell of a grid anchored at the volume's origin becomes one vertex, placed where the
+        # plane quadrics of the cell's triangles are smallest (fusion3d.simplify_mesh on csrc/mesh/mesh_simplify.hip), after
+        # --mesh-min-component; the file, the edge counts and the --score-sample scores are the simplified mesh's, and the "mesh" block gains
+        # simplify: cell, vertices_in, faces_in, vertices, faces, collapsed, duplicates, invalid, placed, fallback, euler
     python tools/run_stream.py --synthetic 8 --out /tmp/eval --fuse /tmp/eval/scene.ply --render-fused
         # + the fused volume ray-cast at every target's pose (TSDFVolume.render): <out>/fused_depth/*.npy beside refined_depth/ (float16,
         # same layout) and the fused depth scored against the same ground truth (errors_fused, fused_coverage, errors_on_covered)
@@ -140,6 +145,9 @@ def parse(argv=None):
                     "with --color the vertices get red / green / blue) and report its size and edge statistics")
     ap.add_argument("--mesh-min-component", type=int, metavar="N", help="with --mesh: drop the connected components of fewer than N triangles "
                     "and the vertices no face uses (fusion3d.filter_mesh) before the mesh is written and its edges are counted")
+    ap.add_argument("--mesh-simplify", type=float, metavar="CELL", help="with --mesh: simplify the mesh by vertex clustering with quadric placement "
+                    "on a grid of CELL metres anchored at the volume's origin (fusion3d.simplify_mesh, after --mesh-min-component); the mesh that "
+                    "is written, counted and scored with --score-sample is the simplified one, and the mesh block gains a simplify block")
     ap.add_argument("--render-fused", action="store_true", help="with --fuse: after the stream, render the volume at every target's pose, "
                     "write the fused depth maps to <out>/fused_depth and score them against the ground truth")
     ap.add_argument("--color", action="store_true", help="with --fuse: fuse every target's frame (the reader's 0..255 RGB, whatever the model is "
@@ -195,6 +203,10 @@ def parse(argv=None):
         ap.error("--mesh-min-component needs --mesh MESH.ply")
     if args.mesh_min_component is not None and args.mesh_min_component < 1:
         ap.error("--mesh-min-component must be at least 1")
+    if args.mesh_simplify is not None and not args.mesh:
+        ap.error("--mesh-simplify needs --mesh MESH.ply")
+    if args.mesh_simplify is not None and not (args.mesh_simplify > 0 and args.mesh_simplify < float("inf")):
+        ap.error("--mesh-simplify must be a positive cell edge in metres")
     if args.color and not args.fuse:
         ap.error("--color needs --fuse PATH.ply")
     if args.score_3d is not None and not args.fuse:
@@ -409,14 +421,16 @@ def run(args):
     if volume is not None and args.mesh:
         from estdepth_amd.fusion3d import mesh_edge_stats
         os.makedirs(os.path.dirname(os.path.abspath(args.mesh)), exist_ok=True)
-        n_vertices, n_faces = volume.save_mesh(args.mesh, min_component=args.mesh_min_component or 0)
-        mesh = volume.extract_mesh(min_component=args.mesh_min_component or 0)
+        n_vertices, n_faces = volume.save_mesh(args.mesh, min_component=args.mesh_min_component or 0, simplify=args.mesh_simplify)
+        mesh = volume.extract_mesh(min_component=args.mesh_min_component or 0, simplify=args.mesh_simplify)
         stats = mesh_edge_stats(mesh["faces"])
         report["mesh"] = {"path": args.mesh, "vertices": n_vertices, "faces": n_faces, "boundary_edges": stats["boundary"],
                           "manifold_edges": stats["manifold"], "non_manifold_edges": stats["non_manifold"]}
         if args.mesh_min_component is not None:       # the file and the edge statistics above are the filtered mesh's
             report["mesh"].update(components=mesh["components"] + mesh["dropped"]["components"], components_kept=mesh["components"],
                                   vertices_dropped=mesh["dropped"]["vertices"], faces_dropped=mesh["dropped"]["faces"])
+        if args.mesh_simplify is not None:            # the file, the edge statistics and the 3D scores are the simplified mesh's
+            report["mesh"].update(simplify=dict(mesh["stats"], cell=args.mesh_simplify, euler=stats["euler"]))
     if args.track and volume is not None:
         report["tracking"] = {"frames": tracked, "dist_max": args.track_dist if args.track_dist is not None else volume.trunc,
                               "max_iter": args.track_iters, "mean_track_ms": float(np.mean(track_ms[1:] or track_ms or [0.0]))}
@@ -452,7 +466,7 @@ def run(args):
             if args.score_visible is not None:                               # only the ground truth some fused target saw
                 visible = dict(cam_poses=torch.stack([p for _, p in fused_at]), cam_intr=torch.stack([seen_by[n][0] for n, _ in fused_at]),
                                image_hw=seen_by[fused_at[0][0]][1], min_views=args.score_visible, depth_max=args.depth_max)
-            scores = compare_meshes(volume.extract_mesh(min_component=args.mesh_min_component or 0), other, args.score_sample,
+            scores = compare_meshes(volume.extract_mesh(min_component=args.mesh_min_component or 0, simplify=args.mesh_simplify), other, args.score_sample,
                                     threshold=args.score_threshold, max_dist=max_dist, downsample=args.score_downsample, visible=visible,
                                     **(dict(exact=True) if args.score_exact else {}), **align)
         torch.cuda.synchronize()

@@ -60,7 +60,14 @@ same minimum formed with torch operators (a chunked brute force over all triangl
 
 times the rigid registration (csrc/track/rigid_align.hip) on 10^5 and 10^6 samples of that mesh against the mesh moved by a fixed twist:
 the apply, system and reduce kernels apart, one whole iteration split into search and system, and the same sums formed with torch
-operators (gathers, einsum, .sum() in float64) on the same device."""
+operators (gathers, einsum, .sum() in float64) on the same device.
+
+    python tools/tsdf_bench.py --mesh-simplify [--reps 50] [--parent-tree DIR] [--out profiles/mesh_simplify_bench.txt]
+
+times the mesh simplification (csrc/mesh/mesh_simplify.hip) on that mesh and on the 204 800-triangle height field: the two kernels apart
+and the whole fusion3d.simplify_mesh -- medians of warm calls between device events -- beside the same sums formed with torch operators
+(gathers and index_add_ in float64).  --parent-tree DIR (a built checkout of the parent commit) adds the gate: the default extract_mesh of
+both trees in alternating pairs of fresh processes."""
 import argparse
 import os
 import sys
@@ -107,11 +114,18 @@ def main():
                     "brute force; writes profiles/mesh_distance_bench.txt unless --out says otherwise")
     ap.add_argument("--register", action="store_true", help="time the rigid registration (csrc/track/rigid_align.hip): its kernels, one whole "
                     "iteration and the same sums with torch operators; writes profiles/rigid_align_bench.txt unless --out says otherwise")
+    ap.add_argument("--mesh-simplify", action="store_true", help="time the mesh simplification (csrc/mesh/mesh_simplify.hip): its kernels, the whole "
+                    "simplify_mesh and the same sums with torch operators; writes profiles/mesh_simplify_bench.txt unless --out says otherwise")
+    ap.add_argument("--parent-tree", metavar="DIR", help="with --mesh-simplify: a built checkout of the parent commit; the default extract_mesh of both "
+                    "trees is timed in alternating pairs of fresh processes")
     ap.add_argument("--color", action="store_true", help="time the colour fuse, the edge colours and the colour render beside the plain figures")
     args = ap.parse_args()
     if args.register:
         args.out = args.out or os.path.join(ROOT, "profiles", "rigid_align_bench.txt")
         return register_main(args)
+    if args.mesh_simplify:
+        args.out = args.out or os.path.join(ROOT, "profiles", "mesh_simplify_bench.txt")
+        return simplify_main(args)
     if args.raycast:
         return raycast_main(args)
     if args.mesh:
@@ -545,6 +559,142 @@ def distance_main(args):
                      "(accuracy %.5f m), exact %8.3f ms (accuracy %.5f m)" % (density, a["n_pred"], a["n_gt"], t_a, a["accuracy"], t_b, b["accuracy"]))
     lines.append("  no bar is set in advance; not measured: an indirection (face index -> vertices) at search time instead of the gathered 48-byte records, "
                  "an LDS broadcast instead of scalar loads in phase A, other big_cells than 64, queries far from the surface")
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        open(args.out, "w").write(text + "\n")
+
+
+EXTRACT_SNIPPET = """
+import sys, numpy as np, torch
+sys.path.insert(0, 'tests')
+import tsdf_ref as R
+from estdepth_amd.fusion3d import TSDFVolume, frustum_volume
+dev = torch.device('cuda:0')
+H, W, T, vox, dims = 480, 640, 3, 0.03, (256, 256, 256)
+K = R.intrinsics(H, W)
+poses = R.scene_poses(T, seed=1)
+depths = torch.from_numpy(np.stack([R.raycast_scene(P, K, H, W) for P in poses]).astype(np.float32)).to(dev)
+vol = TSDFVolume(dims, vox, frustum_volume(torch.from_numpy(poses[0]), torch.from_numpy(K), (H, W), 0.1, 10.0, dims, vox), device=dev)
+vol.integrate(depths, torch.from_numpy(poses), torch.from_numpy(K))
+for _ in range(5):
+    vol.extract_mesh()
+torch.cuda.synchronize()
+ms = []
+for _ in range(%d):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(); vol.extract_mesh(); e1.record(); torch.cuda.synchronize()
+    ms.append(e0.elapsed_time(e1))
+print('EXTRACT_MS %%.4f' %% float(np.median(ms)))
+"""
+
+
+def extract_pairs(parent, reps, pairs=5):
+    """the default extract_mesh of the parent's tree and of this one, in alternating fresh processes -> [(parent ms, this ms), ...]"""
+    import subprocess
+    out = []
+    for _ in range(pairs):
+        row = []
+        for tree in (parent, ROOT):
+            r = subprocess.run([sys.executable, "-c", EXTRACT_SNIPPET % reps], cwd=tree, env=dict(os.environ, PYTHONPATH=tree), capture_output=True,
+                               text=True, timeout=300)
+            if r.returncode != 0:
+                raise RuntimeError("the extract_mesh timing failed in %s (exit %d):\n%s" % (tree, r.returncode, r.stderr[-2000:]))
+            row.append(float(r.stdout.split("EXTRACT_MS")[1].split()[0]))
+        out.append(tuple(row))
+    return out
+
+
+def simplify_main(args):
+    """--mesh-simplify: the two kernels of csrc/mesh/mesh_simplify.hip apart (through the C ABI, on prepared glue), the whole
+    fusion3d.simplify_mesh, and the quadric sums formed with torch operators (gathers, index_add_ in float64), on the mesh of the 256^3
+    bench volume and on the 204 800-triangle height field of --mesh-distance; medians of warm calls between device events."""
+    import ctypes
+    import tsdf_ref as R
+    from estdepth_amd import _native, cloud_metrics
+    from estdepth_amd.fusion3d import TSDFVolume, frustum_volume, simplify_mesh
+    assert torch.cuda.is_available(), "tools/tsdf_bench.py needs a ROCm device"
+    dev = torch.device("cuda:0")
+    H, W, T, vox, dmin, dmax, dims = 480, 640, 3, 0.03, 0.1, 10.0, (256, 256, 256)
+    reps = min(args.reps, 50)
+    K = R.intrinsics(H, W)
+    poses = R.scene_poses(T, seed=1)
+    depths = torch.from_numpy(np.stack([R.raycast_scene(P, K, H, W) for P in poses]).astype(np.float32)).to(dev)
+    origin = frustum_volume(torch.from_numpy(poses[0]), torch.from_numpy(K), (H, W), dmin, dmax, dims, vox)
+    vol = TSDFVolume(dims, vox, origin, device=dev)
+    vol.integrate(depths, torch.from_numpy(poses), torch.from_numpy(K))
+    m = vol.extract_mesh()
+    u = np.linspace(0.0, 4.0, 321)
+    gx, gy = np.meshgrid(u, u, indexing="xy")
+    grid_xyz = torch.from_numpy(np.stack([gx, gy, 0.2 * np.sin(1.7 * gx) * np.cos(1.3 * gy)], -1).reshape(-1, 3).astype(np.float32)).to(dev)
+    i, j = np.meshgrid(np.arange(320), np.arange(320), indexing="xy")
+    v00 = (j * 321 + i).reshape(-1)
+    grid_faces = torch.from_numpy(np.concatenate([np.stack([v00, v00 + 1, v00 + 322], 1), np.stack([v00, v00 + 322, v00 + 321], 1)]).astype(np.int32)).to(dev)
+    lib = _native.lib()
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    stream = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    lines = ["tsdf_bench --mesh-simplify: median of %d warm calls per figure between device events, %s" % (reps, torch.cuda.get_device_name(0)),
+             "nobody has measured these before: the parent commit has nothing comparable, so the times are recorded, not gated"]
+    for name, xyz, faces, cell in (("the mesh of the %d x %d x %d volume" % dims, m["xyz"].contiguous(), m["faces"].contiguous(), 2 * vox),
+                                   ("the 320 x 320 height field over a 4 m square", grid_xyz, grid_faces, 0.05)):
+        V, F = xyz.shape[0], faces.shape[0]
+        out = simplify_mesh(dict(xyz=xyz, faces=faces), cell)
+        Kc, cluster, cell_key = out["count"], out["cluster"], out["cell_key"]
+        lo = xyz.amin(0).cpu().contiguous()
+        d3 = list(cloud_metrics._dims((xyz.amax(0).cpu().double() - lo.double()).tolist(), float(np.float32(cell))))
+        mean = cloud_metrics.voxel_downsample(xyz, cell)[0]                   # the same grid: simplify_mesh's default origin is the bounding box's minimum
+        corner, triple = torch.empty(3 * F, device=dev, dtype=torch.int32), torch.empty((F, 3), device=dev, dtype=torch.int32)
+        counts = torch.empty(2, device=dev, dtype=torch.int64)
+
+        def kernel_faces():
+            assert lib.estd_mesh_cluster_faces(p(faces), F, V, p(cluster), Kc, p(corner), p(triple), p(counts), stream()) == 0
+        kernel_faces()
+        rec_cluster, order = torch.sort(corner, stable=True)
+        segments = torch.searchsorted(rec_cluster, torch.arange(Kc + 1, device=dev, dtype=torch.int32)).contiguous()
+        o_xyz, o_n, o_p = torch.empty((Kc, 3), device=dev), torch.empty((Kc, 3), device=dev), torch.empty(Kc, device=dev, dtype=torch.bool)
+        lo3, dd = (ctypes.c_float * 3)(*lo.tolist()), (ctypes.c_int * 3)(*d3)
+
+        def kernel_quadrics():
+            assert lib.estd_mesh_cluster_quadrics(p(xyz), V, p(faces), F, p(order), p(segments), p(cell_key), Kc, p(mean), lo3, float(np.float32(cell)), dd,
+                                                  2.0 ** -12, p(o_xyz), p(o_n), p(o_p), stream()) == 0
+        kernel_quadrics()
+        assert torch.equal(o_xyz, out["xyz"]) and torch.equal(o_p, out["placed"]), "the prepared glue is not simplify_mesh's"
+        plane = d3[0] * d3[1]
+        g = torch.stack([cell_key % d3[0], (cell_key % plane) // d3[0], cell_key // plane], 1).double()
+        centre = lo.double().to(dev) + (g + 0.5) * float(np.float32(cell))
+
+        def yard():
+            # the same twelve sums with torch operators: gathers, elementwise float64, one index_add_ per cluster table
+            tri = xyz[faces.long()].double()                                  # [F,3,3]
+            a, b, c = tri[:, 0], tri[:, 1], tri[:, 2]
+            mm = torch.linalg.cross(b - a, c - a)
+            k = corner.long().reshape(F, 3)
+            sums = torch.zeros((Kc + 1, 12), device=dev, dtype=torch.float64)
+            outer = (mm[:, :, None] * mm[:, None, :]).reshape(F, 9)[:, [0, 1, 2, 4, 5, 8]]
+            for jj in range(3):
+                delta = (mm * (a - centre[k[:, jj].clamp(max=Kc - 1)])).sum(1, keepdim=True)
+                sums.index_add_(0, k[:, jj], torch.cat([outer, delta * mm, mm], 1))
+            return sums
+        ref = yard()[:Kc, 9:]
+        nn = torch.nn.functional.normalize(ref, dim=1).float()
+        assert float((nn - o_n).abs().max().item()) < 1e-5, "the yardstick and the kernel disagree on the normals"
+        whole = lambda: simplify_mesh(dict(xyz=xyz, faces=faces), cell)
+        t_f, t_q, t_y, t_all = median_ms(kernel_faces, reps), median_ms(kernel_quadrics, reps), median_ms(yard, reps), median_ms(whole, reps)
+        lines += ["%s, cell %.3f m: %d vertices %d triangles -> %d vertices %d triangles (%s)" % (name, cell, V, F, Kc, out["faces"].shape[0], out["stats"]),
+                  "  mesh_cluster_faces_kernel (+ the 16-byte memset)              %8.4f ms  (%.2f G faces/s)" % (t_f, F / t_f / 1e6),
+                  "  mesh_cluster_quadric_kernel, 8 lanes per cluster, %5.1f records per cluster  %8.4f ms  (%.2f G records/s)"
+                  % (3.0 * F / max(Kc, 1), t_q, 3 * F / t_q / 1e6),
+                  "  yardstick: the twelve sums by torch gathers and index_add_ in float64 (no solve)  %8.4f ms  (kernel / yardstick = 1 / %.1f)" % (t_y, t_y / t_q),
+                  "  simplify_mesh, whole call (finite check, keys, two stable sorts, centroids, both kernels, the face glue, read-backs)  %8.4f ms" % t_all]
+    lines.append("  not built and not measured: a lane per cluster, a wave per cluster for very long segments, gathered 16-byte vertex records")
+    if args.parent_tree:
+        pairs = extract_pairs(os.path.abspath(args.parent_tree), reps)
+        lines.append("the gate: the default extract_mesh() of the 256^3 volume, median of %d calls per process, parent commit / this tree in alternating fresh processes:" % reps)
+        lines += ["  pair %d: parent %8.4f ms   this tree %8.4f ms" % (n, a, b) for n, (a, b) in enumerate(pairs)]
+        pa, pb = float(np.median([a for a, _ in pairs])), float(np.median([b for _, b in pairs]))
+        spread = max(max(a for a, _ in pairs) - min(a for a, _ in pairs), max(b for _, b in pairs) - min(b for _, b in pairs))
+        lines.append("  medians: parent %.4f ms, this tree %.4f ms (difference %+.4f ms; the pairs spread over %.4f ms)" % (pa, pb, pb - pa, spread))
     text = "\n".join(lines)
     print(text)
     if args.out:
