@@ -104,12 +104,12 @@ class PointGrid:
         target = _check_cloud(target, "target", "PointGrid")
         self.device, self.n, self.target = target.device, int(target.shape[0]), target      # the cloud in its original order: ``index`` names its rows
         if self.n == 0:
-            self.cell, self.dims, self.lo = float(np.float32(self.max_dist)), (1, 1, 1), torch.zeros(3)
+            self.cell, self.dims, self.lo, self.hi = float(np.float32(self.max_dist)), (1, 1, 1), torch.zeros(3), torch.zeros(3)
             self.records = torch.empty((0, 4), device=self.device)
             self.cell_start = torch.zeros(2, device=self.device, dtype=torch.int32)
             return
         lo, hi = target.amin(0).cpu(), target.amax(0).cpu()
-        self.lo = lo.contiguous()
+        self.lo, self.hi = lo.contiguous(), hi.contiguous()                                   # the cloud's box, host values
         self.cell, self.dims = grid_plan(lo.tolist(), hi.tolist(), self.n, self.max_dist, cell)
         cells = self.dims[0] * self.dims[1] * self.dims[2]
         keys = ops.cloud_cell_keys(target, self.lo, self.cell, self.dims)
@@ -176,7 +176,7 @@ class TriangleGrid:
         _need(faces.shape[0] <= (2 ** 31 - 1) // 3, "%s: at most %d faces, got %d" % (op, (2 ** 31 - 1) // 3, faces.shape[0]))
         self.device, self.xyz, self.faces = faces.device, xyz, faces
         dev, V, F = self.device, int(xyz.shape[0]), int(faces.shape[0])
-        self.cell, self.dims, self.lo = float(np.float32(self.max_dist)), (1, 1, 1), torch.zeros(3)
+        self.cell, self.dims, self.lo, self.hi = float(np.float32(self.max_dist)), (1, 1, 1), torch.zeros(3), torch.zeros(3)
         self.big_cells = 0 if (cell is not None and math.isinf(cell)) else BIG_CELLS if big_cells is None else big_cells
         self.records = self.big_records = torch.empty((0, 12), device=dev)
         self.cell_start = torch.zeros(2, device=dev, dtype=torch.int32)
@@ -191,7 +191,7 @@ class TriangleGrid:
                 self.faces_valid = F - self.invalid
             return
         lo, hi = tri.amin((0, 1)).cpu(), tri.amax((0, 1)).cpu()
-        self.lo = lo.contiguous()
+        self.lo, self.hi = lo.contiguous(), hi.contiguous()                                   # the box of the faces that can be valid, host values
         if cell is not None and math.isinf(cell):
             cell = None
         if cell is None:

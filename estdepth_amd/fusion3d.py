@@ -272,18 +272,26 @@ class TSDFVolume:
         maps = self.render(cam_pose, cam_intr, image_hw, w_min=w_min)
         return dict(depth=maps["depth"], normal=maps["normal"], pose=cam_pose, K=cam_intr)
 
+    @property
+    def centre(self):
+        """the centre of the volume in world coordinates, float64 [3] (numpy): origin + voxel_size * (W, H, D) / 2"""
+        D, H, W = self.dims
+        return self.origin.double().numpy() + 0.5 * self.voxel_size * np.array([W, H, D], np.float64)
+
     def track(self, depth, cam_pose, cam_intr, conf=None, conf_min=0.0, dist_max=None, max_iter=10, min_count=100, w_min=1.0):
         """Refine the camera-to-world guess ``cam_pose`` [4,4] of the depth map ``depth`` [H,W] (``cam_intr`` [3,3], optional ``conf`` gated
         at ``conf_min``) against the fused surface: the model is rendered ONCE at the guess (``render``), then ``tracking.refine_pose``
         runs up to ``max_iter`` Gauss-Newton steps of projective point-to-plane alignment, keeping matches within ``dist_max`` metres
         (default: the truncation distance).  -> its dict: pose (float64 CPU [4,4]; the guess itself where the update was refused),
-        converged, reason, iterations, trace, correction (metres, radians), plus ``matched_share`` = first count / valid depth pixels."""
+        converged, reason, iterations, trace, correction (metres, radians), plus ``matched_share`` = first count / valid depth pixels.
+        The Gauss-Newton systems are solved about the volume's ``centre`` (the pivot of ``tracking.gauss_newton``): the surface lies
+        inside the volume, so the refusal thresholds judge the scene and not its distance from the world origin."""
         from . import tracking
         if not isinstance(depth, torch.Tensor) or depth.dim() < 2:
             raise RuntimeError("track: depth must be a tensor [H,W] (leading 1s allowed), got %s" % (tuple(getattr(depth, "shape", ())),))
         dist_max = self.trunc if dist_max is None else dist_max
         model = self._model_at(cam_pose, cam_intr, tuple(depth.shape[-2:]), w_min)
-        out = tracking.refine_pose(depth, cam_intr, cam_pose, model, conf, conf_min, dist_max, max_iter, min_count, self.z_near)
+        out = tracking.refine_pose(depth, cam_intr, cam_pose, model, conf, conf_min, dist_max, max_iter, min_count, self.z_near, pivot=self.centre)
         out["matched_share"] = out["trace"][0]["count"] / max(int((torch.isfinite(depth) & (depth > self.z_near)).sum().item()), 1)
         return out
 

@@ -11,6 +11,10 @@ One iteration is one apply (csrc/track/rigid_align.hip: moved = T p, normals rot
 of 29 doubles.  The 6 x 6 solve, the exponential map and the stopping rule are ``tracking.gauss_newton``'s, on the host in float64: the
 update is on the LEFT, T <- Exp(xi) T with xi = (t, omega) in the target's axes.  There is no CPU path.
 
+The kernel's Jacobian rows pivot on the world origin; ``register`` has every system solved about the PIVOT of its target, the centre of
+the target's bounding box (``target_pivot``), so that its verdict does not depend on where the target lies in the world.  ``rigid_system``
+keeps returning the sums, A and b about the world origin.
+
 ``src`` is [N,3] float32 on a ROCm device (``src_normal`` likewise); ``target`` is a ``PointGrid`` (with ``target_normal`` [Nt,3] for the
 plane metric or a cosine gate), a ``TriangleGrid`` (its face normals are estd_mesh_face_area's, float64 rounded to fp32 once), or a dict:
 with ``faces`` a mesh, else a cloud with ``xyz`` and optionally ``normal``; numpy arrays are moved to the device.  T is [4,4] float64.
@@ -48,6 +52,7 @@ class _Target:
               % (op, type(target).__name__))
         _need(target.max_dist >= max_dist, "%s: the target's grid finds partners within %g but dist_max is %g" % (op, target.max_dist, max_dist))
         self.grid, self.device, self.mesh = target, target.device, isinstance(target, TriangleGrid)
+        self.pivot = 0.5 * (target.lo.double().numpy() + target.hi.double().numpy())          # host values of the grid: no read-back
         if self.mesh:
             _need(target_normal is None, "%s: a mesh target takes its normals from its faces; target_normal is for clouds" % op)
             self.normal = ops.mesh_face_area(target.xyz, target.faces)[1] if target.faces.shape[0] else torch.empty((0, 3), device=self.device)
@@ -113,6 +118,13 @@ def _args(metric, cos_min, tgt, src_normal, op):
           "%s: the plane metric and the cosine gate need the target's normals (target_normal, or 'normal' in the dict)" % op)
 
 
+def target_pivot(target, max_dist=0.1, target_normal=None):
+    """The pivot ``register`` solves about -> float64 [3]: the centre of the bounding box of the target's points (a cloud) or of the
+    vertices of its faces that can be valid (a mesh), (lo + hi) / 2 in float64 from the fp32 corners the search structure holds"""
+    tgt = target if isinstance(target, _Target) else _Target(target, _check_max_dist(max_dist, "target_pivot"), target_normal, "target_pivot")
+    return tgt.pivot.copy()
+
+
 def rigid_system(src, T, target, metric="plane", dist_max=0.1, src_normal=None, cos_min=None, two_sided=False, target_normal=None):
     """The Gauss-Newton system of ``src`` [N,3] moved by ``T`` [4,4] against ``target`` -> dict(A float64 [6,6] symmetric, b float64 [6]
     (numpy, host), count, rmse = sqrt(sum r^2 / count), residual [N] and match int64 [N] on the device (0 / -1 where a point has no
@@ -136,7 +148,10 @@ def register(src, target, init=None, metric="plane", dist_max=0.1, max_iter=30, 
     stage's result; the search structure is built once with the largest value and the system kernel's gate removes what lies beyond a
     stage's own.  A refused step -- fewer than ``min_count`` partners ("count"), A not positive definite ("cholesky") or its extreme
     eigenvalues more than 1e6 apart ("condition") -- returns the transform of the last accepted stage, or ``init``, with converged False
-    and the reason: nothing half-done is handed back."""
+    and the reason: nothing half-done is handed back.  Every system is solved about ONE pivot, chosen once per call from the target
+    alone: the centre of its bounding box (``target_pivot``; the box is the search structure's, host values, so the choice costs no
+    read-back and is the same for every run).  The three tests above are those of the system about the pivot, and the step norms of the
+    stopping rule are those of the twist about it: the 1e-5 m is a motion at the target, not at the world origin."""
     op = "register"
     stages = [dist_max] if isinstance(dist_max, (int, float)) else list(dist_max)
     _need(len(stages) >= 1, "%s: dist_max must be a distance or a sequence of them" % op)
@@ -157,7 +172,7 @@ def register(src, target, init=None, metric="plane", dist_max=0.1, max_iter=30, 
             return last
         return f
     for d in stages:
-        out = tracking.gauss_newton(system_at(d), T, max_iter, min_count)
+        out = tracking.gauss_newton(system_at(d), T, max_iter, min_count, pivot=tgt.pivot)
         trace += out["trace"]
         iterations += out["iterations"]
         converged, reason = out["converged"], out["reason"]

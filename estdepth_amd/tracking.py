@@ -10,6 +10,10 @@ All per-pixel arithmetic and the 29 sums are csrc/track/frame_align.hip's (the c
 no CPU path.  The 6 x 6 solve, the exponential map and the stopping rule run on the host in float64; every iteration reads 29 doubles
 back.  Depth maps are [H,W] (leading 1s allowed) float32 device tensors, z-depth with pixel centres on integers; poses are
 camera-to-world [4,4]; K is [3,3] in pixels of the maps.  The update is on the LEFT, P <- Exp(xi) P with xi = (t, omega) in world axes.
+
+The kernel's Jacobian rows (n, p x n) pivot on the world origin; the host re-expresses the 6 x 6 system about a PIVOT near the scene
+before it tests and solves it (``solve_step``, ``gauss_newton``): ``refine_pose`` takes the model camera's centre, ``TSDFVolume.track``
+the centre of its volume.  The sums, A and b that ``align_step`` returns stay those about the world origin.
 """
 import math
 
@@ -116,12 +120,45 @@ def align_step(depth, cam_intr, pose_guess, model, conf=None, conf_min=0.0, dist
     return dict(A=A, b=b, count=count, rmse=math.sqrt(rr / count) if count else 0.0, residual=residual, match=match, sums=host)
 
 
-def solve_step(A, b, count, min_count, cond_max=COND_MAX):
+def pivot_matrix(pivot):
+    """G = [[I, 0], [-[c]x, I]] float64 [6,6] for the pivot c: a Jacobian row (n, q x n) about the world origin is G^-1 times the row
+    (n, (q - c) x n) about c, so the system about c is A_c = G A G^T, b_c = G b"""
+    c = np.asarray(pivot, np.float64).reshape(3)
+    G = np.eye(6)
+    G[3:, :3] = -np.array([[0.0, -c[2], c[1]], [c[2], 0.0, -c[0]], [-c[1], c[0], 0.0]])
+    return G
+
+
+def pivoted(A, b, pivot):
+    """the system (A, b) of twists about the world origin re-expressed about ``pivot`` in float64 -> (A_c symmetric, b_c); unchanged for None"""
+    if pivot is None:
+        return A, b
+    G = pivot_matrix(pivot)
+    Ac = G @ np.asarray(A, np.float64) @ G.T
+    return 0.5 * (Ac + Ac.T), G @ np.asarray(b, np.float64)
+
+
+def pivot_step(xi, pivot):
+    """the rigid motion float64 [4,4] of the twist ``xi`` about ``pivot``: C Exp(xi) C^-1 with C the translation by the pivot (Exp(xi) for None)"""
+    E = exp_se3(xi)
+    if pivot is not None:
+        c = np.asarray(pivot, np.float64).reshape(3)
+        E[:3, 3] += c - E[:3, :3] @ c
+    return E
+
+
+def solve_step(A, b, count, min_count, cond_max=COND_MAX, pivot=None):
     """The Gauss-Newton step of one system -> (xi float64 [6] or None, reason): refused with ``reason`` "count" when fewer than
     ``min_count`` pixels matched, "cholesky" when A is not positive definite (or not finite), "condition" when the extreme eigenvalues
-    of A are more than ``cond_max`` apart; else A xi = b by Cholesky and ``reason`` None."""
+    of A are more than ``cond_max`` apart; else A xi = b by Cholesky and ``reason`` None.  With ``pivot`` (a float64 3-vector c) the
+    system is first re-expressed about c (``pivoted``): the three tests and the solve are those of A_c, b_c, and xi is the twist ABOUT c
+    (``pivot_step`` applies it).  The kernels' Jacobians pivot on the world origin, where |q| couples rotation and translation: the
+    condition of A grows with the square of the scene's distance from the origin, that of A_c does not."""
     if count < min_count:
         return None, "count"
+    if not (np.isfinite(A).all() and np.isfinite(b).all()):
+        return None, "cholesky"
+    A, b = pivoted(A, b, pivot)
     if not (np.isfinite(A).all() and np.isfinite(b).all()):
         return None, "cholesky"
     try:
@@ -134,23 +171,29 @@ def solve_step(A, b, count, min_count, cond_max=COND_MAX):
     return np.linalg.solve(Lc.T, np.linalg.solve(Lc, b)), None
 
 
-def gauss_newton(system, pose_guess, max_iter=10, min_count=100, cond_max=COND_MAX):
+def gauss_newton(system, pose_guess, max_iter=10, min_count=100, cond_max=COND_MAX, pivot=None):
     """The host side of ``refine_pose`` for any ``system(pose float64 [4,4]) -> dict(A, b, count, rmse)``: up to ``max_iter`` steps
     P <- Exp(xi) P.  -> dict(pose float64 [4,4], converged, reason, iterations, trace = [dict(rmse, count) per evaluation], correction =
     (translation in metres, angle in radians) of pose relative to the guess).  A refused step (``solve_step``) returns the guess
     unchanged with converged False and the reason; ``reason`` is "converged" once a step is below 1e-5 m and 1e-5 rad, "max_iter" when
-    the iterations run out first (the pose is the refined one, converged False).  ``max_iter=0`` evaluates the system once."""
+    the iterations run out first (the pose is the refined one, converged False).  ``max_iter=0`` evaluates the system once.
+    ``pivot`` (float64 [3], fixed for the whole iteration; None: the world origin): every system is solved about it and the step is
+    the twist about it, P <- C Exp(xi) C^-1 P; the step norms of the stopping rule are those of that twist, so the 1e-5 m is the motion
+    of the pivot, not of the world origin."""
     guess = np.asarray(pose_guess, np.float64).reshape(4, 4).copy()
+    if pivot is not None:
+        pivot = np.asarray(pivot, np.float64).reshape(3).copy()
+        _need(bool(np.isfinite(pivot).all()), "gauss_newton: the pivot holds a value that is not finite")
     P, trace, reason, done = guess.copy(), [], "max_iter", 0
     for it in range(max(int(max_iter), 1)):
         s = system(P)
         trace.append(dict(rmse=float(s["rmse"]), count=int(s["count"])))
         if int(max_iter) < 1:
             break
-        xi, why = solve_step(s["A"], s["b"], s["count"], min_count, cond_max)
+        xi, why = solve_step(s["A"], s["b"], s["count"], min_count, cond_max, pivot)
         if xi is None:
             return dict(pose=guess, converged=False, reason=why, iterations=it, trace=trace, correction=(0.0, 0.0))
-        P = exp_se3(xi) @ P
+        P = pivot_step(xi, pivot) @ P
         done = it + 1
         if np.linalg.norm(xi[:3]) < STEP_T and np.linalg.norm(xi[3:]) < STEP_R:
             reason = "converged"
@@ -161,13 +204,18 @@ def gauss_newton(system, pose_guess, max_iter=10, min_count=100, cond_max=COND_M
                 correction=(float(np.linalg.norm(D[:3, 3])), angle))
 
 
-def refine_pose(depth, cam_intr, pose_guess, model, conf=None, conf_min=0.0, dist_max=0.1, max_iter=10, min_count=100, z_near=1e-3):
+def refine_pose(depth, cam_intr, pose_guess, model, conf=None, conf_min=0.0, dist_max=0.1, max_iter=10, min_count=100, z_near=1e-3, pivot=None):
     """Gauss-Newton refinement of ``pose_guess`` against the FIXED ``model`` maps (arguments as ``align_step``): up to ``max_iter`` steps,
     each one launch and one 29-double read-back, solved on the host in float64 (``gauss_newton``).  The update is refused -- converged
     False, the reason, the guess unchanged -- when fewer than ``min_count`` pixels match, when the Cholesky factorisation of A fails, or
-    when A's extreme eigenvalues are more than COND_MAX = 1e6 apart.  ``pose`` comes back as a float64 CPU tensor [4,4]."""
+    when A's extreme eigenvalues are more than COND_MAX = 1e6 apart.  The system is solved about ``pivot`` (float64 [3], world
+    coordinates; default: the centre of the MODEL's camera, ``model["pose"][:3, 3]``, a host value that is there before the first launch
+    and lies within the depth range of the surface it sees), so the verdict does not depend on where the scene lies in the world.
+    ``pose`` comes back as a float64 CPU tensor [4,4]."""
     guess = _host(pose_guess, (4, 4), "pose_guess", "refine_pose")
     _need(int(max_iter) >= 0 and int(min_count) >= 1, "refine_pose: max_iter must not be negative and min_count at least 1, got %r and %r" % (max_iter, min_count))
-    out = gauss_newton(lambda P: align_step(depth, cam_intr, P, model, conf, conf_min, dist_max, z_near), guess, max_iter, min_count)
+    _need(isinstance(model, dict) and model.get("pose") is not None, "refine_pose: model must be a dict with depth, normal, pose and K")
+    pivot = _host(model["pose"], (4, 4), "the model's pose", "refine_pose")[:3, 3] if pivot is None else _host(pivot, (3,), "pivot", "refine_pose")
+    out = gauss_newton(lambda P: align_step(depth, cam_intr, P, model, conf, conf_min, dist_max, z_near), guess, max_iter, min_count, pivot=pivot)
     out["pose"] = torch.from_numpy(out["pose"])
     return out

@@ -254,9 +254,20 @@ def route_case(n_target, n_query):
     return dict(target=target, query=query, max_dist=0.2)
 
 
-def build_case(name):
-    """dict(target [N,3] f32, query [M,3] f32, max_dist, cell (None or the case's explicit edge))"""
+PLACED_CASE = "rand_64x65"    # the case that is also built at placement.FAMILY_PLACES: the smallest with more than one wave of either cloud
+
+
+def build_case(name, place=None):
+    """dict(target [N,3] f32, query [M,3] f32, max_dist, cell (None or the case's explicit edge)).  ``place`` (placement.py; the rand_
+    cases): the same draws kept in float64, moved to the placement and rounded to fp32 once -- unlike "translated", which adds 100 to
+    fp32 data and so keeps the unplaced cloud's low bits"""
+    import placement as PL
     rng = np.random.RandomState(sum(name.encode()))
+    if PL.key(place) is not None:
+        n, m = (int(v) for v in name[5:].split("x"))
+        t, q = rng.uniform(0.0, 2.0, size=(n, 3)), rng.uniform(0.0, 2.0, size=(m, 3))
+        return dict(name="%s@%s" % (name, PL.label(place)), max_dist=0.15, cell=None, target=PL.points(t, place).astype(np.float32),
+                    query=PL.points(q, place).astype(np.float32))
     box = lambda n, lo=0.0, hi=2.0: rng.uniform(lo, hi, size=(n, 3)).astype(np.float32)
     c = dict(name=name, max_dist=0.15, cell=None)
     if name.startswith("rand_"):

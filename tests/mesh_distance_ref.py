@@ -345,9 +345,20 @@ def walls(rng, small=300):
     return np.concatenate([wall, xyz]), np.concatenate([np.asarray([(0, 1, 2), (0, 2, 3)], np.int32), faces + 4])
 
 
-def build_case(name):
-    """-> dict(q float32 [M,3], xyz float32 [V,3], faces int32 [F,3], max_dist); a function of the name alone"""
+PLACED_CASE = "rand_m65_f65"  # the case that is also built at placement.FAMILY_PLACES: the smallest with more than a wave of queries and of faces
+
+
+def build_case(name, place=None):
+    """-> dict(q float32 [M,3], xyz float32 [V,3], faces int32 [F,3], max_dist); a function of the name alone.  ``place`` (placement.py;
+    the rand_ cases): the draws of the unplaced case kept in float64, moved to the placement and rounded to fp32 once"""
+    import placement as PL
     rng = np.random.default_rng(abs(hash_name(name)))
+    if PL.key(place) is not None:
+        m, f = (int(x[1:]) for x in name.split("_")[1:])
+        xyz = (rng.uniform(0.0, 1.0, (f, 1, 3)) + rng.uniform(-0.08, 0.08, (f, 3, 3))).reshape(-1, 3)              # soup's draws
+        q = rng.uniform(-0.2, 1.2, (m, 3))
+        return dict(q=PL.points(q, place).astype(np.float32), xyz=PL.points(xyz, place).astype(np.float32),
+                    faces=np.arange(3 * f, dtype=np.int32).reshape(f, 3), max_dist=0.5)
     if name.startswith("rand_"):
         m, f = (int(x[1:]) for x in name.split("_")[1:])
         xyz, faces = soup(f, rng)

@@ -359,6 +359,18 @@ def build_case(name):
     return CASES[name]()
 
 
+def placed_case(place):
+    """"interpenetrating" -- three triangles that cross, so the nearest face changes within a pixel row -- built at a placement
+    (placement.py): the float64 vertices and the camera moved there, the vertices rounded to fp32 once, the matrix formed in float64 from
+    the placed pose.  The projection of the contract is float64 from the fp32 vertices, so the reference stays exact; what the placement
+    adds is the cancellation of M_j3 against coordinates of hundreds of metres"""
+    import placement as PL
+    H, W = 33, 41
+    xyz = np.asarray([(-1, -1, 1.5), (1, -1, 2.5), (0, 1, 2.0), (-1, -1, 2.5), (1, -1, 1.5), (0, 1, 2.0), (-1, 0.2, 1.2), (1, 0.2, 1.2), (0, -0.3, 3.0)], np.float64)
+    mat = raster_matrix(PL.pose(look_at((0, 0, 0), (0, 0, 1)), place), intrinsics(H, W))
+    return PL.points(xyz, place).astype(np.float32), _i32([(0, 1, 2), (3, 4, 5), (6, 7, 8)]), mat, H, W, 1e-3
+
+
 def expected(name):
     """the reference's maps of a case, computed once and shared (do not modify)"""
     if name not in _WANT:

@@ -370,6 +370,20 @@ def build_case(name):
     return out
 
 
+PLACED_CASE = "attrs-3"      # the case that is also built at placement.FAMILY_PLACES: the 65-face mesh with attributes, 300 samples
+
+
+def placed_case(place):
+    """PLACED_CASE built at a placement (placement.py): random_mesh's draws kept in float64, moved there and rounded to fp32 once (as
+    "far" does with its 1000 m along every axis); faces, attributes, n and seed are the unplaced case's"""
+    import placement as PL
+    xyz0, faces, attrs, n, seed = build_case(PLACED_CASE)
+    V = xyz0.shape[0]
+    xyz = np.random.default_rng(1).uniform(-1.0, 1.0, (V, 3))                                   # random_mesh(65, 1)'s first draw
+    assert np.array_equal(xyz.astype(np.float32), xyz0)
+    return PL.points(xyz, place).astype(np.float32), faces, attrs, n, seed
+
+
 CASES = ("one", "one-257", "f65-n64", "f65-n1000", "f65-n1000-seed", "areas-1e6", "zero-area", "out-of-range", "no-faces", "no-samples",
          "attrs-1", "attrs-3", "attrs-6", "far", "spheres")
 

@@ -261,8 +261,9 @@ def noisy_sphere(sigma=0.002, seed=1):
     return (xyz + np.random.RandomState(seed).normal(0.0, sigma, xyz.shape)).astype(np.float32), faces
 
 
-def patch(n_faces, seed=3):
-    """the first ``n_faces`` triangles of a bumpy height field with 3 cm spacing (about three vertices per 10 cm cell and axis)"""
+def patch(n_faces, seed=3, place=None):
+    """the first ``n_faces`` triangles of a bumpy height field with 3 cm spacing (about three vertices per 10 cm cell and axis); ``place``
+    (placement.py): the float64 height field moved there before its one rounding to fp32"""
     side = 2
     while 2 * (side - 1) ** 2 < n_faces:
         side += 1
@@ -270,6 +271,9 @@ def patch(n_faces, seed=3):
     u, v = np.meshgrid(np.arange(side) * 0.03, np.arange(side) * 0.03, indexing="xy")
     z = 0.08 * np.sin(7.0 * u) * np.cos(5.0 * v) + rng.normal(0, 0.002, u.shape)
     xyz = np.stack([u + 0.211, v + 0.137, z + 0.5], -1).reshape(-1, 3)
+    if place is not None:
+        import placement as PL
+        xyz = PL.points(xyz, place)
     faces = []
     for r in range(side - 1):
         for c in range(side - 1):
@@ -341,6 +345,9 @@ def build_case(name):
     else:
         raise KeyError(name)
     return np.ascontiguousarray(xyz, np.float32), np.ascontiguousarray(faces, np.int32), cell, origin
+
+
+PLACED_FACES = 257           # the patch that is also built at the placements of placement.py: more than one block of faces
 
 
 CASES = ["patch-0", "patch-1", "patch-63", "patch-64", "patch-65", "patch-257", "one-cluster", "clusters-65", "fan-1", "fan-64", "fan-65", "fan-300",

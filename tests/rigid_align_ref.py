@@ -46,6 +46,7 @@ import functools
 
 import numpy as np
 
+import placement as PL
 import track_ref as TR
 from mesh_distance_ref import icosphere
 
@@ -67,9 +68,10 @@ TWIST = TR.TWIST             # about 1 cm and 0.5 degrees
 
 # ------------------------------------------------------------------------------------------------------------ the scene
 @functools.lru_cache(maxsize=None)
-def scene_mesh(level=1):
+def scene_mesh(level=1, place=None):
     """-> (xyz float32 [V,3], faces int32 [F,3]): the plane z = 2.6 over [-1.6, 1.6] x [-1.2, 1.2] as two triangles whose normals point
-    to -z (towards the cameras), and the two spheres as icospheres of ``level``, outward"""
+    to -z (towards the cameras), and the two spheres as icospheres of ``level``, outward.  ``place`` (placement.py): the float64 vertices
+    moved there before the one rounding to fp32"""
     z = TR.PLANE_Z
     xyz = [np.array([(-1.6, -1.2, z), (1.6, -1.2, z), (1.6, 1.2, z), (-1.6, 1.2, z)], np.float64)]
     faces = [np.array([(0, 2, 1), (0, 3, 2)], np.int64)]
@@ -79,7 +81,10 @@ def scene_mesh(level=1):
         xyz.append(v.astype(np.float64) + np.asarray(centre))
         faces.append(f.astype(np.int64) + n)
         n += v.shape[0]
-    return np.concatenate(xyz).astype(np.float32), np.concatenate(faces).astype(np.int32)
+    xyz = np.concatenate(xyz)
+    if PL.key(place) is not None:
+        xyz = PL.points(xyz, place)
+    return xyz.astype(np.float32), np.concatenate(faces).astype(np.int32)
 
 
 def subdivided(xyz, faces):
@@ -108,8 +113,9 @@ def face_normals(xyz, faces):
     return n / ln[:, None], 0.5 * ln
 
 
-def sample_scene(n, seed):
-    """``n`` points spread by area over the scene's mesh -> (xyz float32 [n,3], normal float32 [n,3], face int64 [n])"""
+def sample_scene(n, seed, place=None):
+    """``n`` points spread by area over the scene's mesh -> (xyz float32 [n,3], normal float32 [n,3], face int64 [n]); ``place``: the
+    float64 samples and normals of the unplaced scene moved there before the one rounding to fp32"""
     xyz, faces = scene_mesh()
     nrm, area = face_normals(xyz, faces)
     rng = np.random.RandomState(seed)
@@ -119,6 +125,8 @@ def sample_scene(n, seed):
     u, v = np.where(fold, 1 - u, u), np.where(fold, 1 - v, v)
     t = xyz.astype(np.float64)[faces.astype(np.int64)[f]]
     p = t[:, 0] + u[:, None] * (t[:, 1] - t[:, 0]) + v[:, None] * (t[:, 2] - t[:, 0])
+    if PL.key(place) is not None:
+        return PL.points(p, place).astype(np.float32), PL.vectors(nrm[f], place).astype(np.float32), f.astype(np.int64)
     return p.astype(np.float32), nrm[f].astype(np.float32), f.astype(np.int64)
 
 
@@ -334,12 +342,42 @@ def unpack(sums):
     return TR.unpack(sums)
 
 
-def solve_step(A, b, count, min_count, cond_max=COND_MAX):
-    """tracking.solve_step in this module's words -> (xi or None, reason)"""
+def target_pivot(target):
+    """registration.target_pivot in this module's words: the centre of the bounding box of the target's fp32 points (a cloud) or of the
+    vertices its faces name (a mesh), (lo + hi) / 2 in float64 -> [3]"""
+    xyz = np.asarray(target["xyz"], np.float32)
+    if "faces" in target:
+        xyz = xyz[np.unique(np.asarray(target["faces"], np.int64))]
+    return 0.5 * (xyz.min(0).astype(np.float64) + xyz.max(0).astype(np.float64))
+
+
+def pivoted(A, b, pivot):
+    """(A, b) of twists about the world origin -> about ``pivot`` c: G = [[I, 0], [-[c]x, I]], A_c = G A G^T, b_c = G b (None: unchanged)"""
+    if pivot is None:
+        return A, b
+    G = np.eye(6)
+    G[3:, :3] = -TR.hat(np.asarray(pivot, np.float64).reshape(3))
+    Ac = G @ A @ G.T
+    return 0.5 * (Ac + Ac.T), G @ b
+
+
+def pivot_step(xi, pivot):
+    """C Exp(xi) C^-1 with C the translation by the pivot: the twist applied about the pivot (None: about the world origin)"""
+    E = exp_se3(xi)
+    if pivot is not None:
+        c = np.asarray(pivot, np.float64).reshape(3)
+        E[:3, 3] += c - E[:3, :3] @ c
+    return E
+
+
+def solve_step(A, b, count, min_count, cond_max=COND_MAX, pivot=None):
+    """tracking.solve_step in this module's words -> (xi or None, reason); with ``pivot`` the tests and the solve are those of the
+    system about it and xi is the twist about it"""
     if count < min_count:
         return None, "count"
     if not (np.isfinite(A).all() and np.isfinite(b).all()):
         return None, "cholesky"
+    A, b = pivoted(A, b, pivot)
     try:
         Lc = np.linalg.cholesky(A)
     except np.linalg.LinAlgError:
@@ -421,19 +459,23 @@ def system64(src, T, target, metric, dist_max, src_normal=None, cos_min=None, tw
     return dict(A=A, b=b, count=count, rmse=float(np.sqrt(rr / count)) if count else 0.0)
 
 
-def refine(src, target, init=None, metric="plane", dist_max=DIST_MAX, max_iter=30, min_count=100, **kw):
-    """the float64 reference registration: registration.register's stages, solve and stopping rule -> dict(T, converged, reason, iterations)"""
+def refine(src, target, init=None, metric="plane", dist_max=DIST_MAX, max_iter=30, min_count=100, pivot=None, **kw):
+    """the float64 reference registration: registration.register's stages, solve and stopping rule -> dict(T, converged, reason, iterations,
+    cond = the condition number of the first system that was tested).  ``pivot``: every system is solved about it and the step is the
+    twist about it, as ``register`` does about ``target_pivot(target)``; None: about the world origin, the method before the pivot"""
     stages = [float(d) for d in (dist_max if isinstance(dist_max, (tuple, list)) else (dist_max,))]
     T = np.eye(4) if init is None else np.asarray(init, np.float64).copy()
-    out = dict(T=T, converged=False, reason="max_iter", iterations=0)
+    out = dict(T=T, converged=False, reason="max_iter", iterations=0, cond=None)
     for d in stages:
         P, reason = T.copy(), "max_iter"
         for _ in range(max_iter):
             s = system64(src, P, target, metric, d, **kw)
-            xi, why = solve_step(s["A"], s["b"], s["count"], min_count)
+            if out["cond"] is None and s["count"] >= min_count:
+                out["cond"] = float(np.linalg.cond(pivoted(s["A"], s["b"], pivot)[0]))
+            xi, why = solve_step(s["A"], s["b"], s["count"], min_count, pivot=pivot)
             if xi is None:
-                return dict(T=T, converged=False, reason=why, iterations=out["iterations"])
-            P = exp_se3(xi) @ P
+                return dict(T=T, converged=False, reason=why, iterations=out["iterations"], cond=out["cond"])
+            P = pivot_step(xi, pivot) @ P
             out["iterations"] += 1
             if np.linalg.norm(xi[:3]) < STEP_T and np.linalg.norm(xi[3:]) < STEP_R:
                 reason = "converged"
@@ -447,19 +489,20 @@ def refine(src, target, init=None, metric="plane", dist_max=DIST_MAX, max_iter=3
 ROUTE_SIZES = (1, 255, 256, 257, 64 * 256 + 1, 16641)
 
 
-def make_case(N, metric="plane", normals=True, by_index=True, two_sided=False, seed=0, name=""):
+def make_case(N, metric="plane", normals=True, by_index=True, two_sided=False, seed=0, name="", place=None):
     """``N`` source points near ``N + 7`` samples of the scene: the partner of point i is index[i] (random; from N = 16 on one index is -1
     and one equals the number of targets).  The moved point lies about 6 mm off its partner, every tenth 0.2 m off (beyond DIST_MAX =
     0.05: the gate is far from both groups); the source normals are the partners' within a few degrees, every eighth negated (kept only
     by the two-sided gate) and every eleventh turned by about 70 degrees (kept by neither).  The system's inputs ``moved`` /
-    ``moved_normal`` are the float64 T p, R n rounded to fp32."""
+    ``moved_normal`` are the float64 T p, R n rounded to fp32.  ``place``: the same case with the scene built at that placement and the
+    transform conjugated to it (the same motion of the scene)."""
     rng = np.random.RandomState(1000 + seed)
     Nt = N + 7
-    q, nq, _ = sample_scene(Nt, seed)
+    q, nq, _ = sample_scene(Nt, seed, place)
     index = rng.randint(0, Nt, size=N).astype(np.int64)
     off = rng.randn(N, 3) * 0.0035
     off[5::10] += 0.2 * np.sign(rng.randn(N, 3)[5::10]) / np.sqrt(3.0)
-    T = exp_se3(TWIST)
+    T = exp_se3(TWIST) if PL.key(place) is None else PL.conjugated(exp_se3(TWIST), place)
     T12 = t12(T)
     T64 = np.eye(4)
     T64[:3, :4] = T12.astype(np.float64)
@@ -518,7 +561,11 @@ CASES.update({
 
 
 @functools.lru_cache(maxsize=None)
-def build_case(name):
+def build_case(name, place=None):
+    """the case ``name``; ``place``: the same case built at that placement (the cases of CASES only)"""
+    if PL.key(place) is not None:
+        n, metric, normals, by_index, two_sided = CASES[name]
+        return make_case(n, metric, normals, by_index, two_sided, seed=len(name) + n % 97, name="%s@%s" % (name, PL.label(place)), place=PL.key(place))
     if name == "tie":
         return tie_case()
     if name == "none":                                      # every partner beyond the gate
@@ -530,15 +577,26 @@ def build_case(name):
 
 
 @functools.lru_cache(maxsize=None)
-def reference(name):
+def reference(name, place=None):
     """the float64 evaluation of a case, computed once and shared"""
-    return evaluate(build_case(name))
+    return evaluate(build_case(name, place))
+
+
+# the cases of the feature suite that are also built at placement.FAMILY_PLACES: the smallest size with more than one workgroup, both
+# metrics and both ways of reading the target
+PLACED_CASES = ("plane-n257", "point-n257", "plane-closest-n257")
 
 
 @functools.lru_cache(maxsize=None)
-def registration_fixture(scale=1.0, n=4000, seed=3):
+def registration_fixture(scale=1.0, n=4000, seed=3, place=None):
     """``n`` samples of the scene's mesh moved by the INVERSE of Exp(scale * TWIST): registering them to the unmoved scene must give
-    T_true = Exp(scale * TWIST) -> dict(src, src_normal, T_true, mesh = dict(xyz, faces), cloud = dict(xyz, normal): other samples)"""
+    T_true = Exp(scale * TWIST) -> dict(src, src_normal, T_true, mesh = dict(xyz, faces), cloud = dict(xyz, normal): other samples).
+    ``place`` (placement.py): the same scene and the same source built at that placement -- the float64 samples moved by the inverse
+    twist and then to the placement, rounded to fp32 once -- with T_true conjugated, W Exp(scale * TWIST) W^-1, and ``centre``, the
+    point the error of a transform is measured at"""
+    place = PL.key(place)
+    if place is not None:
+        return _placed_registration_fixture(scale, n, seed, place)
     xyz, faces = scene_mesh()
     p, nrm, _ = sample_scene(n, seed)
     T = exp_se3(scale * TWIST)
@@ -546,4 +604,36 @@ def registration_fixture(scale=1.0, n=4000, seed=3):
     src = (p.astype(np.float64) @ Ti[:3, :3].T + Ti[:3, 3]).astype(np.float32)
     sn = (nrm.astype(np.float64) @ Ti[:3, :3].T).astype(np.float32)
     cq, cn, _ = sample_scene(4 * n, seed + 1)
-    return dict(src=src, src_normal=sn, T_true=T, mesh=dict(xyz=xyz, faces=faces), cloud=dict(xyz=cq, normal=cn))
+    return dict(src=src, src_normal=sn, T_true=T, mesh=dict(xyz=xyz, faces=faces), cloud=dict(xyz=cq, normal=cn), centre=np.array(SCENE_CENTRE))
+
+
+SCENE_CENTRE = (0.0, 0.0, 2.2)               # between the spheres and the plane: where a transform's error is measured in metres
+
+
+def _placed_registration_fixture(scale, n, seed, place):
+    xyz, faces = scene_mesh(place=place)
+    base = scene_mesh()[0].astype(np.float64)[faces.astype(np.int64)]
+    nrm, area = face_normals(scene_mesh()[0], faces)
+    rng = np.random.RandomState(seed)                                                      # sample_scene's draws, kept in float64
+    f = rng.choice(faces.shape[0], size=n, p=area / area.sum())
+    u, v = rng.uniform(size=n), rng.uniform(size=n)
+    fold = u + v > 1
+    u, v = np.where(fold, 1 - u, u), np.where(fold, 1 - v, v)
+    t = base[f]
+    p = t[:, 0] + u[:, None] * (t[:, 1] - t[:, 0]) + v[:, None] * (t[:, 2] - t[:, 0])
+    T = exp_se3(scale * TWIST)
+    Ti = np.linalg.inv(T)
+    src = PL.points(p @ Ti[:3, :3].T + Ti[:3, 3], place).astype(np.float32)
+    sn = PL.vectors(nrm[f] @ Ti[:3, :3].T, place).astype(np.float32)
+    cq, cn, _ = sample_scene(4 * n, seed + 1, place)
+    return dict(src=src, src_normal=sn, T_true=PL.conjugated(T, place), mesh=dict(xyz=xyz, faces=faces), cloud=dict(xyz=cq, normal=cn),
+                centre=PL.points(np.array(SCENE_CENTRE), place))
+
+
+def transform_error(T, T_true, centre):
+    """(metres at ``centre``, radians): how far T moves the point ``centre`` from where T_true moves it, and the angle between the rotations.
+    pose_error measures the translation at the world origin, where a rotation error of a placed scene is multiplied by its distance"""
+    T, T_true, c = np.asarray(T, np.float64), np.asarray(T_true, np.float64), np.asarray(centre, np.float64)
+    d = (T[:3, :3] @ c + T[:3, 3]) - (T_true[:3, :3] @ c + T_true[:3, 3])
+    Rd = T[:3, :3] @ T_true[:3, :3].T
+    return float(np.linalg.norm(d)), float(np.arccos(np.clip((np.trace(Rd) - 1.0) / 2.0, -1.0, 1.0)))

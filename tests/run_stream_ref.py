@@ -175,8 +175,8 @@ def filter_standin(depths, poses, K, radius=2, min_views=2, dtype=np.float32):
 def track_standin(depths, poses, K, origin, track=True, dtype=np.float32, t_min=1.2):
     """The tool's --track loop with the references in ``dtype``: from the second map on, the model is ray-cast from the volume fused so far
     at the map's own (written) pose (tsdf_raycast_ref.raycast, sampled from ``t_min`` -- in front of the scene -- to the volume's farthest
-    corner), the pose refined against it (track_ref.refine, 10 iterations, dist_max = the truncation distance), and the map fused at the
-    refined pose (tsdf_ref.integrate).  -> (the poses fused at [T,4,4] f64, extract's dict of the final volume)"""
+    corner), the pose refined against it (track_ref.refine, 10 iterations about the volume's centre, dist_max = the truncation distance),
+    and the map fused at the refined pose (tsdf_ref.integrate).  -> (the poses fused at [T,4,4] f64, extract's dict of the final volume)"""
     import math
     import tsdf_raycast_ref as RC
     h, w = depths.shape[-2:]
@@ -190,7 +190,7 @@ def track_standin(depths, poses, K, origin, track=True, dtype=np.float32, t_min=
             n_steps = int(math.ceil(max(far - t_min, 0.0) / VOXEL)) + 1
             m = RC.raycast(D, W, RC.ray_matrix(P, K, origin, VOXEL), h, w, t_min, VOXEL, n_steps, 1.0, dtype=dtype)
             model = dict(depth=m["depth"].astype(np.float32), normal=m["normal"].astype(np.float32), pose=P, K=K)
-            P, _ = T.refine(depths[k], K, P, model, iters=10, dist_max=TRUNC, z_near=1e-3, dtype=dtype)
+            P, _ = T.refine(depths[k], K, P, model, iters=10, pivot=np.asarray(origin, np.float64) + 0.5 * ext, dist_max=TRUNC, z_near=1e-3, dtype=dtype)
         used.append(P)
         ref = integrate_targets(depths[k:k + 1], P[None], K, origin, dtype, D, W)
         D, W = ref["D"].astype(np.float32), ref["Wt"].astype(np.float32)

@@ -40,6 +40,20 @@ def _nearest(c, cell):
 
 
 # ------------------------------------------------------------------------------------------------ against the reference
+@pytest.mark.parametrize("where", ["d64", "d64-rotated", "d512"])
+def test_nearest_away_from_the_origin(where):
+    """64 targets and 65 queries built 64 m and 512 m out and in the turned world (tests/placement.py; the case "translated" adds its 100 m
+    to fp32 data): the bound stays relative to the DISTANCE, because the difference of two nearby fp32 coordinates is exact wherever they
+    lie; the grid's corner is the target's own minimum and moves with it"""
+    import placement as PL
+    c = C.build_case(C.PLACED_CASE, PL.PLACES[where])
+    dmin = C.nearest64(c["query"], c["target"])[0]
+    dist, index = _nearest(c, None)
+    fig = C.compare(dist, index, c["query"], c["target"], c["max_dist"], dmin, c["name"])
+    print("PLACEMENT cloud_nearest %s: %d of %d found; of the bound: dist %.3f index %.3f" % (c["name"], fig["found"], fig["n"], fig["e_dist"], fig["e_index"]))
+    assert fig["found"] >= 1 and float(np.abs(c["target"]).min()) > PL.PLACES[where][0] / 4
+
+
 @pytest.mark.parametrize("binding", BINDINGS)
 @pytest.mark.parametrize("name", C.CASES)
 def test_nearest_against_reference(name, binding, monkeypatch):

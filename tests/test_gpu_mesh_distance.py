@@ -48,6 +48,19 @@ def same(a, b, keys=("dist", "face", "bary", "closest")):
     return all(a[k].shape == b[k].shape and np.array_equal(bits(a[k]), bits(b[k])) for k in keys) and a["invalid"] == b["invalid"]
 
 
+@pytest.mark.parametrize("where", ["d64", "d512"])
+def test_against_the_reference_away_from_the_origin(where):
+    """the 65-query, 65-face soup built 64 m and 512 m out (tests/placement.py) through the unchanged comparison: its allowance follows the
+    magnitudes of the differences the kernel forms, so a kernel that worked in absolute coordinates where it should not would miss it"""
+    import placement as PL
+    case = R.build_case(R.PLACED_CASE, PL.FAMILY_PLACES[where])
+    got, grid = run(case)
+    fig = R.compare(got, case, "%s@%s" % (R.PLACED_CASE, where))
+    print("PLACEMENT mesh_distance %s@%s: %d queries, %d found; of the allowance: dist %.3f face %.3f" % (R.PLACED_CASE, where, fig["queries"], fig["found"],
+                                                                                                     fig["dist"], fig["face"]))
+    assert fig["found"] > 30 and grid.faces_valid == 65 and float(np.abs(case["xyz"]).min()) > PL.FAMILY_PLACES[where][0] / 4
+
+
 @pytest.mark.parametrize("binding", ["torch", "ctypes"])
 @pytest.mark.parametrize("name", R.CASES)
 def test_against_the_reference(name, binding):

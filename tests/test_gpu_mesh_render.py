@@ -119,6 +119,22 @@ def _render_volume(vol, pose, K, what, analytic, voxel, chain, closed):
     return mesh, got
 
 
+@pytest.mark.parametrize("where", ["d64", "d64-rotated", "d512"])
+def test_the_rasteriser_away_from_the_origin(where):
+    """three crossing triangles and their camera 64 m and 512 m out, and 64 m out in a turned world (tests/placement.py), against the
+    float64 reference TO THE BIT, as everywhere in this family: the kernel projects the fp32 vertices in float64 in the contract's order,
+    so the large M_j3 cancels against the large coordinates exactly as it does in numpy"""
+    import placement as PL
+    from estdepth_amd import ops
+    from test_gpu_mesh_raster_routes import as_got
+    case = R.placed_case(PL.PLACES[where])
+    xyz, faces, mat, H, W, zn = case
+    got = as_got(ops.mesh_raster(_dev(xyz), _dev(faces), torch.from_numpy(np.ascontiguousarray(mat)), H, W, zn))
+    fig = R.compare(got, R.raster(*case), "interpenetrating@%s" % where)
+    print("PLACEMENT mesh_raster interpenetrating@%s: %d pixels covered by %d faces, equal to the reference's bits" % (where, fig["covered"], fig["seen"]))
+    assert fig["seen"] == 3 and fig["covered"] > 300
+
+
 def test_render_of_the_fused_sphere():
     from estdepth_amd.fusion3d import TSDFVolume
     D, W, origin, pose, K, analytic, voxel = sphere_case()

@@ -45,6 +45,24 @@ def test_repeated_calls_and_both_bindings_give_the_same_bits(name):
             assert _same(v, again[k]) if isinstance(v, torch.Tensor) else v == again[k], "%s: %s differs (%s)" % (name, k, binding)
 
 
+@pytest.mark.parametrize("where", ["d64", "d64-rotated", "d512"])
+def test_the_kernels_away_from_the_origin(where):
+    """the 65-face mesh with three attribute channels built 64 m and 512 m out and in the turned world (tests/placement.py) through the
+    unchanged comparison: areas and face normals from edge vectors (the differences of nearby coordinates are exact), positions within
+    the bound that follows their magnitude, at most 3 % of the normals left out"""
+    import placement as PL
+    from estdepth_amd import ops
+    from test_gpu_mesh_sample_routes import as_got
+    host = S.placed_case(PL.PLACES[where])
+    xyz, faces, attrs, n, seed = host
+    out = ops.mesh_sample(_dev(xyz), _dev(faces), _dev(attrs), n, seed)
+    fa = ops.mesh_face_area(_dev(xyz), _dev(faces))
+    fig = S.compare(as_got(out, fa[1]), *host, "%s@%s" % (S.PLACED_CASE, where))
+    print("PLACEMENT mesh_sample %s@%s: of the bounds: area %.3f face normal %.3f position %.3f attributes %.3f; %d of %d normals left out"
+          % (S.PLACED_CASE, where, fig["area"], fig["face_normal"], fig["xyz"], fig["attrs"], fig["left_out"], fig["faces"]))
+    assert fig["samples"] == n and float(np.abs(xyz).min()) > PL.PLACES[where][0] / 4
+
+
 def test_sample_mesh_of_a_host_mesh_with_normals_and_colour():
     """numpy arrays as read_ply returns them: uint8 rgb becomes float32 color, normals='vertex' interpolates and normalises"""
     xyz, faces, nrm, n, seed = S.build_case("spheres")

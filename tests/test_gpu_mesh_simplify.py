@@ -58,6 +58,23 @@ def test_the_box_equals_the_reference(box):
     assert sorted(out) == ["cell_key", "cluster", "count", "faces", "normal", "placed", "stats", "xyz"]
 
 
+@pytest.mark.parametrize("where", ["d64", "d64-rotated", "d512"])
+def test_a_placed_patch_equals_the_reference(where):
+    """the 257-face patch built 64 m and 512 m out and in the turned world (tests/placement.py; "offset-1000" of the route suite adds its
+    offset to fp32 data), the grid's corner moved with it: the cell keys are relative to that corner and the quadrics are accumulated in
+    float64 about the cell centres, so the result is the reference's TO THE BIT, as everywhere in this family"""
+    import placement as PL
+    place = PL.PLACES[where]
+    xyz, faces = R.patch(R.PLACED_FACES, place=place)
+    origin = (xyz.min(0).astype(np.float64) - 0.013).astype(np.float32)
+    for org, what in ((None, "the box's corner"), (origin, "a corner of the caller's")):
+        out = simplify_mesh({"xyz": xyz, "faces": faces}, 0.1, origin=org)
+        want = R.simplify(xyz, faces, 0.1, org)
+        n = _equals_reference(out, want, "patch-%d@%s, %s" % (R.PLACED_FACES, where, what))
+        print("PLACEMENT mesh_simplify patch-%d@%s (%s): %d values equal to the reference's bits; %s" % (R.PLACED_FACES, where, what, n, out["stats"]))
+        assert 10 < out["stats"]["vertices"] < xyz.shape[0] and out["stats"]["faces"] > 10 and float(np.abs(xyz).min()) > place[0] / 4
+
+
 def test_the_noisy_sphere_equals_the_reference():
     xyz, faces = R.noisy_sphere()
     rng = np.random.RandomState(4)

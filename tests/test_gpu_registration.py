@@ -11,13 +11,18 @@ points.  The figures are printed (REGISTRATION lines; recorded in profiles/rigid
 Refusals return the guess unchanged: a single plane ("condition"), fewer than min_count partners ("count").  ``rigid_system`` twice gives
 the same 29 doubles bit for bit under both bindings.  ``compare_meshes(align=...)`` on a prediction offset by the small twist brings the
 accuracy back to the unmoved prediction's figure within the sampled scores' own repeatability, MEASURED here as the largest change of
-that figure over three other sampling seeds; without ``align`` the result has today's keys and bits."""
+that figure over three other sampling seeds; without ``align`` the result has today's keys and bits.
+
+Away from the origin: the 257-point cases of both metrics and of both ways to read the target, built 64 m and 512 m out (tests/placement.py),
+through ``rigid_align_ref.compare`` unchanged -- the bounds scale with the coordinates, the ambiguous share stays under its cap (the
+reference alone: tests/test_placement_ref_cpu.py).  The pose solves at those placements: tests/test_gpu_placement.py."""
 import numpy as np
 import pytest
 import torch
 
 from estdepth_amd import registration
 
+import placement as PL
 import rigid_align_ref as R
 from test_gpu_recon3d_routes import _dev, under
 
@@ -42,7 +47,7 @@ def _target(fx, kind):
 def test_register_lands_where_the_reference_lands(kind, metric, scale):
     fx = R.registration_fixture(scale)
     dist = STAGED if scale > 1 else R.DIST_MAX
-    ref = R.refine(fx["src"], fx[kind], metric=metric, dist_max=dist)
+    ref = R.refine(fx["src"], fx[kind], metric=metric, dist_max=dist, pivot=R.target_pivot(fx[kind]))
     out = registration.register(_dev(fx["src"]), _target(fx, kind), metric=metric, dist_max=dist)
     t0, a0 = R.pose_error(np.eye(4), fx["T_true"])
     tr, ar = R.pose_error(ref["T"], fx["T_true"])
@@ -64,7 +69,7 @@ def test_a_single_plane_is_refused_for_its_condition():
     p, n = R.single_plane(2000, 1)
     guess = R.exp_se3(0.2 * R.TWIST)
     out = registration.register(_dev(p), dict(xyz=_dev(p), normal=_dev(n)), init=guess, metric="plane", dist_max=R.DIST_MAX)
-    ref = R.refine(p, dict(xyz=p, normal=n), init=guess, metric="plane", dist_max=R.DIST_MAX)
+    ref = R.refine(p, dict(xyz=p, normal=n), init=guess, metric="plane", dist_max=R.DIST_MAX, pivot=R.target_pivot(dict(xyz=p)))
     assert ref["reason"] == "condition"
     assert not out["converged"] and out["reason"] == "condition" and out["iterations"] == 0
     assert np.array_equal(out["T"], guess) and out["correction"] == (0.0, 0.0)
@@ -80,6 +85,24 @@ def test_too_few_partners_are_refused_for_their_count():
     full = registration.register(_dev(fx["src"]), _target(fx, "mesh"), metric="plane", dist_max=(R.DIST_MAX, 1e-9), min_count=4000)
     first = registration.register(_dev(fx["src"]), _target(fx, "mesh"), metric="plane", dist_max=R.DIST_MAX, min_count=4000)
     assert full["reason"] == "count" and not full["converged"] and first["converged"] and np.array_equal(full["T"], first["T"])
+
+
+@pytest.mark.parametrize("where", list(PL.FAMILY_PLACES))
+@pytest.mark.parametrize("name", R.PLACED_CASES)
+def test_the_kernels_meet_their_bounds_away_from_the_origin(name, where):
+    from estdepth_amd import ops
+    place = PL.FAMILY_PLACES[where]
+    c, ref = R.build_case(name, place), R.reference(name, place)
+    opt = lambda a: _dev(a) if a is not None else None                                                            # noqa: E731
+    moved, mn = ops.rigid_apply(_dev(c["src"]), opt(c["src_normal"]), torch.from_numpy(c["T12"]))
+    res, mt, sums = ops.rigid_system(_dev(c["moved"]), opt(c["moved_normal"]), _dev(c["index"]), _dev(c["target"]), _dev(c["normal"]), c["by_index"],
+                                     c["metric"], c["dist_max"], c["cos_min"], c["two_sided"])
+    got = dict(moved=moved.cpu().numpy(), moved_normal=mn.cpu().numpy() if mn is not None else None, residual=res.cpu().numpy(),
+               match=mt.cpu().numpy(), sums=sums.cpu().numpy())
+    fig = R.compare(got, c, ref, c["name"])
+    assert fig["matched"] >= 0.6 * fig["gated"] and float(np.abs(c["target"]).max()) > place[0] / 2
+    print("PLACEMENT rigid_align %s: moved %.3f residual %.3f sums %.3f of the bound, ambiguous share %.4f, matched %d"
+          % (c["name"], fig["moved_ratio"], fig["residual_ratio"], fig["sum_ratio"], fig["amb_share"], fig["matched"]))
 
 
 @pytest.mark.parametrize("kind,metric", [("mesh", "plane"), ("cloud", "point")])

@@ -63,7 +63,7 @@ def test_score_align_end_to_end(moved_gt, tmp_path, monkeypatch):
     # the float64 reference registration from the same device samples, with the tool's default stages (8, 4, 2 thresholds)
     samples = sample_mesh(state.volume.extract_mesh(), density=DENSITY, seed=0)["xyz"].cpu().numpy()
     assert samples.shape[0] == got["n_pred"]
-    ref = R.refine(samples, mesh, metric="plane", dist_max=tuple(k * got["threshold"] for k in (8.0, 4.0, 2.0)))
+    ref = R.refine(samples, mesh, metric="plane", dist_max=tuple(k * got["threshold"] for k in (8.0, 4.0, 2.0)), pivot=R.target_pivot(mesh))
     T = np.asarray(blk["T"]).reshape(4, 4)
     tr, ar = R.pose_error(ref["T"], G)
     td, ad = R.pose_error(T, G)

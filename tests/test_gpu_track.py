@@ -9,7 +9,12 @@ reference's evaluation GIVEN the device's match map.  Semantic: from a guess off
 <= 1.25 x the error the float64 reference reaches from the same rendered maps (translation and angle each) and below the perturbation;
 fusing the refined frame renders closer to the analytic scene at the true pose than fusing the perturbed one (median and 95th percentile
 of |depth - analytic| in voxels over the frame's own pixels).  The figures of a device run (this file prints them, pytest -s):
-profiles/track_gpu_tests.txt."""
+profiles/track_gpu_tests.txt.
+
+Away from the origin: the 120 x 160 case built 64 m and 128 m out (tests/placement.py; track_ref.PLACED_AT), through ``track_ref.compare``
+unchanged.  Not 512 m: the model pixel a point falls into is decided from a projection in fp32 world coordinates, and beyond 128 m the
+reference alone has more than 3 % of the pixels within the rounding of a pixel edge (0.056 at 256 m, 0.111 at 512 m;
+tests/test_placement_ref_cpu.py measures it).  The pose solve itself is tested out to 512 m in tests/test_gpu_placement.py."""
 import numpy as np
 import pytest
 import torch
@@ -49,6 +54,15 @@ def test_against_reference(name, binding, monkeypatch):
     fig = T.compare(_run(c), c, T.reference(name), "%s %s" % (name, binding))
     assert fig["matched"] > 10000
     print("TRACK-RATIO %s %s residual %.3f sums %.3f amb %.4f" % (name, binding, fig["residual_ratio"], fig["sum_ratio"], fig["amb_share"]))
+
+
+@pytest.mark.parametrize("d", T.PLACED_AT)
+def test_against_reference_away_from_the_origin(d):
+    c, ref = T.build_case(T.PLACED_CASE, (d, False)), T.reference(T.PLACED_CASE, (d, False))
+    fig = T.compare(_run(c), c, ref, c["name"])
+    assert fig["matched"] > 10000 and float(np.abs(c["mats"][0][:, 3]).max()) > d / 2
+    print("PLACEMENT frame_align %s: residual %.3f sums %.3f of the bound, ambiguous share %.4f, matched %d"
+          % (c["name"], fig["residual_ratio"], fig["sum_ratio"], fig["amb_share"], fig["matched"]))
 
 
 def test_full_size():
@@ -187,7 +201,7 @@ def test_track_recovers_a_perturbed_pose(fused, binding, monkeypatch):
     # the float64 reference from the same rendered maps, ten iterations
     maps = vol.render(torch.from_numpy(guess), Kt, (H, W))
     model = dict(depth=maps["depth"].cpu().numpy(), normal=maps["normal"].cpu().numpy(), pose=guess, K=K)
-    P_ref, trace = T.refine(frame.astype(np.float32), K, guess, model, iters=10, dist_max=vol.trunc, z_near=vol.z_near)
+    P_ref, trace = T.refine(frame.astype(np.float32), K, guess, model, iters=10, pivot=vol.centre, dist_max=vol.trunc, z_near=vol.z_near)
     tr, ar = T.pose_error(P_ref, T.HELD_OUT_POSE)
     print("TRACK-SEMANTIC %s: guess off by %.2f mm %.3f deg; device %.3f mm %.4f deg after %d iterations (%s), reference %.3f mm %.4f deg; rmse %.2f -> "
           "%.2f mm, matched share %.3f, correction %.2f mm %.3f deg" % (binding, 1e3 * t0, np.degrees(a0), 1e3 * td, np.degrees(ad), out["iterations"], out["reason"],

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import placement as PL
 import tsdf_ref as R
 from helpers import _binding
 
@@ -67,6 +68,26 @@ def test_integrate_against_reference(name, binding, monkeypatch):
         D0, W0 = gD, gW
     if name == "second":
         assert gW.max() == 4.0
+
+
+@pytest.mark.parametrize("where", list(PL.FAMILY_PLACES))
+def test_integrate_away_from_the_origin(where):
+    """the smallest case with its cameras and the volume's corner 64 m and 512 m out (tests/placement.py): the host forms the voxel-to-pixel
+    matrices in float64 relative to the volume's corner, so the kernel sees the numbers it sees at the origin to their last bits or so;
+    the comparison and its cap are unchanged (the reference alone: tests/test_placement_ref_cpu.py)"""
+    case = R.build_case(R.PLACED_CASE, PL.FAMILY_PLACES[where])
+    assert min(abs(v) for v in case["origin"]) > PL.FAMILY_PLACES[where][0] / 4
+    D0, W0 = _sentinel(case["dims"]), np.zeros(case["dims"], np.float32)
+    vol = _volume(case, fill=D0)
+    gD, gW = _integrate(vol, case)
+    ref = R.integrate(D0, W0, _mats(case), case["depths"], case["confs"], **case["params"])
+    fig = R.compare(gD, gW, ref, D_before=D0, W_before=W0)
+    assert fig["updated"] > 1000
+    print("PLACEMENT tsdf_integrate %s: ambiguous share %.4f, updated %d" % (case["name"], fig["amb_share"], fig["updated"]))
+    ref = R.extract(gD, gW, 1.0, case["voxel"], case["origin"])               # the points of the same volume: positions 64 m and 512 m out
+    got = _points(vol.extract_points(w_min=1.0))
+    assert np.array_equal(np.sort(got["edge"]), ref["edge"]) and len(ref["edge"]) > 1000
+    R.compare_points(got, ref)
 
 
 def test_integrate_full_size():

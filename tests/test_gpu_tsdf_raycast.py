@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+import placement as PL
 import tsdf_ref as R
 import tsdf_raycast_ref as RR
 from helpers import _binding
@@ -25,11 +26,12 @@ _FUSED = {}
 _REFS = {}
 
 
-def _fused(name):
+def _fused(name, place=None):
     """(case, TSDFVolume fused on the device by integrate, D, Wt copied back), once per case"""
+    name = name if PL.key(place) is None else "%s@%s" % (name, PL.label(place))
     if name not in _FUSED:
         from estdepth_amd.fusion3d import TSDFVolume
-        case = R.build_case(name)
+        case = R.build_case(name.split("@")[0], place)
         p = case["params"]
         vol = TSDFVolume(case["dims"], case["voxel"], case["origin"], trunc=p["trunc"], w_max=p["w_max"], z_near=p["z_near"], device=DEV)
         depths = torch.from_numpy(case["depths"]).to(DEV)
@@ -78,6 +80,19 @@ def test_render_against_reference(name, w_min, which, binding, monkeypatch):
         _REFS[name, w_min, which] = _reference(case, D, Wt, pose, w_min)
     fig = RR.compare(got, _REFS[name, w_min, which], "%s w_min %g %s %s" % (name, w_min, which, binding))
     assert fig["hit"] > 1000
+
+
+@pytest.mark.parametrize("where", list(PL.FAMILY_PLACES))
+def test_render_away_from_the_origin(where):
+    """the smallest case fused and rendered 64 m and 512 m out (tests/placement.py): the pixel-to-ray matrix is formed in float64 relative
+    to the volume's corner, so the rays are those at the origin; the comparison and its cap are unchanged"""
+    place = PL.FAMILY_PLACES[where]
+    case, vol, D, Wt = _fused(R.PLACED_CASE, place)
+    pose = PL.pose(RR.HELD_OUT_POSE, place)
+    fig = RR.compare(_render(vol, case, pose, 1.0), _reference(case, D, Wt, pose, 1.0), case["name"])
+    assert fig["hit"] > 1000
+    print("PLACEMENT tsdf_raycast %s: ambiguous share %.4f, hit %d" % (case["name"], fig["amb_share"], fig["hit"]))
+    _FUSED.pop(case["name"])
 
 
 def test_render_full_size():

@@ -52,6 +52,7 @@ import functools
 
 import numpy as np
 
+import placement as PL
 import tsdf_ref as R
 
 U = 2.0 ** -24
@@ -330,16 +331,65 @@ def step(depth, K, pose_guess, model, conf=None, conf_min=0.0, dist_max=DIST_MAX
     return out
 
 
-def refine(depth, K, pose_guess, model, iters=10, **kw):
-    """``iters`` Gauss-Newton steps P <- Exp(xi) P with A xi = b (Cholesky), no stopping rule -> (pose, [rmse per evaluation])"""
+def pivoted(A, b, pivot):
+    """(A, b) of twists about the world origin -> about ``pivot`` c: G = [[I, 0], [-[c]x, I]], A_c = G A G^T, b_c = G b (None: unchanged)"""
+    if pivot is None:
+        return A, b
+    G = np.eye(6)
+    G[3:, :3] = -hat(np.asarray(pivot, np.float64).reshape(3))
+    Ac = G @ A @ G.T
+    return 0.5 * (Ac + Ac.T), G @ b
+
+
+def pivot_step(xi, pivot):
+    """C Exp(xi) C^-1 with C the translation by the pivot: the twist applied about the pivot (None: about the world origin)"""
+    E = exp_se3(xi)
+    if pivot is not None:
+        c = np.asarray(pivot, np.float64).reshape(3)
+        E[:3, 3] += c - E[:3, :3] @ c
+    return E
+
+
+def refine(depth, K, pose_guess, model, iters=10, pivot=None, **kw):
+    """``iters`` Gauss-Newton steps P <- Exp(xi) P with A xi = b (Cholesky), no stopping rule -> (pose, [rmse per evaluation]).
+    ``pivot``: every system is re-expressed about it and the step is the twist about it, as tracking.gauss_newton does (None: the world
+    origin, the method before the pivot)"""
     P, trace = np.asarray(pose_guess, np.float64).copy(), []
     for _ in range(iters):
         s = step(depth, K, P, model, **kw)
         trace.append(s["rmse"])
-        Lc = np.linalg.cholesky(s["A"])
-        xi = np.linalg.solve(Lc.T, np.linalg.solve(Lc, s["b"]))
-        P = exp_se3(xi) @ P
+        A, b = pivoted(s["A"], s["b"], pivot)
+        Lc = np.linalg.cholesky(A)
+        xi = np.linalg.solve(Lc.T, np.linalg.solve(Lc, b))
+        P = pivot_step(xi, pivot) @ P
     return P, trace
+
+
+def refine_stopped(depth, K, pose_guess, model, max_iter=10, min_count=100, pivot=None, cond_max=1e6, step_t=1e-5, step_r=1e-5, **kw):
+    """tracking.refine_pose in this module's words: the refusals (count, cholesky, condition at ``cond_max``) and the stopping rule of
+    tracking.gauss_newton on the float64 systems -> dict(pose, converged, reason, iterations, cond = cond(A_c) of the first system)"""
+    guess = np.asarray(pose_guess, np.float64).copy()
+    P, reason, done, cond = guess.copy(), "max_iter", 0, None
+    for it in range(max_iter):
+        s = step(depth, K, P, model, **kw)
+        if s["count"] < min_count:
+            return dict(pose=guess, converged=False, reason="count", iterations=it, cond=cond)
+        A, b = pivoted(s["A"], s["b"], pivot)
+        cond = float(np.linalg.cond(A)) if cond is None else cond
+        try:
+            Lc = np.linalg.cholesky(A)
+        except np.linalg.LinAlgError:
+            return dict(pose=guess, converged=False, reason="cholesky", iterations=it, cond=cond)
+        ev = np.linalg.eigvalsh(A)
+        if not ev[0] > 0 or ev[-1] > cond_max * ev[0]:
+            return dict(pose=guess, converged=False, reason="condition", iterations=it, cond=cond)
+        xi = np.linalg.solve(Lc.T, np.linalg.solve(Lc, b))
+        P = pivot_step(xi, pivot) @ P
+        done = it + 1
+        if np.linalg.norm(xi[:3]) < step_t and np.linalg.norm(xi[3:]) < step_r:
+            reason = "converged"
+            break
+    return dict(pose=P, converged=reason == "converged", reason=reason, iterations=done, cond=cond)
 
 
 # ------------------------------------------------------------------------------------------------------------ the cases of the suite
@@ -362,7 +412,9 @@ def perturbed(pose, scale=1.0):
     return exp_se3(scale * TWIST) @ np.asarray(pose, np.float64)
 
 
-def make_case(hw, hw_m=None, model="true", conf=False, holes=False, away=False, noise=NOISE, seed=0, name=""):
+def make_case(hw, hw_m=None, model="true", conf=False, holes=False, away=False, noise=NOISE, seed=0, name="", place=None):
+    """``place`` (placement.py): the same case in the placed world.  A depth map does not change when the world moves with its camera;
+    the poses become W P and the model's normals, which are in world axes, W's rotation of them, in float64 before the one rounding"""
     H, W = hw
     Hm, Wm = hw_m or hw
     K, K_m = R.intrinsics(H, W), R.intrinsics(Hm, Wm)
@@ -371,7 +423,12 @@ def make_case(hw, hw_m=None, model="true", conf=False, holes=False, away=False, 
     rng = np.random.RandomState(23 + seed)
     depth = scene_maps(pose, K, H, W)[0]
     depth = (depth * (1.0 + noise * rng.randn(H, W))).astype(np.float32)
-    m_depth, m_normal = (t.astype(np.float32) for t in scene_maps(model_pose, K_m, Hm, Wm))
+    m_depth, m_normal = scene_maps(model_pose, K_m, Hm, Wm)
+    guess = perturbed(pose)
+    if PL.key(place) is not None:
+        m_normal = PL.vectors(m_normal, place)
+        pose, model_pose, guess = PL.pose(pose, place), PL.pose(model_pose, place), PL.pose(guess, place)
+    m_depth, m_normal = m_depth.astype(np.float32), m_normal.astype(np.float32)
     if holes:
         depth[H // 12:H // 4, W // 8:W // 3] = 0.0
         depth[H // 2:H // 2 + H // 8, W // 2:W // 2 + W // 4] = np.nan
@@ -379,7 +436,6 @@ def make_case(hw, hw_m=None, model="true", conf=False, holes=False, away=False, 
         depth[H // 3:H // 3 + 5, 5:15] = -1.0
         m_depth[Hm // 3:Hm // 2, 2 * Wm // 3:5 * Wm // 6] = 0.0
         m_normal[Hm // 3:Hm // 2, 2 * Wm // 3:5 * Wm // 6] = 0.0
-    guess = perturbed(pose)
     if away:
         guess = guess @ np.diag([-1.0, 1.0, -1.0, 1.0])            # half a turn about y: the frame looks away from the model
     cf = rng.uniform(0.0, 1.0, size=(H, W)).astype(np.float32) if conf else None
@@ -401,24 +457,54 @@ def tie_case():
 
 
 @functools.lru_cache(maxsize=None)
-def build_case(name):
+def build_case(name, place=None):
+    """the case ``name``; ``place``: the same case built at that placement (not the tie)"""
     if name == "tie":
+        assert PL.key(place) is None
         return tie_case()
     c = dict(FULL_CASE if name == "full" else CASES[name])
+    if PL.key(place) is not None:
+        return make_case(c.pop("hw"), seed=len(name), name="%s@%s" % (name, PL.label(place)), place=PL.key(place), **c)
     return make_case(c.pop("hw"), seed=len(name), name=name, **c)
 
 
 @functools.lru_cache(maxsize=None)
-def reference(name):
+def reference(name, place=None):
     """the float64 evaluation of a case, computed once and shared"""
-    return evaluate(build_case(name))
+    return evaluate(build_case(name, place))
+
+
+# the placed case of the feature suite: the smallest value case, 64 m and 128 m out -- not 512 m: the reference's own ambiguous share
+# passes AMB_CAP beyond 128 m (tests/test_placement_ref_cpu.py measures it: 0.029 at 128 m, 0.056 at 256 m)
+PLACED_CASE, PLACED_AT = "mid", (64, 128)
 
 
 @functools.lru_cache(maxsize=None)
-def convergence_fixture(hw=(120, 160)):
-    """the held-out frame against the analytic model maps at the true pose, the guess off by TWIST -> dict(depth, K, pose, guess, model)"""
+def convergence_fixture(hw=(120, 160), place=None):
+    """the held-out frame against the analytic model maps at the true pose, the guess off by TWIST -> dict(depth, K, pose, guess, model,
+    centre).  ``place`` (placement.py): the same frame, model and guess in the placed world -- the poses W P, the normals turned in
+    float64 before their one rounding, the twist of the guess conjugated (the same motion of the camera); ``centre``: the placed point
+    the error of a pose is measured at"""
     H, W = hw
     K = R.intrinsics(H, W)
     depth, normal = scene_maps(HELD_OUT_POSE, K, H, W)
-    model = dict(depth=depth.astype(np.float32), normal=normal.astype(np.float32), pose=HELD_OUT_POSE, K=K)
-    return dict(depth=depth.astype(np.float32), K=K, pose=HELD_OUT_POSE, guess=perturbed(HELD_OUT_POSE), model=model)
+    centre = np.array(SCENE_CENTRE)
+    if PL.key(place) is not None:
+        pose, normal, centre = PL.pose(HELD_OUT_POSE, place), PL.vectors(normal, place), PL.points(centre, place)
+        guess = PL.pose(perturbed(HELD_OUT_POSE), place)
+    else:
+        pose, guess = HELD_OUT_POSE, perturbed(HELD_OUT_POSE)
+    model = dict(depth=depth.astype(np.float32), normal=normal.astype(np.float32), pose=pose, K=K)
+    return dict(depth=depth.astype(np.float32), K=K, pose=pose, guess=guess, model=model, centre=centre)
+
+
+SCENE_CENTRE = (0.0, 0.0, 2.2)               # between the spheres and the plane: where a pose's error is measured in metres
+
+
+def pose_error_at(P, P_true, centre):
+    """(metres at ``centre``, radians) of the pose P relative to P_true: how far the motion P P_true^-1 moves the world point ``centre``,
+    and its angle.  pose_error measures the translation at the world origin, where an angle error of a placed scene is multiplied by
+    the scene's distance"""
+    D = np.asarray(P, np.float64) @ np.linalg.inv(np.asarray(P_true, np.float64))
+    c = np.asarray(centre, np.float64)
+    return float(np.linalg.norm(D[:3, :3] @ c + D[:3, 3] - c)), float(np.arccos(np.clip((np.trace(D[:3, :3]) - 1.0) / 2.0, -1.0, 1.0)))

@@ -384,9 +384,27 @@ ROUTE_CASES = {"r%dx%dx%d-t%d-%dx%d" % (dims + (T,) + hw): dict(T=T, hw=hw, dims
                for dims, org in ROUTE_DIMS.items() for T in (1, 8) for hw in ((1, 1), (3, 5), (120, 160))}
 
 
-def build_case(name):
-    """dict(dims, origin, voxel, trunc, poses [T,4,4] f64, K [3,3] f64, depths [T,H,W] f32, confs or None, params for integrate())"""
+PLACED_CASE = "t1"            # the case that is also built at placement.FAMILY_PLACES: the smallest volume and map the feature suite uses
+
+
+def placed_origin(origin, place):
+    """the volume's corner moved with the scene (placement.py; unturned placements only: a volume's axes are the world's) -> three floats
+    that are fp32 values, so that the volume (which keeps its origin in fp32) and the host's float64 matrices start from the same corner"""
+    import placement as PL
+    if PL.key(place) is None:
+        return tuple(origin)
+    assert not place[1], "a volume cannot follow a turned world"
+    return tuple(float(v) for v in (np.asarray(origin, np.float64) + PL.offset(place[0])).astype(np.float32))
+
+
+def build_case(name, place=None):
+    """dict(dims, origin, voxel, trunc, poses [T,4,4] f64, K [3,3] f64, depths [T,H,W] f32, confs or None, params for integrate()).
+    ``place`` (placement.py): the cameras and the volume's origin moved with the scene; the depth maps do not change"""
+    import placement as PL
     c = dict(CASES[name] if name in CASES else ROUTE_CASES[name])
+    if PL.key(place) is not None:
+        base = build_case(name)
+        return dict(base, name="%s@%s" % (name, PL.label(place)), origin=placed_origin(base["origin"], place), poses=PL.pose(base["poses"], place))
     T, (H, W) = c["T"], c["hw"]
     K = intrinsics(H, W)
     poses = scene_poses(T, seed=len(name))
