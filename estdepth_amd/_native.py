@@ -130,6 +130,16 @@ class CloudNearestDesc(ctypes.Structure):
     ]
 
 
+class CloudKnnDesc(ctypes.Structure):
+    """Mirror of struct estd_cloud_knn_desc (include/estd_hip.h)."""
+    _fields_ = [
+        ("M", ctypes.c_longlong), ("N", ctypes.c_longlong),
+        ("query", ctypes.c_void_p), ("order", ctypes.c_void_p), ("records", ctypes.c_void_p), ("cell_start", ctypes.c_void_p),
+        ("dist", ctypes.c_void_p), ("index", ctypes.c_void_p), ("count", ctypes.c_void_p), ("stats", ctypes.c_void_p),
+        ("lo", ctypes.c_float * 3), ("cell", ctypes.c_float), ("max_dist", ctypes.c_float), ("dims", ctypes.c_int * 3), ("k", ctypes.c_int),
+    ]
+
+
 class MeshNearestDesc(ctypes.Structure):
     """Mirror of struct estd_mesh_nearest_desc (include/estd_hip.h)."""
     _fields_ = [
@@ -245,6 +255,9 @@ _SIGNATURES = {
     "estd_cloud_nearest": (ctypes.c_int, [ctypes.POINTER(CloudNearestDesc), c_stream]),
     "estd_cloud_cell_centroids": (ctypes.c_int, [c_float_p, c_float_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
                                                  ctypes.c_longlong, c_float_p, c_float_p, c_stream]),
+    "estd_cloud_knn": (ctypes.c_int, [ctypes.POINTER(CloudKnnDesc), c_stream]),
+    "estd_cloud_normals": (ctypes.c_int, [c_float_p, ctypes.c_longlong, c_float_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                          c_float_p, ctypes.c_int, c_float_p, c_float_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_stream]),
     "estd_frame_align_partials": (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int]),
     "estd_frame_align": (ctypes.c_int, [ctypes.POINTER(FrameAlignDesc), c_stream]),
     "estd_tsdf_mesh_vertices": (ctypes.c_int, [c_float_p, c_float_p, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,

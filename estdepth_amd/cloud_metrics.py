@@ -14,6 +14,11 @@ precision / recall / F-score at a threshold.  The clouds are what ``TSDFVolume.e
     dist, face, bary = tri.query(points, bary=True)                    # the distance to the SURFACE, the face and where on it
     scores = compare_meshes(pred_mesh, gt_mesh, 1111.0, exact=True)    # surfaces scored against surfaces, not against samples
 
+    dist, index, count = grid.knn(points, 16)                          # the 16 nearest targets (csrc/cloud/cloud_knn.hip)
+    fit = estimate_normals(scan, 16, 0.05, toward=(0.0, 0.0, 1.5))     # normals of a cloud that came without: a PCA plane fit
+    keep = remove_outliers(scan, k=16, std_ratio=2.0)["keep"]          # statistical outlier removal over the same search
+    scores = compare_clouds(pred, scan, pred_normal=n, normals=dict(k=16))      # the side without normals gets them estimated
+
 The nearest-neighbour result is defined to the bit (include/estd_hip.h, estd_cloud_nearest): per query the smallest fp32
 ``d2 = fma(dx, dx, fma(dy, dy, dz * dz))`` over ALL targets, the smallest original index attaining it, found iff ``d2 <= max_dist^2``;
 ``dist = sqrt(d2)`` or ``max_dist``, ``index`` or -1.  The uniform grid behind it only decides which targets are looked at first; the cell
@@ -134,6 +139,23 @@ class PointGrid:
             order = torch.arange(points.shape[0], device=self.device, dtype=torch.int64)
         return ops.cloud_nearest(points, order, self.records, self.cell_start, self.lo, self.cell, self.dims, self.max_dist, stats=stats)
 
+    def knn(self, points, k, stats=False):
+        """``points`` [M,3], ``k`` in 1 .. 32 -> (dist [M,k] float32, index [M,k] int32, count [M] int32): the ``k`` nearest targets within
+        ``max_dist``, ascending by (d2, original index); ``count`` of them were found, the slots behind hold ``max_dist`` and -1
+        (csrc/cloud/cloud_knn.hip; include/estd_hip.h, estd_cloud_knn).  Column 0 is ``query``'s result.  ``stats=True`` (measurement
+        only) appends the candidates examined per query, int32 [M]."""
+        _need(isinstance(k, int) and not isinstance(k, bool) and 1 <= k <= ops.CLOUD_KNN_MAX, "PointGrid.knn: k must be an integer in 1 .. %d, got %r" % (ops.CLOUD_KNN_MAX, k))
+        points = _check_cloud(points, "points", "PointGrid.knn", self.device)
+        if points.shape[0] == 0:
+            out = (torch.empty((0, k), device=self.device), torch.empty((0, k), device=self.device, dtype=torch.int32),
+                   torch.empty(0, device=self.device, dtype=torch.int32))
+            return out + (torch.empty(0, device=self.device, dtype=torch.int32),) if stats else out
+        if self.n:
+            order = torch.sort(ops.cloud_cell_keys(points, self.lo, self.cell, self.dims), stable=True)[1]
+        else:
+            order = torch.arange(points.shape[0], device=self.device, dtype=torch.int64)
+        return ops.cloud_knn(points, order, self.records, self.cell_start, self.lo, self.cell, self.dims, self.max_dist, k, stats=stats)
+
 
 def nearest(query, target, max_dist, cell=None):
     """One-shot form of ``PointGrid(target, max_dist, cell).query(query)`` -> (dist [M], index [M])."""
@@ -143,7 +165,95 @@ def nearest(query, target, max_dist, cell=None):
     return PointGrid(target, max_dist, cell).query(query)
 
 
-MAX_PAIRS = ops.MESH_DISTANCE_MAX_PAIRS      # the (cell, face) pairs of a TriangleGrid
+def knn(query, target, k, max_dist, cell=None):
+    """One-shot form of ``PointGrid(target, max_dist, cell).knn(query, k)`` -> (dist [M,k], index [M,k], count [M])."""
+    _check_max_dist(max_dist, "knn")
+    _need(isinstance(query, torch.Tensor) and isinstance(target, torch.Tensor), "knn: query and target must be tensors")
+    _need(query.device == target.device, "knn: query is on %s but the target on %s" % (query.device, target.device))
+    return PointGrid(target, max_dist, cell).knn(query, k)
+
+
+def estimate_normals(points, k, max_dist, toward=None, cov=False, grid=None):
+    """Normals of the cloud ``points`` [N,3] by a plane fit (PCA) over each point's ``k`` nearest neighbours within ``max_dist`` -- the
+    point itself among them, as in PCL and Open3D (csrc/cloud/cloud_knn.hip; include/estd_hip.h, estd_cloud_normals) -> dict:
+    normal [N,3] float32 (unit; zero where not valid), eig [N,3] float32 (the covariance's eigenvalues, ascending), curvature [N]
+    float64 = l0 / (l0 + l1 + l2), the surface variation (0 where the sum is 0), valid [N] uint8 (at least 3 neighbours, l2 > 0 and
+    l1 - l0 > 2^-16 l2: a plane, not a line or a ball), count [N] int32 (the neighbours found), invalid (the rows that are not valid,
+    an int); with ``cov=True`` also cov [N,6] float64 (xx, xy, xz, yy, yz, zz; for tests).  ``toward``: a viewpoint (three numbers) or one
+    per point [N,3] the normals are turned to; None: the component of largest magnitude is positive -- an UNORIENTED normal, which is
+    what normal_consistency (an absolute cosine) and the point-to-plane metric need.  ``grid``: a ``PointGrid`` of these very points to
+    search in (its ``max_dist`` then holds), None to build one."""
+    op = "estimate_normals"
+    _need(isinstance(k, int) and not isinstance(k, bool) and 1 <= k <= ops.CLOUD_KNN_MAX, "%s: k must be an integer in 1 .. %d, got %r" % (op, ops.CLOUD_KNN_MAX, k))
+    if grid is None:
+        grid = PointGrid(points, _check_max_dist(max_dist, op))
+    _need(isinstance(grid, PointGrid), "%s: grid must be a PointGrid" % op)
+    points = _check_cloud(points, "points", op, grid.device)
+    _need(grid.n == points.shape[0], "%s: the grid holds %d points but the cloud %d" % (op, grid.n, points.shape[0]))
+    if toward is not None:
+        if not isinstance(toward, torch.Tensor):
+            toward = torch.from_numpy(np.ascontiguousarray(toward, dtype=np.float32))
+        toward = toward.to(device=grid.device, dtype=torch.float32).contiguous()
+        _need(tuple(toward.shape) in ((3,), tuple(points.shape)) and bool(torch.isfinite(toward).all()),
+              "%s: toward must be three finite numbers or [%d,3], got %s" % (op, points.shape[0], tuple(toward.shape)))
+    _, index, count = grid.knn(points, k)
+    normal, eig, valid, invalid, c = ops.cloud_normals(grid.target, points, index, count, toward, cov=cov)
+    e = eig.double()
+    total = e.sum(1)
+    out = dict(normal=normal, eig=eig, curvature=torch.where(total > 0, e[:, 0] / torch.where(total > 0, total, torch.ones_like(total)), torch.zeros_like(total)),
+               valid=valid, count=count, invalid=int(invalid.item()))
+    if cov:
+        out["cov"] = c
+    return out
+
+
+def remove_outliers(points, k=16, std_ratio=2.0, max_dist=None, min_neighbours=None):
+    """Statistical (and radius) outlier removal of the cloud ``points`` [N,3] over ``PointGrid.knn`` -> dict(keep [N] bool, mean_dist [N]
+    float64, mu, sigma, dropped).  Per point the mean distance to the found neighbours OTHER than the point's own row (``k`` are searched,
+    the point itself among them); mu and sigma (the population's: divided by the number of values) are taken over the points with at
+    least one such neighbour; a point is kept where mean <= mu + ``std_ratio`` sigma, and dropped where it has no other neighbour within
+    ``max_dist`` (mean_dist is ``max_dist`` there).  ``min_neighbours=n`` additionally asks for n neighbours other than itself within
+    ``max_dist`` (the radius rule; needs k > n).  ``max_dist`` None: the diagonal of the cloud's box, so that every point is in reach.
+    Float64 torch arithmetic over the kernel's output."""
+    op = "remove_outliers"
+    _need(isinstance(k, int) and not isinstance(k, bool) and 2 <= k <= ops.CLOUD_KNN_MAX, "%s: k must be an integer in 2 .. %d, got %r" % (op, ops.CLOUD_KNN_MAX, k))
+    _need(isinstance(std_ratio, (int, float)) and math.isfinite(std_ratio) and std_ratio >= 0, "%s: std_ratio must be finite and not negative, got %r" % (op, std_ratio))
+    _need(min_neighbours is None or (isinstance(min_neighbours, int) and 1 <= min_neighbours < k), "%s: min_neighbours must be in 1 .. k - 1, got %r" % (op, min_neighbours))
+    points = _check_cloud(points, "points", op)
+    n, dev = int(points.shape[0]), points.device
+    if n == 0:
+        return dict(keep=torch.zeros(0, device=dev, dtype=torch.bool), mean_dist=torch.zeros(0, device=dev, dtype=torch.float64), mu=0.0, sigma=0.0, dropped=0)
+    if max_dist is None:
+        max_dist = float((points.amax(0).double() - points.amin(0).double()).norm().item()) * (1.0 + 2.0 ** -20) or 1.0
+    max_dist = _check_max_dist(max_dist, op)
+    dist, index, _ = PointGrid(points, max_dist).knn(points, k)
+    other = (index >= 0) & (index != torch.arange(n, device=dev, dtype=torch.int32)[:, None])
+    n_other = other.sum(1)
+    has = n_other > 0
+    total = torch.where(other, dist.double(), torch.zeros((), device=dev, dtype=torch.float64)).sum(1)
+    mean = torch.where(has, total / n_other.clamp(min=1).double(), torch.full((), float(np.float32(max_dist)), device=dev, dtype=torch.float64))
+    sel = mean[has]
+    mu = float(sel.mean().item()) if sel.shape[0] else 0.0
+    sigma = float(sel.std(unbiased=False).item()) if sel.shape[0] else 0.0
+    keep = has & (mean <= mu + float(std_ratio) * sigma)
+    if min_neighbours is not None:
+        keep = keep & (n_other >= min_neighbours)
+    return dict(keep=keep, mean_dist=mean, mu=mu, sigma=sigma, dropped=n - int(keep.sum().item()))
+
+
+NORMALS_KEYS = ("k", "radius")
+
+
+def _normals_arg(normals, threshold, op):
+    """``normals=dict(k=16, radius=None)`` -> (k, radius): ``radius`` None is ``threshold``"""
+    _need(isinstance(normals, dict) and all(key in NORMALS_KEYS for key in normals), "%s: normals must be a dict with keys among %s" % (op, ", ".join(NORMALS_KEYS)))
+    k = 16 if normals.get("k") is None else normals["k"]
+    _need(isinstance(k, int) and not isinstance(k, bool) and 3 <= k <= ops.CLOUD_KNN_MAX, "%s: normals['k'] must be an integer in 3 .. %d, got %r" % (op, ops.CLOUD_KNN_MAX, k))
+    radius = threshold if normals.get("radius") is None else normals["radius"]
+    return k, _check_max_dist(radius, op + " (normals['radius'])")
+
+
+MAX_PAIRS =ops.MESH_DISTANCE_MAX_PAIRS      # the (cell, face) pairs of a TriangleGrid
 BIG_CELLS = ops.MESH_DISTANCE_BIG_CELLS      # a triangle whose box covers more cells goes on the big list
 
 
@@ -312,7 +422,7 @@ def _align(src, src_normal, target, target_normal, align, threshold, op):
 
 
 def compare_clouds(pred, gt, threshold=0.05, max_dist=None, downsample=None, pred_normal=None, gt_normal=None, pred_color=None, gt_color=None,
-                   cell=None, align=None):
+                   cell=None, align=None, normals=None):
     """The 3D scores of the cloud ``pred`` [P,3] against ``gt`` [G,3] (float32, one ROCm device, finite) -> dict of floats / ints:
 
     accuracy / completeness: the mean distance pred -> gt / gt -> pred, each distance clamped to ``max_dist`` (default 20 ``threshold``);
@@ -326,7 +436,12 @@ def compare_clouds(pred, gt, threshold=0.05, max_dist=None, downsample=None, pre
     ``align=dict(metric="plane", dist_max=None, max_iter=30, init=None)`` registers ``pred`` to ``gt`` first (registration.register; the
     plane metric needs ``gt_normal``; ``dist_max`` defaults to 8, 4 and 2 thresholds) and scores the moved prediction, its normals
     rotated; the result gains ``alignment`` = dict(T: 16 numbers row by row, correction, rmse, overlap, iterations, converged, reason).  A
-    registration that did not converge is reported there and the UNMOVED prediction is scored.  With the default None nothing of this runs."""
+    registration that did not converge is reported there and the UNMOVED prediction is scored.  With the default None nothing of this runs.
+    ``normals=dict(k=16, radius=None)``: whichever side comes without normals gets them from its own points (``estimate_normals`` over
+    the ``k`` nearest neighbours within ``radius``, None: ``threshold``; after ``downsample``; unoriented).  Rows the estimate finds not
+    valid leave the normal_consistency pairs, and with ``align`` and the plane metric a ground truth without normals is registered to
+    through its valid rows only (estimated before the down-sampling, on the cloud the registration sees).  The result gains ``normals`` =
+    dict(k, radius, estimated: the sides among "pred", "gt", invalid_pred, invalid_gt).  With the default None nothing of this runs."""
     _need(isinstance(threshold, (int, float)) and math.isfinite(threshold) and threshold > 0, "compare_clouds: threshold must be positive and finite, got %r" % (threshold,))
     if max_dist is None:
         max_dist = 20.0 * threshold
@@ -344,9 +459,18 @@ def compare_clouds(pred, gt, threshold=0.05, max_dist=None, downsample=None, pre
                   "compare_clouds: %s must be float32 %s on the cloud's device" % (name, tuple(cloud.shape)))
             attrs[name] = a.contiguous()
     alignment = None
+    est, rows_ok, early = None, {}, None
+    if normals is not None:
+        nk, nr = _normals_arg(normals, threshold, "compare_clouds")
+        est = dict(k=nk, radius=nr, estimated=[], invalid_pred=0, invalid_gt=0)
     if align is not None:
         from . import registration
-        T, alignment = _align(pred, attrs.get("pred_normal"), PointGrid(gt, _align_reach(align, threshold)), attrs.get("gt_normal"), align, threshold,
+        tgt, tgt_normal = gt, attrs.get("gt_normal")
+        if est is not None and tgt_normal is None and isinstance(align, dict) and align.get("metric", "plane") == "plane":
+            early = estimate_normals(gt, nk, nr)                              # the registration's target: the valid rows of the cloud as it came
+            ok = early["valid"].bool()
+            tgt, tgt_normal = gt[ok].contiguous(), early["normal"][ok].contiguous()
+        T, alignment = _align(pred, attrs.get("pred_normal"), PointGrid(tgt, _align_reach(align, threshold)), tgt_normal, align, threshold,
                               "compare_clouds")
         if T is not None:
             moved = registration.transform(pred, T, attrs.get("pred_normal"))
@@ -364,6 +488,13 @@ def compare_clouds(pred, gt, threshold=0.05, max_dist=None, downsample=None, pre
                 pred = pts
             else:
                 gt = pts
+    if est is not None:
+        for side, cloud in (("pred", pred), ("gt", gt)):
+            if side + "_normal" not in attrs:
+                e = early if (side == "gt" and early is not None and downsample is None) else estimate_normals(cloud, nk, nr)
+                attrs[side + "_normal"], rows_ok[side] = e["normal"], e["valid"].bool()
+                est["estimated"].append(side)
+                est["invalid_" + side] = e["invalid"]
     thr32 = float(np.float32(threshold))
     d_pg, i_pg = PointGrid(gt, max_dist, cell).query(pred)
     d_gp, i_gp = PointGrid(pred, max_dist, cell).query(gt)
@@ -382,8 +513,19 @@ def compare_clouds(pred, gt, threshold=0.05, max_dist=None, downsample=None, pre
     if "pred_normal" in attrs and "gt_normal" in attrs:
         dot = lambda x, y: (x * y).sum(1).abs()
         found = lambda dist, index: index >= 0
-        v = [x for x in (pairs(attrs["pred_normal"], attrs["gt_normal"], d_pg, i_pg, dot, found),
-                         pairs(attrs["gt_normal"], attrs["pred_normal"], d_gp, i_gp, dot, found)) if x is not None]
+
+        def found_valid(src, dst):
+            """found pairs whose estimated normals are valid on both ends (a side with given normals has no mask)"""
+            def keep(dist, index):
+                m = index >= 0
+                if src in rows_ok:
+                    m = m & rows_ok[src]
+                if dst in rows_ok:
+                    m = m & rows_ok[dst][index.clamp(min=0)]
+                return m
+            return keep if rows_ok else found
+        v = [x for x in (pairs(attrs["pred_normal"], attrs["gt_normal"], d_pg, i_pg, dot, found_valid("pred", "gt")),
+                         pairs(attrs["gt_normal"], attrs["pred_normal"], d_gp, i_gp, dot, found_valid("gt", "pred"))) if x is not None]
         out["normal_consistency"] = sum(v) / len(v) if v else 0.0
     if "pred_color" in attrs and "gt_color" in attrs:
         l1 = lambda x, y: (x - y).abs().mean(1)
@@ -393,6 +535,8 @@ def compare_clouds(pred, gt, threshold=0.05, max_dist=None, downsample=None, pre
         out["color_l1"] = sum(v) / len(v) if v else 0.0
     if alignment is not None:
         out["alignment"] = alignment
+    if est is not None:
+        out["normals"] = est
     return out
 
 
@@ -488,7 +632,8 @@ def _exact_scores(a, b, pred, gt, dev, threshold, max_dist, downsample, cell):
     return out
 
 
-def compare_meshes(pred, gt, density, threshold=0.05, max_dist=None, downsample=None, seed=0, cell=None, visible=None, exact=False, align=None):
+def compare_meshes(pred, gt, density, threshold=0.05, max_dist=None, downsample=None, seed=0, cell=None, visible=None, exact=False, align=None,
+                   normals=None):
     """The 3D scores of the SURFACE ``pred`` against the surface ``gt``: both triangle meshes (dicts with ``xyz`` and ``faces``: what
     ``extract_mesh``, ``filter_mesh`` or ``read_ply(faces=True)`` return) are sampled by area at ``density`` points per square metre
     (``fusion3d.sample_mesh``, face normals), and the two clouds go to ``compare_clouds`` unchanged -> its dict plus ``sampled`` =
@@ -513,7 +658,11 @@ def compare_meshes(pred, gt, density, threshold=0.05, max_dist=None, downsample=
     SURFACE (a ``TriangleGrid``; against its points where it has no faces), ``registration.register``; then the moved prediction is
     scored -- its samples, their normals and, for ``exact``, its vertices moved by T.  The result gains ``alignment`` (see
     ``compare_clouds``); a registration that did not converge is reported there and the unmoved prediction is scored.  With the
-    default None nothing of this runs."""
+    default None nothing of this runs.
+    ``normals=dict(k=16, radius=None)``: a side WITHOUT faces that comes without normals gets them estimated from its points, as
+    ``compare_clouds`` documents it (a side with faces has its face normals); with ``align`` and the plane metric such a ground truth is
+    registered to through its valid rows.  Not with ``exact=True``.  The result gains ``normals``.  With the default None nothing of
+    this runs."""
     _need(isinstance(density, (int, float)) and math.isfinite(density) and density > 0, "compare_meshes: density must be positive and finite, got %r" % (density,))
     from . import fusion3d
     _need(all(isinstance(x, dict) and x.get("xyz") is not None for x in (pred, gt)), "compare_meshes: pred and gt must be dicts with 'xyz'")
@@ -530,11 +679,19 @@ def compare_meshes(pred, gt, density, threshold=0.05, max_dist=None, downsample=
     (a, area_a, bad_a), (b, area_b, bad_b) = side(pred), side(gt)
     n_gt = int(b["xyz"].shape[0])
     alignment = None
+    if normals is not None:
+        nk, nr = _normals_arg(normals, threshold, "compare_meshes")
+        _need(not exact, "compare_meshes: normals= is not available with exact=True")
     if align is not None:
         from . import registration
         reach = _align_reach(align, threshold)
-        target = TriangleGrid(gt, reach) if gt.get("faces") is not None else PointGrid(_check_cloud(b["xyz"], "gt", "compare_meshes"), reach)
-        T, alignment = _align(a["xyz"], a.get("normal"), target, None if gt.get("faces") is not None else b.get("normal"), align, threshold,
+        tgt, tgt_normal = b["xyz"], b.get("normal")
+        if gt.get("faces") is None and normals is not None and tgt_normal is None and isinstance(align, dict) and align.get("metric", "plane") == "plane":
+            early = estimate_normals(_check_cloud(tgt, "gt", "compare_meshes"), nk, nr)      # the registration's target: the valid rows
+            ok = early["valid"].bool()
+            tgt, tgt_normal = tgt[ok].contiguous(), early["normal"][ok].contiguous()
+        target = TriangleGrid(gt, reach) if gt.get("faces") is not None else PointGrid(_check_cloud(tgt, "gt", "compare_meshes"), reach)
+        T, alignment = _align(a["xyz"], a.get("normal"), target, None if gt.get("faces") is not None else tgt_normal, align, threshold,
                               "compare_meshes")
         if T is not None:
             a = dict(a)
@@ -550,9 +707,11 @@ def compare_meshes(pred, gt, density, threshold=0.05, max_dist=None, downsample=
     if exact:
         out = _exact_scores(a, b, pred, gt, dev, threshold, max_dist, downsample, cell)
     else:
+        one = (lambda k: k in a or k in b) if normals is not None else both      # with normals=: the side that lacks them gets them estimated
         out = compare_clouds(a["xyz"], b["xyz"], threshold=threshold, max_dist=max_dist, downsample=downsample,
-                             pred_normal=a["normal"] if both("normal") else None, gt_normal=b["normal"] if both("normal") else None,
-                             pred_color=a["color"] if both("color") else None, gt_color=b["color"] if both("color") else None, cell=cell)
+                             pred_normal=a.get("normal") if one("normal") else None, gt_normal=b.get("normal") if one("normal") else None,
+                             pred_color=a["color"] if both("color") else None, gt_color=b["color"] if both("color") else None, cell=cell,
+                             **({} if normals is None else dict(normals=normals)))
     out["sampled"] = dict(density=float(density), n_pred=int(a["xyz"].shape[0]), n_gt=n_gt, area_pred=area_a, area_gt=area_b,
                           invalid_pred=bad_a, invalid_gt=bad_b)
     if visible is not None:

@@ -917,6 +917,72 @@ std::tuple<Tensor, Tensor, Tensor> cloud_nearest(const Tensor& query, const Tens
     return {dist, index, st};
 }
 
+// ------------------------------------------------------------------------------------------------ k nearest neighbours, normals (csrc/cloud/cloud_knn.hip)
+// query [M,3], order int64 [M], records [N,4], cell_start int32 [cells + 1] -> (dist [M,k], index int32 [M,k], count int32 [M], stats
+// int32 [M] when asked for (measurement only), else [0])
+std::tuple<Tensor, Tensor, Tensor, Tensor> cloud_knn(const Tensor& query, const Tensor& order, const Tensor& records, const Tensor& cell_start,
+                                                     const Tensor& lo, double cell, at::IntArrayRef dims, double max_dist, int64_t k, bool stats)
+{
+    const char* op = "cloud_knn";
+    const OpScope scope(query);
+    estd_cloud_knn_desc d{};
+    d.query = check_cloud(query, op, "query", 3);
+    d.records = check_cloud(records, op, "records", 4);
+    const int64_t M = query.size(0), N = records.size(0);
+    d.order = reinterpret_cast<const long long*>(lptr(order, op, "order", query, M));
+    d.max_dist = positive_square_f32(max_dist, op, "max_dist");
+    check_count(k, 1, ESTD_CLOUD_KNN_MAX, op, "k");
+    check_cloud_grid(lo, cell, dims, op, ESTD_CLOUD_MAX_DIM);
+    const int64_t cells = dims[0] * dims[1] * dims[2];
+    TORCH_CHECK(cells <= ESTD_CLOUD_MAX_CELLS, "cloud_knn: ", cells, " cells, at most ", ESTD_CLOUD_MAX_CELLS);
+    d.cell_start = lptr<int32_t>(cell_start, op, "cell_start (cells + 1)", query, cells + 1);
+    Tensor dist = new_f32({M, k}, query), index = at::empty({M, k}, query.options().dtype(at::kInt));
+    Tensor count = at::empty({M}, query.options().dtype(at::kInt));
+    Tensor st = at::empty({stats ? M : 0}, query.options().dtype(at::kInt));
+    if (M) {
+        d.M = (long long)M; d.N = (long long)N; d.k = (int)k;
+        d.dist = dist.data_ptr<float>(); d.index = index.data_ptr<int32_t>(); d.count = count.data_ptr<int32_t>();
+        d.stats = stats ? reinterpret_cast<unsigned int*>(st.data_ptr<int32_t>()) : nullptr;
+        d.cell = (float)cell;
+        for (int j = 0; j < 3; ++j) { d.lo[j] = lo.data_ptr<float>()[j]; d.dims[j] = (int)dims[j]; }
+        check_status(estd_cloud_knn(&d, cur_stream()), "estd_cloud_knn");
+    }
+    return {dist, index, count, st};
+}
+
+// points [N,3], query [M,3], index int32 [M,k], count int32 [M], toward: nothing, [3] or [M,3] -> (normal [M,3], eig [M,3], valid uint8
+// [M], invalid int64 [1], cov float64 [M,6] when asked for, else [0,6])
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> cloud_normals(const Tensor& points, const Tensor& query, const Tensor& index, const Tensor& count,
+                                                                 const OptTensor& toward, bool cov)
+{
+    const char* op = "cloud_normals";
+    const OpScope scope(points);
+    const float* pts = check_cloud(points, op, "points", 3);
+    const float* qs = check_cloud(query, op, "query", 3);
+    const int64_t n = points.size(0), M = query.size(0);
+    TORCH_CHECK(index.defined() && index.dim() == 2 && index.scalar_type() == at::kInt && index.is_contiguous() && index.device() == points.device() &&
+                index.size(0) == M && index.size(1) >= 1 && index.size(1) <= ESTD_CLOUD_KNN_MAX,
+                "cloud_normals: index must be a contiguous int32 [", M, ",k] with 1 <= k <= ", ESTD_CLOUD_KNN_MAX, " on the operator's device");
+    const int32_t* cnt = lptr<int32_t>(count, op, "count", points, M);
+    const float* tw = nullptr;
+    int per_query = 0;
+    if (toward.has_value() && toward->defined()) {
+        tw = fptr(*toward, "toward", true, op);
+        TORCH_CHECK((toward->dim() == 1 && toward->size(0) == 3) || (toward->dim() == 2 && toward->size(0) == M && toward->size(1) == 3),
+                    "cloud_normals: toward must be [3] or [", M, ",3], got ", toward->sizes());
+        per_query = toward->dim() == 2;
+    }
+    Tensor normal = new_f32({M, 3}, points), eig = new_f32({M, 3}, points);
+    Tensor valid = at::empty({M}, points.options().dtype(at::kByte)), invalid = at::zeros({1}, points.options().dtype(at::kLong));
+    Tensor c = at::empty({cov ? M : 0, 6}, points.options().dtype(at::kDouble));
+    if (M)
+        check_status(estd_cloud_normals(pts, (long long)n, qs, (long long)M, index.data_ptr<int32_t>(), cnt, (int)index.size(1), tw, per_query,
+                                        normal.data_ptr<float>(), eig.data_ptr<float>(), valid.data_ptr<uint8_t>(),
+                                        reinterpret_cast<long long*>(invalid.data_ptr<int64_t>()), cov ? c.data_ptr<double>() : nullptr, cur_stream()),
+                     "estd_cloud_normals");
+    return {normal, eig, valid, invalid, c};
+}
+
 // ------------------------------------------------------------------------------------------------ point-to-mesh distance (csrc/mesh/mesh_distance.hip)
 // the grid of the three operators: the rules of check_cloud_grid, at most ESTD_CLOUD_MAX_CELLS cells, big_cells not negative
 static int64_t check_tri_grid(const Tensor& lo, double cell, at::IntArrayRef dims, int64_t big_cells, const char* op)
@@ -1636,6 +1702,10 @@ TORCH_LIBRARY(estdepth_hip, m)
     m.def("cloud_nearest(Tensor query, Tensor order, Tensor records, Tensor cell_start, Tensor lo, float cell, int[] dims, float max_dist, "
           "bool stats) -> (Tensor, Tensor, Tensor)");
     m.def("cloud_cell_centroids(Tensor points, Tensor attrs, Tensor order, Tensor segments) -> (Tensor, Tensor)");
+    m.def("cloud_knn(Tensor query, Tensor order, Tensor records, Tensor cell_start, Tensor lo, float cell, int[] dims, float max_dist, "
+          "int k, bool stats) -> (Tensor, Tensor, Tensor, Tensor)");
+    m.def("cloud_normals(Tensor points, Tensor query, Tensor index, Tensor count, Tensor? toward, bool cov) -> "
+          "(Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("mesh_tri_bins(Tensor xyz, Tensor faces, Tensor lo, float cell, int[] dims, int big_cells) -> (Tensor, Tensor, Tensor)");
     m.def("mesh_tri_fill(Tensor xyz, Tensor faces, Tensor lo, float cell, int[] dims, int big_cells, Tensor offset, int n_pairs) -> "
           "(Tensor, Tensor)");
@@ -1709,6 +1779,8 @@ TORCH_LIBRARY_IMPL(estdepth_hip, CUDA, m)
     m.impl("cloud_cell_keys", cloud_cell_keys);
     m.impl("cloud_nearest", cloud_nearest);
     m.impl("cloud_cell_centroids", cloud_cell_centroids);
+    m.impl("cloud_knn", cloud_knn);
+    m.impl("cloud_normals", cloud_normals);
     m.impl("mesh_tri_bins", mesh_tri_bins);
     m.impl("mesh_tri_fill", mesh_tri_fill);
     m.impl("mesh_nearest", mesh_nearest);

@@ -362,7 +362,7 @@ class TSDFVolume:
         return rec.shape[0], faces.shape[0]
 
     def compare(self, other, threshold=0.05, w_min=1.0, max_dist=None, downsample=None, cell=None, sample=None, seed=0, visible=None, exact=False,
-                align=None):
+                align=None, normals=None):
         """The 3D scores (``cloud_metrics.compare_clouds``: accuracy, completeness, chamfer, precision / recall / F-score at ``threshold``
         metres, ...) of this volume's surface as the prediction against ``other`` as the ground truth: another ``TSDFVolume`` -- both sides
         go through ``extract_points(w_min)`` -- or a dict with ``xyz`` [N,3] and optionally ``normal`` / ``color`` (device tensors or numpy
@@ -377,8 +377,12 @@ class TSDFVolume:
         ``align=dict(metric=, dist_max=, max_iter=, init=)`` registers this volume's surface to ``other`` first and scores the moved
         surface (``cloud_metrics.compare_clouds`` / ``compare_meshes`` document it; the result gains ``alignment``): with ``sample`` both
         sides go to ``compare_meshes`` as meshes, so that the registration runs against the ground truth's surface; without, the two
-        clouds are registered.  With the default None nothing of this runs."""
+        clouds are registered.  With the default None nothing of this runs.
+        ``normals=dict(k=16, radius=None)`` is handed on: a side that comes without normals (a dict without ``normal`` and without faces) gets
+        them estimated from its own points (``cloud_metrics.estimate_normals``); the result gains ``normals``.  With the default None nothing
+        of this runs."""
         from . import cloud_metrics
+        more = {} if normals is None else dict(normals=normals)
         if visible is not None and sample is None:
             raise RuntimeError("compare: visible= needs sample=density (the ground-truth surface is sampled, then restricted)")
         if exact and sample is None:
@@ -386,7 +390,7 @@ class TSDFVolume:
         if exact or (align is not None and sample is not None):    # the surfaces themselves: cloud_metrics.compare_meshes owns that path
             mesh = lambda x: x.extract_mesh(w_min=w_min) if isinstance(x, TSDFVolume) else x
             return cloud_metrics.compare_meshes(mesh(self), mesh(other), sample, threshold=threshold, max_dist=max_dist, downsample=downsample,
-                                                seed=seed, cell=cell, visible=visible, exact=bool(exact), **({} if align is None else dict(align=align)))
+                                                seed=seed, cell=cell, visible=visible, exact=bool(exact), **({} if align is None else dict(align=align)), **more)
 
         def side(x):
             if sample is not None:
@@ -413,9 +417,10 @@ class TSDFVolume:
             b, n_gt, n_seen = cloud_metrics.restrict_to_visible(gt_mesh, b, visible, threshold, "compare")
             seen = dict(n_gt=n_gt, n_gt_visible=n_seen)
         out = cloud_metrics.compare_clouds(a["xyz"], b["xyz"], threshold=threshold, max_dist=max_dist, downsample=downsample,
-                                           pred_normal=a.get("normal") if "normal" in b else None, gt_normal=b.get("normal") if "normal" in a else None,
+                                           pred_normal=a.get("normal") if "normal" in b or normals is not None else None,
+                                           gt_normal=b.get("normal") if "normal" in a or normals is not None else None,
                                            pred_color=a.get("color") if "color" in b else None, gt_color=b.get("color") if "color" in a else None,
-                                           cell=cell, **({} if align is None else dict(align=align)))
+                                           cell=cell, **({} if align is None else dict(align=align)), **more)
         return out if seen is None else dict(out, **seen)
 
     def reset(self):

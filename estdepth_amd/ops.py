@@ -1625,6 +1625,78 @@ def cloud_cell_centroids(points, attrs, order, segments):
     return out, out_attrs
 
 
+# ---------------------------------------------------------------------------------- k nearest neighbours, normals (csrc/cloud/cloud_knn.hip)
+CLOUD_KNN_MAX = 32              # ESTD_CLOUD_KNN_MAX (include/estd_hip.h)
+
+
+def cloud_knn(query, order, records, cell_start, lo, cell, dims, max_dist, k, stats=False):
+    """The ``k`` nearest targets of every row of ``query`` [M,3] -> (dist [M,k] float32, index [M,k] int32, count [M] int32[, stats [M]
+    int32]) on the query's device, ascending by (d2, index); the slots from ``count`` on hold max_dist and -1.  ``records`` /
+    ``cell_start`` / ``order``: as for cloud_nearest.  The contract is spelled out in include/estd_hip.h (estd_cloud_knn)."""
+    cell, max_dist, dims, k = float(cell), float(max_dist), [int(v) for v in dims], int(k)
+    if _use_torch():
+        dist, index, count, st = T().cloud_knn(query, order, records, cell_start, lo, cell, dims, max_dist, k, bool(stats))
+        return (dist, index, count, st) if stats else (dist, index, count)
+    op = "cloud_knn"
+    _cloud(query, op, "query")
+    _cloud(records, op, "records", cols=4)
+    M, n, dev = query.shape[0], records.shape[0], query.device
+    _ivec(order, op, "order", dev, M)
+    _need(records.device == dev, "cloud_knn: records are on %s but the query on %s" % (records.device, dev))
+    _positive_square(max_dist, op, "max_dist")
+    _count(k, 1, CLOUD_KNN_MAX, op, "k")
+    lo3, dims = _cloud_grid(lo, cell, dims, op, CLOUD_MAX_DIM)
+    cells = dims[0] * dims[1] * dims[2]
+    _need(cells <= CLOUD_MAX_CELLS, "cloud_knn: %d cells, at most %d" % (cells, CLOUD_MAX_CELLS))
+    _ivec(cell_start, op, "cell_start (cells + 1)", dev, cells + 1, torch.int32)
+    with torch.cuda.device(dev):
+        dist, index = torch.empty((M, k), device=dev), torch.empty((M, k), device=dev, dtype=torch.int32)
+        count = torch.empty(M, device=dev, dtype=torch.int32)
+        st = torch.empty(M, device=dev, dtype=torch.int32) if stats else None
+        if M:
+            d = N.CloudKnnDesc()
+            d.M, d.N, d.k = M, n, k
+            d.query, d.order, d.records, d.cell_start = query.data_ptr(), order.data_ptr(), records.data_ptr(), cell_start.data_ptr()
+            d.dist, d.index, d.count = dist.data_ptr(), index.data_ptr(), count.data_ptr()
+            d.stats = st.data_ptr() if stats else None
+            d.cell, d.max_dist = cell, max_dist
+            d.lo[:], d.dims[:] = lo3, dims
+            N.check(N.lib().estd_cloud_knn(ctypes.byref(d), _stream()), "estd_cloud_knn")
+    return (dist, index, count, st) if stats else (dist, index, count)
+
+
+def cloud_normals(points, query, index, count, toward=None, cov=False):
+    """Normals by a plane fit over the neighbours ``index`` [M,k] int32 / ``count`` [M] int32 (cloud_knn's) of ``query`` [M,3] in the
+    cloud ``points`` [N,3] -> (normal [M,3], eig [M,3] ascending, valid [M] uint8, invalid int64 [1], cov float64 [M,6] or None).
+    ``toward``: None, or a device tensor [3] or [M,3] the normals are turned to.  The contract: include/estd_hip.h (estd_cloud_normals)."""
+    if _use_torch():
+        normal, eig, valid, invalid, c = T().cloud_normals(points, query, index, count, toward, bool(cov))
+        return normal, eig, valid, invalid, (c if cov else None)
+    op = "cloud_normals"
+    _cloud(points, op, "points")
+    _cloud(query, op, "query")
+    n, M, dev = points.shape[0], query.shape[0], points.device
+    _need(query.device == dev, "cloud_normals: query is on %s but the points on %s" % (query.device, dev))
+    _need(isinstance(index, torch.Tensor) and index.dim() == 2 and index.dtype == torch.int32 and index.is_contiguous() and index.device == dev
+          and index.shape[0] == M and 1 <= index.shape[1] <= CLOUD_KNN_MAX,
+          "cloud_normals: index must be a contiguous int32 [%d,k] with 1 <= k <= %d on the operator's device" % (M, CLOUD_KNN_MAX))
+    _ivec(count, op, "count", dev, M, torch.int32)
+    per_query = 0
+    if toward is not None:
+        _chk(toward, "toward", op=op, dev=dev)
+        _need(tuple(toward.shape) in ((3,), (M, 3)), "cloud_normals: toward must be [3] or [%d,3], got %s" % (M, list(toward.shape)))
+        per_query = int(toward.dim() == 2)
+    with torch.cuda.device(dev):
+        normal, eig = torch.empty((M, 3), device=dev), torch.empty((M, 3), device=dev)
+        valid, invalid = torch.empty(M, device=dev, dtype=torch.uint8), torch.zeros(1, device=dev, dtype=torch.int64)
+        c = torch.empty((M, 6), device=dev, dtype=torch.float64) if cov else None
+        if M:
+            N.check(N.lib().estd_cloud_normals(_p(points), n, _p(query), M, ctypes.c_void_p(index.data_ptr()), ctypes.c_void_p(count.data_ptr()),
+                                               int(index.shape[1]), _p(toward), per_query, _p(normal), _p(eig), ctypes.c_void_p(valid.data_ptr()),
+                                               ctypes.c_void_p(invalid.data_ptr()), _p(c), _stream()), "estd_cloud_normals")
+    return normal, eig, valid, invalid, c
+
+
 # ---------------------------------------------------------------------------------- mesh simplification (csrc/mesh/mesh_simplify.hip)
 MESH_MAX_FACES = 0x7fffffff // 3      # 3 F stays within int32
 

@@ -673,6 +673,62 @@ int estd_cloud_nearest(const estd_cloud_nearest_desc* desc, estd_stream_t stream
 int estd_cloud_cell_centroids(const float* points, const float* attrs, int C, long long n, const long long* order,
                               const long long* segments, long long K, float* out_points, float* out_attrs, estd_stream_t stream);
 
+/* ---- k nearest neighbours and PCA normals of a point cloud (csrc/cloud/cloud_knn.hip; numpy form: tests/cloud_knn_ref.py) ----
+ * The k nearest targets per query.  THE CONTRACT, defined to the bit and independent of the grid: for query q and EVERY target p, in
+ * fp32, d2 exactly as estd_cloud_nearest forms it:
+ *   dx = qx - px, dy = qy - py, dz = qz - pz;   d2 = fma(dx, dx, fma(dy, dy, dz * dz)).
+ *   A candidate's key is the pair (d2, original index), ordered lexicographically.  The result is the k smallest keys among the
+ *   candidates with d2 <= r2, r2 = max_dist * max_dist (formed once by the entry point in fp32), in ascending order;
+ *   count[q] = how many there are (<= k);   dist[q][j] = the IEEE correctly rounded square root of the j-th d2, index[q][j] its index;
+ *   the slots j >= count[q] hold max_dist and -1.
+ * 1 <= k <= ESTD_CLOUD_KNN_MAX.  Column 0 is, bit for bit, what estd_cloud_nearest returns.  Every element of dist [M][k], index [M][k]
+ * (int32) and count [M] (int32) is written by every call with plain stores and no atomics: two calls give the same bits, and the grid,
+ * the cell edge and `order` change none.  N == 0: nothing is found.  M == 0: no launch.
+ *
+ * records, cell_start, the grid and `order` are estd_cloud_nearest's (an `order` entry outside 0..M-1 is ignored).  The kernel walks
+ * the same rings and stops in front of ring r >= 2 once (1 - 2^-5) ((r - 1) cell)^2 exceeds the d2 of the current k-th key (r2 while
+ * fewer than k candidates have been found); a candidate that ties the k-th d2 is still examined, so the index decides.  `stats` (or
+ * NULL; measurement only): [M] uint32, the candidates whose distance was evaluated.
+ * ESTD_ERR_ARG (before any launch, no device needed): what estd_cloud_nearest refuses, k outside 1..ESTD_CLOUD_KNN_MAX, with M > 0 a
+ * null count.  ESTD_ERR_UNSUPPORTED: M or N >= 2^31. */
+#define ESTD_CLOUD_KNN_MAX 32
+typedef struct estd_cloud_knn_desc {
+    long long M, N;                               /* queries, targets */
+    const float* query;                           /* [M][3] */
+    const long long* order;                       /* [M] or NULL */
+    const float* records;                         /* [N][4], sorted by key */
+    const int* cell_start;                        /* [dims[0] dims[1] dims[2] + 1] */
+    float* dist;                                  /* [M][k] */
+    int* index;                                   /* [M][k] */
+    int* count;                                   /* [M] */
+    unsigned int* stats;                          /* NULL, or [M] */
+    float lo[3];                                  /* host values, copied into the launch arguments */
+    float cell;
+    float max_dist;
+    int dims[3];
+    int k;
+} estd_cloud_knn_desc;
+int estd_cloud_knn(const estd_cloud_knn_desc* desc, estd_stream_t stream);
+
+/* Normals by a plane fit over the neighbours estd_cloud_knn found: points [n][3] is the cloud that index [m][k] (int32) names, query
+ * [m][3] the points the lists belong to (read for the sign only), count [m] (int32, clamped to 0..k) how many entries of a row are used,
+ * in list order.  With c = count[q] and p_i the used neighbours, everything in float64 and uncontracted (numpy reproduces the bits):
+ *   mean_j = (sum_i (double)p_i[j]) / c;   x_i = (double)p_i - mean;   C_ab = sum_i (x_ia * x_ib), each product rounded, then added,
+ *   ab = xx, xy, xz, yy, yz, zz -> cov [m][6] (or NULL; for tests and measurement).  c == 0 or a refused row: zeros.
+ * The eigenproblem of C is solved in float64 inside the kernel by the cyclic Jacobi method (eight sweeps).  eig [m][3]: the eigenvalues
+ * ascending, clamped at 0 from below, rounded to fp32 once.  normal [m][3]: the unit eigenvector of the smallest, rounded to fp32 once.
+ *   valid[q] = 1 iff c >= 3, every used index lies in [0, n), l2 > 0 and (l1 - l0) > 2^-16 l2; otherwise 0, and the normal is zero.
+ *   An index out of range is never an address: the row is invalid, and its eig and cov are zero.  invalid[0] (int64) = the invalid rows,
+ *   one integer atomic per wave (set to 0 by the entry point first).
+ * Sign.  toward (or NULL): 3 floats (toward_per_query == 0) or [m][3] (toward_per_query != 0) on the device; the fp32 normal is flipped
+ *   so that sum_j n_j ((double)toward_j - (double)query_j) >= 0, evaluated in float64 left to right.  Without toward, or when that sum
+ *   is exactly 0, the component of largest magnitude is positive, the lowest axis winning among equal magnitudes.
+ * ESTD_ERR_ARG (before any launch): n or m negative, k outside 1..ESTD_CLOUD_KNN_MAX, with m > 0 a null query, index, count, normal,
+ * eig, valid or invalid, with m > 0 and n > 0 null points.  ESTD_ERR_UNSUPPORTED: n or m >= 2^31.  m == 0: no launch, nothing written. */
+int estd_cloud_normals(const float* points, long long n, const float* query, long long m, const int* index, const int* count, int k,
+                       const float* toward, int toward_per_query, float* normal, float* eig, unsigned char* valid, long long* invalid,
+                       double* cov, estd_stream_t stream);
+
 /* ---- frame-to-model alignment of a depth map (csrc/track/frame_align.hip) -------------------------
  * Projective point-to-plane alignment, KinectFusion's tracking step: ONE live depth map against ONE set of model maps, the depth and
  * normal maps estd_tsdf_raycast writes (normals in world axes towards the cameras, no hit = zeros).  One call forms the Gauss-Newton

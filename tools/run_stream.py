@@ -45,6 +45,10 @@ ground-truth depth.  Needs an MI355X (the model has no CPU path).
     python tools/run_stream.py --synthetic 8 --out /tmp/eval --fuse /tmp/eval/scene.ply --score-3d GT.ply --render-gt-mesh
         # + ground-truth depth from the mesh: the same renders go to <out>/gt_mesh_depth/<stem>.npy, and the predictions are scored against
         # them (errors_vs_gt_mesh, gt_mesh_coverage, errors_on_gt_mesh_covered): the 2D protocol of scenes that ship a mesh and no depth
+    python tools/run_stream.py --synthetic 8 --out /tmp/eval --fuse /tmp/eval/scene.ply --score-3d SCAN.ply --score-align plane --score-normals
+        # + a ground truth that comes WITHOUT normals (a laser scan, a PLY with x y z only): normals are estimated from its own points --
+        # a plane fit over the 16 nearest neighbours within the threshold (cloud_metrics.estimate_normals, csrc/cloud/cloud_knn.hip) -- so
+        # that normal_consistency and the plane metric are there; recon_3d gains normals: k, radius, estimated, invalid_pred, invalid_gt
     python tools/run_stream.py --synthetic 8 --out /tmp/eval --fuse /tmp/eval/scene.ply --track
         # + frame-to-model tracking (estdepth_amd.tracking): from the second fused target on, every target's pose is refined against the
         # volume (TSDFVolume.track: point-to-plane alignment of its depth map with the ray-cast model) before the target is fused -- the
@@ -181,6 +185,12 @@ def parse(argv=None):
     ap.add_argument("--score-align-dist", type=float, nargs="+", default=None, metavar="D", help="with --score-align: partners farther than D "
                     "metres are left out; several decreasing values run as stages (default: 8, 4 and 2 score thresholds)")
     ap.add_argument("--score-align-iters", type=int, default=30, metavar="N", help="with --score-align: Gauss-Newton iterations per stage at most")
+    ap.add_argument("--score-normals", type=int, nargs="?", const=16, default=None, metavar="K", help="with --score-3d GT.ply: a ground truth "
+                    "without normals (a laser scan, a PLY without nx ny nz) gets them estimated from its own points -- a plane fit over the K "
+                    "(default 16) nearest neighbours (cloud_metrics.estimate_normals; csrc/cloud/cloud_knn.hip) -- so that normal_consistency "
+                    "and the plane metric of --score-align are there; recon_3d gains a normals block")
+    ap.add_argument("--score-normals-radius", type=float, default=None, metavar="R", help="with --score-normals: neighbours within R metres "
+                    "(default: --score-threshold)")
     ap.add_argument("--render-gt-mesh", action="store_true", help="with --score-3d GT.ply (a mesh): write its depth at every fused target's pose "
                     "to <out>/gt_mesh_depth and score the predictions against it: errors_vs_gt_mesh, gt_mesh_coverage, errors_on_gt_mesh_covered")
     ap.add_argument("--score-downsample", type=float, default=None, help="with --score-3d: voxel-grid down-sampling of both clouds first (metres)")
@@ -234,6 +244,16 @@ def parse(argv=None):
         ap.error("--score-align-dist takes positive distances in decreasing order")
     if args.score_align_iters < 0:
         ap.error("--score-align-iters must not be negative")
+    if args.score_normals is not None and not isinstance(args.score_3d, str):
+        ap.error("--score-normals needs --score-3d GT.ply (a ground-truth file: the reader's own depth maps give a volume with normals)")
+    if args.score_normals is None and args.score_normals_radius is not None:
+        ap.error("--score-normals-radius needs --score-normals")
+    if args.score_normals is not None and not 3 <= args.score_normals <= 32:
+        ap.error("--score-normals takes 3 to 32 neighbours")
+    if args.score_normals is not None and args.score_exact:
+        ap.error("--score-normals is not available with --score-exact")
+    if args.score_normals_radius is not None and not 0 < args.score_normals_radius < float("inf"):
+        ap.error("--score-normals-radius must be positive and finite")
     if args.score_visible is not None and args.score_sample is None:
         ap.error("--score-visible needs --score-sample DENSITY (the samples of the ground-truth surface are what is restricted)")
     if args.score_visible is not None and args.score_visible < 1:
@@ -448,6 +468,8 @@ def run(args):
         if args.score_align is not None:
             align = dict(align=dict(metric=args.score_align, max_iter=args.score_align_iters,
                                     dist_max=tuple(args.score_align_dist) if args.score_align_dist is not None else None))
+        if args.score_normals is not None:
+            align["normals"] = dict(k=args.score_normals, radius=args.score_normals_radius)
         torch.cuda.synchronize()
         t0 = time.time()
         if args.score_sample is None:

@@ -67,7 +67,14 @@ operators (gathers, einsum, .sum() in float64) on the same device.
 times the mesh simplification (csrc/mesh/mesh_simplify.hip) on that mesh and on the 204 800-triangle height field: the two kernels apart
 and the whole fusion3d.simplify_mesh -- medians of warm calls between device events -- beside the same sums formed with torch operators
 (gathers and index_add_ in float64).  --parent-tree DIR (a built checkout of the parent commit) adds the gate: the default extract_mesh of
-both trees in alternating pairs of fresh processes."""
+both trees in alternating pairs of fresh processes.
+
+    python tools/tsdf_bench.py --cloud-knn [--reps 30] [--parent-tree DIR] [--out profiles/cloud_knn_bench.txt]
+
+times the k-nearest-neighbour search and the PCA normals (csrc/cloud/cloud_knn.hip) at k = 8, 16, 32 on the cloud extracted from that
+volume and on a 200 704-point height field: the two kernels apart, the whole cloud_metrics.estimate_normals and the candidates examined
+per query, beside the same result with torch operators (cdist + topk, gathers, batched linalg.eigh) where the distance matrix fits.
+--parent-tree DIR adds compare_clouds with default arguments in both trees, in alternating pairs of fresh processes."""
 import argparse
 import os
 import sys
@@ -116,8 +123,11 @@ def main():
                     "iteration and the same sums with torch operators; writes profiles/rigid_align_bench.txt unless --out says otherwise")
     ap.add_argument("--mesh-simplify", action="store_true", help="time the mesh simplification (csrc/mesh/mesh_simplify.hip): its kernels, the whole "
                     "simplify_mesh and the same sums with torch operators; writes profiles/mesh_simplify_bench.txt unless --out says otherwise")
+    ap.add_argument("--cloud-knn", action="store_true", help="time the k-nearest-neighbour search and the PCA normals (csrc/cloud/cloud_knn.hip): its "
+                    "kernels, the whole estimate_normals and the same result with torch operators; writes profiles/cloud_knn_bench.txt unless --out "
+                    "says otherwise")
     ap.add_argument("--parent-tree", metavar="DIR", help="with --mesh-simplify: a built checkout of the parent commit; the default extract_mesh of both "
-                    "trees is timed in alternating pairs of fresh processes")
+                    "trees is timed in alternating pairs of fresh processes (with --cloud-knn: the default compare_clouds)")
     ap.add_argument("--color", action="store_true", help="time the colour fuse, the edge colours and the colour render beside the plain figures")
     args = ap.parse_args()
     if args.register:
@@ -126,6 +136,9 @@ def main():
     if args.mesh_simplify:
         args.out = args.out or os.path.join(ROOT, "profiles", "mesh_simplify_bench.txt")
         return simplify_main(args)
+    if args.cloud_knn:
+        args.out = args.out or os.path.join(ROOT, "profiles", "cloud_knn_bench.txt")
+        return knn_main(args)
     if args.raycast:
         return raycast_main(args)
     if args.mesh:
@@ -692,6 +705,139 @@ def simplify_main(args):
         pairs = extract_pairs(os.path.abspath(args.parent_tree), reps)
         lines.append("the gate: the default extract_mesh() of the 256^3 volume, median of %d calls per process, parent commit / this tree in alternating fresh processes:" % reps)
         lines += ["  pair %d: parent %8.4f ms   this tree %8.4f ms" % (n, a, b) for n, (a, b) in enumerate(pairs)]
+        pa, pb = float(np.median([a for a, _ in pairs])), float(np.median([b for _, b in pairs]))
+        spread = max(max(a for a, _ in pairs) - min(a for a, _ in pairs), max(b for _, b in pairs) - min(b for _, b in pairs))
+        lines.append("  medians: parent %.4f ms, this tree %.4f ms (difference %+.4f ms; the pairs spread over %.4f ms)" % (pa, pb, pb - pa, spread))
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        open(args.out, "w").write(text + "\n")
+
+
+COMPARE_SNIPPET = """
+import numpy as np, torch
+from estdepth_amd.cloud_metrics import compare_clouds
+rng = np.random.RandomState(0)
+u = rng.uniform(0.0, 4.0, size=(2, 200000, 2))
+f = lambda p, dz: np.stack([p[:, 0], p[:, 1], 0.2 * np.sin(1.7 * p[:, 0]) * np.cos(1.3 * p[:, 1]) + dz], 1).astype(np.float32)
+a, b = torch.from_numpy(f(u[0], 0.0)).cuda(), torch.from_numpy(f(u[1], 0.01)).cuda()
+ts = []
+for i in range(%d + 3):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(); compare_clouds(a, b, threshold=0.05, downsample=0.02); e1.record(); torch.cuda.synchronize()
+    ts.append(e0.elapsed_time(e1))
+print("COMPARE_MS", float(np.median(ts[3:])))
+"""
+
+
+def compare_pairs(parent, reps, pairs=5):
+    """compare_clouds with default arguments in the parent's tree and in this one, in alternating fresh processes -> [(parent ms, this ms), ...]"""
+    import subprocess
+    out = []
+    for _ in range(pairs):
+        row = []
+        for tree in (parent, ROOT):
+            r = subprocess.run([sys.executable, "-c", COMPARE_SNIPPET % reps], cwd=tree, env=dict(os.environ, PYTHONPATH=tree), capture_output=True,
+                               text=True, timeout=300)
+            if r.returncode != 0:
+                raise RuntimeError("the compare_clouds timing failed in %s (exit %d):\n%s" % (tree, r.returncode, r.stderr[-2000:]))
+            row.append(float(r.stdout.split("COMPARE_MS")[1].split()[0]))
+        out.append(tuple(row))
+    return out
+
+
+def knn_main(args):
+    """--cloud-knn: the search kernel and the normals kernel of csrc/cloud/cloud_knn.hip apart (through the C ABI, on a prepared grid),
+    the whole cloud_metrics.estimate_normals and the candidates examined per query, at k = 8, 16, 32, on the cloud extracted from the
+    256^3 bench volume and on a 200 704-point height field; the yardstick is the same result by torch operators (cdist + topk, gathers,
+    float64 covariances, batched linalg.eigh) on the first 16 384 points, where the distance matrix fits; medians of warm calls."""
+    import ctypes
+    import tsdf_ref as R
+    from estdepth_amd import _native, cloud_metrics, ops
+    from estdepth_amd.fusion3d import TSDFVolume, frustum_volume
+    assert torch.cuda.is_available(), "tools/tsdf_bench.py needs a ROCm device"
+    dev = torch.device("cuda:0")
+    H, W, T, vox, dmin, dmax, dims = 480, 640, 3, 0.03, 0.1, 10.0, (256, 256, 256)
+    reps = min(args.reps, 30)
+    K = R.intrinsics(H, W)
+    poses = R.scene_poses(T, seed=1)
+    depths = torch.from_numpy(np.stack([R.raycast_scene(P, K, H, W) for P in poses]).astype(np.float32)).to(dev)
+    origin = frustum_volume(torch.from_numpy(poses[0]), torch.from_numpy(K), (H, W), dmin, dmax, dims, vox)
+    vol = TSDFVolume(dims, vox, origin, device=dev)
+    vol.integrate(depths, torch.from_numpy(poses), torch.from_numpy(K))
+    cloud_a = vol.extract_points()["xyz"].contiguous()
+    u = np.linspace(0.0, 4.0, 448)
+    gx, gy = np.meshgrid(u, u, indexing="xy")
+    cloud_b = torch.from_numpy(np.stack([gx, gy, 0.2 * np.sin(1.7 * gx) * np.cos(1.3 * gy)], -1).reshape(-1, 3).astype(np.float32)).to(dev)
+    lib = _native.lib()
+    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+    stream = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    lines = ["tsdf_bench --cloud-knn: median of %d warm calls per figure between device events, %s" % (reps, torch.cuda.get_device_name(0)),
+             "nobody has measured these before: the parent commit has nothing comparable, so the times are recorded, not gated"]
+    for name, pts, radius in (("the cloud of the %d x %d x %d volume (voxel %.2f m)" % (dims + (vox,)), cloud_a, 0.12),
+                              ("the 448 x 448 height field over a 4 m square", cloud_b, 0.04)):
+        n = int(pts.shape[0])
+        grid = cloud_metrics.PointGrid(pts, radius)
+        order = torch.sort(ops.cloud_cell_keys(pts, grid.lo, grid.cell, grid.dims), stable=True)[1].contiguous()
+        lines.append("%s: %d points, neighbours within %.2f m, cell %.4f m, %d x %d x %d cells" % ((name, n, radius, grid.cell) + tuple(grid.dims)))
+        for k in (8, 16, 32):
+            dist, index = torch.empty((n, k), device=dev), torch.empty((n, k), device=dev, dtype=torch.int32)
+            count, st = torch.empty(n, device=dev, dtype=torch.int32), torch.empty(n, device=dev, dtype=torch.int32)
+            d = _native.CloudKnnDesc()
+            d.M, d.N, d.k = n, n, k
+            d.query, d.order, d.records, d.cell_start = pts.data_ptr(), order.data_ptr(), grid.records.data_ptr(), grid.cell_start.data_ptr()
+            d.dist, d.index, d.count, d.stats = dist.data_ptr(), index.data_ptr(), count.data_ptr(), None
+            d.cell, d.max_dist = grid.cell, radius
+            d.lo[:], d.dims[:] = grid.lo.tolist(), grid.dims
+
+            def search():
+                assert lib.estd_cloud_knn(ctypes.byref(d), stream()) == 0
+            normal, eig = torch.empty((n, 3), device=dev), torch.empty((n, 3), device=dev)
+            valid, invalid = torch.empty(n, device=dev, dtype=torch.uint8), torch.zeros(1, device=dev, dtype=torch.int64)
+
+            def fit():
+                assert lib.estd_cloud_normals(p(pts), n, p(pts), n, p(index), p(count), k, None, 0, p(normal), p(eig), p(valid), p(invalid), None, stream()) == 0
+            search()
+            fit()
+            whole = lambda: cloud_metrics.estimate_normals(pts, k, radius)
+            out = whole()
+            assert torch.equal(out["normal"], normal) and torch.equal(out["count"], count), "the prepared grid is not estimate_normals'"
+            t_s, t_f, t_all = median_ms(search, reps), median_ms(fit, reps), median_ms(whole, reps)
+            d.stats = st.data_ptr()
+            search()
+            torch.cuda.synchronize()
+            d.stats = None
+            lines.append("  k = %2d: knn_search_kernel %8.4f ms (%.1f M queries/s, %.1f candidates examined per query, %.2f neighbours found)   "
+                         "knn_normals_kernel %8.4f ms   estimate_normals, whole call (finite check, grid build, two sorts, both kernels, curvature, one "
+                         "read-back) %8.4f ms   %d rows not valid" % (k, t_s, n / t_s / 1e3, float(st.double().mean()), float(count.double().mean()), t_f,
+                                                                      t_all, int(invalid.item())))
+        # the yardstick on a subset: the distance matrix of 16 384 points is 1 GiB in fp32
+        m, k = min(n, 16384), 16
+        sub = pts[:m].contiguous()
+
+        def yard():
+            dd, ii = torch.cdist(sub, sub).topk(k, dim=1, largest=False)
+            nb = sub[ii].double()                                             # [m,k,3]
+            inside = (dd <= radius)[..., None].double()
+            cnt = inside.sum(1).clamp(min=1.0)
+            x = (nb - (nb * inside).sum(1, keepdim=True) / cnt[:, None]) * inside
+            w, v = torch.linalg.eigh(x.transpose(1, 2) @ x)
+            return w, v[:, :, 0]
+        sub_out = cloud_metrics.estimate_normals(sub, k, radius)
+        w, v = yard()
+        ok = sub_out["valid"].bool()
+        agree = float(((v[ok].float() * sub_out["normal"][ok]).sum(1).abs() > 1 - 1e-4).double().mean()) if bool(ok.any()) else 1.0
+        t_y, t_k = median_ms(yard, max(reps // 3, 3)), median_ms(lambda: cloud_metrics.estimate_normals(sub, k, radius), reps)
+        lines.append("  yardstick on the first %d points, k = 16: cdist + topk, gathers, float64 covariances, batched linalg.eigh %8.4f ms;  "
+                     "estimate_normals on the same points %8.4f ms (1 / %.1f); %.2f %% of the valid normals agree to 1e-4"
+                     % (m, t_y, t_k, t_y / t_k, 100.0 * agree))
+    lines.append("  not built and not measured: a list kept sorted by insertion, instances by k range, a multi-lane covariance (it changes the order of the sums)")
+    if args.parent_tree:
+        pairs = compare_pairs(os.path.abspath(args.parent_tree), reps)
+        lines.append("the default path: compare_clouds(threshold=0.05, downsample=0.02) on two 200 000-point clouds, median of %d calls per process, "
+                     "parent commit / this tree in alternating fresh processes:" % reps)
+        lines += ["  pair %d: parent %8.4f ms   this tree %8.4f ms" % (i, a, b) for i, (a, b) in enumerate(pairs)]
         pa, pb = float(np.median([a for a, _ in pairs])), float(np.median([b for _, b in pairs]))
         spread = max(max(a for a, _ in pairs) - min(a for a, _ in pairs), max(b for _, b in pairs) - min(b for _, b in pairs))
         lines.append("  medians: parent %.4f ms, this tree %.4f ms (difference %+.4f ms; the pairs spread over %.4f ms)" % (pa, pb, pb - pa, spread))
