@@ -258,6 +258,13 @@ _SIGNATURES = {
     "estd_cloud_knn": (ctypes.c_int, [ctypes.POINTER(CloudKnnDesc), c_stream]),
     "estd_cloud_normals": (ctypes.c_int, [c_float_p, ctypes.c_longlong, c_float_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                           c_float_p, ctypes.c_int, c_float_p, c_float_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_stream]),
+    "estd_cloud_spfh": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_void_p, ctypes.c_void_p, c_stream]),
+    "estd_cloud_fpfh": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int] +
+                        [ctypes.c_void_p] * 5 + [c_stream]),
+    "estd_feature_match": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong] + [ctypes.c_void_p] * 5 + [c_stream]),
+    "estd_ransac_pairs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_double,
+                                         ctypes.c_double] + [ctypes.c_void_p] * 5 + [c_stream]),
     "estd_frame_align_partials": (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int]),
     "estd_frame_align": (ctypes.c_int, [ctypes.POINTER(FrameAlignDesc), c_stream]),
     "estd_tsdf_mesh_vertices": (ctypes.c_int, [c_float_p, c_float_p, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,

@@ -28,7 +28,8 @@ SOURCES = ["conv3d_mfma.hip", "conv3d_wino2.hip", "conv3d_wino3.hip", "conv3d_xo
            "plane_sweep.hip", "est_fusion.hip", "refine2d.hip", "conv1x1.hip", "conv2d_taps.hip", "tsdf.hip", "tsdf_raycast.hip",
            "depth_consistency.hip", "cloud_nn.hip", "cloud/cloud_knn.hip", "track/frame_align.hip", "track/rigid_align.hip",
            "mesh/tsdf_mesh.hip", "mesh/mesh_components.hip",
-           "mesh/mesh_sample.hip", "mesh/mesh_raster.hip", "mesh/mesh_distance.hip", "mesh/mesh_simplify.hip"]
+           "mesh/mesh_sample.hip", "mesh/mesh_raster.hip", "mesh/mesh_distance.hip", "mesh/mesh_simplify.hip",
+           "register/global_register.hip"]
 AB_SOURCES = ["conv3d_wino.hip", "conv3d_split_bf16.hip", "conv2d_wino.hip", "conv2d_split_bf16.hip", "conv3d_wino2x.hip"]
 BUILD_AB = os.environ.get("ESTD_BUILD_AB", "0") == "1"
 if BUILD_AB:

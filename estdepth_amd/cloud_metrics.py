@@ -403,21 +403,40 @@ def _side(dist, index, max_dist, threshold):
                 share=float((dist < threshold).double().mean().item()) if n else 0.0, clamped=int((index < 0).sum().item()))
 
 
-ALIGN_KEYS = ("metric", "dist_max", "max_iter", "init")
+ALIGN_KEYS = ("metric", "dist_max", "max_iter", "init", "voxel", "hypotheses", "seed")
 
 
 def _align(src, src_normal, target, target_normal, align, threshold, op):
     """``align=dict(metric="plane", dist_max=(8, 4, 2) x threshold, max_iter=30, init=None)``: register the predicted points ``src`` to the
-    ground truth (registration.register) -> (T float64 [4,4] or None when the registration did not converge, the ``alignment`` block)"""
+    ground truth (registration.register) -> (T float64 [4,4] or None when the registration did not converge, the ``alignment`` block).
+    ``init="global"`` with ``voxel=V`` (and optionally ``hypotheses``, ``seed``) starts from ``registration.register_global``: the block
+    gains ``global`` = dict(fitness, count, pairs, hypothesis, T_global); a winner refused for its inliers ends the alignment there."""
     from . import registration
     _need(isinstance(align, dict) and all(k in ALIGN_KEYS for k in align), "%s: align must be a dict with keys among %s" % (op, ", ".join(ALIGN_KEYS)))
     _need(isinstance(threshold, (int, float)) and math.isfinite(threshold) and threshold > 0, "%s: threshold must be positive and finite, got %r" % (op, threshold))
     dist = align.get("dist_max")
-    out = registration.register(src, target, init=align.get("init"), metric=align.get("metric", "plane"),
+    init, first = align.get("init"), None
+    is_global = isinstance(init, str)
+    _need(is_global or not any(k in align for k in ("voxel", "hypotheses", "seed")), "%s: align's voxel, hypotheses and seed go with init='global'" % op)
+    if is_global:
+        _need(init == "global" and align.get("voxel") is not None, "%s: align's init must be a [4,4] transform or 'global' with voxel=V, got %r" % (op, init))
+        whole = dict(xyz=target.xyz, faces=target.faces) if isinstance(target, TriangleGrid) else target.target
+        g = registration.register_global(src, whole, align["voxel"], src_normal=src_normal, target_normal=target_normal,
+                                         hypotheses=align.get("hypotheses", 65536), seed=align.get("seed", 0), refine=None)
+        first = dict(fitness=float(g["fitness"]), count=int(g["count"]), pairs=int(g["pairs"]), hypothesis=int(g["hypothesis"]),
+                     T_global=[float(v) for v in g["T_global"].reshape(-1)])
+        init = g["T_global"]
+        if g["reason"] == "inliers":
+            eye = [float(v) for v in np.eye(4).reshape(-1)]
+            return None, {"T": eye, "correction": [0.0, 0.0], "rmse": 0.0, "overlap": 0.0, "iterations": 0, "converged": False, "reason": "inliers",
+                          "global": first}
+    out = registration.register(src, target, init=init, metric=align.get("metric", "plane"),
                                 dist_max=tuple(k * threshold for k in (8.0, 4.0, 2.0)) if dist is None else dist,
                                 max_iter=30 if align.get("max_iter") is None else align["max_iter"], target_normal=target_normal)
     block = dict(T=[float(v) for v in out["T"].reshape(-1)], correction=[float(v) for v in out["correction"]], rmse=float(out["rmse"]),
                  overlap=float(out["overlap"]), iterations=int(out["iterations"]), converged=bool(out["converged"]), reason=out["reason"])
+    if first is not None:
+        block["global"] = first
     return (out["T"] if out["converged"] else None), block
 
 

@@ -172,4 +172,21 @@ __device__ __forceinline__ float lerpf(float a, float b, float f) { return fmaf(
 __device__ __forceinline__ float project_row(const float* m, float x, float y, float z) { return fmaf(z, fmaf(m[0], x, fmaf(m[1], y, m[2])), m[3]); }
 __device__ __forceinline__ bool depth_ok(float d, float z_near) { return d > z_near && d < __builtin_inff(); }          // false for a NaN
 
+// ---- counter-based random numbers (csrc/mesh/mesh_sample.hip, csrc/register/global_register.hip) ----
+// the finaliser of SplitMix64 (Steele, Lea, Flood 2014)
+__device__ __forceinline__ unsigned long long mix64(unsigned long long z)
+{
+    z ^= z >> 30;
+    z *= 0xbf58476d1ce4e5b9ull;
+    z ^= z >> 27;
+    z *= 0x94d049bb133111ebull;
+    z ^= z >> 31;
+    return z;
+}
+// two rounds over (seed, i, stream), all arithmetic modulo 2^64: no state, so element i is a function of (seed, i, stream) alone
+__device__ __forceinline__ unsigned long long h64(unsigned long long seed, unsigned long long i, unsigned long long stream)
+{
+    return mix64(mix64(seed + (i + 1ull) * 0x9e3779b97f4a7c15ull) + (stream + 1ull) * 0xd1b54a32d192ed03ull);
+}
+
 #endif

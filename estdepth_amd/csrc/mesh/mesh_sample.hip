@@ -13,6 +13,7 @@
 //
 // The mixer is counter based and holds no state: sample i is a function of (seed, i) and the mesh alone, whatever the launch shape.
 #include "../estd_common.h"
+#include "../estd_device.h"
 
 namespace {
 
@@ -20,22 +21,7 @@ constexpr int WG = 256;
 
 __device__ __forceinline__ bool in_range(int i, int V) { return (unsigned)i < (unsigned)V; }
 
-// the finaliser of SplitMix64 (Steele, Lea, Flood 2014)
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z)
-{
-    z ^= z >> 30;
-    z *= 0xbf58476d1ce4e5b9ull;
-    z ^= z >> 27;
-    z *= 0x94d049bb133111ebull;
-    z ^= z >> 31;
-    return z;
-}
-
-// two rounds over (seed, i, stream), all arithmetic modulo 2^64; h32 is the upper half
-__device__ __forceinline__ unsigned long long h64(unsigned long long seed, unsigned long long i, unsigned long long stream)
-{
-    return mix64(mix64(seed + (i + 1ull) * 0x9e3779b97f4a7c15ull) + (stream + 1ull) * 0xd1b54a32d192ed03ull);
-}
+// the mixer h64(seed, i, stream): csrc/estd_device.h (two rounds of SplitMix64's finaliser; h32 is the upper half)
 
 __global__ __launch_bounds__(WG) void mesh_face_area_kernel(const float* xyz, int V, const int* faces, long long F, double* area,
                                                             float* face_normal, unsigned long long* invalid)

@@ -983,6 +983,107 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> cloud_normals(const Tensor& p
     return {normal, eig, valid, invalid, c};
 }
 
+// ------------------------------------------------------------------------------------------------ global registration (csrc/register/global_register.hip)
+// a contiguous [rows, cols] (cols == 0: [rows]) tensor of type S on `like`'s device; rows < 0: any number below 2^31
+template <class S>
+static const S* check_table(const Tensor& t, const char* op, const char* name, const Tensor& like, int64_t rows, int64_t cols, const char* type)
+{
+    TORCH_CHECK(t.defined() && t.scalar_type() == c10::CppTypeToScalarType<S>::value && t.is_contiguous() && t.device() == like.device() &&
+                t.dim() == (cols ? 2 : 1) && (rows < 0 ? t.size(0) <= 0x7fffffffLL : t.size(0) == rows) && (!cols || t.size(1) == cols),
+                op, ": ", name, " must be a contiguous ", type, " [", rows < 0 ? "n" : std::to_string(rows).c_str(), cols ? "," : "",
+                cols ? std::to_string(cols).c_str() : "", "] on the operator's device");
+    return t.data_ptr<S>();
+}
+
+struct KnnLists { const float* points; const float* normal; const int32_t* index; const int32_t* count; int64_t n, k; };
+// the cloud, its normals and estd_cloud_knn's lists over it, as the two descriptor operators take them
+static KnnLists check_knn_lists(const Tensor& points, const Tensor& normal, const Tensor& index, const Tensor& count, const char* op)
+{
+    KnnLists a{};
+    a.points = check_cloud(points, op, "points", 3);
+    a.n = points.size(0);
+    a.normal = check_table<float>(normal, op, "normal", points, a.n, 3, "float32");
+    TORCH_CHECK(index.defined() && index.dim() == 2 && index.scalar_type() == at::kInt && index.is_contiguous() && index.device() == points.device() &&
+                index.size(0) == a.n && index.size(1) >= 1 && index.size(1) <= ESTD_CLOUD_KNN_MAX,
+                op, ": index must be a contiguous int32 [", a.n, ",k] with 1 <= k <= ", ESTD_CLOUD_KNN_MAX, " on the operator's device");
+    a.index = index.data_ptr<int32_t>();
+    a.k = index.size(1);
+    a.count = check_table<int32_t>(count, op, "count", points, a.n, 0, "int32");
+    return a;
+}
+
+// points [n,3], normal [n,3], index int32 [n,k], count int32 [n] -> (hist int32 [n,33], pairs int32 [n])
+std::tuple<Tensor, Tensor> cloud_spfh(const Tensor& points, const Tensor& normal, const Tensor& index, const Tensor& count, bool oriented)
+{
+    const char* op = "cloud_spfh";
+    const OpScope scope(points);
+    const KnnLists a = check_knn_lists(points, normal, index, count, op);
+    Tensor hist = at::empty({a.n, ESTD_FPFH_BINS}, points.options().dtype(at::kInt)), pairs = at::empty({a.n}, points.options().dtype(at::kInt));
+    if (a.n)
+        check_status(estd_cloud_spfh(a.points, a.normal, (long long)a.n, a.index, a.count, (int)a.k, oriented ? 1 : 0, hist.data_ptr<int32_t>(),
+                                     pairs.data_ptr<int32_t>(), cur_stream()), "estd_cloud_spfh");
+    return {hist, pairs};
+}
+
+// ... and hist, pairs -> (desc [n,33], valid uint8 [n], invalid int64 [1])
+std::tuple<Tensor, Tensor, Tensor> cloud_fpfh(const Tensor& points, const Tensor& normal, const Tensor& index, const Tensor& count, const Tensor& hist,
+                                              const Tensor& pairs)
+{
+    const char* op = "cloud_fpfh";
+    const OpScope scope(points);
+    const KnnLists a = check_knn_lists(points, normal, index, count, op);
+    const int32_t* h = check_table<int32_t>(hist, op, "hist", points, a.n, ESTD_FPFH_BINS, "int32");
+    const int32_t* pr = check_table<int32_t>(pairs, op, "pairs", points, a.n, 0, "int32");
+    Tensor desc = new_f32({a.n, ESTD_FPFH_BINS}, points), valid = at::empty({a.n}, points.options().dtype(at::kByte));
+    Tensor invalid = at::zeros({1}, points.options().dtype(at::kLong));
+    if (a.n)
+        check_status(estd_cloud_fpfh(a.points, a.normal, (long long)a.n, a.index, a.count, (int)a.k, h, pr, desc.data_ptr<float>(),
+                                     valid.data_ptr<uint8_t>(), reinterpret_cast<long long*>(invalid.data_ptr<int64_t>()), cur_stream()),
+                     "estd_cloud_fpfh");
+    return {desc, valid, invalid};
+}
+
+// a [m,33], b [n,33], masks uint8 [m] / [n] or nothing -> (index int32 [m], d2 [m], d2_second [m])
+std::tuple<Tensor, Tensor, Tensor> feature_match(const Tensor& a, const Tensor& b, const OptTensor& a_valid, const OptTensor& b_valid)
+{
+    const char* op = "feature_match";
+    const OpScope scope(a);
+    fptr(a, "a", true, op);
+    const float* pa = check_table<float>(a, op, "a", a, -1, ESTD_FPFH_BINS, "float32");
+    const float* pb = check_table<float>(b, op, "b", a, -1, ESTD_FPFH_BINS, "float32");
+    const int64_t m = a.size(0), n = b.size(0);
+    const uint8_t* va = (a_valid.has_value() && a_valid->defined()) ? check_table<uint8_t>(*a_valid, op, "a_valid", a, m, 0, "uint8") : nullptr;
+    const uint8_t* vb = (b_valid.has_value() && b_valid->defined()) ? check_table<uint8_t>(*b_valid, op, "b_valid", a, n, 0, "uint8") : nullptr;
+    Tensor index = at::empty({m}, a.options().dtype(at::kInt)), d2 = new_f32({m}, a), second = new_f32({m}, a);
+    if (m)
+        check_status(estd_feature_match(pa, (long long)m, pb, (long long)n, va, vb, index.data_ptr<int32_t>(), d2.data_ptr<float>(),
+                                        second.data_ptr<float>(), cur_stream()), "estd_feature_match");
+    return {index, d2, second};
+}
+
+// P [c,3], Q [c,3] -> (count int32 [H], status uint8 [H], ssq float64 [H], T float64 [H,12], best int64 [1]: the key of the header)
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> ransac_pairs(const Tensor& P, const Tensor& Q, int64_t hypotheses, int64_t seed, double dist_max,
+                                                                double edge_ratio)
+{
+    const char* op = "ransac_pairs";
+    const OpScope scope(P);
+    const float* p = check_cloud(P, op, "P", 3);
+    const int64_t c = P.size(0);
+    const float* q = check_table<float>(Q, op, "Q", P, c, 3, "float32");
+    check_count(hypotheses, 0, 0x7fffffffLL, op, "hypotheses");
+    TORCH_CHECK(std::isfinite(dist_max) && dist_max >= 0, op, ": dist_max must be finite and not negative, got ", dist_max);
+    TORCH_CHECK(edge_ratio >= 0 && edge_ratio <= 1, op, ": edge_ratio must lie in 0 .. 1, got ", edge_ratio);
+    const int64_t H = hypotheses;
+    Tensor count = at::empty({H}, P.options().dtype(at::kInt)), status = at::empty({H}, P.options().dtype(at::kByte));
+    Tensor ssq = at::empty({H}, P.options().dtype(at::kDouble)), T = at::empty({H, 12}, P.options().dtype(at::kDouble));
+    Tensor best = at::zeros({1}, P.options().dtype(at::kLong));
+    if (H)
+        check_status(estd_ransac_pairs(p, q, (long long)c, (long long)H, (unsigned long long)seed, dist_max, edge_ratio, count.data_ptr<int32_t>(),
+                                       status.data_ptr<uint8_t>(), ssq.data_ptr<double>(), T.data_ptr<double>(),
+                                       reinterpret_cast<unsigned long long*>(best.data_ptr<int64_t>()), cur_stream()), "estd_ransac_pairs");
+    return {count, status, ssq, T, best};
+}
+
 // ------------------------------------------------------------------------------------------------ point-to-mesh distance (csrc/mesh/mesh_distance.hip)
 // the grid of the three operators: the rules of check_cloud_grid, at most ESTD_CLOUD_MAX_CELLS cells, big_cells not negative
 static int64_t check_tri_grid(const Tensor& lo, double cell, at::IntArrayRef dims, int64_t big_cells, const char* op)
@@ -1706,6 +1807,10 @@ TORCH_LIBRARY(estdepth_hip, m)
           "int k, bool stats) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("cloud_normals(Tensor points, Tensor query, Tensor index, Tensor count, Tensor? toward, bool cov) -> "
           "(Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("cloud_spfh(Tensor points, Tensor normal, Tensor index, Tensor count, bool oriented) -> (Tensor, Tensor)");
+    m.def("cloud_fpfh(Tensor points, Tensor normal, Tensor index, Tensor count, Tensor hist, Tensor pairs) -> (Tensor, Tensor, Tensor)");
+    m.def("feature_match(Tensor a, Tensor b, Tensor? a_valid, Tensor? b_valid) -> (Tensor, Tensor, Tensor)");
+    m.def("ransac_pairs(Tensor P, Tensor Q, int hypotheses, int seed, float dist_max, float edge_ratio) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("mesh_tri_bins(Tensor xyz, Tensor faces, Tensor lo, float cell, int[] dims, int big_cells) -> (Tensor, Tensor, Tensor)");
     m.def("mesh_tri_fill(Tensor xyz, Tensor faces, Tensor lo, float cell, int[] dims, int big_cells, Tensor offset, int n_pairs) -> "
           "(Tensor, Tensor)");
@@ -1781,6 +1886,10 @@ TORCH_LIBRARY_IMPL(estdepth_hip, CUDA, m)
     m.impl("cloud_cell_centroids", cloud_cell_centroids);
     m.impl("cloud_knn", cloud_knn);
     m.impl("cloud_normals", cloud_normals);
+    m.impl("cloud_spfh", cloud_spfh);
+    m.impl("cloud_fpfh", cloud_fpfh);
+    m.impl("feature_match", feature_match);
+    m.impl("ransac_pairs", ransac_pairs);
     m.impl("mesh_tri_bins", mesh_tri_bins);
     m.impl("mesh_tri_fill", mesh_tri_fill);
     m.impl("mesh_nearest", mesh_nearest);

@@ -10,6 +10,7 @@ channel multiples, 32-bit limits) come back as its status, a RuntimeError as wel
 import collections
 import ctypes
 import math
+import numbers
 import os
 
 import torch
@@ -1695,6 +1696,116 @@ def cloud_normals(points, query, index, count, toward=None, cov=False):
                                                int(index.shape[1]), _p(toward), per_query, _p(normal), _p(eig), ctypes.c_void_p(valid.data_ptr()),
                                                ctypes.c_void_p(invalid.data_ptr()), _p(c), _stream()), "estd_cloud_normals")
     return normal, eig, valid, invalid, c
+
+
+# ---------------------------------------------------------------------------------- global registration (csrc/register/global_register.hip)
+FPFH_BINS = 33                  # ESTD_FPFH_BINS (include/estd_hip.h)
+
+
+def _table(t, op, name, dev, rows, cols, dtype, type_name):
+    """a contiguous [rows, cols] (cols == 0: [rows]) tensor of ``dtype`` on ``dev``; rows None: any number below 2^31.  csrc/torch_ops.cpp:
+    check_table()."""
+    _need(isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous() and t.device == dev and t.dim() == (2 if cols else 1)
+          and (t.shape[0] <= 0x7fffffff if rows is None else t.shape[0] == rows) and (not cols or t.shape[1] == cols),
+          "%s: %s must be a contiguous %s [%s%s] on the operator's device" % (op, name, type_name, "n" if rows is None else rows, ",%d" % cols if cols else ""))
+
+
+def _knn_lists(points, normal, index, count, op):
+    """the cloud, its normals and cloud_knn's lists over it, as the two descriptor operators take them -> (n, k)"""
+    _cloud(points, op, "points")
+    n, dev = points.shape[0], points.device
+    _table(normal, op, "normal", dev, n, 3, torch.float32, "float32")
+    _need(isinstance(index, torch.Tensor) and index.dim() == 2 and index.dtype == torch.int32 and index.is_contiguous() and index.device == dev
+          and index.shape[0] == n and 1 <= index.shape[1] <= CLOUD_KNN_MAX,
+          "%s: index must be a contiguous int32 [%d,k] with 1 <= k <= %d on the operator's device" % (op, n, CLOUD_KNN_MAX))
+    _table(count, op, "count", dev, n, 0, torch.int32, "int32")
+    return n, int(index.shape[1])
+
+
+def cloud_spfh(points, normal, index, count, oriented=True):
+    """Simplified point feature histograms of the cloud ``points`` [n,3] with normals ``normal`` [n,3] (a zero row: none) over the lists
+    ``index`` [n,k] int32 / ``count`` [n] int32 that cloud_knn found for the cloud against itself -> (hist int32 [n,33], pairs int32 [n]).
+    ``oriented=False`` folds the features so that the sign of a normal does not matter.  The contract: include/estd_hip.h (estd_cloud_spfh)."""
+    if _use_torch():
+        return tuple(T().cloud_spfh(points, normal, index, count, bool(oriented)))
+    op = "cloud_spfh"
+    n, k = _knn_lists(points, normal, index, count, op)
+    dev = points.device
+    with torch.cuda.device(dev):
+        hist, pairs = torch.empty((n, FPFH_BINS), device=dev, dtype=torch.int32), torch.empty(n, device=dev, dtype=torch.int32)
+        if n:
+            N.check(N.lib().estd_cloud_spfh(_p(points), _p(normal), n, _p(index), _p(count), k, int(bool(oriented)), _p(hist), _p(pairs), _stream()),
+                    "estd_cloud_spfh")
+    return hist, pairs
+
+
+def cloud_fpfh(points, normal, index, count, hist, pairs):
+    """Fast point feature histograms from cloud_spfh's ``hist`` / ``pairs`` over the same cloud and lists -> (desc [n,33] float32, valid
+    uint8 [n], invalid int64 [1]).  The contract: include/estd_hip.h (estd_cloud_fpfh)."""
+    if _use_torch():
+        return tuple(T().cloud_fpfh(points, normal, index, count, hist, pairs))
+    op = "cloud_fpfh"
+    n, k = _knn_lists(points, normal, index, count, op)
+    dev = points.device
+    _table(hist, op, "hist", dev, n, FPFH_BINS, torch.int32, "int32")
+    _table(pairs, op, "pairs", dev, n, 0, torch.int32, "int32")
+    with torch.cuda.device(dev):
+        desc, valid = torch.empty((n, FPFH_BINS), device=dev), torch.empty(n, device=dev, dtype=torch.uint8)
+        invalid = torch.zeros(1, device=dev, dtype=torch.int64)
+        if n:
+            N.check(N.lib().estd_cloud_fpfh(_p(points), _p(normal), n, _p(index), _p(count), k, _p(hist), _p(pairs), _p(desc), _p(valid), _p(invalid),
+                                            _stream()), "estd_cloud_fpfh")
+    return desc, valid, invalid
+
+
+def feature_match(a, b, a_valid=None, b_valid=None):
+    """Per row of ``a`` [m,33] the nearest and second-nearest row of ``b`` [n,33] (float32; ``a_valid`` / ``b_valid``: uint8 masks or None)
+    by brute force -> (index int32 [m], d2 [m], d2_second [m]); -1 / inf where there is none.  The contract: include/estd_hip.h
+    (estd_feature_match)."""
+    if _use_torch():
+        return tuple(T().feature_match(a, b, a_valid, b_valid))
+    op = "feature_match"
+    _chk(a, "a", op=op)
+    dev = a.device
+    _table(a, op, "a", dev, None, FPFH_BINS, torch.float32, "float32")
+    _table(b, op, "b", dev, None, FPFH_BINS, torch.float32, "float32")
+    m, n = a.shape[0], b.shape[0]
+    if a_valid is not None:
+        _table(a_valid, op, "a_valid", dev, m, 0, torch.uint8, "uint8")
+    if b_valid is not None:
+        _table(b_valid, op, "b_valid", dev, n, 0, torch.uint8, "uint8")
+    with torch.cuda.device(dev):
+        index, d2, second = torch.empty(m, device=dev, dtype=torch.int32), torch.empty(m, device=dev), torch.empty(m, device=dev)
+        if m:
+            N.check(N.lib().estd_feature_match(_p(a), m, _p(b), n, _p(a_valid), _p(b_valid), _p(index), _p(d2), _p(second), _stream()),
+                    "estd_feature_match")
+    return index, d2, second
+
+
+def ransac_pairs(P, Q, hypotheses, seed, dist_max, edge_ratio):
+    """Three-point hypotheses over the correspondences ``P`` [c,3] -> ``Q`` [c,3] -> (count int32 [H], status uint8 [H], ssq float64 [H],
+    T float64 [H,12], best int64 [1]: (count << 32) | (0xffffffff - h) of the winner, 0 when nothing was scored).  The contract:
+    include/estd_hip.h (estd_ransac_pairs)."""
+    for name, v in (("hypotheses", hypotheses), ("seed", seed)):              # no silent truncation of 4.7, no True
+        _need(isinstance(v, numbers.Integral) and not isinstance(v, bool), "ransac_pairs: %s must be an integer, got %r" % (name, v))
+    H, seed, dist_max, edge_ratio = int(hypotheses), int(seed) & 0xffffffffffffffff, float(dist_max), float(edge_ratio)
+    if _use_torch():
+        return tuple(T().ransac_pairs(P, Q, H, seed - (1 << 64) if seed >> 63 else seed, dist_max, edge_ratio))
+    op = "ransac_pairs"
+    _cloud(P, op, "P")
+    c, dev = P.shape[0], P.device
+    _table(Q, op, "Q", dev, c, 3, torch.float32, "float32")
+    _count(H, 0, 0x7fffffff, op, "hypotheses")
+    _need(math.isfinite(dist_max) and dist_max >= 0, "%s: dist_max must be finite and not negative, got %r" % (op, dist_max))
+    _need(0 <= edge_ratio <= 1, "%s: edge_ratio must lie in 0 .. 1, got %r" % (op, edge_ratio))
+    with torch.cuda.device(dev):
+        count, status = torch.empty(H, device=dev, dtype=torch.int32), torch.empty(H, device=dev, dtype=torch.uint8)
+        ssq, Tm = torch.empty(H, device=dev, dtype=torch.float64), torch.empty((H, 12), device=dev, dtype=torch.float64)
+        best = torch.zeros(1, device=dev, dtype=torch.int64)
+        if H:
+            N.check(N.lib().estd_ransac_pairs(_p(P), _p(Q), c, H, seed, dist_max, edge_ratio, _p(count), _p(status), _p(ssq), _p(Tm), _p(best),
+                                              _stream()), "estd_ransac_pairs")
+    return count, status, ssq, Tm, best
 
 
 # ---------------------------------------------------------------------------------- mesh simplification (csrc/mesh/mesh_simplify.hip)

@@ -19,7 +19,15 @@ keeps returning the sums, A and b about the world origin.
 plane metric or a cosine gate), a ``TriangleGrid`` (its face normals are estd_mesh_face_area's, float64 rounded to fp32 once), or a dict:
 with ``faces`` a mesh, else a cloud with ``xyz`` and optionally ``normal``; numpy arrays are moved to the device.  T is [4,4] float64.
 
-Out of scope: a scale (Sim(3)), robust kernels beyond the two gates, global registration from an arbitrary start, colour terms.
+From an arbitrary start, ``register_global`` goes first (csrc/register/global_register.hip): FPFH descriptors of both sides (``fpfh``),
+mutual nearest matches in descriptor space (``match_features``), three-point hypotheses scored over the correspondences
+(``ransac_pairs``), and ``register(init=)`` from the winner.
+
+    out = register_global(src, target, voxel=0.05, refine=dict(metric="plane"))       # out["T"], out["T_global"], out["fitness"]
+
+Out of scope: a scale (Sim(3)), robust kernels beyond the two gates, colour terms (in the metric or the descriptors), graph-based or
+branch-and-bound global methods, hypotheses scored against the whole target instead of the correspondences, orientation propagation
+for estimated normals.
 """
 import math
 
@@ -184,3 +192,159 @@ def register(src, target, init=None, metric="plane", dist_max=0.1, max_iter=30, 
     return dict(T=T, converged=converged, reason=reason, iterations=iterations, trace=trace, correction=(float(np.linalg.norm(D[:3, 3])), angle),
                 rmse=trace[-1]["rmse"] if trace else 0.0, count=trace[-1]["count"] if trace else 0,
                 overlap=last["overlap"] if last is not None else 0.0)
+
+
+# ---------------------------------------------------------------------------------- global registration (csrc/register/global_register.hip)
+STATUS = ("scored", "repeated", "edges", "degenerate")       # estd_ransac_pairs' status 0 .. 3
+MIN_INLIERS = 20
+
+
+def fpfh(points, normal, k=32, radius=None, oriented=True, grid=None):
+    """FPFH descriptors of the cloud ``points`` [N,3] with ``normal`` [N,3] (a zero row: no normal) over each point's ``k`` nearest
+    neighbours within ``radius`` (``PointGrid.knn``, the point itself among them) -> dict(desc [N,33] float32: three groups of 11 bins,
+    each summing to 1; valid uint8 [N]: the point has a normal and at least 3 counted pairs; pairs int32 [N]; invalid: the rows that are
+    not valid, an int; hist int32 [N,33]: the SPFH counts).  ``oriented=False`` folds the angles so that the descriptor does not depend
+    on the sign of any normal -- what ``estimate_normals(toward=None)`` needs.  ``grid``: a ``PointGrid`` of these very points (its
+    ``max_dist`` is then the radius).  The bins use a pseudo-angle instead of atan2 and there is no source/target swap: not PCL's bits.
+    The contract: include/estd_hip.h (estd_cloud_spfh, estd_cloud_fpfh)."""
+    op = "fpfh"
+    _need(isinstance(k, int) and not isinstance(k, bool) and 1 <= k <= ops.CLOUD_KNN_MAX, "%s: k must be an integer in 1 .. %d, got %r" % (op, ops.CLOUD_KNN_MAX, k))
+    _need(grid is not None or radius is not None, "%s: radius (or a grid) must be given" % op)
+    if grid is None:
+        grid = PointGrid(points, _check_max_dist(radius, op))
+    _need(isinstance(grid, PointGrid), "%s: grid must be a PointGrid" % op)
+    points = _check_cloud(points, "points", op, grid.device)
+    normal = _check_cloud(normal, "normal", op, grid.device)
+    _need(grid.n == points.shape[0] == normal.shape[0], "%s: the grid holds %d points, the cloud %d and normal %d rows"
+          % (op, grid.n, points.shape[0], normal.shape[0]))
+    _, index, count = grid.knn(points, k)
+    hist, pairs = ops.cloud_spfh(points, normal, index, count, bool(oriented))
+    desc, valid, invalid = ops.cloud_fpfh(points, normal, index, count, hist, pairs)
+    return dict(desc=desc, valid=valid, pairs=pairs, invalid=int(invalid.item()), hist=hist)
+
+
+def match_features(a, b, a_valid=None, b_valid=None, mutual=True, ratio=None):
+    """Correspondences between the descriptors ``a`` [M,33] and ``b`` [N,33] (estd_feature_match: brute force, nearest and second
+    nearest) -> (pairs int64 [C,2]: rows of a and b, ascending in a; d2 float32 [C]).  ``mutual``: row i of a and row j of b are kept
+    only when each is the other's nearest (the kernel runs both ways, the intersection is taken with torch).  ``ratio``: Lowe's test,
+    kept iff d2 < ratio^2 d2_second (in float64), i.e. the distance ratio is below ``ratio``."""
+    op = "match_features"
+    _need(ratio is None or (isinstance(ratio, (int, float)) and 0 < ratio <= 1), "%s: ratio must lie in (0, 1] or be None, got %r" % (op, ratio))
+    index, d2, second = ops.feature_match(a, b, a_valid, b_valid)
+    keep = index >= 0
+    if mutual:
+        back = ops.feature_match(b, a, b_valid, a_valid)[0]
+        if back.shape[0]:
+            keep &= back[index.clamp_min(0).long()].long() == torch.arange(index.shape[0], device=index.device)
+    if ratio is not None:
+        keep &= d2.double() < float(ratio) * float(ratio) * second.double()
+    rows = torch.nonzero(keep)[:, 0]
+    return torch.stack([rows, index[rows].long()], 1), d2[rows]
+
+
+def ransac_pairs(src_xyz, tgt_xyz, pairs, dist_max, hypotheses=65536, seed=0, edge_ratio=0.9):
+    """The rigid transform most of the correspondences ``pairs`` int64 [C,2] (rows of ``src_xyz`` and ``tgt_xyz``) agree on: every one of
+    ``hypotheses`` three-point samples (a counter-based draw from ``seed``) is tested and scored over all C pairs (estd_ransac_pairs)
+    -> dict(T float64 [4,4] numpy: the winner's transform, the identity when nothing was scored; hypothesis: its number or -1; count:
+    its inliers within ``dist_max``; fitness = count / C; ssq: the sum of their squared residuals; status: dict of tallies -- scored,
+    repeated (an index drawn twice), edges (Open3D's edge-length test with ``edge_ratio``), degenerate).  The winner is the largest
+    count and among equals the smallest hypothesis number: the same from every call."""
+    op = "ransac_pairs"
+    src_xyz = _check_cloud(src_xyz, "src_xyz", op)
+    tgt_xyz = _check_cloud(tgt_xyz, "tgt_xyz", op, src_xyz.device)
+    _need(isinstance(pairs, torch.Tensor) and pairs.dtype == torch.int64 and pairs.dim() == 2 and pairs.shape[1] == 2 and pairs.device == src_xyz.device,
+          "%s: pairs must be int64 [C,2] on the clouds' device" % op)
+    C = int(pairs.shape[0])
+    if C:
+        lo, hi = pairs.amin(0).tolist(), pairs.amax(0).tolist()
+        _need(min(lo) >= 0 and hi[0] < src_xyz.shape[0] and hi[1] < tgt_xyz.shape[0], "%s: pairs names a row outside the clouds" % op)
+    P, Q = src_xyz[pairs[:, 0]].contiguous(), tgt_xyz[pairs[:, 1]].contiguous()
+    count, status, ssq, Tm, best = ops.ransac_pairs(P, Q, hypotheses, seed, dist_max, edge_ratio)
+    key = int(best.item())
+    tally = torch.bincount(status.long(), minlength=4).tolist() if status.shape[0] else [0, 0, 0, 0]
+    out = dict(T=np.eye(4), hypothesis=-1, count=0, fitness=0.0, ssq=0.0, status=dict(zip(STATUS, tally)))
+    if key:
+        h = 0xffffffff - (key & 0xffffffff)
+        out["T"][:3, :4] = Tm[h].cpu().numpy().reshape(3, 4)
+        out.update(hypothesis=h, count=key >> 32, fitness=(key >> 32) / C, ssq=float(ssq[h].item()))
+    return out
+
+
+def _unit_rows(n):
+    """rows scaled to unit length in float64 and rounded once; a zero row stays zero"""
+    d = n.double()
+    length = d.norm(dim=1, keepdim=True)
+    return torch.where(length > 0, d / torch.where(length > 0, length, torch.ones_like(length)), torch.zeros_like(d)).float().contiguous()
+
+
+def _thinned(xyz, normal, voxel, k, normal_radius):
+    """one side of ``register_global``: voxel-thinned points with unit normals -> (points, normals, estimated)"""
+    from .cloud_metrics import estimate_normals, voxel_downsample
+    points, attrs, _ = voxel_downsample(xyz, voxel, normal)
+    if normal is not None:
+        return points, _unit_rows(attrs), False
+    return points, estimate_normals(points, min(k, ops.CLOUD_KNN_MAX), normal_radius)["normal"], True
+
+
+def register_global(src, target, voxel, src_normal=None, target_normal=None, k=32, feature_radius=None, normal_radius=None, dist_max=None,
+                    hypotheses=65536, seed=0, min_count=MIN_INLIERS, refine=None, edge_ratio=0.9, oriented=None):
+    """Registration from an ARBITRARY start: FPFH descriptors on both sides, mutual nearest matches, three-point hypotheses over them,
+    and -- with ``refine`` -- ``register`` from the winner.  ``src`` [N,3]; ``target``: a cloud [M,3], a dict(xyz[, normal]) or a mesh
+    dict(xyz, faces), which is sampled by area first (4 / voxel^2 points per square metre, with its face normals).  Both sides are
+    thinned with ``voxel_downsample(voxel)`` (normals averaged and scaled to unit length); a side without normals gets them from
+    ``estimate_normals(k, normal_radius = 2 voxel)``, and then BOTH sides use the folded descriptor (``oriented=False``), since estimated
+    normals have no side (``oriented=False`` asks for the folded descriptor also where both sides bring normals, for sources whose
+    normals follow different conventions).  ``feature_radius`` = 5 voxel, ``dist_max`` = 1.5 voxel by default.  The stage needs
+    distinctive geometry and overlap: on a plane with two spheres, or against a target most of which the source never saw, no
+    hypothesis gathers ``min_count`` inliers and the winner is refused.
+    ``refine``: None, or a dict of ``register``'s arguments (metric, dist_max -- default (4, 2, 1) voxel --, max_iter, min_count, cos_min,
+    two_sided); the refinement runs on the thinned source against the mesh, or against the thinned target cloud with its normals.
+    -> dict(T float64 [4,4]: src moved by it lies on the target; T_global: the winner of the hypotheses; fitness, count, pairs (the
+    number of correspondences), hypothesis, status; converged, reason; refine: ``register``'s dict or None; clouds: the thinned points
+    and normals of both sides and ``oriented``).  A winner with fewer than ``min_count`` inliers is never applied: T and T_global are the
+    identity, converged False, reason "inliers" -- the rule of ``register``'s refusals.  Without ``refine`` a winner that passes has
+    reason "global"; with it converged and reason are the refinement's."""
+    from . import fusion3d
+    op = "register_global"
+    _need(isinstance(voxel, (int, float)) and math.isfinite(voxel) and voxel > 0, "%s: voxel must be positive and finite, got %r" % (op, voxel))
+    _need(isinstance(min_count, int) and min_count >= 3, "%s: min_count must be an integer of at least 3, got %r" % (op, min_count))
+    _need(refine is None or isinstance(refine, dict), "%s: refine must be None or a dict of register's arguments" % op)
+    voxel = float(voxel)
+    feature_radius = 5.0 * voxel if feature_radius is None else feature_radius
+    normal_radius = 2.0 * voxel if normal_radius is None else normal_radius
+    dist_max = 1.5 * voxel if dist_max is None else dist_max
+    src, src_normal = _src(src, src_normal, op, None)
+    dev, mesh = src.device, None
+    if isinstance(target, dict):
+        _need(target.get("xyz") is not None, "%s: a target dict needs 'xyz'" % op)
+        if target.get("faces") is not None:
+            _need(target_normal is None, "%s: a mesh target takes its normals from its faces; target_normal is for clouds" % op)
+            mesh = dict(zip(("xyz", "faces"), fusion3d._mesh_arg(dict(xyz=fusion3d._on_device(target["xyz"], dev), faces=target["faces"]), op)))
+            sampled = fusion3d.sample_mesh(mesh, density=4.0 / (voxel * voxel), seed=seed)
+            target, target_normal = sampled["xyz"], sampled["normal"]
+        else:
+            if target_normal is None and target.get("normal") is not None:
+                target_normal = fusion3d._on_device(target["normal"], dev)
+            target = fusion3d._on_device(target["xyz"], dev)
+    target, target_normal = _src(target, target_normal, op, dev)
+    sp, sn, s_est = _thinned(src, src_normal, voxel, k, normal_radius)
+    tp, tn, t_est = _thinned(target, target_normal, voxel, k, normal_radius)
+    _need(oriented is None or (isinstance(oriented, bool) and not (oriented and (s_est or t_est))),
+          "%s: oriented must be None or a bool, and True only when both sides bring their normals" % op)
+    oriented = not (s_est or t_est) if oriented is None else oriented
+    fs = fpfh(sp, sn, k, feature_radius, oriented)
+    ft = fpfh(tp, tn, k, feature_radius, oriented)
+    pairs, _ = match_features(fs["desc"], ft["desc"], fs["valid"], ft["valid"], mutual=True)
+    win = ransac_pairs(sp, tp, pairs, dist_max, hypotheses, seed, edge_ratio)
+    out = dict(T=np.eye(4), T_global=np.eye(4), fitness=win["fitness"], count=win["count"], pairs=int(pairs.shape[0]), hypothesis=win["hypothesis"],
+               status=win["status"], converged=False, reason="inliers", refine=None,
+               clouds=dict(src=sp, src_normal=sn, target=tp, target_normal=tn, oriented=oriented))
+    if win["count"] < min_count:
+        return out
+    out.update(T=win["T"].copy(), T_global=win["T"], converged=True, reason="global")
+    if refine is not None:
+        kw = dict(refine)
+        kw.setdefault("dist_max", (4.0 * voxel, 2.0 * voxel, voxel))
+        fine = register(sp, mesh if mesh is not None else dict(xyz=tp, normal=tn), init=win["T"], src_normal=sn, **kw)
+        out.update(T=fine["T"], converged=fine["converged"], reason=fine["reason"], refine=fine)
+    return out

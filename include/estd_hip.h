@@ -729,6 +729,81 @@ int estd_cloud_normals(const float* points, long long n, const float* query, lon
                        const float* toward, int toward_per_query, float* normal, float* eig, unsigned char* valid, long long* invalid,
                        double* cov, estd_stream_t stream);
 
+/* ---- global registration: FPFH descriptors, feature matching, three-point hypotheses (csrc/register/global_register.hip; numpy form:
+ * tests/global_reg_ref.py) ----
+ * Every decision below is taken in float64 operations (or integers) written in a fixed order and NOT contracted: a * b + c is a rounded
+ * product and a rounded sum.  dot(a, b) = (a0 b0 + a1 b1) + a2 b2;  cross(a, b) = (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0);
+ * norm(a) = sqrt(dot(a, a)) with the IEEE square root; a / s divides each component.  No float atomics anywhere: two calls, either
+ * binding and any launch shape give the same bits.
+ *
+ * SPFH (simplified point feature histograms).  points [n][3], normal [n][3] (a row of three zeros: no normal), index [n][k] (int32) and
+ * count [n] (int32, clamped to 0..k) as estd_cloud_knn writes them for the cloud against itself, 1 <= k <= ESTD_CLOUD_KNN_MAX.  For point
+ * s and each used list entry t, in list order, everything widened to float64:
+ *   d = p_t - p_s;  len = norm(d);  dn = d / len;  u = n_s;  phi = dot(u, dn);  v = cross(dn, u);  vl = norm(v);  v = v / vl;
+ *   w = cross(u, v);  alpha = dot(v, n_t);  y = dot(w, n_t);  x = dot(u, n_t).
+ *   The pair is SKIPPED (not counted) when t == s, t lies outside [0, n) (never an address), n_s or n_t is zero, len == 0 or vl == 0.
+ *   oriented != 0:  a = min(max(alpha, -1), 1), f = phi alike;  bin_alpha = min(10, (int)floor((a + 1) * 5.5)), bin_phi alike;
+ *                   q = |x| + |y|;  bin_theta = 5 when q == 0, else with r = y / q and
+ *                   pa = r (x >= 0), 2 - r (x < 0, y >= 0), -2 - r (otherwise):  min(10, (int)floor((pa + 2) * 2.75)).
+ *   oriented == 0:  alpha, phi, y, x are replaced by their absolute values first, and the half ranges are cut into the same 11 bins:
+ *                   bin_alpha = min(10, (int)floor(min(alpha, 1) * 11)), bin_phi alike;  bin_theta = 5 when q == 0, else
+ *                   min(10, (int)floor((y / q) * 11)).  Changing the sign of any normal changes no bit of the result.
+ *   The pseudo-angle pa is a monotone function of atan2(y, x) in [-2, 2]: no transcendental function is evaluated.  PCL bins atan2
+ *   itself and swaps source and target by the angle to the connecting line; neither is done here.
+ *   hist [n][33] (int32): the counts, alpha in 0..10, phi in 11..21, theta in 22..32;  pairs [n] (int32): the pairs counted.
+ * ESTD_ERR_ARG: n negative, k outside 1..ESTD_CLOUD_KNN_MAX, with n > 0 a null pointer.  ESTD_ERR_UNSUPPORTED: n >= 2^31.  n == 0: no
+ * launch. */
+#define ESTD_FPFH_BINS 33
+int estd_cloud_spfh(const float* points, const float* normal, long long n, const int* index, const int* count, int k, int oriented,
+                    int* hist, int* pairs, estd_stream_t stream);
+
+/* FPFH from the SPFH of a cloud: the same points, normal, index, count and k, hist and pairs as estd_cloud_spfh wrote them.  For point
+ * i, acc_b = 0, m = 0, and for each used list entry j in list order that is not i, lies in [0, n), has pairs_j > 0 and
+ * d2 = dot(p_j - p_i, p_j - p_i) > 0 (float64):  wj = 1.0 / ((double)pairs_j * d2);  acc_b = acc_b + (double)hist_j[b] * wj for
+ * every b;  m = m + 1.  Then
+ *   F_b = (pairs_i > 0 ? (double)hist_i[b] / (double)pairs_i : 0.0) + (m > 0 ? acc_b / (double)m : 0.0),
+ * and per group of 11 bins g = (((F_0 + F_1) + F_2) + ... + F_10);  desc [n][33] (fp32) = (float)(F_b / g), or 0 for a group with
+ * g == 0: rounded to fp32 once.  valid [n] (uint8) = 1 iff n_i is not zero and pairs_i >= 3;  invalid[0] (int64) = the rows with
+ * valid == 0, one integer atomic per wave (set to 0 by the entry point first).
+ * ESTD_ERR_ARG / ESTD_ERR_UNSUPPORTED: as for estd_cloud_spfh.  n == 0: no launch, nothing written. */
+int estd_cloud_fpfh(const float* points, const float* normal, long long n, const int* index, const int* count, int k, const int* hist,
+                    const int* pairs, float* desc, unsigned char* valid, long long* invalid, estd_stream_t stream);
+
+/* Nearest and second-nearest descriptor by brute force.  a [m][33], b [n][33] (fp32); a_valid [m], b_valid [n] (uint8, or NULL: every
+ * row).  For row i of a and every row j of b with b_valid[j] != 0, in fp32:
+ *   e_c = a[i][c] - b[j][c];   d2 = e_0 * e_0;   d2 = fma(e_c, e_c, d2) for c = 1 .. 32 in this order.
+ * index [m] (int32) = the j of the smallest key (d2, j), d2 [m] its d2, d2_second [m] the second smallest d2 of the row (equal to d2
+ * when two rows tie).  Without a partner: -1, +inf;  with a single one: d2_second = +inf;  a row with a_valid[i] == 0 gets -1, +inf, +inf.
+ * A d2 that is NaN never wins.  ESTD_ERR_ARG: m or n negative, with m > 0 a null a or output, with m > 0 and n > 0 a null b.
+ * ESTD_ERR_UNSUPPORTED: m or n >= 2^31.  m == 0: no launch. */
+int estd_feature_match(const float* a, long long m, const float* b, long long n, const unsigned char* a_valid, const unsigned char* b_valid,
+                       int* index, float* d2, float* d2_second, estd_stream_t stream);
+
+/* Three-point hypotheses over correspondences (RANSAC's hypothesise-and-verify, every hypothesis evaluated).  P [c][3], Q [c][3] (fp32):
+ * row r pairs a source point with a target point.  Hypothesis h in 0 .. hypotheses - 1 draws c_j = h64(seed, h, j) mod c, j = 0, 1, 2
+ * (the mixer of estd_mesh_sample: two rounds of SplitMix64's finaliser, see there), a, b, c = rows c_0, c_1, c_2, widened to float64.
+ * status [hypotheses] (uint8), tested in this order:
+ *   1  two of c_0, c_1, c_2 are equal;
+ *   2  for one of the edges (a, b), (b, c), (c, a), with lp = norm of the edge in P and lq in Q:  lp < edge_ratio * lq or
+ *      lq < edge_ratio * lp  (Open3D's edge-length checker);
+ *   3  a degenerate frame: on either side norm(b - a) == 0 or norm(cross(e1, c - a)) == 0, or R or t below is not finite;
+ *   0  scored.
+ * The transform, closed form: on each side e1 = (b - a) / norm(b - a);  e3 = cross(e1, c - a) / its norm;  e2 = cross(e3, e1);
+ *   R_ij = (e1q_i e1p_j + e2q_i e2p_j) + e3q_i e3p_j;   cen = ((a + b) + c) / 3.0;   t_i = cenq_i - ((R_i0 cenp_0 + R_i1 cenp_1) + R_i2 cenp_2).
+ * The score over ALL rows r:  m_i = ((R_i0 p_0 + R_i1 p_1) + R_i2 p_2) + t_i;  e = m - q;  r2 = (e_0 e_0 + e_1 e_1) + e_2 e_2;  the row
+ * is an inlier iff r2 <= dist_max * dist_max (the product formed once, in float64).
+ *   count [hypotheses] (int32) = the inliers;  ssq [hypotheses] (float64) = the sum of their r2: lane l of 64 adds its rows l, l + 64, ...
+ *   in ascending order, then the lanes are joined by an exclusive-or butterfly (lane distances 32 .. 1), as estd_rigid_system joins them;
+ *   T [hypotheses][12] (float64) = the rows of [R | t].  A hypothesis with status != 0 gets count 0, ssq 0 and T zero.
+ *   best[0] (uint64, set to 0 by the entry point first) = the largest key  (count << 32) | (0xffffffff - h)  over the scored hypotheses,
+ *   by an integer atomic maximum: the largest count and among equals the smallest h, whatever the schedule; 0 = nothing was scored.
+ * ESTD_ERR_ARG: c or hypotheses negative, dist_max not finite or negative, edge_ratio outside [0, 1], with hypotheses > 0 a null output,
+ * with hypotheses > 0 and c > 0 a null P or Q.  ESTD_ERR_UNSUPPORTED: c or hypotheses >= 2^31.  hypotheses == 0: no launch, nothing
+ * written.  c == 0: every status is 1. */
+int estd_ransac_pairs(const float* P, const float* Q, long long c, long long hypotheses, unsigned long long seed, double dist_max,
+                      double edge_ratio, int* count, unsigned char* status, double* ssq, double* T, unsigned long long* best,
+                      estd_stream_t stream);
+
 /* ---- frame-to-model alignment of a depth map (csrc/track/frame_align.hip) -------------------------
  * Projective point-to-plane alignment, KinectFusion's tracking step: ONE live depth map against ONE set of model maps, the depth and
  * normal maps estd_tsdf_raycast writes (normals in world axes towards the cameras, no hit = zeros).  One call forms the Gauss-Newton

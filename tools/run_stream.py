@@ -185,6 +185,11 @@ def parse(argv=None):
     ap.add_argument("--score-align-dist", type=float, nargs="+", default=None, metavar="D", help="with --score-align: partners farther than D "
                     "metres are left out; several decreasing values run as stages (default: 8, 4 and 2 score thresholds)")
     ap.add_argument("--score-align-iters", type=int, default=30, metavar="N", help="with --score-align: Gauss-Newton iterations per stage at most")
+    ap.add_argument("--score-align-global", type=float, nargs="?", const=-1.0, default=None, metavar="VOXEL", help="with --score-align: start the "
+                    "registration from a GLOBAL one (estdepth_amd.registration.register_global: FPFH descriptors, mutual matches and three-point "
+                    "hypotheses on both sides thinned to VOXEL metres, default 1.5 score thresholds) -- for a ground truth metres and tens of "
+                    "degrees away, where ICP alone refuses or lands on a wrong pose; the alignment block gains global: fitness, count, pairs, "
+                    "hypothesis, T_global")
     ap.add_argument("--score-normals", type=int, nargs="?", const=16, default=None, metavar="K", help="with --score-3d GT.ply: a ground truth "
                     "without normals (a laser scan, a PLY without nx ny nz) gets them estimated from its own points -- a plane fit over the K "
                     "(default 16) nearest neighbours (cloud_metrics.estimate_normals; csrc/cloud/cloud_knn.hip) -- so that normal_consistency "
@@ -244,6 +249,10 @@ def parse(argv=None):
         ap.error("--score-align-dist takes positive distances in decreasing order")
     if args.score_align_iters < 0:
         ap.error("--score-align-iters must not be negative")
+    if args.score_align_global is not None and args.score_align is None:
+        ap.error("--score-align-global needs --score-align")
+    if args.score_align_global is not None and args.score_align_global != -1.0 and not 0 < args.score_align_global < float("inf"):
+        ap.error("--score-align-global takes a positive voxel edge in metres")
     if args.score_normals is not None and not isinstance(args.score_3d, str):
         ap.error("--score-normals needs --score-3d GT.ply (a ground-truth file: the reader's own depth maps give a volume with normals)")
     if args.score_normals is None and args.score_normals_radius is not None:
@@ -468,6 +477,8 @@ def run(args):
         if args.score_align is not None:
             align = dict(align=dict(metric=args.score_align, max_iter=args.score_align_iters,
                                     dist_max=tuple(args.score_align_dist) if args.score_align_dist is not None else None))
+            if args.score_align_global is not None:
+                align["align"].update(init="global", voxel=1.5 * args.score_threshold if args.score_align_global == -1.0 else args.score_align_global)
         if args.score_normals is not None:
             align["normals"] = dict(k=args.score_normals, radius=args.score_normals_radius)
         torch.cuda.synchronize()

@@ -74,7 +74,14 @@ both trees in alternating pairs of fresh processes.
 times the k-nearest-neighbour search and the PCA normals (csrc/cloud/cloud_knn.hip) at k = 8, 16, 32 on the cloud extracted from that
 volume and on a 200 704-point height field: the two kernels apart, the whole cloud_metrics.estimate_normals and the candidates examined
 per query, beside the same result with torch operators (cdist + topk, gathers, batched linalg.eigh) where the distance matrix fits.
---parent-tree DIR adds compare_clouds with default arguments in both trees, in alternating pairs of fresh processes."""
+--parent-tree DIR adds compare_clouds with default arguments in both trees, in alternating pairs of fresh processes.
+
+    python tools/tsdf_bench.py --global-register [--reps 30] [--parent-tree DIR] [--out profiles/global_register_bench.txt]
+
+times the four kernels of the global registration (csrc/register/global_register.hip) and the whole register_global on that volume's
+cloud against itself moved and on the 200 704-point height field thinned to 2 cm and to 5 cm, the matcher beside torch.cdist + argmin on
+the same descriptors and the hypothesis scoring beside the same sums with torch operators.  --parent-tree DIR adds compare_clouds and
+register with default arguments in both trees, in alternating pairs of fresh processes."""
 import argparse
 import os
 import sys
@@ -126,8 +133,12 @@ def main():
     ap.add_argument("--cloud-knn", action="store_true", help="time the k-nearest-neighbour search and the PCA normals (csrc/cloud/cloud_knn.hip): its "
                     "kernels, the whole estimate_normals and the same result with torch operators; writes profiles/cloud_knn_bench.txt unless --out "
                     "says otherwise")
+    ap.add_argument("--global-register", action="store_true", help="time the global registration (csrc/register/global_register.hip): its four "
+                    "kernels, the whole register_global, the matcher beside torch.cdist + argmin and the hypothesis scoring beside torch operators; "
+                    "writes profiles/global_register_bench.txt unless --out says otherwise")
     ap.add_argument("--parent-tree", metavar="DIR", help="with --mesh-simplify: a built checkout of the parent commit; the default extract_mesh of both "
-                    "trees is timed in alternating pairs of fresh processes (with --cloud-knn: the default compare_clouds)")
+                    "trees is timed in alternating pairs of fresh processes (with --cloud-knn: the default compare_clouds; with --global-register: "
+                    "the default compare_clouds and register)")
     ap.add_argument("--color", action="store_true", help="time the colour fuse, the edge colours and the colour render beside the plain figures")
     args = ap.parse_args()
     if args.register:
@@ -139,6 +150,9 @@ def main():
     if args.cloud_knn:
         args.out = args.out or os.path.join(ROOT, "profiles", "cloud_knn_bench.txt")
         return knn_main(args)
+    if args.global_register:
+        args.out = args.out or os.path.join(ROOT, "profiles", "global_register_bench.txt")
+        return global_register_main(args)
     if args.raycast:
         return raycast_main(args)
     if args.mesh:
@@ -731,14 +745,34 @@ print("COMPARE_MS", float(np.median(ts[3:])))
 """
 
 
-def compare_pairs(parent, reps, pairs=5):
-    """compare_clouds with default arguments in the parent's tree and in this one, in alternating fresh processes -> [(parent ms, this ms), ...]"""
+REGISTER_SNIPPET = """
+import numpy as np, torch
+from estdepth_amd.registration import register
+rng = np.random.RandomState(0)
+u = rng.uniform(0.0, 4.0, size=(2, 50000, 2))
+f = lambda p: np.stack([p[:, 0], p[:, 1], 0.2 * np.sin(1.7 * p[:, 0]) * np.cos(1.3 * p[:, 1])], 1)
+g = lambda p: np.stack([-0.34 * np.cos(1.7 * p[:, 0]) * np.cos(1.3 * p[:, 1]), 0.26 * np.sin(1.7 * p[:, 0]) * np.sin(1.3 * p[:, 1]), np.ones(len(p))], 1)
+n = g(u[1]); n /= np.linalg.norm(n, axis=1, keepdims=True)
+a = torch.from_numpy((f(u[0]) + (0.004, -0.003, 0.005)).astype(np.float32)).cuda()
+tgt = dict(xyz=torch.from_numpy(f(u[1]).astype(np.float32)).cuda(), normal=torch.from_numpy(n.astype(np.float32)).cuda())
+ts = []
+for i in range(%d + 3):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(); register(a, tgt); e1.record(); torch.cuda.synchronize()
+    ts.append(e0.elapsed_time(e1))
+print("COMPARE_MS", float(np.median(ts[3:])))
+"""
+
+
+def compare_pairs(parent, reps, pairs=5, snippet=COMPARE_SNIPPET):
+    """compare_clouds with default arguments (or another ``snippet`` that prints COMPARE_MS) in the parent's tree and in this one, in
+    alternating fresh processes -> [(parent ms, this ms), ...]"""
     import subprocess
     out = []
     for _ in range(pairs):
         row = []
         for tree in (parent, ROOT):
-            r = subprocess.run([sys.executable, "-c", COMPARE_SNIPPET % reps], cwd=tree, env=dict(os.environ, PYTHONPATH=tree), capture_output=True,
+            r = subprocess.run([sys.executable, "-c", snippet % reps], cwd=tree, env=dict(os.environ, PYTHONPATH=tree), capture_output=True,
                                text=True, timeout=300)
             if r.returncode != 0:
                 raise RuntimeError("the compare_clouds timing failed in %s (exit %d):\n%s" % (tree, r.returncode, r.stderr[-2000:]))
@@ -841,6 +875,131 @@ def knn_main(args):
         pa, pb = float(np.median([a for a, _ in pairs])), float(np.median([b for _, b in pairs]))
         spread = max(max(a for a, _ in pairs) - min(a for a, _ in pairs), max(b for _, b in pairs) - min(b for _, b in pairs))
         lines.append("  medians: parent %.4f ms, this tree %.4f ms (difference %+.4f ms; the pairs spread over %.4f ms)" % (pa, pb, pb - pa, spread))
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        open(args.out, "w").write(text + "\n")
+
+
+def global_register_main(args):
+    """--global-register: the four kernels of csrc/register/global_register.hip apart (through the C ABI, on prepared lists) and the whole
+    registration.register_global, on the cloud extracted from the 256^3 bench volume against itself moved and on the 200 704-point
+    height field thinned to 2 cm and to 5 cm against itself moved; the matcher beside torch.cdist + argmin on the same descriptors, the
+    hypothesis scoring beside the same sums with torch operators; medians of warm calls.  --parent-tree DIR adds compare_clouds and
+    register with default arguments in both trees, in alternating pairs of fresh processes."""
+    import ctypes
+    import tsdf_ref as R
+    from estdepth_amd import _native, cloud_metrics, registration
+    from estdepth_amd.fusion3d import TSDFVolume, frustum_volume
+    assert torch.cuda.is_available(), "tools/tsdf_bench.py needs a ROCm device"
+    dev = torch.device("cuda:0")
+    H, W, T, vox, dmin, dmax, dims = 480, 640, 3, 0.03, 0.1, 10.0, (256, 256, 256)
+    reps = min(args.reps, 30)
+    K = R.intrinsics(H, W)
+    poses = R.scene_poses(T, seed=1)
+    depths = torch.from_numpy(np.stack([R.raycast_scene(P, K, H, W) for P in poses]).astype(np.float32)).to(dev)
+    origin = frustum_volume(torch.from_numpy(poses[0]), torch.from_numpy(K), (H, W), dmin, dmax, dims, vox)
+    vol = TSDFVolume(dims, vox, origin, device=dev)
+    vol.integrate(depths, torch.from_numpy(poses), torch.from_numpy(K))
+    cloud_a = vol.extract_points()["xyz"].contiguous()
+    u = np.linspace(0.0, 4.0, 448)
+    gx, gy = np.meshgrid(u, u, indexing="xy")
+    cloud_b = torch.from_numpy(np.stack([gx, gy, 0.2 * np.sin(1.7 * gx) * np.cos(1.3 * gy)], -1).reshape(-1, 3).astype(np.float32)).to(dev)
+    M = np.eye(4)                                                             # the motion of the second side: 100 degrees about a skew axis, 2 m
+    ax, th = np.array([1.0, 2.0, 3.0]) / np.sqrt(14.0), np.radians(100.0)
+    Kx = np.array([[0, -ax[2], ax[1]], [ax[2], 0, -ax[0]], [-ax[1], ax[0], 0]])
+    M[:3, :3], M[:3, 3] = np.eye(3) + np.sin(th) * Kx + (1 - np.cos(th)) * (Kx @ Kx), (1.0, -1.0, 1.5)
+    lib = _native.lib()
+    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+    stream = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    hyp, k = 65536, 32
+    lines = ["tsdf_bench --global-register: median of %d warm calls per figure between device events, %s" % (reps, torch.cuda.get_device_name(0)),
+             "first measurements: the parent commit has nothing comparable, so the times are recorded, not gated; k = %d, %d hypotheses" % (k, hyp)]
+    for name, raw, voxel in (("the cloud of the %d x %d x %d volume (voxel %.2f m), thinned to 6 cm" % (dims + (vox,)), cloud_a, 0.06),
+                             ("the 448 x 448 height field over a 4 m square, thinned to 5 cm", cloud_b, 0.05),
+                             ("the 448 x 448 height field over a 4 m square, thinned to 2 cm", cloud_b, 0.02)):
+        moved = registration.transform(raw, M)
+        sides = []
+        for pts_raw in (raw, moved):
+            pts = cloud_metrics.voxel_downsample(pts_raw, voxel)[0].contiguous()
+            nrm = cloud_metrics.estimate_normals(pts, 16, 2.0 * voxel)["normal"].contiguous()
+            _, index, count = cloud_metrics.PointGrid(pts, 5.0 * voxel).knn(pts, k)
+            sides.append((pts, nrm, index.contiguous(), count.contiguous()))
+        pts, nrm, index, count = sides[0]
+        n = int(pts.shape[0])
+        hist, pairs_n = torch.empty((n, 33), device=dev, dtype=torch.int32), torch.empty(n, device=dev, dtype=torch.int32)
+        desc, valid = torch.empty((n, 33), device=dev), torch.empty(n, device=dev, dtype=torch.uint8)
+        invalid = torch.zeros(1, device=dev, dtype=torch.int64)
+
+        def spfh():
+            assert lib.estd_cloud_spfh(p(pts), p(nrm), n, p(index), p(count), k, 0, p(hist), p(pairs_n), stream()) == 0
+
+        def fpfh():
+            assert lib.estd_cloud_fpfh(p(pts), p(nrm), n, p(index), p(count), k, p(hist), p(pairs_n), p(desc), p(valid), p(invalid), stream()) == 0
+        spfh()
+        fpfh()
+        fa = registration.fpfh(pts, nrm, k, 5.0 * voxel, oriented=False)
+        fb = registration.fpfh(sides[1][0], sides[1][1], k, 5.0 * voxel, oriented=False)
+        assert torch.equal(fa["desc"], desc), "the prepared lists are not fpfh's"
+        a, b, m = fa["desc"], fb["desc"], int(fb["desc"].shape[0])
+        mi, md, ms2 = torch.empty(n, device=dev, dtype=torch.int32), torch.empty(n, device=dev), torch.empty(n, device=dev)
+
+        def match():
+            assert lib.estd_feature_match(p(a), n, p(b), m, None, None, p(mi), p(md), p(ms2), stream()) == 0
+
+        def yard_match():
+            return torch.cdist(a, b).argmin(1)
+        match()
+        agree = float((yard_match() == mi.long()).double().mean())
+        pr, _ = registration.match_features(a, b, fa["valid"], fb["valid"])
+        C = int(pr.shape[0])
+        P, Q = pts[pr[:, 0]].contiguous(), sides[1][0][pr[:, 1]].contiguous()
+        dist_max = 1.5 * voxel
+        cnt, status = torch.empty(hyp, device=dev, dtype=torch.int32), torch.empty(hyp, device=dev, dtype=torch.uint8)
+        ssq, Tm = torch.empty(hyp, device=dev, dtype=torch.float64), torch.empty((hyp, 12), device=dev, dtype=torch.float64)
+        best = torch.zeros(1, device=dev, dtype=torch.int64)
+
+        def ransac():
+            assert lib.estd_ransac_pairs(p(P), p(Q), C, hyp, 0, dist_max, 0.9, p(cnt), p(status), p(ssq), p(Tm), p(best), stream()) == 0
+        ransac()
+        torch.cuda.synchronize()
+        scored = torch.nonzero(status == 0)[:, 0][:4096]
+        Ts = Tm[scored].reshape(-1, 3, 4)
+        P64, Q64 = P.double(), Q.double()
+
+        def yard_score():                                                     # the same sums for the first 4 096 scored hypotheses
+            e = torch.einsum("hij,cj->hci", Ts[:, :, :3], P64) + Ts[:, None, :, 3] - Q64[None]
+            r2 = (e * e).sum(-1)
+            inl = r2 <= dist_max * dist_max
+            return inl.sum(1), (r2 * inl).sum(1)
+        same = bool(torch.equal(yard_score()[0].int(), cnt[scored])) if scored.numel() else True
+        whole = lambda: registration.register_global(raw, moved, voxel, hypotheses=hyp)
+        out = whole()
+        t = {f.__name__: median_ms(f, reps) for f in (spfh, fpfh, match, ransac)}
+        t_ym, t_ys, t_all = median_ms(yard_match, max(reps // 3, 3)), median_ms(yard_score, max(reps // 3, 3)) if scored.numel() else 0.0, median_ms(whole, max(reps // 3, 3))
+        n_scored = int((status == 0).sum().item())
+        lines += ["%s: %d and %d points, normals estimated (k = 16), folded descriptors" % (name, n, m),
+                  "  greg_spfh_kernel<false> %8.4f ms   greg_fpfh_kernel %8.4f ms   (%.1f M points/s together)" % (t["spfh"], t["fpfh"], n / (t["spfh"] + t["fpfh"]) / 1e3),
+                  "  greg_match_kernel %d x %d  %8.4f ms (%.1f G fma/s)   yardstick torch.cdist + argmin %8.4f ms (kernel / yardstick = %.2f; %.2f %% of the "
+                  "rows name the same partner)" % (n, m, t["match"], 33.0 * n * m / t["match"] / 1e6, t_ym, t["match"] / t_ym, 100.0 * agree),
+                  "  greg_ransac_kernel, %d correspondences, %d of %d hypotheses scored  %8.4f ms (%.1f G rows/s)   yardstick: the sums of the first %d "
+                  "scored hypotheses with torch operators (einsum, float64) %8.4f ms, the same counts: %s (per scored hypothesis: kernel %.3f us, yardstick %.3f us)"
+                  % (C, n_scored, hyp, t["ransac"], n_scored * C / max(t["ransac"], 1e-9) / 1e6, int(scored.numel()), t_ys, same,
+                     1e3 * t["ransac"] / max(n_scored, 1), 1e3 * t_ys / max(int(scored.numel()), 1)),
+                  "  register_global, whole call (two thinnings, two normal fits, four searches, descriptors, two matches, hypotheses, read-backs) "
+                  "%8.4f ms: %d pairs, winner %d with %d inliers (%s)" % (t_all, out["pairs"], out["hypothesis"], out["count"], out["reason"])]
+    lines.append("  not built and not measured: a matcher whose workgroups split b between them (it launches ceil(M / 64) workgroups, each over all of "
+                 "b), FPFH with fewer accumulators per lane, hypotheses scored in fp32")
+    if args.parent_tree:
+        for what, snippet in (("compare_clouds(threshold=0.05, downsample=0.02) on two 200 000-point clouds", COMPARE_SNIPPET),
+                              ("register() with default arguments, 50 000 points onto 50 000 with normals", REGISTER_SNIPPET)):
+            pairs = compare_pairs(os.path.abspath(args.parent_tree), reps, snippet=snippet)
+            lines.append("the default path: %s, median of %d calls per process, parent commit / this tree in alternating fresh processes:" % (what, reps))
+            lines += ["  pair %d: parent %8.4f ms   this tree %8.4f ms" % (i, x, y) for i, (x, y) in enumerate(pairs)]
+            pa, pb = float(np.median([x for x, _ in pairs])), float(np.median([y for _, y in pairs]))
+            spread = max(max(x for x, _ in pairs) - min(x for x, _ in pairs), max(y for _, y in pairs) - min(y for _, y in pairs))
+            lines.append("  medians: parent %.4f ms, this tree %.4f ms (difference %+.4f ms; the pairs spread over %.4f ms)" % (pa, pb, pb - pa, spread))
     text = "\n".join(lines)
     print(text)
     if args.out:
