@@ -98,6 +98,19 @@ def _check_max_dist(max_dist, op):
     return float(max_dist)
 
 
+def _cell_starts(sorted_keys, dims):
+    """the dense cell table of a grid: cell_start[key] = how many of the (ascending) ``sorted_keys`` are smaller than ``key``, int32"""
+    cells = dims[0] * dims[1] * dims[2]
+    return torch.searchsorted(sorted_keys, torch.arange(cells + 1, device=sorted_keys.device, dtype=torch.int64), out_int32=True).contiguous()
+
+
+def _query_order(grid, points, gridded):
+    """the order a search takes its queries in: by their own cell key in ``grid`` (stable), or as they come when nothing is ``gridded``"""
+    if gridded:
+        return torch.sort(ops.cloud_cell_keys(points, grid.lo, grid.cell, grid.dims), stable=True)[1]
+    return torch.arange(points.shape[0], device=grid.device, dtype=torch.int64)
+
+
 class PointGrid:
     """The search structure of one target cloud: the stable sort by cell key, the dense cell table and the 16-byte records, built once.
     ``target`` [N,3] float32 on a ROCm device with finite coordinates (N = 0: nothing is ever found); ``cell``: the cell edge, None for the
@@ -116,10 +129,9 @@ class PointGrid:
         lo, hi = target.amin(0).cpu(), target.amax(0).cpu()
         self.lo, self.hi = lo.contiguous(), hi.contiguous()                                   # the cloud's box, host values
         self.cell, self.dims = grid_plan(lo.tolist(), hi.tolist(), self.n, self.max_dist, cell)
-        cells = self.dims[0] * self.dims[1] * self.dims[2]
         keys = ops.cloud_cell_keys(target, self.lo, self.cell, self.dims)
         sorted_keys, order = torch.sort(keys, stable=True)
-        self.cell_start = torch.searchsorted(sorted_keys, torch.arange(cells + 1, device=self.device, dtype=torch.int64), out_int32=True).contiguous()
+        self.cell_start = _cell_starts(sorted_keys, self.dims)
         rec = torch.empty((self.n, 4), device=self.device, dtype=torch.int32)    # filled as integers: the bits of the coordinates and the original index
         rec[:, :3] = target[order].view(torch.int32)
         rec[:, 3] = order.to(torch.int32)
@@ -133,10 +145,7 @@ class PointGrid:
         if points.shape[0] == 0:
             out = (torch.empty(0, device=self.device), torch.empty(0, device=self.device, dtype=torch.int64))
             return out + (torch.empty(0, device=self.device, dtype=torch.int32),) if stats else out
-        if self.n:
-            order = torch.sort(ops.cloud_cell_keys(points, self.lo, self.cell, self.dims), stable=True)[1]
-        else:
-            order = torch.arange(points.shape[0], device=self.device, dtype=torch.int64)
+        order = _query_order(self, points, self.n > 0)
         return ops.cloud_nearest(points, order, self.records, self.cell_start, self.lo, self.cell, self.dims, self.max_dist, stats=stats)
 
     def knn(self, points, k, stats=False):
@@ -150,10 +159,7 @@ class PointGrid:
             out = (torch.empty((0, k), device=self.device), torch.empty((0, k), device=self.device, dtype=torch.int32),
                    torch.empty(0, device=self.device, dtype=torch.int32))
             return out + (torch.empty(0, device=self.device, dtype=torch.int32),) if stats else out
-        if self.n:
-            order = torch.sort(ops.cloud_cell_keys(points, self.lo, self.cell, self.dims), stable=True)[1]
-        else:
-            order = torch.arange(points.shape[0], device=self.device, dtype=torch.int64)
+        order = _query_order(self, points, self.n > 0)
         return ops.cloud_knn(points, order, self.records, self.cell_start, self.lo, self.cell, self.dims, self.max_dist, k, stats=stats)
 
 
@@ -329,8 +335,7 @@ class TriangleGrid:
         if pairs:
             keys, pair_face = ops.mesh_tri_fill(xyz, faces, self.lo, self.cell, self.dims, big, (cum - count).contiguous(), pairs)
             sorted_keys, order = torch.sort(keys, stable=True)
-            cells = self.dims[0] * self.dims[1] * self.dims[2]
-            self.cell_start = torch.searchsorted(sorted_keys, torch.arange(cells + 1, device=dev, dtype=torch.int64), out_int32=True).contiguous()
+            self.cell_start = _cell_starts(sorted_keys, self.dims)
             self.records = self._records(pair_face[order].long())
         else:
             self.cell, self.dims = float(np.float32(self.max_dist)), (1, 1, 1)                    # no grid: phase B does not run
@@ -353,10 +358,7 @@ class TriangleGrid:
         if M == 0 or self.faces_valid == 0:                       # nothing to search: no launch
             out = (torch.full((M,), float(np.float32(self.max_dist)), device=self.device), torch.full((M,), -1, device=self.device, dtype=torch.int32))
             return out + ((torch.zeros((M, 2), device=self.device),) if bary else ()) + ((torch.zeros((M, 3), device=self.device),) if closest else ())
-        if self.n_pairs:
-            order = torch.sort(ops.cloud_cell_keys(points, self.lo, self.cell, self.dims), stable=True)[1]
-        else:
-            order = torch.arange(M, device=self.device, dtype=torch.int64)
+        order = _query_order(self, points, self.n_pairs > 0)
         dist, face, b, c = ops.mesh_nearest(points, order, self.big_records, self.records, self.cell_start, self.lo, self.cell, self.dims,
                                             self.max_dist, bary=bary, closest=closest)
         return (dist, face) + ((b,) if bary else ()) + ((c,) if closest else ())

@@ -8,12 +8,11 @@
 // there are.  dist = sqrt(d2) (IEEE), slots from count on hold max_dist and -1.  A set of smallest keys and then a sort: the result does
 // not depend on the order candidates are met in, so the grid, the cell edge and the order of the queries change no bit.
 //
-// Structure: PointGrid's records, cell table and cell-sorted query order as csrc/cloud_nn.hip defines them, one lane per query and the
-// same ring walk.  Only the stopping rule differs: the search stops in front of ring r >= 2 when  LB_SCALE * ((r - 1) * cell)^2 > kth,
-// kth = the d2 of the current k-th key once the list is full and r2 before that.  The argument of cloud_nn.hip's header carries over with
-// "best" read as "the k-th": a target in ring r or beyond is at least (r - 1 - 2^-11) cell edges away, so once the bound exceeds the d2
-// of the k-th key no such target can enter the list or tie its last place (strict comparison: a candidate that ties the k-th d2 is
-// still examined, and the index decides).  While the list is not full every candidate within r2 enters, so the bound is r2.
+// Structure: PointGrid's records, cell table and cell-sorted query order as csrc/cloud_nn.hip defines them (a candidate is one target
+// point in one cell), one lane per query, and the ring walk of csrc/estd_device.h (grid_ring_walk, with the argument why no ring is
+// skipped too early).  bound() returns kth = the d2 of the current k-th key once the list is full and r2 before that: while the list is
+// not full every candidate within r2 enters, and afterwards a candidate further away than the k-th key can neither enter the list nor tie
+// its last place.  A candidate that ties the k-th d2 is still examined (the walk's comparison is strict), and the index decides.
 //
 // The list: 64-bit keys  bits(d2) << 32 | index  (d2 is not negative and never NaN for finite inputs, so unsigned integer order is the
 // pair's order; csrc/mesh/mesh_raster.hip's trick) in LDS, slot-major: keys[slot][lane], so the 64 lanes of the wave touch consecutive
@@ -34,12 +33,12 @@
 // sum_j n_j ((double)v_j - (double)q_j) >= 0 in float64; without it, or when that sum is exactly 0, the component of largest magnitude
 // is positive (the lowest axis among equal magnitudes).  The invalid rows are counted with one integer atomic per wave.
 #include "estd_common.h"
+#include "estd_device.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr float LB_SCALE = 0.96875f;            // 1 - 2^-5, as in cloud_nn.hip
 constexpr int KNN_WAVE = 64;                    // one wave per workgroup: a lane owns a column of the list
 constexpr int JACOBI_SWEEPS = 8;                // quadratic convergence: a 3 x 3 matrix is diagonal to float64 after 5 or 6
 
@@ -53,17 +52,9 @@ struct KnnParams {
     int* count;
     unsigned int* stats;
     int M, N, k;
-    int dims[3];
-    float lo[3];
-    float cell, inv_cell, max_dist, r2;
+    estd_grid grid;
+    float max_dist, r2;
 };
-
-// the clamped cell coordinate of cloud_nn.hip
-__device__ inline int knn_cell_coord(float p, float lo, float inv_cell, int dim)
-{
-    const float t = floorf((p - lo) * inv_cell);
-    return (int)fminf(fmaxf(t, 0.f), (float)(dim - 1));
-}
 
 template <bool STATS>
 __global__ __launch_bounds__(KNN_WAVE) void knn_search_kernel(const KnnParams p)
@@ -84,12 +75,6 @@ __global__ __launch_bounds__(KNN_WAVE) void knn_search_kernel(const KnnParams p)
     unsigned int examined = 0;
 
     if (p.N > 0) {
-        const int X = p.dims[0], Y = p.dims[1], Z = p.dims[2];
-        const int cx = knn_cell_coord(qx, p.lo[0], p.inv_cell, X);
-        const int cy = knn_cell_coord(qy, p.lo[1], p.inv_cell, Y);
-        const int cz = knn_cell_coord(qz, p.lo[2], p.inv_cell, Z);
-        const int r_max = max(max(max(cx, X - 1 - cx), max(cy, Y - 1 - cy)), max(cz, Z - 1 - cz));      // the last ring that meets the grid
-
         // the largest key of the column and its slot, once the list is full
         auto rescan = [&]() {
             unsigned long long w = col[0];
@@ -123,29 +108,7 @@ __global__ __launch_bounds__(KNN_WAVE) void knn_search_kernel(const KnnParams p)
             }
         };
 
-#pragma unroll 1
-        for (int r = 0; r <= r_max; ++r) {
-            if (r >= 2) {
-                const float reach = (float)(r - 1) * p.cell;
-                if (reach * reach * LB_SCALE > kth) break;
-            }
-            const int z0 = max(cz - r, 0), z1 = min(cz + r, Z - 1), y0 = max(cy - r, 0), y1 = min(cy + r, Y - 1);
-            const int xa = cx - r, xb = cx + r;
-#pragma unroll 1
-            for (int z = z0; z <= z1; ++z) {
-                const bool z_face = z - cz == r || cz - z == r;
-#pragma unroll 1
-                for (int y = y0; y <= y1; ++y) {
-                    const int row = (z * Y + y) * X;
-                    if (z_face || y - cy == r || cy - y == r) {
-                        scan(row + max(xa, 0), row + min(xb, X - 1));
-                    } else {
-                        if (xa >= 0) scan(row + xa, row + xa);
-                        if (xb <= X - 1) scan(row + xb, row + xb);
-                    }
-                }
-            }
-        }
+        grid_ring_walk(p.grid, qx, qy, qz, [&]() { return kth; }, scan);
     }
 
     // ascending: selection sort of the lane's column, each place written out as it is settled
@@ -290,19 +253,6 @@ __global__ __launch_bounds__(256) void knn_normals_kernel(const NormalsParams p)
     if (b != 0ull && (threadIdx.x & 63u) == 0u) atomicAdd(p.invalid, (unsigned long long)__popcll(b));
 }
 
-inline bool knn_finite(float v) { return v - v == 0.f; }
-
-// the rules of cloud_nn.hip's grid_ok: lo finite, cell and its fp32 reciprocal positive and finite, 1 <= dims_j <= max_dim
-inline bool knn_grid_ok(const float* lo3, float cell, const int* dims3, int max_dim)
-{
-    if (!knn_finite(cell) || !(cell > 0.f)) return false;
-    const float inv = 1.0f / cell;
-    if (!knn_finite(inv) || !(inv > 0.f)) return false;
-    for (int j = 0; j < 3; ++j)
-        if (!knn_finite(lo3[j]) || dims3[j] < 1 || dims3[j] > max_dim) return false;
-    return true;
-}
-
 }  // namespace
 
 extern "C" int estd_cloud_knn(const estd_cloud_knn_desc* d, estd_stream_t s)
@@ -310,27 +260,15 @@ extern "C" int estd_cloud_knn(const estd_cloud_knn_desc* d, estd_stream_t s)
     if (!d) return ESTD_ERR_ARG;
     if (d->M < 0 || d->N < 0) return ESTD_ERR_ARG;
     if (d->k < 1 || d->k > ESTD_CLOUD_KNN_MAX) return ESTD_ERR_ARG;
-    if (!knn_finite(d->max_dist) || !(d->max_dist > 0.f)) return ESTD_ERR_ARG;
-    const float r2 = d->max_dist * d->max_dist;                               // formed once, here
-    if (!knn_finite(r2)) return ESTD_ERR_ARG;                                 // a max_dist whose square leaves fp32
-    if (d->N > 0) {
-        if (!knn_grid_ok(d->lo, d->cell, d->dims, ESTD_CLOUD_MAX_DIM)) return ESTD_ERR_ARG;
-        if ((long long)d->dims[0] * d->dims[1] * d->dims[2] > ESTD_CLOUD_MAX_CELLS) return ESTD_ERR_ARG;
-        if (!d->records || !d->cell_start) return ESTD_ERR_ARG;
-        if (reinterpret_cast<unsigned long long>(d->records) & 15ull) return ESTD_ERR_ARG;      // a record is one 16-byte load
-    }
+    KnnParams p{};
+    if (estd_search_args(d->max_dist, d->N, d->lo, d->cell, d->dims, d->records, d->cell_start, &p.grid, &p.r2) != ESTD_OK) return ESTD_ERR_ARG;
     if (d->M > 0x7fffffffLL || d->N > 0x7fffffffLL) return ESTD_ERR_UNSUPPORTED;
     if (d->M == 0) return ESTD_OK;
     if (!d->query || !d->dist || !d->index || !d->count) return ESTD_ERR_ARG;
-    KnnParams p{};
     p.query = d->query; p.order = d->order; p.records = reinterpret_cast<const float4*>(d->records); p.cell_start = d->cell_start;
     p.dist = d->dist; p.index = d->index; p.count = d->count; p.stats = d->stats;
     p.M = (int)d->M; p.N = (int)d->N; p.k = d->k;
-    p.max_dist = d->max_dist; p.r2 = r2;
-    if (d->N > 0) {
-        p.cell = d->cell; p.inv_cell = 1.0f / d->cell;
-        for (int j = 0; j < 3; ++j) { p.lo[j] = d->lo[j]; p.dims[j] = d->dims[j]; }
-    }
+    p.max_dist = d->max_dist;
     const dim3 grid((unsigned)estd_ceil_div(d->M, KNN_WAVE));
     if (d->stats) hipLaunchKernelGGL(knn_search_kernel<true>, grid, dim3(KNN_WAVE), 0, estd_stream(s), p);
     else hipLaunchKernelGGL(knn_search_kernel<false>, grid, dim3(KNN_WAVE), 0, estd_stream(s), p);

@@ -8,19 +8,13 @@
 // A minimum and then the smallest index: the result does not depend on the order candidates are met in, so the acceleration structure cannot
 // change a bit of it as long as it never skips a candidate that could win or tie.
 //
-// Structure: a uniform grid over the target's bounding box with a dense cell table.  cloud_cell_keys_kernel computes
-//     c_j = (int)min(max(floor((p_j - lo_j) * inv_cell), 0), dims_j - 1),    key = (c_z dims_y + c_y) dims_x + c_x
-// for targets and queries alike (a query outside the box gets the clamped cell); the host sorts the targets by key (stable), builds
-// cell_start[key] = the number of targets with a smaller key, and keeps the sorted targets as 16-byte records (x, y, z, the bits of the
-// original index): a candidate is ONE 16-byte load, and the cells x0 .. x1 of one grid row are ONE contiguous range of records.
-//
-// Search: ring r = the cells at Chebyshev distance r from the query's cell, r = 0, 1, 2, ...  A ring is walked row by row: a row on the
-// ring's z or y face is one range (x - r .. x + r), any other row contributes its two end cells.  Lower bound: with dims_j <= 1024 the fp32
-// cell coordinate is off by at most 3 * 2^-24 * 1024 < 2^-12 cells from the real one, for the query and for the target, so a target in ring r
-// is at least (r - 1 - 2^-11) cell edges away (also for a clamped query: it lies further out on the clamped axis).  The search stops in
-// front of ring r >= 2 when  LB_SCALE * ((r - 1) * cell)^2 > best,  best = the smallest d2 so far (starting at r2, so max_dist bounds the
-// search as well) and LB_SCALE = 1 - 2^-5: the roundings of the bound need 1 - 2^-10, the margin is 32 times that.  A candidate that
-// ties best is NOT skipped by the strict comparison.  The cell edge is therefore a tuning parameter only.
+// Structure and search: the uniform grid and the ring walk of csrc/estd_device.h (grid_ring_walk; the argument why no ring is skipped too
+// early stands there, once).  What is this file's own: a candidate is ONE target point, its box of cells the one cell
+//     c_j = cell_coord(p_j),    key = (c_z dims_y + c_y) dims_x + c_x,
+// which cloud_cell_keys_kernel computes for targets and queries alike (a query outside the box gets the clamped cell).  The host sorts the
+// targets by key (stable), builds cell_start[key] = the number of targets with a smaller key, and keeps the sorted targets as 16-byte
+// records (x, y, z, the bits of the original index): a candidate is ONE 16-byte load.  bound() returns best = the smallest d2 so far,
+// starting at r2.  A candidate that ties best is still examined (the walk's comparison is strict), and the smaller index wins it.
 //
 // Launch shape: one lane per query, the queries taken in the order of THEIR cell key (`order`, sorted by the host): the 64 lanes of a wave
 // sit in the same few cells, walk the same rows and load the same records -- broadcast or neighbouring 16-byte loads out of L1 / L2 instead
@@ -33,10 +27,9 @@
 // inside a cell the original order is kept) and passes the segment bounds; one lane per (cell, column) adds its column of the cell's points
 // in float64 in that order, divides by the count in float64 and rounds to fp32 once.  Cells come out in ascending key order.
 #include "estd_common.h"
+#include "estd_device.h"
 
 namespace {
-
-constexpr float LB_SCALE = 0.96875f;            // 1 - 2^-5
 
 struct CloudKeysParams {
     const float* points;
@@ -46,13 +39,6 @@ struct CloudKeysParams {
     float inv_cell;
     int dims[3];
 };
-
-// the clamped cell coordinate; the clamp is done in float so that a far query (or an infinite product) converts safely
-__device__ inline int cell_coord(float p, float lo, float inv_cell, int dim)
-{
-    const float t = floorf((p - lo) * inv_cell);
-    return (int)fminf(fmaxf(t, 0.f), (float)(dim - 1));
-}
 
 __global__ __launch_bounds__(256) void cloud_cell_keys_kernel(const CloudKeysParams p)
 {
@@ -74,9 +60,8 @@ struct CloudNearestParams {
     long long* index;
     unsigned int* stats;
     int M, N;
-    int dims[3];
-    float lo[3];
-    float cell, inv_cell, max_dist, r2;
+    estd_grid grid;
+    float max_dist, r2;
 };
 
 // STATS (the bench tool's counter): per query the candidates whose distance was evaluated
@@ -93,12 +78,6 @@ __global__ __launch_bounds__(256) void cloud_nearest_kernel(const CloudNearestPa
     unsigned int examined = 0;
 
     if (p.N > 0) {
-        const int X = p.dims[0], Y = p.dims[1], Z = p.dims[2];
-        const int cx = cell_coord(qx, p.lo[0], p.inv_cell, X);
-        const int cy = cell_coord(qy, p.lo[1], p.inv_cell, Y);
-        const int cz = cell_coord(qz, p.lo[2], p.inv_cell, Z);
-        const int r_max = max(max(max(cx, X - 1 - cx), max(cy, Y - 1 - cy)), max(cz, Z - 1 - cz));      // the last ring that meets the grid
-
         // the records of cells k0 .. k1 of one row
         auto scan = [&](int k0, int k1) {
             const int beg = max(p.cell_start[k0], 0), end = min(p.cell_start[k1 + 1], p.N);
@@ -115,29 +94,7 @@ __global__ __launch_bounds__(256) void cloud_nearest_kernel(const CloudNearestPa
             }
         };
 
-#pragma unroll 1
-        for (int r = 0; r <= r_max; ++r) {
-            if (r >= 2) {
-                const float reach = (float)(r - 1) * p.cell;
-                if (reach * reach * LB_SCALE > best) break;
-            }
-            const int z0 = max(cz - r, 0), z1 = min(cz + r, Z - 1), y0 = max(cy - r, 0), y1 = min(cy + r, Y - 1);
-            const int xa = cx - r, xb = cx + r;
-#pragma unroll 1
-            for (int z = z0; z <= z1; ++z) {
-                const bool z_face = z - cz == r || cz - z == r;
-#pragma unroll 1
-                for (int y = y0; y <= y1; ++y) {
-                    const int row = (z * Y + y) * X;
-                    if (z_face || y - cy == r || cy - y == r) {
-                        scan(row + max(xa, 0), row + min(xb, X - 1));
-                    } else {
-                        if (xa >= 0) scan(row + xa, row + xa);
-                        if (xb <= X - 1) scan(row + xb, row + xb);
-                    }
-                }
-            }
-        }
+        grid_ring_walk(p.grid, qx, qy, qz, [&]() { return best; }, scan);
     }
 
     const bool found = best_index != 0x7fffffff;
@@ -180,32 +137,18 @@ __global__ __launch_bounds__(256) void cloud_cell_centroids_kernel(const CloudCe
     else p.out_attrs[k * p.C + (col - 3)] = mean;
 }
 
-inline bool finite_f(float v) { return v - v == 0.f; }
-
-// lo finite, cell and its fp32 reciprocal positive and finite, 1 <= dims_j <= max_dim
-inline bool grid_ok(const float* lo3, float cell, const int* dims3, int max_dim)
-{
-    if (!lo3 || !dims3) return false;
-    if (!finite_f(cell) || !(cell > 0.f)) return false;
-    const float inv = 1.0f / cell;
-    if (!finite_f(inv) || !(inv > 0.f)) return false;
-    for (int j = 0; j < 3; ++j)
-        if (!finite_f(lo3[j]) || dims3[j] < 1 || dims3[j] > max_dim) return false;
-    return true;
-}
-
 }  // namespace
 
 extern "C" int estd_cloud_cell_keys(const float* points, long long n, const float* lo3, float cell, const int* dims3, long long* keys,
                                     estd_stream_t s)
 {
-    if (n < 0 || !grid_ok(lo3, cell, dims3, ESTD_CLOUD_KEY_MAX_DIM)) return ESTD_ERR_ARG;
+    if (n < 0 || !estd_grid_ok(lo3, cell, dims3, ESTD_CLOUD_KEY_MAX_DIM, 0)) return ESTD_ERR_ARG;
     if (n == 0) return ESTD_OK;
     if (!points || !keys) return ESTD_ERR_ARG;
     if (n > 0x7fffffffLL) return ESTD_ERR_UNSUPPORTED;
     CloudKeysParams p{};
     p.points = points; p.keys = keys; p.n = n;
-    p.inv_cell = 1.0f / cell;                                                 // formed once, here, for targets and queries alike
+    p.inv_cell = estd_inv_cell(cell);
     for (int j = 0; j < 3; ++j) { p.lo[j] = lo3[j]; p.dims[j] = dims3[j]; }
     hipLaunchKernelGGL(cloud_cell_keys_kernel, dim3((unsigned)estd_ceil_div(n, 256)), dim3(256), 0, estd_stream(s), p);
     return ESTD_LAUNCH_CHECK();
@@ -215,27 +158,15 @@ extern "C" int estd_cloud_nearest(const estd_cloud_nearest_desc* d, estd_stream_
 {
     if (!d) return ESTD_ERR_ARG;
     if (d->M < 0 || d->N < 0) return ESTD_ERR_ARG;
-    if (!finite_f(d->max_dist) || !(d->max_dist > 0.f)) return ESTD_ERR_ARG;
-    const float r2 = d->max_dist * d->max_dist;                               // formed once, here
-    if (!finite_f(r2)) return ESTD_ERR_ARG;                                   // a max_dist whose square leaves fp32
-    if (d->N > 0) {
-        if (!grid_ok(d->lo, d->cell, d->dims, ESTD_CLOUD_MAX_DIM)) return ESTD_ERR_ARG;
-        if ((long long)d->dims[0] * d->dims[1] * d->dims[2] > ESTD_CLOUD_MAX_CELLS) return ESTD_ERR_ARG;
-        if (!d->records || !d->cell_start) return ESTD_ERR_ARG;
-        if (reinterpret_cast<unsigned long long>(d->records) & 15ull) return ESTD_ERR_ARG;      // a record is one 16-byte load
-    }
+    CloudNearestParams p{};
+    if (estd_search_args(d->max_dist, d->N, d->lo, d->cell, d->dims, d->records, d->cell_start, &p.grid, &p.r2) != ESTD_OK) return ESTD_ERR_ARG;
     if (d->M > 0x7fffffffLL || d->N > 0x7fffffffLL) return ESTD_ERR_UNSUPPORTED;
     if (d->M == 0) return ESTD_OK;
     if (!d->query || !d->dist || !d->index) return ESTD_ERR_ARG;
-    CloudNearestParams p{};
     p.query = d->query; p.order = d->order; p.records = reinterpret_cast<const float4*>(d->records); p.cell_start = d->cell_start;
     p.dist = d->dist; p.index = d->index; p.stats = d->stats;
     p.M = (int)d->M; p.N = (int)d->N;
-    p.max_dist = d->max_dist; p.r2 = r2;
-    if (d->N > 0) {
-        p.cell = d->cell; p.inv_cell = 1.0f / d->cell;
-        for (int j = 0; j < 3; ++j) { p.lo[j] = d->lo[j]; p.dims[j] = d->dims[j]; }
-    }
+    p.max_dist = d->max_dist;
     const dim3 grid((unsigned)estd_ceil_div(d->M, 256));
     if (d->stats) hipLaunchKernelGGL(cloud_nearest_kernel<true>, grid, dim3(256), 0, estd_stream(s), p);
     else hipLaunchKernelGGL(cloud_nearest_kernel<false>, grid, dim3(256), 0, estd_stream(s), p);

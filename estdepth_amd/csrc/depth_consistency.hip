@@ -90,8 +90,6 @@ __global__ __launch_bounds__(256) void depth_consistency_kernel(const Consistenc
     }
 }
 
-inline bool finite_f(float v) { return v - v == 0.f; }
-
 }  // namespace
 
 extern "C" int estd_depth_consistency(const estd_depth_consistency_desc* d, estd_stream_t s)
@@ -99,12 +97,12 @@ extern "C" int estd_depth_consistency(const estd_depth_consistency_desc* d, estd
     if (!d) return ESTD_ERR_ARG;
     if (!d->target || !d->views || !d->visible || !d->depth || !d->rel_err) return ESTD_ERR_ARG;
     if (d->S < 1 || d->S > ESTD_CONSISTENCY_MAX_SOURCES || d->H < 2 || d->W < 2) return ESTD_ERR_ARG;
-    if (!finite_f(d->px_max) || !(d->px_max > 0.f) || !finite_f(d->rel_max) || !(d->rel_max > 0.f)) return ESTD_ERR_ARG;
-    if (!finite_f(d->z_near) || !(d->z_near >= 0.f)) return ESTD_ERR_ARG;
+    if (!estd_finite(d->px_max) || !(d->px_max > 0.f) || !estd_finite(d->rel_max) || !(d->rel_max > 0.f)) return ESTD_ERR_ARG;
+    if (!estd_finite(d->z_near) || !(d->z_near >= 0.f)) return ESTD_ERR_ARG;
     for (int i = 0; i < d->S; ++i) {
         if (!d->source[i]) return ESTD_ERR_ARG;
         for (int j = 0; j < 24; ++j)
-            if (!finite_f(d->mats[i][j / 12][j % 12])) return ESTD_ERR_ARG;
+            if (!estd_finite(d->mats[i][j / 12][j % 12])) return ESTD_ERR_ARG;
     }
     if ((long long)d->H * d->W > 0x7fffffffLL) return ESTD_ERR_UNSUPPORTED;         // one workgroup per 16 x 16 pixels on blockIdx.x
     ConsistencyParams p{};
@@ -112,7 +110,7 @@ extern "C" int estd_depth_consistency(const estd_depth_consistency_desc* d, estd
     p.tiles_x = estd_ceil_div(d->W, 16);
     p.z_near = d->z_near; p.rel_max = d->rel_max;
     p.px_max2 = d->px_max * d->px_max;                                               // formed once, here
-    if (!(p.px_max2 > 0.f) || !finite_f(p.px_max2)) return ESTD_ERR_ARG;             // a px_max whose square leaves fp32
+    if (!(p.px_max2 > 0.f) || !estd_finite(p.px_max2)) return ESTD_ERR_ARG;             // a px_max whose square leaves fp32
     p.target = d->target; p.views = d->views; p.visible = d->visible; p.depth = d->depth; p.rel_err = d->rel_err;
     for (int i = 0; i < d->S; ++i) {
         p.source[i] = d->source[i];

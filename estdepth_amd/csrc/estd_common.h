@@ -71,6 +71,50 @@ static inline int estd_conv3d_readback_kind(bool res_any, bool accumulate)
 // a positive finite float (false for a NaN)
 static inline bool finite_pos(float v) { return v > 0.f && v < __builtin_inff(); }
 
+// finite (false for a NaN and for either infinity)
+static inline bool estd_finite(float v) { return v - v == 0.f; }
+
+// ---- the uniform grid of the 3D back end: the host side of its one set of checks (the device side: csrc/estd_device.h) ----
+// the reciprocal of the cell edge, formed here alone: keys, bins and searches multiply by the same fp32 value
+static inline float estd_inv_cell(float cell) { return 1.0f / cell; }
+
+// lo finite, cell and its fp32 reciprocal positive and finite, 1 <= dims_j <= max_dim, at most max_cells cells (0: no cap on the product)
+static inline bool estd_grid_ok(const float* lo3, float cell, const int* dims3, int max_dim, long long max_cells)
+{
+    if (!lo3 || !dims3) return false;
+    if (!estd_finite(cell) || !(cell > 0.f)) return false;
+    const float inv = estd_inv_cell(cell);
+    if (!estd_finite(inv) || !(inv > 0.f)) return false;
+    for (int j = 0; j < 3; ++j)
+        if (!estd_finite(lo3[j]) || dims3[j] < 1 || dims3[j] > max_dim) return false;
+    return max_cells <= 0 || (long long)dims3[0] * dims3[1] * dims3[2] <= max_cells;
+}
+
+// what a ring search reads of its grid (grid_ring_walk, csrc/estd_device.h); a member of the search kernels' parameter blocks
+struct estd_grid {
+    int dims[3];
+    float lo[3];
+    float cell, inv_cell;
+};
+
+// The arguments the grid searches share -> ESTD_OK or ESTD_ERR_ARG.  max_dist positive and finite; *r2 = max_dist^2, formed here alone, finite
+// (not a max_dist whose square leaves fp32); with n > 0 candidates in the cell table: the grid rules, `records` and `cell_start` given,
+// `records` 16-byte aligned (a record is read with 16-byte loads), and *g filled.  With n == 0 *g stays as it is: the kernels never read it.
+static inline int estd_search_args(float max_dist, long long n, const float* lo3, float cell, const int* dims3, const void* records,
+                                   const int* cell_start, estd_grid* g, float* r2)
+{
+    if (!estd_finite(max_dist) || !(max_dist > 0.f)) return ESTD_ERR_ARG;
+    *r2 = max_dist * max_dist;
+    if (!estd_finite(*r2)) return ESTD_ERR_ARG;
+    if (n > 0) {
+        if (!estd_grid_ok(lo3, cell, dims3, ESTD_CLOUD_MAX_DIM, ESTD_CLOUD_MAX_CELLS)) return ESTD_ERR_ARG;
+        if (!records || !cell_start || (reinterpret_cast<unsigned long long>(records) & 15ull)) return ESTD_ERR_ARG;
+        g->cell = cell; g->inv_cell = estd_inv_cell(cell);
+        for (int j = 0; j < 3; ++j) { g->lo[j] = lo3[j]; g->dims[j] = dims3[j]; }
+    }
+    return ESTD_OK;
+}
+
 // csrc/conv3d_wino2_c16.hip: the 16 -> 16 + head instance behind estd_conv3d_k3_wino2 (arguments validated by the caller)
 int estd_wino2_c16_launch(const estd_conv3d_desc& d, hipStream_t stream);
 

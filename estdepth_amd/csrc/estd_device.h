@@ -10,6 +10,7 @@
 #include <type_traits>
 #include <utility>
 
+#include "estd_common.h"                        // estd_grid
 #include "estd_hip.h"
 
 // ---- vector types ----
@@ -187,6 +188,79 @@ __device__ __forceinline__ unsigned long long mix64(unsigned long long z)
 __device__ __forceinline__ unsigned long long h64(unsigned long long seed, unsigned long long i, unsigned long long stream)
 {
     return mix64(mix64(seed + (i + 1ull) * 0x9e3779b97f4a7c15ull) + (stream + 1ull) * 0xd1b54a32d192ed03ull);
+}
+
+// ---- never an address from a foreign index or a value that is no number ----
+__device__ __forceinline__ bool in_range(int i, int V) { return (unsigned)i < (unsigned)V; }
+__device__ __forceinline__ bool finite_f32(float v) { return v - v == 0.f; }
+
+// ---- the uniform-grid search (csrc/cloud_nn.hip, csrc/cloud/cloud_knn.hip, csrc/mesh/mesh_distance.hip) ----
+// The structure: a uniform grid (estd_grid, csrc/estd_common.h) with a dense cell table.  A CANDIDATE (a point, a triangle) is registered in
+// every cell of its BOX OF CELLS, the product of the intervals cell_coord(low corner) .. cell_coord(high corner) of its bounding box per
+// axis -- for a point the box of one cell.  The records of a cell are contiguous and the cells of one grid row follow each other:
+// cell_start[key] .. cell_start[key + 1], key = (c_z dims_y + c_y) dims_x + c_x.  A query searches from ITS cell_coord; outside the grid's
+// box that is the clamped cell.
+//
+// The walk: ring r = the cells at Chebyshev distance r from the query's cell, r = 0, 1, 2, ..., row by row: a row on the ring's z or y
+// face is one range (x - r .. x + r), any other row contributes its two end cells.  It stops in front of ring r >= 2 when
+//     LB_SCALE * ((r - 1) * cell)^2 > bound(),
+// bound() = the d2 a candidate has to reach to change the result (it starts at r2 = max_dist^2, so max_dist bounds the search as well), and
+// after ring r_max, the last one that meets the grid.
+//
+// Why nothing is skipped.  cell_coord is monotone in the coordinate, so every point of a candidate (a convex combination of what spans its
+// bounding box) has per axis a cell coordinate inside the candidate's box of cells.  A candidate not met in rings 0 .. r - 1 has no cell
+// within Chebyshev distance r - 1 of the query's cell; its box is a product of intervals, so along ONE axis the whole interval is r or
+// more cells away.  With dims_j <= 1024 (ESTD_CLOUD_MAX_DIM, estd_grid_ok) the fp32 cell coordinate is off by at most
+// 3 * 2^-24 * 1024 < 2^-12 cells from the real one, for the query and for the corner that bounds the box on that side, so every point of
+// the candidate is at least (r - 1 - 2^-11) cell edges from the query along that axis -- also for a clamped query, which lies further
+// out than its cell on the clamped axis, provided the candidates lie inside the grid's box (the host layer takes the box from them).
+// LB_SCALE = 1 - 2^-5: the 2^-11 and the roundings of the bound need 1 - 2^-10, the margin is 32 times that.  The comparison is STRICT: a
+// candidate whose d2 EQUALS bound() is still examined, so a rule that breaks ties by index sees every tie.  The result is then a function
+// of the candidate set alone and the cell edge is a tuning parameter only.
+constexpr float LB_SCALE = 0.96875f;            // 1 - 2^-5
+
+// the clamped cell coordinate; the clamp is done in float so that a far query (or an infinite product) converts safely.  Never contracted,
+// whatever the including file sets: keys, bins and searches have to agree on every bit (there is no multiply-add to fuse; this keeps it so)
+__device__ __forceinline__ int cell_coord(float p, float lo, float inv_cell, int dim)
+{
+#pragma clang fp contract(off)
+    const float t = floorf((p - lo) * inv_cell);
+    return (int)fminf(fmaxf(t, 0.f), (float)(dim - 1));
+}
+
+// bound(): the d2 the lower bound is compared to, read anew in front of every ring; scan(k0, k1): visits the records of cells k0 .. k1 of
+// one row (k0 <= k1, both inside the table)
+template <typename Bound, typename Scan>
+__device__ __forceinline__ void grid_ring_walk(const estd_grid& g, float qx, float qy, float qz, Bound&& bound, Scan&& scan)
+{
+    const int X = g.dims[0], Y = g.dims[1], Z = g.dims[2];
+    const int cx = cell_coord(qx, g.lo[0], g.inv_cell, X);
+    const int cy = cell_coord(qy, g.lo[1], g.inv_cell, Y);
+    const int cz = cell_coord(qz, g.lo[2], g.inv_cell, Z);
+    const int r_max = max(max(max(cx, X - 1 - cx), max(cy, Y - 1 - cy)), max(cz, Z - 1 - cz));      // the last ring that meets the grid
+#pragma unroll 1
+    for (int r = 0; r <= r_max; ++r) {
+        if (r >= 2) {
+            const float reach = (float)(r - 1) * g.cell;
+            if (reach * reach * LB_SCALE > bound()) break;
+        }
+        const int z0 = max(cz - r, 0), z1 = min(cz + r, Z - 1), y0 = max(cy - r, 0), y1 = min(cy + r, Y - 1);
+        const int xa = cx - r, xb = cx + r;
+#pragma unroll 1
+        for (int z = z0; z <= z1; ++z) {
+            const bool z_face = z - cz == r || cz - z == r;
+#pragma unroll 1
+            for (int y = y0; y <= y1; ++y) {
+                const int row = (z * Y + y) * X;
+                if (z_face || y - cy == r || cy - y == r) {
+                    scan(row + max(xa, 0), row + min(xb, X - 1));
+                } else {
+                    if (xa >= 0) scan(row + xa, row + xa);
+                    if (xb <= X - 1) scan(row + xb, row + xb);
+                }
+            }
+        }
+    }
 }
 
 #endif

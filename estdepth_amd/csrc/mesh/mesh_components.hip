@@ -21,6 +21,7 @@
 // index or a smaller member of v's tree.  A stale read costs steps, never correctness: the one decision that takes effect is the CAS,
 // which compares against the memory's value.  The launches are ordered by the stream; what one launch stored, the next one reads.
 #include "../estd_common.h"
+#include "../estd_device.h"
 
 namespace {
 
@@ -79,8 +80,6 @@ __device__ __forceinline__ void unite(int* parent, int a, int b)
         a = find_root_halving(parent, old);
     }
 }
-
-__device__ __forceinline__ bool in_range(int i, int V) { return (unsigned)i < (unsigned)V; }
 
 __global__ __launch_bounds__(WG) void mesh_cc_init_kernel(int* parent, int* triangles, long long* invalid, long long invalid_start, int V)
 {

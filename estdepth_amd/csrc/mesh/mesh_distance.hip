@@ -8,9 +8,10 @@
 // not depend on the order candidates are met in, nor on how often one is met, so the search structure cannot change a bit of it as
 // long as it never skips a candidate that could win or tie.
 //
-// Structure, as csrc/cloud_nn.hip's: a uniform grid with a dense cell table.  A triangle is registered in every cell the bounding box
-// of its three vertices covers (cell_coord of the box's two corners, the function estd_cloud_cell_keys uses); a triangle whose box
-// covers more than `big_cells` cells goes on the BIG LIST instead, which every query tests in full.
+// Structure: the uniform grid and the ring walk of csrc/estd_device.h (grid_ring_walk, with the argument why no ring is skipped too
+// early).  A candidate is a TRIANGLE, registered in every cell the bounding box of its three vertices covers (cell_coord of the box's
+// two corners, the function estd_cloud_cell_keys uses); a triangle whose box covers more than `big_cells` cells goes on the BIG LIST
+// instead, which every query tests in full.
 //   mesh_tri_bins_kernel   one lane per triangle: validity (indices, finite vertices, the fp32 normal), the box of cells, the number of
 //                          (cell, face) pairs it will write and its flag (0 invalid, 1 grid, 2 big list); the invalid ones are counted
 //                          with ONE integer atomic add per wave
@@ -21,38 +22,21 @@
 // contiguous range.
 //   mesh_nearest_kernel    one lane per query, the queries in the order of their own cell key.  Phase A tests every record of the big
 //                          list: the record's address is the same for every lane, so the loads are scalar loads into SGPRs (one per
-//                          wave, not 64 identical vector loads).  Phase B is cloud_nn's ring search over the cell table.
+//                          wave, not 64 identical vector loads).  Phase B is the ring walk over the cell table.
 //
-// The bound of phase B.  cell_coord is monotone in the coordinate, so every vertex of a registered triangle, and with it every point of
-// the triangle (a convex combination, inside the box of the vertices), has per axis a cell coordinate between those of the box's
-// corners.  A triangle that was not met in rings 0 .. r - 1 has no cell within Chebyshev distance r - 1 of the query's cell; its box of
-// cells is a product of intervals, so along one axis the whole interval is r or more cells away.  With dims_j <= 1024 an fp32 cell
-// coordinate is off by less than 2^-12 cells from the real one (cloud_nn.hip), for the query and for the vertex that bounds the box on
-// that side, so every point of the triangle is at least (r - 1 - 2^-11) cell edges from the query along that axis -- also for a query
-// outside the grid's box, whose clamped cell only lies nearer to the grid than the query does.  The search stops in front of ring
-// r >= 2 when LB_SCALE ((r - 1) cell)^2 > best, best = the smallest d2 so far, starting at r2 = max_dist^2: a candidate that ties best is
-// not skipped (strict comparison), and the loop runs over at most max(dims) rings.  The bound needs the valid triangles' vertices inside
-// the grid's box, which the host layer guarantees (the box is theirs).
+// The bound of phase B: bound() returns best = the smallest d2 so far over BOTH phases, starting at r2 = max_dist^2.  A triangle that ties
+// best is still examined (the walk's comparison is strict), and the smaller face index wins it; a triangle met in several cells is
+// examined several times, which a minimum does not notice.  The walk's argument needs the valid triangles' vertices inside the grid's
+// box, which the host layer guarantees (the box is theirs).
 //
 // No LDS, no scratch, no spinning, nothing between workgroups; the only atomic is the invalid count.
 #include "../estd_common.h"
+#include "../estd_device.h"
 
 namespace {
 
 constexpr int WG = 256;
-constexpr float LB_SCALE = 0.96875f;            // 1 - 2^-5, as in cloud_nn.hip
 constexpr int NO_FACE = 0x7fffffff;
-
-__device__ __forceinline__ bool in_range(int i, int V) { return (unsigned)i < (unsigned)V; }
-__device__ __forceinline__ bool finite_d(float v) { return v - v == 0.f; }
-
-// estd_cloud_cell_keys' clamped cell coordinate
-__device__ __forceinline__ int cell_coord(float p, float lo, float inv_cell, int dim)
-{
-#pragma clang fp contract(off)
-    const float t = floorf((p - lo) * inv_cell);
-    return (int)fminf(fmaxf(t, 0.f), (float)(dim - 1));
-}
 
 __device__ __forceinline__ float dot3(float x0, float x1, float x2, float y0, float y1, float y2)
 {
@@ -121,8 +105,8 @@ __device__ __forceinline__ int tri_box(const float* xyz, int V, const int* faces
     const float* b = xyz + 3ll * v1;
     const float* c = xyz + 3ll * v2;
     const float ax = a[0], ay = a[1], az = a[2], bx = b[0], by = b[1], bz = b[2], cx = c[0], cy = c[1], cz = c[2];
-    if (!(finite_d(ax) && finite_d(ay) && finite_d(az) && finite_d(bx) && finite_d(by) && finite_d(bz) && finite_d(cx) && finite_d(cy) &&
-          finite_d(cz)))
+    if (!(finite_f32(ax) && finite_f32(ay) && finite_f32(az) && finite_f32(bx) && finite_f32(by) && finite_f32(bz) && finite_f32(cx) &&
+          finite_f32(cy) && finite_f32(cz)))
         return 0;
     const float abx = bx - ax, aby = by - ay, abz = bz - az, acx = cx - ax, acy = cy - ay, acz = cz - az;
     // two ROUNDED products and their difference, no fma: a face that names a vertex twice (ab == ac, or one of them 0) gives exactly 0
@@ -190,9 +174,8 @@ struct MeshNearestParams {
     float* bary;
     float* closest;
     int M, B, P;
-    int dims[3];
-    float lo[3];
-    float cell, inv_cell, max_dist, r2;
+    estd_grid grid;
+    float max_dist, r2;
 };
 
 __global__ __launch_bounds__(WG) void mesh_nearest_kernel(const MeshNearestParams p)
@@ -222,43 +205,15 @@ __global__ __launch_bounds__(WG) void mesh_nearest_kernel(const MeshNearestParam
 #pragma unroll 1
     for (int j = 0; j < p.B; ++j) test(p.big + 3ll * j);
 
-    // phase B: the rings of cloud_nn.hip over the cell table
+    // phase B: the rings over the cell table
     if (p.P > 0) {
-        const int X = p.dims[0], Y = p.dims[1], Z = p.dims[2];
-        const int cx = cell_coord(qx, p.lo[0], p.inv_cell, X);
-        const int cy = cell_coord(qy, p.lo[1], p.inv_cell, Y);
-        const int cz = cell_coord(qz, p.lo[2], p.inv_cell, Z);
-        const int r_max = max(max(max(cx, X - 1 - cx), max(cy, Y - 1 - cy)), max(cz, Z - 1 - cz));      // the last ring that meets the grid
-
         auto scan = [&](int k0, int k1) {
             const int beg = max(p.cell_start[k0], 0), end = min(p.cell_start[k1 + 1], p.P);
 #pragma unroll 1
             for (int j = beg; j < end; ++j) test(p.records + 3ll * j);
         };
 
-#pragma unroll 1
-        for (int r = 0; r <= r_max; ++r) {
-            if (r >= 2) {
-                const float reach = (float)(r - 1) * p.cell;
-                if (reach * reach * LB_SCALE > best) break;
-            }
-            const int z0 = max(cz - r, 0), z1 = min(cz + r, Z - 1), y0 = max(cy - r, 0), y1 = min(cy + r, Y - 1);
-            const int xa = cx - r, xb = cx + r;
-#pragma unroll 1
-            for (int z = z0; z <= z1; ++z) {
-                const bool z_face = z - cz == r || cz - z == r;
-#pragma unroll 1
-                for (int y = y0; y <= y1; ++y) {
-                    const int row = (z * Y + y) * X;
-                    if (z_face || y - cy == r || cy - y == r) {
-                        scan(row + max(xa, 0), row + min(xb, X - 1));
-                    } else {
-                        if (xa >= 0) scan(row + xa, row + xa);
-                        if (xb <= X - 1) scan(row + xb, row + xb);
-                    }
-                }
-            }
-        }
+        grid_ring_walk(p.grid, qx, qy, qz, [&]() { return best; }, scan);
     }
 
     const bool found = best_face != NO_FACE;
@@ -282,24 +237,10 @@ __global__ __launch_bounds__(WG) void mesh_nearest_kernel(const MeshNearestParam
     }
 }
 
-inline bool finite_f(float v) { return v - v == 0.f; }
-
-// lo finite, cell and its fp32 reciprocal positive and finite, 1 <= dims_j <= ESTD_CLOUD_MAX_DIM, at most ESTD_CLOUD_MAX_CELLS cells
-inline bool grid_ok(const float* lo3, float cell, const int* dims3)
-{
-    if (!lo3 || !dims3) return false;
-    if (!finite_f(cell) || !(cell > 0.f)) return false;
-    const float inv = 1.0f / cell;
-    if (!finite_f(inv) || !(inv > 0.f)) return false;
-    for (int j = 0; j < 3; ++j)
-        if (!finite_f(lo3[j]) || dims3[j] < 1 || dims3[j] > ESTD_CLOUD_MAX_DIM) return false;
-    return (long long)dims3[0] * dims3[1] * dims3[2] <= ESTD_CLOUD_MAX_CELLS;
-}
-
 inline TriGrid tri_grid(const float* lo3, float cell, const int* dims3, int big_cells)
 {
     TriGrid g{};
-    g.inv_cell = 1.0f / cell;                                                // formed once, here, as estd_cloud_cell_keys forms it
+    g.inv_cell = estd_inv_cell(cell);
     for (int j = 0; j < 3; ++j) { g.lo[j] = lo3[j]; g.dims[j] = dims3[j]; }
     g.big_cells = big_cells;
     return g;
@@ -310,7 +251,8 @@ inline TriGrid tri_grid(const float* lo3, float cell, const int* dims3, int big_
 extern "C" int estd_mesh_tri_bins(const float* xyz, long long n_vertices, const int* faces, long long n_faces, const float* lo3, float cell,
                                   const int* dims3, int big_cells, int* count, int* flag, long long* invalid, estd_stream_t s)
 {
-    if (n_faces < 0 || n_vertices < 0 || big_cells < 0 || !invalid || !grid_ok(lo3, cell, dims3)) return ESTD_ERR_ARG;
+    if (n_faces < 0 || n_vertices < 0 || big_cells < 0 || !invalid) return ESTD_ERR_ARG;
+    if (!estd_grid_ok(lo3, cell, dims3, ESTD_CLOUD_MAX_DIM, ESTD_CLOUD_MAX_CELLS)) return ESTD_ERR_ARG;
     if ((n_vertices > 0 && !xyz) || (n_faces > 0 && (!faces || !count || !flag))) return ESTD_ERR_ARG;
     if (n_vertices > 0x7fffffffLL || n_faces > 0x7fffffffLL / 3) return ESTD_ERR_UNSUPPORTED;
     if (hipMemsetAsync(invalid, 0, sizeof(long long), estd_stream(s)) != hipSuccess) return ESTD_ERR_LAUNCH;
@@ -324,7 +266,8 @@ extern "C" int estd_mesh_tri_fill(const float* xyz, long long n_vertices, const 
                                   const int* dims3, int big_cells, const long long* offset, long long n_pairs, long long* keys, int* pair_face,
                                   estd_stream_t s)
 {
-    if (n_faces < 0 || n_vertices < 0 || big_cells < 0 || n_pairs < 0 || !grid_ok(lo3, cell, dims3)) return ESTD_ERR_ARG;
+    if (n_faces < 0 || n_vertices < 0 || big_cells < 0 || n_pairs < 0) return ESTD_ERR_ARG;
+    if (!estd_grid_ok(lo3, cell, dims3, ESTD_CLOUD_MAX_DIM, ESTD_CLOUD_MAX_CELLS)) return ESTD_ERR_ARG;
     if (n_vertices > 0x7fffffffLL || n_faces > 0x7fffffffLL / 3 || n_pairs > ESTD_MESH_DISTANCE_MAX_PAIRS) return ESTD_ERR_UNSUPPORTED;
     if (n_pairs == 0 || n_faces == 0) return ESTD_OK;
     if (!xyz || !faces || !offset || !keys || !pair_face) return ESTD_ERR_ARG;
@@ -337,27 +280,17 @@ extern "C" int estd_mesh_nearest(const estd_mesh_nearest_desc* d, estd_stream_t 
 {
     if (!d) return ESTD_ERR_ARG;
     if (d->M < 0 || d->B < 0 || d->P < 0) return ESTD_ERR_ARG;
-    if (!finite_f(d->max_dist) || !(d->max_dist > 0.f)) return ESTD_ERR_ARG;
-    const float r2 = d->max_dist * d->max_dist;                               // formed once, here
-    if (!finite_f(r2)) return ESTD_ERR_ARG;
+    MeshNearestParams p{};
+    if (estd_search_args(d->max_dist, d->P, d->lo, d->cell, d->dims, d->records, d->cell_start, &p.grid, &p.r2) != ESTD_OK) return ESTD_ERR_ARG;
     if (d->B > 0 && (!d->big_records || (reinterpret_cast<unsigned long long>(d->big_records) & 15ull))) return ESTD_ERR_ARG;
-    if (d->P > 0) {
-        if (!grid_ok(d->lo, d->cell, d->dims)) return ESTD_ERR_ARG;
-        if (!d->records || !d->cell_start || (reinterpret_cast<unsigned long long>(d->records) & 15ull)) return ESTD_ERR_ARG;
-    }
     if (d->M > 0x7fffffffLL || d->B > ESTD_MESH_DISTANCE_MAX_PAIRS || d->P > ESTD_MESH_DISTANCE_MAX_PAIRS) return ESTD_ERR_UNSUPPORTED;
     if (d->M == 0) return ESTD_OK;
     if (!d->query || !d->dist || !d->face) return ESTD_ERR_ARG;
-    MeshNearestParams p{};
     p.query = d->query; p.order = d->order;
     p.big = reinterpret_cast<const float4*>(d->big_records); p.records = reinterpret_cast<const float4*>(d->records);
     p.cell_start = d->cell_start; p.dist = d->dist; p.face = d->face; p.bary = d->bary; p.closest = d->closest;
     p.M = (int)d->M; p.B = (int)d->B; p.P = (int)d->P;
-    p.max_dist = d->max_dist; p.r2 = r2;
-    if (d->P > 0) {
-        p.cell = d->cell; p.inv_cell = 1.0f / d->cell;
-        for (int j = 0; j < 3; ++j) { p.lo[j] = d->lo[j]; p.dims[j] = d->dims[j]; }
-    }
+    p.max_dist = d->max_dist;
     hipLaunchKernelGGL(mesh_nearest_kernel, dim3((unsigned)estd_ceil_div(d->M, WG)), dim3(WG), 0, estd_stream(s), p);
     return ESTD_LAUNCH_CHECK();
 }

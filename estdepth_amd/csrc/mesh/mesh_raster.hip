@@ -21,6 +21,7 @@
 // is formed; the whole image otherwise (a triangle that crosses the camera plane).  A triangle whose det is 0 or not finite is skipped:
 // c = det / S is then 0, infinite or a NaN for every S, and contributes to no pixel.  No float atomics, no LDS, no inline assembly.
 #include "../estd_common.h"
+#include "../estd_device.h"
 
 namespace {
 
@@ -29,8 +30,6 @@ constexpr long long RASTER_SPLIT_WAVES = 8192;      // below this many triangles
 constexpr long long RASTER_MAX_PARTS = 64;          // at most this many
 
 struct RasterMat { double m[12]; };
-
-__device__ __forceinline__ bool in_range(int i, int V) { return (unsigned)i < (unsigned)V; }
 
 // q_j = ((M_j0 x + M_j1 y) + M_j2 z) + M_j3
 __device__ __forceinline__ void project(const RasterMat& M, const float* p, double* q)

@@ -19,8 +19,6 @@ namespace {
 
 constexpr int WG = 256;
 
-__device__ __forceinline__ bool in_range(int i, int V) { return (unsigned)i < (unsigned)V; }
-
 // the mixer h64(seed, i, stream): csrc/estd_device.h (two rounds of SplitMix64's finaliser; h32 is the upper half)
 
 __global__ __launch_bounds__(WG) void mesh_face_area_kernel(const float* xyz, int V, const int* faces, long long F, double* area,

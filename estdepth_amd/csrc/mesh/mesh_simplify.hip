@@ -19,13 +19,12 @@
 // rows of `faces` and mostly neighbouring vertices; a lane per cluster would read 64 unrelated segments per wave and leave a cluster of 300
 // records to one lane.  No LDS, no float atomics, no inline assembly; the outputs are plain vector stores.
 #include "../estd_common.h"
+#include "../estd_device.h"
 
 namespace {
 
 constexpr int WG = 256;
 constexpr int GROUP = 8;                            // lanes per cluster in mesh_cluster_quadric_kernel; the reference's sum tree depends on it
-
-__device__ __forceinline__ bool in_range(int i, int V) { return (unsigned)i < (unsigned)V; }
 
 __global__ __launch_bounds__(WG) void mesh_cluster_faces_kernel(const int* faces, long long F, int V, const int* cluster, int K, int* corner,
                                                                 int* triple, unsigned long long* counts)
@@ -156,20 +155,6 @@ __global__ __launch_bounds__(WG) void mesh_cluster_quadric_kernel(const QuadricP
     on[2] = flat ? 0.f : (float)(nz / len);
 }
 
-inline bool finite_f(float v) { return v - v == 0.f; }
-
-// the grid estd_cloud_cell_keys accepts: lo finite, cell and its fp32 reciprocal positive and finite, 1 <= dims_j <= ESTD_CLOUD_KEY_MAX_DIM
-inline bool grid_ok(const float* lo3, float cell, const int* dims3)
-{
-    if (!lo3 || !dims3) return false;
-    if (!finite_f(cell) || !(cell > 0.f)) return false;
-    const float inv = 1.0f / cell;
-    if (!finite_f(inv) || !(inv > 0.f)) return false;
-    for (int j = 0; j < 3; ++j)
-        if (!finite_f(lo3[j]) || dims3[j] < 1 || dims3[j] > ESTD_CLOUD_KEY_MAX_DIM) return false;
-    return true;
-}
-
 }  // namespace
 
 extern "C" int estd_mesh_cluster_faces(const int* faces, long long n_faces, long long n_vertices, const int* cluster, long long n_clusters,
@@ -190,7 +175,8 @@ extern "C" int estd_mesh_cluster_quadrics(const float* xyz, long long n_vertices
                                           const float* lo3, float cell, const int* dims3, double reg, float* out_xyz, float* out_normal,
                                           unsigned char* placed, estd_stream_t s)
 {
-    if (n_faces < 0 || n_vertices < 0 || n_clusters < 0 || n_clusters > n_vertices || !grid_ok(lo3, cell, dims3)) return ESTD_ERR_ARG;
+    if (n_faces < 0 || n_vertices < 0 || n_clusters < 0 || n_clusters > n_vertices) return ESTD_ERR_ARG;
+    if (!estd_grid_ok(lo3, cell, dims3, ESTD_CLOUD_KEY_MAX_DIM, 0)) return ESTD_ERR_ARG;      // the grid estd_cloud_cell_keys accepts
     if (!(reg >= 0.0 && reg < (double)__builtin_inf())) return ESTD_ERR_ARG;     // negative, infinite or a NaN
     if ((n_vertices > 0 && !xyz) || (n_faces > 0 && (!faces || !order))) return ESTD_ERR_ARG;
     if (n_clusters > 0 && (!segments || !cell_key || !mean || !out_xyz || !out_normal || !placed)) return ESTD_ERR_ARG;

@@ -137,8 +137,6 @@ __global__ __launch_bounds__(64) void frame_align_reduce_kernel(const double* pa
     if (lane == 0) sums[k] = s;
 }
 
-inline bool finite_f(float v) { return v - v == 0.f; }
-
 inline long long n_tiles(int H, int W) { return (long long)estd_ceil_div(W, 16) * estd_ceil_div(H, 16); }
 
 }  // namespace
@@ -154,13 +152,13 @@ extern "C" int estd_frame_align(const estd_frame_align_desc* d, estd_stream_t s)
     if (!d) return ESTD_ERR_ARG;
     if (!d->depth || !d->m_depth || !d->m_normal || !d->residual || !d->match || !d->partials || !d->sums) return ESTD_ERR_ARG;
     if (d->H <= 0 || d->W <= 0 || d->Hm <= 0 || d->Wm <= 0) return ESTD_ERR_ARG;
-    if (!finite_f(d->dist_max) || !(d->dist_max > 0.f)) return ESTD_ERR_ARG;
+    if (!estd_finite(d->dist_max) || !(d->dist_max > 0.f)) return ESTD_ERR_ARG;
     const float dist2 = d->dist_max * d->dist_max;                                          // formed once, here
-    if (!(dist2 > 0.f) || !finite_f(dist2)) return ESTD_ERR_ARG;                            // a dist_max whose square leaves fp32
-    if (!finite_f(d->z_near) || !(d->z_near >= 0.f)) return ESTD_ERR_ARG;
+    if (!(dist2 > 0.f) || !estd_finite(dist2)) return ESTD_ERR_ARG;                            // a dist_max whose square leaves fp32
+    if (!estd_finite(d->z_near) || !(d->z_near >= 0.f)) return ESTD_ERR_ARG;
     if (d->conf && !(d->conf_min == d->conf_min)) return ESTD_ERR_ARG;                       // a NaN threshold
     for (int j = 0; j < 12; ++j)
-        if (!finite_f(d->L[j]) || !finite_f(d->Fm[j]) || !finite_f(d->Bm[j])) return ESTD_ERR_ARG;
+        if (!estd_finite(d->L[j]) || !estd_finite(d->Fm[j]) || !estd_finite(d->Bm[j])) return ESTD_ERR_ARG;
     if ((long long)d->H * d->W > 0x7fffffffLL || (long long)d->Hm * d->Wm > 0x7fffffffLL) return ESTD_ERR_UNSUPPORTED;
     AlignParams p{};
     p.H = d->H; p.W = d->W; p.Hm = d->Hm; p.Wm = d->Wm;

@@ -156,8 +156,6 @@ __global__ __launch_bounds__(64) void rigid_reduce_kernel(const double* partials
     if (lane == 0) sums[k] = s;
 }
 
-inline bool finite_f(float v) { return v - v == 0.f; }
-
 constexpr long long LIMIT = 0x7fffffffLL;                                                    // sizes stay below 2^31
 
 }  // namespace
@@ -167,7 +165,7 @@ extern "C" int estd_rigid_apply(const float* src, const float* src_normal, long 
 {
     if (n < 0 || !T12) return ESTD_ERR_ARG;
     for (int j = 0; j < 12; ++j)
-        if (!finite_f(T12[j])) return ESTD_ERR_ARG;
+        if (!estd_finite(T12[j])) return ESTD_ERR_ARG;
     if (n > 0 && (!src || !moved)) return ESTD_ERR_ARG;
     if (n > 0 && ((src_normal != nullptr) != (moved_normal != nullptr))) return ESTD_ERR_ARG;
     if (n > LIMIT) return ESTD_ERR_UNSUPPORTED;
@@ -190,11 +188,11 @@ extern "C" int estd_rigid_system(const estd_rigid_system_desc* d, estd_stream_t 
     if (!d) return ESTD_ERR_ARG;
     if (d->N < 0 || d->Nt < 0 || d->Nn < 0) return ESTD_ERR_ARG;
     if (d->metric != ESTD_RIGID_PLANE && d->metric != ESTD_RIGID_POINT) return ESTD_ERR_ARG;
-    if (!finite_f(d->dist_max) || !(d->dist_max > 0.f)) return ESTD_ERR_ARG;
+    if (!estd_finite(d->dist_max) || !(d->dist_max > 0.f)) return ESTD_ERR_ARG;
     const float dist2 = d->dist_max * d->dist_max;                                          // formed once, here
-    if (!(dist2 > 0.f) || !finite_f(dist2)) return ESTD_ERR_ARG;
+    if (!(dist2 > 0.f) || !estd_finite(dist2)) return ESTD_ERR_ARG;
     if (d->moved_normal && !(d->cos_min == d->cos_min)) return ESTD_ERR_ARG;                 // a NaN threshold
-    const bool use_cos = d->moved_normal && finite_f(d->cos_min);
+    const bool use_cos = d->moved_normal && estd_finite(d->cos_min);
     if (!d->sums) return ESTD_ERR_ARG;
     if (d->N > 0 && (!d->moved || !d->index || !d->residual || !d->match || !d->partials)) return ESTD_ERR_ARG;
     if (d->N > 0 && d->Nt > 0 && !d->target) return ESTD_ERR_ARG;

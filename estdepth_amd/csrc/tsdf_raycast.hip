@@ -218,16 +218,14 @@ __global__ __launch_bounds__(256) void tsdf_raycast_kernel(const std::conditiona
     }
 }
 
-inline bool finite_f(float v) { return v - v == 0.f; }
-
 template <class Desc, class Params>
 inline int raycast_setup(const Desc* d, Params& p)
 {
     if (!d->tsdf || !d->weight || !d->depth || !d->normal || !d->out_weight) return ESTD_ERR_ARG;
     if (d->H <= 0 || d->W <= 0 || d->n_steps <= 0) return ESTD_ERR_ARG;
-    if (!finite_f(d->dt) || !(d->dt > 0.f) || !finite_f(d->t_min) || !(d->t_min >= 0.f) || !(d->w_min == d->w_min)) return ESTD_ERR_ARG;
+    if (!estd_finite(d->dt) || !(d->dt > 0.f) || !estd_finite(d->t_min) || !(d->t_min >= 0.f) || !(d->w_min == d->w_min)) return ESTD_ERR_ARG;
     for (int i = 0; i < 12; ++i)
-        if (!finite_f(d->mat[i])) return ESTD_ERR_ARG;
+        if (!estd_finite(d->mat[i])) return ESTD_ERR_ARG;
     if (d->Z <= 0 || d->Y <= 0 || d->X <= 0 || (d->X & 3)) return ESTD_ERR_ARG;
     // the volume limits of the other entry points; one workgroup per 16 x 16 pixels on blockIdx.x; k is exact in fp32 up to 2^24
     if (d->Z > 65535 || d->Y > 65535 * 4 || d->X > (1 << 20)) return ESTD_ERR_UNSUPPORTED;

@@ -83,6 +83,24 @@ def test_no_source_defines_a_shared_helper(path):
     assert not again, "%s defines %s: csrc/estd_device.h already does" % (os.path.relpath(path, ROOT), ", ".join(again))
 
 
+def test_the_grid_search_is_written_once():
+    # the private copies of the cell coordinate, the finite test and the grid check the search sources held before they moved
+    gone = re.compile(r"\b(?:knn_cell_coord|knn_finite|knn_grid_ok|finite_f|grid_ok)\b")
+    for path in hip_sources():
+        code = _code(path)
+        assert not gone.search(code), "%s: %s" % (os.path.relpath(path, ROOT), gone.search(code).group(0))
+        # the ring walk's first line: csrc/estd_device.h has the only one (grid_ring_walk)
+        assert "for (int r = 0; r <= r_max" not in code, os.path.relpath(path, ROOT)
+    assert _code(HEADER).count("for (int r = 0; r <= r_max") == 1
+    # the host side of the checks: one definition each under csrc/
+    for name in ("estd_finite", "estd_grid_ok", "estd_search_args"):
+        found = []
+        for base, _, files in os.walk(CSRC):
+            found += [os.path.join(base, f) for f in files if _function_def(name).search(_code(os.path.join(base, f)))]
+        assert [os.path.relpath(p, CSRC) for p in found] == ["estd_common.h"], (name, found)
+        assert len(_function_def(name).findall(_code(found[0]))) == 1, name
+
+
 def test_make_rsrc_without_a_unit_is_gone():
     for base, _, files in os.walk(CSRC):
         for f in files:
