@@ -47,7 +47,7 @@ def _forms(plan, route):
     return sorted({form for la in ops.CONV3D_ROUTES[route] for form in la.weights.values() if plan._packs.has(form)})
 
 
-@pytest.mark.parametrize("case", G3.CASES)
+@pytest.mark.parametrize("case", G3.CASES + G3.READBACK)
 def test_conv3d_default_build_routes(case, build, switches):
     build(False)
     switches(**{k: v for k, v in case["sw"].items() if k != "BINDING"})
@@ -170,7 +170,7 @@ def test_conv3d_packs_the_forms_of_its_route(plan, sw, epi, route, forms, build,
     assert stub_launch.calls == [("conv3d_k3", la.variant) for la in ops.CONV3D_ROUTES[route]]
 
 
-@pytest.mark.parametrize("case", G3.CASES)
+@pytest.mark.parametrize("case", G3.CASES + G3.READBACK)
 def test_conv3d_every_case_packs_the_forms_the_table_names(case, build, switches, stub_launch):
     build(False)
     switches(**{k: v for k, v in case["sw"].items() if k != "BINDING"})

@@ -1,8 +1,9 @@
 """Every dispatch route of ops.Conv3dPlan.run (the 3x3x3 convolution) against the fp64 reference of tests/conv3d_ref.py.
 
 One case per (route, plan, activation, epilogue, strides, switches).  Each case
-  * asserts WHICH kernels ran (torch.profiler kernel names): a silent fallback to another route is a failure, and the deliberate
-    fallback cases assert the route they fall back to;
+  * asserts WHICH kernel instances ran (torch.profiler kernel names, template arguments included, against the copy of the launchers'
+    instance choice in tests/conv3d_instances.py): a silent fallback to another route or to a sibling instance (a wider read-back kind, a
+    lost STATS) is a failure, and the deliberate fallback cases assert the instance they fall back to;
   * compares every output (out_main, out_extra, out_head, the finalised GroupNorm statistics) element by element with the reference:
     |gpu - ref| <= C_ROUTE[route] * 2^-24 * A (A: the same pipeline on absolute values), next to the max-relative bar 3e-6 max |ref|;
   * carves every output out of a larger buffer filled with a NaN sentinel and requires everything the contract does not write -- channels
@@ -13,9 +14,17 @@ One case per (route, plan, activation, epilogue, strides, switches).  Each case
     total size crosses 2^31 bytes (64-bit batch offsets; the reference then at sampled voxels only);
   * runs every small-shape case again where each workgroup of the persistent grid walks a range of several tiles (thin columns, a large batch,
     two grid sizes: test_conv3d_route_over_multi_tile_ranges).
+  * runs every subset of the read-back streams per kernel family (READBACK: test_conv3d_readback_subsets) and the four-wave form of the
+    two-axis kernel in a child process (test_conv3d_wino2_four_wave_form); test_every_claimed_instance_ran closes the module: all 25
+    instances of the default library ran.
 Both bindings launch from one wiring (ops.CONV3D_ROUTES): one small-shape case of every route, and the reset-gate cases, run under both and
 must agree bit for bit."""
+import hashlib
+import json
+import os
 import re
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -23,6 +32,7 @@ import torch
 
 import conv3d_ref as R
 import tile_ranges_ref as TR
+from conv3d_instances import ALL, INSTANCES, KERNELS, SHARED, Refused, instance       # noqa: F401 (INSTANCES: tests/test_kernel_ledger_cpu.py)
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -31,24 +41,26 @@ DEV = torch.device("cuda:0")
 # (in the comments), times at least 3.  The Winograd routes sit BELOW the direct kernel: their transforms shorten the fp32 sums.
 # The many-tile cases added later (test_conv3d_route_over_multi_tile_ranges) are held to the same constants; their sums have the same 27 x cin
 # terms, their worst ratios (in brackets, over 2 x 90 k voxels per case instead of a few thousand) are the tail of the same distribution.
+# So are the read-back subsets (READBACK; second brackets: the worst family x subset) and the four-wave form of the two-axis kernel, whose
+# outputs are the eight-wave form's bit for bit; every family x subset is in profiles/conv3d_instances_gpu_tests.txt.
 C_ROUTE = {
-    "direct": 18.0,           # measured 5.79 (33 -> 33, out_main) [6.43: 33 -> 32]
-    "wino3": 7.0,             # measured 2.25 (32 -> 32, out_main) [2.29: 33 -> 32]
-    "wino2": 8.0,             # measured 2.47 (32 -> 32 + statistics, out_main) [2.55]
+    "direct": 18.0,           # measured 5.79 (33 -> 33, out_main) [6.43: 33 -> 32] [5.15: 32 -> 32 scale; 33 -> 32 3.91, 16 -> 16 4.54]
+    "wino3": 7.0,             # measured 2.25 (32 -> 32, out_main) [2.29: 33 -> 32] [1.55: scale]
+    "wino2": 8.0,             # measured 2.47 (32 -> 32 + statistics, out_main) [2.55] [2.19: 32 -> 32 scale; 33 -> 32 1.91; four waves 2.51]
     "wino2_xout": 7.0,        # measured 2.16 (out_main; channel 32: 0.70) [3.15; channel 32: 0.91]
-    "wino2_o16": 5.0,         # measured 1.63 (with statistics, out_main) [1.83]
+    "wino2_o16": 5.0,         # measured 1.63 (with statistics, out_main) [1.83] [1.28: res + res2]
     "wino2_c16": 2.0,         # measured 0.63 (head) [0.71]
     "wino3+xout": 7.0,        # measured 2.26 (out_main; channel 32: 0.93) [2.33]
 }
-KERNELS = {
-    "direct": {"conv3d_k3_kernel"},
-    "wino3": {"conv3d_wino3_kernel"},
-    "wino2": {"conv3d_wino2_kernel"},
-    "wino2_xout": {"conv3d_wino2_kernel"},
-    "wino2_o16": {"conv3d_wino2_kernel"},
-    "wino2_c16": {"conv3d_wino2_c16_kernel"},
-    "wino3+xout": {"conv3d_wino3_kernel", "conv3d_xout_kernel"},
-}
+# INSTANCES (tests/conv3d_instances.py): route -> the template instances it launches, the table tests/test_kernel_ledger_cpu.py holds
+# against the emitted kernels; every case asserts the exact set instance(route, plan, epilogue) predicts.  No kernel named conv3d_* of the
+# default build is left to another suite:
+NOT_ROUTES = {}
+KERNEL_RE = re.compile(r"\b(conv3d_\w*?_kernel)(<[^>()]*>)?")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# csrc/conv3d_wino2.hip latches ESTD_WINO2_WAVES at the first call: the form this process runs
+WAVES = 4 if os.environ.get("ESTD_WINO2_WAVES", "").strip() == "4" else 8
+_RAN = set()                           # every conv3d instance the profiler saw in this process, and in the children it started
 SWITCHES = ("CONV3D_ALGO", "W3", "W3_EXTRA", "W3_XOUT", "W2_XOUT", "W2X", "BINDING")
 DEFAULT = dict(CONV3D_ALGO="wino2", W3=True, W3_EXTRA=True, W3_XOUT=True, W2_XOUT=True, W2X=False)
 DIRECT = dict(CONV3D_ALGO="direct")
@@ -88,6 +100,8 @@ CASES = [
     # ---- two-axis Winograd (ESTD_W3=0)
     C("wino2-32-split20-res-res2-scale-acc", "wino2", "32>32", ("tanh", "relu", 20), ("res", "res2", "scale", "acc"), 64, 36, W2, both=True),
     C("wino2-32-none-stats", "wino2", "32>32", ("none",), ("stats",), 36, 32, W2),
+    C("wino2-32-acc", "wino2", "32>32", ("relu", "tanh", 16), ("acc",), 32, 40, W2),                 # RBK 1
+    C("wino2-32-res-scale", "wino2", "32>32", ("relu",), ("res", "scale"), 36, 32, W2),               # RBK 2
     C("wino2-33to32-tanh", "wino2", "33>32", ("tanh",), (), 36, 40, W2),
     C("wino2-33to32-relu-res-acc", "wino2", "33>32", ("relu",), ("res", "acc"), 32, 32, W2),
     # ---- the two-axis kernel's 33 -> 33 instance (ESTD_W3_XOUT=0)
@@ -124,6 +138,36 @@ CASES = [
     # ---- batches of more than 2^31 bytes (64-bit batch offsets)
     C("big-batch-wino3", "wino3", "32>32", ("relu",), (), 32, 32, shapes=BIG),
     C("big-batch-split33", "wino3+xout", "33>33", ("relu",), (), 32, 32, shapes=BIG),
+]
+
+# ---- every subset of the read-back streams, per kernel family.  An RBK = 3 instance also serves the RBK 1 and 2 calls of the forms that have
+# no narrower one (scalar channel, 32 -> 16, four waves), an RBK = 2 instance "scale only" and "residual2 only", and the direct kernel takes
+# all of it as run-time flags: a stream that is absent is a NULL pointer / accumulate = 0 INSIDE an instance compiled for it.
+# a batch, an odd depth whose last pair is half empty, H and W one past a tile (W one short of two)
+RB_SHAPES = [(2, 2, 9, 17), (1, 33, 17, 15)]
+RB_SUBSETS = [("res",), ("res2",), ("scale",), ("acc",), ("res", "res2"), ("res", "acc"), ("scale", "acc"), ("res", "res2", "scale", "acc")]
+RB_BOTH = ("res2",)                    # under both bindings: the first stream NULL, the second not
+RB_FAMILIES = [
+    # (id, route, plan, activations, in_stride, out_stride, switches, subsets an existing small-shape case runs already)
+    # wino3-32-split8-res, wino3-32-split20-acc, wino3-32-split16-acc-scale
+    ("wino3-32", "wino3", "32>32", ("tanh", "relu", 16), 36, 40, None, [("res",), ("acc",), ("scale", "acc")]),
+    # wino2-32-acc, wino2-32-split20-res-res2-scale-acc
+    ("wino2-32", "wino2", "32>32", ("relu",), 32, 36, W2, [("acc",), ("res", "res2", "scale", "acc")]),
+    # wino2-33to32-relu-res-acc
+    ("wino2-33to32", "wino2", "33>32", ("tanh",), 36, 32, W2, [("res", "acc")]),
+    # o16-split8-res-res2-scale-acc
+    ("o16", "wino2_o16", "32>16", ("relu", "tanh", 8), 32, 24, None, [("res", "res2", "scale", "acc")]),
+    # direct-32-split20-res-res2-scale-acc
+    ("direct-32", "direct", "32>32", ("tanh", "relu", 20), 36, 40, DIRECT, [("res", "res2", "scale", "acc")]),
+    ("direct-33to32", "direct", "33>32", ("relu", "tanh", 8), 64, 36, DIRECT, []),
+    ("direct-16to16", "direct", "16>16", ("relu",), 32, 24, DIRECT, []),
+]
+READBACK = [C("%s-%s" % (fid, "-".join(sub)), route, plan, acts, sub, ins, outs, sw, shapes=RB_SHAPES, both=sub == RB_BOTH)
+            for fid, route, plan, acts, ins, outs, sw, have in RB_FAMILIES for sub in RB_SUBSETS if sub not in have] + [
+    # under the default switches the three-axis kernel's scalar-channel instance has no read-back stream: the two-axis kernel's takes the call
+    C("fallback-33to32-residual-to-wino2", "wino2", "33>32", ("relu",), ("res",), 36, 32, shapes=RB_SHAPES),
+    # the gated 32 -> 16 instance has none either, and nothing to fall back to: refused by the launcher, before any launch
+    C("refused-o16-gate-res", "wino2_o16", "32>16", ("none",), ("gate", "res"), 32, 16, shapes=RB_SHAPES[:1], both=True),
 ]
 
 
@@ -203,8 +247,9 @@ class _Switches:
         return False
 
 
-def _launch(case, plan, dims, binding, seed):
-    """one run of the case: inputs, guarded outputs, the launch under the case's switches and the profiler -> (kernels, results)"""
+def _launch(case, plan, dims, binding, seed, refused=False):
+    """one run of the case: inputs, guarded outputs, the launch under the case's switches and the profiler -> (kernel instances, results);
+    ``refused``: the call must raise instead"""
     from estdepth_amd import ops
     N, D, H, W = dims
     nvox = N * D * H * W
@@ -255,14 +300,23 @@ def _launch(case, plan, dims, binding, seed):
     before = kw["out"].clone() if "out" in kw else None
     with _Switches(dict(case["sw"], BINDING=binding)):
         with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CUDA]) as prof:
-            plan.run(x, dims, **kw)
+            if refused:
+                with pytest.raises(RuntimeError):
+                    plan.run(x, dims, **kw)
+            else:
+                plan.run(x, dims, **kw)
             torch.cuda.synchronize()
-    kernels = set()
-    for e in prof.key_averages():
-        m = re.search(r"(conv3d_\w*?_kernel)", e.key)
-        if m:
-            kernels.add(m.group(1))
+    kernels = {m.group(1) + (m.group(2) or "") for e in prof.key_averages() for m in [KERNEL_RE.search(e.key)] if m}
+    _RAN.update(kernels)
     return kernels, x, kw, before, bufs
+
+
+def _want(case):
+    """the instances the case must run in this process (None: the launcher refuses the call)"""
+    try:
+        return instance(case["route"], case["plan"], case["epi"], WAVES)
+    except Refused:
+        return None
 
 
 def _finalize(bufs, dims):
@@ -316,28 +370,48 @@ def _check(case, dims, reference, bufs, worst, what):
         worst["stats"] = max(worst.get("stats", 0.0), ratio)
 
 
-@pytest.mark.parametrize("case", CASES)
-def test_conv3d_route_against_fp64(case):
+def _against_fp64(case, tag=""):
+    """the protocol of the module docstring for one case on its shapes, under one binding or both"""
     from estdepth_amd import ops
     seed = sum(map(ord, case["route"] + case["plan"]))
     pa = _plan_args(case["plan"], case["acts"], seed)
     plan = ops.Conv3dPlan(device=DEV, **pa)
+    want = _want(case)
     worst = {}
     for dims in case["shapes"]:
         got = {}
         for binding in ("torch", "ctypes") if case["both"] else ("torch",):
-            kernels, x, kw, before, bufs = _launch(case, plan, dims, binding, seed + sum(dims))
+            kernels, x, kw, before, bufs = _launch(case, plan, dims, binding, seed + sum(dims), refused=want is None)
             what = "%s/%s" % (case["route"], binding)
+            if want is None:                                                    # refused before any launch: no kernel, every byte the sentinel
+                assert not kernels, "%s %s: refused, but ran %s" % (what, dims, sorted(kernels))
+                for key, (buf, _, _, _) in bufs.items():
+                    assert _untouched(buf, 0, 0) == 0, "%s %s: refused, but %s was written" % (what, dims, key)
+                continue
             _compare(case, pa, dims, x, kw, before, bufs, worst, what)          # (first: a wrong result names the output it is wrong in)
-            assert kernels == KERNELS[case["route"]], "%s %s: ran %s" % (what, dims, sorted(kernels))
+            assert kernels == want, "%s %s: ran %s, expected %s" % (what, dims, sorted(kernels), sorted(want))
             got[binding] = {k: v[0].clone() for k, v in bufs.items()}
             del x, kw, before, bufs
-        if case["both"]:
+        if case["both"] and want is not None:
             for k in got["torch"]:
                 assert torch.equal(got["torch"][k].view(torch.int8), got["ctypes"][k].view(torch.int8)), "bindings differ on %s" % k
         del got
         torch.cuda.empty_cache()
-    print("ROUTE-RATIO %s %s %s" % (case["route"], case["plan"], " ".join("%s=%.2f" % kv for kv in sorted(worst.items()))))
+    print("ROUTE-RATIO %s %s %s%s" % (case["route"], case["plan"], tag, " ".join("%s=%.2f" % kv for kv in sorted(worst.items()))))
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_conv3d_route_against_fp64(case):
+    _against_fp64(case)
+
+
+@pytest.mark.parametrize("case", READBACK)
+def test_conv3d_readback_subsets(case, request):
+    """Every subset of {residual, residual2, out_scale, accumulate} no small-shape case above runs, per kernel family (READBACK), under the
+    protocol of test_conv3d_route_against_fp64: the fp64 reference, the route's bound, the sentinel bands, the exact instance -- which for
+    the forms without an instance per read-back kind is the RBK = 3 one with NULL streams.  A call the launcher refuses must raise under
+    both bindings with no conv3d kernel in the profile and every output byte still the sentinel."""
+    _against_fp64(case, "readback[%s] " % request.node.callspec.id)
 
 
 def _written_blocks(bufs):
@@ -351,7 +425,7 @@ def test_conv3d_route_over_multi_tile_ranges(case, request):
     """Every tile-edge case once more on the many-tile shapes of tests/tile_ranges_ref.py (thin columns, a large batch: ranges of 4-12 tiles
     per workgroup with middle tiles, whole columns inside a range, ranges across batch elements and starts on the odd last depth pair),
     under the full grid and under set_reserved_cus(128): every element of every output against one fp64 reference per shape, the same
-    bound, sentinel bands and kernel names, and the outputs of the two grids (and of both bindings, where the case runs both) bit-identical.
+    bound, sentinel bands and kernel instances, and the outputs of the two grids (and of both bindings, where the case runs both) bit-identical.
     The GroupNorm partials are indexed by the canonical 8 x 16 tile (n, d, h-tile, w-tile), not by workgroup: each grid writes exactly
     ops.conv3d_grid(...) blocks -- the direct kernel's tile count, which the model reproduces -- and the same bits."""
     from estdepth_amd import ops
@@ -360,6 +434,7 @@ def test_conv3d_route_over_multi_tile_ranges(case, request):
     seed = sum(map(ord, case["route"] + case["plan"]))
     pa = _plan_args(case["plan"], case["acts"], seed)
     plan = ops.Conv3dPlan(device=DEV, **pa)
+    want = _want(case)
     worst = {}
     prev = ops.get_reserved_cus()
     try:
@@ -377,7 +452,7 @@ def test_conv3d_route_over_multi_tile_ranges(case, request):
                     assert torch.equal(x, x0)                                   # (one reference serves every launch of the shape)
                     what = "%s/%s reserve %d" % (case["route"], binding, r)
                     _check(case, dims, reference, bufs, worst, what)
-                    assert kernels == KERNELS[case["route"]], "%s %s: ran %s" % (what, dims, sorted(kernels))
+                    assert kernels == want, "%s %s: ran %s, expected %s" % (what, dims, sorted(kernels), sorted(want))
                     if "stats" in bufs:
                         assert _written_blocks(bufs) == TR.geometry3d("direct", dims)[3], "%s %s: partial blocks written" % (what, dims)
                     got[r, binding] = {k: v[0].clone() for k, v in bufs.items()}
@@ -395,3 +470,155 @@ def test_conv3d_route_over_multi_tile_ranges(case, request):
         ops.set_reserved_cus(prev)
     print("ROUTE-RATIO %s %s ranges[%s] %s" % (case["route"], case["plan"], request.node.callspec.id,
                                                " ".join("%s=%.2f" % kv for kv in sorted(worst.items()))))
+
+
+# ------------------------------------------------------------------------------------- the four-wave form (a child process)
+def _job(jid, route, plan, acts, epi, ins, outs, sw, shapes, reserves):
+    """a case in JSON form for run_job: it crosses into a child process"""
+    return dict(id=jid, route=route, plan=plan, acts=list(acts), epi=sorted(epi), ins=ins, outs=outs, sw=sw or {},
+                shapes=[list(s) for s in shapes], reserves=list(reserves))
+
+
+def run_job(job, check=True):
+    """One case on every shape of the job under every grid of job["reserves"], in THIS process (whose ESTD_WINO2_WAVES is latched):
+    the exact instance per launch, the grids bit-identical and, with ``check``, every output against the fp64 reference with the route's
+    bound and the sentinel bands.  -> dict(ran, worst ratios, sums: SHA-256 of every guarded buffer per shape)"""
+    from estdepth_amd import ops
+    case = dict(route=job["route"], plan=job["plan"], acts=tuple(job["acts"]), epi=set(job["epi"]), ins=job["ins"], outs=job["outs"],
+                sw=dict(DEFAULT, **job["sw"]))
+    seed = sum(map(ord, case["route"] + case["plan"]))
+    pa = _plan_args(case["plan"], case["acts"], seed)
+    plan = ops.Conv3dPlan(device=DEV, **pa)
+    want = instance(case["route"], case["plan"], case["epi"], WAVES)
+    worst, ran, sums = {}, set(), {}
+    prev = ops.get_reserved_cus()
+    try:
+        for dims in map(tuple, job["shapes"]):
+            reference, first = None, None
+            for r in job["reserves"]:
+                assert ops.set_reserved_cus(r) == r
+                kernels, x, kw, before, bufs = _launch(case, plan, dims, "torch", seed + sum(dims))
+                what = "%s reserve %d" % (job["id"], r)
+                if check:
+                    if reference is None:
+                        reference = _reference(pa, dims, x, kw, before)
+                    _check(case, dims, reference, bufs, worst, what)
+                assert kernels == want, "%s %s: ran %s, expected %s" % (what, dims, sorted(kernels), sorted(want))
+                ran |= kernels
+                got = {k: v[0].clone() for k, v in bufs.items()}
+                if first is None:
+                    first = got
+                for k in first:
+                    assert torch.equal(first[k].view(torch.int8), got[k].view(torch.int8)), "%s: the grids differ on %s (%s)" % (what, k, dims)
+                del x, kw, before, bufs, got
+            for k, v in first.items():
+                sums["%s %s" % ("x".join(map(str, dims)), k)] = hashlib.sha256(v.view(torch.uint8).cpu().numpy().tobytes()).hexdigest()
+            del first, reference
+            torch.cuda.empty_cache()
+    finally:
+        ops.set_reserved_cus(prev)
+    return dict(ran=sorted(ran), worst=worst, sums=sums)
+
+
+def _child(env, jobs):
+    """run_job of every job in ONE fresh process with ``env`` (the latched switch) -> {job id: run_job's result}; failures are reported
+    per job.  The child starts nothing more on the device once a synchronize fails."""
+    code = ("import json, sys, traceback\n"
+            "sys.path.insert(0, 'tests')\n"
+            "import torch\n"
+            "import test_gpu_conv3d_routes as T\n"
+            "for j in json.loads(sys.argv[1]):\n"
+            "    try:\n"
+            "        print('CASE ' + json.dumps([j['id'], T.run_job(j)]), flush=True)\n"
+            "    except BaseException:\n"
+            "        print('FAIL ' + json.dumps([j['id'], traceback.format_exc()[-1500:]]), flush=True)\n"
+            "        try:\n"
+            "            torch.cuda.synchronize()\n"
+            "        except BaseException:\n"
+            "            sys.exit(3)\n")
+    r = subprocess.run([sys.executable, "-c", code, json.dumps(jobs)], cwd=ROOT, env=dict(os.environ, **env), capture_output=True, text=True,
+                       timeout=600)
+    if r.returncode < 0 or r.returncode in (3, 134, 139):       # a crashed GPU process: start nothing more on this device
+        pytest.exit("child %s ended with status %d:\n%s\n%s" % (env, r.returncode, r.stdout[-3000:], r.stderr[-3000:]), returncode=1)
+    got, fails = {}, []
+    for line in r.stdout.splitlines():
+        if line.startswith("CASE "):
+            jid, res = json.loads(line[5:])
+            got[jid] = res
+            _RAN.update(res["ran"])
+        elif line.startswith("FAIL "):
+            fails.append(json.loads(line[5:]))
+    assert r.returncode == 0, (env, r.returncode, r.stdout[-1500:], r.stderr[-1500:])
+    assert not fails, "%s: %s" % (env, "\n".join("%s: %s" % tuple(f) for f in fails))
+    assert sorted(got) == sorted(j["id"] for j in jobs), (env, sorted(got))
+    return got
+
+
+FOUR_WAVES = dict(ESTD_WINO2_WAVES="4")
+# read-back kinds 0, 1, 2, 3 of the plain 32 -> 32 form: the two tile-edge shapes of READBACK and one many-tile shape, both grids
+W4_JOBS = [_job("w4-32-" + ("-".join(epi) or "plain"), "wino2", "32>32", acts, epi, ins, outs, W2,
+                RB_SHAPES + TR.ranges3d(TR.ROUTE_FAMILY["wino2"])[:1], TR.RESERVES)
+           for acts, epi, ins, outs in ((("relu",), (), 32, 32), (("relu", "tanh", 16), ("acc",), 32, 40), (("relu",), ("res", "scale"), 36, 32),
+                                        (("tanh", "relu", 20), ("res", "res2", "scale", "acc"), 64, 36))]
+# the forms that have no four-wave version: one launch each
+W4_JOBS += [_job("w4-33to32", "wino2", "33>32", ("tanh",), (), 36, 40, W2, RB_SHAPES[:1], (0,)),
+            _job("w4-o16", "wino2_o16", "32>16", ("none",), (), 32, 16, None, RB_SHAPES[:1], (0,)),
+            _job("w4-33to33", "wino2_xout", "33>33", ("relu",), (), 36, 40, W2XOUT, RB_SHAPES[:1], (0,))]
+W4_INSTANCES = {"w4-32-plain": "conv3d_wino2_kernel<4, 0, false, false, false, false>",
+                "w4-33to32": "conv3d_wino2_kernel<8, 0, true, false, false, false>",
+                "w4-o16": "conv3d_wino2_kernel<8, 0, false, true, false, false>",
+                "w4-33to33": "conv3d_wino2_kernel<8, 0, true, false, true, false>"}       # every other job: <4, 3, false, ...>
+
+
+def test_conv3d_wino2_four_wave_form():
+    """ESTD_WINO2_WAVES=4 (latched at the first call, hence a fresh child process): one wave per SIMD holds both channel halves,
+    conv3d_wino2_kernel<4, 0, ...> and <4, 3, ...>.  The child runs the read-back kinds 0 - 3 of the plain 32 -> 32 form under the whole
+    protocol (fp64 reference, C_ROUTE["wino2"], sentinel bands, exact instance, both grids bit-identical), and one launch of each form
+    that has no four-wave version, which must still run its <8, ...> instance.
+
+    Both forms form every output with the same operations in the same order.  A wave of the eight-wave form owns the channel half
+    nh0 = wave >> 2, a wave of the four-wave form loops over x = 0, 1 in its place; per (product t, half x) the MFMA chain runs
+    step -> component pair h -> component e over the same fragments and the same weights (load_w: byte offset x * 2048 against
+    nh0 * 2048), the output transforms (fold_sd) and the epilogue (bn_act, residuals, scale, running sum) are written once for both.
+    So the parent, which runs the same inputs in the eight-wave form, requires the SAME BITS of every output."""
+    if WAVES != 8:
+        pytest.fail("run this suite without ESTD_WINO2_WAVES: the parent process is the eight-wave side of the comparison")
+    got = _child(FOUR_WAVES, W4_JOBS)
+    for job in W4_JOBS:
+        res = got[job["id"]]
+        want = W4_INSTANCES.get(job["id"], "conv3d_wino2_kernel<4, 3, false, false, false, false>")
+        assert res["ran"] == [want], (job["id"], res["ran"])
+        print("ROUTE-RATIO %s %s four-wave[%s] %s" % (job["route"], job["plan"], job["id"],
+                                                      " ".join("%s=%.2f" % kv for kv in sorted(res["worst"].items()))))
+        mine = run_job(job, check=False)                     # the eight-wave form on the same inputs (its own cases hold it to the reference)
+        assert mine["ran"] == sorted(instance(job["route"], job["plan"], job["epi"], 8)), (job["id"], mine["ran"])
+        diff = sorted(k for k in res["sums"] if res["sums"][k] != mine["sums"].get(k))
+        assert sorted(res["sums"]) == sorted(mine["sums"]) and not diff, "%s: four and eight waves differ on %s" % (job["id"], diff)
+
+
+def _first_case(inst):
+    """a case of this module that runs the instance in the eight-wave form"""
+    for p in CASES + READBACK:
+        case = p.values[0]
+        if case["shapes"] is not BIG and case["shapes"] is not FULL and inst in (_want(case) or ()):
+            return case
+    return None
+
+
+def test_every_claimed_instance_ran():
+    """the instances the profiler saw under this module's cases and in the four-wave child are exactly the claimed ones (should this
+    test run alone: one small launch per missing instance, one small child for the four-wave pair)"""
+    from estdepth_amd import ops
+    if WAVES == 8 and not any(k.startswith("conv3d_wino2_kernel<4,") for k in _RAN):
+        _child(FOUR_WAVES, [_job(j["id"], j["route"], j["plan"], j["acts"], j["epi"], j["ins"], j["outs"], j["sw"], RB_SHAPES[:1], (0,))
+                            for j in (W4_JOBS[0], W4_JOBS[3])])
+    for inst in sorted(ALL - _RAN):
+        case = _first_case(inst)
+        if case is None:
+            continue
+        seed = sum(map(ord, case["route"] + case["plan"]))
+        plan = ops.Conv3dPlan(device=DEV, **_plan_args(case["plan"], case["acts"], seed))
+        kernels = _launch(case, plan, RB_SHAPES[0], "torch", seed)[0]
+        assert kernels == _want(case), (inst, sorted(kernels))
+    print("CONV3D-INSTANCES %d ran:\n  %s" % (len(_RAN), "\n  ".join(sorted(_RAN))))
+    assert _RAN == ALL, "never ran: %s; not claimed: %s" % (sorted(ALL - _RAN), sorted(_RAN - ALL))

@@ -2,14 +2,14 @@
 (tools/kernel_resources.py: the demangled names and the compiler's resource remarks, nothing else) and every ``*_kernel`` function must be
 claimed by exactly one GPU route suite's table -- or by a NOT_ROUTES entry that says why it is no route:
 
-    tests/test_gpu_conv3d_routes.py        KERNELS          by kernel name (the instance is predicted per case from the plan's route)
+    tests/test_gpu_conv3d_routes.py        INSTANCES        per instance, template arguments included (tests/conv3d_instances.py)
     tests/test_gpu_conv2d_routes.py        ROUTES           by name prefix (the instance is predicted per case by the dispatcher copies)
     tests/test_gpu_sweep_fusion_routes.py  INSTANCES        per instance, template arguments included
     tests/test_gpu_glue2d_routes.py        INSTANCES        per instance
     tests/test_gpu_recon3d_routes.py       INSTANCES        per instance
 
-so a kernel added to a source cannot ship without a test that names it.  For the three per-instance tables nothing claimed may be absent
-from the emitted set either.  The 25 instances of the glue and reconstruction suites hold no array the compiler could not keep in
+so a kernel -- for the per-instance suites: a template instance -- added to a source cannot ship without a test that names it.  For the
+four per-instance tables nothing claimed may be absent from the emitted set either.  The 25 instances of the glue and reconstruction suites hold no array the compiler could not keep in
 registers: no scratch, no spilled vector register, and no spilled scalar register either -- but for the two plain integrate instances,
 whose known counts are pinned (SGPR_IN_LANES)."""
 import glob
@@ -35,7 +35,7 @@ NOT_ROUTES = {
     "conv3d_wino2x_kernel": "superseded A/B kernel (ESTD_BUILD_AB=1 builds only): tests/test_gpu_wino.py under the ab mark",
     "conv3d_k3_split_kernel": "superseded A/B kernel (ESTD_BUILD_AB=1 builds only): tests/test_gpu_split_conv.py under the ab mark",
 }
-PER_INSTANCE = (("sweep_fusion", GS), ("glue2d", GG), ("recon3d", GR))
+PER_INSTANCE = (("conv3d", G3), ("sweep_fusion", GS), ("glue2d", GG), ("recon3d", GR))
 # Scalar registers the compiler parks in VGPR lanes (v_writelane / v_readlane: no scratch, no memory traffic), at most.  The plain integrate
 # instances take the per-frame arguments of eight frames (128 SGPRs) by value and the scalar file cannot hold them beside the rest.  That
 # is accepted there: the kernel is bound by the projection arithmetic of every voxel (profiles/tsdf_bench.txt: 0.150 ms for
@@ -82,8 +82,6 @@ def _base(inst):
 def _claims(inst):
     """the suites (or NOT_ROUTES tables) that claim an emitted instance"""
     base, who = _base(inst), []
-    if any(base in ks for ks in G3.KERNELS.values()):
-        who.append("conv3d")
     if any(base.startswith(prefix) for prefix, _ in G2.ROUTES):
         who.append("conv2d")
     for name, mod in PER_INSTANCE:
