@@ -140,6 +140,26 @@ class CloudKnnDesc(ctypes.Structure):
     ]
 
 
+class CloudCountWithinDesc(ctypes.Structure):
+    """Mirror of struct estd_cloud_count_within_desc (include/estd_hip.h)."""
+    _fields_ = [
+        ("M", ctypes.c_longlong), ("N", ctypes.c_longlong),
+        ("query", ctypes.c_void_p), ("order", ctypes.c_void_p), ("records", ctypes.c_void_p), ("cell_start", ctypes.c_void_p),
+        ("count", ctypes.c_void_p),
+        ("lo", ctypes.c_float * 3), ("cell", ctypes.c_float), ("radius", ctypes.c_float), ("dims", ctypes.c_int * 3),
+    ]
+
+
+class CloudDbscanDesc(ctypes.Structure):
+    """Mirror of struct estd_cloud_dbscan_desc (include/estd_hip.h)."""
+    _fields_ = [
+        ("N", ctypes.c_longlong),
+        ("records", ctypes.c_void_p), ("cell_start", ctypes.c_void_p),
+        ("count", ctypes.c_void_p), ("parent", ctypes.c_void_p), ("label", ctypes.c_void_p), ("size", ctypes.c_void_p), ("noise", ctypes.c_void_p),
+        ("lo", ctypes.c_float * 3), ("cell", ctypes.c_float), ("eps", ctypes.c_float), ("dims", ctypes.c_int * 3), ("min_points", ctypes.c_int),
+    ]
+
+
 class MeshNearestDesc(ctypes.Structure):
     """Mirror of struct estd_mesh_nearest_desc (include/estd_hip.h)."""
     _fields_ = [
@@ -258,6 +278,8 @@ _SIGNATURES = {
     "estd_cloud_knn": (ctypes.c_int, [ctypes.POINTER(CloudKnnDesc), c_stream]),
     "estd_cloud_normals": (ctypes.c_int, [c_float_p, ctypes.c_longlong, c_float_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                           c_float_p, ctypes.c_int, c_float_p, c_float_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_stream]),
+    "estd_cloud_count_within": (ctypes.c_int, [ctypes.POINTER(CloudCountWithinDesc), c_stream]),
+    "estd_cloud_dbscan": (ctypes.c_int, [ctypes.POINTER(CloudDbscanDesc), c_stream]),
     "estd_cloud_spfh": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                        ctypes.c_void_p, ctypes.c_void_p, c_stream]),
     "estd_cloud_fpfh": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int] +

@@ -26,7 +26,7 @@ LIB = os.path.join(OUT_DIR, "libestd_hip%s.so" % os.environ.get("ESTD_LIB_SUFFIX
 # are built, exported (include/estd_hip.h: #ifdef ESTD_BUILD_AB), bound and tested only with ESTD_BUILD_AB=1 in the environment.
 SOURCES = ["conv3d_mfma.hip", "conv3d_wino2.hip", "conv3d_wino3.hip", "conv3d_xout.hip", "conv3d_wino2_c16.hip", "conv2d_mfma.hip", "conv2d_wino2.hip",
            "plane_sweep.hip", "est_fusion.hip", "refine2d.hip", "conv1x1.hip", "conv2d_taps.hip", "tsdf.hip", "tsdf_raycast.hip",
-           "depth_consistency.hip", "cloud_nn.hip", "cloud/cloud_knn.hip", "track/frame_align.hip", "track/rigid_align.hip",
+           "depth_consistency.hip", "cloud_nn.hip", "cloud/cloud_knn.hip", "cloud/cloud_cluster.hip", "track/frame_align.hip", "track/rigid_align.hip",
            "mesh/tsdf_mesh.hip", "mesh/mesh_components.hip",
            "mesh/mesh_sample.hip", "mesh/mesh_raster.hip", "mesh/mesh_distance.hip", "mesh/mesh_simplify.hip",
            "register/global_register.hip"]

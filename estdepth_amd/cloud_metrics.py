@@ -18,6 +18,10 @@ precision / recall / F-score at a threshold.  The clouds are what ``TSDFVolume.e
     fit = estimate_normals(scan, 16, 0.05, toward=(0.0, 0.0, 1.5))     # normals of a cloud that came without: a PCA plane fit
     keep = remove_outliers(scan, k=16, std_ratio=2.0)["keep"]          # statistical outlier removal over the same search
     scores = compare_clouds(pred, scan, pred_normal=n, normals=dict(k=16))      # the side without normals gets them estimated
+    near = grid.count_within(points, 0.05)                             # how many targets within 5 cm, no cap (csrc/cloud/cloud_cluster.hip)
+    c = cluster_dbscan(cloud, eps=0.04, min_points=6)                  # DBSCAN: label, cluster, sizes, noise
+    keep = filter_clusters(cloud, 0.04, 6, min_size=200)["keep"]       # the cloud without its floaters
+    scores = compare_clouds(pred, gt, clusters=dict(eps=0.04, min_points=6, min_size=200))      # ... dropped before the scoring
 
 The nearest-neighbour result is defined to the bit (include/estd_hip.h, estd_cloud_nearest): per query the smallest fp32
 ``d2 = fma(dx, dx, fma(dy, dy, dz * dz))`` over ALL targets, the smallest original index attaining it, found iff ``d2 <= max_dist^2``;
@@ -162,6 +166,18 @@ class PointGrid:
         order = _query_order(self, points, self.n > 0)
         return ops.cloud_knn(points, order, self.records, self.cell_start, self.lo, self.cell, self.dims, self.max_dist, k, stats=stats)
 
+    def count_within(self, points, radius=None):
+        """``points`` [M,3] -> int32 [M]: the number of targets within ``radius`` of each point (d2 <= radius^2 in fp32, inclusive; a
+        point that is a target counts itself), without a cap (csrc/cloud/cloud_cluster.hip; include/estd_hip.h, estd_cloud_count_within).
+        ``radius`` must not exceed the grid's ``max_dist`` (the default cell is chosen for it); None: ``max_dist``."""
+        radius = self.max_dist if radius is None else _check_max_dist(radius, "PointGrid.count_within")
+        _need(radius <= self.max_dist, "PointGrid.count_within: radius %g exceeds the grid's max_dist %g" % (radius, self.max_dist))
+        points = _check_cloud(points, "points", "PointGrid.count_within", self.device)
+        if points.shape[0] == 0:
+            return torch.empty(0, device=self.device, dtype=torch.int32)
+        order = _query_order(self, points, self.n > 0)
+        return ops.cloud_count_within(points, order, self.records, self.cell_start, self.lo, self.cell, self.dims, radius)
+
 
 def nearest(query, target, max_dist, cell=None):
     """One-shot form of ``PointGrid(target, max_dist, cell).query(query)`` -> (dist [M], index [M])."""
@@ -245,6 +261,96 @@ def remove_outliers(points, k=16, std_ratio=2.0, max_dist=None, min_neighbours=N
     if min_neighbours is not None:
         keep = keep & (n_other >= min_neighbours)
     return dict(keep=keep, mean_dist=mean, mu=mu, sigma=sigma, dropped=n - int(keep.sum().item()))
+
+
+def _check_min_points(min_points, op):
+    _need(isinstance(min_points, int) and not isinstance(min_points, bool) and 1 <= min_points < 2 ** 31, "%s: min_points must be an integer >= 1, got %r" % (op, min_points))
+    return min_points
+
+
+def cluster_dbscan(points, eps, min_points=10, cell=None):
+    """Density-based clustering (DBSCAN) of the cloud ``points`` [N,3] (csrc/cloud/cloud_cluster.hip; the contract, defined to the
+    integer: include/estd_hip.h, estd_cloud_dbscan).  Two points are neighbours when their fp32 ``d2 <= eps^2`` (inclusive; a point is
+    its own neighbour), a point with at least ``min_points`` neighbours is a CORE point, clusters are the connected components of the
+    core points under that relation, a point that is not core joins the cluster of its nearest core neighbour (the smaller index among
+    equals) or is noise -> dict:
+    label [N] int32 (the smallest core index of the point's cluster, -1 for noise), cluster [N] int32 (-1, or a dense id 0 .. C-1, the
+    clusters ordered by ascending label), count [N] int32 (the neighbours, the point among them), core [N] bool, roots [C] int64 (the
+    labels, ascending), sizes [C] int32 (the points per cluster, borders included), n_clusters, noise (ints).
+    The search grid is built with cell edge ``eps`` -- not ``grid_plan``'s surface default: a walk to a fixed radius visits about
+    ``eps / cell + 2`` rings whatever it finds -- unless ``cell`` gives another; it never changes an output, and neither does the order
+    of the rows beyond permuting the partition with them."""
+    op = "cluster_dbscan"
+    eps = _check_max_dist(eps, op)
+    min_points = _check_min_points(min_points, op)
+    _need(cell is None or (isinstance(cell, (int, float)) and math.isfinite(cell) and cell > 0), "%s: cell must be positive and finite, got %r" % (op, cell))
+    points = _check_cloud(points, "points", op)
+    n, dev = int(points.shape[0]), points.device
+    if n == 0:
+        e = lambda dtype: torch.empty(0, device=dev, dtype=dtype)
+        return dict(label=e(torch.int32), cluster=e(torch.int32), count=e(torch.int32), core=e(torch.bool), roots=e(torch.int64), sizes=e(torch.int32),
+                    n_clusters=0, noise=0)
+    grid = PointGrid(points, eps, eps if cell is None else cell)
+    label, count, size, noise = ops.cloud_dbscan(grid.records, grid.cell_start, grid.lo, grid.cell, grid.dims, eps, min_points)
+    roots = torch.nonzero(size > 0).reshape(-1)
+    dense = torch.full((n,), -1, device=dev, dtype=torch.int32)
+    dense[roots] = torch.arange(roots.shape[0], device=dev, dtype=torch.int32)
+    cluster = torch.where(label >= 0, dense[label.clamp(min=0).long()], torch.full((), -1, device=dev, dtype=torch.int32))
+    return dict(label=label, cluster=cluster, count=count, core=count >= min_points, roots=roots, sizes=size[roots], n_clusters=int(roots.shape[0]),
+                noise=int(noise.item()))
+
+
+def _check_cluster_filter(min_size, keep_largest, op):
+    for name, v in (("min_size", min_size), ("keep_largest", keep_largest)):
+        _need(v is None or (isinstance(v, int) and not isinstance(v, bool) and v >= 0), "%s: %s must be None or an integer that is not negative, got %r" % (op, name, v))
+
+
+def filter_clusters(points, eps, min_points=10, min_size=None, keep_largest=None, cell=None):
+    """The rows of the cloud ``points`` [N,3] that belong to its large clusters (``cluster_dbscan(points, eps, min_points)``): the
+    clusters with at least ``min_size`` points are kept (None: every cluster), and with ``keep_largest=k`` only the k of them with the
+    most points (ties go to the smaller label).  Noise is always dropped.  -> dict(keep [N] bool, cluster [N] int32 and sizes [C] as
+    ``cluster_dbscan`` returns them, n_clusters, clusters_kept, kept / dropped: the points kept / dropped, noise: the noise points among
+    the dropped).  What ``fusion3d.filter_mesh`` does for a mesh by its connectivity; the mask is torch glue over the kernels' labels."""
+    op = "filter_clusters"
+    _check_cluster_filter(min_size, keep_largest, op)
+    c = cluster_dbscan(points, eps, min_points, cell)
+    sizes, dev = c["sizes"], c["cluster"].device
+    keep_c = sizes >= (0 if min_size is None else min_size)
+    if keep_largest is not None:
+        at = torch.nonzero(keep_c).reshape(-1)                                  # by ascending label: the stable sort settles ties that way
+        order = torch.sort(sizes[at].to(torch.int64), descending=True, stable=True)[1]
+        keep_c = torch.zeros_like(keep_c)
+        keep_c[at[order[:keep_largest]]] = True
+    keep = (c["cluster"] >= 0) & torch.cat([keep_c, torch.zeros(1, device=dev, dtype=torch.bool)])[c["cluster"].long()]
+    kept = int(keep.sum().item())
+    return dict(keep=keep, cluster=c["cluster"], sizes=sizes, n_clusters=c["n_clusters"], clusters_kept=int(keep_c.sum().item()), kept=kept,
+                dropped=int(keep.shape[0]) - kept, noise=c["noise"])
+
+
+CLUSTERS_KEYS = ("eps", "min_points", "min_size", "keep_largest", "sides")
+
+
+def _clusters_arg(clusters, op):
+    """``clusters=dict(eps, min_points=10, min_size=None, keep_largest=None, sides=("pred",))`` -> (filter_clusters' arguments, sides)"""
+    _need(isinstance(clusters, dict) and "eps" in clusters and all(k in CLUSTERS_KEYS for k in clusters),
+          "%s: clusters must be a dict with eps and optionally %s" % (op, ", ".join(CLUSTERS_KEYS[1:])))
+    sides = clusters.get("sides", ("pred",))
+    sides = (sides,) if isinstance(sides, str) else tuple(sides)
+    _need(len(sides) > 0 and all(s in ("pred", "gt") for s in sides), "%s: clusters['sides'] must name 'pred', 'gt' or both, got %r" % (op, sides))
+    kw = dict(eps=_check_max_dist(clusters["eps"], op + " (clusters['eps'])"),
+              min_points=_check_min_points(10 if clusters.get("min_points") is None else clusters["min_points"], op + " (clusters)"),
+              min_size=clusters.get("min_size"), keep_largest=clusters.get("keep_largest"))
+    _check_cluster_filter(kw["min_size"], kw["keep_largest"], op + " (clusters)")
+    return kw, sides
+
+
+def _drop_floaters(xyz, cols, kw):
+    """one side of a comparison through ``filter_clusters`` -> (the rows kept, the per-point tensors ``cols`` (a dict; None entries
+    pass) alike, the side's entry of the ``clusters`` block)"""
+    f = filter_clusters(xyz, **kw)
+    keep = f["keep"]
+    return (xyz[keep].contiguous(), {k: (v if v is None else v[keep].contiguous()) for k, v in cols.items()},
+            dict(n_clusters=f["n_clusters"], kept=f["kept"], dropped=f["dropped"], noise=f["noise"]))
 
 
 NORMALS_KEYS = ("k", "radius")
@@ -443,7 +549,7 @@ def _align(src, src_normal, target, target_normal, align, threshold, op):
 
 
 def compare_clouds(pred, gt, threshold=0.05, max_dist=None, downsample=None, pred_normal=None, gt_normal=None, pred_color=None, gt_color=None,
-                   cell=None, align=None, normals=None):
+                   cell=None, align=None, normals=None, clusters=None):
     """The 3D scores of the cloud ``pred`` [P,3] against ``gt`` [G,3] (float32, one ROCm device, finite) -> dict of floats / ints:
 
     accuracy / completeness: the mean distance pred -> gt / gt -> pred, each distance clamped to ``max_dist`` (default 20 ``threshold``);
@@ -462,7 +568,11 @@ def compare_clouds(pred, gt, threshold=0.05, max_dist=None, downsample=None, pre
     the ``k`` nearest neighbours within ``radius``, None: ``threshold``; after ``downsample``; unoriented).  Rows the estimate finds not
     valid leave the normal_consistency pairs, and with ``align`` and the plane metric a ground truth without normals is registered to
     through its valid rows only (estimated before the down-sampling, on the cloud the registration sees).  The result gains ``normals`` =
-    dict(k, radius, estimated: the sides among "pred", "gt", invalid_pred, invalid_gt).  With the default None nothing of this runs."""
+    dict(k, radius, estimated: the sides among "pred", "gt", invalid_pred, invalid_gt).  With the default None nothing of this runs.
+    ``clusters=dict(eps, min_points=10, min_size=None, keep_largest=None, sides=("pred",))``: the named sides lose their floaters FIRST
+    (``filter_clusters`` on the cloud as it came, its normals and colours carried along); alignment, normal estimation and
+    down-sampling see the filtered cloud.  The result gains ``clusters`` = dict(side: dict(n_clusters, kept, dropped, noise)).  With the
+    default None nothing of this runs and every result is the same bits as before."""
     _need(isinstance(threshold, (int, float)) and math.isfinite(threshold) and threshold > 0, "compare_clouds: threshold must be positive and finite, got %r" % (threshold,))
     if max_dist is None:
         max_dist = 20.0 * threshold
@@ -479,6 +589,19 @@ def compare_clouds(pred, gt, threshold=0.05, max_dist=None, downsample=None, pre
             _need(isinstance(a, torch.Tensor) and a.dtype == torch.float32 and tuple(a.shape) == tuple(cloud.shape) and a.device == cloud.device,
                   "compare_clouds: %s must be float32 %s on the cloud's device" % (name, tuple(cloud.shape)))
             attrs[name] = a.contiguous()
+    dropped = None
+    if clusters is not None:
+        kw, sides = _clusters_arg(clusters, "compare_clouds")
+        dropped = {}
+        for side in ("pred", "gt"):
+            if side in sides:
+                names = [k for k in (side + "_normal", side + "_color") if k in attrs]
+                cloud, cols, dropped[side] = _drop_floaters(pred if side == "pred" else gt, {k: attrs[k] for k in names}, kw)
+                attrs.update(cols)
+                if side == "pred":
+                    pred = cloud
+                else:
+                    gt = cloud
     alignment = None
     est, rows_ok, early = None, {}, None
     if normals is not None:
@@ -558,6 +681,8 @@ def compare_clouds(pred, gt, threshold=0.05, max_dist=None, downsample=None, pre
         out["alignment"] = alignment
     if est is not None:
         out["normals"] = est
+    if dropped is not None:
+        out["clusters"] = dropped
     return out
 
 
@@ -654,7 +779,7 @@ def _exact_scores(a, b, pred, gt, dev, threshold, max_dist, downsample, cell):
 
 
 def compare_meshes(pred, gt, density, threshold=0.05, max_dist=None, downsample=None, seed=0, cell=None, visible=None, exact=False, align=None,
-                   normals=None):
+                   normals=None, clusters=None):
     """The 3D scores of the SURFACE ``pred`` against the surface ``gt``: both triangle meshes (dicts with ``xyz`` and ``faces``: what
     ``extract_mesh``, ``filter_mesh`` or ``read_ply(faces=True)`` return) are sampled by area at ``density`` points per square metre
     (``fusion3d.sample_mesh``, face normals), and the two clouds go to ``compare_clouds`` unchanged -> its dict plus ``sampled`` =
@@ -683,7 +808,11 @@ def compare_meshes(pred, gt, density, threshold=0.05, max_dist=None, downsample=
     ``normals=dict(k=16, radius=None)``: a side WITHOUT faces that comes without normals gets them estimated from its points, as
     ``compare_clouds`` documents it (a side with faces has its face normals); with ``align`` and the plane metric such a ground truth is
     registered to through its valid rows.  Not with ``exact=True``.  The result gains ``normals``.  With the default None nothing of
-    this runs."""
+    this runs.
+    ``clusters=dict(eps, min_points=10, min_size=None, keep_largest=None, sides=("pred",))``: the SAMPLES of the named sides lose their
+    floaters first, as ``compare_clouds`` documents it -- before the alignment and the visibility restriction; the result gains
+    ``clusters``.  Not with ``exact=True`` (the surfaces themselves are the targets there: ``fusion3d.filter_mesh`` cleans a mesh).  With
+    the default None nothing of this runs."""
     _need(isinstance(density, (int, float)) and math.isfinite(density) and density > 0, "compare_meshes: density must be positive and finite, got %r" % (density,))
     from . import fusion3d
     _need(all(isinstance(x, dict) and x.get("xyz") is not None for x in (pred, gt)), "compare_meshes: pred and gt must be dicts with 'xyz'")
@@ -698,6 +827,17 @@ def compare_meshes(pred, gt, density, threshold=0.05, max_dist=None, downsample=
         out = {k: fusion3d._on_device(v, dev) for k, v in (("xyz", x["xyz"]), ("normal", x.get("normal")), ("color", color)) if v is not None}
         return out, None, 0
     (a, area_a, bad_a), (b, area_b, bad_b) = side(pred), side(gt)
+    dropped = None
+    if clusters is not None:
+        _need(not exact, "compare_meshes: clusters= is not available with exact=True")
+        kw, sides = _clusters_arg(clusters, "compare_meshes")
+        dropped = {}
+
+        def cleaned(s, name):
+            xyz, cols, dropped[name] = _drop_floaters(_check_cloud(s["xyz"], name, "compare_meshes"), {k: s[k] for k in ("normal", "color") if k in s}, kw)
+            return dict(s, xyz=xyz, **cols)
+        a = cleaned(a, "pred") if "pred" in sides else a
+        b = cleaned(b, "gt") if "gt" in sides else b
     n_gt = int(b["xyz"].shape[0])
     alignment = None
     if normals is not None:
@@ -739,4 +879,6 @@ def compare_meshes(pred, gt, density, threshold=0.05, max_dist=None, downsample=
         out["sampled"].update(n_gt_visible=int(b["xyz"].shape[0]), visible_share=int(b["xyz"].shape[0]) / n_gt if n_gt else 0.0)
     if alignment is not None:
         out["alignment"] = alignment
+    if dropped is not None:
+        out["clusters"] = dropped
     return out

@@ -263,4 +263,70 @@ __device__ __forceinline__ void grid_ring_walk(const estd_grid& g, float qx, flo
     }
 }
 
+// ---- the lock-free union-find (csrc/mesh/mesh_components.hip, csrc/cloud/cloud_cluster.hip) ----
+// The forest.  parent[v] only ever holds v itself or a smaller member of v's tree, and it only ever decreases: an init launch stores v;
+// a HOOK, the successful atomicCAS(&parent[a], a, b) with b < a, is the one store that joins two trees; a SHORTCUT, atomicMin(&parent[v],
+// g) with g a member of v's tree below parent[v], joins nothing.  So every path strictly descends and ends at a root (parent[r] == r),
+// the root is the smallest member of its tree, an element that has been hooked never becomes a root again, and once every edge is
+// hooked the trees are the components: the labels do not depend on the order in which the lanes ran.
+//
+// Visibility.  The per-XCD L2s are not coherent and a CU's L1 is never refreshed, so a hook kernel takes nothing from a load for
+// granted: every write of parent[] is an agent-scope atomic (atomicCAS, atomicMin), every read a relaxed agent-scope atomic load (served
+// by the L2, never the L1), and ANY value a read returns -- fresh or stale -- was stored at that address at some time, hence is v's own
+// index or a smaller member of v's tree.  A stale read costs steps, never correctness: the one decision that takes effect is the CAS,
+// which compares against the memory's value.  The launches are ordered by the stream; what one launch stored, the next one reads.
+__device__ __forceinline__ int parent_load(const int* parent, int v)
+{
+    return __hip_atomic_load(parent + v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// the root of v's tree as far as this lane can see.  Terminates whatever the loads return: a value read at parent[v] is <= v, the loop
+// goes on only while it is < v, and indices are not negative -- at most v steps.  The result is v itself or a smaller member of v's
+// tree; it was a root when the value read at it was stored, not necessarily now.
+__device__ __forceinline__ int find_root(const int* parent, int v)
+{
+    int p = parent_load(parent, v);
+    while (p != v) {
+        v = p;
+        p = parent_load(parent, v);
+    }
+    return v;
+}
+
+// find_root with path halving, for a hook kernel: every element on the way is pointed at its grandparent, so the chains that the first
+// round of hooks builds (every lane starts on a forest of single elements at once) are not walked at full length again.  The shortcut
+// is an agent-scope atomicMin -- parent[v] only ever DEcreases -- and it is applied to v only after a read showed parent[v] = p != v, so
+// v is no root and never becomes one again: a shortcut cannot undo or pre-empt a hook.  g was read at parent[p] and p at parent[v],
+// so g is a member of v's tree and g < p < v: the invariant of the forest holds.  Termination as in find_root: v strictly decreases.
+__device__ __forceinline__ int find_root_halving(int* parent, int v)
+{
+    int p = parent_load(parent, v);
+    while (p != v) {
+        const int g = parent_load(parent, p);
+        if (g != p) atomicMin(parent + v, g);
+        v = p;
+        p = g;
+    }
+    return v;
+}
+
+// merge the trees of a and b.  Invariant: a and b are in the trees of the two elements the call was given (each is replaced by an
+// ancestor of itself only).  Termination: every iteration ends the loop (a == b: one tree already; or the CAS put root a under b < a),
+// or replaces a, the larger of the two, by a strictly smaller index >= 0 -- the CAS failed, so it returned parent[a] != a, hence < a, and
+// the search goes on from THAT value (find_root_halving only descends further).  a + b strictly decreases and is bounded below: no
+// iteration waits for another lane, none repeats a state.  b need not be a root: hooking a root under any smaller member of the other
+// tree keeps every path descending.  Every tree has exactly one root, its smallest member (all paths descend to it), so a root a and a
+// smaller b are never in one tree: a successful CAS always merges two trees and removes exactly one root.
+__device__ __forceinline__ void unite(int* parent, int a, int b)
+{
+    a = find_root_halving(parent, a);
+    b = find_root_halving(parent, b);
+    while (a != b) {
+        if (a < b) { const int t = a; a = b; b = t; }
+        const int old = atomicCAS(parent + a, a, b);
+        if (old == a) break;
+        a = find_root_halving(parent, old);
+    }
+}
+
 #endif

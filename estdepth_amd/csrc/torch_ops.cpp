@@ -950,6 +950,63 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> cloud_knn(const Tensor& query, const 
     return {dist, index, count, st};
 }
 
+// ------------------------------------------------------------------------------------------------ clustering (csrc/cloud/cloud_cluster.hip)
+// query [M,3], order int64 [M], records [N,4], cell_start int32 [cells + 1] -> count int32 [M]: the targets within `radius`
+Tensor cloud_count_within(const Tensor& query, const Tensor& order, const Tensor& records, const Tensor& cell_start, const Tensor& lo, double cell,
+                          at::IntArrayRef dims, double radius)
+{
+    const char* op = "cloud_count_within";
+    const OpScope scope(query);
+    estd_cloud_count_within_desc d{};
+    d.query = check_cloud(query, op, "query", 3);
+    d.records = check_cloud(records, op, "records", 4);
+    const int64_t M = query.size(0), N = records.size(0);
+    d.order = reinterpret_cast<const long long*>(lptr(order, op, "order", query, M));
+    d.radius = positive_square_f32(radius, op, "radius");
+    check_cloud_grid(lo, cell, dims, op, ESTD_CLOUD_MAX_DIM);
+    const int64_t cells = dims[0] * dims[1] * dims[2];
+    TORCH_CHECK(cells <= ESTD_CLOUD_MAX_CELLS, "cloud_count_within: ", cells, " cells, at most ", ESTD_CLOUD_MAX_CELLS);
+    d.cell_start = lptr<int32_t>(cell_start, op, "cell_start (cells + 1)", query, cells + 1);
+    Tensor count = at::empty({M}, query.options().dtype(at::kInt));
+    if (M) {
+        d.M = (long long)M; d.N = (long long)N;
+        d.count = count.data_ptr<int32_t>();
+        d.cell = (float)cell;
+        for (int j = 0; j < 3; ++j) { d.lo[j] = lo.data_ptr<float>()[j]; d.dims[j] = (int)dims[j]; }
+        check_status(estd_cloud_count_within(&d, cur_stream()), "estd_cloud_count_within");
+    }
+    return count;
+}
+
+// records [N,4], cell_start int32 [cells + 1] -> (label int32 [N], count int32 [N], size int32 [N], noise int32 [1])
+std::tuple<Tensor, Tensor, Tensor, Tensor> cloud_dbscan(const Tensor& records, const Tensor& cell_start, const Tensor& lo, double cell,
+                                                        at::IntArrayRef dims, double eps, int64_t min_points)
+{
+    const char* op = "cloud_dbscan";
+    const OpScope scope(records);
+    estd_cloud_dbscan_desc d{};
+    d.records = check_cloud(records, op, "records", 4);
+    const int64_t N = records.size(0);
+    d.eps = positive_square_f32(eps, op, "eps");
+    check_count(min_points, 1, 0x7fffffffLL, op, "min_points");
+    check_cloud_grid(lo, cell, dims, op, ESTD_CLOUD_MAX_DIM);
+    const int64_t cells = dims[0] * dims[1] * dims[2];
+    TORCH_CHECK(cells <= ESTD_CLOUD_MAX_CELLS, "cloud_dbscan: ", cells, " cells, at most ", ESTD_CLOUD_MAX_CELLS);
+    d.cell_start = lptr<int32_t>(cell_start, op, "cell_start (cells + 1)", records, cells + 1);
+    const auto i32 = records.options().dtype(at::kInt);
+    Tensor label = at::empty({N}, i32), count = at::empty({N}, i32), size = at::empty({N}, i32), parent = at::empty({N}, i32);
+    Tensor noise = N ? at::empty({1}, i32) : at::zeros({1}, i32);
+    if (N) {
+        d.N = (long long)N; d.min_points = (int)min_points;
+        d.count = count.data_ptr<int32_t>(); d.parent = parent.data_ptr<int32_t>(); d.label = label.data_ptr<int32_t>();
+        d.size = size.data_ptr<int32_t>(); d.noise = noise.data_ptr<int32_t>();
+        d.cell = (float)cell;
+        for (int j = 0; j < 3; ++j) { d.lo[j] = lo.data_ptr<float>()[j]; d.dims[j] = (int)dims[j]; }
+        check_status(estd_cloud_dbscan(&d, cur_stream()), "estd_cloud_dbscan");
+    }
+    return {label, count, size, noise};
+}
+
 // points [N,3], query [M,3], index int32 [M,k], count int32 [M], toward: nothing, [3] or [M,3] -> (normal [M,3], eig [M,3], valid uint8
 // [M], invalid int64 [1], cov float64 [M,6] when asked for, else [0,6])
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> cloud_normals(const Tensor& points, const Tensor& query, const Tensor& index, const Tensor& count,
@@ -1805,6 +1862,9 @@ TORCH_LIBRARY(estdepth_hip, m)
     m.def("cloud_cell_centroids(Tensor points, Tensor attrs, Tensor order, Tensor segments) -> (Tensor, Tensor)");
     m.def("cloud_knn(Tensor query, Tensor order, Tensor records, Tensor cell_start, Tensor lo, float cell, int[] dims, float max_dist, "
           "int k, bool stats) -> (Tensor, Tensor, Tensor, Tensor)");
+    m.def("cloud_count_within(Tensor query, Tensor order, Tensor records, Tensor cell_start, Tensor lo, float cell, int[] dims, float radius) -> Tensor");
+    m.def("cloud_dbscan(Tensor records, Tensor cell_start, Tensor lo, float cell, int[] dims, float eps, int min_points) -> "
+          "(Tensor, Tensor, Tensor, Tensor)");
     m.def("cloud_normals(Tensor points, Tensor query, Tensor index, Tensor count, Tensor? toward, bool cov) -> "
           "(Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("cloud_spfh(Tensor points, Tensor normal, Tensor index, Tensor count, bool oriented) -> (Tensor, Tensor)");
@@ -1885,6 +1945,8 @@ TORCH_LIBRARY_IMPL(estdepth_hip, CUDA, m)
     m.impl("cloud_nearest", cloud_nearest);
     m.impl("cloud_cell_centroids", cloud_cell_centroids);
     m.impl("cloud_knn", cloud_knn);
+    m.impl("cloud_count_within", cloud_count_within);
+    m.impl("cloud_dbscan", cloud_dbscan);
     m.impl("cloud_normals", cloud_normals);
     m.impl("cloud_spfh", cloud_spfh);
     m.impl("cloud_fpfh", cloud_fpfh);

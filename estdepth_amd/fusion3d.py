@@ -312,12 +312,21 @@ class TSDFVolume:
         """voxels some frame has updated"""
         return int((self.volume[1] > 0).sum().item())
 
-    def save_ply(self, path, w_min=1.0, color_scale=1.0, color_offset=0.0):
+    def save_ply(self, path, w_min=1.0, color_scale=1.0, color_offset=0.0, clusters=None, stats=None):
         """binary little-endian PLY with normals (host side); returns the number of points.  A colour volume appends uchar red / green /
         blue = clamp(round(c * color_scale + color_offset), 0, 255); ``color_scale`` / ``color_offset``: a scalar or three values (one per
-        channel), e.g. 255 for 0..1 images or (255 std, 255 mean) to undo a normalisation."""
+        channel), e.g. 255 for 0..1 images or (255 std, 255 mean) to undo a normalisation.
+        ``clusters=dict(eps, min_points=10, min_size=None, keep_largest=None)``: the points (in the order they are written in) go through
+        ``cloud_metrics.filter_clusters`` first and only the rows it keeps are written; ``stats`` (a dict) then receives n_clusters,
+        clusters_kept, kept, dropped and noise.  With the default None nothing more is launched and the file is the same bytes."""
         pts = self.extract_points(w_min=w_min)
         order = torch.argsort(pts["edge"])
+        if clusters is not None:
+            from . import cloud_metrics
+            f = cloud_metrics.filter_clusters(pts["xyz"][order].contiguous(), **clusters)
+            order = order[f["keep"]]
+            if stats is not None:
+                stats.update({k: f[k] for k in ("n_clusters", "clusters_kept", "kept", "dropped", "noise")})
         rec = torch.cat([pts["xyz"][order], pts["normal"][order]], 1).cpu().contiguous()
         rgb = None
         if self.color is not None:
@@ -362,7 +371,7 @@ class TSDFVolume:
         return rec.shape[0], faces.shape[0]
 
     def compare(self, other, threshold=0.05, w_min=1.0, max_dist=None, downsample=None, cell=None, sample=None, seed=0, visible=None, exact=False,
-                align=None, normals=None):
+                align=None, normals=None, clusters=None):
         """The 3D scores (``cloud_metrics.compare_clouds``: accuracy, completeness, chamfer, precision / recall / F-score at ``threshold``
         metres, ...) of this volume's surface as the prediction against ``other`` as the ground truth: another ``TSDFVolume`` -- both sides
         go through ``extract_points(w_min)`` -- or a dict with ``xyz`` [N,3] and optionally ``normal`` / ``color`` (device tensors or numpy
@@ -380,9 +389,14 @@ class TSDFVolume:
         clouds are registered.  With the default None nothing of this runs.
         ``normals=dict(k=16, radius=None)`` is handed on: a side that comes without normals (a dict without ``normal`` and without faces) gets
         them estimated from its own points (``cloud_metrics.estimate_normals``); the result gains ``normals``.  With the default None nothing
-        of this runs."""
+        of this runs.
+        ``clusters=dict(eps, min_points=10, min_size=None, keep_largest=None, sides=("pred",))`` is handed on too: the named sides lose
+        their floaters first (``cloud_metrics.filter_clusters``; not with ``exact=True``); the result gains ``clusters``.  With the default
+        None nothing of this runs."""
         from . import cloud_metrics
         more = {} if normals is None else dict(normals=normals)
+        if clusters is not None:
+            more["clusters"] = clusters
         if visible is not None and sample is None:
             raise RuntimeError("compare: visible= needs sample=density (the ground-truth surface is sampled, then restricted)")
         if exact and sample is None:

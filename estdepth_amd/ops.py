@@ -1666,6 +1666,67 @@ def cloud_knn(query, order, records, cell_start, lo, cell, dims, max_dist, k, st
     return (dist, index, count, st) if stats else (dist, index, count)
 
 
+# ---------------------------------------------------------------------------------- clustering (csrc/cloud/cloud_cluster.hip)
+def cloud_count_within(query, order, records, cell_start, lo, cell, dims, radius):
+    """The number of targets within ``radius`` of every row of ``query`` [M,3] (d2 <= radius^2, inclusive, no cap) -> int32 [M] on the
+    query's device.  ``records`` / ``cell_start`` / ``order``: as for cloud_nearest.  include/estd_hip.h, estd_cloud_count_within."""
+    cell, radius, dims = float(cell), float(radius), [int(v) for v in dims]
+    if _use_torch():
+        return T().cloud_count_within(query, order, records, cell_start, lo, cell, dims, radius)
+    op = "cloud_count_within"
+    _cloud(query, op, "query")
+    _cloud(records, op, "records", cols=4)
+    M, n, dev = query.shape[0], records.shape[0], query.device
+    _ivec(order, op, "order", dev, M)
+    _need(records.device == dev, "cloud_count_within: records are on %s but the query on %s" % (records.device, dev))
+    _positive_square(radius, op, "radius")
+    lo3, dims = _cloud_grid(lo, cell, dims, op, CLOUD_MAX_DIM)
+    cells = dims[0] * dims[1] * dims[2]
+    _need(cells <= CLOUD_MAX_CELLS, "cloud_count_within: %d cells, at most %d" % (cells, CLOUD_MAX_CELLS))
+    _ivec(cell_start, op, "cell_start (cells + 1)", dev, cells + 1, torch.int32)
+    with torch.cuda.device(dev):
+        count = torch.empty(M, device=dev, dtype=torch.int32)
+        if M:
+            d = N.CloudCountWithinDesc()
+            d.M, d.N = M, n
+            d.query, d.order, d.records, d.cell_start = query.data_ptr(), order.data_ptr(), records.data_ptr(), cell_start.data_ptr()
+            d.count = count.data_ptr()
+            d.cell, d.radius = cell, radius
+            d.lo[:], d.dims[:] = lo3, dims
+            N.check(N.lib().estd_cloud_count_within(ctypes.byref(d), _stream()), "estd_cloud_count_within")
+    return count
+
+
+def cloud_dbscan(records, cell_start, lo, cell, dims, eps, min_points):
+    """DBSCAN of the cloud the key-sorted ``records`` [N,4] hold -> (label int32 [N], count int32 [N], size int32 [N], noise int32 [1]),
+    all by ORIGINAL index: the smallest core index of the point's cluster or -1, the neighbours within ``eps`` (the point itself among
+    them), the points per label, the points labelled -1.  The contract is spelled out in include/estd_hip.h (estd_cloud_dbscan)."""
+    cell, eps, dims, min_points = float(cell), float(eps), [int(v) for v in dims], int(min_points)
+    if _use_torch():
+        return tuple(T().cloud_dbscan(records, cell_start, lo, cell, dims, eps, min_points))
+    op = "cloud_dbscan"
+    _cloud(records, op, "records", cols=4)
+    n, dev = records.shape[0], records.device
+    _positive_square(eps, op, "eps")
+    _count(min_points, 1, 0x7fffffff, op, "min_points")
+    lo3, dims = _cloud_grid(lo, cell, dims, op, CLOUD_MAX_DIM)
+    cells = dims[0] * dims[1] * dims[2]
+    _need(cells <= CLOUD_MAX_CELLS, "cloud_dbscan: %d cells, at most %d" % (cells, CLOUD_MAX_CELLS))
+    _ivec(cell_start, op, "cell_start (cells + 1)", dev, cells + 1, torch.int32)
+    with torch.cuda.device(dev):
+        label, count, size, parent = (torch.empty(n, device=dev, dtype=torch.int32) for _ in range(4))
+        noise = torch.empty(1, device=dev, dtype=torch.int32) if n else torch.zeros(1, device=dev, dtype=torch.int32)
+        if n:
+            d = N.CloudDbscanDesc()
+            d.N, d.min_points = n, min_points
+            d.records, d.cell_start = records.data_ptr(), cell_start.data_ptr()
+            d.count, d.parent, d.label, d.size, d.noise = count.data_ptr(), parent.data_ptr(), label.data_ptr(), size.data_ptr(), noise.data_ptr()
+            d.cell, d.eps = cell, eps
+            d.lo[:], d.dims[:] = lo3, dims
+            N.check(N.lib().estd_cloud_dbscan(ctypes.byref(d), _stream()), "estd_cloud_dbscan")
+    return label, count, size, noise
+
+
 def cloud_normals(points, query, index, count, toward=None, cov=False):
     """Normals by a plane fit over the neighbours ``index`` [M,k] int32 / ``count`` [M] int32 (cloud_knn's) of ``query`` [M,3] in the
     cloud ``points`` [N,3] -> (normal [M,3], eig [M,3] ascending, valid [M] uint8, invalid int64 [1], cov float64 [M,6] or None).

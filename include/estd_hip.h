@@ -729,6 +729,66 @@ int estd_cloud_normals(const float* points, long long n, const float* query, lon
                        const float* toward, int toward_per_query, float* normal, float* eig, unsigned char* valid, long long* invalid,
                        double* cov, estd_stream_t stream);
 
+/* ---- density-based clustering of a point cloud, DBSCAN (csrc/cloud/cloud_cluster.hip; numpy form: tests/cloud_cluster_ref.py) ----
+ * Neighbours within a radius.  For query q and EVERY target p, in fp32, d2 exactly as estd_cloud_nearest forms it:
+ *   dx = qx - px, dy = qy - py, dz = qz - pz;   d2 = fma(dx, dx, fma(dy, dy, dz * dz));
+ *   count[q] = the number of targets with d2 <= r2, r2 = radius * radius (formed once by the entry point in fp32).  The test is
+ *   INCLUSIVE: a target at d2 == r2 counts.  There is no cap on the count.
+ * count [M] (int32) is written by every call with plain stores; records, cell_start, the grid and `order` are estd_cloud_nearest's (an
+ * `order` entry outside 0..M-1 is ignored), and the cell edge changes no value: the kernel walks the rings up to the constant bound r2.
+ * N == 0: every count is 0.  M == 0: no launch.
+ * ESTD_ERR_ARG (before any launch, no device needed): what estd_cloud_nearest refuses (radius in the place of max_dist), with M > 0 a
+ * null query or count.  ESTD_ERR_UNSUPPORTED: M or N >= 2^31. */
+typedef struct estd_cloud_count_within_desc {
+    long long M, N;                               /* queries, targets */
+    const float* query;                           /* [M][3] */
+    const long long* order;                       /* [M] or NULL */
+    const float* records;                         /* [N][4], sorted by key */
+    const int* cell_start;                        /* [dims[0] dims[1] dims[2] + 1] */
+    int* count;                                   /* [M] */
+    float lo[3];                                  /* host values, copied into the launch arguments */
+    float cell;
+    float radius;
+    int dims[3];
+} estd_cloud_count_within_desc;
+int estd_cloud_count_within(const estd_cloud_count_within_desc* desc, estd_stream_t stream);
+
+/* DBSCAN of the cloud the records hold (N points, original indices 0..N-1).  THE CONTRACT, defined to the integer and independent of
+ * the grid, the launch shape and the scheduling:
+ *   d2(i, j) is the expression above between points i and j.  It is exactly symmetric: negating dx, dy and dz changes no bit.
+ *   r2 = eps * eps, formed once by the entry point in fp32.  j is a NEIGHBOUR of i iff d2(i, j) <= r2 (inclusive); i is its own.
+ *   count[i] = the number of neighbours of i.  i is a CORE point iff count[i] >= min_points.
+ *   Clusters are the connected components of the graph on the CORE POINTS ONLY, with an edge where two core points are neighbours; a
+ *   point that is not core never links two clusters.
+ *   label[i], i core     = the smallest original index among the core points of i's component.
+ *   label[i], i not core = label[b], b the core neighbour of i with the smallest key (d2(i, b), b), ordered lexicographically: the
+ *                          nearest core neighbour, the smaller index among equals; -1 (noise) when i has no core neighbour.
+ *   size[r]  = the number of points i, core or not, with label[i] == r; 0 at every index that is no label.
+ *   noise[0] = the number of points with label -1.
+ * count, label, size [N] and noise [1] (all int32) are written completely by every call; parent [N] (int32) is work space whose content
+ * afterwards is unspecified.  The only atomics are integer ones (compare-and-swap and min on parent, add on size and noise); all of
+ * them commute, so two calls give the same values.  A permutation of the points permutes the partition with it.  A record whose index
+ * lies outside 0..N-1 is skipped and never an address.  N == 0 launches nothing and writes nothing.
+ * ESTD_ERR_ARG (before any launch, no device needed): a null descriptor, N negative, min_points < 1, eps not finite or <= 0 or with a
+ * square that leaves fp32; with N > 0: null or misaligned records, null cell_start, a grid estd_cloud_nearest would refuse, a null
+ * count, parent, label, size or noise.  ESTD_ERR_UNSUPPORTED: N >= 2^31. */
+typedef struct estd_cloud_dbscan_desc {
+    long long N;                                  /* points */
+    const float* records;                         /* [N][4], sorted by key */
+    const int* cell_start;                        /* [dims[0] dims[1] dims[2] + 1] */
+    int* count;                                   /* [N] */
+    int* parent;                                  /* [N], work space */
+    int* label;                                   /* [N] */
+    int* size;                                    /* [N] */
+    int* noise;                                   /* [1] */
+    float lo[3];                                  /* host values, copied into the launch arguments */
+    float cell;
+    float eps;
+    int dims[3];
+    int min_points;
+} estd_cloud_dbscan_desc;
+int estd_cloud_dbscan(const estd_cloud_dbscan_desc* desc, estd_stream_t stream);
+
 /* ---- global registration: FPFH descriptors, feature matching, three-point hypotheses (csrc/register/global_register.hip; numpy form:
  * tests/global_reg_ref.py) ----
  * Every decision below is taken in float64 operations (or integers) written in a fixed order and NOT contracted: a * b + c is a rounded

@@ -49,6 +49,10 @@ ground-truth depth.  Needs an MI355X (the model has no CPU path).
         # + a ground truth that comes WITHOUT normals (a laser scan, a PLY with x y z only): normals are estimated from its own points --
         # a plane fit over the 16 nearest neighbours within the threshold (cloud_metrics.estimate_normals, csrc/cloud/cloud_knn.hip) -- so
         # that normal_consistency and the plane metric are there; recon_3d gains normals: k, radius, estimated, invalid_pred, invalid_gt
+    python tools/run_stream.py --synthetic 8 --out /tmp/eval --fuse /tmp/eval/scene.ply --score-3d --cloud-min-cluster 200
+        # + the fused cloud without its floaters: the points are clustered by density (cloud_metrics.filter_clusters: DBSCAN with
+        # --cloud-cluster-eps, default two voxel edges, and --cloud-cluster-min-points, default 6); the noise and every cluster of fewer than
+        # 200 points are dropped before scene.ply is written and scored; a "cloud_clusters" block in metrics.json
     python tools/run_stream.py --synthetic 8 --out /tmp/eval --fuse /tmp/eval/scene.ply --track
         # + frame-to-model tracking (estdepth_amd.tracking): from the second fused target on, every target's pose is refined against the
         # volume (TSDFVolume.track: point-to-plane alignment of its depth map with the ray-cast model) before the target is fused -- the
@@ -145,6 +149,13 @@ def parse(argv=None):
     ap.add_argument("--no-feature-cache", action="store_true")
     ap.add_argument("--fuse", metavar="PATH.ply", help="fuse every target's depth / fused_prob into a TSDF volume on the device "
                                                        "(estdepth_amd.fusion3d) and write its surface points here")
+    ap.add_argument("--cloud-min-cluster", type=int, metavar="N", help="with --fuse: cluster the fused points by density (DBSCAN; "
+                    "cloud_metrics.filter_clusters) and drop the noise and every cluster of fewer than N points before the cloud is written and "
+                    "scored; metrics.json gains a cloud_clusters block")
+    ap.add_argument("--cloud-cluster-eps", type=float, default=None, metavar="E", help="with --cloud-min-cluster: the neighbourhood radius in metres "
+                    "(default: two voxel edges, which links the 26-neighbourhood of the extraction's one-point-per-voxel cloud; a default, not a tuned value)")
+    ap.add_argument("--cloud-cluster-min-points", type=int, default=None, metavar="K", help="with --cloud-min-cluster: a point with K neighbours within E "
+                    "(itself among them) is a core point (default: 6 of the roughly 12 a surface holds in that radius; a default, not a tuned value)")
     ap.add_argument("--mesh", metavar="MESH.ply", help="with --fuse: also write the fused surface as a triangle mesh (TSDFVolume.save_mesh; "
                     "with --color the vertices get red / green / blue) and report its size and edge statistics")
     ap.add_argument("--mesh-min-component", type=int, metavar="N", help="with --mesh: drop the connected components of fewer than N triangles "
@@ -214,6 +225,18 @@ def parse(argv=None):
         ap.error("--render-fused needs --fuse PATH.ply")
     if args.mesh and not args.fuse:
         ap.error("--mesh needs --fuse PATH.ply")
+    if args.cloud_min_cluster is not None and not args.fuse:
+        ap.error("--cloud-min-cluster needs --fuse PATH.ply")
+    if args.cloud_min_cluster is not None and args.cloud_min_cluster < 1:
+        ap.error("--cloud-min-cluster must be at least 1")
+    if args.cloud_min_cluster is None and (args.cloud_cluster_eps is not None or args.cloud_cluster_min_points is not None):
+        ap.error("--cloud-cluster-eps and --cloud-cluster-min-points need --cloud-min-cluster N")
+    if args.cloud_cluster_eps is not None and not 0 < args.cloud_cluster_eps < float("inf"):
+        ap.error("--cloud-cluster-eps must be a positive radius in metres")
+    if args.cloud_cluster_min_points is not None and args.cloud_cluster_min_points < 1:
+        ap.error("--cloud-cluster-min-points must be at least 1")
+    if args.cloud_min_cluster is not None and args.score_exact:
+        ap.error("--cloud-min-cluster is not available with --score-exact (the surfaces themselves are scored there: --mesh-min-component cleans a mesh)")
     if args.mesh_min_component is not None and not args.mesh:
         ap.error("--mesh-min-component needs --mesh MESH.ply")
     if args.mesh_min_component is not None and args.mesh_min_component < 1:
@@ -443,10 +466,17 @@ def run(args):
               "predictions_resized_to_gt_grid": resized}
     if geo is not None:
         report.update(consistency=geo.summary(), errors_filtered=errs_filtered.mean(), filtered_coverage=geo_count["kept"] / max(geo_count["gt"], 1))
+    clusters = None
+    if volume is not None and args.cloud_min_cluster is not None:                # the floaters leave before the cloud is written and scored
+        clusters = dict(eps=args.cloud_cluster_eps if args.cloud_cluster_eps is not None else 2.0 * args.voxel_size,
+                        min_points=args.cloud_cluster_min_points if args.cloud_cluster_min_points is not None else 6, min_size=args.cloud_min_cluster)
     if volume is not None:
         os.makedirs(os.path.dirname(os.path.abspath(args.fuse)), exist_ok=True)
-        report.update(fused_voxels=volume.fused_voxels(), points=volume.save_ply(args.fuse),
+        found = {}
+        report.update(fused_voxels=volume.fused_voxels(), points=volume.save_ply(args.fuse, clusters=clusters, stats=found),
                       mean_fuse_ms=float(np.mean(fuse_ms[1:] or fuse_ms)))
+        if clusters is not None:
+            report["cloud_clusters"] = dict(found, eps=clusters["eps"], min_points=clusters["min_points"], min_size=clusters["min_size"])
     if volume is not None and args.mesh:
         from estdepth_amd.fusion3d import mesh_edge_stats
         os.makedirs(os.path.dirname(os.path.abspath(args.mesh)), exist_ok=True)
@@ -481,6 +511,8 @@ def run(args):
                 align["align"].update(init="global", voxel=1.5 * args.score_threshold if args.score_align_global == -1.0 else args.score_align_global)
         if args.score_normals is not None:
             align["normals"] = dict(k=args.score_normals, radius=args.score_normals_radius)
+        if clusters is not None:
+            align["clusters"] = dict(clusters, sides=("pred",))
         torch.cuda.synchronize()
         t0 = time.time()
         if args.score_sample is None:

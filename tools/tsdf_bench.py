@@ -81,7 +81,15 @@ per query, beside the same result with torch operators (cdist + topk, gathers, b
 times the four kernels of the global registration (csrc/register/global_register.hip) and the whole register_global on that volume's
 cloud against itself moved and on the 200 704-point height field thinned to 2 cm and to 5 cm, the matcher beside torch.cdist + argmin on
 the same descriptors and the hypothesis scoring beside the same sums with torch operators.  --parent-tree DIR adds compare_clouds and
-register with default arguments in both trees, in alternating pairs of fresh processes."""
+register with default arguments in both trees, in alternating pairs of fresh processes.
+
+    python tools/tsdf_bench.py --cloud-cluster [--reps 30] [--parent-tree DIR] [--out profiles/cloud_cluster_bench.txt]
+
+times the density-based clustering (csrc/cloud/cloud_cluster.hip) on that volume's cloud and on the 200 704-point height field at eps of 2
+and 4 point spacings: the four kernels apart (the profiler's device times), the entry point and the whole cloud_metrics.cluster_dbscan --
+medians of warm calls -- beside the same partition from torch operators (cdist, masks, argmin) and scipy's connected_components on the
+first 16 384 points.  --parent-tree DIR adds compare_clouds with default arguments and mesh_components in both trees, in alternating pairs
+of fresh processes."""
 import argparse
 import os
 import sys
@@ -136,6 +144,9 @@ def main():
     ap.add_argument("--global-register", action="store_true", help="time the global registration (csrc/register/global_register.hip): its four "
                     "kernels, the whole register_global, the matcher beside torch.cdist + argmin and the hypothesis scoring beside torch operators; "
                     "writes profiles/global_register_bench.txt unless --out says otherwise")
+    ap.add_argument("--cloud-cluster", action="store_true", help="time the density-based clustering (csrc/cloud/cloud_cluster.hip): its four kernels, "
+                    "the entry point, the whole cluster_dbscan and the same partition with torch operators and scipy; writes "
+                    "profiles/cloud_cluster_bench.txt unless --out says otherwise")
     ap.add_argument("--parent-tree", metavar="DIR", help="with --mesh-simplify: a built checkout of the parent commit; the default extract_mesh of both "
                     "trees is timed in alternating pairs of fresh processes (with --cloud-knn: the default compare_clouds; with --global-register: "
                     "the default compare_clouds and register)")
@@ -153,6 +164,9 @@ def main():
     if args.global_register:
         args.out = args.out or os.path.join(ROOT, "profiles", "global_register_bench.txt")
         return global_register_main(args)
+    if args.cloud_cluster:
+        args.out = args.out or os.path.join(ROOT, "profiles", "cloud_cluster_bench.txt")
+        return cluster_main(args)
     if args.raycast:
         return raycast_main(args)
     if args.mesh:
@@ -875,6 +889,140 @@ def knn_main(args):
         pa, pb = float(np.median([a for a, _ in pairs])), float(np.median([b for _, b in pairs]))
         spread = max(max(a for a, _ in pairs) - min(a for a, _ in pairs), max(b for _, b in pairs) - min(b for _, b in pairs))
         lines.append("  medians: parent %.4f ms, this tree %.4f ms (difference %+.4f ms; the pairs spread over %.4f ms)" % (pa, pb, pb - pa, spread))
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        open(args.out, "w").write(text + "\n")
+
+
+COMPONENTS_SNIPPET = """
+import numpy as np, torch
+from estdepth_amd.fusion3d import mesh_components
+n = 321
+idx = np.arange(n * n).reshape(n, n)
+a, b, c, d = idx[:-1, :-1].ravel(), idx[:-1, 1:].ravel(), idx[1:, :-1].ravel(), idx[1:, 1:].ravel()
+faces = torch.from_numpy(np.concatenate([np.stack([a, b, c], 1), np.stack([b, d, c], 1)]).astype(np.int32)).cuda()
+ts = []
+for i in range(%d + 3):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(); mesh_components(faces, n * n); e1.record(); torch.cuda.synchronize()
+    ts.append(e0.elapsed_time(e1))
+print("COMPARE_MS", float(np.median(ts[3:])))
+"""
+
+
+def cluster_main(args):
+    """--cloud-cluster: the four kernels of csrc/cloud/cloud_cluster.hip apart (the profiler's device time of every launch of the entry
+    point, through the C ABI on a prepared grid), the entry point and the whole cloud_metrics.cluster_dbscan, at eps of 2 and 4 point
+    spacings with min_points = 6, on the cloud extracted from the 256^3 bench volume and on a 200 704-point height field; the yardstick is
+    the same partition by torch operators (cdist, masks, argmin) and scipy.sparse.csgraph.connected_components on the first 16 384
+    points, where the distance matrix fits; medians of warm calls."""
+    import ctypes
+    import re
+    import time
+    import tsdf_ref as R
+    from estdepth_amd import _native, cloud_metrics
+    from estdepth_amd.fusion3d import TSDFVolume, frustum_volume
+    assert torch.cuda.is_available(), "tools/tsdf_bench.py needs a ROCm device"
+    dev = torch.device("cuda:0")
+    H, W, T, vox, dmin, dmax, dims = 480, 640, 3, 0.03, 0.1, 10.0, (256, 256, 256)
+    reps, min_points = min(args.reps, 30), 6
+    K = R.intrinsics(H, W)
+    poses = R.scene_poses(T, seed=1)
+    depths = torch.from_numpy(np.stack([R.raycast_scene(P, K, H, W) for P in poses]).astype(np.float32)).to(dev)
+    origin = frustum_volume(torch.from_numpy(poses[0]), torch.from_numpy(K), (H, W), dmin, dmax, dims, vox)
+    vol = TSDFVolume(dims, vox, origin, device=dev)
+    vol.integrate(depths, torch.from_numpy(poses), torch.from_numpy(K))
+    cloud_a = vol.extract_points()["xyz"].contiguous()
+    u = np.linspace(0.0, 4.0, 448)
+    gx, gy = np.meshgrid(u, u, indexing="xy")
+    cloud_b = torch.from_numpy(np.stack([gx, gy, 0.2 * np.sin(1.7 * gx) * np.cos(1.3 * gy)], -1).reshape(-1, 3).astype(np.float32)).to(dev)
+    lib = _native.lib()
+    stream = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    kernels = ("dbscan_count_kernel", "dbscan_hook_kernel", "dbscan_flatten_kernel", "dbscan_border_kernel")
+    lines = ["tsdf_bench --cloud-cluster: median of %d warm calls per figure, %s; min_points = %d" % (reps, torch.cuda.get_device_name(0), min_points),
+             "nobody has measured these before: the parent commit has nothing comparable, so the times are recorded, not gated"]
+    for name, pts, spacing in (("the cloud of the %d x %d x %d volume (voxel %.2f m)" % (dims + (vox,)), cloud_a, vox),
+                               ("the 448 x 448 height field over a 4 m square", cloud_b, 4.0 / 447.0)):
+        n = int(pts.shape[0])
+        lines.append("%s: %d points, point spacing %.5f m" % (name, n, spacing))
+        for mult in (2, 4):
+            eps = mult * spacing
+            grid = cloud_metrics.PointGrid(pts, eps, eps)
+            count, parent, label, size = (torch.empty(n, device=dev, dtype=torch.int32) for _ in range(4))
+            noise = torch.empty(1, device=dev, dtype=torch.int32)
+            d = _native.CloudDbscanDesc()
+            d.N, d.min_points = n, min_points
+            d.records, d.cell_start = grid.records.data_ptr(), grid.cell_start.data_ptr()
+            d.count, d.parent, d.label, d.size, d.noise = count.data_ptr(), parent.data_ptr(), label.data_ptr(), size.data_ptr(), noise.data_ptr()
+            d.cell, d.eps = grid.cell, eps
+            d.lo[:], d.dims[:] = grid.lo.tolist(), grid.dims
+
+            def call():
+                assert lib.estd_cloud_dbscan(ctypes.byref(d), stream()) == 0
+            call()
+            whole = lambda: cloud_metrics.cluster_dbscan(pts, eps, min_points)
+            out = whole()
+            assert torch.equal(out["label"], label) and torch.equal(out["count"], count), "the prepared grid is not cluster_dbscan's"
+            t_call, t_all = median_ms(call, reps), median_ms(whole, reps)
+            with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CUDA]) as prof:
+                for _ in range(reps):
+                    call()
+                torch.cuda.synchronize()
+            per = {k: [] for k in kernels}
+            for e in prof.events():
+                m = re.search(r"dbscan_\w+_kernel", e.name)
+                if m and m.group(0) in per:
+                    per[m.group(0)].append(float(getattr(e, "device_time_total", 0.0) or getattr(e, "cuda_time_total", 0.0)) / 1e3)
+            t_k = "   ".join("%s %8.4f ms" % (k, float(np.median(per[k])) if per[k] else float("nan")) for k in kernels)
+            lines.append("  eps = %d spacings = %.5f m, cell %.5f m, %d x %d x %d cells: %.1f neighbours per point, %d core, %d clusters, %d noise"
+                         % ((mult, eps, grid.cell) + tuple(grid.dims) + (float(count.double().mean()), int(out["core"].sum()), out["n_clusters"], out["noise"])))
+            lines.append("    %s" % t_k)
+            lines.append("    estd_cloud_dbscan, the four launches %8.4f ms (%.1f M points/s)   cluster_dbscan, whole call (finite check, grid build, one sort, "
+                         "the kernels, dense ids, one read-back) %8.4f ms" % (t_call, n / t_call / 1e3, t_all))
+        # the yardstick on a subset: the distance matrix of 16 384 points is 1 GiB in fp32
+        from scipy.sparse import coo_matrix
+        from scipy.sparse.csgraph import connected_components
+        m, eps = min(n, 16384), 2 * spacing
+        sub = pts[:m].contiguous()
+
+        def yard():
+            dist = torch.cdist(sub, sub)
+            nb = dist <= eps
+            core = nb.sum(1) >= min_points
+            ij = (nb & core[:, None] & core[None, :]).nonzero().cpu().numpy()
+            n_comp, lab = connected_components(coo_matrix((np.ones(ij.shape[0], np.int8), (ij[:, 0], ij[:, 1])), shape=(m, m)), directed=False)
+            near = torch.where(nb & core[None, :], dist, torch.full((), float("inf"), device=dev)).min(1)
+            return core, lab, near
+        core, lab, near = yard()
+        sub_out = cloud_metrics.cluster_dbscan(sub, eps, min_points)
+        n_yard = int(np.unique(lab[core.cpu().numpy()]).shape[0])
+
+        def wall(fn, k):
+            ts = []
+            for _ in range(k):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                ts.append(1e3 * (time.perf_counter() - t0))
+            return float(np.median(ts))
+        t_y, t_c = wall(yard, max(reps // 6, 3)), wall(lambda: cloud_metrics.cluster_dbscan(sub, eps, min_points), reps)
+        lines.append("  yardstick on the first %d points, eps = 2 spacings: cdist, masks, scipy connected_components, argmin %9.3f ms wall;  cluster_dbscan on "
+                     "the same points %8.3f ms wall (1 / %.1f); %d clusters against %d, core points agree on %.2f %%"
+                     % (m, t_y, t_c, t_y / t_c, n_yard, sub_out["n_clusters"], 100.0 * float((core == sub_out["core"]).double().mean())))
+    lines.append("  not built and not measured: a core flag in record order (count[index] is gathered instead), a cell edge of eps / 2, an early test of "
+                 "equal roots before unite, a cell-level union for cells whose diagonal is below eps")
+    if args.parent_tree:
+        for what, snippet in (("compare_clouds(threshold=0.05, downsample=0.02) on two 200 000-point clouds", COMPARE_SNIPPET),
+                              ("mesh_components on the 204 800-triangle height field", COMPONENTS_SNIPPET)):
+            pairs = compare_pairs(os.path.abspath(args.parent_tree), reps, snippet=snippet)
+            lines.append("the default path: %s, median of %d calls per process, parent commit / this tree in alternating fresh processes:" % (what, reps))
+            lines += ["  pair %d: parent %8.4f ms   this tree %8.4f ms" % (i, a, b) for i, (a, b) in enumerate(pairs)]
+            pa, pb = float(np.median([a for a, _ in pairs])), float(np.median([b for _, b in pairs]))
+            spread = max(max(a for a, _ in pairs) - min(a for a, _ in pairs), max(b for _, b in pairs) - min(b for _, b in pairs))
+            lines.append("  medians: parent %.4f ms, this tree %.4f ms (difference %+.4f ms; the pairs spread over %.4f ms)" % (pa, pb, pb - pa, spread))
     text = "\n".join(lines)
     print(text)
     if args.out:
